@@ -17,16 +17,22 @@ the per-GPU scan work per step is fixed), per-rank top-k are merged with one
 all-gather inside the library.  `--workload c3 / c5 --gpus 8` are BASELINE
 configs[2] / configs[4] at full size (10 M rows).
 
-How the line is produced (round 3's driver run lost most of it behind one hung section): the process the driver
-starts does the MANDATORY part itself, in this order -- build, recall against float64, the timed steps, oracle parity +
-cpu_baseline -- and from there on the line exists.  Every other section runs in a CHILD of this script
+A plain run does only what the headline figure needs: data + build, warmup (settle steps included), the K timed steps,
+`--dump-outputs DIR` (the last timed step's answers as DIR/<name>.npy) and the line.  Everything else described below --
+recall, the un-settled and overlapped passes, parity, cpu_baseline and every optional section -- runs with `--full`.
+
+How the line is produced with `--full` (round 3's driver run lost most of it behind one hung section): the process the
+driver starts does the MANDATORY part itself, in this order -- build, recall against float64, the timed steps, oracle
+parity + cpu_baseline -- and from there on the line exists.  Every other section runs in a CHILD of this script
 (`--section NAME`), one at a time, each in its own session with its own budget (killed as a process group when it is
 not back), writing what it has measured to a file after every step: configs (other_configs + exact_scan), hnsw,
 build (pages + CPU build baseline), the PMC traffic passes, sweeps, and the sections that start backends LAST.  A
 failed section is a `failures` entry and exit code 2 -- with the whole line printed; one that only ran out of its budget (a slow
 box) is a `failures` entry with the prefix "budget:" and leaves the exit code alone.
 
-What the line carries besides the contract's fields (rank 0, N = 1):
+A plain line carries, besides the contract's fields: config, roofline (without `traffic`: null), build_secs,
+kmeans_iterations, center_rank_ms_per_step, scan_ms_per_step, overlap_lanes, bench_wall_secs (N > 1: multi_gpu).
+What --full adds (rank 0, N = 1):
   parity       the GPU's answers for `parity_checked_queries` queries compared with the CPU oracle's
                (tid, distance) for the SAME index and queries, tie-tolerant; a mismatch exits non-zero
   recall_at_10 against an exact float64 brute force over all rows (N > 1: every rank over the rows
@@ -451,7 +457,10 @@ def reference_baseline(centers, offsets, vectors, tids, queries, probes, k, dtyp
                str(procs), str(secs), str(secs_single), os.path.join(d, "answers.bin"),
                "f32" if dtype == api.PGV_F32 else "f16", "l2" if ops == api.PGV_OPS_L2 else "ip"]
         t0 = time.perf_counter()
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=secs + secs_single + 240)
+        # the libraries of this tree (oracle/_ref may have been built elsewhere: its run path follows the program's real location)
+        env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join([os.path.join(ROOT, "pgvector_amd", "lib"), os.path.join(ROOT, "oracle")] +
+                                                                [x for x in [os.environ.get("LD_LIBRARY_PATH")] if x]))
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=secs + secs_single + 240, env=env)
         t_run = time.perf_counter() - t0
         if r.returncode != 0:
             raise RuntimeError("ref_scan_bench exit code %d: %s" % (r.returncode, r.stderr[-300:]))
@@ -534,6 +543,9 @@ def cpu_build_assign(host_rows, dtype, ops, out):
         out["error"] = repr(e)
 
 
+MAX_OWN_CTX_BACKENDS = 14
+
+
 def concurrent_backends(index, device, qhost, queries, probes, k, args, dev, out, flush):
     """what a server looks like to the device: N backends against ONE uploaded index.  (a) backends as threads of a
     plain C driver, one query at a time each (pgv_query_rank + pgv_query_scan, the amgettuple path); the same as
@@ -559,11 +571,14 @@ def concurrent_backends(index, device, qhost, queries, probes, k, args, dev, out
     # the same with PROCESSES, which is what a Postgres backend is: every process imports the ONE device mirror
     # (pgv_index_export / pgv_index_import: hipIpc, no copy) and scans it on a context and stream of its own
     out["single_query_processes"] = {}
-    # (32 own-context processes -- 7-10 k QPS on these boxes, profiles/r03/processes_*.json, DESIGN 4.8b -- only with
-    # --all-process-rows: that row costs the most and teaches the least in a driver run)
-    proc_rows = (1, 4, 8, 16, 32) if args.all_process_rows else (1, 4, 8, 16)
+    # every backend here opens the device; with this script's parent and the section child that owns the mirror, at most
+    # MAX_OWN_CTX_BACKENDS of them keep the run at 16 processes on the device (earlier rounds' 16 / 32 rows:
+    # profiles/r03/processes_*.json)
+    proc_rows = (1, 4, 8, MAX_OWN_CTX_BACKENDS)
     if os.environ.get("PGV_BENCH_PROC_ROWS"):   # e.g. "5,6,7,8": where the own-context cliff sits (profiles/r06/own_context_cliff.md)
         proc_rows = tuple(int(x) for x in os.environ["PGV_BENCH_PROC_ROWS"].split(","))
+        if max(proc_rows) > MAX_OWN_CTX_BACKENDS:
+            raise ValueError("PGV_BENCH_PROC_ROWS %r: at most %d own-context backends" % (proc_rows, MAX_OWN_CTX_BACKENDS))
     for nb in proc_rows:
         log("  backends: %d processes" % nb)
         try:
@@ -594,7 +609,10 @@ def concurrent_backends(index, device, qhost, queries, probes, k, args, dev, out
     # ... and with GPU-less client PROCESSES in front of two lane-server processes: the pool's slots, lane words and
     # payload ring live in a shared segment (non-private futexes, a robust process-shared mutex)
     out["pooled_single_query_processes"] = {}
-    for nc in (16, 64, 256, 1024):
+    # (1024 clients only with --all-process-rows: with the 3 lane servers, the section child and this script the row runs
+    # about 1032 processes at once, over a limit of 1024 processes per job -- a run under such a limit was stopped in
+    # this row.  The clients hold no device; the GPU-process count of the row is 5)
+    for nc in (16, 64, 256, 1024) if args.all_process_rows else (16, 64, 256):
         log("  backends: %d pooled client processes" % nc)
         try:
             out["pooled_single_query_processes"][str(nc)] = _host.run_backend_processes(
@@ -1198,6 +1216,24 @@ def timed_steps(fn, steps, warmup=2):
     return (time.perf_counter() - t0) / steps
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """`--dump-outputs DIR`: every array (rows = queries of the batch) as DIR/<name>.npy; over DUMP_CAP_BYTES in all, the
+    same fixed, seeded sample of rows from each (sorted, so row order is kept) -- two builds compare output for output"""
+    os.makedirs(d, exist_ok=True)
+    rows = min(a.shape[0] for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    keep = None
+    if total > DUMP_CAP_BYTES:
+        keep = np.sort(np.random.default_rng(12345).choice(rows, max(1, rows * DUMP_CAP_BYTES // total), replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a if keep is None else a[keep]))
+    log("outputs of the last timed step: %s in %s%s" % (", ".join(sorted(arrays)), d,
+                                                         "" if keep is None else " (%d of %d rows, seeded sample)" % (len(keep), rows)))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The line the driver parses.  Round 4's line had grown to ~21 KB (sweeps, backends, notes) and the driver's record of it
 # came back `parsed: null`.  What goes to fd 1 now is ONE compact object, capped at LINE_CAP bytes: the contract fields,
@@ -1390,8 +1426,9 @@ def emit_line(fd, full):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # How the ONE JSON line is kept safe (round 3's driver run lost everything behind a section that hung):
-#   1. the parent process does only what the line cannot do without, in this order: build, recall, the timed steps,
-#      oracle parity + cpu_baseline.  From there on the line exists and is complete as far as the contract goes.
+#   1. the parent process does only what the line cannot do without, in this order: build, recall (--full), the timed
+#      steps, oracle parity + cpu_baseline (--full).  From there on the line exists and is complete as far as the contract
+#      goes.  Steps 2-4 below are --full's too (a plain run starts no child).
 #   2. everything else runs in CHILD processes of this same script (`--section NAME`), one after the other, each in a
 #      session of its own with a budget of its own; a child that is not back in time is killed with its whole process
 #      group and the next one starts.  A child writes what it has measured to a file after every step, so a cut
@@ -2202,7 +2239,8 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="skip the live rocprofv3 PMC passes")
     ap.add_argument("--sections", default=",".join(SECTION_ORDER),
                     help="optional sections to run, in this order (default: all of %s)" % ",".join(SECTION_ORDER))
-    ap.add_argument("--all-process-rows", action="store_true", help="also 32 own-context backend processes")
+    ap.add_argument("--all-process-rows", action="store_true", help="also the row of 1024 pooled client processes "
+                    "(over 1024 processes in all)")
     ap.add_argument("--budget-secs", type=int, default=420, help="no optional section STARTS once the run is this old")
     ap.add_argument("--watchdog-secs", type=int, default=720, help="last resort for the parent process: print the line as "
                     "far as it has got and exit 2 (0: no watchdog)")
@@ -2237,7 +2275,14 @@ def main():
                     "group (the first `import torch` on a fresh box takes 1-2 minutes)")
     ap.add_argument("--no-self-launch", action="store_true", help="--gpus N > 1 without WORLD_SIZE in the environment is an "
                     "error instead of starting the N ranks from here")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: recall against float64, "
+                    "the un-settled and the overlapped passes, oracle parity + cpu_baseline and the optional sections (off: "
+                    "set up, warm up, time the K steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the last timed step's "
+                    "answers (distances float32, tids float64) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     HARD.update(sigma=args.hard_sigma, alpha=args.hard_alpha, zipf=args.hard_zipf)
     PLACEMENT["policy"] = args.placement
     t_program = time.perf_counter()
@@ -2352,23 +2397,25 @@ def main():
         comm.search_batch(index, q, probes, k, out=(out_d, out_t))
         return out_d, out_t
 
-    # ---------------------------------------------------------------- recall vs exact fp64
-    WATCH["section"] = "recall against float64"
-    rq = min(args.recall_queries, total_batch)
-    rqueries = queries[1][:rq].contiguous()
-    # exact float64 brute force over every row; with N ranks each one scans the rows it holds and the per-rank
-    # exact top-k are merged (never the GPUs' own fp32 scan as its own ground truth)
-    exact_d, _ = exact_topk_fp64(vectors, rqueries, k, metric)
-    if not sharded:
-        got_d, got_s, got_t = index.search_batch(rqueries, probes, k, want_tid=True)
-        recall_truth = "exact float64 brute force over all %d rows, %d queries" % (n, rq)
-    else:
-        exact_d = sharding.merge_exact_topk(exact_d, k)
-        got_d, got_t = comm.search_batch(index, rqueries, probes, k)
-        recall_truth = "exact float64 brute force, every rank over the rows it holds, merged over %d ranks, %d queries" % (world, rq)
-    ctx.sync()
-    recall = recall_at_k(got_d, exact_d, k)
-    log("recall@%d = %.4f at probes=%d (%s)" % (k, recall, probes, recall_truth))
+    # ---------------------------------------------------------------- recall vs exact fp64 (--full)
+    recall = recall_truth = None
+    if args.full:
+        WATCH["section"] = "recall against float64"
+        rq = min(args.recall_queries, total_batch)
+        rqueries = queries[1][:rq].contiguous()
+        # exact float64 brute force over every row; with N ranks each one scans the rows it holds and the per-rank
+        # exact top-k are merged (never the GPUs' own fp32 scan as its own ground truth)
+        exact_d, _ = exact_topk_fp64(vectors, rqueries, k, metric)
+        if not sharded:
+            got_d, got_s, got_t = index.search_batch(rqueries, probes, k, want_tid=True)
+            recall_truth = "exact float64 brute force over all %d rows, %d queries" % (n, rq)
+        else:
+            exact_d = sharding.merge_exact_topk(exact_d, k)
+            got_d, got_t = comm.search_batch(index, rqueries, probes, k)
+            recall_truth = "exact float64 brute force, every rank over the rows it holds, merged over %d ranks, %d queries" % (world, rq)
+        ctx.sync()
+        recall = recall_at_k(got_d, exact_d, k)
+        log("recall@%d = %.4f at probes=%d (%s)" % (k, recall, probes, recall_truth))
 
     # ----------------------------------------------------------------- timed
     WATCH["section"] = "timed steps"
@@ -2377,7 +2424,8 @@ def main():
         # ranking / planning / top-k / recheck run under the other's list scan; every batch is complete inside the timed
         # region (the synchronize below waits for all streams)
         index.set_overlap(args.overlap)
-    # the K steps once BEFORE any settling (the un-settled number beside `value`)
+    # the K steps once BEFORE any settling (the un-settled number beside `value`, reported with --full; a plain
+    # run takes them as warmup, so that the device has done the same work as in a --full run when the settling starts)
     for i in range(args.warmup):
         step(i)
     if world > 1:
@@ -2387,7 +2435,7 @@ def main():
     for i in range(args.steps):
         step(args.warmup + i)
     torch.cuda.synchronize()
-    unsettled_qps = total_batch * args.steps / (time.perf_counter() - t_u)   # (this rank's clock: detail only)
+    unsettled_qps = total_batch * args.steps / (time.perf_counter() - t_u) if args.full else None   # (this rank's clock)
     settle_steps = 0
     if args.settle_ms > 0:
         # (every rank runs the same number: the sharded step has collectives in it)
@@ -2421,8 +2469,12 @@ def main():
     ctx.set_profiling(False)
     if not sharded and args.overlap > 1:
         index.set_overlap(1)     # everything below reads its answers in stream order again
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (step(warmup + steps - 1)), before anything below reuses the buffers
+        dump_outputs(args.dump_outputs, {"distances": out_d.float().cpu().numpy(),
+                                         "tids": out_t.cpu().numpy().astype(np.float64)})
     overlapped = None
-    if not sharded and args.overlap == 1 and args.overlap_lanes > 1 and not args.child:
+    if args.full and not sharded and args.overlap == 1 and args.overlap_lanes > 1 and not args.child:
         # the same K steps once more with one caller's consecutive batches on `overlap_lanes` internal streams
         # (pgv_index_set_overlap: list scans take turns, everything else of a batch runs under another batch's scan).
         # Not `value`: the scan launches of the timed region above are timed without company, these are not.
@@ -2502,8 +2554,6 @@ def main():
                    "batch_per_gpu": args.batch, "settle_steps": settle_steps, "parallelism": "lists sharded over %d ranks (%s by rows); k-means all-reduce, probe-list and "
                                   "top-k all-gathers inside libpgv_hip (RCCL on the library's stream)" % (world, args.placement),
                    "local_rows": H.local_rows},
-        "value_unsettled": unsettled_qps,
-        "recall_at_10": recall, "recall_ground_truth": recall_truth,
         "build_secs": build_t["total"], "build_phases_secs": build_t, "kmeans_iterations": iters,
         "build_assign": {"rows": build_stats["assign_rows"],
                          "rechecked_fraction": build_stats["assign_recheck_rows"] / build_stats["assign_rows"]
@@ -2519,6 +2569,12 @@ def main():
         "scan_path": "exact vector-ALU kernels (--exact-scan)" if args.exact_scan else "auto",
         "overlap_lanes": args.overlap if not sharded else 1,
     }
+    if unsettled_qps is not None:
+        line["value_unsettled"] = unsettled_qps
+    if recall is not None:
+        line["recall_at_10"], line["recall_ground_truth"] = recall, recall_truth
+    if args.dump_outputs:
+        line["outputs"] = args.dump_outputs
     if overlapped:
         line["overlapped_batches"] = overlapped
     if sharded:
@@ -2560,8 +2616,8 @@ def main():
                                 "h2d_bytes_per_step": int(args.batch * dim * esize),
                                 "d2h_bytes_per_step": int(args.batch * k * 20)}
 
-    # --------------------------------------------------- parity with the CPU oracle + its speed (mandatory, in-process)
-    if single and not args.no_cpu_baseline:
+    # --------------------------------------------------- parity with the CPU oracle + its speed (--full, in-process)
+    if single and args.full and not args.no_cpu_baseline:
         WATCH["section"] = "oracle parity + cpu_baseline"
         try:
             pq = min(256, total_batch)
@@ -2621,8 +2677,8 @@ def main():
             failures.append("oracle parity / cpu_baseline did not run: %r" % (e,))
     line["mandatory_secs"] = time.perf_counter() - t_program
 
-    # ------------------------------------------------------------- optional sections: children, one at a time
-    if single and not (args.no_sweeps and args.no_traffic):
+    # ------------------------------------------------------------- optional sections (--full): children, one at a time
+    if single and args.full and not (args.no_sweeps and args.no_traffic):
         wanted = [s for s in args.sections.split(",") if s]
         for name in SECTION_ORDER:
             if name not in wanted:

@@ -44,8 +44,12 @@ def test_the_references_own_gettuple_functions_drive_the_hooks_on_the_gpu():
     through the hook lines inside them (the CPU-side equalities with the oracle are tests/test_ext_runtime_cpu.py's)."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    r = subprocess.run([REF_DRIVER], capture_output=True, text=True, timeout=900, env=env)
+    # the libraries of THIS tree: oracle/_ref may have been built elsewhere and brought here, and its run path resolves
+    # against the program's real location, not against the tree it sits in
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env["LD_LIBRARY_PATH"] = os.pathsep.join([os.path.join(root, "pgvector_amd", "lib"), os.path.join(root, "oracle")] +
+                                             [x for x in [env.get("LD_LIBRARY_PATH")] if x])
+    r = subprocess.run([REF_DRIVER], capture_output=True, text=True, timeout=900, env=env)
     if os.path.isdir(os.path.join(root, "gpurun_out")):
         with open(os.path.join(root, "gpurun_out", "ext_driver_ref_gpu.log"), "w") as f:
             f.write(r.stdout + "\n---- stderr ----\n" + r.stderr)

@@ -102,7 +102,7 @@ def test_bench_n_gpu_code_path_with_one_rccl_rank(tmp_path):
     for k_ in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k_, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--sharded-path", "--workload", "small", "--steps", "3",
-                        "--warmup", "1", "--settle-ms", "0"], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+                        "--warmup", "1", "--settle-ms", "0", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["recall_at_10"] >= 0.99 and line["value"] > 0

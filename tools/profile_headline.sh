@@ -14,7 +14,7 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 export PYTHONPATH=$root
-python bench.py > "$out/bench.json" 2> "$out/bench.err"
+python bench.py --full > "$out/bench.json" 2> "$out/bench.err"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d "$out/trace" -o trace --output-format csv -- \
     python "$root/bench.py" --no-cpu-baseline --no-sweeps --no-traffic > "$out/trace_bench.json" 2> "$out/trace.err"
