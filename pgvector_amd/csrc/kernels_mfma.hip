@@ -43,6 +43,7 @@
 // not notice) or one fp16 MFMA.
 #include "pgv_device.h"
 
+#include <algorithm>
 #include <cfloat>
 
 namespace pgv {
@@ -923,11 +924,15 @@ constexpr int kScanWaves = 4;      // one 32 x 32 tile each: a task is 128 rows
 // round trip, ~1 us) behind the others' streaming, so the 32-query form keeps TWO fills in flight (slice sl + 2 is issued
 // while slice sl is multiplied, the wait is vmcnt(5): this wavefront's five DMA instructions of the younger fill may
 // still be out).  60 KB of LDS: two workgroups per CU, which such a launch does not have anyway.
-template <typename T, int METRIC, int NW, bool NT, int NQ, int NS = 2>
+// SH: the fp16 residual shadow of an fp32 L2 index (kernels_shadow.hip): rows are shadow rows, queries the cast queries,
+// and the value is |x|^2 + t - 2^(1 + s + s_q) acc with the pair's t (ScanPair::pad) and the query's factor (qscale)
+template <typename T, int METRIC, int NW, bool NT, int NQ, int NS = 2, bool SH = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3 ? 2 : 3, NS == 3 ? 2 : 3))) void mfma_scan_kernel(
     const char *__restrict__ rows, const char *__restrict__ queries, const ScanTask *__restrict__ tasks,
     const int *__restrict__ ntasks_ptr, int *__restrict__ task_counter, const ScanPair *__restrict__ pairs,
-    const float *__restrict__ row_norms, int nvec, const char *__restrict__ zeros16, float *__restrict__ out) {
+    const float *__restrict__ row_norms, int nvec, const char *__restrict__ zeros16, float *__restrict__ out,
+    const float *__restrict__ qscale) {
+    static_assert(!SH || (METRIC == 0 && sizeof(T) == 2), "the shadow scan: fp16 rows, L2");
     constexpr int ROWS = 32 * NW;
     constexpr int NGROUPS = (NQ + ROWS) / 8;          // DMA instructions per stage (8 rows each)
     constexpr int NDMA = (NGROUPS + NW - 1) / NW;               // ... per wavefront, at most
@@ -935,7 +940,24 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
     static_assert(NS == 2 || (NS == 3 && NQ == 32 && NGROUPS % NW == 0), "three stages: the 32-query form only");
     __shared__ __attribute__((aligned(16))) char smem[NS * STAGE];
     __shared__ int64_t pair_rel[NQ];
+    __shared__ float2 pair_ts[SH ? NQ : 1];  // SH: the pair's t and its query's factor
     __shared__ int lds_task;
+    // the output value of an accumulated dot product (SH: finished in place by shadow_values, before the stores)
+    auto value = [&](float acc, float rn) -> float {
+        if constexpr (SH)
+            return acc;
+        else
+            return METRIC == 0 ? fmaf(-2.f, acc, rn) : -acc;
+    };
+    // |x|^2 + t - 2^(1 + s + s_q) acc, slot by slot: one value live at a time (hoisting the 2 x 16 operands of a whole
+    // tile spills at three waves per SIMD)
+    auto shadow_values = [&](auto &acc, int n, float rn, auto slot) {
+#pragma unroll
+        for (int r = 0; r < n; r++) {
+            const float2 ts = pair_ts[slot(r)];
+            acc[r] = fmaf(-ts.y, acc[r], rn + ts.x);
+        }
+    };
 
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -970,6 +992,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
             // slots past the task's last query repeat that query
             const ScanPair pr = pairs[task.pair0 + ((int)threadIdx.x < np ? (int)threadIdx.x : np - 1)];
             pair_rel[threadIdx.x] = pr.out_rel + task.row0;
+            if constexpr (SH) {
+                pair_ts[threadIdx.x] = make_float2(__int_as_float(pr.pad), qscale[pr.query]);
+            }
         }
         const char *src[NDMA];
 #pragma unroll
@@ -1078,12 +1103,16 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
             const int j32w = wave * 32 + l31;
             if (j32w < task.nrows) {
                 const float rn = METRIC == 0 ? row_norms[task.row0 + j32w] : 0.f;
+                if constexpr (SH) {
+                    shadow_values(suml, 16, rn, [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * half; });
+                    if (upper) shadow_values(sumu, 16, rn, [&](int r) { return 32 + (r & 3) + 8 * (r >> 2) + 4 * half; });
+                }
                 {
                     int64_t rel[16];
 #pragma unroll
                     for (int r = 0; r < 16; r++) rel[r] = pair_rel[(r & 3) + 8 * (r >> 2) + 4 * half];
 #pragma unroll
-                    for (int r = 0; r < 16; r++) out[rel[r] + j32w] = METRIC == 0 ? fmaf(-2.f, suml[r], rn) : -suml[r];
+                    for (int r = 0; r < 16; r++) out[rel[r] + j32w] = value(suml[r], rn);
                 }
                 if (upper) {
                     // (slots past the task's last query repeat that query: same value, same address)
@@ -1091,7 +1120,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
 #pragma unroll
                     for (int r = 0; r < 16; r++) rel[r] = pair_rel[32 + (r & 3) + 8 * (r >> 2) + 4 * half];
 #pragma unroll
-                    for (int r = 0; r < 16; r++) out[rel[r] + j32w] = METRIC == 0 ? fmaf(-2.f, sumu[r], rn) : -sumu[r];
+                    for (int r = 0; r < 16; r++) out[rel[r] + j32w] = value(sumu[r], rn);
                 }
             }
           }
@@ -1163,7 +1192,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
                     }
                 }
             }
-            const f32x16 acc = (acc4[0] + acc4[1]) + (acc4[2] + acc4[3]);
+            f32x16 acc = (acc4[0] + acc4[1]) + (acc4[2] + acc4[3]);
+            if constexpr (SH)
+                shadow_values(acc, 16, j32 < task.nrows ? row_norms[task.row0 + j32] : 0.f,
+                              [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * half; });
             // lane: row j32 of the task; register r: query (r & 3) + 8 (r >> 2) + 4 half.  Slots past the
             // task's last query hold copies of that query (same operands, same value, same address): they
             // are stored too, so that the 16 stores are one straight run -- a branch per store makes hipcc
@@ -1175,7 +1207,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
                 const float rn = METRIC == 0 ? row_norms[task.row0 + j32] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; r++)
-                    out[rel[r] + j32] = METRIC == 0 ? fmaf(-2.f, acc[r], rn) : -acc[r];
+                    out[rel[r] + j32] = value(acc[r], rn);
             }
         }
         if (narrow) {
@@ -1212,7 +1244,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
                         Mma16x4<T>::run(c04, c14, a, b0, b1, c);
                 }
             }
-            const f32x4 c0 = (c04[0] + c04[1]) + (c04[2] + c04[3]), c1 = (c14[0] + c14[1]) + (c14[2] + c14[3]);
+            f32x4 c0 = (c04[0] + c04[1]) + (c04[2] + c04[3]), c1 = (c14[0] + c14[1]) + (c14[2] + c14[3]);
             // lane: rows wave * 32 + l15 (c0) and + 16 (c1); register r: query 4 kg + r
             int64_t rel[4];
 #pragma unroll
@@ -1220,13 +1252,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NS == 3
             const int ja = wave * 32 + l15, jb = ja + 16;
             const float rna = (METRIC == 0 && ja < task.nrows) ? row_norms[task.row0 + ja] : 0.f;
             const float rnb = (METRIC == 0 && jb < task.nrows) ? row_norms[task.row0 + jb] : 0.f;
+            if constexpr (SH) {
+                shadow_values(c0, 4, rna, [&](int r) { return 4 * kg + r; });
+                shadow_values(c1, 4, rnb, [&](int r) { return 4 * kg + r; });
+            }
             if (ja < task.nrows) {
 #pragma unroll
-                for (int r = 0; r < 4; r++) out[rel[r] + ja] = METRIC == 0 ? fmaf(-2.f, c0[r], rna) : -c0[r];
+                for (int r = 0; r < 4; r++) out[rel[r] + ja] = value(c0[r], rna);
             }
             if (jb < task.nrows) {
 #pragma unroll
-                for (int r = 0; r < 4; r++) out[rel[r] + jb] = METRIC == 0 ? fmaf(-2.f, c1[r], rnb) : -c1[r];
+                for (int r = 0; r < 4; r++) out[rel[r] + jb] = value(c1[r], rnb);
             }
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the pair table and the task id have been read ...
@@ -1281,6 +1317,14 @@ namespace pgv {
 
 int mfma_scan_rows_per_task() { return 32 * kScanWaves; }
 int mfma_scan_queries_per_task() { return kScanQueries; }
+// products per accumulator chain of an fp16 list scan, whichever form takes a task: 16 per slice (32-query form: one
+// 32x32x16 MFMA per chain and slice), 32 per two slices (16-wide form: chain c + 2 (slice parity)), 64 per slice of a
+// quarter (64-query form) -- the last is the largest
+int shadow_chain_length(const RowGeom &g16) {
+    const int nslices = (g16.nvec + 7) / 8;
+    const int a = 16 * nslices, b = 32 * ((nslices + 1) / 2), c = 64 * ((nslices + 3) / 4);
+    return std::max(a, std::max(b, c));
+}
 // ... or twice that, when the lists of a batch are probed by more than ~12 queries on average (the 64-query form)
 int mfma_scan_queries_per_task_wide() { return 2 * kScanQueries; }
 
@@ -1301,7 +1345,7 @@ int launch_row_norms(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void
 int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,
                      const void *queries, const ScanTask *tasks, const int *ntasks_dev, int ntasks_bound,
                      const ScanPair *pairs, const float *row_norms, const float *query_norms, float *out,
-                     bool stream_rows, int queries_per_task) {
+                     bool stream_rows, int queries_per_task, const float *shadow_scale) {
     if (ntasks_bound <= 0) return PGV_OK;
     if (queries_per_task != 32 && queries_per_task != 64) PGV_FAIL(PGV_ERR_ARG, "mfma scan: %d queries per task", queries_per_task);
     if (metric != PGV_L2SQ && metric != PGV_NEG_IP) PGV_FAIL(PGV_ERR_ARG, "mfma scan: L2 / inner product only");
@@ -1324,10 +1368,11 @@ int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const Row
         return e ? atoi(e) : -1;
     }();
     const bool deep = queries_per_task == 32 && deep_env != 0 && ntasks_bound <= 2 * ctx->num_cus;
-#define PGV_MSCAN_Q(T, M, NT, Q, S)                                                                                     \
-    hipLaunchKernelGGL((mfma_scan_kernel<T, M, kScanWaves, NT, Q, S>), dim3(grid), dim3(kScanWaves * 64), 0, ctx->stream, \
-                       static_cast<const char *>(rows), static_cast<const char *>(queries), tasks, ntasks_dev, counter, \
-                       pairs, row_norms, g.nvec, static_cast<const char *>(ctx->zeros.p), out)
+#define PGV_MSCAN_QS(T, M, NT, Q, S, SH)                                                                                  \
+    hipLaunchKernelGGL((mfma_scan_kernel<T, M, kScanWaves, NT, Q, S, SH>), dim3(grid), dim3(kScanWaves * 64), 0,          \
+                       ctx->stream, static_cast<const char *>(rows), static_cast<const char *>(queries), tasks, ntasks_dev, \
+                       counter, pairs, row_norms, g.nvec, static_cast<const char *>(ctx->zeros.p), out, shadow_scale)
+#define PGV_MSCAN_Q(T, M, NT, Q, S) PGV_MSCAN_QS(T, M, NT, Q, S, false)
 #define PGV_MSCAN_NT(T, M, NT)                   \
     do {                                         \
         if (queries_per_task == 64)              \
@@ -1344,7 +1389,24 @@ int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const Row
         else                         \
             PGV_MSCAN_NT(T, M, false); \
     } while (0)
-    if (dtype == PGV_F32) {
+    if (shadow_scale) {
+        // the fp16 residual shadow of an fp32 L2 index (rows / queries: shadow rows, cast queries)
+        if (metric != PGV_L2SQ || dtype != PGV_F16) PGV_FAIL(PGV_ERR_ARG, "mfma scan: the shadow form is fp16 L2 only");
+#define PGV_MSCAN_SH(NT)                                   \
+    do {                                                   \
+        if (queries_per_task == 64)                        \
+            PGV_MSCAN_QS(__half, 0, NT, 64, 2, true);       \
+        else if (deep)                                     \
+            PGV_MSCAN_QS(__half, 0, NT, 32, 3, true);       \
+        else                                               \
+            PGV_MSCAN_QS(__half, 0, NT, 32, 2, true);       \
+    } while (0)
+        if (stream_rows)
+            PGV_MSCAN_SH(true);
+        else
+            PGV_MSCAN_SH(false);
+#undef PGV_MSCAN_SH
+    } else if (dtype == PGV_F32) {
         if (metric == PGV_L2SQ)
             PGV_MSCAN(float, 0);
         else
@@ -1358,6 +1420,7 @@ int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const Row
 #undef PGV_MSCAN
 #undef PGV_MSCAN_NT
 #undef PGV_MSCAN_Q
+#undef PGV_MSCAN_QS
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -335,9 +335,9 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     const int64_t *__restrict__ list_off, const int32_t *__restrict__ probe_lists,
     const int64_t *__restrict__ probe_off, int probes,
     const int64_t *__restrict__ seg_start, int64_t fixed_len,
-    const unsigned *__restrict__ row_norm_max, ScanBound bound, int nq, float *__restrict__ out_dist,
-    int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid, int32_t *__restrict__ out_i32,
-    int32_t *__restrict__ flags) {
+    const unsigned *__restrict__ row_norm_max, ScanBound bound, const float *__restrict__ eps_add, int nq,
+    float *__restrict__ out_dist, int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid,
+    int32_t *__restrict__ out_i32, int32_t *__restrict__ flags) {
     __shared__ float exact[kRecheckCap];
     __shared__ __attribute__((aligned(16))) unsigned long long ent[kRecheckCap];
     const int q = blockIdx.x;
@@ -368,7 +368,9 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     // (pgv_internal.h, ScanBound; the norms computed here and there carry a relative error of a few u themselves:
     // one part in a thousand on top covers it)
     const float cross = 2.f * sqrtf(qn * rn);
-    const float eps = 1.001f * (bound.g_sq * (qn + rn + cross) + bound.g_dot * cross + bound.g_norm * rn);
+    // (eps_add: the per-query term of the shadow scan, ScanBound)
+    const float eps = 1.001f * (bound.g_sq * (qn + rn + cross) + bound.g_dot * cross + bound.g_norm * rn +
+                                (eps_add ? eps_add[q] : 0.f));
     // NaN / inf anywhere: everything is in the band
     unsigned band = 0u;
     if (kk > 0) {
@@ -462,7 +464,7 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
     int lg, const char *__restrict__ queries, const int32_t *__restrict__ probe_lists,
     const int64_t *__restrict__ probe_off, int probes, const int64_t *__restrict__ seg_start, int64_t fixed_len,
     const int32_t *__restrict__ flags, int nq, float *__restrict__ seg_vals, int k, int kp, int cap,
-    const unsigned *__restrict__ row_norm_max, ScanBound bound, int widen,
+    const unsigned *__restrict__ row_norm_max, ScanBound bound, const float *__restrict__ eps_add, int widen,
     float *__restrict__ out_dist, int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid,
     int32_t *__restrict__ out_i32, double *__restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -513,7 +515,8 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
             for (int w = 0; w < kQWaves; w++) qn += qn_part[w];
             const float rn = __uint_as_float(*row_norm_max);
             const float cross = 2.f * sqrtf(qn * rn);
-            const float eps = 1.001f * (bound.g_sq * (qn + rn + cross) + bound.g_dot * cross + bound.g_norm * rn);
+            const float eps = 1.001f * (bound.g_sq * (qn + rn + cross) + bound.g_dot * cross + bound.g_norm * rn +
+                                        (eps_add ? eps_add[q] : 0.f));
             const int kk = nw < k ? nw : k;
             unsigned band = 0u;
             if (kk > 0) {
@@ -783,14 +786,15 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                          const float *approx_val, const int64_t *cand_pos, const int64_t *cand_slot,
                          const int64_t *seg_start, int64_t fixed_len, const ScanBound &bound,
                          float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags, int32_t *out_i32,
-                         const int32_t *probe_lists, const int64_t *probe_off, int probes) {
+                         const int32_t *probe_lists, const int64_t *probe_off, int probes, const float *eps_add) {
     if (nq <= 0) return PGV_OK;
     if (kprime > kRecheckCap || k > kprime) PGV_FAIL(PGV_ERR_ARG, "recheck: k' = %d outside k..%d", kprime, kRecheckCap);
 #define PGV_RECHECK(T)                                                                                              \
     hipLaunchKernelGGL(batch_recheck_kernel<T>, dim3(nq), dim3(kQThreads), 0, ctx->stream,                           \
                        static_cast<const char *>(xr.vectors), xr.tids, xr.geom.nvec, xr.geom.lpr_log2,               \
                        static_cast<const char *>(q_dev), kprime, k, approx_val, cand_pos, cand_slot, xr.list_offsets, \
-                       probe_lists, probe_off, probes, seg_start, fixed_len, xr.norm_max, bound, nq, out_dist, out_slot, out_tid, out_i32, flags)
+                       probe_lists, probe_off, probes, seg_start, fixed_len, xr.norm_max, bound, eps_add, nq, out_dist, out_slot,  \
+                       out_tid, out_i32, flags)
     if (xr.dtype == PGV_F32)
         PGV_RECHECK(float);
     else
@@ -803,7 +807,7 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
 int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
                      const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
                      const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32) {
+                     uint64_t *out_tid, int32_t *out_i32, const float *eps_add) {
     if (nq <= 0) return PGV_OK;
     double *stats = (ctx->profiling && ctx->stats_dev.p && probe_lists) ? ctx->stats_dev.as<double>() : nullptr;
     if (k > 4096) PGV_FAIL(PGV_ERR_ARG, "top-k: k = %d exceeds the supported 4096", k);
@@ -817,8 +821,8 @@ int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int n
     hipLaunchKernelGGL(batch_fix_kernel<T>, dim3(grid), dim3(kQThreads), lds, ctx->stream,                           \
                        static_cast<const char *>(xr.vectors), xr.list_offsets, xr.tids, xr.geom.nvec,                \
                        xr.geom.lpr_log2, static_cast<const char *>(q_dev), probe_lists, probe_off, probes, seg_start, \
-                       fixed_len, flags, nq, seg_vals, k, kp, cap, xr.norm_max, bound, widen, out_dist, out_slot, out_tid,    \
-                       out_i32, stats)
+                       fixed_len, flags, nq, seg_vals, k, kp, cap, xr.norm_max, bound, eps_add, widen, out_dist,      \
+                       out_slot, out_tid, out_i32, stats)
     if (xr.dtype == PGV_F32)
         PGV_FIX(float);
     else

@@ -360,6 +360,7 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
     res->ntasks_dev = reinterpret_cast<int *>(totals + 2);
     res->seg_start = seg_start;
     res->probe_off = probe_off;
+    res->pair_start = pair_start;
     return PGV_OK;
 }
 

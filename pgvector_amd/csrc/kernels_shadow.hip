@@ -1,0 +1,242 @@
+// kernels_shadow.hip -- the fp16 residual shadow of an fp32 L2 index and the per-batch terms of its list scan.
+//
+// The batched MFMA list scan of an L2 index only PRE-FILTERS: batch_recheck_kernel recomputes the reference's exact
+// sum((q - x)^2) over the fp32 rows for the candidates inside a proven rounding band.  The pre-filter
+// therefore need not read the fp32 rows.  It reads a shadow of half the bytes instead:
+//
+//   x = c_l + rho            (c_l: the center of the row's list)
+//   shadow row  = fp16(rho * 2^-s)          one power-of-two scale s per index: the largest |rho_i| lands near 2^14
+//   query row   = fp16(q * 2^-s_q)          one power-of-two scale s_q per query, cast once per batch
+//   pair term t = -2 q.c_l                  fp32, once per probed (query, list) pair
+//   value       = |x|^2 + t - 2^(1 + s + s_q) (shadow_q . shadow_x)
+//
+// which is the same quantity |x|^2 - 2 q.x the fp32 scan computes, up to an error that the query-cast kernel bounds
+// per query (shadow_query_kernel; the derivation is next to ScanBound in pgv_internal.h).  E and P of the index
+// (largest |rho - 2^s shadow| and largest |2^s shadow| over its rows) are measured here when the shadow is written,
+// so the bound holds whatever the data: subnormals, huge values and uneven lists only widen the band.
+#include "pgv_device.h"
+
+#include <cfloat>
+
+namespace pgv {
+
+namespace {
+
+// the list of row r: last l with list_off[l] <= r (empty lists share an offset with the next one)
+__device__ __forceinline__ int list_of_row(const int64_t *__restrict__ list_off, int nlists, int64_t r) {
+    int lo = 0, hi = nlists - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (list_off[mid] <= r)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// 2^e - 14 scale of a largest magnitude m: m * 2^-s lies in (2^13, 2^14] (0 / non-finite: s = 0)
+__device__ __forceinline__ int scale_for(float m) {
+    if (!(m > 0.f) || !isfinite(m)) return 0;
+    int e;
+    (void)frexpf(m, &e);  // m = f 2^e, f in [0.5, 1)
+    return e - 14;
+}
+
+// pass 1: the largest |x_i - c_i| over the index (bits of a non-negative float: integer order is float order)
+__global__ __launch_bounds__(256) void shadow_absmax_kernel(const float *__restrict__ rows, const float *__restrict__ centers,
+                                                            const int64_t *__restrict__ list_off, int nlists, int64_t n,
+                                                            int ld, unsigned *__restrict__ max_bits) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int l = list_of_row(list_off, nlists, r);
+    const float *x = rows + (size_t)r * ld;
+    const float *c = centers + (size_t)l * ld;
+    float m = 0.f;
+    for (int i = lane; i < ld; i += kWave) {
+        const float d = fabsf(x[i] - c[i]);
+        m = (d > m || d != d) ? d : m;  // (NaN is kept: its bits compare above every number)
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v = __shfl_xor(m, o);
+        m = (v > m || v != v) ? v : m;
+    }
+    if (lane == 0 && __float_as_uint(m) > __hip_atomic_load(max_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMax(max_bits, __float_as_uint(m));
+}
+
+// pass 2: the shadow rows, and per row |rho - 2^s shadow|^2 and |2^s shadow|^2 in fp64 (maxima as bits of
+// non-negative doubles).  rho is formed in fp64 too: the difference of two floats is exact there unless their
+// exponents lie ~30 apart (the host adds 2^-40 P for that)
+__global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restrict__ rows, const float *__restrict__ centers,
+                                                           const int64_t *__restrict__ list_off, int nlists, int64_t n,
+                                                           int ld, int ld16, const unsigned *__restrict__ max_bits,
+                                                           __half *__restrict__ shadow,
+                                                           unsigned long long *__restrict__ ep_bits) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= n) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int l = list_of_row(list_off, nlists, r);
+    const int s = scale_for(__uint_as_float(*max_bits));
+    const float *x = rows + (size_t)r * ld;
+    const float *c = centers + (size_t)l * ld;
+    __half *h = shadow + (size_t)r * ld16;
+    const double up = ldexp(1.0, s);  // (exact: |s| stays far inside fp64's exponent range)
+    double e2 = 0.0, p2 = 0.0;
+    for (int i = lane; i < ld16; i += kWave) {
+        __half v = __float2half(0.f);
+        if (i < ld) {
+            v = __float2half(ldexpf(x[i] - c[i], -s));
+            const double back = (double)__half2float(v) * up;
+            const double d = ((double)x[i] - (double)c[i]) - back;
+            e2 = fma(d, d, e2);
+            p2 = fma(back, back, p2);
+        }
+        h[i] = v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        e2 += __shfl_xor(e2, o);
+        p2 += __shfl_xor(p2, o);
+    }
+    if (lane == 0) {
+        // (NaN / inf rows: the host finds a non-finite E or P and drops the shadow).  A million atomics on one word take
+        // ~11 ms: nearly every row is below the maximum seen so far and only looks
+        const unsigned long long eb = (unsigned long long)__double_as_longlong(e2 != e2 ? INFINITY : e2),
+                                 pb = (unsigned long long)__double_as_longlong(p2 != p2 ? INFINITY : p2);
+        if (eb > __hip_atomic_load(&ep_bits[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&ep_bits[0], eb);
+        if (pb > __hip_atomic_load(&ep_bits[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&ep_bits[1], pb);
+    }
+}
+
+// One wavefront per query: the fp16 query row 2^-s_q q (scale per query), the epilogue's factor 2^(1 + s + s_q), and
+// the additive term of the rounding band that the shadow adds (pgv_internal.h, ScanBound).  The terms are formed in
+// fp64 and rounded up into fp32.
+__global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restrict__ queries, int nq, int ld, int ld16,
+                                                           ShadowTerms st, const float *__restrict__ center_norm_max,
+                                                           const float *__restrict__ row_norm_max,
+                                                           __half *__restrict__ qcast, float *__restrict__ qscale,
+                                                           float *__restrict__ qeps) {
+    const int q = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (q >= nq) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const float *x = queries + (size_t)q * ld;
+    float m = 0.f;
+    for (int i = lane; i < ld; i += kWave) {
+        const float a = fabsf(x[i]);
+        m = (a > m || a != a) ? a : m;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v = __shfl_xor(m, o);
+        m = (v > m || v != v) ? v : m;
+    }
+    const int sq = scale_for(m);
+    const double up = ldexp(1.0, sq);
+    double qq = 0.0, dd = 0.0, hh = 0.0;  // |q|^2, |q - q^|^2, |q^|^2
+    __half *h = qcast + (size_t)q * ld16;
+    for (int i = lane; i < ld16; i += kWave) {
+        __half v = __float2half(0.f);
+        if (i < ld) {
+            v = __float2half(ldexpf(x[i], -sq));
+            const double back = (double)__half2float(v) * up, xi = (double)x[i];
+            qq = fma(xi, xi, qq);
+            dd = fma(xi - back, xi - back, dd);  // (xi - back: exact in fp64)
+            hh = fma(back, back, hh);
+        }
+        h[i] = v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        qq += __shfl_xor(qq, o);
+        dd += __shfl_xor(dd, o);
+        hh += __shfl_xor(hh, o);
+    }
+    if (lane == 0) {
+        const int e = 1 + st.s + sq;
+        const double qn = sqrt(qq), dq = sqrt(dd), qh = sqrt(hh);
+        const double cmax = sqrt((double)*center_norm_max * (1.0 + st.g_cn)), rn = (double)*row_norm_max * (1.0 + st.g_cn);
+        const double tmax = 2.0 * qn * cmax;  // |t| of every pair of this query (exact value)
+        const double u = 5.9604644775390625e-8;
+        double eps = 2.0 * (qn * st.E + dq * st.P)               // representation of rows and query in fp16
+                     + st.g_dot * 2.0 * qh * st.P                // fp16 products, fp32 chains of the matrix cores
+                     + st.g_pair * tmax                          // the pair term's fp32 chain
+                     + 4.0 * u * (rn + tmax * (1.0 + st.g_pair) + 2.0 * qh * st.P * (1.0 + st.g_dot));  // epilogue
+        eps = eps * (1.0 + 1.0 / 1048576.0) + 4.0 * (double)FLT_MIN;  // fp32 rounding up; what underflowed on the way
+        // a scale outside the normal fp32 range (or non-finite input) would not be exact: everything in the band
+        if (e < -125 || e > 125 || !(eps < 1e30)) eps = INFINITY;
+        qscale[q] = ldexpf(1.f, e < -125 ? 0 : (e > 125 ? 0 : e));
+        qeps[q] = (float)eps;
+    }
+}
+
+// One wavefront per probed (query, list) pair: t = -2 q.c_l into the pair's free word.  Each lane runs ONE fmaf chain
+// over ceil(ld / 64) elements, then six shuffle additions: gamma_(ceil(ld / 64) + 6) |q||c_l| (ShadowTerms::g_pair).
+__global__ __launch_bounds__(256) void shadow_pair_kernel(const float *__restrict__ queries, const float *__restrict__ centers,
+                                                          const int64_t *__restrict__ pair_start, int nlists, int64_t npairs,
+                                                          int ld, ScanPair *__restrict__ pairs) {
+    const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pos >= npairs) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    int lo = 0, hi = nlists - 1;  // last list whose first pair is <= pos
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (pair_start[mid] <= pos)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const int q = pairs[pos].query;
+    const float *x = queries + (size_t)q * ld;
+    const float *c = centers + (size_t)lo * ld;
+    float a = 0.f;
+    for (int i = lane; i < ld; i += kWave) a = fmaf(x[i], c[i], a);
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+    if (lane == 0) pairs[pos].pad = (int32_t)__float_as_uint(-2.f * a);
+}
+
+}  // namespace
+
+int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *rows, const void *centers,
+                        const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words) {
+    if (n <= 0) return PGV_OK;
+    // words: [0] max |rho_i| bits (u32) | [1..2] E^2, P^2 bits (u64 at byte 8)
+    PGV_HIP(hipMemsetAsync(words, 0, 24, ctx->stream));
+    unsigned *max_bits = static_cast<unsigned *>(words);
+    unsigned long long *ep = reinterpret_cast<unsigned long long *>(static_cast<char *>(words) + 8);
+    const dim3 grid((unsigned)((n + 3) / 4));
+    hipLaunchKernelGGL(shadow_absmax_kernel, grid, dim3(256), 0, ctx->stream, static_cast<const float *>(rows),
+                       static_cast<const float *>(centers), list_off, nlists, n, g32.ld, max_bits);
+    hipLaunchKernelGGL(shadow_build_kernel, grid, dim3(256), 0, ctx->stream, static_cast<const float *>(rows),
+                       static_cast<const float *>(centers), list_off, nlists, n, g32.ld, g16.ld, max_bits, static_cast<__half *>(shadow), ep);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int shadow_scale_of(float max_abs) {
+    if (!(max_abs > 0.f) || !std::isfinite(max_abs)) return 0;
+    int e;
+    (void)std::frexp(max_abs, &e);
+    return e - 14;
+}
+
+int launch_shadow_query(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *queries, int nq,
+                        const ShadowTerms &st, const float *center_norm_max, const float *row_norm_max, void *qcast,
+                        float *qscale, float *qeps) {
+    if (nq <= 0) return PGV_OK;
+    hipLaunchKernelGGL(shadow_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream,
+                       static_cast<const float *>(queries), nq, g32.ld, g16.ld, st, center_norm_max, row_norm_max, static_cast<__half *>(qcast),
+                       qscale, qeps);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_shadow_pairs(pgv_ctx *ctx, const RowGeom &g32, const void *queries, const void *centers,
+                        const int64_t *pair_start, int nlists, int64_t npairs, ScanPair *pairs) {
+    if (npairs <= 0) return PGV_OK;
+    hipLaunchKernelGGL(shadow_pair_kernel, dim3((unsigned)((npairs + 3) / 4)), dim3(256), 0, ctx->stream,
+                       static_cast<const float *>(queries), static_cast<const float *>(centers), pair_start, nlists, npairs,
+                       g32.ld, pairs);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+}  // namespace pgv

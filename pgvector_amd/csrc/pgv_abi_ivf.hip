@@ -55,6 +55,62 @@ void index_host_tables(pgv_index *ix) {
 extern "C++" {
 namespace {
 
+// PGV_SCAN_SHADOW: 0 = never build or use the fp16 residual shadow, 1 = always (fp32 L2 indexes), unset = the default
+// policy: fp32 L2 indexes whose rows stream past the caches (what the list scan reads from HBM; below that the shadow
+// would only cost memory).  Read at every index creation and batch, so that one process can compare both forms
+int shadow_env() {
+    const char *e = getenv("PGV_SCAN_SHADOW");
+    return e ? atoi(e) : -1;
+}
+
+// The fp16 residual shadow of an fp32 L2 index (kernels_shadow.hip; the bound: pgv_internal.h, ScanBound), built once
+// with the index -- its rows never change afterwards.  Its own allocation (+50 % of the fp32 row bytes), outside the
+// exportable arena; no device memory for it is no error: the list scan keeps the fp32 rows
+int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
+    const int env = shadow_env();
+    if (env == 0 || ix->metric != PGV_L2SQ || ix->dtype != PGV_F32 || ix->nrows <= 0 || !ix->row_norms || !ix->center_norms)
+        return PGV_OK;
+    if (env < 0 && !rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows)) return PGV_OK;
+    const RowGeom g16 = row_geom(ix->dim, PGV_F16);
+    const size_t bytes = ((size_t)ix->nrows * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
+    void *sh = nullptr;
+    if (hipMalloc(&sh, bytes + 256) != hipSuccess) {
+        (void)hipGetLastError();
+        return PGV_OK;
+    }
+    void *words = static_cast<char *>(sh) + bytes;  // [0] max |x_i - c_i| | [8] E^2 | [16] P^2
+    int rc = launch_shadow_build(ctx, ix->geom, g16, ix->vectors, ix->centers, ix->list_offsets, ix->nlists, ix->nrows, sh,
+                                 words);
+    unsigned char h[24];
+    if (rc == PGV_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+                         hipMemcpy(h, words, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)) {
+        set_error("shadow build failed: %s", hipGetErrorString(hipGetLastError()));
+        rc = PGV_ERR_DEVICE;
+    }
+    if (rc != PGV_OK) {
+        (void)hipFree(sh);
+        return rc;
+    }
+    float max_abs;
+    double e2, p2;
+    memcpy(&max_abs, h, 4);
+    memcpy(&e2, h + 8, 8);
+    memcpy(&p2, h + 16, 8);
+    const double P = std::sqrt(p2), E = std::sqrt(e2);
+    if (!std::isfinite(E) || !std::isfinite(P) || !std::isfinite(max_abs)) {  // NaN / inf rows: the fp32 scan
+        (void)hipFree(sh);
+        return PGV_OK;
+    }
+    // rounded up: the fp64 sums (relative 1e-9 covers them many times over) and rho itself in fp64 (x_i - c_i is
+    // exact there unless the exponents lie ~30 apart: 1e-12 |rho| <= 1e-12 (P + E) covers that)
+    ix->shadow = sh;
+    ix->shadow_geom = g16;
+    ix->shadow_s = shadow_scale_of(max_abs);
+    ix->shadow_E = (E + 1e-12 * (P + E)) * (1.0 + 1e-9);
+    ix->shadow_P = P * (1.0 + 1e-9);
+    return PGV_OK;
+}
+
 // The mirror of an index whose list offsets are known: one allocation, host tables, the norms the MFMA paths want.
 // `fill` enqueues (on ctx->stream) whatever brings centers / vectors / tids into the carved arrays.
 template <typename Fill>
@@ -113,6 +169,7 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
                                    reinterpret_cast<unsigned *>(ix->center_norms + nlists))) != PGV_OK)
             return fail(rc);
     }
+    if ((rc = shadow_create(ctx, ix)) != PGV_OK) return fail(rc);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess)
         return fail((set_error("index upload failed: %s", hipGetErrorString(hipGetLastError())), PGV_ERR_DEVICE));
     *out = ix;
@@ -651,6 +708,7 @@ void pgv_index_free(pgv_index *ix) {
         else
             (void)hipFree(ix->arena);
     }
+    if (ix->shadow) (void)hipFree(ix->shadow);
     delete ix->refs;
     delete ix;
 }
@@ -933,6 +991,31 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
     float *cand_val = sc.cand_val;
     int64_t *cand_pos = sc.cand_pos;
     int32_t *flags = sc.flags;
+    // fp32 L2 with the fp16 residual shadow (kernels_shadow.hip): the scan streams half the bytes.  Per batch: the
+    // cast queries, their factors 2^(1 + s + s_q) and band terms, and every probed pair's -2 q.c_l
+    const bool shadow = approx && ix->shadow && shadow_env() != 0;
+    void *qcast = nullptr;
+    float *qscale = nullptr, *qeps = nullptr;
+    if (shadow) {
+        const RowGeom &g16 = ix->shadow_geom;
+        const size_t qb = ((size_t)nq * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
+        PGV_TRY(ctx->sh_q.ensure(qb + 2 * sizeof(float) * (size_t)nq));
+        qcast = ctx->sh_q.p;
+        qscale = reinterpret_cast<float *>(ctx->sh_q.as<char>() + qb);
+        qeps = qscale + nq;
+        constexpr double u = 5.9604644775390625e-8;  // 2^-24
+        ShadowTerms st;
+        st.s = ix->shadow_s;
+        st.E = ix->shadow_E;
+        st.P = ix->shadow_P;
+        st.g_dot = gamma_n(shadow_chain_length(g16) + 4.0, u);
+        st.g_pair = gamma_n((ix->geom.ld + 63) / 64 + 6.0, u);
+        st.g_cn = gamma_n(ix->geom.ld / 64.0 + 10.0, u);
+        PGV_TRY(launch_shadow_query(ctx, ix->geom, g16, q_dev, nq, st, ix->center_norms + ix->nlists,
+                                    ix->row_norms + ix->nrows, qcast, qscale, qeps));
+        PGV_TRY(launch_shadow_pairs(ctx, ix->geom, q_dev, ix->centers, plan.pair_start, ix->nlists, (int64_t)nq * probes,
+                                    plan.pairs));
+    }
 
     // GetScanItems: one streaming pass
     PGV_TRY(ctx->plan_d.ensure(sizeof(float) * (size_t)(plan.out_bound > 0 ? plan.out_bound : 1)));
@@ -941,7 +1024,11 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
         PGV_TRY(scan_turn_begin(ctx));
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin(0.0, 0.0));  // pairs / rows of this launch are accumulated on the device
-        if (use_mfma)
+        if (shadow)
+            PGV_TRY(launch_mfma_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->shadow, qcast, plan.tasks,
+                                     plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
+                                     seg_vals, rows_stream_past_caches(ix->shadow_geom, PGV_F16, ix->nrows), qt, qscale));
+        else if (use_mfma)
             PGV_TRY(launch_mfma_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
                                      plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
                                      seg_vals, rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows), qt));
@@ -966,17 +1053,19 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
         // k' candidates by the expansion, their exact distances, the head; queries whose candidate
         // set cannot be proven complete (flags) take the exact pass over their whole segment
         // (the 64-query form of the scan keeps its four chains as consecutive quarters of the row: whole 128-byte slices)
-        const ScanBound gamma = wide ? scan_bound_chain(ctx, ix->geom.ld, dense_chain_length(ix->geom, ix->dtype))
-                                     : scan_bound(ctx, ix->geom.ld);
+        ScanBound gamma = wide ? scan_bound_chain(ctx, ix->geom.ld, dense_chain_length(ix->geom, ix->dtype))
+                               : scan_bound(ctx, ix->geom.ld);
+        if (shadow)  // |x|^2's rounding (worst case) and the exact form's; the rest is the per-query term qeps
+            gamma = {0.f, 0.f, gamma_n(ix->geom.ld / 64.0 + 10.0, 5.9604645e-8), gamma.g_ref};
         PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, kprime, cand_val, cand_pos, flags + nq));
         const ExactRows xr{ix->vectors, ix->tids, ix->list_offsets, ix->geom, ix->dtype,
                            reinterpret_cast<const unsigned *>(ix->row_norms + ix->nrows)};
         // (the candidates' positions become row slots inside the recheck)
         PGV_TRY(launch_batch_recheck(ctx, xr, q_dev, nq, kprime, k, cand_val, cand_pos, nullptr, plan.seg_start, 0,
                                      gamma, od.as<float>(), os.as<int64_t>(), ot.as<uint64_t>(), flags, nullptr,
-                                     probe_lists, plan.probe_off, probes));
+                                     probe_lists, plan.probe_off, probes, qeps));
         PGV_TRY(launch_batch_fix(ctx, xr, q_dev, nq, probe_lists, plan.probe_off, probes, plan.seg_start, 0, flags,
-                                 seg_vals, k, gamma, od.as<float>(), os.as<int64_t>(), ot.as<uint64_t>()));
+                                 seg_vals, k, gamma, od.as<float>(), os.as<int64_t>(), ot.as<uint64_t>(), nullptr, qeps));
     } else {
         PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, k, od.as<float>(), pos));
         PGV_TRY(launch_positions_to_slots(ctx, ix, probe_lists, plan.probe_off, nq, probes, k, pos,

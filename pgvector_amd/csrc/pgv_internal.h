@@ -113,6 +113,7 @@ struct pgv_ctx {
     int dense_plan_nq = -1, dense_plan_kind = -1;
     bool counters_clean = false;  // ctx->counters starts zeroed; mfma_scan_kernel leaves its words zero again
     pgv::DBuf ms_a;  // MFMA list scan: query norms | candidate values, positions, slots | flags
+    pgv::DBuf sh_q;  // the shadow list scan (kernels_shadow.hip): cast queries | their factors | their band terms
     pgv::DBuf mf_d;  // MFMA assignment split over center parts: the parts' candidates per row
     pgv::DBuf mf_a, mf_b, mf_c, zeros;  // MFMA assignment: norms, pre-filter candidates, redo list; 16 zero bytes
     pgv::DBuf stats_dev;  // profiling: {pairs, rows streamed} of the batched list scans, as doubles
@@ -167,6 +168,14 @@ struct pgv_index {
     void *arena = nullptr;
     size_t arena_bytes = 0;
     bool imported = false;            // arena was opened with hipIpcOpenMemHandle: closed, not freed
+    // fp32 L2 indexes: the fp16 residual shadow the batched MFMA list scan streams instead of `vectors`
+    // (kernels_shadow.hip): [nrows x shadow_geom.ld] fp16((x - c_l) 2^-shadow_s).  Its own allocation (the IPC
+    // handle carries the arena only); shared by pgv_index_share views and freed with the arena; null when not built
+    void *shadow = nullptr;
+    pgv::RowGeom shadow_geom{};
+    int shadow_s = 0;
+    double shadow_E = 0.0;            // max over rows |(x - c_l) - 2^s shadow|, rounded up
+    double shadow_P = 0.0;            // max over rows |2^s shadow|, rounded up
     std::vector<int64_t> h_offsets;   // host copy
     std::vector<int64_t> len_prefix;  // len_prefix[p] = rows in the p longest lists (output size bound)
     int64_t max_list_len = 0;
@@ -290,8 +299,31 @@ namespace pgv {
 //   worst case over statistical +4 % (1 M x 1000 x 1536 fp32), +10 % (1.25 M x 4096 x 3072 fp16), redo 0 - 0.06 %.
 //   One unit roundoff per product of the chain is what the bound charges; tools/mfma_numerics.py shows the fp32 matrix
 //   instructions to BE an fmaf chain bit for bit and the fp16 ones to lose at most 3.2 u per 16 products (charged: 16 u).
+//
+// The fp16 residual shadow (kernels_shadow.hip) -- the list scan of an fp32 L2 index over a shadow row
+// rho~ = fp16((x - c_l) 2^-s) and a cast query q^ = 2^s_q fp16(q 2^-s_q) computes
+//     a = fl(|x|^2 + t) - 2^(1 + s + s_q) acc,   t = fl(-2 q.c_l),   acc = fl(q^' . rho~)
+// for the same s = |x|^2 - 2 q.c_l - 2 q.rho (x = c_l + rho).  The band of such a scan is ScanBound {0, 0, g_norm, g_ref}
+// (worst-case g_norm: |x|^2 is the fp32 rows' own) plus a PER-QUERY term, computed in fp64 by shadow_query_kernel and
+// rounded up into fp32, that covers every other difference between a and s:
+//     representation   2 (|q| E + |q - q^| P):  q.rho - q^.(2^s rho~) = q.(rho - 2^s rho~) + (q - q^).(2^s rho~)
+//                      (E = max |rho - 2^s rho~|, P = max |2^s rho~|, measured over the index's rows in fp64)
+//     matrix cores     g_dot 2 |q^| P, g_dot = gamma_(chain + 4): fp16 products are exact in fp32, each of the four
+//                      accumulator chains adds at most `chain` of them (shadow_chain_length; the instructions lose at
+//                      most 3.2 u per 16 products, charged u per product), two additions join the chains
+//     pair term        gamma_(ceil(ld / 64) + 6) 2 |q| max|c|: shadow_pair_kernel's per-lane fmaf chain + 6 shuffle
+//                      additions; max|c| from center_norms[nlists] (itself within gamma_(ld / 64 + 10))
+//     epilogue         4 u (|x|^2 + |t| + 2 |q^| P): the addition |x|^2 + t and the final fmaf round once each
+// and 4 FLT_MIN for whatever underflowed on the way; the 1.001 factor of the scans' eps applies on top.  A query whose
+// scale 2^(1 + s + s_q) leaves the normal fp32 range, or whose terms are not finite, gets an infinite term: its band
+// holds everything and batch_fix_kernel scores it exactly.
 struct ScanBound {
     float g_sq, g_dot, g_norm, g_ref;
+};
+struct ShadowTerms {  // shadow_query_kernel's inputs
+    int s;
+    double E, P;
+    double g_dot, g_pair, g_cn;  // g_cn: relative error of the stored largest |x|^2 / |c|^2
 };
 inline float gamma_n(double n, double v) { return (float)(n * v / (1.0 - n * v)); }
 inline ScanBound scan_bound(const pgv_ctx *ctx, int dim) {
@@ -432,7 +464,18 @@ int launch_row_norms(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void
 int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,
                      const void *queries, const ScanTask *tasks, const int *ntasks_dev, int ntasks_bound,
                      const ScanPair *pairs, const float *row_norms, const float *query_norms, float *out, bool stream_rows,
-                     int queries_per_task = 32);
+                     int queries_per_task = 32, const float *shadow_scale = nullptr);
+// kernels_shadow.hip: the fp16 residual shadow of an fp32 L2 index (pgv_index::shadow) and its per-batch terms.
+// words: 24 device bytes, [0] bits of the largest |x_i - c_i|, [8] / [16] bits of the largest E^2 / P^2 (fp64)
+int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *rows, const void *centers,
+                        const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words);
+int shadow_scale_of(float max_abs);  // s of the largest |x_i - c_i|
+int shadow_chain_length(const RowGeom &g16);  // kernels_mfma.hip: products per accumulator chain of any scan form, at most
+int launch_shadow_query(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *queries, int nq,
+                        const ShadowTerms &st, const float *center_norm_max, const float *row_norm_max, void *qcast,
+                        float *qscale, float *qeps);
+int launch_shadow_pairs(pgv_ctx *ctx, const RowGeom &g32, const void *queries, const void *centers,
+                        const int64_t *pair_start, int nlists, int64_t npairs, ScanPair *pairs);
 int mfma_scan_queries_per_task_wide();  // 64: tasks of the batches whose lists are probed by many queries each
 
 // kernels_build.hip: rows of 32-bit words gathered by index (the HNSW mirror's per-element payload)
@@ -457,6 +500,7 @@ struct PlanResult {
     int64_t out_bound = 0;
     int64_t *seg_start = nullptr; // device [nq + 1]
     int64_t *probe_off = nullptr; // device [nq x probes]
+    int64_t *pair_start = nullptr; // device [nlists + 1]: the first pair of each list
 };
 int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists, int nq,
                       int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res);
@@ -480,13 +524,15 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                          const int64_t *seg_start, int64_t fixed_len, const ScanBound &bound,
                          float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags,
                          int32_t *out_i32 = nullptr, const int32_t *probe_lists = nullptr,
-                         const int64_t *probe_off = nullptr, int probes = 0);  // cand_slot null: slots from the positions
+                         const int64_t *probe_off = nullptr, int probes = 0,
+                         const float *eps_add = nullptr);  // cand_slot null: slots from the positions; eps_add: per query
+                                                           // term of the band (the shadow scan), or null
 // the flagged queries start to end: exact scores of the whole segment, head, output row (out_slot: row slots, or
 // center ids for the dense form)
 int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
                      const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
                      const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32 = nullptr);
+                     uint64_t *out_tid, int32_t *out_i32 = nullptr, const float *eps_add = nullptr);
 int launch_iota_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *lists_dev, int nlists,
                       const int64_t *probe_off, int64_t *out_slot);
 
