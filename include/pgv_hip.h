@@ -182,6 +182,9 @@ typedef struct pgv_stats
 	double		scan_redo_queries;
 	/* ... and those that a wider candidate set (256 instead of k') did settle, without the exact pass */
 	double		scan_widened_queries;
+	/* fp32 L2 batches scanned on the matrix cores: queries whose pre-filter read the fp16 residual shadow
+	 * of the index instead of its fp32 rows (counted whether or not profiling is on) */
+	double		scan_shadow_queries;
 }			pgv_stats;
 int			pgv_ctx_set_profiling(pgv_ctx * ctx, int on);
 /*

@@ -263,6 +263,7 @@ int pgv_ctx_reset_stats(pgv_ctx *ctx) {
     ctx->aux_ms = 0;
     ctx->aux_launches = 0;
     ctx->aux_pairs = 0;
+    ctx->scan_shadow_queries = 0;
     for (pgv_ctx *c : ctx->children) PGV_TRY(pgv_ctx_reset_stats(c));
     return PGV_OK;
 }
@@ -288,6 +289,7 @@ int pgv_ctx_get_stats(pgv_ctx *ctx, pgv_stats *out) {
     out->scan_unique_rows = dev_acc[5];
     out->scan_redo_queries = dev_acc[6];
     out->scan_widened_queries = dev_acc[7];
+    out->scan_shadow_queries = ctx->scan_shadow_queries;
     for (pgv_ctx *c : ctx->children) {  // what the lanes of overlapping batches did counts as this context's
         pgv_stats cs;
         PGV_TRY(pgv_ctx_get_stats(c, &cs));
@@ -304,6 +306,7 @@ int pgv_ctx_get_stats(pgv_ctx *ctx, pgv_stats *out) {
         out->scan_unique_rows += cs.scan_unique_rows;
         out->scan_redo_queries += cs.scan_redo_queries;
         out->scan_widened_queries += cs.scan_widened_queries;
+        out->scan_shadow_queries += cs.scan_shadow_queries;
     }
     return PGV_OK;
 }

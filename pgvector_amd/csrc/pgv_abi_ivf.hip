@@ -1015,6 +1015,7 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
                                     ix->row_norms + ix->nrows, qcast, qscale, qeps));
         PGV_TRY(launch_shadow_pairs(ctx, ix->geom, q_dev, ix->centers, plan.pair_start, ix->nlists, (int64_t)nq * probes,
                                     plan.pairs));
+        ctx->scan_shadow_queries += nq;
     }
 
     // GetScanItems: one streaming pass

@@ -139,6 +139,7 @@ struct pgv_ctx {
     double aux_ms = 0.0;
     int64_t aux_launches = 0;
     double aux_pairs = 0.0;
+    double scan_shadow_queries = 0.0;  // queries of batched list scans that read the fp16 residual shadow
     // lanes of indexes whose batches overlap (pgv_index_set_overlap): contexts with streams of their own that belong to
     // an index of this context; pgv_ctx_sync waits for them, the settings and the statistics include them
     std::vector<pgv_ctx *> children;

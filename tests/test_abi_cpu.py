@@ -49,3 +49,18 @@ def test_no_cpu_fallback_without_gpu():
         pgvector_amd.api.Context(0)
     assert e.value.code == _lib.PGV_ERR_DEVICE
     assert "no CPU path" in e.value.message
+
+
+def test_stats_struct_matches_the_header():
+    """pgvector_amd/_lib.py PgvStats mirrors `pgv_stats` of include/pgv_hip.h member for member: the library writes the
+    whole struct, so a missing or reordered field on the Python side reads the wrong doubles (or writes past the end)"""
+    text = open(os.path.join(ROOT, "include", "pgv_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = re.search(r"typedef\s+struct\s+pgv_stats\s*\{(.*?)\}\s*pgv_stats\s*;", text, flags=re.S)
+    assert body, "pgv_stats not found in include/pgv_hip.h"
+    members = re.findall(r"\b(double|int64_t)\s+([a-z_][a-z0-9_]*)\s*;", body.group(1))
+    assert len(members) == body.group(1).count(";"), "a member of pgv_stats that is neither double nor int64_t"
+    ctypes_of = {"double": ctypes.c_double, "int64_t": ctypes.c_int64}
+    assert [n for _, n in members] == [n for n, _ in _lib.PgvStats._fields_]
+    assert [ctypes_of[t] for t, _ in members] == [t for _, t in _lib.PgvStats._fields_]
+    assert members[-1][1] == "scan_shadow_queries"

@@ -59,6 +59,25 @@ def test_mfma_fp16_chain_rounds_to_nearest(ctx, nq):
     assert (v[:, 0] == np.float32(1.0 + 2.0 ** -23)).all(), v[:, 0].astype(np.float64) - 1.0
 
 
+@pytest.mark.parametrize("nq", [8, 64])
+def test_mfma_fp16_subnormal_operands_are_not_flushed(ctx, nq):
+    """The fp16 residual shadow's bound (E and P, measured with __half2float at build) assumes that the matrix cores
+    read fp16 subnormals exactly as __half2float does.  Products whose one or both operands are subnormal, each alone in
+    its row so that the row's value is that product: 2^-24 x 1, 2^-20 x 2^-14 (= 2^-34, a normal fp32) and
+    2^-20 x 2^-20.  A flushing pipeline gives 0."""
+    dim, n = 256, 32
+    rows = np.zeros((n, dim), dtype=np.float16)
+    queries = np.zeros((nq, dim), dtype=np.float16)
+    rows[0, 0], queries[:, 0] = np.float16(2.0 ** -24), 1.0
+    rows[1, 4], queries[:, 4] = np.float16(2.0 ** -20), np.float16(2.0 ** -14)
+    rows[2, 136], queries[:, 136] = np.float16(2.0 ** -20), np.float16(2.0 ** -20)
+    rows[3, 0], rows[3, 136] = np.float16(2.0 ** -24), np.float16(2.0 ** -20)  # both in one row: 2^-24 + 2^-40
+    assert rows[0, 0] == 2.0 ** -24 and rows[1, 4] == 2.0 ** -20 and queries[0, 136] == 2.0 ** -20  # (representable)
+    v = _ip_values(ctx, api.PGV_F16, rows, queries)
+    for r, want in ((0, 2.0 ** -24), (1, 2.0 ** -34), (2, 2.0 ** -40), (3, 2.0 ** -24 + 2.0 ** -40)):
+        assert (v[:, r] == np.float32(want)).all(), (r, v[:, r].astype(np.float64) / want)
+
+
 # ------------------------------------------------- nobody may hang: the gate, clients that die, leaders that die
 def _small_index(ctx, oracle):
     from oracle import pyoracle as po
@@ -162,6 +181,8 @@ def test_config_scale_answers_are_the_oracles(ctx, oracle, name, n, dim, lists, 
     st = ctx.stats()
     ctx.set_profiling(False)
     assert st["scan_launches"] >= 1 and st["scan_redo_queries"] == 0        # the matrix-core scan, deterministic bound
+    if name in ("headline", "c2"):  # fp32 L2 rows of 1 GiB or more: the default policy scans the fp16 residual shadow
+        assert st["scan_shadow_queries"] > 0, st
     gd, gt = gd.cpu().numpy(), gt.cpu().numpy()
     centers_h = centers.cpu().numpy() if hasattr(centers, "cpu") else np.asarray(centers)
     ix = oracle.index_struct(po.OPS_L2 if ops == "l2" else po.OPS_IP, po.ORA_F32 if tdt == "f32" else po.ORA_F16, centers_h,

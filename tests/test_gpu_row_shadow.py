@@ -51,8 +51,12 @@ def _both(ctx, monkeypatch, dim, rows, centers, off, queries, probes, k, lanes=1
                 d, s, t = ix.search_batch(queries[b::batches], probes, k, want_tid=True)
                 res.append((d, s, t))
             ctx.sync()
+            st = ctx.stats()
             if env == "1":
-                redo = ctx.stats()["scan_redo_queries"]
+                redo = st["scan_redo_queries"]
+                assert st["scan_shadow_queries"] > 0, st  # the shadow ran: no silent fall-back to the fp32 scan
+            else:
+                assert st["scan_shadow_queries"] == 0, st
             out.append([(np.asarray(d).copy(), np.asarray(s).copy(), np.asarray(t).copy()) for d, s, t in res])
         finally:
             ctx.set_profiling(False)
