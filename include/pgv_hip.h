@@ -116,6 +116,13 @@ int			pgv_abi_version(void);
 
 /* number of HIP devices visible (0 when there is no GPU / no driver) */
 int			pgv_device_count(void);
+/*
+ * Products per accumulator chain that the deterministic rounding band of the matrix-core L2 paths charges for rows of
+ * `dim` elements (ScanBound's g_dot = gamma_(chain + 4)): path 0 the list scan and center ranking on the 32-query
+ * kernel, 1 the list scan on the 64-query kernel, 2 pgv_exact_topk's 128 x 128 tiling.  For tests and diagnostics;
+ * needs no device.  -1: unknown dtype / path.
+ */
+int			pgv_scan_chain_length(int dim, pgv_dtype dtype, int path);
 /* free / total HBM of a device in bytes as the driver reports them now (all processes' allocations counted) */
 int			pgv_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
 /*

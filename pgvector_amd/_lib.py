@@ -32,7 +32,7 @@ PGV_BOUND_STATISTICAL, PGV_BOUND_WORST_CASE = 0, 1
 
 # every symbol include/pgv_hip.h declares (tests check the library exports each)
 SYMBOLS = [
-    "pgv_last_error", "pgv_abi_version", "pgv_device_count", "pgv_ctx_create", "pgv_ctx_destroy",
+    "pgv_last_error", "pgv_abi_version", "pgv_device_count", "pgv_scan_chain_length", "pgv_ctx_create", "pgv_ctx_destroy",
     "pgv_ctx_sync", "pgv_ctx_stream", "pgv_timer_start", "pgv_timer_stop", "pgv_ctx_set_profiling", "pgv_ctx_set_exact_scan", "pgv_index_share", "pgv_pinned_alloc", "pgv_pinned_free",
     "pgv_ctx_reset_stats", "pgv_ctx_get_stats", "pgv_index_upload", "pgv_index_free",
     "pgv_index_rows", "pgv_index_lists", "pgv_rank_lists", "pgv_scan_lists", "pgv_search_batch", "pgv_scan_batch",
@@ -93,6 +93,8 @@ def _load():
     lib.pgv_last_error.argtypes = []
     lib.pgv_abi_version.restype = I
     lib.pgv_device_count.restype = I
+    lib.pgv_scan_chain_length.argtypes = [I, I, I]
+    lib.pgv_scan_chain_length.restype = I
     lib.pgv_ctx_create.argtypes = [I, P, C.POINTER(P)]
     lib.pgv_ctx_destroy.argtypes = [P]
     lib.pgv_ctx_destroy.restype = None

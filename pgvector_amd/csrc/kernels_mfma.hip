@@ -137,9 +137,10 @@ template <> struct Mma<__half> {
 };
 
 // The list scan's forms: FOUR independent accumulators per output (chain e gets every 4th k-group), summed as
-// (c0 + c1) + (c2 + c3) in the epilogue.  Each chain adds up dim / 4 products, so the worst-case rounding error of the
-// dot product is gamma_(dim/4 + 2) sum |a_i b_i| instead of gamma_dim -- which is what makes the DETERMINISTIC
-// completeness bound of the L2 scan (scan_bound, pgv_internal.h) as tight as the statistical one was; the
+// (c0 + c1) + (c2 + c3) in the epilogue.  Each chain adds up `chain` products -- dim / 4 for fp32, whole instructions of
+// 16 products for fp16, so up to 16 ceil(dim / 64) (scan_chain_length below) -- and the worst-case rounding error of
+// the dot product is gamma_(chain + 2) sum |a_i b_i| instead of gamma_dim, which is what makes the DETERMINISTIC
+// completeness bound of the L2 scan (scan_bound_chain, pgv_internal.h) as tight as the statistical one was; the
 // chains are also independent MFMA issue streams (no dependent-issue stalls).
 template <typename T> struct Mma4;
 template <> struct Mma4<float> {
@@ -1324,6 +1325,16 @@ int shadow_chain_length(const RowGeom &g16) {
     const int nslices = (g16.nvec + 7) / 8;
     const int a = 16 * nslices, b = 32 * ((nslices + 1) / 2), c = 64 * ((nslices + 3) / 4);
     return std::max(a, std::max(b, c));
+}
+// products per accumulator chain of mfma_scan_kernel, at most, whichever form may take a task of the launch (`wide`: the
+// 64-query kernel, whose tasks of <= 32 queries still take the four-chain forms).  fp32: chain e is every 4th element in
+// both four-chain forms, a quarter of whole slices in the 64-query one.  fp16: the cases of shadow_chain_length -- with
+// an odd slice count the 16-wide form puts 32 ceil(S / 2) products on chains 0 and 1, more than the ld / 4 an even split
+// would (64-d: 32, not 16).  What scan_bound_chain computes g_dot from; tests/chain_model.py restates the chains.
+int scan_chain_length(const RowGeom &g, pgv_dtype dtype, bool wide) {
+    const int nslices = (g.nvec + 7) / 8, quarter = (nslices + 3) / 4;
+    if (dtype == PGV_F32) return std::max(g.ld / 4, wide ? 32 * quarter : 0);
+    return std::max(16 * nslices, std::max(32 * ((nslices + 1) / 2), wide ? 64 * quarter : 0));
 }
 // ... or twice that, when the lists of a batch are probed by more than ~12 queries on average (the 64-query form)
 int mfma_scan_queries_per_task_wide() { return 2 * kScanQueries; }

@@ -87,6 +87,12 @@ extern "C" {
 const char *pgv_last_error(void) { return pgv::g_err; }
 int pgv_abi_version(void) { return PGV_ABI_VERSION; }
 
+int pgv_scan_chain_length(int dim, pgv_dtype dtype, int path) {
+    if ((dtype != PGV_F32 && dtype != PGV_F16) || dim <= 0 || path < 0 || path > 2) return -1;
+    const pgv::RowGeom g = pgv::row_geom(dim, dtype);
+    return path == 2 ? pgv::dense_chain_length(g, dtype) : pgv::scan_chain_length(g, dtype, path == 1);
+}
+
 int pgv_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {

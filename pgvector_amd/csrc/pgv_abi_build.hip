@@ -138,7 +138,8 @@ int pgv_exact_topk(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, co
             ApproxScratch sc;
             PGV_TRY(sc.carve(ctx, ctx->ms_b, cn, kprime));
             // the candidates are proven complete with the rounding bound of the kernel that produced the values
-            const ScanBound bound = dense128 ? scan_bound_chain(ctx, g.ld, dense_chain_length(g, dtype)) : scan_bound(ctx, g.ld);
+            const ScanBound bound = scan_bound_chain(ctx, g.ld, dense128 ? dense_chain_length(g, dtype)
+                                                                          : scan_chain_length(g, dtype, false));
             if (dense128)
                 PGV_TRY(launch_mfma_dense(ctx, metric, dtype, g, r_dev, n, qp, cn, norms, mat, n));
             else

@@ -775,13 +775,15 @@ int rank_lists_dev(pgv_index *ix, const void *q_dev, int nq, int maxprobes,
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, cand, sc.cand_val, sc.cand_pos, sc.flags + nq));
         const ExactRows xr{ix->centers, nullptr, nullptr, ix->geom, ix->dtype,
                            reinterpret_cast<const unsigned *>(ix->center_norms + ix->nlists)};
+        // (dense_scan: the 32-query kernel, its 16-wide form for a last group of <= 16 queries)
+        const ScanBound bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, false));
         // a center's position in the matrix row is its id: cand_pos serves as the slots
         // the center ids leave as the int32 list ids the callers want (no conversion pass)
         PGV_TRY(launch_batch_recheck(ctx, xr, q_dev, nq, cand, maxprobes, sc.cand_val, sc.cand_pos, sc.cand_pos, nullptr,
-                                     ix->nlists, scan_bound(ctx, ix->geom.ld), dist, nullptr, nullptr, sc.flags,
+                                     ix->nlists, bound, dist, nullptr, nullptr, sc.flags,
                                      out_lists_dev));
         PGV_TRY(launch_batch_fix(ctx, xr, q_dev, nq, nullptr, nullptr, 0, nullptr, ix->nlists, sc.flags, mat, maxprobes,
-                                 scan_bound(ctx, ix->geom.ld), dist, nullptr, nullptr, out_lists_dev));
+                                 bound, dist, nullptr, nullptr, out_lists_dev));
         return PGV_OK;
     } else {
         PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
@@ -1053,9 +1055,9 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
     if (approx) {
         // k' candidates by the expansion, their exact distances, the head; queries whose candidate
         // set cannot be proven complete (flags) take the exact pass over their whole segment
-        // (the 64-query form of the scan keeps its four chains as consecutive quarters of the row: whole 128-byte slices)
-        ScanBound gamma = wide ? scan_bound_chain(ctx, ix->geom.ld, dense_chain_length(ix->geom, ix->dtype))
-                               : scan_bound(ctx, ix->geom.ld);
+        // (the 64-query form of the scan keeps its four chains as consecutive quarters of the row: whole 128-byte slices;
+        // the chain length covers every form that a task of this launch may take)
+        ScanBound gamma = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, wide));
         if (shadow)  // |x|^2's rounding (worst case) and the exact form's; the rest is the per-query term qeps
             gamma = {0.f, 0.f, gamma_n(ix->geom.ld / 64.0 + 10.0, 5.9604645e-8), gamma.g_ref};
         PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, kprime, cand_val, cand_pos, flags + nq));

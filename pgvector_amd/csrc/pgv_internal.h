@@ -280,10 +280,18 @@ namespace pgv {
 //   worst case     deterministic (Higham, Accuracy and Stability of Numerical Algorithms, Lemma 3.1 / eq. 3.5: a sum of n
 //                  rounded products in ANY order errs by at most gamma_n sum |a_i b_i|, gamma_n = n u / (1 - n u)), with
 //                  u = 2^-24 per operation: the matrix pipeline rounds products and accumulator additions to nearest,
-//                  which tests/test_gpu_round4.py pins on the hardware (half-way cases through both MFMA shapes):
-//                    g_dot   gamma_(dim/4 + 4): the kernel keeps FOUR independent accumulators per output, each adds
-//                            dim / 4 products (Cauchy-Schwarz: sum |q_i x_i| <= |q||x|), two more additions join them
-//                            and the final fma(-2, dot, |x|^2) rounds once
+//                  which tests/test_gpu_round4.py pins on the hardware (half-way cases through both MFMA shapes);
+//                  which element joins which chain in what order, in every form, is restated by tests/chain_model.py
+//                  and pinned bit for bit (fp32) by tests/test_gpu_scan_band.py and tests/mp_scan_band_worker.py, which
+//                  also attack the band with rows whose error reaches ~0.9 of the g_dot term in either direction:
+//                    g_dot   gamma_(chain + 4): the kernel keeps FOUR independent accumulators per output, each adds at
+//                            most `chain` products (Cauchy-Schwarz: sum |q_i x_i| <= |q||x|), at most three more
+//                            additions join them and the final fma(-2, dot, |x|^2) rounds once.  `chain` is
+//                            scan_chain_length() / dense_chain_length(): dim / 4 for fp32 rows in the four-chain forms;
+//                            for fp16 rows a chain takes whole instructions of 16 (32-query form) or 32 (16-wide form:
+//                            chain c + 2 x slice parity) products, so with S = ceil(dim / 64) slices it holds up to
+//                            max(16 S, 32 ceil(S / 2)) of them -- 32 at 64-d, where dim / 4 would say 16; the 64-query
+//                            form and mfma_dense_kernel keep quarters of whole slices (32 or 64 products each)
 //                    g_norm  gamma_(dim/64 + 10): row_norms_kernel's per-lane chains of dim / 64 fmas + 6 shuffle
 //                            additions, + the final fma
 //                    g_ref   2 gamma_(dim + 2): the exact form sum((q - x)^2) that decides among the candidates (here
@@ -299,7 +307,9 @@ namespace pgv {
 //   every row whose 4th value was inside (10 % of 3072-d rows: 32 -> 123 ms).  Measured (profiles/r06/assign_bounds.md):
 //   worst case over statistical +4 % (1 M x 1000 x 1536 fp32), +10 % (1.25 M x 4096 x 3072 fp16), redo 0 - 0.06 %.
 //   One unit roundoff per product of the chain is what the bound charges; tools/mfma_numerics.py shows the fp32 matrix
-//   instructions to BE an fmaf chain bit for bit and the fp16 ones to lose at most 3.2 u per 16 products (charged: 16 u).
+//   instructions to BE an fmaf chain bit for bit and the fp16 ones to lose at most 3.2 u per 16 products on random
+//   inputs; swamping inputs (every product half an ulp of the accumulator) reach about 5 u per 16 on an MI355X
+//   (profiles/r08_scan_band.md) -- charged: 16 u.
 //
 // The fp16 residual shadow (kernels_shadow.hip) -- the list scan of an fp32 L2 index over a shadow row
 // rho~ = fp16((x - c_l) 2^-s) and a cast query q^ = 2^s_q fp16(q 2^-s_q) computes
@@ -310,8 +320,8 @@ namespace pgv {
 //     representation   2 (|q| E + |q - q^| P):  q.rho - q^.(2^s rho~) = q.(rho - 2^s rho~) + (q - q^).(2^s rho~)
 //                      (E = max |rho - 2^s rho~|, P = max |2^s rho~|, measured over the index's rows in fp64)
 //     matrix cores     g_dot 2 |q^| P, g_dot = gamma_(chain + 4): fp16 products are exact in fp32, each of the four
-//                      accumulator chains adds at most `chain` of them (shadow_chain_length; the instructions lose at
-//                      most 3.2 u per 16 products, charged u per product), two additions join the chains
+//                      accumulator chains adds at most `chain` of them (shadow_chain_length; the instructions lose
+//                      about 5 u per 16 products at worst, see above, charged u per product), two additions join them
 //     pair term        gamma_(ceil(ld / 64) + 6) 2 |q| max|c|: shadow_pair_kernel's per-lane fmaf chain + 6 shuffle
 //                      additions; max|c| from center_norms[nlists] (itself within gamma_(ld / 64 + 10))
 //     epilogue         4 u (|x|^2 + |t| + 2 |q^| P): the addition |x|^2 + t and the final fmaf round once each
@@ -327,6 +337,8 @@ struct ShadowTerms {  // shadow_query_kernel's inputs
     double g_dot, g_pair, g_cn;  // g_cn: relative error of the stored largest |x|^2 / |c|^2
 };
 inline float gamma_n(double n, double v) { return (float)(n * v / (1.0 - n * v)); }
+// (the callers go through scan_bound_chain: this is the part that does not depend on the kernel form, and the g_dot of
+// fp32 rows in the four-chain forms)
 inline ScanBound scan_bound(const pgv_ctx *ctx, int dim) {
     if (ctx->bound_mode == 0) return {8.f * std::sqrt((float)dim + 4.f) * 5.9604645e-8f, 0.f, 0.f, 0.f};
     constexpr double v = 5.9604645e-8;  // 2^-24: round to nearest (tests/test_gpu_round4.py)
@@ -472,6 +484,7 @@ int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, co
                         const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words);
 int shadow_scale_of(float max_abs);  // s of the largest |x_i - c_i|
 int shadow_chain_length(const RowGeom &g16);  // kernels_mfma.hip: products per accumulator chain of any scan form, at most
+int scan_chain_length(const RowGeom &g, pgv_dtype dtype, bool wide);  // ... of a plain scan: the forms a launch may use
 int launch_shadow_query(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *queries, int nq,
                         const ShadowTerms &st, const float *center_norm_max, const float *row_norm_max, void *qcast,
                         float *qscale, float *qeps);
