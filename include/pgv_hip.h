@@ -185,9 +185,12 @@ typedef struct pgv_stats
 	 * over the probed part of the index would stream (scan_rows / scan_unique_rows = passes) */
 	double		scan_unique_rows;
 	/* L2 batches scanned on the matrix cores: queries whose k' candidates could not be proven to hold
-	 * the whole head and took the exact pass over their segment as well */
+	 * the whole head and took the exact pass over their segment as well.  The batch's center ranking
+	 * (pgv_rank_lists / pgv_search_batch: maxprobes + 16 candidates of the centers, on the fp16 center
+	 * shadow where the index has one) counts here too: a query appears once per half that flagged it */
 	double		scan_redo_queries;
-	/* ... and those that a wider candidate set (256 instead of k') did settle, without the exact pass */
+	/* ... and those that a wider candidate set (256 instead of k') did settle, without the exact pass
+	 * (list scan and center ranking alike) */
 	double		scan_widened_queries;
 	/* fp32 L2 batches scanned on the matrix cores: queries whose pre-filter read the fp16 residual shadow
 	 * of the index instead of its fp32 rows (counted whether or not profiling is on) */

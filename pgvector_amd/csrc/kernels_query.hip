@@ -75,6 +75,73 @@ __device__ __forceinline__ float group_distance(const char *row, const char *qp,
     return finish<METRIC>(group_sum_to_last(acc0 + acc1, lg));
 }
 
+// group_distance<float, 0> and, over the same loads, the inner product q.row in two accumulators of its own (the pair
+// terms of the shadow scan, pgv_internal.h: pair_chain_length).  The chain of sum((q - x)^2) is group_distance's
+// operation for operation: its value does not change by a bit.
+__device__ __forceinline__ float group_distance_dot(const char *row, const char *qp, int nvec, int lane_in, int lg, float *dot) {
+    const int lpr = 1 << lg;
+    float acc0 = 0.f, acc1 = 0.f, dot0 = 0.f, dot1 = 0.f;
+    int v = lane_in;
+    for (; v + lpr < nvec; v += 2 * lpr) {
+        const Raw16 a0 = load16(row + (size_t)v * sizeof(Raw16));
+        const Raw16 a1 = load16(row + (size_t)(v + lpr) * sizeof(Raw16));
+        const Raw16 q0 = load16(qp + (size_t)v * sizeof(Raw16));
+        const Raw16 q1 = load16(qp + (size_t)(v + lpr) * sizeof(Raw16));
+        acc0 = accum_slice<float, 0>(acc0, a0, q0);
+        acc1 = accum_slice<float, 0>(acc1, a1, q1);
+        dot0 = accum_slice<float, 1>(dot0, a0, q0);
+        dot1 = accum_slice<float, 1>(dot1, a1, q1);
+    }
+    if (v < nvec) {
+        const Raw16 a0 = load16(row + (size_t)v * sizeof(Raw16)), q0 = load16(qp + (size_t)v * sizeof(Raw16));
+        acc0 = accum_slice<float, 0>(acc0, a0, q0);
+        dot0 = accum_slice<float, 1>(dot0, a0, q0);
+    }
+    *dot = group_sum_to_last(dot0 + dot1, lg);
+    return finish<0>(group_sum_to_last(acc0 + acc1, lg));
+}
+
+// score_rows<float, 0, 0> with q.row of every row to out_dot[j] beside the distance
+template <typename RowPtr>
+__device__ __forceinline__ void score_rows_dot(RowPtr row_ptr, int64_t first, int64_t end, const char *qp, int nvec, int lg,
+                                               float *out, float *out_dot) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    const int rpw = kWave >> lg;  // rows per wavefront step
+    const int g = lane >> lg, lane_in = lane & ((1 << lg) - 1);
+    for (int64_t j0 = first + (int64_t)wave * rpw; j0 < end; j0 += (int64_t)kQWaves * rpw) {
+        const int64_t j = j0 + g;
+        const bool valid = j < end;
+        float dot;
+        const float d = group_distance_dot(row_ptr(valid ? j : end - 1), qp, nvec, lane_in, lg, &dot);
+        if (valid && lane_in == (1 << lg) - 1) {
+            out[j] = d;
+            out_dot[j] = dot;
+        }
+    }
+}
+
+// t = -2 q.row of the k rows a query's output row names (slot < 0: none, t = 0), one wavefront per row with
+// shadow_pair_kernel's chain: a flagged query of the ranking, whose lists batch_fix_kernel has just decided
+__device__ __forceinline__ void fill_pair_terms(const char *vectors, size_t row_bytes, const char *qrow, int ld,
+                                                const int32_t *slots_i32, const int64_t *slots_i64, int k,
+                                                float *__restrict__ pair_t) {
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int i = threadIdx.x >> 6; i < k; i += kQWaves) {
+        // (written by this workgroup's other wavefronts a moment ago, before a barrier: agent-scope loads)
+        const int64_t slot = slots_i32 ? (int64_t)__hip_atomic_load(slots_i32 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                       : __hip_atomic_load(slots_i64 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        float a = 0.f;
+        if (slot >= 0) {
+            const float *x = reinterpret_cast<const float *>(qrow);
+            const float *c = reinterpret_cast<const float *>(vectors + (size_t)slot * row_bytes);
+            for (int e = lane; e < ld; e += kWave) a = fmaf(x[e], c[e], a);
+            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+        }
+        if (lane == 0) pair_t[i] = -2.f * a;
+    }
+}
+
 // rows [first, end) given by a functor row_ptr(j) -> const char*, distances to out[j]
 template <typename T, int METRIC, int NCH, typename RowPtr>
 __device__ __forceinline__ void score_rows(RowPtr row_ptr, int64_t first, int64_t end, const char *qp, int nvec, int lg,
@@ -327,7 +394,10 @@ __global__ __launch_bounds__(kQThreads) void mq_head_kernel(
 // unless no row outside the candidates can belong to the head.
 constexpr int kRecheckCap = 256;  // k' <= 256: rank_sort_entries' reach
 
-template <typename T>
+// DOT (fp32 rows; the center ranking in front of a shadow scan): q.row is accumulated beside the exact distance over the
+// same loads, and the threads that emit the k rows also write t = -2 q.row to pair_t[q * k + rank] -- the pair terms of
+// the list scan that follows, in probe order, for one more accumulator instead of a kernel of 10 240 dot products
+template <typename T, bool DOT = false>
 __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     const char *__restrict__ vectors, const uint64_t *__restrict__ tids, int nvec, int lg,
     const char *__restrict__ queries, int kprime, int k, const float *__restrict__ approx_val,
@@ -337,8 +407,10 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     const int64_t *__restrict__ seg_start, int64_t fixed_len,
     const unsigned *__restrict__ row_norm_max, ScanBound bound, const float *__restrict__ eps_add, int nq,
     float *__restrict__ out_dist, int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid,
-    int32_t *__restrict__ out_i32, int32_t *__restrict__ flags) {
+    int32_t *__restrict__ out_i32, int32_t *__restrict__ flags, float *__restrict__ pair_t) {
+    static_assert(!DOT || std::is_same<T, float>::value, "pair terms: fp32 rows");
     __shared__ float exact[kRecheckCap];
+    __shared__ float dots[DOT ? kRecheckCap : 1];
     __shared__ __attribute__((aligned(16))) unsigned long long ent[kRecheckCap];
     const int q = blockIdx.x;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
@@ -401,8 +473,12 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
         slots[threadIdx.x] = slot;
     }
     __syncthreads();
-    score_rows<T, 0, 0>([&](int64_t j) { return vectors + (size_t)slots[j] * row_bytes; }, 0, cnt,
-                        queries + (size_t)q * row_bytes, nvec, lg, exact);
+    if constexpr (DOT)
+        score_rows_dot([&](int64_t j) { return vectors + (size_t)slots[j] * row_bytes; }, 0, cnt,
+                       queries + (size_t)q * row_bytes, nvec, lg, exact, dots);
+    else
+        score_rows<T, 0, 0>([&](int64_t j) { return vectors + (size_t)slots[j] * row_bytes; }, 0, cnt,
+                            queries + (size_t)q * row_bytes, nvec, lg, exact);
     __syncthreads();
     if ((int)threadIdx.x < kRecheckCap)
         ent[threadIdx.x] = (int)threadIdx.x < cnt
@@ -430,6 +506,7 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
         if (out_slot) out_slot[o] = my_slot;
         if (out_i32) out_i32[o] = (int32_t)my_slot;
         if (out_tid) out_tid[o] = tids ? tids[my_slot] : ~0ull;
+        if constexpr (DOT) pair_t[o] = -2.f * dots[threadIdx.x];
     }
     if ((int)threadIdx.x >= kk && (int)threadIdx.x < k) {  // fewer tuples than the head asked for
         const size_t o = (size_t)q * k + threadIdx.x;
@@ -437,6 +514,7 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
         if (out_slot) out_slot[o] = -1;
         if (out_i32) out_i32[o] = -1;
         if (out_tid) out_tid[o] = ~0ull;
+        if constexpr (DOT) pair_t[o] = 0.f;
     }
     if (threadIdx.x == 0) {
         // the band reaches the end of the candidates and there are rows beyond them: one of those may be in it too
@@ -466,7 +544,7 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
     const int32_t *__restrict__ flags, int nq, float *__restrict__ seg_vals, int k, int kp, int cap,
     const unsigned *__restrict__ row_norm_max, ScanBound bound, const float *__restrict__ eps_add, int widen,
     float *__restrict__ out_dist, int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid,
-    int32_t *__restrict__ out_i32, double *__restrict__ stats) {
+    int32_t *__restrict__ out_i32, double *__restrict__ stats, float *__restrict__ pair_t) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);  // [cap >= max(kp, kWide)]
     SelShared *sel = reinterpret_cast<SelShared *>(smem + (size_t)cap * 8);
@@ -496,6 +574,18 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
         };
         float *v = seg_vals + base;
         const char *qrow = queries + (size_t)q * row_bytes;
+        // pair_t (fp32 rows; the ranking in front of a shadow scan): the pair terms of the output row this workgroup
+        // writes -- batch_recheck_kernel's were those of the lists it emitted, which are being replaced
+        auto pair_terms = [&]() {
+            if constexpr (std::is_same<T, float>::value) {
+                if (pair_t) {
+                    __threadfence();
+                    __syncthreads();
+                    fill_pair_terms(vectors, row_bytes, qrow, nvec * 4, out_i32 ? out_i32 + (size_t)q * k : nullptr,
+                                    out_slot ? out_slot + (size_t)q * k : nullptr, k, pair_t + (size_t)q * k);
+                }
+            }
+        };
         bool settled = false;
         if (widen && k <= kWide / 2) {
             // (1) the kWide smallest approximate values, ascending by (value, position)
@@ -557,6 +647,7 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
                     if (out_tid) out_tid[o] = ~0ull;
                 }
                 if (stats && threadIdx.x == 0) atomicAdd(&stats[7], 1.0);  // profiling: settled by the wider candidate set
+                pair_terms();
             }
             __syncthreads();  // ent / exact / slots are reused
         }
@@ -578,6 +669,7 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
             if (out_i32) out_i32[(size_t)q * k + i] = (int32_t)slot;
             if (out_tid) out_tid[(size_t)q * k + i] = (have && tids) ? tids[slot] : ~0ull;
         }
+        pair_terms();
         __syncthreads();  // ent / sel are reused by the next flagged query
     }
 }
@@ -786,19 +878,23 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                          const float *approx_val, const int64_t *cand_pos, const int64_t *cand_slot,
                          const int64_t *seg_start, int64_t fixed_len, const ScanBound &bound,
                          float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags, int32_t *out_i32,
-                         const int32_t *probe_lists, const int64_t *probe_off, int probes, const float *eps_add) {
+                         const int32_t *probe_lists, const int64_t *probe_off, int probes, const float *eps_add,
+                         float *pair_t) {
     if (nq <= 0) return PGV_OK;
     if (kprime > kRecheckCap || k > kprime) PGV_FAIL(PGV_ERR_ARG, "recheck: k' = %d outside k..%d", kprime, kRecheckCap);
-#define PGV_RECHECK(T)                                                                                              \
-    hipLaunchKernelGGL(batch_recheck_kernel<T>, dim3(nq), dim3(kQThreads), 0, ctx->stream,                           \
+    if (pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "recheck: pair terms are for fp32 rows");
+#define PGV_RECHECK(T, DOT)                                                                                         \
+    hipLaunchKernelGGL((batch_recheck_kernel<T, DOT>), dim3(nq), dim3(kQThreads), 0, ctx->stream,                    \
                        static_cast<const char *>(xr.vectors), xr.tids, xr.geom.nvec, xr.geom.lpr_log2,               \
                        static_cast<const char *>(q_dev), kprime, k, approx_val, cand_pos, cand_slot, xr.list_offsets, \
                        probe_lists, probe_off, probes, seg_start, fixed_len, xr.norm_max, bound, eps_add, nq, out_dist, out_slot,  \
-                       out_tid, out_i32, flags)
-    if (xr.dtype == PGV_F32)
-        PGV_RECHECK(float);
+                       out_tid, out_i32, flags, pair_t)
+    if (pair_t)
+        PGV_RECHECK(float, true);
+    else if (xr.dtype == PGV_F32)
+        PGV_RECHECK(float, false);
     else
-        PGV_RECHECK(__half);
+        PGV_RECHECK(__half, false);
 #undef PGV_RECHECK
     PGV_HIP(hipGetLastError());
     return PGV_OK;
@@ -807,9 +903,11 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
 int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
                      const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
                      const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32, const float *eps_add) {
+                     uint64_t *out_tid, int32_t *out_i32, const float *eps_add, float *pair_t) {
     if (nq <= 0) return PGV_OK;
-    double *stats = (ctx->profiling && ctx->stats_dev.p && probe_lists) ? ctx->stats_dev.as<double>() : nullptr;
+    if (pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "fix: pair terms are for fp32 rows");
+    // (the ranking's flagged queries count like the list scan's: pgv_stats scan_widened_queries / scan_redo_queries)
+    double *stats = (ctx->profiling && ctx->stats_dev.p) ? ctx->stats_dev.as<double>() : nullptr;
     if (k > 4096) PGV_FAIL(PGV_ERR_ARG, "top-k: k = %d exceeds the supported 4096", k);
     int kp = 2;
     while (kp < k) kp <<= 1;
@@ -822,7 +920,7 @@ int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int n
                        static_cast<const char *>(xr.vectors), xr.list_offsets, xr.tids, xr.geom.nvec,                \
                        xr.geom.lpr_log2, static_cast<const char *>(q_dev), probe_lists, probe_off, probes, seg_start, \
                        fixed_len, flags, nq, seg_vals, k, kp, cap, xr.norm_max, bound, eps_add, widen, out_dist,      \
-                       out_slot, out_tid, out_i32, stats)
+                       out_slot, out_tid, out_i32, stats, pair_t)
     if (xr.dtype == PGV_F32)
         PGV_FIX(float);
     else

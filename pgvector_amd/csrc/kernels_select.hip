@@ -95,7 +95,8 @@ __global__ void plan_pairs_kernel(const int32_t *__restrict__ probe_lists,
                                   const int64_t *__restrict__ probe_off,
                                   const int64_t *__restrict__ seg_start,
                                   const int64_t *__restrict__ pair_start, int *__restrict__ fill,
-                                  int nq, int probes, ScanPair *__restrict__ pairs) {
+                                  int nq, int probes, const float *__restrict__ pair_t,
+                                  ScanPair *__restrict__ pairs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)nq * probes) return;
     const int q = (int)(i / probes);
@@ -104,7 +105,8 @@ __global__ void plan_pairs_kernel(const int32_t *__restrict__ probe_lists,
     ScanPair pr;
     pr.out_rel = seg_start[q] + probe_off[i] - list_off[l];
     pr.query = q;
-    pr.pad = 0;
+    // the shadow scan's t = -2 q.c_l of the pair, where the ranking computed it ([nq x probes], probe order: i)
+    pr.pad = pair_t ? (int32_t)__float_as_uint(pair_t[i]) : 0;
     pairs[pos] = pr;
 }
 
@@ -294,7 +296,7 @@ int launch_cast_pos_to_i32(pgv_ctx *ctx, const int64_t *pos, int64_t n, int32_t 
 }
 
 int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists, int nq,
-                      int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res) {
+                      int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res, const float *pair_t) {
     const int nlists = ix->nlists;
     const size_t npairs = (size_t)nq * probes;
 
@@ -338,7 +340,7 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
                        pair_start, task_start, totals);
     hipLaunchKernelGGL(plan_pairs_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0,
                        ctx->stream, probe_lists, ix->list_offsets, probe_off, seg_start,
-                       pair_start, fill, nq, probes, ctx->pairs.as<ScanPair>());
+                       pair_start, fill, nq, probes, pair_t, ctx->pairs.as<ScanPair>());
     {
         const int64_t want = (res->ntasks_bound + 255) / 256;
         const int64_t cap = (int64_t)ctx->num_cus * 8;

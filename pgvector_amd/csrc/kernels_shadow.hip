@@ -43,19 +43,19 @@ __device__ __forceinline__ int scale_for(float m) {
     return e - 14;
 }
 
-// pass 1: the largest |x_i - c_i| over the index (bits of a non-negative float: integer order is float order)
+// pass 1: the largest |x_i - c_i| over the index (bits of a non-negative float: integer order is float order).
+// centers == null: the rows are cast as they are (c = 0; the shadow of the centers themselves, launch_shadow_build)
 __global__ __launch_bounds__(256) void shadow_absmax_kernel(const float *__restrict__ rows, const float *__restrict__ centers,
                                                             const int64_t *__restrict__ list_off, int nlists, int64_t n,
                                                             int ld, unsigned *__restrict__ max_bits) {
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n) return;
     const int lane = threadIdx.x & (kWave - 1);
-    const int l = list_of_row(list_off, nlists, r);
     const float *x = rows + (size_t)r * ld;
-    const float *c = centers + (size_t)l * ld;
+    const float *c = centers ? centers + (size_t)list_of_row(list_off, nlists, r) * ld : nullptr;
     float m = 0.f;
     for (int i = lane; i < ld; i += kWave) {
-        const float d = fabsf(x[i] - c[i]);
+        const float d = fabsf(c ? x[i] - c[i] : x[i]);
         m = (d > m || d != d) ? d : m;  // (NaN is kept: its bits compare above every number)
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -77,19 +77,19 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n) return;
     const int lane = threadIdx.x & (kWave - 1);
-    const int l = list_of_row(list_off, nlists, r);
     const int s = scale_for(__uint_as_float(*max_bits));
     const float *x = rows + (size_t)r * ld;
-    const float *c = centers + (size_t)l * ld;
+    const float *c = centers ? centers + (size_t)list_of_row(list_off, nlists, r) * ld : nullptr;
     __half *h = shadow + (size_t)r * ld16;
     const double up = ldexp(1.0, s);  // (exact: |s| stays far inside fp64's exponent range)
     double e2 = 0.0, p2 = 0.0;
     for (int i = lane; i < ld16; i += kWave) {
         __half v = __float2half(0.f);
         if (i < ld) {
-            v = __float2half(ldexpf(x[i] - c[i], -s));
+            const float ci = c ? c[i] : 0.f;
+            v = __float2half(ldexpf(x[i] - ci, -s));
             const double back = (double)__half2float(v) * up;
-            const double d = ((double)x[i] - (double)c[i]) - back;
+            const double d = ((double)x[i] - (double)ci) - back;
             e2 = fma(d, d, e2);
             p2 = fma(back, back, p2);
         }
@@ -111,12 +111,16 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
 
 // One wavefront per query: the fp16 query row 2^-s_q q (scale per query), the epilogue's factor 2^(1 + s + s_q), and
 // the additive term of the rounding band that the shadow adds (pgv_internal.h, ScanBound).  The terms are formed in
-// fp64 and rounded up into fp32.
+// fp64 and rounded up into fp32.  One cast serves both consumers of a batch: cscale / ceps (null: not wanted) are the
+// factor 2^(1 + s_c + s_q) and the band term of the center ranking over the centers' shadow (RankShadowTerms), qscale /
+// qeps (null: not wanted) those of the list scan.
 __global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restrict__ queries, int nq, int ld, int ld16,
-                                                           ShadowTerms st, const float *__restrict__ center_norm_max,
+                                                           ShadowTerms st, RankShadowTerms rt,
+                                                           const float *__restrict__ center_norm_max,
                                                            const float *__restrict__ row_norm_max,
                                                            __half *__restrict__ qcast, float *__restrict__ qscale,
-                                                           float *__restrict__ qeps) {
+                                                           float *__restrict__ qeps, float *__restrict__ cscale,
+                                                           float *__restrict__ ceps) {
     const int q = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (q >= nq) return;
     const int lane = threadIdx.x & (kWave - 1);
@@ -150,12 +154,26 @@ __global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restri
         dd += __shfl_xor(dd, o);
         hh += __shfl_xor(hh, o);
     }
-    if (lane == 0) {
+    const double u = 5.9604644775390625e-8;
+    if (lane == 0 && ceps) {
+        // the center ranking: a = |c|^2 - 2^(1 + s_c + s_q) acc for s = |c|^2 - 2 q.c; |c|^2's own rounding is the
+        // ScanBound's g_norm term, no pair term
+        const int e = 1 + rt.s + sq;
+        const double qn = sqrt(qq), dq = sqrt(dd), qh = sqrt(hh);
+        const double cn = (double)*center_norm_max * (1.0 + rt.g_cn);
+        double eps = 2.0 * (qn * rt.E + dq * rt.P)                       // representation of centers and query in fp16
+                     + rt.g_dot * 2.0 * qh * rt.P                        // fp16 products, fp32 chains of the matrix cores
+                     + 4.0 * u * (cn + 2.0 * qh * rt.P * (1.0 + rt.g_dot));  // epilogue: the final fmaf (|c|^2 + 0 is exact)
+        eps = eps * (1.0 + 1.0 / 1048576.0) + 4.0 * (double)FLT_MIN;
+        if (e < -125 || e > 125 || !(eps < 1e30)) eps = INFINITY;
+        cscale[q] = ldexpf(1.f, e < -125 ? 0 : (e > 125 ? 0 : e));
+        ceps[q] = (float)eps;
+    }
+    if (lane == 0 && qeps) {
         const int e = 1 + st.s + sq;
         const double qn = sqrt(qq), dq = sqrt(dd), qh = sqrt(hh);
         const double cmax = sqrt((double)*center_norm_max * (1.0 + st.g_cn)), rn = (double)*row_norm_max * (1.0 + st.g_cn);
         const double tmax = 2.0 * qn * cmax;  // |t| of every pair of this query (exact value)
-        const double u = 5.9604644775390625e-8;
         double eps = 2.0 * (qn * st.E + dq * st.P)               // representation of rows and query in fp16
                      + st.g_dot * 2.0 * qh * st.P                // fp16 products, fp32 chains of the matrix cores
                      + st.g_pair * tmax                          // the pair term's fp32 chain
@@ -169,7 +187,9 @@ __global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restri
 }
 
 // One wavefront per probed (query, list) pair: t = -2 q.c_l into the pair's free word.  Each lane runs ONE fmaf chain
-// over ceil(ld / 64) elements, then six shuffle additions: gamma_(ceil(ld / 64) + 6) |q||c_l| (ShadowTerms::g_pair).
+// over ceil(ld / 64) elements, then six shuffle additions: gamma_(ceil(ld / 64) + 6) |q||c_l| (ShadowTerms::g_pair,
+// pair_chain_length).  For probe lists that did not come from this batch's own ranking (pgv_scan_batch, the sharded
+// search): pgv_search_batch takes t from the ranking's exact recheck instead (batch_recheck_kernel, pair_t).
 __global__ __launch_bounds__(256) void shadow_pair_kernel(const float *__restrict__ queries, const float *__restrict__ centers,
                                                           const int64_t *__restrict__ pair_start, int nlists, int64_t npairs,
                                                           int ld, ScanPair *__restrict__ pairs) {
@@ -198,6 +218,7 @@ __global__ __launch_bounds__(256) void shadow_pair_kernel(const float *__restric
 int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *rows, const void *centers,
                         const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words) {
     if (n <= 0) return PGV_OK;
+    // (centers null: the rows themselves are cast -- the shadow of an index's centers, E_c and P_c in the same words)
     // words: [0] max |rho_i| bits (u32) | [1..2] E^2, P^2 bits (u64 at byte 8)
     PGV_HIP(hipMemsetAsync(words, 0, 24, ctx->stream));
     unsigned *max_bits = static_cast<unsigned *>(words);
@@ -219,12 +240,12 @@ int shadow_scale_of(float max_abs) {
 }
 
 int launch_shadow_query(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *queries, int nq,
-                        const ShadowTerms &st, const float *center_norm_max, const float *row_norm_max, void *qcast,
-                        float *qscale, float *qeps) {
+                        const ShadowTerms &st, const RankShadowTerms &rt, const float *center_norm_max,
+                        const float *row_norm_max, void *qcast, float *qscale, float *qeps, float *cscale, float *ceps) {
     if (nq <= 0) return PGV_OK;
     hipLaunchKernelGGL(shadow_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream,
-                       static_cast<const float *>(queries), nq, g32.ld, g16.ld, st, center_norm_max, row_norm_max, static_cast<__half *>(qcast),
-                       qscale, qeps);
+                       static_cast<const float *>(queries), nq, g32.ld, g16.ld, st, rt, center_norm_max, row_norm_max,
+                       static_cast<__half *>(qcast), qscale, qeps, cscale, ceps);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -203,7 +203,8 @@ int resolve_events(pgv_ctx *ctx) {
 // --------------------------------------------------- dense scan (host-planned)
 // rows [0, nrows) x queries [0, nq): out[q * out_stride + r].  Used for center
 // ranking, exact scans and k-means++ rounds; tasks are planned on the host since
-// their shape depends only on sizes.
+// their shape depends only on sizes.  shadow_scale (mfma, fp16 L2): the shadow form of the kernel over a center
+// shadow and cast queries -- the plan's pairs carry pad = 0, so t = 0 and the value is |c|^2 - shadow_scale[q] acc.
 int rows_per_task_for(pgv_ctx *ctx, int64_t total_rows, int64_t groups) {
     // aim at >= 8 tasks per CU, 32..256 rows each
     int64_t want_tasks = (int64_t)ctx->num_cus * 8;
@@ -226,7 +227,7 @@ static bool dense_keep() {
 int dense_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
                const void *rows_dev, int64_t nrows, const void *queries_dev, int nq,
                int64_t out_stride, float *out_dev, bool mfma = false, const float *row_norms = nullptr,
-               const float *query_norms = nullptr) {
+               const float *query_norms = nullptr, const float *shadow_scale = nullptr) {
     if (nrows <= 0 || nq <= 0) return PGV_OK;
     // one query against contiguous rows (a k-means++ round, pgv_distance_batch): no plan, no task counter -- the
     // single-query path's streaming kernel, whole rows in flight (k-means of the headline build: 0.137 -> 0.104 s)
@@ -306,7 +307,7 @@ int dense_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &
     PGV_TRY(timer.begin((double)nrows * nq, (double)nrows * ngroups, true));
     if (mfma)
         PGV_TRY(launch_mfma_scan(ctx, metric, dtype, g, rows_dev, queries_dev, dt, dn, (int)ntasks, dp, row_norms,
-                                 query_norms, out_dev, rows_stream_past_caches(g, dtype, nrows)));
+                                 query_norms, out_dev, rows_stream_past_caches(g, dtype, nrows), qt, shadow_scale));
     else if (use_tile)
         PGV_TRY(launch_tile_scan(ctx, metric, dtype, g, rows_dev, queries_dev, dt, dn, (int)ntasks, dp, out_dev));
     else

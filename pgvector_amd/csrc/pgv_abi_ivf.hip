@@ -63,9 +63,20 @@ int shadow_env() {
     return e ? atoi(e) : -1;
 }
 
+// PGV_RANK_SHADOW: how a batch of an index with a center shadow is ranked and where its shadow scan's pair terms come from
+//   0      the fp32 centers rank, shadow_pair_kernel computes t (the path before the center shadow)
+//   1      (default) the fp16 center shadow ranks, the ranking's exact recheck hands t on
+//   2      the fp16 center shadow ranks, shadow_pair_kernel computes t (tests: both routes of t on one ranking)
+// Read at every batch: A/B runs on one build, and tests that compare the paths in one process tree
+int rank_shadow_env() {
+    const char *e = getenv("PGV_RANK_SHADOW");
+    return e ? atoi(e) : 1;
+}
+
 // The fp16 residual shadow of an fp32 L2 index (kernels_shadow.hip; the bound: pgv_internal.h, ScanBound), built once
 // with the index -- its rows never change afterwards.  Its own allocation (+50 % of the fp32 row bytes), outside the
-// exportable arena; no device memory for it is no error: the list scan keeps the fp32 rows
+// exportable arena; no device memory for it is no error: the list scan keeps the fp32 rows.  The same allocation holds
+// the fp16 copy of the centers that the batch ranking multiplies: rows | 256 bytes of words | centers
 int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
     const int env = shadow_env();
     if (env == 0 || ix->metric != PGV_L2SQ || ix->dtype != PGV_F32 || ix->nrows <= 0 || !ix->row_norms || !ix->center_norms)
@@ -73,15 +84,21 @@ int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
     if (env < 0 && !rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows)) return PGV_OK;
     const RowGeom g16 = row_geom(ix->dim, PGV_F16);
     const size_t bytes = ((size_t)ix->nrows * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
+    const size_t cbytes = ((size_t)ix->nlists * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
     void *sh = nullptr;
-    if (hipMalloc(&sh, bytes + 256) != hipSuccess) {
+    if (hipMalloc(&sh, bytes + 256 + cbytes) != hipSuccess) {
         (void)hipGetLastError();
         return PGV_OK;
     }
-    void *words = static_cast<char *>(sh) + bytes;  // [0] max |x_i - c_i| | [8] E^2 | [16] P^2
+    // [0] max |x_i - c_i| | [8] E^2 | [16] P^2 of the rows; at byte 32 the same of the centers (max |c_i|, E_c^2, P_c^2)
+    void *words = static_cast<char *>(sh) + bytes;
+    void *csh = static_cast<char *>(sh) + bytes + 256;
     int rc = launch_shadow_build(ctx, ix->geom, g16, ix->vectors, ix->centers, ix->list_offsets, ix->nlists, ix->nrows, sh,
                                  words);
-    unsigned char h[24];
+    if (rc == PGV_OK)
+        rc = launch_shadow_build(ctx, ix->geom, g16, ix->centers, nullptr, nullptr, 0, ix->nlists, csh,
+                                 static_cast<char *>(words) + 32);
+    unsigned char h[56];
     if (rc == PGV_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess ||
                          hipMemcpy(h, words, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess)) {
         set_error("shadow build failed: %s", hipGetErrorString(hipGetLastError()));
@@ -108,7 +125,76 @@ int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
     ix->shadow_s = shadow_scale_of(max_abs);
     ix->shadow_E = (E + 1e-12 * (P + E)) * (1.0 + 1e-9);
     ix->shadow_P = P * (1.0 + 1e-9);
+    // the centers' copy, rounded up the same way; a non-finite E_c or P_c (NaN / inf in a center) drops it alone: the
+    // ranking stays on the fp32 centers
+    float cmax_abs;
+    double ce2, cp2;
+    memcpy(&cmax_abs, h + 32, 4);
+    memcpy(&ce2, h + 40, 8);
+    memcpy(&cp2, h + 48, 8);
+    const double Pc = std::sqrt(cp2), Ec = std::sqrt(ce2);
+    if (std::isfinite(Ec) && std::isfinite(Pc) && std::isfinite(cmax_abs)) {
+        ix->cshadow = csh;
+        ix->cshadow_s = shadow_scale_of(cmax_abs);
+        ix->cshadow_E = (Ec + 1e-12 * (Pc + Ec)) * (1.0 + 1e-9);
+        ix->cshadow_P = Pc * (1.0 + 1e-9);
+    }
     return PGV_OK;
+}
+
+// What the shadow paths of ONE batch share (ctx->sh_q): shadow_query_kernel runs once, ahead of the ranking, and serves
+// the ranking over the center shadow and the list scan over the row shadow; the ranking's recheck leaves the probed
+// pairs' t = -2 q.c_l for the scan's plan.  pgv_search_batch passes one through both halves; a half that gets none
+// (pgv_rank_lists, pgv_scan_batch, the sharded search) prepares what it needs itself.
+struct ShadowBatch {
+    void *qcast = nullptr;                     // [nq x g16.ld] fp16 queries
+    float *qscale = nullptr, *qeps = nullptr;  // the list scan's factors 2^(1 + s + s_q) and band terms
+    float *cscale = nullptr, *ceps = nullptr;  // the ranking's 2^(1 + s_c + s_q) and band terms
+    float *pair_t = nullptr;                   // [nq x probes]
+    bool scan_follows = false;                 // set by the caller: scan_batch_dev will run on the ranking's lists
+    bool cast_for_scan = false, cast_for_rank = false, pairs_done = false;
+};
+
+int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool for_rank, bool for_scan, ShadowBatch *sb) {
+    pgv_ctx *ctx = ix->ctx;
+    const RowGeom &g16 = ix->shadow_geom;
+    const size_t qb = ((size_t)nq * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
+    PGV_TRY(ctx->sh_q.ensure(qb + sizeof(float) * (size_t)nq * (4 + (size_t)probes)));
+    sb->qcast = ctx->sh_q.p;
+    sb->qscale = reinterpret_cast<float *>(ctx->sh_q.as<char>() + qb);
+    sb->qeps = sb->qscale + nq;
+    sb->cscale = sb->qeps + nq;
+    sb->ceps = sb->cscale + nq;
+    sb->pair_t = sb->ceps + nq;
+    constexpr double u = 5.9604644775390625e-8;  // 2^-24
+    ShadowTerms st{};
+    st.s = ix->shadow_s;
+    st.E = ix->shadow_E;
+    st.P = ix->shadow_P;
+    st.g_dot = gamma_n(shadow_chain_length(g16) + 4.0, u);
+    st.g_pair = gamma_n((double)pair_chain_length(ix->geom), u);
+    st.g_cn = gamma_n(ix->geom.ld / 64.0 + 10.0, u);
+    RankShadowTerms rt{};
+    rt.s = ix->cshadow_s;
+    rt.E = ix->cshadow_E;
+    rt.P = ix->cshadow_P;
+    rt.g_dot = st.g_dot;  // (dense_scan's tasks take the 32-query and 16-wide forms: shadow_chain_length covers both)
+    rt.g_cn = st.g_cn;
+    PGV_TRY(launch_shadow_query(ctx, ix->geom, g16, q_dev, nq, st, rt, ix->center_norms + ix->nlists,
+                                ix->row_norms + ix->nrows, sb->qcast, for_scan ? sb->qscale : nullptr,
+                                for_scan ? sb->qeps : nullptr, for_rank ? sb->cscale : nullptr,
+                                for_rank ? sb->ceps : nullptr));
+    sb->cast_for_scan = for_scan;
+    sb->cast_for_rank = for_rank;
+    return PGV_OK;
+}
+
+// the list scan of this batch would read the row shadow (scan_batch_impl's own conditions, known before the ranking)
+bool shadow_scan_expected(const pgv_index *ix, int nq, int probes, int k) {
+    const double share = (double)nq * probes / (double)ix->nlists;
+    const bool small = (share <= 0.4 || nq <= 4) && nq <= 1024 && probes <= query_max_batch_lists() && k <= query_head_cap();
+    return !small && share > 3.0 && k <= 192 && !ix->ctx->no_mfma_scan && ix->metric == PGV_L2SQ && ix->row_norms &&
+           ix->shadow && shadow_env() != 0;
 }
 
 // The mirror of an index whose list offsets are known: one allocation, host tables, the norms the MFMA paths want.
@@ -740,8 +826,8 @@ int pgv_index_lists(const pgv_index *ix) { return ix ? ix->nlists : -1; }
 
 
 // device-side core of GetScanLists for nq staged queries
-int rank_lists_dev(pgv_index *ix, const void *q_dev, int nq, int maxprobes,
-                          int32_t *out_lists_dev, float *out_dist_dev) {
+static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprobes,
+                           int32_t *out_lists_dev, float *out_dist_dev, ShadowBatch *sb) {
     pgv_ctx *ctx = ix->ctx;
     // distance matrix [nq x nlists], then the maxprobes smallest per row
     PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * (size_t)nq * ix->nlists));
@@ -764,26 +850,52 @@ int rank_lists_dev(pgv_index *ix, const void *q_dev, int nq, int maxprobes,
         return launch_multi_rank(ctx, ix, q_dev, nq, ctx->dist_mat.as<float>(), cd_stride, maxprobes, out_lists_dev,
                                  out_dist_dev);
     }
-    const int cand = maxprobes + 16 < ix->nlists ? maxprobes + 16 : ix->nlists;
+    int cand = maxprobes + 16 < ix->nlists ? maxprobes + 16 : ix->nlists;
+    // the fp16 center shadow (below) ranks with a band ~0.8 wide on the headline, where the bulk of the 1000 centers lies
+    // a few dozen to the unit: with 16 spare candidates 2.5 queries of 1024 a step were flagged and widened (measured,
+    // profiles/r09_step_overhead.md: their batch_fix_kernel pass cost ~25 us a step).  54 spare cost nothing -- the
+    // selection pads 10 + 16 to 32 and 10 + 54 to 64 entries, the list scan's own shape, and the recheck reads only
+    // the band's prefix
+    const int rank_env = rank_shadow_env();
+    const bool rank_sh = ix->metric == PGV_L2SQ && ix->cshadow && ix->dtype == PGV_F32 && rank_env != 0 && shadow_env() != 0;
+    if (rank_sh && maxprobes + 54 <= 256) cand = maxprobes + 54 < ix->nlists ? maxprobes + 54 : ix->nlists;
     const bool mfma = nq >= 128 && ix->nlists >= 64 && !ctx->no_mfma_scan &&
                       (ix->metric == PGV_NEG_IP || (ix->metric == PGV_L2SQ && ix->center_norms && cand <= 256));
     if (mfma && ix->metric == PGV_L2SQ) {
         ApproxScratch sc;
         PGV_TRY(sc.carve(ctx, ctx->ms_b, nq, cand));
-        PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
-                           true, ix->center_norms, nullptr));
+        // fp32 centers with an fp16 copy: the expansion only picks the candidates, so it multiplies the
+        // copy and the cast queries -- the three-stage fp16 form of the kernel, half the bytes -- and the band grows by
+        // the per-query term ceps (pgv_internal.h).  The cast runs here, once for the batch: the list scan that follows
+        // reads the same fp16 queries
+        ShadowBatch own;
+        if (!sb) sb = &own;
+        const bool scan_follows = sb->scan_follows;
+        if (rank_sh) {
+            PGV_TRY(shadow_batch_cast(ix, q_dev, nq, maxprobes, true, scan_follows, sb));
+            PGV_TRY(dense_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->cshadow, ix->nlists, sb->qcast, nq, ix->nlists,
+                               mat, true, ix->center_norms, nullptr, sb->cscale));
+        } else {
+            PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
+                               true, ix->center_norms, nullptr));
+        }
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, cand, sc.cand_val, sc.cand_pos, sc.flags + nq));
         const ExactRows xr{ix->centers, nullptr, nullptr, ix->geom, ix->dtype,
                            reinterpret_cast<const unsigned *>(ix->center_norms + ix->nlists)};
         // (dense_scan: the 32-query kernel, its 16-wide form for a last group of <= 16 queries)
-        const ScanBound bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, false));
+        ScanBound bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, false));
+        if (rank_sh)  // |c|^2's rounding (worst case) and the exact form's; the rest is the per-query term ceps
+            bound = {0.f, 0.f, gamma_n(ix->geom.ld / 64.0 + 10.0, 5.9604645e-8), bound.g_ref};
+        // the pair terms of the shadow scan that follows: q.c of the lists emitted, beside their exact distances
+        float *pair_t = (rank_sh && rank_env == 1 && scan_follows) ? sb->pair_t : nullptr;
         // a center's position in the matrix row is its id: cand_pos serves as the slots
         // the center ids leave as the int32 list ids the callers want (no conversion pass)
         PGV_TRY(launch_batch_recheck(ctx, xr, q_dev, nq, cand, maxprobes, sc.cand_val, sc.cand_pos, sc.cand_pos, nullptr,
                                      ix->nlists, bound, dist, nullptr, nullptr, sc.flags,
-                                     out_lists_dev));
+                                     out_lists_dev, nullptr, nullptr, 0, rank_sh ? sb->ceps : nullptr, pair_t));
         PGV_TRY(launch_batch_fix(ctx, xr, q_dev, nq, nullptr, nullptr, 0, nullptr, ix->nlists, sc.flags, mat, maxprobes,
-                                 bound, dist, nullptr, nullptr, out_lists_dev));
+                                 bound, dist, nullptr, nullptr, out_lists_dev, rank_sh ? sb->ceps : nullptr, pair_t));
+        sb->pairs_done = pair_t != nullptr;
         return PGV_OK;
     } else {
         PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
@@ -792,6 +904,10 @@ int rank_lists_dev(pgv_index *ix, const void *q_dev, int nq, int maxprobes,
     }
     PGV_TRY(launch_cast_pos_to_i32(ctx, pos, (int64_t)nq * maxprobes, out_lists_dev));
     return PGV_OK;
+}
+
+int rank_lists_dev(pgv_index *ix, const void *q_dev, int nq, int maxprobes, int32_t *out_lists_dev, float *out_dist_dev) {
+    return rank_lists_impl(ix, q_dev, nq, maxprobes, out_lists_dev, out_dist_dev, nullptr);
 }
 
 int pgv_rank_lists(pgv_index *ix, const void *queries, int nq, int maxprobes, int32_t *out_lists,
@@ -923,8 +1039,8 @@ static int scan_turn_end(pgv_ctx *ctx) {
     return PGV_OK;
 }
 
-int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
-                          int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid) {
+static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
+                           int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid, ShadowBatch *sb) {
     pgv_ctx *ctx = ix->ctx;
     // invert to list-major work.  Queries per list on average decides how wide a group is
     // worth.  Lists probed by more than 8 queries go to the tile kernel (16 queries per pass
@@ -977,11 +1093,19 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
     const int rows_per_task = use_mfma ? mfma_scan_rows_per_task()
                                        : (use_tile ? rpt_tiles * tile_scan_tile_rows(ix->geom)
                                                    : (qt >= 16 ? 256 : (qt >= 4 ? 128 : 64)));
-    PlanResult plan;
-    PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, qt, rows_per_task, ctx->profiling, &plan));
-
     // MFMA L2: scratch for the candidates' exact tail
     const bool approx = use_mfma && ix->metric == PGV_L2SQ;
+    // fp32 L2 with the fp16 residual shadow (kernels_shadow.hip): the scan streams half the bytes.  Per batch: the
+    // cast queries, their factors 2^(1 + s + s_q) and band terms, and every probed pair's -2 q.c_l.  A batch that
+    // pgv_search_batch ranked over the center shadow brings all three (ShadowBatch); otherwise they are made here
+    const bool shadow = approx && ix->shadow && shadow_env() != 0;
+    ShadowBatch own;
+    if (!sb) sb = &own;
+    if (shadow && !sb->cast_for_scan) PGV_TRY(shadow_batch_cast(ix, q_dev, nq, probes, false, true, sb));
+    const float *pair_t = (shadow && sb->pairs_done) ? sb->pair_t : nullptr;
+    PlanResult plan;
+    PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, qt, rows_per_task, ctx->profiling, &plan, pair_t));
+
     int kprime = k;
     ApproxScratch sc;
     if (approx) {
@@ -993,30 +1117,15 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
     float *cand_val = sc.cand_val;
     int64_t *cand_pos = sc.cand_pos;
     int32_t *flags = sc.flags;
-    // fp32 L2 with the fp16 residual shadow (kernels_shadow.hip): the scan streams half the bytes.  Per batch: the
-    // cast queries, their factors 2^(1 + s + s_q) and band terms, and every probed pair's -2 q.c_l
-    const bool shadow = approx && ix->shadow && shadow_env() != 0;
     void *qcast = nullptr;
     float *qscale = nullptr, *qeps = nullptr;
     if (shadow) {
-        const RowGeom &g16 = ix->shadow_geom;
-        const size_t qb = ((size_t)nq * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
-        PGV_TRY(ctx->sh_q.ensure(qb + 2 * sizeof(float) * (size_t)nq));
-        qcast = ctx->sh_q.p;
-        qscale = reinterpret_cast<float *>(ctx->sh_q.as<char>() + qb);
-        qeps = qscale + nq;
-        constexpr double u = 5.9604644775390625e-8;  // 2^-24
-        ShadowTerms st;
-        st.s = ix->shadow_s;
-        st.E = ix->shadow_E;
-        st.P = ix->shadow_P;
-        st.g_dot = gamma_n(shadow_chain_length(g16) + 4.0, u);
-        st.g_pair = gamma_n((ix->geom.ld + 63) / 64 + 6.0, u);
-        st.g_cn = gamma_n(ix->geom.ld / 64.0 + 10.0, u);
-        PGV_TRY(launch_shadow_query(ctx, ix->geom, g16, q_dev, nq, st, ix->center_norms + ix->nlists,
-                                    ix->row_norms + ix->nrows, qcast, qscale, qeps));
-        PGV_TRY(launch_shadow_pairs(ctx, ix->geom, q_dev, ix->centers, plan.pair_start, ix->nlists, (int64_t)nq * probes,
-                                    plan.pairs));
+        qcast = sb->qcast;
+        qscale = sb->qscale;
+        qeps = sb->qeps;
+        if (!pair_t)  // lists that did not come from this batch's ranking over the center shadow
+            PGV_TRY(launch_shadow_pairs(ctx, ix->geom, q_dev, ix->centers, plan.pair_start, ix->nlists, (int64_t)nq * probes,
+                                        plan.pairs));
         ctx->scan_shadow_queries += nq;
     }
 
@@ -1081,6 +1190,11 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
     return sync_if(ctx, need);
 }
 
+int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes, int k, float *out_dist,
+                   int64_t *out_slot, uint64_t *out_tid) {
+    return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, nullptr);
+}
+
 int check_batch_args(pgv_index *ix, const void *queries, int nq, int probes, int k, float *out_dist,
                             uint64_t *out_tid, const char *who) {
     if (!ix) PGV_FAIL(PGV_ERR_ARG, "%s: index is NULL", who);
@@ -1112,8 +1226,11 @@ int pgv_search_batch(pgv_index *ix, const void *queries, int nq, int probes, int
     // GetScanLists for the whole batch
     PGV_TRY(ctx->idx_stage.ensure(sizeof(int32_t) * (size_t)nq * probes));
     int32_t *probe_lists = ctx->idx_stage.as<int32_t>();
-    PGV_TRY(rank_lists_dev(ix, q_dev, nq, probes, probe_lists, nullptr));
-    return scan_batch_dev(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid);
+    // one query cast for the batch where both halves read fp16, and the ranking's q.c_l for the scan
+    ShadowBatch sb;
+    sb.scan_follows = shadow_scan_expected(ix, nq, probes, k);
+    PGV_TRY(rank_lists_impl(ix, q_dev, nq, probes, probe_lists, nullptr, &sb));
+    return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, &sb);
 }
 
 int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *probe_lists, int probes, int k,

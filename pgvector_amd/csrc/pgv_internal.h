@@ -113,7 +113,9 @@ struct pgv_ctx {
     int dense_plan_nq = -1, dense_plan_kind = -1;
     bool counters_clean = false;  // ctx->counters starts zeroed; mfma_scan_kernel leaves its words zero again
     pgv::DBuf ms_a;  // MFMA list scan: query norms | candidate values, positions, slots | flags
-    pgv::DBuf sh_q;  // the shadow list scan (kernels_shadow.hip): cast queries | their factors | their band terms
+    // the shadow paths of a batch (kernels_shadow.hip): cast queries | list-scan factors, band terms | ranking factors,
+    // band terms | the probed pairs' t = -2 q.c_l in probe order (written by the ranking's exact recheck)
+    pgv::DBuf sh_q;
     pgv::DBuf mf_d;  // MFMA assignment split over center parts: the parts' candidates per row
     pgv::DBuf mf_a, mf_b, mf_c, zeros;  // MFMA assignment: norms, pre-filter candidates, redo list; 16 zero bytes
     pgv::DBuf stats_dev;  // profiling: {pairs, rows streamed} of the batched list scans, as doubles
@@ -177,6 +179,12 @@ struct pgv_index {
     int shadow_s = 0;
     double shadow_E = 0.0;            // max over rows |(x - c_l) - 2^s shadow|, rounded up
     double shadow_P = 0.0;            // max over rows |2^s shadow|, rounded up
+    // ... and the fp16 copy of its centers that the batch ranking multiplies instead of `centers`:
+    // [nlists x shadow_geom.ld] fp16(c 2^-cshadow_s), inside the shadow's allocation; null when not built
+    void *cshadow = nullptr;
+    int cshadow_s = 0;
+    double cshadow_E = 0.0;           // max over centers |c - 2^s_c cshadow|, rounded up
+    double cshadow_P = 0.0;           // max over centers |2^s_c cshadow|, rounded up
     std::vector<int64_t> h_offsets;   // host copy
     std::vector<int64_t> len_prefix;  // len_prefix[p] = rows in the p longest lists (output size bound)
     int64_t max_list_len = 0;
@@ -322,12 +330,33 @@ namespace pgv {
 //     matrix cores     g_dot 2 |q^| P, g_dot = gamma_(chain + 4): fp16 products are exact in fp32, each of the four
 //                      accumulator chains adds at most `chain` of them (shadow_chain_length; the instructions lose
 //                      about 5 u per 16 products at worst, see above, charged u per product), two additions join them
-//     pair term        gamma_(ceil(ld / 64) + 6) 2 |q| max|c|: shadow_pair_kernel's per-lane fmaf chain + 6 shuffle
-//                      additions; max|c| from center_norms[nlists] (itself within gamma_(ld / 64 + 10))
+//     pair term        gamma_(pair_chain_length) 2 |q| max|c|; max|c| from center_norms[nlists] (itself within
+//                      gamma_(ld / 64 + 10)).  t reaches the scan by one of two routes, and the term covers the longer:
+//                        shadow_pair_kernel (pgv_scan_batch; batch_fix_kernel's fill for a flagged ranking query): one
+//                          fmaf chain of ceil(ld / 64) elements per lane + 6 shuffle additions: ceil(ld / 64) + 6
+//                        batch_recheck_kernel of the ranking (pgv_search_batch; group_distance_dot): 2^lg lanes per row
+//                          (RowGeom::lpr_log2), each lane two fmaf chains that take its 16-byte vectors in turn: at most
+//                          4 ceil(ceil(nvec / 2^lg) / 2) products, one addition joins the two, lg DPP additions join the
+//                          lanes: 4 ceil(ceil(nvec / 2^lg) / 2) + 1 + lg.  The final -2 * (q.c) is exact.
+//                      1536-d: 30 by the first route, 19 by the second -- the term does not grow there.  The second is
+//                      longer where row_geom puts few lanes on a row (a vector count that does not divide among many
+//                      lanes; at most 64 vectors per lane, so never more than 4 * 32 + 1 + 6 = 135): 249-d has 63
+//                      vectors on one lane, 129 roundings against 10, and its term grows by 119 u 2 |q| max|c|
 //     epilogue         4 u (|x|^2 + |t| + 2 |q^| P): the addition |x|^2 + t and the final fmaf round once each
 // and 4 FLT_MIN for whatever underflowed on the way; the 1.001 factor of the scans' eps applies on top.  A query whose
 // scale 2^(1 + s + s_q) leaves the normal fp32 range, or whose terms are not finite, gets an infinite term: its band
 // holds everything and batch_fix_kernel scores it exactly.
+//
+// The center shadow -- the batch ranking of such an index multiplies c~ = fp16(c 2^-s_c) and the same cast
+// query: a = fl(|c|^2 - 2^(1 + s_c + s_q) acc) for s = |c|^2 - 2 q.c (the dense plan's pairs carry t = 0, so |c|^2 + t is
+// exact).  The band is ScanBound {0, 0, g_norm, g_ref} (the fp32 center_norms are the index's own) plus a per-query term
+// from the same kernel (RankShadowTerms), derived like the scan's with E_c = max |c - 2^s_c c~|, P_c = max |2^s_c c~|:
+//     representation   2 (|q| E_c + |q - q^| P_c)
+//     matrix cores     g_dot 2 |q^| P_c, g_dot = gamma_(shadow_chain_length + 4)
+//     epilogue         4 u (max |c|^2 + 2 |q^| P_c): the final fmaf rounds once
+// There is no pair term.  Nothing in it depends on the data being benign: E_c and P_c are measured, and a query whose
+// band swallows all its candidates (maxprobes + 54 under this ranking, rank_lists_impl) goes through batch_fix_kernel as
+// under the fp32 ranking.
 struct ScanBound {
     float g_sq, g_dot, g_norm, g_ref;
 };
@@ -336,7 +365,19 @@ struct ShadowTerms {  // shadow_query_kernel's inputs
     double E, P;
     double g_dot, g_pair, g_cn;  // g_cn: relative error of the stored largest |x|^2 / |c|^2
 };
+struct RankShadowTerms {  // ... for the center ranking over the centers' shadow
+    int s;
+    double E, P;
+    double g_dot, g_cn;
+};
 inline float gamma_n(double n, double v) { return (float)(n * v / (1.0 - n * v)); }
+// roundings on the way to a pair term t = -2 q.c_l, whichever route computes it (the paragraph above)
+inline int pair_chain_length(const RowGeom &g32) {
+    const int by_pair_kernel = (g32.ld + 63) / 64 + 6;
+    const int per_lane = (g32.nvec + (1 << g32.lpr_log2) - 1) >> g32.lpr_log2;
+    const int by_recheck = 4 * ((per_lane + 1) / 2) + 1 + g32.lpr_log2;
+    return by_pair_kernel > by_recheck ? by_pair_kernel : by_recheck;
+}
 // (the callers go through scan_bound_chain: this is the part that does not depend on the kernel form, and the g_dot of
 // fp32 rows in the four-chain forms)
 inline ScanBound scan_bound(const pgv_ctx *ctx, int dim) {
@@ -485,9 +526,10 @@ int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, co
 int shadow_scale_of(float max_abs);  // s of the largest |x_i - c_i|
 int shadow_chain_length(const RowGeom &g16);  // kernels_mfma.hip: products per accumulator chain of any scan form, at most
 int scan_chain_length(const RowGeom &g, pgv_dtype dtype, bool wide);  // ... of a plain scan: the forms a launch may use
+// (qscale / qeps: the list scan's factors and band terms, cscale / ceps: the center ranking's; either pair may be null)
 int launch_shadow_query(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *queries, int nq,
-                        const ShadowTerms &st, const float *center_norm_max, const float *row_norm_max, void *qcast,
-                        float *qscale, float *qeps);
+                        const ShadowTerms &st, const RankShadowTerms &rt, const float *center_norm_max,
+                        const float *row_norm_max, void *qcast, float *qscale, float *qeps, float *cscale, float *ceps);
 int launch_shadow_pairs(pgv_ctx *ctx, const RowGeom &g32, const void *queries, const void *centers,
                         const int64_t *pair_start, int nlists, int64_t npairs, ScanPair *pairs);
 int mfma_scan_queries_per_task_wide();  // 64: tasks of the batches whose lists are probed by many queries each
@@ -516,8 +558,10 @@ struct PlanResult {
     int64_t *probe_off = nullptr; // device [nq x probes]
     int64_t *pair_start = nullptr; // device [nlists + 1]: the first pair of each list
 };
+// pair_t: [nq x probes] the pairs' t = -2 q.c_l in probe order (the shadow scan; from the ranking), or null: t = 0
 int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists, int nq,
-                      int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res);
+                      int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res,
+                      const float *pair_t = nullptr);
 int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_start, int nseg,
                          int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word = nullptr);
 int launch_positions_to_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists,
@@ -539,14 +583,16 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                          float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags,
                          int32_t *out_i32 = nullptr, const int32_t *probe_lists = nullptr,
                          const int64_t *probe_off = nullptr, int probes = 0,
-                         const float *eps_add = nullptr);  // cand_slot null: slots from the positions; eps_add: per query
-                                                           // term of the band (the shadow scan), or null
+                         const float *eps_add = nullptr,   // cand_slot null: slots from the positions; eps_add: per query
+                         float *pair_t = nullptr);         // term of the band (the shadow paths), or null; pair_t: fp32
+                                                           // rows only, [nq x k] -2 q.row of the rows emitted, or null
 // the flagged queries start to end: exact scores of the whole segment, head, output row (out_slot: row slots, or
 // center ids for the dense form)
 int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
                      const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
                      const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32 = nullptr, const float *eps_add = nullptr);
+                     uint64_t *out_tid, int32_t *out_i32 = nullptr, const float *eps_add = nullptr,
+                     float *pair_t = nullptr);
 int launch_iota_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *lists_dev, int nlists,
                       const int64_t *probe_off, int64_t *out_slot);
 
