@@ -130,24 +130,32 @@ __global__ __launch_bounds__(kKmThreads) void kmpp_pick_kernel(
 }
 
 // The same pick with the samples sharded by row over `nranks` processes (global sample order =
-// rank order): every rank knows every rank's weight total (all-gathered); the walk first steps
-// over whole ranks, then -- on the rank it ends in -- over that rank's blocks and weights.  The
-// owner writes the chosen row into its send slot, everybody else zeros; after the all-gather of
-// the slots every rank copies slot *owner_out into centers[round + 1].
+// rank order): every rank knows every rank's weight total and sample count (all-gathered); the walk
+// first steps over whole ranks, then -- on the rank it ends in -- over that rank's blocks and weights.
+// The reference's walk ends on the first SAMPLE at which `choice <= 0`, also one of weight 0 (a draw
+// of 0.0, or every weight 0 when there are more lists than distinct rows: global sample 0), so what
+// lets a rank end the walk is that it holds a sample, not that it holds weight; the last rank with
+// samples ends it regardless.  The owner writes the chosen row into its send slot, everybody else
+// zeros; after the all-gather of the slots every rank copies slot *owner_out into centers[round + 1].
 __global__ __launch_bounds__(kKmThreads) void kmpp_pick_sharded_kernel(
     const char *__restrict__ samples, int n, const float *__restrict__ weight,
-    const double *__restrict__ block_sums, int nblocks, const double *__restrict__ totals, int nranks, int rank,
+    const double *__restrict__ block_sums, int nblocks, const double *__restrict__ totals,
+    const int64_t *__restrict__ counts, int nranks, int rank,
     const double *__restrict__ draws, int round, char *__restrict__ send_row, int nvec, int32_t *__restrict__ owner_out) {
     __shared__ WalkLds w;
     __shared__ int owner;
     if (threadIdx.x == 0) {
         double grand = 0.0;
-        for (int r = 0; r < nranks; r++) grand += totals[r];
+        int last = 0;
+        for (int r = 0; r < nranks; r++) {
+            grand += totals[r];
+            if (counts[r] > 0) last = r;
+        }
         double choice = grand * draws[round];
-        int o = nranks - 1;
-        for (int r = 0; r < nranks - 1; r++) {
-            // a rank without weight cannot hold the choice; the last rank with samples ends the walk regardless
-            if (choice - totals[r] <= 0 && totals[r] > 0) {
+        int o = last;
+        for (int r = 0; r < last; r++) {
+            if (counts[r] <= 0) continue;  // no sample to end on
+            if (choice - totals[r] <= 0) {
                 o = r;
                 break;
             }
@@ -430,11 +438,11 @@ int launch_kmpp_total(pgv_ctx *ctx, const double *block_sums, int nblocks, doubl
 }
 
 int launch_kmpp_pick_sharded(pgv_ctx *ctx, const RowGeom &g, const void *samples, int n, const float *weight,
-                             const double *block_sums, const double *totals, int nranks, int rank, const double *draws,
-                             int round, void *send_row, int32_t *owner_out) {
+                             const double *block_sums, const double *totals, const int64_t *counts, int nranks, int rank,
+                             const double *draws, int round, void *send_row, int32_t *owner_out) {
     hipLaunchKernelGGL(kmpp_pick_sharded_kernel, dim3(1), dim3(kKmThreads), 0, ctx->stream,
-                       static_cast<const char *>(samples), n, weight, block_sums, kmpp_block_count(n), totals, nranks,
-                       rank, draws, round, static_cast<char *>(send_row), g.nvec, owner_out);
+                       static_cast<const char *>(samples), n, weight, block_sums, kmpp_block_count(n), totals, counts,
+                       nranks, rank, draws, round, static_cast<char *>(send_row), g.nvec, owner_out);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -280,7 +280,7 @@ int pgv_kmeans_sharded(pgv_comm *cm, pgv_ops ops, pgv_dtype dtype, int dim, cons
                 PGV_HIP(hipMemsetAsync(my_total, 0, sizeof(double), ctx->stream));
             }
             PGV_TRY(comm_all_gather(cm, my_total, totals, sizeof(double)));
-            PGV_TRY(launch_kmpp_pick_sharded(ctx, g, s_dev, n, weight, block_sums, totals, R, cm->rank, draws_dev, i,
+            PGV_TRY(launch_kmpp_pick_sharded(ctx, g, s_dev, n, weight, block_sums, totals, cnt_dev, R, cm->rank, draws_dev, i,
                                              send_row, owner));
             PGV_TRY(comm_all_gather(cm, send_row, rows_all, row_bytes));
             PGV_TRY(launch_kmpp_take_row(ctx, g, rows_all, owner, centers_dev, i));

@@ -632,8 +632,8 @@ int launch_kmpp_pick(pgv_ctx *ctx, const RowGeom &g, const void *samples, int n,
                      int round, void *centers, int32_t *picked);
 int launch_kmpp_total(pgv_ctx *ctx, const double *block_sums, int nblocks, double *out);
 int launch_kmpp_pick_sharded(pgv_ctx *ctx, const RowGeom &g, const void *samples, int n, const float *weight,
-                             const double *block_sums, const double *totals, int nranks, int rank, const double *draws,
-                             int round, void *send_row, int32_t *owner_out);
+                             const double *block_sums, const double *totals, const int64_t *counts, int nranks, int rank,
+                             const double *draws, int round, void *send_row, int32_t *owner_out);
 int launch_kmpp_take_row(pgv_ctx *ctx, const RowGeom &g, const void *gathered, const int32_t *owner, void *centers,
                          int round);
 int launch_lloyd_pack(pgv_ctx *ctx, const int32_t *counts, const unsigned long long *changes, int k, float *tail);

@@ -300,7 +300,8 @@ def test_kmeanspp_picks_match_on_exact_data(ctx, oracle):
 @pytest.mark.parametrize("ops,dtype", [(po.OPS_L2, po.ORA_F32), (po.OPS_IP, po.ORA_F32), (po.OPS_L2, po.ORA_F16),
                                        (po.OPS_COSINE, po.ORA_F16)])
 def test_one_lloyd_step_from_given_centers(ctx, oracle, ops, dtype):
-    """assignment identical (up to float ties), new centers within 1e-5 (SURVEY hard part 3)"""
+    """assignment identical (up to float ties); new centers bit for bit under L2, within 1e-5 under the spherical
+    opclasses (SURVEY hard part 3)"""
     dim, k = 24, 30
     samples = gen(4000, dim, seed=81, dist="clustered", clusters=k, dtype=dtype)
     if ops != po.OPS_L2:
@@ -317,8 +318,11 @@ def test_one_lloyd_step_from_given_centers(ctx, oracle, ops, dtype):
     want_centers, want_counts = oracle.kmeans_compute_new_centers(ops, dtype, samples, closest, k, oracle.prng(1))
     got_centers = api.lloyd_finish(ctx, pops, DT[dtype], dim, sums, counts, api.make_rng(seed=1))
     np.testing.assert_array_equal(counts, want_counts)
-    assert_close(got_centers.astype(np.float64), want_centers.astype(np.float64), rtol=RTOL,
-                 atol=1e-3 if dtype == po.ORA_F16 else 1e-7, what="new centers")
+    if ops == po.OPS_L2:
+        np.testing.assert_array_equal(got_centers, want_centers)
+    else:  # the renormalisation's last rounding may differ (test_gpu_kmeans_edges.py holds it to 1 ulp)
+        assert_close(got_centers.astype(np.float64), want_centers.astype(np.float64), rtol=RTOL,
+                     atol=1e-3 if dtype == po.ORA_F16 else 1e-7, what="new centers")
 
 
 def test_kmeans_end_to_end_quality_and_rules(ctx, oracle):
