@@ -334,6 +334,16 @@ int			pgv_search_batch(pgv_index * index, const void *queries, int nq, int probe
 							 float *out_dist, int64_t *out_slot, uint64_t *out_tid);
 
 /*
+ * The query cast of the fp16 shadow paths on its own, for tests: what pgv_search_batch prepares once per batch for an
+ * fp32 L2 index that has its fp16 shadows (PGV_ERR_STATE otherwise).  out_qcast [nq x ld16] fp16 bits, ld16 = dim
+ * rounded up to 8: the queries times 2^-s_q, s_q per query; out_qscale / out_qeps [nq]: the list scan's factor
+ * 2^(1 + s + s_q) and the query's term of its rounding band; out_cscale / out_ceps [nq]: the same for the center
+ * ranking.  Any output may be NULL.  Host or device pointers; complete on return.
+ */
+int			pgv_index_shadow_cast(pgv_index * index, const void *queries, int nq, void *out_qcast, float *out_qscale,
+								  float *out_qeps, float *out_cscale, float *out_ceps);
+
+/*
  * The GetScanItems half of pgv_search_batch on its own: the probe lists were chosen
  * elsewhere (pgv_rank_lists, possibly on another GPU: with the index sharded by list,
  * every rank ranks a slice of the queries against the replicated centers, the probe lists

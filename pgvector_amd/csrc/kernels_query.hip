@@ -396,7 +396,10 @@ constexpr int kRecheckCap = 256;  // k' <= 256: rank_sort_entries' reach
 
 // DOT (fp32 rows; the center ranking in front of a shadow scan): q.row is accumulated beside the exact distance over the
 // same loads, and the threads that emit the k rows also write t = -2 q.row to pair_t[q * k + rank] -- the pair terms of
-// the list scan that follows, in probe order, for one more accumulator instead of a kernel of 10 240 dot products
+// the list scan that follows, in probe order, for one more accumulator instead of a kernel of 10 240 dot products.
+// emit (DOT only; cnt null: off): the same threads do the plan's counting for the lists they emit (plan_count_kernel's
+// work, PlanEmit in pgv_internal.h): cnt[list] += 1, and through LDS the query's probe_off prefix and seg_len.  cnt was
+// cleared by the topk_kernel in front of this launch.  Fill rows (-1) count nothing and have length 0.
 template <typename T, bool DOT = false>
 __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     const char *__restrict__ vectors, const uint64_t *__restrict__ tids, int nvec, int lg,
@@ -407,7 +410,7 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     const int64_t *__restrict__ seg_start, int64_t fixed_len,
     const unsigned *__restrict__ row_norm_max, ScanBound bound, const float *__restrict__ eps_add, int nq,
     float *__restrict__ out_dist, int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid,
-    int32_t *__restrict__ out_i32, int32_t *__restrict__ flags, float *__restrict__ pair_t) {
+    int32_t *__restrict__ out_i32, int32_t *__restrict__ flags, float *__restrict__ pair_t, PlanEmit emit) {
     static_assert(!DOT || std::is_same<T, float>::value, "pair terms: fp32 rows");
     __shared__ float exact[kRecheckCap];
     __shared__ float dots[DOT ? kRecheckCap : 1];
@@ -516,6 +519,23 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
         if (out_tid) out_tid[o] = ~0ull;
         if constexpr (DOT) pair_t[o] = 0.f;
     }
+    if constexpr (DOT) {
+        if (emit.cnt) {  // (block-uniform; k <= kRecheckCap)
+            __syncthreads();  // every thread has read its slot and ranked itself: slots[] is free
+            if ((int)threadIdx.x < cnt && rank < k) {
+                atomicAdd(&emit.cnt[my_slot], 1);
+                slots[rank] = emit.list_off[my_slot + 1] - emit.list_off[my_slot];
+            }
+            if ((int)threadIdx.x >= kk && (int)threadIdx.x < k) slots[threadIdx.x] = 0;
+            __syncthreads();
+            if ((int)threadIdx.x < k) {
+                int64_t run = 0;
+                for (int i = 0; i < (int)threadIdx.x; i++) run += slots[i];
+                emit.probe_off[(size_t)q * k + threadIdx.x] = run;
+                if ((int)threadIdx.x == k - 1) emit.seg_len[q] = run + slots[threadIdx.x];
+            }
+        }
+    }
     if (threadIdx.x == 0) {
         // the band reaches the end of the candidates and there are rows beyond them: one of those may be in it too
         const int32_t flag = (m > ncand && cnt == ncand) ? 1 : 0;
@@ -534,6 +554,9 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
 //   (2) otherwise scores every row of its segment with the exact form (the whole segment, what the exact kernels would
 //       have done), selects the head like topk_kernel and writes the query's output row.
 // Workgroups without a flagged query leave at once.
+// emit (with pair_t: the ranking in front of a shadow scan; cnt null: off): batch_recheck_kernel has counted the lists
+// it emitted for the query; its row is replaced here, so the old lists are taken out of cnt again, the new ones added,
+// and the query's probe_off and seg_len rewritten (k <= kWide).
 constexpr int kWide = kRecheckCap;
 
 template <typename T>
@@ -544,7 +567,7 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
     const int32_t *__restrict__ flags, int nq, float *__restrict__ seg_vals, int k, int kp, int cap,
     const unsigned *__restrict__ row_norm_max, ScanBound bound, const float *__restrict__ eps_add, int widen,
     float *__restrict__ out_dist, int64_t *__restrict__ out_slot, uint64_t *__restrict__ out_tid,
-    int32_t *__restrict__ out_i32, double *__restrict__ stats, float *__restrict__ pair_t) {
+    int32_t *__restrict__ out_i32, double *__restrict__ stats, float *__restrict__ pair_t, PlanEmit emit) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);  // [cap >= max(kp, kWide)]
     SelShared *sel = reinterpret_cast<SelShared *>(smem + (size_t)cap * 8);
@@ -583,9 +606,33 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
                     __syncthreads();
                     fill_pair_terms(vectors, row_bytes, qrow, nvec * 4, out_i32 ? out_i32 + (size_t)q * k : nullptr,
                                     out_slot ? out_slot + (size_t)q * k : nullptr, k, pair_t + (size_t)q * k);
+                    if (emit.cnt) {  // the new row's lists into the plan (slots[] is free: a barrier lies behind its readers)
+                        if ((int)threadIdx.x < k) {
+                            const int l = __hip_atomic_load(out_i32 + (size_t)q * k + threadIdx.x, __ATOMIC_RELAXED,
+                                                            __HIP_MEMORY_SCOPE_AGENT);
+                            if (l >= 0) atomicAdd(&emit.cnt[l], 1);
+                            slots[threadIdx.x] = l >= 0 ? emit.list_off[l + 1] - emit.list_off[l] : 0;
+                        }
+                        __syncthreads();
+                        if ((int)threadIdx.x < k) {
+                            int64_t run = 0;
+                            for (int i = 0; i < (int)threadIdx.x; i++) run += slots[i];
+                            emit.probe_off[(size_t)q * k + threadIdx.x] = run;
+                            if ((int)threadIdx.x == k - 1) emit.seg_len[q] = run + slots[threadIdx.x];
+                        }
+                    }
                 }
             }
         };
+        if constexpr (std::is_same<T, float>::value) {
+            if (pair_t && emit.cnt) {  // (block-uniform) the lists batch_recheck_kernel emitted and counted: out again
+                if ((int)threadIdx.x < k) {
+                    const int l = out_i32[(size_t)q * k + threadIdx.x];
+                    if (l >= 0) atomicSub(&emit.cnt[l], 1);
+                }
+                __syncthreads();  // read before any thread of this workgroup writes the new row
+            }
+        }
         bool settled = false;
         if (widen && k <= kWide / 2) {
             // (1) the kWide smallest approximate values, ascending by (value, position)
@@ -879,8 +926,10 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                          const int64_t *seg_start, int64_t fixed_len, const ScanBound &bound,
                          float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags, int32_t *out_i32,
                          const int32_t *probe_lists, const int64_t *probe_off, int probes, const float *eps_add,
-                         float *pair_t) {
+                         float *pair_t, const PlanEmit &emit) {
     if (nq <= 0) return PGV_OK;
+    if (emit.cnt && !(pair_t && out_i32 && emit.probe_off && emit.seg_len && emit.list_off))
+        PGV_FAIL(PGV_ERR_ARG, "recheck: the plan is counted where the pair terms are written");
     if (kprime > kRecheckCap || k > kprime) PGV_FAIL(PGV_ERR_ARG, "recheck: k' = %d outside k..%d", kprime, kRecheckCap);
     if (pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "recheck: pair terms are for fp32 rows");
 #define PGV_RECHECK(T, DOT)                                                                                         \
@@ -888,7 +937,7 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                        static_cast<const char *>(xr.vectors), xr.tids, xr.geom.nvec, xr.geom.lpr_log2,               \
                        static_cast<const char *>(q_dev), kprime, k, approx_val, cand_pos, cand_slot, xr.list_offsets, \
                        probe_lists, probe_off, probes, seg_start, fixed_len, xr.norm_max, bound, eps_add, nq, out_dist, out_slot,  \
-                       out_tid, out_i32, flags, pair_t)
+                       out_tid, out_i32, flags, pair_t, emit)
     if (pair_t)
         PGV_RECHECK(float, true);
     else if (xr.dtype == PGV_F32)
@@ -903,8 +952,10 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
 int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
                      const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
                      const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32, const float *eps_add, float *pair_t) {
+                     uint64_t *out_tid, int32_t *out_i32, const float *eps_add, float *pair_t, const PlanEmit &emit) {
     if (nq <= 0) return PGV_OK;
+    if (emit.cnt && !(pair_t && out_i32 && k <= kWide && emit.probe_off && emit.seg_len && emit.list_off))
+        PGV_FAIL(PGV_ERR_ARG, "fix: the plan is counted where the pair terms are written, k <= %d", kWide);
     if (pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "fix: pair terms are for fp32 rows");
     // (the ranking's flagged queries count like the list scan's: pgv_stats scan_widened_queries / scan_redo_queries)
     double *stats = (ctx->profiling && ctx->stats_dev.p) ? ctx->stats_dev.as<double>() : nullptr;
@@ -920,7 +971,7 @@ int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int n
                        static_cast<const char *>(xr.vectors), xr.list_offsets, xr.tids, xr.geom.nvec,                \
                        xr.geom.lpr_log2, static_cast<const char *>(q_dev), probe_lists, probe_off, probes, seg_start, \
                        fixed_len, flags, nq, seg_vals, k, kp, cap, xr.norm_max, bound, eps_add, widen, out_dist,      \
-                       out_slot, out_tid, out_i32, stats, pair_t)
+                       out_slot, out_tid, out_i32, stats, pair_t, emit)
     if (xr.dtype == PGV_F32)
         PGV_FIX(float);
     else

@@ -66,20 +66,29 @@ __device__ void block_exclusive_scan(int n, F value, int64_t *out, int64_t *scra
     __syncthreads();
 }
 
+// acc (profiling, or null): the batch's pair and streamed-row counts are added to the device accumulators here -- the
+// third pass already forms every list's groups and length, so plan_stats_kernel's launch is not needed behind this one.
+// The addends are integers held in doubles (far below 2^53): their sum is exact in any order, the same bits as
+// plan_stats_kernel's.
 __global__ __launch_bounds__(1024) void plan_scan_kernel(
     const int *__restrict__ cnt, const int64_t *__restrict__ list_off,
     const int64_t *__restrict__ seg_len, int nq, int nlists, int qt, int rows_per_task,
     int64_t *__restrict__ seg_start, int64_t *__restrict__ pair_start,
-    int64_t *__restrict__ task_start, int64_t *__restrict__ totals /*[2]: out elems, tasks*/) {
+    int64_t *__restrict__ task_start, int64_t *__restrict__ totals /*[2]: out elems, tasks*/,
+    double *__restrict__ acc) {
     __shared__ int64_t scratch[1024 / 64 + 1];
+    __shared__ double red[2][1024 / 64];
     block_exclusive_scan(nq, [&](int i) { return seg_len[i]; }, seg_start, scratch);
     block_exclusive_scan(nlists, [&](int i) { return (int64_t)cnt[i]; }, pair_start, scratch);
+    double rows = 0.0, uniq = 0.0;
     block_exclusive_scan(
         nlists,
         [&](int i) {
             const int64_t len = list_off[i + 1] - list_off[i];
             const int64_t ng = (cnt[i] + qt - 1) / qt;
             const int64_t nc = (len + rows_per_task - 1) / rows_per_task;
+            rows += (double)ng * (double)len;
+            uniq += ng > 0 ? (double)len : 0.0;
             return ng * nc;
         },
         task_start, scratch);
@@ -88,16 +97,36 @@ __global__ __launch_bounds__(1024) void plan_scan_kernel(
         totals[1] = task_start[nlists];
         *reinterpret_cast<int *>(totals + 2) = (int)task_start[nlists];  // what the scan kernels read
     }
+    if (acc) {  // (block-uniform)
+        for (int o = 32; o > 0; o >>= 1) {
+            rows += __shfl_xor(rows, o);
+            uniq += __shfl_xor(uniq, o);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            red[0][threadIdx.x >> 6] = rows;
+            red[1][threadIdx.x >> 6] = uniq;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double r = 0.0, u = 0.0;
+            for (int w = 0; w < (int)(blockDim.x >> 6); w++) {
+                r += red[0][w];
+                u += red[1][w];
+            }
+            acc[0] += (double)seg_start[nq];  // (row, query) pairs
+            acc[1] += r;                      // rows streamed
+            acc[5] += u;                      // rows of the lists at least one query probes
+        }
+    }
 }
 
-__global__ void plan_pairs_kernel(const int32_t *__restrict__ probe_lists,
-                                  const int64_t *__restrict__ list_off,
-                                  const int64_t *__restrict__ probe_off,
-                                  const int64_t *__restrict__ seg_start,
-                                  const int64_t *__restrict__ pair_start, int *__restrict__ fill,
-                                  int nq, int probes, const float *__restrict__ pair_t,
-                                  ScanPair *__restrict__ pairs) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void plan_pairs_body(int64_t i, const int32_t *__restrict__ probe_lists,
+                                                const int64_t *__restrict__ list_off,
+                                                const int64_t *__restrict__ probe_off,
+                                                const int64_t *__restrict__ seg_start,
+                                                const int64_t *__restrict__ pair_start, int *__restrict__ fill,
+                                                int nq, int probes, const float *__restrict__ pair_t,
+                                                ScanPair *__restrict__ pairs) {
     if (i >= (int64_t)nq * probes) return;
     const int q = (int)(i / probes);
     const int l = probe_lists[i];
@@ -110,14 +139,26 @@ __global__ void plan_pairs_kernel(const int32_t *__restrict__ probe_lists,
     pairs[pos] = pr;
 }
 
+__global__ void plan_pairs_kernel(const int32_t *__restrict__ probe_lists,
+                                  const int64_t *__restrict__ list_off,
+                                  const int64_t *__restrict__ probe_off,
+                                  const int64_t *__restrict__ seg_start,
+                                  const int64_t *__restrict__ pair_start, int *__restrict__ fill,
+                                  int nq, int probes, const float *__restrict__ pair_t,
+                                  ScanPair *__restrict__ pairs) {
+    plan_pairs_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, probe_lists, list_off, probe_off, seg_start, pair_start,
+                    fill, nq, probes, pair_t, pairs);
+}
+
 // one thread per task: the list by bisection of task_start (the lists' tasks are consecutive), then chunk-major
 // inside the list -- tasks that stream the same rows sit next to each other in the queue
-__global__ void plan_tasks_kernel(const int *__restrict__ cnt, const int64_t *__restrict__ list_off,
-                                  const int64_t *__restrict__ pair_start,
-                                  const int64_t *__restrict__ task_start, int nlists, int qt,
-                                  int rows_per_task, ScanTask *__restrict__ tasks) {
+__device__ __forceinline__ void plan_tasks_body(int64_t first, int64_t stride, const int *__restrict__ cnt,
+                                                const int64_t *__restrict__ list_off,
+                                                const int64_t *__restrict__ pair_start,
+                                                const int64_t *__restrict__ task_start, int nlists, int qt,
+                                                int rows_per_task, ScanTask *__restrict__ tasks) {
     const int64_t ntasks = task_start[nlists];
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < ntasks; t += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t t = first; t < ntasks; t += stride) {
         int lo = 0, hi = nlists - 1;  // last list whose first task is <= t (lists without tasks share a start)
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
@@ -143,6 +184,32 @@ __global__ void plan_tasks_kernel(const int *__restrict__ cnt, const int64_t *__
     }
 }
 
+__global__ void plan_tasks_kernel(const int *__restrict__ cnt, const int64_t *__restrict__ list_off,
+                                  const int64_t *__restrict__ pair_start,
+                                  const int64_t *__restrict__ task_start, int nlists, int qt,
+                                  int rows_per_task, ScanTask *__restrict__ tasks) {
+    plan_tasks_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, cnt, list_off,
+                    pair_start, task_start, nlists, qt, rows_per_task, tasks);
+}
+
+// plan_pairs_kernel and plan_tasks_kernel in one grid: both read what plan_scan_kernel wrote and nothing of each other
+// (the pairs' scatter writes fill and pairs, the tasks read cnt and the three prefix arrays), so the first pair_blocks
+// workgroups scatter the pairs, the others write the tasks, and no workgroup waits for another
+__global__ void plan_pairs_tasks_kernel(const int32_t *__restrict__ probe_lists, const int64_t *__restrict__ list_off,
+                                        const int64_t *__restrict__ probe_off, const int64_t *__restrict__ seg_start,
+                                        const int64_t *__restrict__ pair_start, const int64_t *__restrict__ task_start,
+                                        const int *__restrict__ cnt, int *__restrict__ fill, int nq, int probes, int nlists,
+                                        int qt, int rows_per_task, const float *__restrict__ pair_t, int pair_blocks,
+                                        ScanPair *__restrict__ pairs, ScanTask *__restrict__ tasks) {
+    if ((int)blockIdx.x < pair_blocks)  // (block-uniform)
+        plan_pairs_body((int64_t)blockIdx.x * blockDim.x + threadIdx.x, probe_lists, list_off, probe_off, seg_start,
+                        pair_start, fill, nq, probes, pair_t, pairs);
+    else
+        plan_tasks_body((int64_t)(blockIdx.x - pair_blocks) * blockDim.x + threadIdx.x,
+                        (int64_t)(gridDim.x - pair_blocks) * blockDim.x, cnt, list_off, pair_start, task_start, nlists, qt,
+                        rows_per_task, tasks);
+}
+
 // float8 ordering: NaN after everything, strict
 __device__ __forceinline__ bool dist_before(float a, float b) { return float_to_key(a) < float_to_key(b); }
 
@@ -152,7 +219,7 @@ __device__ __forceinline__ bool dist_before(float a, float b) { return float_to_
 __global__ __launch_bounds__(kSelThreads) void topk_kernel(
     const float *__restrict__ vals, const int64_t *__restrict__ seg_start, int64_t fixed_len,
     int k, int kp, int cap, float *__restrict__ out_val, int64_t *__restrict__ out_pos,
-    int32_t *__restrict__ zero_word) {
+    int32_t *__restrict__ zero_word, int32_t *__restrict__ zero_range, int zero_n) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);  // [cap >= kp]
     SelShared *s = reinterpret_cast<SelShared *>(smem + (size_t)cap * 8);
@@ -161,6 +228,10 @@ __global__ __launch_bounds__(kSelThreads) void topk_kernel(
     // a counter the NEXT kernel in the stream starts from zero (the flagged-query count of the exact tail):
     // cleared here instead of by a memset launch of its own
     if (zero_word && seg == 0 && threadIdx.x == 0) *zero_word = 0;
+    // ... and the plan's list counters (cnt | fill, launch_plan_batch) in front of the kernels that count into them:
+    // the grid shares the range, a word each
+    if (zero_range)
+        for (int i = seg * kSelThreads + (int)threadIdx.x; i < zero_n; i += (int)gridDim.x * kSelThreads) zero_range[i] = 0;
     const int64_t base = seg_start ? seg_start[seg] : (int64_t)seg * fixed_len;
     const int64_t m = seg_start ? seg_start[seg + 1] - base : fixed_len;
     const float *v = vals + base;
@@ -295,8 +366,28 @@ int launch_cast_pos_to_i32(pgv_ctx *ctx, const int64_t *pos, int64_t n, int32_t 
     return PGV_OK;
 }
 
+// plan_a: cnt[nlists] | fill[nlists]   (ints, zero before the first kernel that counts into them)
+// plan_b: probe_off[nq*probes] | seg_len[nq] | seg_start[nq+1] | pair_start[nlists+1]
+//         | task_start[nlists+1] | totals[2] | ntasks (int)
+int plan_batch_reserve(pgv_ctx *ctx, int nlists, int nq, int probes, PlanBuffers *pb) {
+    const size_t npairs = (size_t)nq * probes;
+    PGV_TRY(ctx->plan_a.ensure(sizeof(int) * 2 * (size_t)nlists));
+    const size_t nb = npairs + (size_t)nq + (size_t)nq + 1 + 2 * ((size_t)nlists + 1) + 3;
+    PGV_TRY(ctx->plan_b.ensure(sizeof(int64_t) * nb));
+    pb->cnt = ctx->plan_a.as<int>();
+    pb->fill = pb->cnt + nlists;
+    pb->probe_off = ctx->plan_b.as<int64_t>();
+    pb->seg_len = pb->probe_off + npairs;
+    pb->seg_start = pb->seg_len + nq;
+    pb->pair_start = pb->seg_start + nq + 1;
+    pb->task_start = pb->pair_start + nlists + 1;
+    pb->totals = pb->task_start + nlists + 1;
+    return PGV_OK;
+}
+
 int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists, int nq,
-                      int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res, const float *pair_t) {
+                      int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res, const float *pair_t,
+                      bool counted) {
     const int nlists = ix->nlists;
     const size_t npairs = (size_t)nq * probes;
 
@@ -314,48 +405,57 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
     res->out_bound = (int64_t)nq * ix->len_prefix[probes];
     if (res->ntasks_bound > 0x7fffffff) PGV_FAIL(PGV_ERR_ARG, "plan: too many tasks");
 
-    // plan_a: cnt[nlists] | fill[nlists]   (ints, zeroed every call)
-    PGV_TRY(ctx->plan_a.ensure(sizeof(int) * 2 * (size_t)nlists));
-    // plan_b: probe_off[nq*probes] | seg_len[nq] | seg_start[nq+1] | pair_start[nlists+1]
-    //         | task_start[nlists+1] | totals[2] | ntasks (int)
-    const size_t nb = npairs + (size_t)nq + (size_t)nq + 1 + 2 * ((size_t)nlists + 1) + 3;
-    PGV_TRY(ctx->plan_b.ensure(sizeof(int64_t) * nb));
+    // (counted: the same sizes were reserved ahead of the ranking, so neither buffer moves here)
+    PlanBuffers pb;
+    PGV_TRY(plan_batch_reserve(ctx, nlists, nq, probes, &pb));
     PGV_TRY(ctx->pairs.ensure(sizeof(ScanPair) * npairs));
     PGV_TRY(ctx->tasks.ensure(sizeof(ScanTask) * (size_t)(res->ntasks_bound > 0 ? res->ntasks_bound : 1) + 16));
-    int *cnt = ctx->plan_a.as<int>();
-    int *fill = cnt + nlists;
-    int64_t *probe_off = ctx->plan_b.as<int64_t>();
-    int64_t *seg_len = probe_off + npairs;
-    int64_t *seg_start = seg_len + nq;
-    int64_t *pair_start = seg_start + nq + 1;
-    int64_t *task_start = pair_start + nlists + 1;
-    int64_t *totals = task_start + nlists + 1;
+    int *cnt = pb.cnt, *fill = pb.fill;
+    int64_t *probe_off = pb.probe_off, *seg_len = pb.seg_len, *seg_start = pb.seg_start, *pair_start = pb.pair_start;
+    int64_t *task_start = pb.task_start, *totals = pb.totals;
     ScanTask *tasks = ctx->tasks.as<ScanTask>();
-
-    PGV_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * 2 * (size_t)nlists, ctx->stream));
-    hipLaunchKernelGGL(plan_count_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream,
-                       probe_lists, ix->list_offsets, nq, probes, cnt, probe_off, seg_len);
-    hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt,
-                       ix->list_offsets, seg_len, nq, nlists, qt, rows_per_task, seg_start,
-                       pair_start, task_start, totals);
-    hipLaunchKernelGGL(plan_pairs_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0,
-                       ctx->stream, probe_lists, ix->list_offsets, probe_off, seg_start,
-                       pair_start, fill, nq, probes, pair_t, ctx->pairs.as<ScanPair>());
-    {
-        const int64_t want = (res->ntasks_bound + 255) / 256;
-        const int64_t cap = (int64_t)ctx->num_cus * 8;
-        hipLaunchKernelGGL(plan_tasks_kernel, dim3((unsigned)(want < 1 ? 1 : (want > cap ? cap : want))), dim3(256), 0,
-                           ctx->stream, cnt, ix->list_offsets, pair_start, task_start, nlists, qt, rows_per_task, tasks);
-    }
-    PGV_HIP(hipGetLastError());
-
+    const int64_t want = (res->ntasks_bound + 255) / 256;
+    const int64_t cap = (int64_t)ctx->num_cus * 8;
+    const unsigned task_blocks = (unsigned)(want < 1 ? 1 : (want > cap ? cap : want));
+    const unsigned pair_blocks = (unsigned)((npairs + 255) / 256);
     res->ntasks = res->ntasks_bound;
     res->total_out = res->out_bound;
-    if (read_totals) {  // profiling: exact pair / streamed-row counts, accumulated on the device
-        PGV_TRY(ctx->stats_dev.ensure(8 * sizeof(double)));
-        hipLaunchKernelGGL(plan_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, cnt,
-                           ix->list_offsets, totals, nlists, qt, ctx->stats_dev.as<double>());
+
+    if (counted) {
+        // pgv_search_batch behind a ranking over the center shadow: the ranking's kernels have cleared cnt | fill
+        // (topk_kernel), counted the lists and written probe_off / seg_len where they emitted them (batch_recheck_kernel;
+        // batch_fix_kernel for the queries it redid).  Two launches are left: the prefix sums (with the profiling totals)
+        // and the pairs and tasks in one grid.
+        double *acc = nullptr;
+        if (read_totals) {
+            PGV_TRY(ctx->stats_dev.ensure(8 * sizeof(double)));
+            acc = ctx->stats_dev.as<double>();
+        }
+        hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt, ix->list_offsets, seg_len, nq, nlists,
+                           qt, rows_per_task, seg_start, pair_start, task_start, totals, acc);
+        hipLaunchKernelGGL(plan_pairs_tasks_kernel, dim3(pair_blocks + task_blocks), dim3(256), 0, ctx->stream, probe_lists,
+                           ix->list_offsets, probe_off, seg_start, pair_start, task_start, cnt, fill, nq, probes, nlists, qt,
+                           rows_per_task, pair_t, (int)pair_blocks, ctx->pairs.as<ScanPair>(), tasks);
         PGV_HIP(hipGetLastError());
+    } else {
+        PGV_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * 2 * (size_t)nlists, ctx->stream));
+        hipLaunchKernelGGL(plan_count_kernel, dim3((nq + 255) / 256), dim3(256), 0, ctx->stream,
+                           probe_lists, ix->list_offsets, nq, probes, cnt, probe_off, seg_len);
+        hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt,
+                           ix->list_offsets, seg_len, nq, nlists, qt, rows_per_task, seg_start,
+                           pair_start, task_start, totals, static_cast<double *>(nullptr));
+        hipLaunchKernelGGL(plan_pairs_kernel, dim3(pair_blocks), dim3(256), 0,
+                           ctx->stream, probe_lists, ix->list_offsets, probe_off, seg_start,
+                           pair_start, fill, nq, probes, pair_t, ctx->pairs.as<ScanPair>());
+        hipLaunchKernelGGL(plan_tasks_kernel, dim3(task_blocks), dim3(256), 0,
+                           ctx->stream, cnt, ix->list_offsets, pair_start, task_start, nlists, qt, rows_per_task, tasks);
+        PGV_HIP(hipGetLastError());
+        if (read_totals) {  // profiling: exact pair / streamed-row counts, accumulated on the device
+            PGV_TRY(ctx->stats_dev.ensure(8 * sizeof(double)));
+            hipLaunchKernelGGL(plan_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, cnt,
+                               ix->list_offsets, totals, nlists, qt, ctx->stats_dev.as<double>());
+            PGV_HIP(hipGetLastError());
+        }
     }
     res->tasks = tasks;
     res->pairs = ctx->pairs.as<ScanPair>();
@@ -367,7 +467,8 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
 }
 
 int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_start, int nseg,
-                         int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word) {
+                         int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word,
+                         int32_t *zero_range, int zero_n) {
     if (nseg <= 0 || k <= 0) return PGV_OK;
     if (k > 4096) PGV_FAIL(PGV_ERR_ARG, "top-k: k = %d exceeds the supported 4096", k);
     int kp = 1;
@@ -376,7 +477,7 @@ int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_sta
     const int cap = kp > kFastCap ? kp : kFastCap;
     const size_t lds = (size_t)cap * 8 + sizeof(SelShared);
     hipLaunchKernelGGL(topk_kernel, dim3(nseg), dim3(kSelThreads), lds, ctx->stream, vals,
-                       seg_start, fixed_len, k, kp, cap, out_val, out_pos, zero_word);
+                       seg_start, fixed_len, k, kp, cap, out_val, out_pos, zero_word, zero_range, zero_n);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

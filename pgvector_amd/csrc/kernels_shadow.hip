@@ -114,6 +114,69 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
 // fp64 and rounded up into fp32.  One cast serves both consumers of a batch: cscale / ceps (null: not wanted) are the
 // factor 2^(1 + s_c + s_q) and the band term of the center ranking over the centers' shadow (RankShadowTerms), qscale /
 // qeps (null: not wanted) those of the list scan.
+//
+// The row is read ONCE, with 16-byte loads, into registers: a lane owns chunks of 8 consecutive elements (two loads, one
+// 16-byte store of fp16), kCastChunks of them cover rows up to 64 * 8 * kCastChunks = 2048 elements; a longer row is
+// read twice, chunk by chunk (once for the maximum, once for the cast).  The maximum and the cast are per element, so
+// the fp16 row and the power-of-two scales do not depend on which lane holds what.  The three fp64 sums run as four
+// independent chains per lane (element e of a chunk feeds chain e & 3) in place of one chain of ld / 64 dependent
+// FMAs; the order of summation differs from a single chain's, which the band terms allow: they are upper bounds formed
+// in fp64 (relative error of any order of n additions <= n 2^-53) and inflated by 2^-20 before they are rounded up.
+constexpr int kCastChunks = 4;
+
+struct CastChunk {
+    float4 a, b;
+};
+
+__device__ __forceinline__ float absmax_keep_nan(float m, float v) {
+    const float a = fabsf(v);
+    return (a > m || a != a) ? a : m;  // (NaN is kept: it poisons the scale's input, the band becomes infinite)
+}
+
+__device__ __forceinline__ CastChunk cast_chunk_load(const float *__restrict__ x, int c, int ld) {
+    CastChunk r;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    // (ld is a multiple of 4, ld16 of 8: the second half of the last chunk may lie past the fp32 row)
+    r.a = 8 * c < ld ? *reinterpret_cast<const float4 *>(x + 8 * c) : zero;
+    r.b = 8 * c + 4 < ld ? *reinterpret_cast<const float4 *>(x + 8 * c + 4) : zero;
+    return r;
+}
+
+__device__ __forceinline__ float cast_chunk_max(const CastChunk &r, float m) {
+    m = absmax_keep_nan(m, r.a.x);
+    m = absmax_keep_nan(m, r.a.y);
+    m = absmax_keep_nan(m, r.a.z);
+    m = absmax_keep_nan(m, r.a.w);
+    m = absmax_keep_nan(m, r.b.x);
+    m = absmax_keep_nan(m, r.b.y);
+    m = absmax_keep_nan(m, r.b.z);
+    m = absmax_keep_nan(m, r.b.w);
+    return m;
+}
+
+// the chunk's eight fp16 values as one 16-byte store; the elements below ld feed the sums (those past it are padding: 0)
+__device__ __forceinline__ void cast_chunk_store(const CastChunk &r, int c, int ld, int sq, double up, __half *__restrict__ h,
+                                                 double (&qq)[4], double (&dd)[4], double (&hh)[4]) {
+    const float xs[8] = {r.a.x, r.a.y, r.a.z, r.a.w, r.b.x, r.b.y, r.b.z, r.b.w};
+    union {
+        __half v[8];
+        uint4 w;
+    } out;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        __half v = __float2half(0.f);
+        if (8 * c + e < ld) {
+            v = __float2half(ldexpf(xs[e], -sq));
+            const double back = (double)__half2float(v) * up, xi = (double)xs[e];
+            qq[e & 3] = fma(xi, xi, qq[e & 3]);
+            dd[e & 3] = fma(xi - back, xi - back, dd[e & 3]);  // (xi - back: exact in fp64)
+            hh[e & 3] = fma(back, back, hh[e & 3]);
+        }
+        out.v[e] = v;
+    }
+    *reinterpret_cast<uint4 *>(h + 8 * c) = out.w;
+}
+
 __global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restrict__ queries, int nq, int ld, int ld16,
                                                            ShadowTerms st, RankShadowTerms rt,
                                                            const float *__restrict__ center_norm_max,
@@ -125,10 +188,21 @@ __global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restri
     if (q >= nq) return;
     const int lane = threadIdx.x & (kWave - 1);
     const float *x = queries + (size_t)q * ld;
+    __half *h = qcast + (size_t)q * ld16;
+    const int nchunks = ld16 / 8;
+    const bool in_regs = nchunks <= kWave * kCastChunks;  // (wavefront-uniform)
+    CastChunk reg[kCastChunks];
     float m = 0.f;
-    for (int i = lane; i < ld; i += kWave) {
-        const float a = fabsf(x[i]);
-        m = (a > m || a != a) ? a : m;
+    if (in_regs) {
+#pragma unroll
+        for (int j = 0; j < kCastChunks; j++) {
+            const int c = lane + j * kWave;
+            reg[j] = cast_chunk_load(x, c < nchunks ? c : nchunks, ld);  // (chunk nchunks: past the row, zeros, no load)
+        }
+#pragma unroll
+        for (int j = 0; j < kCastChunks; j++) m = cast_chunk_max(reg[j], m);
+    } else {
+        for (int c = lane; c < nchunks; c += kWave) m = cast_chunk_max(cast_chunk_load(x, c, ld), m);
     }
     for (int o = 32; o > 0; o >>= 1) {
         const float v = __shfl_xor(m, o);
@@ -136,19 +210,19 @@ __global__ __launch_bounds__(256) void shadow_query_kernel(const float *__restri
     }
     const int sq = scale_for(m);
     const double up = ldexp(1.0, sq);
-    double qq = 0.0, dd = 0.0, hh = 0.0;  // |q|^2, |q - q^|^2, |q^|^2
-    __half *h = qcast + (size_t)q * ld16;
-    for (int i = lane; i < ld16; i += kWave) {
-        __half v = __float2half(0.f);
-        if (i < ld) {
-            v = __float2half(ldexpf(x[i], -sq));
-            const double back = (double)__half2float(v) * up, xi = (double)x[i];
-            qq = fma(xi, xi, qq);
-            dd = fma(xi - back, xi - back, dd);  // (xi - back: exact in fp64)
-            hh = fma(back, back, hh);
+    double qq4[4] = {0.0, 0.0, 0.0, 0.0}, dd4[4] = {0.0, 0.0, 0.0, 0.0}, hh4[4] = {0.0, 0.0, 0.0, 0.0};
+    if (in_regs) {
+#pragma unroll
+        for (int j = 0; j < kCastChunks; j++) {
+            const int c = lane + j * kWave;
+            if (c < nchunks) cast_chunk_store(reg[j], c, ld, sq, up, h, qq4, dd4, hh4);
         }
-        h[i] = v;
+    } else {
+        for (int c = lane; c < nchunks; c += kWave) cast_chunk_store(cast_chunk_load(x, c, ld), c, ld, sq, up, h, qq4, dd4, hh4);
     }
+    double qq = (qq4[0] + qq4[1]) + (qq4[2] + qq4[3]);  // |q|^2
+    double dd = (dd4[0] + dd4[1]) + (dd4[2] + dd4[3]);  // |q - q^|^2
+    double hh = (hh4[0] + hh4[1]) + (hh4[2] + hh4[3]);  // |q^|^2
     for (int o = 32; o > 0; o >>= 1) {
         qq += __shfl_xor(qq, o);
         dd += __shfl_xor(dd, o);

@@ -153,6 +153,10 @@ struct ShadowBatch {
     float *pair_t = nullptr;                   // [nq x probes]
     bool scan_follows = false;                 // set by the caller: scan_batch_dev will run on the ranking's lists
     bool cast_for_scan = false, cast_for_rank = false, pairs_done = false;
+    // the ranking's kernels also cleared the plan's counters and counted the lists they emitted (PlanEmit; plan_nq x
+    // plan_probes: the batch the plan's buffers were reserved for)
+    bool plan_counted = false;
+    int plan_nq = 0, plan_probes = 0;
 };
 
 int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool for_rank, bool for_scan, ShadowBatch *sb) {
@@ -879,23 +883,39 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
             PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
                                true, ix->center_norms, nullptr));
         }
-        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, cand, sc.cand_val, sc.cand_pos, sc.flags + nq));
+        // the pair terms of the shadow scan that follows: q.c of the lists emitted, beside their exact distances
+        float *pair_t = (rank_sh && rank_env == 1 && scan_follows) ? sb->pair_t : nullptr;
+        // ... and its plan's counting: the buffers are sized here, ahead of the kernels that write them;
+        // the selection clears cnt | fill (every call: nothing is assumed of what an earlier call left), the recheck
+        // counts the lists where it emits them and batch_fix_kernel moves the counts of the queries it redoes
+        PlanEmit emit;
+        PlanBuffers pbuf;
+        if (pair_t) {
+            PGV_TRY(plan_batch_reserve(ctx, ix->nlists, nq, maxprobes, &pbuf));
+            emit.cnt = pbuf.cnt;
+            emit.probe_off = pbuf.probe_off;
+            emit.seg_len = pbuf.seg_len;
+            emit.list_off = ix->list_offsets;
+        }
+        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, cand, sc.cand_val, sc.cand_pos, sc.flags + nq,
+                                     emit.cnt, emit.cnt ? 2 * ix->nlists : 0));
         const ExactRows xr{ix->centers, nullptr, nullptr, ix->geom, ix->dtype,
                            reinterpret_cast<const unsigned *>(ix->center_norms + ix->nlists)};
         // (dense_scan: the 32-query kernel, its 16-wide form for a last group of <= 16 queries)
         ScanBound bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, false));
         if (rank_sh)  // |c|^2's rounding (worst case) and the exact form's; the rest is the per-query term ceps
             bound = {0.f, 0.f, gamma_n(ix->geom.ld / 64.0 + 10.0, 5.9604645e-8), bound.g_ref};
-        // the pair terms of the shadow scan that follows: q.c of the lists emitted, beside their exact distances
-        float *pair_t = (rank_sh && rank_env == 1 && scan_follows) ? sb->pair_t : nullptr;
         // a center's position in the matrix row is its id: cand_pos serves as the slots
         // the center ids leave as the int32 list ids the callers want (no conversion pass)
         PGV_TRY(launch_batch_recheck(ctx, xr, q_dev, nq, cand, maxprobes, sc.cand_val, sc.cand_pos, sc.cand_pos, nullptr,
                                      ix->nlists, bound, dist, nullptr, nullptr, sc.flags,
-                                     out_lists_dev, nullptr, nullptr, 0, rank_sh ? sb->ceps : nullptr, pair_t));
+                                     out_lists_dev, nullptr, nullptr, 0, rank_sh ? sb->ceps : nullptr, pair_t, emit));
         PGV_TRY(launch_batch_fix(ctx, xr, q_dev, nq, nullptr, nullptr, 0, nullptr, ix->nlists, sc.flags, mat, maxprobes,
-                                 bound, dist, nullptr, nullptr, out_lists_dev, rank_sh ? sb->ceps : nullptr, pair_t));
+                                 bound, dist, nullptr, nullptr, out_lists_dev, rank_sh ? sb->ceps : nullptr, pair_t, emit));
         sb->pairs_done = pair_t != nullptr;
+        sb->plan_counted = emit.cnt != nullptr;
+        sb->plan_nq = nq;
+        sb->plan_probes = maxprobes;
         return PGV_OK;
     } else {
         PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
@@ -1104,7 +1124,9 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
     if (shadow && !sb->cast_for_scan) PGV_TRY(shadow_batch_cast(ix, q_dev, nq, probes, false, true, sb));
     const float *pair_t = (shadow && sb->pairs_done) ? sb->pair_t : nullptr;
     PlanResult plan;
-    PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, qt, rows_per_task, ctx->profiling, &plan, pair_t));
+    // (the ranking of this very batch counted into the plan's buffers: what is left of the plan is two launches)
+    const bool counted = pair_t && sb->plan_counted && sb->plan_nq == nq && sb->plan_probes == probes;
+    PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, qt, rows_per_task, ctx->profiling, &plan, pair_t, counted));
 
     int kprime = k;
     ApproxScratch sc;
@@ -1252,6 +1274,32 @@ int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *pr
     PGV_TRY(stage_flat(ctx, probe_lists, sizeof(int32_t) * (size_t)nq * probes, ctx->idx_stage, &pl_dev));
     return scan_batch_dev(ix, q_dev, nq, static_cast<const int32_t *>(pl_dev), probes, k, out_dist, out_slot,
                           out_tid);
+}
+
+// the query cast of the shadow paths on its own (tests: shadow_query_kernel's outputs against a host model)
+int pgv_index_shadow_cast(pgv_index *ix, const void *queries, int nq, void *out_qcast, float *out_qscale, float *out_qeps,
+                          float *out_cscale, float *out_ceps) {
+    if (!ix || !queries || nq < 1) PGV_FAIL(PGV_ERR_ARG, "pgv_index_shadow_cast: index/queries is NULL or nq < 1");
+    if (!ix->shadow || !ix->cshadow) PGV_FAIL(PGV_ERR_STATE, "pgv_index_shadow_cast: the index has no fp16 shadow");
+    pgv_ctx *ctx = ix->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    const void *q_dev;
+    PGV_TRY(stage_rows(ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ctx->q_stage, &q_dev));
+    ShadowBatch sb;
+    PGV_TRY(shadow_batch_cast(ix, q_dev, nq, 1, true, true, &sb));
+    const struct {
+        void *dst;
+        const void *src;
+        size_t bytes;
+    } parts[] = {{out_qcast, sb.qcast, (size_t)nq * ix->shadow_geom.ld * sizeof(uint16_t)},
+                 {out_qscale, sb.qscale, sizeof(float) * (size_t)nq},
+                 {out_qeps, sb.qeps, sizeof(float) * (size_t)nq},
+                 {out_cscale, sb.cscale, sizeof(float) * (size_t)nq},
+                 {out_ceps, sb.ceps, sizeof(float) * (size_t)nq}};
+    for (const auto &p : parts)
+        if (p.dst) PGV_HIP(hipMemcpyAsync(p.dst, p.src, p.bytes, hipMemcpyDefault, ctx->stream));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    return PGV_OK;
 }
 
 // ------------------------------------------------------- one query at a time

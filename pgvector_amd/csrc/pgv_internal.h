@@ -558,12 +558,32 @@ struct PlanResult {
     int64_t *probe_off = nullptr; // device [nq x probes]
     int64_t *pair_start = nullptr; // device [nlists + 1]: the first pair of each list
 };
+// the plan's device scratch of one batch (ctx->plan_a / plan_b, carved)
+struct PlanBuffers {
+    int *cnt = nullptr, *fill = nullptr;                    // [nlists] queries per list | the pairs' scatter cursors
+    int64_t *probe_off = nullptr, *seg_len = nullptr;       // [nq x probes] | [nq]: a query's lists inside its segment
+    int64_t *seg_start = nullptr, *pair_start = nullptr, *task_start = nullptr, *totals = nullptr;
+};
+// sizes and carves them.  launch_plan_batch calls it; pgv_search_batch calls it AHEAD of a ranking whose kernels clear
+// and fill cnt / probe_off / seg_len (PlanEmit), so that the buffers do not move in between
+int plan_batch_reserve(pgv_ctx *ctx, int nlists, int nq, int probes, PlanBuffers *pb);
+// what the ranking's exact tail does of the plan while it emits a query's lists (batch_recheck_kernel<float, true>,
+// batch_fix_kernel): cnt[list] += 1 per list emitted, the query's probe_off prefix and seg_len.  cnt == null: nothing
+struct PlanEmit {
+    int *cnt = nullptr;
+    int64_t *probe_off = nullptr, *seg_len = nullptr;
+    const int64_t *list_off = nullptr;  // the INDEX's list offsets (the ranking's rows are the centers)
+};
 // pair_t: [nq x probes] the pairs' t = -2 q.c_l in probe order (the shadow scan; from the ranking), or null: t = 0
+// counted: cnt | fill were cleared and cnt, probe_off and seg_len written by the ranking of this batch (PlanEmit) --
+// no memset, no plan_count_kernel, pairs and tasks in one launch, the profiling totals inside plan_scan_kernel
 int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists, int nq,
                       int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res,
-                      const float *pair_t = nullptr);
+                      const float *pair_t = nullptr, bool counted = false);
+// zero_word / zero_range[zero_n]: words that kernels LATER in the stream start from zero, cleared here (or null)
 int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_start, int nseg,
-                         int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word = nullptr);
+                         int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word = nullptr,
+                         int32_t *zero_range = nullptr, int zero_n = 0);
 int launch_positions_to_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists,
                               const int64_t *probe_off, int nq, int probes, int k,
                               const int64_t *pos, int64_t *out_slot, uint64_t *out_tid);
@@ -584,15 +604,16 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
                          int32_t *out_i32 = nullptr, const int32_t *probe_lists = nullptr,
                          const int64_t *probe_off = nullptr, int probes = 0,
                          const float *eps_add = nullptr,   // cand_slot null: slots from the positions; eps_add: per query
-                         float *pair_t = nullptr);         // term of the band (the shadow paths), or null; pair_t: fp32
-                                                           // rows only, [nq x k] -2 q.row of the rows emitted, or null
+                         float *pair_t = nullptr,          // term of the band (the shadow paths), or null; pair_t: fp32
+                         const PlanEmit &emit = PlanEmit());  // rows only, [nq x k] -2 q.row of the rows emitted, or null;
+                                                              // emit: with pair_t only (the center ranking)
 // the flagged queries start to end: exact scores of the whole segment, head, output row (out_slot: row slots, or
 // center ids for the dense form)
 int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
                      const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
                      const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
                      uint64_t *out_tid, int32_t *out_i32 = nullptr, const float *eps_add = nullptr,
-                     float *pair_t = nullptr);
+                     float *pair_t = nullptr, const PlanEmit &emit = PlanEmit());
 int launch_iota_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *lists_dev, int nlists,
                       const int64_t *probe_off, int64_t *out_slot);
 
