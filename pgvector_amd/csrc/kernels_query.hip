@@ -921,24 +921,53 @@ int launch_multi_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int 
     return PGV_OK;
 }
 
-int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, int kprime, int k,
-                         const float *approx_val, const int64_t *cand_pos, const int64_t *cand_slot,
-                         const int64_t *seg_start, int64_t fixed_len, const ScanBound &bound,
-                         float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags, int32_t *out_i32,
-                         const int32_t *probe_lists, const int64_t *probe_off, int probes, const float *eps_add,
-                         float *pair_t, const PlanEmit &emit) {
-    if (nq <= 0) return PGV_OK;
-    if (emit.cnt && !(pair_t && out_i32 && emit.probe_off && emit.seg_len && emit.list_off))
-        PGV_FAIL(PGV_ERR_ARG, "recheck: the plan is counted where the pair terms are written");
-    if (kprime > kRecheckCap || k > kprime) PGV_FAIL(PGV_ERR_ARG, "recheck: k' = %d outside k..%d", kprime, kRecheckCap);
-    if (pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "recheck: pair terms are for fp32 rows");
-#define PGV_RECHECK(T, DOT)                                                                                         \
-    hipLaunchKernelGGL((batch_recheck_kernel<T, DOT>), dim3(nq), dim3(kQThreads), 0, ctx->stream,                    \
-                       static_cast<const char *>(xr.vectors), xr.tids, xr.geom.nvec, xr.geom.lpr_log2,               \
-                       static_cast<const char *>(q_dev), kprime, k, approx_val, cand_pos, cand_slot, xr.list_offsets, \
-                       probe_lists, probe_off, probes, seg_start, fixed_len, xr.norm_max, bound, eps_add, nq, out_dist, out_slot,  \
-                       out_tid, out_i32, flags, pair_t, emit)
-    if (pair_t)
+namespace {
+struct ApproxScratch {  // the tail's candidates and flags, carved from the caller's buffer
+    float *cand_val = nullptr;   // [nq x kprime] approximate values, ascending
+    int64_t *cand_pos = nullptr; // [nq x kprime] positions in the query's segment (the row slots of a dense run)
+    int32_t *flags = nullptr;    // [nq] flags | count | list of flagged queries
+    int carve(DBuf &buf, int nq, int kprime) {
+        const size_t nk = (size_t)nq * kprime;
+        const size_t a1 = (sizeof(float) * nk + 15) & ~(size_t)15, a2 = a1 + sizeof(int64_t) * nk;
+        PGV_TRY(buf.ensure(a2 + sizeof(int32_t) * (2 * (size_t)nq + 1)));
+        cand_val = buf.as<float>();
+        cand_pos = reinterpret_cast<int64_t *>(buf.as<char>() + a1);
+        flags = reinterpret_cast<int32_t *>(buf.as<char>() + a2);
+        return PGV_OK;
+    }
+};
+}  // namespace
+
+int launch_exact_tail(pgv_ctx *ctx, const ExactTail &t, DBuf &scratch) {
+    if (t.nq <= 0) return PGV_OK;
+    const ExactRows &xr = t.rows;
+    const bool dense = t.dense();
+    if (dense ? (t.fixed_len <= 0 || t.probe_off || t.seg_start || t.probes != 0)
+              : (t.fixed_len != 0 || !t.probe_off || !t.seg_start || t.probes < 1))
+        PGV_FAIL(PGV_ERR_ARG, "exact tail: a list plan or one dense run");
+    if (t.kprime > kRecheckCap || t.k > t.kprime)
+        PGV_FAIL(PGV_ERR_ARG, "exact tail: k' = %d outside k..%d", t.kprime, kRecheckCap);
+    if (t.pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "exact tail: pair terms are for fp32 rows");
+    static_assert(kWide >= kRecheckCap, "k <= k' <= kWide: batch_fix_kernel's emit");
+    if (t.emit.cnt && !(dense && t.pair_t && t.out_i32 && t.emit.probe_off && t.emit.seg_len && t.emit.list_off))
+        PGV_FAIL(PGV_ERR_ARG, "exact tail: the plan is counted where the pair terms are written");
+    ApproxScratch sc;
+    PGV_TRY(sc.carve(scratch, t.nq, t.kprime));
+    const int64_t *cand_slot = dense ? sc.cand_pos : nullptr;  // a dense run's positions ARE the slots
+    const int64_t *seg_start = dense ? nullptr : t.seg_start;
+    const int64_t fixed_len = dense ? t.fixed_len : 0;
+    // flags[nq], the flagged-query count, starts from zero; so do the plan's cnt | fill under emit (one word per list
+    // each; the ranking's rows are the centers: fixed_len lists)
+    PGV_TRY(launch_topk_segments(ctx, t.approx, seg_start, t.nq, fixed_len, t.kprime, sc.cand_val, sc.cand_pos,
+                                 sc.flags + t.nq, t.emit.cnt, t.emit.cnt ? 2 * (int)fixed_len : 0));
+#define PGV_RECHECK(T, DOT)                                                                                          \
+    hipLaunchKernelGGL((batch_recheck_kernel<T, DOT>), dim3(t.nq), dim3(kQThreads), 0, ctx->stream,                   \
+                       static_cast<const char *>(xr.vectors), xr.tids, xr.geom.nvec, xr.geom.lpr_log2,                \
+                       static_cast<const char *>(t.queries), t.kprime, t.k, sc.cand_val, sc.cand_pos, cand_slot,      \
+                       xr.list_offsets, t.probe_lists, t.probe_off, t.probes, seg_start, fixed_len, xr.norm_max,      \
+                       t.bound, t.eps_add, t.nq, t.out_dist, t.out_slot, t.out_tid, t.out_i32, sc.flags, t.pair_t,    \
+                       t.emit)
+    if (t.pair_t)
         PGV_RECHECK(float, true);
     else if (xr.dtype == PGV_F32)
         PGV_RECHECK(float, false);
@@ -946,32 +975,19 @@ int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, i
         PGV_RECHECK(__half, false);
 #undef PGV_RECHECK
     PGV_HIP(hipGetLastError());
-    return PGV_OK;
-}
-
-int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
-                     const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
-                     const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32, const float *eps_add, float *pair_t, const PlanEmit &emit) {
-    if (nq <= 0) return PGV_OK;
-    if (emit.cnt && !(pair_t && out_i32 && k <= kWide && emit.probe_off && emit.seg_len && emit.list_off))
-        PGV_FAIL(PGV_ERR_ARG, "fix: the plan is counted where the pair terms are written, k <= %d", kWide);
-    if (pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "fix: pair terms are for fp32 rows");
     // (the ranking's flagged queries count like the list scan's: pgv_stats scan_widened_queries / scan_redo_queries)
     double *stats = (ctx->profiling && ctx->stats_dev.p) ? ctx->stats_dev.as<double>() : nullptr;
-    if (k > 4096) PGV_FAIL(PGV_ERR_ARG, "top-k: k = %d exceeds the supported 4096", k);
     int kp = 2;
-    while (kp < k) kp <<= 1;
+    while (kp < t.k) kp <<= 1;
     const int cap = kp > kFastCap ? kp : kFastCap;
-    const int widen = ctx->no_widen ? 0 : 1;
     const size_t lds = (size_t)cap * 8 + sizeof(SelShared);
-    const int grid = nq < ctx->num_cus ? nq : ctx->num_cus;
-#define PGV_FIX(T)                                                                                                   \
-    hipLaunchKernelGGL(batch_fix_kernel<T>, dim3(grid), dim3(kQThreads), lds, ctx->stream,                           \
-                       static_cast<const char *>(xr.vectors), xr.list_offsets, xr.tids, xr.geom.nvec,                \
-                       xr.geom.lpr_log2, static_cast<const char *>(q_dev), probe_lists, probe_off, probes, seg_start, \
-                       fixed_len, flags, nq, seg_vals, k, kp, cap, xr.norm_max, bound, eps_add, widen, out_dist,      \
-                       out_slot, out_tid, out_i32, stats, pair_t, emit)
+    const int grid = t.nq < ctx->num_cus ? t.nq : ctx->num_cus;
+#define PGV_FIX(T)                                                                                                    \
+    hipLaunchKernelGGL(batch_fix_kernel<T>, dim3(grid), dim3(kQThreads), lds, ctx->stream,                            \
+                       static_cast<const char *>(xr.vectors), xr.list_offsets, xr.tids, xr.geom.nvec,                 \
+                       xr.geom.lpr_log2, static_cast<const char *>(t.queries), t.probe_lists, t.probe_off, t.probes,  \
+                       seg_start, fixed_len, sc.flags, t.nq, t.approx, t.k, kp, cap, xr.norm_max, t.bound, t.eps_add, \
+                       ctx->no_widen ? 0 : 1, t.out_dist, t.out_slot, t.out_tid, t.out_i32, stats, t.pair_t, t.emit)
     if (xr.dtype == PGV_F32)
         PGV_FIX(float);
     else

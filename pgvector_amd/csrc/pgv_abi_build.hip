@@ -135,22 +135,24 @@ int pgv_exact_topk(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, co
         // 128 queries instead of once per 32
         const bool dense128 = mfma && cn >= 128 && n >= 128 && !no_dense;
         if (mfma && metric == PGV_L2SQ) {
-            ApproxScratch sc;
-            PGV_TRY(sc.carve(ctx, ctx->ms_b, cn, kprime));
+            ExactTail tail;
+            tail.rows = {r_dev, nullptr, nullptr, g, dtype, reinterpret_cast<const unsigned *>(norms + n)};
+            tail.queries = qp;
+            tail.nq = cn;
+            tail.kprime = kprime;
+            tail.k = k;
+            tail.approx = mat;
+            tail.fixed_len = n;  // a row's position in the matrix row is its index
             // the candidates are proven complete with the rounding bound of the kernel that produced the values
-            const ScanBound bound = scan_bound_chain(ctx, g.ld, dense128 ? dense_chain_length(g, dtype)
-                                                                          : scan_chain_length(g, dtype, false));
+            tail.bound = scan_bound_chain(ctx, g.ld, dense128 ? dense_chain_length(g, dtype)
+                                                              : scan_chain_length(g, dtype, false));
+            tail.out_dist = cd;
+            tail.out_slot = ci;
             if (dense128)
                 PGV_TRY(launch_mfma_dense(ctx, metric, dtype, g, r_dev, n, qp, cn, norms, mat, n));
             else
                 PGV_TRY(dense_scan(ctx, metric, dtype, g, r_dev, n, qp, cn, n, mat, true, norms, nullptr));
-            PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, kprime, sc.cand_val, sc.cand_pos, sc.flags + cn));
-            const ExactRows xr{r_dev, nullptr, nullptr, g, dtype, reinterpret_cast<const unsigned *>(norms + n)};
-            // a row's position in the matrix row is its index: cand_pos serves as the slots
-            PGV_TRY(launch_batch_recheck(ctx, xr, qp, cn, kprime, k, sc.cand_val, sc.cand_pos, sc.cand_pos, nullptr, n,
-                                         bound, cd, ci, nullptr, sc.flags));
-            PGV_TRY(launch_batch_fix(ctx, xr, qp, cn, nullptr, nullptr, 0, nullptr, n, sc.flags, mat, k, bound,
-                                     cd, ci, nullptr));
+            PGV_TRY(launch_exact_tail(ctx, tail, ctx->ms_b));
         } else {
             if (dense128)
                 PGV_TRY(launch_mfma_dense(ctx, metric, dtype, g, r_dev, n, qp, cn, nullptr, mat, n));

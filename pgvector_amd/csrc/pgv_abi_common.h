@@ -356,28 +356,9 @@ struct Rng {
 
 }  // namespace
 
-// ---- shared by the IVFFlat scans and the exact scan: the candidates of the MFMA L2 paths
+// ---- shared by the IVFFlat scans and the exact scan
 namespace {
 
-struct ApproxScratch {
-    float *cand_val = nullptr;   // [nq x kprime] approximate values, ascending
-    int64_t *cand_pos = nullptr; // [nq x kprime] positions in the query's segment (center ids for the ranking)
-    int32_t *flags = nullptr;    // [nq] flags | count | list of flagged queries
-    int carve(pgv_ctx *ctx, DBuf &buf, int nq, int kprime) {
-        (void)ctx;
-        const size_t nk = (size_t)nq * kprime;
-        const size_t a1 = (sizeof(float) * nk + 15) & ~(size_t)15, a2 = a1 + sizeof(int64_t) * nk,
-                     a3 = a2 + sizeof(int32_t) * (2 * (size_t)nq + 1);
-        PGV_TRY(buf.ensure(a3));
-        char *b = buf.as<char>();
-        cand_val = reinterpret_cast<float *>(b);
-        cand_pos = reinterpret_cast<int64_t *>(b + a1);
-        flags = reinterpret_cast<int32_t *>(b + a2);  // flags[nq], the count, is cleared by the candidates' top-k launch
-        return PGV_OK;
-    }
-};
-
-// k' of the MFMA L2 selections: the head asked for and a margin the rounding bound clears easily
 // Device memory that another process may map (pgv_index_export / pgv_hnsw_export: hipIpcGetMemHandle, dmabuf mode).
 // The runtime carves allocations below 2 MiB out of shared 2 MiB blocks; the handle of such a fragment is the BLOCK's,
 // and on this pool's driver (round 6, two boxes, every run) hipIpcGetMemHandle of a small mirror returned "invalid
@@ -390,6 +371,11 @@ static inline hipError_t malloc_exportable(void **p, size_t bytes) {
     return hipMalloc(p, rounded ? rounded : kExportGranule);
 }
 
+// k' of the MFMA L2 paths: the candidates kept per query by the expansion's values, 32 .. 256 -- the head asked for and
+// a margin the rounding bound clears easily.  4 k rounded UP to the power of two the selection pads to anyway (k = 10:
+// 64 instead of 40 at no cost in topk_kernel, and the recheck reads only the rounding band's prefix) -- which is what
+// lets the deterministic band of a 3072-d halfvec scan (~50 candidates wide) fit without the widening pass; k + 64 past
+// 64, while that fits batch_recheck_kernel's 256
 static int approx_candidates(int k) {
     if (k <= 8) return 32;
     if (4 * k > 256) return k + 64;

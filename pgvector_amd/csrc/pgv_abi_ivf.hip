@@ -151,12 +151,10 @@ struct ShadowBatch {
     float *qscale = nullptr, *qeps = nullptr;  // the list scan's factors 2^(1 + s + s_q) and band terms
     float *cscale = nullptr, *ceps = nullptr;  // the ranking's 2^(1 + s_c + s_q) and band terms
     float *pair_t = nullptr;                   // [nq x probes]
-    bool scan_follows = false;                 // set by the caller: scan_batch_dev will run on the ranking's lists
-    bool cast_for_scan = false, cast_for_rank = false, pairs_done = false;
-    // the ranking's kernels also cleared the plan's counters and counted the lists they emitted (PlanEmit; plan_nq x
-    // plan_probes: the batch the plan's buffers were reserved for)
-    bool plan_counted = false;
-    int plan_nq = 0, plan_probes = 0;
+    bool scan_follows = false;                 // set by the caller: the shadow scan will run on the ranking's lists
+    bool cast_for_scan = false;                // qscale / qeps are written
+    // the ranking left pair_t, cleared the plan's counters and counted the lists it emitted into them (PlanEmit)
+    bool pairs_done = false;
 };
 
 int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool for_rank, bool for_scan, ShadowBatch *sb) {
@@ -177,7 +175,7 @@ int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool
     st.P = ix->shadow_P;
     st.g_dot = gamma_n(shadow_chain_length(g16) + 4.0, u);
     st.g_pair = gamma_n((double)pair_chain_length(ix->geom), u);
-    st.g_cn = gamma_n(ix->geom.ld / 64.0 + 10.0, u);
+    st.g_cn = shadow_band(ix->geom.ld, 0.f, u).g_norm;
     RankShadowTerms rt{};
     rt.s = ix->cshadow_s;
     rt.E = ix->cshadow_E;
@@ -189,16 +187,7 @@ int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool
                                 for_scan ? sb->qeps : nullptr, for_rank ? sb->cscale : nullptr,
                                 for_rank ? sb->ceps : nullptr));
     sb->cast_for_scan = for_scan;
-    sb->cast_for_rank = for_rank;
     return PGV_OK;
-}
-
-// the list scan of this batch would read the row shadow (scan_batch_impl's own conditions, known before the ranking)
-bool shadow_scan_expected(const pgv_index *ix, int nq, int probes, int k) {
-    const double share = (double)nq * probes / (double)ix->nlists;
-    const bool small = (share <= 0.4 || nq <= 4) && nq <= 1024 && probes <= query_max_batch_lists() && k <= query_head_cap();
-    return !small && share > 3.0 && k <= 192 && !ix->ctx->no_mfma_scan && ix->metric == PGV_L2SQ && ix->row_norms &&
-           ix->shadow && shadow_env() != 0;
 }
 
 // The mirror of an index whose list offsets are known: one allocation, host tables, the norms the MFMA paths want.
@@ -826,9 +815,6 @@ int pgv_index_tids(pgv_index *ix, const int64_t *slots, int64_t n, uint64_t *out
 int64_t pgv_index_rows(const pgv_index *ix) { return ix ? ix->nrows : -1; }
 int pgv_index_lists(const pgv_index *ix) { return ix ? ix->nlists : -1; }
 
-// scratch of an approximate (MFMA) L2 pass over nq queries keeping kprime candidates each
-
-
 // device-side core of GetScanLists for nq staged queries
 static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprobes,
                            int32_t *out_lists_dev, float *out_dist_dev, ShadowBatch *sb) {
@@ -866,8 +852,6 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
     const bool mfma = nq >= 128 && ix->nlists >= 64 && !ctx->no_mfma_scan &&
                       (ix->metric == PGV_NEG_IP || (ix->metric == PGV_L2SQ && ix->center_norms && cand <= 256));
     if (mfma && ix->metric == PGV_L2SQ) {
-        ApproxScratch sc;
-        PGV_TRY(sc.carve(ctx, ctx->ms_b, nq, cand));
         // fp32 centers with an fp16 copy: the expansion only picks the candidates, so it multiplies the
         // copy and the cast queries -- the three-stage fp16 form of the kernel, half the bytes -- and the band grows by
         // the per-query term ceps (pgv_internal.h).  The cast runs here, once for the batch: the list scan that follows
@@ -884,38 +868,32 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
                                true, ix->center_norms, nullptr));
         }
         // the pair terms of the shadow scan that follows: q.c of the lists emitted, beside their exact distances
-        float *pair_t = (rank_sh && rank_env == 1 && scan_follows) ? sb->pair_t : nullptr;
+        ExactTail tail;
+        tail.pair_t = (rank_sh && rank_env == 1 && scan_follows) ? sb->pair_t : nullptr;
         // ... and its plan's counting: the buffers are sized here, ahead of the kernels that write them;
         // the selection clears cnt | fill (every call: nothing is assumed of what an earlier call left), the recheck
         // counts the lists where it emits them and batch_fix_kernel moves the counts of the queries it redoes
-        PlanEmit emit;
         PlanBuffers pbuf;
-        if (pair_t) {
+        if (tail.pair_t) {
             PGV_TRY(plan_batch_reserve(ctx, ix->nlists, nq, maxprobes, &pbuf));
-            emit.cnt = pbuf.cnt;
-            emit.probe_off = pbuf.probe_off;
-            emit.seg_len = pbuf.seg_len;
-            emit.list_off = ix->list_offsets;
+            tail.emit = {pbuf.cnt, pbuf.probe_off, pbuf.seg_len, ix->list_offsets};
         }
-        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, cand, sc.cand_val, sc.cand_pos, sc.flags + nq,
-                                     emit.cnt, emit.cnt ? 2 * ix->nlists : 0));
-        const ExactRows xr{ix->centers, nullptr, nullptr, ix->geom, ix->dtype,
-                           reinterpret_cast<const unsigned *>(ix->center_norms + ix->nlists)};
+        tail.rows = {ix->centers, nullptr, nullptr, ix->geom, ix->dtype,
+                     reinterpret_cast<const unsigned *>(ix->center_norms + ix->nlists)};
+        tail.queries = q_dev;
+        tail.nq = nq;
+        tail.kprime = cand;
+        tail.k = maxprobes;
+        tail.approx = mat;
+        tail.fixed_len = ix->nlists;  // a center's position in the matrix row is its id
         // (dense_scan: the 32-query kernel, its 16-wide form for a last group of <= 16 queries)
-        ScanBound bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, false));
-        if (rank_sh)  // |c|^2's rounding (worst case) and the exact form's; the rest is the per-query term ceps
-            bound = {0.f, 0.f, gamma_n(ix->geom.ld / 64.0 + 10.0, 5.9604645e-8), bound.g_ref};
-        // a center's position in the matrix row is its id: cand_pos serves as the slots
-        // the center ids leave as the int32 list ids the callers want (no conversion pass)
-        PGV_TRY(launch_batch_recheck(ctx, xr, q_dev, nq, cand, maxprobes, sc.cand_val, sc.cand_pos, sc.cand_pos, nullptr,
-                                     ix->nlists, bound, dist, nullptr, nullptr, sc.flags,
-                                     out_lists_dev, nullptr, nullptr, 0, rank_sh ? sb->ceps : nullptr, pair_t, emit));
-        PGV_TRY(launch_batch_fix(ctx, xr, q_dev, nq, nullptr, nullptr, 0, nullptr, ix->nlists, sc.flags, mat, maxprobes,
-                                 bound, dist, nullptr, nullptr, out_lists_dev, rank_sh ? sb->ceps : nullptr, pair_t, emit));
-        sb->pairs_done = pair_t != nullptr;
-        sb->plan_counted = emit.cnt != nullptr;
-        sb->plan_nq = nq;
-        sb->plan_probes = maxprobes;
+        tail.bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, false));
+        if (rank_sh) tail.bound = shadow_band(ix->geom.ld, tail.bound.g_ref);
+        tail.eps_add = rank_sh ? sb->ceps : nullptr;
+        tail.out_dist = dist;
+        tail.out_i32 = out_lists_dev;  // the center ids leave as the int32 list ids the callers want (no conversion pass)
+        PGV_TRY(launch_exact_tail(ctx, tail, ctx->ms_b));
+        sb->pairs_done = tail.pair_t != nullptr;
         return PGV_OK;
     } else {
         PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
@@ -1043,11 +1021,6 @@ int pgv_scan_lists(pgv_index *ix, const void *query, const int32_t *lists, int n
     return sync_if(ctx, need);
 }
 
-// k' of the MFMA L2 paths: the candidates kept per query by the expansion's values.  4 k rounded UP to the power of two
-// the selection pads to anyway (k = 10: 64 instead of 40 at no cost in topk_kernel, and the recheck reads only the
-// rounding band's prefix) -- which is what lets the deterministic band of a 3072-d halfvec scan (~50 candidates wide)
-// fit without the widening pass; k + 64 past 64
-
 // GetScanItems + head of the sorted stream for staged queries and device probe lists
 // lanes of overlapping batches: this stream's list scan starts when the previous lane's has ended
 static int scan_turn_begin(pgv_ctx *ctx) {
@@ -1059,17 +1032,61 @@ static int scan_turn_end(pgv_ctx *ctx) {
     return PGV_OK;
 }
 
-static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
-                           int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid, ShadowBatch *sb) {
-    pgv_ctx *ctx = ix->ctx;
-    // invert to list-major work.  Queries per list on average decides how wide a group is
-    // worth.  Lists probed by more than 8 queries go to the tile kernel (16 queries per pass
-    // over the rows) when the row shape allows it.
+// What the batched list scan does with nq queries x probes lists and heads of k, decided from the batch's shape before
+// anything is launched: scan_batch_impl follows it, and pgv_search_batch tells the ranking of it ahead of time (`shadow`)
+struct ScanPath {
+    bool per_query = false;  // every query scans its own lists: mq_scan_kernel + mq_head_kernel, nothing below applies
+    bool use_mfma = false;   // the matrix cores (32 queries per pass)
+    bool use_tile = false;   // the tile kernel (16 queries per pass over the rows)
+    bool wide = false;       // the 64-query form of the matrix-core kernel
+    int qt = 0, rows_per_task = 0;  // queries | rows per task
+    bool approx = false;     // MFMA L2: the values only pick candidates, the exact tail decides
+    bool shadow = false;     // ... and come from the fp16 residual shadow (kernels_shadow.hip): half the bytes
+};
+static ScanPath scan_path(const pgv_index *ix, int nq, int probes, int k) {
+    ScanPath p;
+    // invert to list-major work.  Queries per list on average decides how wide a group is worth.  Lists probed by more
+    // than 8 queries go to the tile kernel (16 queries per pass over the rows) when the row shape allows it.
     const double share = (double)nq * probes / (double)ix->nlists;
     // Too few queries to share rows between them (every probed list belongs to one query): the list-major plan
     // gains nothing and costs a dozen launches.  Each query scans its own lists (mq_scan_kernel) and selects
     // its own head (mq_head_kernel): two launches, the single-query kernels with one grid row per query.
-    if ((share <= 0.4 || nq <= 4) && nq <= 1024 && probes <= query_max_batch_lists() && k <= query_head_cap()) {
+    p.per_query = (share <= 0.4 || nq <= 4) && nq <= 1024 && probes <= query_max_batch_lists() && k <= query_head_cap();
+    if (p.per_query) return p;
+    // ... and to the matrix cores (32 queries per pass) for L2 / inner product heads of up to 192
+    p.use_mfma = share > 3.0 && k <= 192 && !ix->ctx->no_mfma_scan &&
+                 (ix->metric == PGV_NEG_IP || (ix->metric == PGV_L2SQ && ix->row_norms));
+    p.use_tile = !p.use_mfma && tile_scan_supported(ix->geom) && share > 8.0;
+    // lists probed by more than 32 queries of the batch are streamed once per group of `qt` queries: from ~12 queries per
+    // list on average (configs[2] / [4]: 1024 x 64 probes over 4096 lists = 16) enough lists pass 32 for the 64-query
+    // form of the kernel to pay (PGV_SCAN_WIDE = 0 / 1 forces it off / on: A/B)
+    static const int wide_env = [] {
+        const char *e = getenv("PGV_SCAN_WIDE");
+        return e ? atoi(e) : -1;
+    }();
+    // measured (10 M rows, lists 4096, probes 64, 1024 queries): 3072-d fp16 88.5 k -> 93.3 k QPS (scan 10.81 -> 10.19 ms); 1536-d
+    // fp32: HBM traffic -16 % (passes 1.26 -> 1.06) but the scan only 11.83 -> 11.43 ms, 81.7 k -> 84.4 k QPS (round 6; one GPU's
+    // share 612 k -> 640 k) -- a task of two fp32 tiles per stage fill runs the matrix pipes at ~90 %, so the 64-query form
+    // buys a few per cent there, not the traffic's 16; below ~12 queries per list it costs (headline, share 10: -3 %)
+    p.wide = p.use_mfma && (wide_env < 0 ? share > 12.0 : wide_env != 0);
+    p.qt = p.use_mfma ? (p.wide ? mfma_scan_queries_per_task_wide() : mfma_scan_queries_per_task())
+                      : (p.use_tile ? tile_scan_queries_per_task()
+                                    : scan_group_size(ix->geom, ix->dtype, (int)std::ceil(share)));
+    constexpr int rpt_tiles = 20;  // tiles per task (measured best of 10 / 20 / 40 / 80 on the headline batch)
+    p.rows_per_task = p.use_mfma ? mfma_scan_rows_per_task()
+                                 : (p.use_tile ? rpt_tiles * tile_scan_tile_rows(ix->geom)
+                                               : (p.qt >= 16 ? 256 : (p.qt >= 4 ? 128 : 64)));
+    p.approx = p.use_mfma && ix->metric == PGV_L2SQ;
+    // fp32 L2 with the fp16 residual shadow: the scan streams half the bytes
+    p.shadow = p.approx && ix->shadow && shadow_env() != 0;
+    return p;
+}
+
+static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
+                           int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid, ShadowBatch *sb) {
+    pgv_ctx *ctx = ix->ctx;
+    const ScanPath path = scan_path(ix, nq, probes, k);
+    if (path.per_query) {
         const int64_t bound = ix->len_prefix[probes];  // rows of the `probes` longest lists
         const int64_t seg_stride = (bound + 7) / 4 * 4;
         PGV_TRY(ctx->plan_d.ensure(sizeof(float) * (size_t)nq * seg_stride));
@@ -1090,61 +1107,17 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
         PGV_TRY(ot.finish(ctx, &need));
         return sync_if(ctx, need);
     }
-    // ... and to the matrix cores (32 queries per pass) for L2 / inner product heads of up to 192
-    const bool use_mfma = share > 3.0 && k <= 192 && !ctx->no_mfma_scan &&
-                          (ix->metric == PGV_NEG_IP || (ix->metric == PGV_L2SQ && ix->row_norms));
-    const bool use_tile = !use_mfma && tile_scan_supported(ix->geom) && share > 8.0;
-    // lists probed by more than 32 queries of the batch are streamed once per group of `qt` queries: from ~12 queries per
-    // list on average (configs[2] / [4]: 1024 x 64 probes over 4096 lists = 16) enough lists pass 32 for the 64-query
-    // form of the kernel to pay (PGV_SCAN_WIDE = 0 / 1 forces it off / on: A/B)
-    static const int wide_env = [] {
-        const char *e = getenv("PGV_SCAN_WIDE");
-        return e ? atoi(e) : -1;
-    }();
-    // measured (10 M rows, lists 4096, probes 64, 1024 queries): 3072-d fp16 88.5 k -> 93.3 k QPS (scan 10.81 -> 10.19 ms); 1536-d
-    // fp32: HBM traffic -16 % (passes 1.26 -> 1.06) but the scan only 11.83 -> 11.43 ms, 81.7 k -> 84.4 k QPS (round 6; one GPU's
-    // share 612 k -> 640 k) -- a task of two fp32 tiles per stage fill runs the matrix pipes at ~90 %, so the 64-query form
-    // buys a few per cent there, not the traffic's 16; below ~12 queries per list it costs (headline, share 10: -3 %)
-    const bool wide = use_mfma && (wide_env < 0 ? share > 12.0 : wide_env != 0);
-    const int qt = use_mfma ? (wide ? mfma_scan_queries_per_task_wide() : mfma_scan_queries_per_task())
-                            : (use_tile ? tile_scan_queries_per_task()
-                                        : scan_group_size(ix->geom, ix->dtype, (int)std::ceil(share)));
-    constexpr int rpt_tiles = 20;  // tiles per task (measured best of 10 / 20 / 40 / 80 on the headline batch)
-    const int rows_per_task = use_mfma ? mfma_scan_rows_per_task()
-                                       : (use_tile ? rpt_tiles * tile_scan_tile_rows(ix->geom)
-                                                   : (qt >= 16 ? 256 : (qt >= 4 ? 128 : 64)));
-    // MFMA L2: scratch for the candidates' exact tail
-    const bool approx = use_mfma && ix->metric == PGV_L2SQ;
-    // fp32 L2 with the fp16 residual shadow (kernels_shadow.hip): the scan streams half the bytes.  Per batch: the
-    // cast queries, their factors 2^(1 + s + s_q) and band terms, and every probed pair's -2 q.c_l.  A batch that
-    // pgv_search_batch ranked over the center shadow brings all three (ShadowBatch); otherwise they are made here
-    const bool shadow = approx && ix->shadow && shadow_env() != 0;
+    // A batch that pgv_search_batch ranked over the center shadow brings the shadow scan's cast queries, their factors
+    // 2^(1 + s + s_q) and band terms, and every probed pair's -2 q.c_l (ShadowBatch); otherwise they are made here
     ShadowBatch own;
     if (!sb) sb = &own;
-    if (shadow && !sb->cast_for_scan) PGV_TRY(shadow_batch_cast(ix, q_dev, nq, probes, false, true, sb));
-    const float *pair_t = (shadow && sb->pairs_done) ? sb->pair_t : nullptr;
+    if (path.shadow && !sb->cast_for_scan) PGV_TRY(shadow_batch_cast(ix, q_dev, nq, probes, false, true, sb));
+    const float *pair_t = (path.shadow && sb->pairs_done) ? sb->pair_t : nullptr;
     PlanResult plan;
-    // (the ranking of this very batch counted into the plan's buffers: what is left of the plan is two launches)
-    const bool counted = pair_t && sb->plan_counted && sb->plan_nq == nq && sb->plan_probes == probes;
-    PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, qt, rows_per_task, ctx->profiling, &plan, pair_t, counted));
-
-    int kprime = k;
-    ApproxScratch sc;
-    if (approx) {
-        // 32 .. 256 candidates: the head asked for and a margin the rounding bound clears easily (4 k while that
-        // fits batch_recheck_kernel's 256, k + 64 beyond)
-        kprime = approx_candidates(k);
-        PGV_TRY(sc.carve(ctx, ctx->ms_a, nq, kprime));
-    }
-    float *cand_val = sc.cand_val;
-    int64_t *cand_pos = sc.cand_pos;
-    int32_t *flags = sc.flags;
-    void *qcast = nullptr;
-    float *qscale = nullptr, *qeps = nullptr;
-    if (shadow) {
-        qcast = sb->qcast;
-        qscale = sb->qscale;
-        qeps = sb->qeps;
+    // (pair_t set: the ranking of this very batch also counted into the plan's buffers -- the plan is two launches)
+    PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, path.qt, path.rows_per_task, ctx->profiling, &plan, pair_t,
+                              pair_t != nullptr));
+    if (path.shadow) {
         if (!pair_t)  // lists that did not come from this batch's ranking over the center shadow
             PGV_TRY(launch_shadow_pairs(ctx, ix->geom, q_dev, ix->centers, plan.pair_start, ix->nlists, (int64_t)nq * probes,
                                         plan.pairs));
@@ -1158,20 +1131,20 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
         PGV_TRY(scan_turn_begin(ctx));
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin(0.0, 0.0));  // pairs / rows of this launch are accumulated on the device
-        if (shadow)
-            PGV_TRY(launch_mfma_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->shadow, qcast, plan.tasks,
+        if (path.shadow)
+            PGV_TRY(launch_mfma_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->shadow, sb->qcast, plan.tasks,
                                      plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
-                                     seg_vals, rows_stream_past_caches(ix->shadow_geom, PGV_F16, ix->nrows), qt, qscale));
-        else if (use_mfma)
+                                     seg_vals, rows_stream_past_caches(ix->shadow_geom, PGV_F16, ix->nrows), path.qt, sb->qscale));
+        else if (path.use_mfma)
             PGV_TRY(launch_mfma_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
                                      plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
-                                     seg_vals, rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows), qt));
-        else if (use_tile)
+                                     seg_vals, rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows), path.qt));
+        else if (path.use_tile)
             PGV_TRY(launch_tile_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
                                      plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, seg_vals));
         else
             PGV_TRY(launch_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
-                                plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, qt, seg_vals));
+                                plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, path.qt, seg_vals));
         PGV_TRY(timer.end());
         PGV_TRY(scan_turn_end(ctx));
     }
@@ -1183,23 +1156,28 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
     PGV_TRY(ot.init(out_tid, sizeof(uint64_t) * (size_t)nq * k, ctx->sel_b));
     PGV_TRY(ctx->sel_a.ensure(sizeof(int64_t) * (size_t)nq * k));
     int64_t *pos = ctx->sel_a.as<int64_t>();
-    if (approx) {
-        // k' candidates by the expansion, their exact distances, the head; queries whose candidate
-        // set cannot be proven complete (flags) take the exact pass over their whole segment
+    if (path.approx) {
         // (the 64-query form of the scan keeps its four chains as consecutive quarters of the row: whole 128-byte slices;
         // the chain length covers every form that a task of this launch may take)
-        ScanBound gamma = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, wide));
-        if (shadow)  // |x|^2's rounding (worst case) and the exact form's; the rest is the per-query term qeps
-            gamma = {0.f, 0.f, gamma_n(ix->geom.ld / 64.0 + 10.0, 5.9604645e-8), gamma.g_ref};
-        PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, kprime, cand_val, cand_pos, flags + nq));
-        const ExactRows xr{ix->vectors, ix->tids, ix->list_offsets, ix->geom, ix->dtype,
-                           reinterpret_cast<const unsigned *>(ix->row_norms + ix->nrows)};
-        // (the candidates' positions become row slots inside the recheck)
-        PGV_TRY(launch_batch_recheck(ctx, xr, q_dev, nq, kprime, k, cand_val, cand_pos, nullptr, plan.seg_start, 0,
-                                     gamma, od.as<float>(), os.as<int64_t>(), ot.as<uint64_t>(), flags, nullptr,
-                                     probe_lists, plan.probe_off, probes, qeps));
-        PGV_TRY(launch_batch_fix(ctx, xr, q_dev, nq, probe_lists, plan.probe_off, probes, plan.seg_start, 0, flags,
-                                 seg_vals, k, gamma, od.as<float>(), os.as<int64_t>(), ot.as<uint64_t>(), nullptr, qeps));
+        ExactTail tail;
+        tail.rows = {ix->vectors, ix->tids, ix->list_offsets, ix->geom, ix->dtype,
+                     reinterpret_cast<const unsigned *>(ix->row_norms + ix->nrows)};
+        tail.queries = q_dev;
+        tail.nq = nq;
+        tail.kprime = approx_candidates(k);
+        tail.k = k;
+        tail.approx = seg_vals;
+        tail.probe_lists = probe_lists;  // (the candidates' positions become row slots inside the recheck)
+        tail.probe_off = plan.probe_off;
+        tail.probes = probes;
+        tail.seg_start = plan.seg_start;
+        tail.bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, path.wide));
+        if (path.shadow) tail.bound = shadow_band(ix->geom.ld, tail.bound.g_ref);
+        tail.eps_add = path.shadow ? sb->qeps : nullptr;
+        tail.out_dist = od.as<float>();
+        tail.out_slot = os.as<int64_t>();
+        tail.out_tid = ot.as<uint64_t>();
+        PGV_TRY(launch_exact_tail(ctx, tail, ctx->ms_a));
     } else {
         PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, k, od.as<float>(), pos));
         PGV_TRY(launch_positions_to_slots(ctx, ix, probe_lists, plan.probe_off, nq, probes, k, pos,
@@ -1250,7 +1228,7 @@ int pgv_search_batch(pgv_index *ix, const void *queries, int nq, int probes, int
     int32_t *probe_lists = ctx->idx_stage.as<int32_t>();
     // one query cast for the batch where both halves read fp16, and the ranking's q.c_l for the scan
     ShadowBatch sb;
-    sb.scan_follows = shadow_scan_expected(ix, nq, probes, k);
+    sb.scan_follows = scan_path(ix, nq, probes, k).shadow;
     PGV_TRY(rank_lists_impl(ix, q_dev, nq, probes, probe_lists, nullptr, &sb));
     return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, &sb);
 }

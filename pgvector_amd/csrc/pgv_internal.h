@@ -391,6 +391,12 @@ inline ScanBound scan_bound_chain(const pgv_ctx *ctx, int dim, int chain) {
     if (ctx->bound_mode != 0) b.g_dot = gamma_n(chain + 4.0, 5.9604645e-8);
     return b;
 }
+// the band of the shadow paths (ranking over the center shadow, scan over the row shadow): the stored |x|^2's rounding,
+// worst case whatever the bound mode, and the exact form's g_ref; the rest is the per-query term (ceps / qeps).  u: 2^-24
+// as the caller writes it (shadow_query_kernel's terms: the exact 5.9604644775390625e-8, another float at some lengths)
+inline ScanBound shadow_band(int ld, float g_ref, double u = 5.9604645e-8) {
+    return {0.f, 0.f, gamma_n(ld / 64.0 + 10.0, u), g_ref};
+}
 struct ExpansionBound {
     float gamma;        // of |x|^2 + 2 |q||x| (expansion terms)
     float gamma_exact;  // of (|q| + |x|)^2 (the exact value's own rounding; 0 in the statistical model)
@@ -597,23 +603,35 @@ struct ExactRows {
     pgv_dtype dtype;
     const unsigned *norm_max;      // bits of the largest |row|^2
 };
-int launch_batch_recheck(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, int kprime, int k,
-                         const float *approx_val, const int64_t *cand_pos, const int64_t *cand_slot,
-                         const int64_t *seg_start, int64_t fixed_len, const ScanBound &bound,
-                         float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *flags,
-                         int32_t *out_i32 = nullptr, const int32_t *probe_lists = nullptr,
-                         const int64_t *probe_off = nullptr, int probes = 0,
-                         const float *eps_add = nullptr,   // cand_slot null: slots from the positions; eps_add: per query
-                         float *pair_t = nullptr,          // term of the band (the shadow paths), or null; pair_t: fp32
-                         const PlanEmit &emit = PlanEmit());  // rows only, [nq x k] -2 q.row of the rows emitted, or null;
-                                                              // emit: with pair_t only (the center ranking)
-// the flagged queries start to end: exact scores of the whole segment, head, output row (out_slot: row slots, or
-// center ids for the dense form)
-int launch_batch_fix(pgv_ctx *ctx, const ExactRows &xr, const void *q_dev, int nq, const int32_t *probe_lists,
-                     const int64_t *probe_off, int probes, const int64_t *seg_start, int64_t fixed_len,
-                     const int32_t *flags, float *seg_vals, int k, const ScanBound &bound, float *out_dist, int64_t *out_slot,
-                     uint64_t *out_tid, int32_t *out_i32 = nullptr, const float *eps_add = nullptr,
-                     float *pair_t = nullptr, const PlanEmit &emit = PlanEmit());
+// One tail: the k' smallest approximate values of every query's segment (topk_kernel), their exact distances and the
+// first k of them (batch_recheck_kernel), and the queries whose rounding band could not be proven complete start to end
+// (batch_fix_kernel).  A query's segment is EITHER its probed lists' rows in probe order (probe_lists set: a list plan) OR
+// one dense run of fixed_len rows, the same for every query, whose positions are the row slots (probe_lists null)
+struct ExactTail {
+    ExactRows rows;                        // the rows the candidates come from
+    const void *queries = nullptr;         // [nq] staged query rows, in the rows' format
+    int nq = 0;                            // queries
+    int kprime = 0;                        // candidates kept per query, k <= k' <= 256
+    int k = 0;                             // rows emitted per query
+    float *approx = nullptr;               // the expansion's values, segment after segment (a redone query's are overwritten)
+    const int32_t *probe_lists = nullptr;  // list plan: [nq x probes] the lists of each query, in probe order
+    const int64_t *probe_off = nullptr;    // list plan: [nq x probes] where each list starts inside its query's segment
+    int probes = 0;                        // list plan: lists per query
+    const int64_t *seg_start = nullptr;    // list plan: [nq + 1] where each query's segment starts in approx
+    int64_t fixed_len = 0;                 // dense run: rows per query; approx is [nq x fixed_len]
+    ScanBound bound{};                     // the rounding bound of the kernel that produced approx
+    const float *eps_add = nullptr;        // [nq] per-query term added to the band (the shadow paths), or null
+    float *out_dist = nullptr;             // [nq x k] exact distances, ascending; INFINITY where a segment has fewer rows
+    int64_t *out_slot = nullptr;           // [nq x k] row slots (-1: none), or null
+    uint64_t *out_tid = nullptr;           // [nq x k] the rows' tids (~0: none), or null
+    int32_t *out_i32 = nullptr;            // [nq x k] the slots as int32 (the ranking's list ids), or null
+    float *pair_t = nullptr;               // [nq x k] -2 q.row of the rows emitted (fp32 rows only; the ranking), or null
+    PlanEmit emit;                         // the plan's counting of the lists emitted (the ranking, with pair_t and out_i32)
+    bool dense() const { return probe_lists == nullptr; }
+};
+// the three launches.  The candidates and the flags are carved from `scratch`; the selection launch also clears what the
+// two kernels behind it start from zero: the flagged-query count and, under emit, the plan's cnt | fill
+int launch_exact_tail(pgv_ctx *ctx, const ExactTail &t, DBuf &scratch);
 int launch_iota_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *lists_dev, int nlists,
                       const int64_t *probe_off, int64_t *out_slot);
 
