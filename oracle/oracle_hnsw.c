@@ -838,7 +838,9 @@ ora_hnsw_build_parallel(int ops, int dtype, int dim, const void *rows, int64_t n
  * A graph somebody else built (the GPU build, a staged index), given the way the index stores it: per element its
  * level and the neighbor tuple's (level + 2) * m slots, layer lc at (level - lc) * m, an invalid slot (-1) ends a
  * layer's list (HnswLoadNeighborTids, src/hnswutils.c:761-794).  `values` are the INDEX values (already
- * normalised for cosine); element e answers with heap row e.  Only ora_hnsw_search may be used on the result.
+ * normalised for cosine); element e answers with heap row e.  ora_hnsw_search may be used on the result, and -- on a
+ * graph imported with empty tuples, whose lists then carry their true distances -- ora_hnsw_update_connections and
+ * ora_hnsw_set_neighbors (below), read back with ora_hnsw_neighbors.
  */
 ora_hnsw *
 ora_hnsw_import(int ops, int dtype, int dim, const void *values, int64_t n, int m, const int32_t *levels,
@@ -939,6 +941,46 @@ ora_hnsw_neighbors(const ora_hnsw * g, int64_t e, int lc, int32_t *out)
 	for (int i = 0; i < na->length; i++)
 		out[i] = na->items[i].element;
 	return na->length;
+}
+
+/*
+ * HnswUpdateConnection (update_connection above, unchanged) for n requests in the order given: request i links
+ * new_element[i], at distance[i] from owner[i], into owner[i]'s list on layer lc[i] (the loop body of
+ * HnswUpdateNeighborsInMemory, src/hnswbuild.c:376-405).  For the tests of the device's graph updates: the caller makes
+ * the order the reference's.  Returns 0, or -1 for a request outside the graph.
+ */
+int
+ora_hnsw_update_connections(ora_hnsw * g, int64_t n, const int32_t *owner, const int32_t *lc, const int32_t *new_element,
+							const float *distance)
+{
+	for (int64_t i = 0; i < n; i++)
+	{
+		if (owner[i] < 0 || owner[i] >= g->nelements || new_element[i] < 0 || new_element[i] >= g->nelements ||
+			lc[i] < 0 || lc[i] > g->elements[owner[i]].level)
+			return -1;
+		update_connection(g, &g->elements[owner[i]].neighbors[lc[i]], new_element[i], distance[i], layer_m(g->m, lc[i]));
+	}
+	return 0;
+}
+
+/* element e's list on layer lc replaced by n (<= lm) neighbors with their distances: a new element's own selection put
+ * in place (HnswAddConnections as the in-memory build leaves it).  Returns 0 / -1. */
+int
+ora_hnsw_set_neighbors(ora_hnsw * g, int64_t e, int lc, int n, const int32_t *ids, const float *distance)
+{
+	neighbor_array *a;
+
+	if (e < 0 || e >= g->nelements || lc < 0 || lc > g->elements[e].level || n < 0 || n > layer_m(g->m, lc))
+		return -1;
+	a = &g->elements[e].neighbors[lc];
+	a->length = 0;
+	for (int i = 0; i < n; i++)
+	{
+		hnsw_candidate hc = {ids[i], distance[i]};
+
+		neighbors_push(a, hc);
+	}
+	return 0;
 }
 
 int64_t

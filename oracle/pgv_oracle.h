@@ -192,7 +192,8 @@ ora_hnsw   *ora_hnsw_build(int ops, int dtype, int dim, const void *rows, int64_
  * nthreads inserters into one shared graph; one thread gives ora_hnsw_build's graph */
 ora_hnsw   *ora_hnsw_build_parallel(int ops, int dtype, int dim, const void *rows, int64_t n,
 									int m, int ef_construction, uint64_t seed, int nthreads);
-/* a graph built elsewhere, as neighbor tuples (see oracle_hnsw.c); only ora_hnsw_search applies */
+/* a graph built elsewhere, as neighbor tuples (see oracle_hnsw.c): for ora_hnsw_search, and -- imported with empty
+ * tuples -- for the two calls below */
 ora_hnsw   *ora_hnsw_import(int ops, int dtype, int dim, const void *values, int64_t n, int m,
 							const int32_t *levels, const int64_t *nbr_start, const int32_t *nbr, int32_t entry);
 void		ora_hnsw_free(ora_hnsw * g);
@@ -204,6 +205,11 @@ int			ora_hnsw_level(const ora_hnsw * g, int64_t e);
 /* copies up to lm neighbor ids of element e at layer lc; returns the count */
 int			ora_hnsw_neighbors(const ora_hnsw * g, int64_t e, int lc, int32_t *out);
 int64_t		ora_hnsw_element_row(const ora_hnsw * g, int64_t e);
+/* HnswUpdateConnection for n (owner, layer, new element, distance) requests in the order given; 0 / -1 */
+int			ora_hnsw_update_connections(ora_hnsw * g, int64_t n, const int32_t *owner, const int32_t *lc,
+										const int32_t *new_element, const float *distance);
+/* element e's list on layer lc := n neighbors with their distances (a new element's own selection); 0 / -1 */
+int			ora_hnsw_set_neighbors(ora_hnsw * g, int64_t e, int lc, int n, const int32_t *ids, const float *distance);
 /* hnswgettuple first batch (src/hnswscan.c:25-56 + :293-326): top-k rows.
  * out_scored (may be NULL) = so->tuples, the number of scored elements. */
 int			ora_hnsw_search(const ora_hnsw * g, const void *query, int ef_search, int k,

@@ -135,6 +135,10 @@ class Oracle:
             L.ora_hnsw_level.argtypes = [P, I64]
             L.ora_hnsw_neighbors.restype = I
             L.ora_hnsw_neighbors.argtypes = [P, I64, I, P]
+            L.ora_hnsw_update_connections.restype = I
+            L.ora_hnsw_update_connections.argtypes = [P, I64, P, P, P, P]
+            L.ora_hnsw_set_neighbors.restype = I
+            L.ora_hnsw_set_neighbors.argtypes = [P, I64, I, I, P, P]
             L.ora_hnsw_element_row.restype = I64
             L.ora_hnsw_element_row.argtypes = [P, I64]
             L.ora_hnsw_search.restype = I
@@ -358,7 +362,8 @@ class HnswGraph:
     @classmethod
     def from_tuples(cls, ora, ops, dtype, values, m, levels, nbr_start, nbr, entry):
         """a graph built elsewhere (the GPU build, a staged index) in the index's neighbor-tuple layout; `values` are
-        the index values (normalised for cosine), element e answers with row e.  Only search() applies."""
+        the index values (normalised for cosine), element e answers with row e.  search() applies, and -- on a graph
+        given with empty tuples -- update_connections() / set_neighbors()."""
         self = cls.__new__(cls)
         self.ora, self.ops, self.dtype, self.m = ora, ops, dtype, m
         self.rows = ora.arr(values, dtype)
@@ -391,6 +396,22 @@ class HnswGraph:
         scored = C.c_int64()
         n = self.ora.lib.ora_hnsw_search(self.h, _p(q), ef_search, k, _p(rows), _p(dist), C.byref(scored))
         return rows[:n], dist[:n], scored.value
+
+    def update_connections(self, owner, lc, new_element, distance):
+        """HnswUpdateConnection for each request (owner, layer, new element, its distance to the owner), in order"""
+        owner, lc, new_element = (np.ascontiguousarray(x, dtype=np.int32) for x in (owner, lc, new_element))
+        distance = np.ascontiguousarray(distance, dtype=np.float32)
+        assert owner.shape == lc.shape == new_element.shape == distance.shape and owner.ndim == 1
+        rc = self.ora.lib.ora_hnsw_update_connections(self.h, owner.size, _p(owner), _p(lc), _p(new_element), _p(distance))
+        assert rc == 0, "a request outside the graph"
+
+    def set_neighbors(self, e, lc, ids, distance):
+        """element e's list on layer lc := ids with their distances (a new element's own selection)"""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        distance = np.ascontiguousarray(distance, dtype=np.float32)
+        assert ids.shape == distance.shape
+        rc = self.ora.lib.ora_hnsw_set_neighbors(self.h, int(e), int(lc), ids.size, _p(ids), _p(distance))
+        assert rc == 0, "a list outside the graph or longer than the layer's m"
 
     def export(self):
         """flat arrays for a device/host mirror: per element row, level, heap-tid-free neighbor table.

@@ -11,7 +11,9 @@
  *   - kernels_hnsw.hip includes it with PGV_LINK_FN = __device__: hnsw_link_kernel runs it, one lane per list;
  *   - tests/c/mock_hip.c includes it as host C, so that the CPU tests of the host build exercise this very code.
  * pgvector_amd/host/hnsw_build.c holds the older host-side replay of the same steps (pointer-based, with a cached sort
- * order); the GPU tests build the same graphs both ways.
+ * order); tests/test_gpu_round5.py builds the same graphs both ways.  tests/test_gpu_hnsw_link_edges.py drives the device
+ * compilation (hnsw_link_kernel<32 / 64 / 200>, PGV_HNSW_LINK_SERIAL=1 for the small m) and the wavefront kernel with
+ * hand-made requests against tests/hnsw_link_model.py: Algorithm 4 with every flag recomputed, pinned to the oracle.
  */
 #ifndef PGV_HNSW_LINK_CORE_H
 #define PGV_HNSW_LINK_CORE_H

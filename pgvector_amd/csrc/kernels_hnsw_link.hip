@@ -335,7 +335,8 @@ __global__ __launch_bounds__(64) void hnsw_link_kernel(LinkArgs g) {
 // across the lanes: the sort is a rank (every lane counts the keys above its own), CheckElementCloser against the
 // neighbors chosen so far is one comparison per lane and a ballot, the record's pair distances are read from LDS, where
 // the wavefront put them in one coalesced sweep.  Decisions, flags, the dropped candidate and the slot the newcomer takes
-// are hnsw_link_core.h's, step for step (tests: the graphs of the two kernels and of the host replay are the same).  One
+// are hnsw_link_core.h's, step for step (tests/test_gpu_hnsw_link_edges.py: both kernels against the reference's rule on
+// hand-made batches, and against each other; tests/test_gpu_round5.py: whole builds against the host replay).  One
 // difference that changes nothing: a check that meets BOTH a deciding pair and a pair that was not fetched stops for
 // the missing one here, whatever their order in the reference's loop -- the list then waits for its member triangle and
 // comes to the same decision.

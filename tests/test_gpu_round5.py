@@ -198,26 +198,7 @@ def test_the_64_query_scan_form_for_fp32_too_in_a_process_that_forces_it():
 
 # ---------------------------------------------------------------------------------------------------------------------
 # SelectNeighbors of the elements being inserted, on the device (pgv_hnsw_build_neighbors)
-def _host_select(ids, dist, tri, lm):
-    """src/hnswutils.c:1064-1165 for a list without cached flags, candidates nearest first, pair distances in the
-    (u, v < u) triangle: (neighbors, distances, closer flags) in r's order"""
-    nw = len(ids)
-    if nw <= lm:
-        return ids[::-1].tolist(), dist[::-1].tolist(), [0] * nw
-    chosen, looked = [], 0
-    for j in range(nw):
-        if len(chosen) >= lm:
-            break
-        looked = j + 1
-        if all(tri[j * (j - 1) // 2 + r] > dist[j] for r in chosen):
-            chosen.append(j)
-    order = list(chosen)
-    for x in range(looked):
-        if len(order) >= lm:
-            break
-        if x not in chosen:
-            order.append(x)
-    return [int(ids[x]) for x in order], [float(dist[x]) for x in order], [1 if i < len(chosen) else 0 for i in range(len(order))]
+from hnsw_link_model import host_select as _host_select  # noqa: E402  (the plain sweep of SelectNeighbors)
 
 
 @pytest.mark.parametrize("metric,dist_kind,dim", [(api.PGV_L2SQ, "clustered", 48), (api.PGV_L2SQ, "int10", 8), (api.PGV_NEG_IP, "normal", 96)])
