@@ -580,6 +580,46 @@ typedef enum pgv_bit_metric
 int			pgv_bit_distance_batch(pgv_ctx * ctx, pgv_bit_metric metric, int nbits,
 								   const void *query, const void *rows, int64_t n, double *out);
 
+/*
+ * `ORDER BY b <~> $1 LIMIT k` without an index, for a BATCH of queries (hamming_distance src/bitvec.c:45-56 over
+ * BitHammingDistanceDefault src/bitutils.c:49-73, feeding the executor's top-N sort): the first stage of the
+ * binary-quantization query of the reference's README.  queries [nq x bytes] and rows [n x bytes], bytes =
+ * (nbits + 7) / 8: VARBITS payloads as pgv_bit_distance_batch takes them, contiguous, first bit = most significant bit
+ * of byte 0; bytes are counted whole like the reference does, so the caller's pad bits are zero (as PostgreSQL keeps
+ * them).  out_dist [nq x k] Hamming distances ascending, as floats (exact: at most 512 000), out_idx [nq x k] row
+ * indexes, ties by lower index (pgv_exact_topk's rule); entries beyond n are +inf / -1.  Every array may be host or
+ * device memory; device rows whose byte length is a multiple of 16 are used in place.  1 <= k <= 4096,
+ * 0 <= nbits <= 512 000 (nbits == 0: every distance is 0, the answer is rows 0 .. min(k, n) - 1), n <= 2^32.  The
+ * queries are served in chunks of min(nq, max(1, 2^30 / n)) (whole multiples of 32 from 32 on), so that a chunk's
+ * distance matrix stays at or under 2^30 floats.
+ */
+int			pgv_bit_topk(pgv_ctx * ctx, int nbits, const void *queries, int nq,
+						 const void *rows, int64_t n, int k, float *out_dist, int64_t *out_idx);
+
+/*
+ * binary_quantize (src/vector.c:952-979, halfvec_binary_quantize in src/halfvec.c): bit i = x[i] > 0, exactly the C
+ * comparison -- +0.0, -0.0, NaN and negatives give 0, every positive value 1 (+inf and the subnormals included; the
+ * bit is decided from the element's pattern, not by a floating-point compare).  rows [n x dim] host or device,
+ * out_bits [n x (dim + 7) / 8] bytes host or device, packed contiguous, first element in the most significant bit of
+ * byte 0, the unused low bits of a row's last byte zero: what pgv_bit_topk reads.
+ */
+int			pgv_binary_quantize(pgv_ctx * ctx, pgv_dtype dtype, int dim, const void *rows, int64_t n, void *out_bits);
+
+/*
+ * The outer ORDER BY of the two-stage query (`ORDER BY embedding <=> $1 LIMIT k` over the subquery's rows: one
+ * l2_distance / vector_negative_inner_product / l1_distance call per surviving row, src/vector.c:579-725, halfvec
+ * twins src/halfvec.c:605-748): exact kernel values of each query against ITS candidates only.
+ *   rows [n x dim], queries [nq x dim], cand [nq x kc] row indexes (-1 = none), k <= kc <= 4096, n < 2^31
+ *   out_dist [nq x k] ascending kernel values (L2 squared / -ip / L1, like pgv_exact_topk), out_idx [nq x k] row indexes;
+ *   ties by lower candidate position; +inf / -1 padded.
+ * The values come from the exact vector-ALU kernel that serves pgv_hnsw_score (no matrix-core expansion).  A candidate
+ * of -1 scores +inf whatever the rows hold (and with n == 0 no row is read at all).  A candidate >= n or < -1 is
+ * PGV_ERR_ARG when cand is host memory; when cand is device memory it is NOT checked and the behaviour is undefined.
+ * For cosine the caller passes normalised rows with PGV_NEG_IP, as elsewhere in this ABI.
+ */
+int			pgv_rerank(pgv_ctx * ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *queries, int nq,
+					   const void *rows, int64_t n, const int64_t *cand, int kc, int k, float *out_dist, int64_t *out_idx);
+
 /* --------------------------------------------------------------- HNSW side */
 
 /*

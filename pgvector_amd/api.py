@@ -527,6 +527,55 @@ def bit_distance_batch(ctx, metric, nbits, query, rows):
     return out
 
 
+def _as_bytes(x):
+    return x.contiguous() if _is_torch(x) else np.ascontiguousarray(x, dtype=np.uint8)
+
+
+def bit_topk(ctx, nbits, queries, rows, k, out=None):
+    """pgv_bit_topk: `ORDER BY b <~> $1 LIMIT k` for a batch of packed bit strings: queries [nq x (nbits + 7) // 8] uint8
+    against rows [n x (nbits + 7) // 8] uint8 -> (dist [nq x k] float32, idx [nq x k] int64), ties to the lower row"""
+    queries, rows = _as_bytes(queries), _as_bytes(rows)
+    nq, n = int(queries.shape[0]), int(rows.shape[0])
+    dist, idx = out if out is not None else (_empty_like_kind(queries, (nq, k), np.float32),
+                                            _empty_like_kind(queries, (nq, k), np.int64))
+    check(lib.pgv_bit_topk(ctx.h, int(nbits), ptr(queries) if nbits and nq else None, nq, ptr(rows) if nbits and n else None, n,
+                           int(k), ptr(dist), ptr(idx)))
+    return dist, idx
+
+
+def binary_quantize(ctx, dtype, dim, rows):
+    """pgv_binary_quantize: rows [n x dim] -> packed bits [n x (dim + 7) // 8] uint8, bit i = rows[:, i] > 0, first element
+    in the top bit of byte 0 (np.packbits' order)"""
+    rows = as_dtype(rows, dtype)
+    n = int(rows.shape[0])
+    out = _empty_like_kind(rows, (n, (dim + 7) // 8), np.uint8)
+    check(lib.pgv_binary_quantize(ctx.h, dtype, dim, ptr(rows) if n else None, n, ptr(out)))
+    return out
+
+
+def rerank(ctx, metric, dtype, dim, queries, rows, cand, k):
+    """pgv_rerank: exact kernel values of each query against its own candidate rows cand [nq x kc] int64 (-1 = none)
+    -> (dist [nq x k], idx [nq x k]), ties to the lower candidate position"""
+    queries, rows = as_dtype(queries, dtype), as_dtype(rows, dtype)
+    cand = cand.contiguous() if _is_torch(cand) else np.ascontiguousarray(cand, dtype=np.int64)
+    nq, n, kc = int(queries.shape[0]), int(rows.shape[0]), int(cand.shape[1])
+    dist = _empty_like_kind(queries, (nq, k), np.float32)
+    idx = _empty_like_kind(queries, (nq, k), np.int64)
+    check(lib.pgv_rerank(ctx.h, metric, dtype, dim, ptr(queries), nq, ptr(rows) if n else None, n, ptr(cand), kc, int(k),
+                         ptr(dist), ptr(idx)))
+    return dist, idx
+
+
+def binary_search(ctx, metric, dtype, dim, queries, rows, bits, kc, k, want_candidates=False):
+    """the two-stage query of binary quantization: quantise the queries, the kc nearest rows of `bits` (the rows'
+    binary_quantize image) by Hamming distance, then the k nearest of those by the exact metric over `rows`
+    -> (dist [nq x k], idx [nq x k]) and, on request, stage one's (hamming [nq x kc], cand [nq x kc])"""
+    qbits = binary_quantize(ctx, dtype, dim, queries)
+    hamming, cand = bit_topk(ctx, dim, qbits, bits, kc)
+    dist, idx = rerank(ctx, metric, dtype, dim, queries, rows, cand, k)
+    return (dist, idx, hamming, cand) if want_candidates else (dist, idx)
+
+
 class IvfBuilder:
     """pgv_builder_*: heap rows assigned and kept on the device, finish() = the tuplesort by list as a device gather
     whose result is the mirror itself"""

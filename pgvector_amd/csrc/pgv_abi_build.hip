@@ -213,27 +213,133 @@ int pgv_bit_distance_batch(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const
         g.lpr_log2 = 6;
         while (g.lpr_log2 > 0 && (1 << (g.lpr_log2 - 1)) >= g.nvec) g.lpr_log2--;
         g.nchunks = (g.nvec + (1 << g.lpr_log2) - 1) >> g.lpr_log2;
-        auto stage = [&](const void *src, int64_t cnt, DBuf &scratch, const void **outp) -> int {
-            const bool dev = is_device_ptr(src);
-            if (dev && g.ld == bytes) {
-                *outp = src;
-                return PGV_OK;
-            }
-            PGV_TRY(scratch.ensure((size_t)cnt * g.ld));
-            PGV_HIP(hipMemsetAsync(scratch.p, 0, (size_t)cnt * g.ld, ctx->stream));
-            PGV_HIP(hipMemcpy2DAsync(scratch.p, (size_t)g.ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt,
-                                     dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-            if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));
-            *outp = scratch.p;
-            return PGV_OK;
-        };
         const void *q_dev, *r_dev;
-        PGV_TRY(stage(query, 1, ctx->q_stage, &q_dev));
-        PGV_TRY(stage(rows, n, ctx->rows_stage, &r_dev));
+        PGV_TRY(stage_bit_rows(ctx, query, 1, bytes, g.ld, ctx->q_stage, &q_dev));
+        PGV_TRY(stage_bit_rows(ctx, rows, n, bytes, g.ld, ctx->rows_stage, &r_dev));
         PGV_TRY(launch_bit_distance(ctx, metric == PGV_BIT_HAMMING ? 0 : 1, g, r_dev, q_dev, n, od.as<double>()));
     }
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
+// `ORDER BY b <~> $1 LIMIT k` without an index for a batch of queries: pgv_exact_topk's structure over packed bits.  The
+// scan (hamming_tile_kernel, kernels_bit.hip) fills the chunk's distance matrix mat[q * n + row] with the integer counts
+// as floats (exact: at most 512 000), launch_topk_segments selects with ties to the lower row.
+int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const void *rows, int64_t n, int k, float *out_dist,
+                 int64_t *out_idx) {
+    if (!ctx || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: ctx/out_dist/out_idx is NULL");
+    if (nbits < 0 || nbits > 64000 * 8) PGV_FAIL(PGV_ERR_DIMS, "bit length %d out of range", nbits);
+    if (nq < 0 || n < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: nq/n < 0");
+    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: k %d outside 1..4096", k);
+    if (n > 0xffffffffll) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: more than 2^32 rows");
+    if (nq == 0) return PGV_OK;
+    if (nbits > 0 && (!queries || (n > 0 && !rows))) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: queries/rows is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    const int bytes = (nbits + 7) / 8;  // VARBITBYTES
+    // rows in whole 16-byte vectors like pgv_bit_distance_batch's, queries in whole register slices of the scan kernel
+    const int row_ld = (bytes + 15) / 16 * 16;
+    const int slice = bit_topk_slice_bytes();
+    const int q_ld = (bytes + slice - 1) / slice * slice;
+    const void *q_dev = nullptr, *r_dev = nullptr;
+    if (bytes > 0 && n > 0) {
+        PGV_TRY(stage_bit_rows(ctx, queries, nq, bytes, q_ld, ctx->q_stage, &q_dev));
+        PGV_TRY(stage_bit_rows(ctx, rows, n, bytes, row_ld, ctx->rows_stage, &r_dev));
+    }
+    OutArg od, oi;
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
+    PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
+
+    // the distance matrix of a query chunk stays at or under 2^30 floats, in whole 32-query tiles of the scan kernel
+    int chunk = n > 0 ? (int)std::min<int64_t>(nq, std::max<int64_t>(1, ((int64_t)1 << 30) / n)) : nq;
+    if (chunk >= 32) chunk = chunk / 32 * 32;
+    for (int q0 = 0; q0 < nq; q0 += chunk) {
+        const int cn = std::min(chunk, nq - q0);
+        PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * std::max<size_t>((size_t)cn * (size_t)n, 4)));
+        float *mat = ctx->dist_mat.as<float>();
+        if (n > 0 && bytes == 0) {
+            // empty bit strings: every distance is 0 (src/bitutils.c:71), so the ties leave rows 0 .. k - 1
+            PGV_HIP(hipMemsetAsync(mat, 0, sizeof(float) * (size_t)cn * (size_t)n, ctx->stream));
+        } else if (n > 0) {
+            ScanTimer timer{ctx};
+            PGV_TRY(timer.begin((double)n * cn, (double)n * ((cn + 31) / 32), true));
+            PGV_TRY(launch_hamming_tiles(ctx, r_dev, row_ld / 16, n, static_cast<const char *>(q_dev) + (size_t)q0 * q_ld, q_ld,
+                                         cn, mat));
+            PGV_TRY(timer.end());
+        }
+        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, od.as<float>() + (size_t)q0 * k,
+                                     oi.as<int64_t>() + (size_t)q0 * k));
+    }
+    bool need = false;
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(oi.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
+int pgv_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *rows, int64_t n, void *out_bits) {
+    if (!ctx || !out_bits) PGV_FAIL(PGV_ERR_ARG, "pgv_binary_quantize: ctx/out_bits is NULL");
+    PGV_TRY(check_common(dtype, dim));
+    if (n < 0) PGV_FAIL(PGV_ERR_ARG, "n < 0");
+    if (n == 0) return PGV_OK;
+    if (!rows) PGV_FAIL(PGV_ERR_ARG, "rows is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    const void *r_dev;
+    PGV_TRY(stage_flat(ctx, rows, (size_t)n * dim * elem_size(dtype), ctx->rows_stage, &r_dev));
+    OutArg ob;
+    PGV_TRY(ob.init(out_bits, (size_t)n * ((dim + 7) / 8), ctx->out_stage));
+    PGV_TRY(launch_binary_quantize(ctx, dtype, dim, r_dev, n, ob.dev));
+    bool need = false;
+    PGV_TRY(ob.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
+// The outer ORDER BY of the two-stage query: score_gather_kernel (pgv_hnsw_score's exact per-pair kernel) over the
+// nq x kc (candidate, query) pairs, +inf for the "none" entries, launch_topk_segments over segments of kc (ties to the
+// lower position), positions back to row indexes.
+int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *queries, int nq, const void *rows,
+               int64_t n, const int64_t *cand, int kc, int k, float *out_dist, int64_t *out_idx) {
+    if (!ctx || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: ctx/out_dist/out_idx is NULL");
+    PGV_TRY(check_common(dtype, dim));
+    PGV_TRY(check_metric(metric));
+    if (nq < 0 || n < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: nq/n < 0");
+    if (kc < 1 || kc > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: kc %d outside 1..4096", kc);
+    if (k < 1 || k > kc) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: k %d outside 1..kc = %d", k, kc);
+    if (n > 0x7fffffffll) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: more than 2^31 - 1 rows");
+    if (nq == 0) return PGV_OK;
+    if (!queries || !cand || (n > 0 && !rows)) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: queries/cand/rows is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    const int64_t total = (int64_t)nq * kc;
+    if (!is_device_ptr(cand))
+        for (int64_t i = 0; i < total; i++)
+            if (cand[i] < -1 || cand[i] >= n)
+                PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: candidate %lld of query %lld outside -1..%lld", (long long)cand[i],
+                         (long long)(i / kc), (long long)n - 1);
+    const RowGeom g = row_geom(dim, dtype);
+    const void *q_dev, *r_dev = nullptr, *c_dev;
+    PGV_TRY(stage_rows(ctx, queries, nq, dim, dtype, g, ctx->q_stage, &q_dev));
+    if (n > 0) PGV_TRY(stage_rows(ctx, rows, n, dim, dtype, g, ctx->rows_stage, &r_dev));
+    PGV_TRY(stage_flat(ctx, cand, sizeof(int64_t) * (size_t)total, ctx->idx_stage, &c_dev));
+    const int64_t *cd = static_cast<const int64_t *>(c_dev);
+    OutArg od, oi;
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
+    PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
+    // plan_a: slot[total] | query_of[total]   plan_b: values[total]   plan_c: selected positions [nq x k]
+    PGV_TRY(ctx->plan_a.ensure(sizeof(int32_t) * 2 * (size_t)total));
+    PGV_TRY(ctx->plan_b.ensure(sizeof(float) * (size_t)total));
+    PGV_TRY(ctx->plan_c.ensure(sizeof(int64_t) * (size_t)nq * k));
+    int32_t *slot = ctx->plan_a.as<int32_t>(), *query_of = slot + total;
+    float *vals = ctx->plan_b.as<float>();
+    int64_t *pos = ctx->plan_c.as<int64_t>();
+    if (n > 0) {
+        PGV_TRY(launch_rerank_pairs(ctx, cd, total, kc, slot, query_of));
+        PGV_TRY(launch_score_gather(ctx, metric, dtype, g, r_dev, q_dev, slot, query_of, total, vals));
+    }
+    PGV_TRY(launch_rerank_mask(ctx, cd, total, vals));  // (n == 0: every entry is "none")
+    PGV_TRY(launch_topk_segments(ctx, vals, nullptr, nq, kc, k, od.as<float>(), pos));
+    PGV_TRY(launch_rerank_map(ctx, cd, nq, kc, k, pos, oi.as<int64_t>()));
+    bool need = false;
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(oi.finish(ctx, &need));
     return sync_if(ctx, need);
 }
 

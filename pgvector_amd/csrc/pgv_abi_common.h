@@ -95,6 +95,23 @@ int stage_flat(pgv_ctx *ctx, const void *src, size_t bytes, DBuf &scratch, const
     return PGV_OK;
 }
 
+// packed bit rows [cnt x bytes] (host or device; VARBITS payloads) -> device rows of `ld` bytes each, zero padded.  When
+// the source already lives on the device with ld == bytes it is used in place.  (pgv_bit_distance_batch and pgv_bit_topk)
+int stage_bit_rows(pgv_ctx *ctx, const void *src, int64_t cnt, int bytes, int ld, DBuf &scratch, const void **outp) {
+    const bool dev = is_device_ptr(src);
+    if (dev && ld == bytes) {
+        *outp = src;
+        return PGV_OK;
+    }
+    PGV_TRY(scratch.ensure((size_t)cnt * ld));
+    PGV_HIP(hipMemsetAsync(scratch.p, 0, (size_t)cnt * ld, ctx->stream));
+    PGV_HIP(hipMemcpy2DAsync(scratch.p, (size_t)ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt,
+                             dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));
+    *outp = scratch.p;
+    return PGV_OK;
+}
+
 // An output the caller gave us: computed straight into it when it is device
 // memory, otherwise into scratch and copied back by finish().
 struct OutArg {

@@ -434,6 +434,20 @@ int launch_cosine(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void *r
 int launch_bit_distance(pgv_ctx *ctx, int mode, const RowGeom &g, const void *rows, const void *query, int64_t n,
                         double *out);
 
+// kernels_bit.hip: binary quantization.  The Hamming distances of every query x every row in 256-row x 32-query tiles
+// (pgv_bit_topk): rows [n x nvec] 16-byte vectors, queries [nq x qbytes] with qbytes a multiple of
+// bit_topk_slice_bytes(), both zero padded; out[q * n + row]
+int bit_topk_slice_bytes();
+int launch_hamming_tiles(pgv_ctx *ctx, const void *rows, int nvec, int64_t n, const void *queries, int qbytes, int nq,
+                         float *out);
+// rows [n x dim] tightly packed -> out_bits [n x (dim + 7) / 8], bit i = x[i] > 0, first element in the top bit
+int launch_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *rows, int64_t n, void *out_bits);
+// pgv_rerank around launch_score_gather and launch_topk_segments: cand [nq x kc] -> (slot, query_of) of the pairs
+// (-1: row 0); +inf over the values of the -1 entries; selected positions -> cand entries
+int launch_rerank_pairs(pgv_ctx *ctx, const int64_t *cand, int64_t total, int kc, int32_t *slot, int32_t *query_of);
+int launch_rerank_mask(pgv_ctx *ctx, const int64_t *cand, int64_t total, float *vals);
+int launch_rerank_map(pgv_ctx *ctx, const int64_t *cand, int nq, int kc, int k, const int64_t *pos, int64_t *out_idx);
+
 // kernels_hnsw.hip: the whole first batch of an HNSW scan, one workgroup per query
 int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out);
 struct HnswSearchArgs {
