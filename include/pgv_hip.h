@@ -642,6 +642,27 @@ int			pgv_hnsw_upload_payload(pgv_ctx * ctx, pgv_metric metric, pgv_dtype dtype,
 int			pgv_hnsw_get_payload(pgv_hnsw * h, const int64_t *elements, int n, void *out);
 
 /*
+ * The mirror of an HNSW index over BIT strings -- `USING hnsw ((binary_quantize(embedding)::bit(n)) bit_hamming_ops)`,
+ * the index the reference's README puts under the two-stage binary-quantization query (opclass sql/vector.sql:901-905,
+ * FUNCTION 1 hamming_distance; type info hnsw_bit_support, src/hnswutils.c:1403-1416).  It replaces what hnswgettuple's
+ * first batch (GetScanItems, src/hnswscan.c:25-56) does on such an index: the same walk, every candidate scored with
+ * hamming_distance (src/bitvec.c:45-56 over BitHammingDistanceDefault, src/bitutils.c:49-73).
+ *   elements [n x (nbits + 7) / 8] bytes, host or device: VARBITS payloads as pgv_bit_topk takes them, contiguous,
+ *   first bit = most significant bit of byte 0, the caller's pad bits zero (bytes are counted whole, like the reference);
+ *   1 <= nbits <= 64 000 (HNSW_MAX_DIM * 32), else PGV_ERR_DIMS; payload / payload_bytes as pgv_hnsw_upload_payload
+ *   (NULL / 0: none).
+ * metric must be PGV_BIT_HAMMING.  PGV_BIT_JACCARD is PGV_ERR_ARG: jaccard_distance is a float8 ratio, the walk's keys
+ * are fp32 and would merge distinct distances, and the reference's stop test is strict on the float8 value.
+ * On such a mirror pgv_hnsw_search / pgv_hnsw_score take queries [nq x (nbits + 7) / 8] in the same layout and return
+ * the Hamming distances as floats (exact: at most 64 000); pgv_hnsw_score_pairs likewise; pgv_hnsw_set_graph,
+ * pgv_hnsw_update_graph, pgv_hnsw_get_payload, pgv_hnsw_share and pgv_hnsw_export / pgv_hnsw_import work as on any
+ * mirror (views and importers know the element type and nbits).  Every build-side entry (pgv_hnsw_build_*,
+ * pgv_hnsw_link_*, pgv_hnsw_score_groups) returns PGV_ERR_ARG before any launch: bit graphs are not built here.
+ */
+int			pgv_hnsw_upload_bits(pgv_ctx * ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
+								 const void *payload, int payload_bytes, pgv_hnsw * *out);
+
+/*
  * The HNSW mirror across processes, like pgv_index_export / pgv_index_import: the element vectors and the graph
  * (set with pgv_hnsw_set_graph) stay in the exporting process's HBM, importers map them read-only and search on
  * their own context (stream, visited bitmaps).  Graph patches by the owner (pgv_hnsw_update_graph) are seen by the

@@ -47,6 +47,7 @@ SYMBOLS = [
     "pgv_index_tids", "pgv_hnsw_export", "pgv_hnsw_import", "pgv_hnsw_share", "pgv_hnsw_device", "pgv_exact_topk", "pgv_ctx_set_bound",
     "pgv_hnsw_upload_payload", "pgv_hnsw_get_payload", "pgv_builder_begin", "pgv_builder_add", "pgv_builder_set_centers", "pgv_builder_rows", "pgv_builder_finish", "pgv_builder_free", "pgv_index_drain",
     "pgv_index_set_overlap", "pgv_index_shadow_cast", "pgv_bit_topk", "pgv_binary_quantize", "pgv_rerank",
+    "pgv_hnsw_upload_bits",
 ]
 
 
@@ -121,6 +122,7 @@ def _load():
     lib.pgv_hnsw_device.argtypes = [P]
     lib.pgv_hnsw_upload_payload.argtypes = [P, I, I, I, P, I64, P, I, C.POINTER(P)]
     lib.pgv_hnsw_get_payload.argtypes = [P, P, I, P]
+    lib.pgv_hnsw_upload_bits.argtypes = [P, I, I, P, I64, P, I, C.POINTER(P)]
     lib.pgv_exact_topk.argtypes = [P, I, I, I, P, I, P, I64, I, P, P]
     lib.pgv_ctx_set_bound.argtypes = [P, I]
     lib.pgv_builder_begin.argtypes = [P, I, I, I, I, P, I64, C.POINTER(P)]

@@ -762,3 +762,81 @@ class Hnsw:
         check(lib.pgv_hnsw_score(self.h, ptr(queries), int(queries.shape[0]), ptr(slot), ptr(query_of),
                                  n, ptr(out)))
         return out
+
+
+class BitHnsw(Hnsw):
+    """device mirror of an HNSW index over packed bit strings, `USING hnsw (... bit_hamming_ops)` (pgv_hnsw_upload_bits):
+    elements [n x (nbits + 7) // 8] uint8, first bit in the top bit of byte 0 (np.packbits' order), pad bits zero.
+    set_graph, update_graph, get_payload, export and close are Hnsw's; search and score take packed queries and return
+    Hamming distances as float32 (exact)."""
+
+    def __init__(self, ctx, nbits, elements, payload=None, metric=PGV_BIT_HAMMING):
+        self.ctx, self.metric, self.dtype, self.dim, self.nbits = ctx, metric, None, int(nbits), int(nbits)
+        elements = _as_bytes(elements)
+        n = int(elements.shape[0])
+        h = C.c_void_p()
+        self.payload_words = 0
+        if payload is not None:
+            payload = np.ascontiguousarray(payload, dtype=np.uint32)
+            self.payload_words = int(payload.shape[1])
+        check(lib.pgv_hnsw_upload_bits(ctx.h, int(metric), int(nbits), ptr(elements) if n else None, n, ptr(payload),
+                                       4 * self.payload_words, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    @classmethod
+    def from_handle(cls, ctx, handle, nbits=None):
+        """pgv_hnsw_import of a bit mirror's export: the handle carries the element type and nbits"""
+        v = super().from_handle(ctx, handle, None)
+        v.nbits = nbits
+        return v
+
+    def share(self, ctx):
+        v = BitHnsw.__new__(BitHnsw)
+        h = C.c_void_p()
+        check(lib.pgv_hnsw_share(self.h, ctx.h, C.byref(h)))
+        v.ctx, v.metric, v.dtype, v.dim, v.nbits, v.h = ctx, self.metric, None, self.dim, self.nbits, h
+        v.payload_words = self.payload_words
+        v._owner = self   # keeps the owner alive
+        ctx._adopt(v)
+        return v
+
+    def search(self, queries, ef_search, k, want_scored=True):
+        """pgv_hnsw_search on a bit mirror: queries [nq x (nbits + 7) // 8] uint8 ->
+        (element slots [nq x k] nearest first / -1, Hamming distances [nq x k] float32 / +inf, scored [nq] or None)"""
+        queries = _as_bytes(queries)
+        nq = int(queries.shape[0])
+        elem = _empty_like_kind(queries, (nq, k), np.int64)
+        dist = _empty_like_kind(queries, (nq, k), np.float32)
+        scored = _empty_like_kind(queries, (nq,), np.int64) if want_scored else None
+        check(lib.pgv_hnsw_search(self.h, ptr(queries), nq, int(ef_search), int(k), ptr(elem), ptr(dist), ptr(scored)))
+        return elem, dist, scored
+
+    def score(self, queries, slot, query_of=None):
+        """pgv_hnsw_score on a bit mirror: Hamming distance of element slot[i] to packed query query_of[i]"""
+        queries = _as_bytes(queries)
+        slot = np.ascontiguousarray(slot, dtype=np.int32) if not _is_torch(slot) else slot
+        if query_of is not None and not _is_torch(query_of):
+            query_of = np.ascontiguousarray(query_of, dtype=np.int32)
+        n = int(slot.shape[0])
+        out = _empty_like_kind(slot, (n,), np.float32)
+        check(lib.pgv_hnsw_score(self.h, ptr(queries), int(queries.shape[0]), ptr(slot), ptr(query_of), n, ptr(out)))
+        return out
+
+    def score_pairs(self, a, b):
+        """pgv_hnsw_score_pairs: Hamming distance between element slots a[i] and b[i]"""
+        a, b = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32)
+        out = np.empty((a.size,), dtype=np.float32)
+        check(lib.pgv_hnsw_score_pairs(self.h, ptr(a), ptr(b), int(a.size), ptr(out)))
+        return out
+
+
+def binary_search_hnsw(ctx, metric, dtype, dim, queries, rows, bit_hnsw, ef_search, kc, k, want_candidates=False):
+    """the INDEXED two-stage query of binary quantization (the reference README's `USING hnsw (... bit_hamming_ops)`
+    form): quantise the queries, the kc <= ef_search nearest elements of `bit_hnsw` (a BitHnsw over the rows'
+    binary_quantize image, element slot i = row i) by walking its graph, then the k nearest of those by the exact metric
+    over `rows` -> (dist [nq x k], idx [nq x k]) and, on request, stage one's (hamming [nq x kc], cand [nq x kc], scored)"""
+    qbits = binary_quantize(ctx, dtype, dim, queries)
+    cand, hamming, scored = bit_hnsw.search(qbits, ef_search, kc)
+    dist, idx = rerank(ctx, metric, dtype, dim, queries, rows, cand, k)
+    return (dist, idx, hamming, cand, scored) if want_candidates else (dist, idx)

@@ -81,6 +81,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     float *__restrict__ out_dist = run.out_dist;
     int64_t *__restrict__ out_scored = run.out_scored;
     constexpr int N = VecTraits<T>::N;
+    constexpr bool kBits = std::is_same_v<T, BitRow>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lm0 = 2 * g.m;
     // layout: query row | W keys [2][ef] | W ids [2][ef] | batch keys [lm0] | batch ids [lm0] | scalars
@@ -110,6 +111,8 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     // 352 k QPS with R = 1, 456 k with R = 2; 1 M x 1536: 366-403 k with R = 2, 385-413 k with R = 4, the default;
     // profiles/r05/hnsw_build_device_link.md).  Each row keeps its own accumulator and element order: the distances do not
     // depend on R.
+    // A bit mirror (T = BitRow, bit_hamming_ops: hamming_distance, src/bitvec.c:45-56) counts the differing bits of the
+    // same 16-byte vectors in an integer; the count (<= 64 000) and every partial sum of the reduction are exact in fp32.
     auto score_rows = [&](auto rc, int nb) __attribute__((always_inline)) {
         constexpr int R = decltype(rc)::value;
         const int step = kHnswWaves * rpw;
@@ -117,13 +120,13 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             int idx[R];
             bool valid[R];
             const char *rp[R];
-            float acc[R];
+            std::conditional_t<kBits, int, float> acc[R];
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 idx[r] = base + rsub + r * step;
                 valid[r] = idx[r] < nb;
                 rp[r] = g.rows + (size_t)bi[valid[r] ? idx[r] : nb - 1] * row_bytes;
-                acc[r] = 0.f;
+                acc[r] = 0;
             }
 #pragma unroll 2
             for (int c = 0; c < g.nchunks; c++) {
@@ -134,17 +137,22 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
 #pragma unroll
                 for (int r = 0; r < R; r++) rv[r] = load16(rp[r] + (size_t)vc * sizeof(Raw16));
                 const Raw16 qv = lq[vc];
-                Unpacked<T> uq(qv);
+                if constexpr (kBits) {
 #pragma unroll
-                for (int r = 0; r < R; r++) {
-                    Unpacked<T> ur(rv[r]);
+                    for (int r = 0; r < R; r++) acc[r] += ok ? hamming16(rv[r], qv) : 0;
+                } else {
+                    Unpacked<T> uq(qv);
 #pragma unroll
-                    for (int e = 0; e < N; e++) acc[r] = accum<METRIC>(acc[r], ok ? ur.v[e] : 0.f, ok ? uq.v[e] : 0.f);
+                    for (int r = 0; r < R; r++) {
+                        Unpacked<T> ur(rv[r]);
+#pragma unroll
+                        for (int e = 0; e < N; e++) acc[r] = accum<METRIC>(acc[r], ok ? ur.v[e] : 0.f, ok ? uq.v[e] : 0.f);
+                    }
                 }
             }
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                const float sum = group_sum_to_last(acc[r], g.lpr_log2);
+                const float sum = group_sum_to_last((float)acc[r], g.lpr_log2);
                 if (sub == lpr - 1 && valid[r]) bk[idx[r]] = float_to_key(finish<METRIC>(sum));
             }
         }
@@ -668,6 +676,23 @@ __global__ __launch_bounds__(256) void hnsw_select_wave_kernel(const int32_t *__
 
 }  // namespace
 
+// Lanes per bit row.  row_geom minimises wasted lane-trips of rows that are hundreds of vectors long; a bit row is 1 to
+// 500 vectors (1536 bits: 12), a walk's batch is at most 2 m of them, and a batch costs what its longest chain of
+// dependent loads costs.  So a row is spread over the smallest power of two of lanes that covers it in ONE trip (every
+// vector of every row of a batch in flight at once; the idle lanes of a 12-vector row on 16 lanes cost nothing a
+// latency-bound walk would notice), a whole wavefront in ceil(nvec / 64) <= 8 trips past 64 vectors (8192 bits).
+RowGeom bit_row_geom(int nbits) {
+    RowGeom g;
+    const int bytes = (nbits + 7) / 8;
+    g.nvec = (bytes + kVecBytes - 1) / kVecBytes;
+    if (g.nvec < 1) g.nvec = 1;
+    g.ld = g.nvec * kVecBytes;
+    g.lpr_log2 = 0;
+    while (g.lpr_log2 < 6 && (1 << g.lpr_log2) < g.nvec) g.lpr_log2++;
+    g.nchunks = (g.nvec + (1 << g.lpr_log2) - 1) >> g.lpr_log2;
+    return g;
+}
+
 int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out) {
     const int words = (int)((n + 31) / 32) + 1;
     int grid = ctx->num_cus * 4;
@@ -678,10 +703,11 @@ int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out) {
     return grid;
 }
 
-int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &geom, const void *rows,
-                       int64_t n, const int32_t *levels, const int64_t *nbr_start, const int32_t *nbr, int m,
-                       int32_t entry, const HnswSearchArgs &a, uint32_t *bitmaps, int words, int grid, int *counter) {
-    HnswDev g;
+// the graph and one launch's queries and outputs as the kernel takes them
+static void hnsw_kernel_args(const RowGeom &geom, const void *rows, int64_t n, const int32_t *levels,
+                             const int64_t *nbr_start, const int32_t *nbr, int m, int32_t entry, const HnswSearchArgs &a,
+                             HnswDev *gp, HnswRun *rp) {
+    HnswDev &g = *gp;
     g.rows = static_cast<const char *>(rows);
     g.nvec = geom.nvec;
     g.lpr_log2 = geom.lpr_log2;
@@ -692,7 +718,7 @@ int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const R
     g.m = m;
     g.entry = entry;
     g.n = n;
-    HnswRun run;
+    HnswRun &run = *rp;
     run.queries = static_cast<const char *>(a.queries);
     run.qids = a.qids;
     run.qlevels = a.qlevels;
@@ -710,6 +736,14 @@ int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const R
         static const int per_trip = getenv("PGV_HNSW_ROWS_PER_TRIP") ? atoi(getenv("PGV_HNSW_ROWS_PER_TRIP")) : 4;
         run.rows_per_trip = per_trip >= 4 ? 4 : (per_trip == 1 ? 1 : 2);
     }
+}
+
+int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &geom, const void *rows,
+                       int64_t n, const int32_t *levels, const int64_t *nbr_start, const int32_t *nbr, int m,
+                       int32_t entry, const HnswSearchArgs &a, uint32_t *bitmaps, int words, int grid, int *counter) {
+    HnswDev g;
+    HnswRun run;
+    hnsw_kernel_args(geom, rows, n, levels, nbr_start, nbr, m, entry, a, &g, &run);
     PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
 #define PGV_HNSW_M(T)                                                                      \
     switch (metric) {                                                                      \
@@ -727,6 +761,16 @@ int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const R
     }
 #undef PGV_HNSW_M
     PGV_FAIL(PGV_ERR_ARG, "hnsw search: unknown metric %d", (int)metric);
+}
+
+int launch_hnsw_search_bits(pgv_ctx *ctx, const RowGeom &geom, const void *rows, int64_t n, const int32_t *levels,
+                            const int64_t *nbr_start, const int32_t *nbr, int m, int32_t entry, const HnswSearchArgs &a,
+                            uint32_t *bitmaps, int words, int grid, int *counter) {
+    HnswDev g;
+    HnswRun run;
+    hnsw_kernel_args(geom, rows, n, levels, nbr_start, nbr, m, entry, a, &g, &run);
+    PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+    return launch_hnsw_t<BitRow, 0>(ctx, g, run, bitmaps, words, grid, counter);  // (the metric slot is unused)
 }
 
 int launch_hnsw_patch(pgv_ctx *ctx, int32_t *nbr, const int64_t *nbr_start, int64_t n, const int32_t *ids,

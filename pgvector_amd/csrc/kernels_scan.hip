@@ -182,14 +182,15 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
     const int64_t base = ((int64_t)blockIdx.x * kScanWaves + wave) * R * rpw;
     if (base >= npairs) return;
 
-    float acc[R];
+    constexpr bool kBits = std::is_same_v<T, BitRow>;  // packed bit rows: the differing bits, counted in an integer
+    std::conditional_t<kBits, int, float> acc[R];
     const char *rp[R];
     const char *qp[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
         int64_t p = base + r * rpw + rsub;
         p = p < npairs ? p : npairs - 1;
-        acc[r] = 0.f;
+        acc[r] = 0;
         rp[r] = rows + (size_t)slot[p] * row_bytes;
         qp[r] = queries + (size_t)(query_of ? query_of[p] : 0) * row_bytes;
     }
@@ -203,19 +204,24 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
             rv[r] = load16(rp[r] + (size_t)vc * sizeof(Raw16));
             qv[r] = load16(qp[r] + (size_t)vc * sizeof(Raw16));
         }
+        if constexpr (kBits) {
 #pragma unroll
-        for (int r = 0; r < R; r++) {
-            Unpacked<T> ur(rv[r]);
-            Unpacked<T> uq(qv[r]);
+            for (int r = 0; r < R; r++) acc[r] += ok ? hamming16(rv[r], qv[r]) : 0;
+        } else {
 #pragma unroll
-            for (int e = 0; e < N; e++)
-                acc[r] = accum<METRIC>(acc[r], ok ? ur.v[e] : 0.f, ok ? uq.v[e] : 0.f);
+            for (int r = 0; r < R; r++) {
+                Unpacked<T> ur(rv[r]);
+                Unpacked<T> uq(qv[r]);
+#pragma unroll
+                for (int e = 0; e < N; e++)
+                    acc[r] = accum<METRIC>(acc[r], ok ? ur.v[e] : 0.f, ok ? uq.v[e] : 0.f);
+            }
         }
     }
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const int64_t p = base + r * rpw + rsub;
-        float s = group_sum_to_last(acc[r], lpr_log2);
+        float s = group_sum_to_last((float)acc[r], lpr_log2);  // (a bit count and its partial sums are exact in fp32)
         if (sub == lpr - 1 && p < npairs) out[p] = finish<METRIC>(s);
     }
 }
@@ -473,6 +479,11 @@ int launch_score_gather(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const 
     }
 #undef PGV_GATHER
     PGV_FAIL(PGV_ERR_ARG, "score: unknown metric %d", (int)metric);
+}
+
+int launch_score_gather_bits(pgv_ctx *ctx, const RowGeom &g, const void *rows, const void *queries, const int32_t *slot,
+                             const int32_t *query_of, int64_t npairs, float *out) {
+    return launch_gather_t<BitRow, 0>(ctx, g, rows, queries, slot, query_of, npairs, out);  // (the metric slot is unused)
 }
 
 int launch_score_groups(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,

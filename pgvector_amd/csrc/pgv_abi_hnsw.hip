@@ -16,12 +16,62 @@ static size_t hnsw_payload_offset(int64_t n, size_t row_bytes) {
     return ((size_t)(n > 0 ? n : 1) * row_bytes + 255) & ~(size_t)255;
 }
 
+// a bit mirror (pgv_hnsw_upload_bits): rows of whole bytes scored by xor + popcount; no build-side entry serves it
+static bool hnsw_is_bits(const pgv_hnsw *h) { return h->nbits > 0; }
+
+#define PGV_NO_BITS(h, who)                                                                                      \
+    do {                                                                                                         \
+        if ((h) && hnsw_is_bits(h))                                                                              \
+            PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits) is searched and scored, not built on", who); \
+    } while (0)
+
+// the geometry of a mirror's rows: dim elements of dtype, or nbits bits
+static RowGeom hnsw_geom(int dim, pgv_dtype dtype, int nbits) { return nbits > 0 ? bit_row_geom(nbits) : row_geom(dim, dtype); }
+// bytes of one row as the caller packs it, and as the mirror keeps it (whole 16-byte vectors)
+static size_t hnsw_src_row_bytes(int dim, pgv_dtype dtype, int nbits) {
+    return nbits > 0 ? (size_t)(nbits + 7) / 8 : (size_t)dim * elem_size(dtype);
+}
+static size_t hnsw_row_bytes(const RowGeom &g) { return (size_t)g.nvec * kVecBytes; }
+
+// queries [nq x dim] of the mirror's element type -> device rows in the mirror's row layout
+static int hnsw_stage_queries(pgv_hnsw *h, const void *queries, int nq, const void **q_dev) {
+    pgv_ctx *ctx = h->ctx;
+    if (hnsw_is_bits(h))
+        return stage_bit_rows(ctx, queries, nq, (h->nbits + 7) / 8, h->geom.ld, ctx->q_stage, q_dev);
+    return stage_rows(ctx, queries, nq, h->dim, h->dtype, h->geom, ctx->q_stage, q_dev);
+}
+
+static int hnsw_upload_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nbits, const void *elements,
+                            int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out);
+
 int pgv_hnsw_upload_payload(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *elements,
                             int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {
     if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload: ctx/out is NULL");
     *out = nullptr;
     PGV_TRY(check_common(dtype, dim));
     PGV_TRY(check_metric(metric));
+    return hnsw_upload_rows(ctx, metric, dtype, dim, 0, elements, n, payload, payload_bytes, out);
+}
+
+// The element rows of an HNSW index over bit strings (`USING hnsw (... bit_hamming_ops)`, sql/vector.sql:901-905; type
+// info hnsw_bit_support, src/hnswutils.c:1403-1416): what hnswgettuple's first batch (src/hnswscan.c:25-56) scores with
+// hamming_distance (src/bitvec.c:45-56 over BitHammingDistanceDefault, src/bitutils.c:49-73) when it walks such an index.
+int pgv_hnsw_upload_bits(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
+                         const void *payload, int payload_bytes, pgv_hnsw **out) {
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_bits: ctx/out is NULL");
+    *out = nullptr;
+    if (metric == PGV_BIT_JACCARD)
+        PGV_FAIL(PGV_ERR_ARG,
+                 "pgv_hnsw_upload_bits: bit_jaccard_ops is not served: jaccard_distance is a float8 ratio, and the walk's "
+                 "fp32 keys would merge distances that the reference's strict stop test tells apart");
+    if (metric != PGV_BIT_HAMMING) PGV_FAIL(PGV_ERR_ARG, "unknown bit metric %d", (int)metric);
+    if (nbits < 1 || nbits > kHnswMaxBits)
+        PGV_FAIL(PGV_ERR_DIMS, "bit dimensions %d outside 1..%d (HNSW_MAX_DIM * 32, src/hnswutils.c:1414)", nbits, kHnswMaxBits);
+    return hnsw_upload_rows(ctx, PGV_L2SQ, PGV_F32, nbits, nbits, elements, n, payload, payload_bytes, out);
+}
+
+static int hnsw_upload_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nbits, const void *elements,
+                            int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {
     if (n < 0 || (n > 0 && !elements)) PGV_FAIL(PGV_ERR_ARG, "bad elements");
     if (payload_bytes < 0 || payload_bytes > 4096 || (payload_bytes & 3) || (payload_bytes > 0 && n > 0 && !payload))
         PGV_FAIL(PGV_ERR_ARG, "payload: 0..4096 bytes per element in whole words, got %d", payload_bytes);
@@ -32,9 +82,10 @@ int pgv_hnsw_upload_payload(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, in
     h->metric = metric;
     h->dtype = dtype;
     h->dim = dim;
+    h->nbits = nbits;
     h->n = n;
-    h->geom = row_geom(dim, dtype);
-    const size_t es = elem_size(dtype), row_bytes = (size_t)h->geom.ld * es;
+    h->geom = hnsw_geom(dim, dtype, nbits);
+    const size_t row_bytes = hnsw_row_bytes(h->geom), src_bytes = hnsw_src_row_bytes(dim, dtype, nbits);
     const size_t bytes = (size_t)(n > 0 ? n : 1) * row_bytes;
     // the payload (what a scan needs to turn an element into heap TIDs) rides in the same allocation, so that the one
     // IPC handle of the elements carries it to importing processes
@@ -56,13 +107,13 @@ int pgv_hnsw_upload_payload(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, in
     if (n > 0) {
         const bool dev = is_device_ptr(elements);
         hipError_t e;
-        if (h->geom.ld == dim) {
+        if (row_bytes == src_bytes) {
             e = hipMemcpyAsync(h->elements, elements, (size_t)n * row_bytes,
                                dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
         } else {
             e = hipMemsetAsync(h->elements, 0, bytes, ctx->stream);
             if (e == hipSuccess)
-                e = hipMemcpy2DAsync(h->elements, row_bytes, elements, (size_t)dim * es, (size_t)dim * es,
+                e = hipMemcpy2DAsync(h->elements, row_bytes, elements, src_bytes, src_bytes,
                                      (size_t)n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -119,6 +170,7 @@ int pgv_hnsw_share(pgv_hnsw *h, pgv_ctx *ctx, pgv_hnsw **out) {
     v->metric = h->metric;
     v->dtype = h->dtype;
     v->dim = h->dim;
+    v->nbits = h->nbits;
     v->n = h->n;
     v->geom = h->geom;
     v->elements = h->elements;
@@ -159,7 +211,7 @@ struct HnswHandleWire {
     int32_t device, metric, dtype, dim, m, entry;
     int64_t n, nbr_total;
     uint64_t graph_bytes;
-    int32_t payload_bytes, pad;
+    int32_t payload_bytes, nbits;  // nbits > 0: a bit mirror (pgv_hnsw_upload_bits); 0 otherwise, as the word always was
     hipIpcMemHandle_t elements, graph;
 };
 static_assert(sizeof(HnswHandleWire) <= PGV_INDEX_HANDLE_BYTES, "pgv_index_handle too small for an HNSW mirror");
@@ -187,6 +239,7 @@ int pgv_hnsw_export(pgv_hnsw *h, pgv_index_handle *out) {
     w.nbr_total = h->nbr_total;
     w.graph_bytes = h->graph_bytes;
     w.payload_bytes = h->payload_bytes;
+    w.nbits = h->nbits;
     hipError_t e = hipIpcGetMemHandle(&w.elements, h->elements);
     if (e == hipSuccess) e = hipIpcGetMemHandle(&w.graph, h->graph);
     if (e != hipSuccess) {
@@ -209,7 +262,10 @@ int pgv_hnsw_import(pgv_ctx *ctx, const pgv_index_handle *handle, pgv_hnsw **out
         PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_import: the handle was exported by this process");
     if (w.device != ctx->device)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_import: the mirror lives on device %d, the context on %d", w.device, ctx->device);
-    PGV_TRY(check_common((pgv_dtype)w.dtype, w.dim));
+    if (w.nbits != 0) {
+        if (w.nbits < 1 || w.nbits > kHnswMaxBits || w.dim != w.nbits) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_import: corrupt handle");
+    } else
+        PGV_TRY(check_common((pgv_dtype)w.dtype, w.dim));
     PGV_TRY(check_metric((pgv_metric)w.metric));
     if (w.n < 1 || w.m < 2 || w.m > 100 || w.entry < -1 || w.entry >= w.n || w.nbr_total < 0 || w.payload_bytes < 0 ||
         w.payload_bytes > 4096)
@@ -222,7 +278,8 @@ int pgv_hnsw_import(pgv_ctx *ctx, const pgv_index_handle *handle, pgv_hnsw **out
     h->dtype = (pgv_dtype)w.dtype;
     h->dim = w.dim;
     h->n = w.n;
-    h->geom = row_geom(w.dim, h->dtype);
+    h->nbits = w.nbits;
+    h->geom = hnsw_geom(w.dim, h->dtype, w.nbits);
     h->m = w.m;
     h->entry = w.entry;
     h->imported = true;
@@ -245,7 +302,7 @@ int pgv_hnsw_import(pgv_ctx *ctx, const pgv_index_handle *handle, pgv_hnsw **out
     h->nbr = reinterpret_cast<int32_t *>(base + lb + sb);
     h->payload_bytes = w.payload_bytes;
     h->payload = w.payload_bytes > 0
-                     ? static_cast<char *>(h->elements) + hnsw_payload_offset(h->n, (size_t)h->geom.ld * elem_size(h->dtype))
+                     ? static_cast<char *>(h->elements) + hnsw_payload_offset(h->n, hnsw_row_bytes(h->geom))
                      : nullptr;
     *out = h;
     return PGV_OK;
@@ -279,14 +336,18 @@ int pgv_hnsw_score(pgv_hnsw *h, const void *queries, int nq, const int32_t *slot
     pgv_ctx *ctx = h->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     const void *q_dev, *s_dev, *qo_dev = nullptr;
-    PGV_TRY(stage_rows(ctx, queries, nq, h->dim, h->dtype, h->geom, ctx->q_stage, &q_dev));
+    PGV_TRY(hnsw_stage_queries(h, queries, nq, &q_dev));
     PGV_TRY(stage_flat(ctx, slot, sizeof(int32_t) * (size_t)npairs, ctx->idx_stage, &s_dev));
     if (query_of) PGV_TRY(stage_flat(ctx, query_of, sizeof(int32_t) * (size_t)npairs, ctx->plan_d, &qo_dev));
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
-    PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, q_dev,
-                                static_cast<const int32_t *>(s_dev), static_cast<const int32_t *>(qo_dev),
-                                npairs, od.as<float>()));
+    if (hnsw_is_bits(h))
+        PGV_TRY(launch_score_gather_bits(ctx, h->geom, h->elements, q_dev, static_cast<const int32_t *>(s_dev),
+                                         static_cast<const int32_t *>(qo_dev), npairs, od.as<float>()));
+    else
+        PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, q_dev,
+                                    static_cast<const int32_t *>(s_dev), static_cast<const int32_t *>(qo_dev),
+                                    npairs, od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -347,7 +408,7 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
     PGV_HIP(hipSetDevice(ctx->device));
     PGV_TRY(hnsw_graph_acquire(h));
     const void *q_dev;
-    PGV_TRY(stage_rows(ctx, queries, nq, h->dim, h->dtype, h->geom, ctx->q_stage, &q_dev));
+    PGV_TRY(hnsw_stage_queries(h, queries, nq, &q_dev));
     int words = 0;
     const int grid = hnsw_search_grid(ctx, nq, h->n, &words);
     PGV_TRY(h->bitmaps.ensure((size_t)grid * words * sizeof(uint32_t)));
@@ -364,9 +425,13 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
     a.out_elem = oe.as<int64_t>();
     a.out_dist = od.as<float>();
     a.out_scored = out_scored ? os.as<int64_t>() : nullptr;
-    PGV_TRY(launch_hnsw_search(ctx, h->metric, h->dtype, h->geom, h->elements, h->n, h->levels, h->nbr_start,
-                               h->nbr, h->m, h->entry, a, h->bitmaps.as<uint32_t>(), words, grid,
-                               ctx->counters.as<int>()));
+    if (hnsw_is_bits(h))
+        PGV_TRY(launch_hnsw_search_bits(ctx, h->geom, h->elements, h->n, h->levels, h->nbr_start, h->nbr, h->m, h->entry, a,
+                                        h->bitmaps.as<uint32_t>(), words, grid, ctx->counters.as<int>()));
+    else
+        PGV_TRY(launch_hnsw_search(ctx, h->metric, h->dtype, h->geom, h->elements, h->n, h->levels, h->nbr_start,
+                                   h->nbr, h->m, h->entry, a, h->bitmaps.as<uint32_t>(), words, grid,
+                                   ctx->counters.as<int>()));
     bool need = false;
     PGV_TRY(oe.finish(ctx, &need));
     PGV_TRY(od.finish(ctx, &need));
@@ -377,6 +442,7 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
 int pgv_hnsw_build_search(pgv_hnsw *h, const int32_t *elements, const int32_t *insert_levels, int nq,
                           int ef_construction, int layer_cap, int32_t *out_ids, float *out_dist, int32_t *out_count) {
     if (!h || !out_ids || !out_dist || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_search: handle/out is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_build_search");
     hnsw_view_refresh(h);
     if (nq < 0 || layer_cap < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     if (ef_construction < 4 || ef_construction > 1000)
@@ -506,6 +572,7 @@ int pgv_hnsw_build_neighbors(pgv_hnsw *h, const int32_t *elements, const int32_t
                              int32_t *out_count, int64_t *out_pairs) {
     if (!h || !out_ids || !out_dist || !out_closer || !out_count)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_neighbors: handle/out is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_build_neighbors");
     hnsw_view_refresh(h);
     PGV_TRY(hnsw_build_args(h, "pgv_hnsw_build_neighbors", nq, ef_construction, layer_cap));
     if (out_pairs) *out_pairs = 0;
@@ -536,6 +603,7 @@ int pgv_hnsw_build_neighbors(pgv_hnsw *h, const int32_t *elements, const int32_t
 int pgv_hnsw_build_search_keep(pgv_hnsw *h, const int32_t *elements, const int32_t *insert_levels, int nq, int ef_construction,
                                int layer_cap, int slot) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_search_keep: handle is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_build_search_keep");
     hnsw_view_refresh(h);
     pgv_hnsw *o = h->view_of ? h->view_of : h;
     if (!o->link) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_build_search_keep needs pgv_hnsw_link_begin");
@@ -569,6 +637,7 @@ int pgv_hnsw_build_select_kept(pgv_hnsw *h, int slot, int32_t *out_ids, float *o
                                int64_t *out_pairs) {
     if (!h || !out_ids || !out_dist || !out_closer || !out_count)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_select_kept: handle/out is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_build_select_kept");
     // (no view refresh: the entry point may be moving under pgv_hnsw_link_apply on another thread, and nothing here looks
     // at the graph -- the kept lists, the element rows and m, which is fixed for the build)
     pgv_hnsw *o = h->view_of ? h->view_of : h;
@@ -597,9 +666,13 @@ int pgv_hnsw_score_pairs(pgv_hnsw *h, const int32_t *a, const int32_t *b, int64_
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
     // the element mirror is its own query array: pair i = (row a[i], "query" b[i])
-    PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements,
-                                static_cast<const int32_t *>(a_dev), static_cast<const int32_t *>(b_dev), npairs,
-                                od.as<float>()));
+    if (hnsw_is_bits(h))
+        PGV_TRY(launch_score_gather_bits(ctx, h->geom, h->elements, h->elements, static_cast<const int32_t *>(a_dev),
+                                         static_cast<const int32_t *>(b_dev), npairs, od.as<float>()));
+    else
+        PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements,
+                                    static_cast<const int32_t *>(a_dev), static_cast<const int32_t *>(b_dev), npairs,
+                                    od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -608,6 +681,7 @@ int pgv_hnsw_score_pairs(pgv_hnsw *h, const int32_t *a, const int32_t *b, int64_
 int pgv_hnsw_score_groups(pgv_hnsw *h, const int32_t *ids, const int64_t *ids_start, const int32_t *from,
                           const int64_t *pair_start, int ngroups, int64_t nids, int64_t npairs, float *out) {
     if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_score_groups: handle/out is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_score_groups");
     if (ngroups < 0 || nids < 0 || npairs < 0) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     if (ngroups == 0 || npairs == 0) return PGV_OK;
     if (!ids || !ids_start || !from || !pair_start) PGV_FAIL(PGV_ERR_ARG, "ids/ids_start/from/pair_start is NULL");
@@ -680,6 +754,7 @@ static void hnsw_link_free(pgv_hnsw *o) {
 
 int pgv_hnsw_link_begin(pgv_hnsw *h) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin: handle is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_link_begin");
     if (h->imported || h->view_of) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_begin: an imported mirror / a view is read-only");
     if (h->m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin needs pgv_hnsw_set_graph first");
     pgv_ctx *ctx = h->ctx;
@@ -716,6 +791,7 @@ int pgv_hnsw_link_begin(pgv_hnsw *h) {
 int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *linked, int nq, int layer_cap,
                           const int32_t *sel_ids, const float *sel_dist, const uint8_t *sel_closer, const int32_t *sel_count,
                           int64_t *out_pairs) {
+    PGV_NO_BITS(h, "pgv_hnsw_link_prepare");
     if (!h || !h->link) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_prepare needs pgv_hnsw_link_begin");
     if (nq < 0 || layer_cap < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     HnswLinkState *L = h->link;
@@ -828,6 +904,7 @@ int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *l
 }
 
 int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
+    PGV_NO_BITS(h, "pgv_hnsw_link_apply");
     if (!h || !h->link || !h->link->prepared) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_apply needs pgv_hnsw_link_prepare");
     if (entry < -1 || entry >= h->n) PGV_FAIL(PGV_ERR_ARG, "entry point %d out of range", (int)entry);
     HnswLinkState *L = h->link;
@@ -897,6 +974,7 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
 
 int pgv_hnsw_link_end(pgv_hnsw *h, int32_t *out_nbr, int64_t *out_pairs, int64_t *out_deferred) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_end: handle is NULL");
+    PGV_NO_BITS(h, "pgv_hnsw_link_end");
     if (out_pairs) *out_pairs = 0;
     if (out_deferred) *out_deferred = 0;
     if (!h->link) return PGV_OK;

@@ -22,6 +22,12 @@ template <> struct VecTraits<__half> {
     static constexpr int N = 8;
 };
 
+// ... or 128 bits of a packed bit string (the HNSW mirror of a bit_hamming_ops index, pgv_hnsw::nbits): a tag, never a value
+struct BitRow {};
+template <> struct VecTraits<BitRow> {
+    static constexpr int N = 128;
+};
+
 struct alignas(16) Raw16 {
     uint32_t w[4];
 };
@@ -34,6 +40,12 @@ __device__ __forceinline__ Raw16 raw16_zero() {
 
 __device__ __forceinline__ Raw16 load16(const void *p) {
     return *reinterpret_cast<const Raw16 *>(p);
+}
+
+// differing bits of two 16-byte slices (BitHammingDistanceDefault, src/bitutils.c:49-73: popcount of the xor, whole
+// bytes; zero padding adds nothing)
+__device__ __forceinline__ int hamming16(const Raw16 &a, const Raw16 &b) {
+    return __popc(a.w[0] ^ b.w[0]) + __popc(a.w[1] ^ b.w[1]) + __popc(a.w[2] ^ b.w[2]) + __popc(a.w[3] ^ b.w[3]);
 }
 
 // unpack to fp32 lanes (exact for binary16: src/halfutils.h:62-141)

@@ -62,6 +62,8 @@ bool is_device_ptr(const void *p);
 
 constexpr int kVecBytes = 16;  // every row is padded to whole 16-byte vectors in HBM
 
+constexpr int kHnswMaxBits = 64000;  // bit rows of an HNSW mirror: HNSW_MAX_DIM * 32 (src/hnswutils.c:1414)
+
 inline int elem_size(pgv_dtype t) { return t == PGV_F32 ? 4 : 2; }
 // padded row length in elements
 inline int padded_dim(int dim, pgv_dtype t) {
@@ -77,6 +79,9 @@ struct RowGeom {
     int nchunks;    // loop trips over the row
 };
 RowGeom row_geom(int dim, pgv_dtype t);
+// ... of a packed bit row of nbits (kernels_hnsw.hip): the lane split of the walk and the pair scorer over a bit
+// mirror (pgv_hnsw::nbits); ld is the padded row length in BYTES
+RowGeom bit_row_geom(int nbits);
 
 // one unit of streaming work: rows [row0, row0 + nrows) scored against
 // pairs [pair0, pair0 + npairs)
@@ -221,6 +226,9 @@ struct pgv_hnsw {
     pgv_metric metric = PGV_L2SQ;
     pgv_dtype dtype = PGV_F32;
     int dim = 0;
+    // > 0: a mirror of packed bit strings (pgv_hnsw_upload_bits).  Its element type is not a pgv_dtype: rows are nbits
+    // bits in geom.nvec 16-byte vectors, scored by xor + popcount; metric, dtype and dim are unused (dim = nbits)
+    int nbits = 0;
     int64_t n = 0;
     pgv::RowGeom geom{};
     void *elements = nullptr;  // [n x ld]
@@ -421,6 +429,9 @@ int launch_expand_groups(pgv_ctx *ctx, const int32_t *ids, const int64_t *ids_st
 int launch_score_gather(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
                         const void *rows, const void *queries, const int32_t *slot,
                         const int32_t *query_of, int64_t npairs, float *out);
+// ... over packed bit rows (g: bit_row_geom): the Hamming distance of each pair, exact
+int launch_score_gather_bits(pgv_ctx *ctx, const RowGeom &g, const void *rows, const void *queries, const int32_t *slot,
+                             const int32_t *query_of, int64_t npairs, float *out);
 // the pairs (u, v < u), u >= from, inside groups of rows, in 4 x 4 tiles (bit for bit score_gather's values).  Group g is
 // ids[ids_at[g] ..) (ids_at NULL: g * ids_stride), n_arr[g] rows (NULL: ids_at[g + 1] - ids_at[g]), from_arr[g] (NULL: 1);
 // its pairs go to out[pair_at[g] ..); pair_at[g + 1] == pair_at[g]: nothing wanted
@@ -466,6 +477,10 @@ struct HnswSearchArgs {
 int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &geom, const void *rows,
                        int64_t n, const int32_t *levels, const int64_t *nbr_start, const int32_t *nbr, int m,
                        int32_t entry, const HnswSearchArgs &a, uint32_t *bitmaps, int words, int grid, int *counter);
+// ... over packed bit rows (geom: bit_row_geom; queries in the same layout): the same walk, Hamming distances
+int launch_hnsw_search_bits(pgv_ctx *ctx, const RowGeom &geom, const void *rows, int64_t n, const int32_t *levels,
+                            const int64_t *nbr_start, const int32_t *nbr, int m, int32_t entry, const HnswSearchArgs &a,
+                            uint32_t *bitmaps, int words, int grid, int *counter);
 int launch_hnsw_patch(pgv_ctx *ctx, int32_t *nbr, const int64_t *nbr_start, int64_t n, const int32_t *ids,
                       const int64_t *packed_off, const int32_t *packed, int nupd);
 
