@@ -7,8 +7,8 @@
  *
  * Plain C, no pointers into a graph: the list is three arrays (element, distance, closer flag) plus each item's "local"
  * -- its index in the record's id list, which is how the pair distances are found (a triangle (u, v < u), u >= from, the
- * layout pgv_hnsw_score_groups / hnsw_link_pairs_kernel write).  ONE source for two compilations:
- *   - kernels_hnsw.hip includes it with PGV_LINK_FN = __device__: hnsw_link_kernel runs it, one lane per list;
+ * layout score_groups_kernel, expand_groups_kernel and hnsw_link_pairs_kernel write).  ONE source for two compilations:
+ *   - kernels_hnsw_link.hip includes it with PGV_LINK_FN = __device__: hnsw_link_kernel runs it, one lane per list;
  *   - tests/c/mock_hip.c includes it as host C, so that the CPU tests of the host build exercise this very code.
  * pgvector_amd/host/hnsw_build.c holds the older host-side replay of the same steps (pointer-based, with a cached sort
  * order); tests/test_gpu_round5.py builds the same graphs both ways.  tests/test_gpu_hnsw_link_edges.py drives the device

@@ -465,9 +465,10 @@ int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *
 // and a list of at most lm candidates is taken whole, in W's own (furthest first) order (:1072-1073).
 //
 // Three launches on the searches' stream: which lists need thinning and where their pair triangles go (one workgroup:
-// an exclusive scan), the (u, v < u) slot pairs of those lists for score_gather_kernel, and -- after the scoring -- the
-// sweep itself, one lane per list: its inner loop is a dependent chain of comparisons, the lists of a batch are
-// thousands, and a wavefront's 64 lists share nothing, so lanes are the parallelism.
+// an exclusive scan), those lists' (u, v < u) distances (score_groups_kernel, or expand_groups_kernel's slot pairs
+// through score_gather_kernel), and the sweep itself, one lane per list: its inner loop is a dependent chain of
+// comparisons, the lists of a batch are thousands, and a wavefront's 64 lists share nothing, so lanes are the
+// parallelism.
 
 // pairs of list g = (query, layer): cnt * (cnt - 1) / 2 when it has to be thinned, else none; start[] by exclusive scan
 // (256 threads: a larger workgroup waits for a whole CU's worth of room while another stream's searches fill the chip)
@@ -519,26 +520,6 @@ __global__ __launch_bounds__(256) void hnsw_select_plan_kernel(const int32_t *__
         __syncthreads();
     }
     if (threadIdx.x == 0) pair_start[ngroups] = carry_s;
-}
-
-// the pairs (u, v < u) of every list that is thinned, u ascending then v: a[] = slot of u, b[] = slot of v
-__global__ __launch_bounds__(256) void hnsw_select_pairs_kernel(const int32_t *__restrict__ lw_ids, const int32_t *__restrict__ cnt,
-                                                                 const int64_t *__restrict__ pair_start, int ngroups, int ef,
-                                                                 int32_t *__restrict__ a, int32_t *__restrict__ b) {
-    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        int64_t at = pair_start[g];
-        if (pair_start[g + 1] == at) continue;
-        const int32_t *gi = lw_ids + (size_t)g * ef;
-        const int n = cnt[g];
-        for (int u = 1; u < n; u++) {
-            const int32_t iu = gi[u];
-            for (int v = threadIdx.x; v < u; v += blockDim.x) {
-                a[at + v] = iu;
-                b[at + v] = gi[v];
-            }
-            at += u;
-        }
-    }
 }
 
 // the sweep: list g's candidates are lw_ids / lw_dist[g * ef ..), nearest first; tri = its pair distances.
@@ -703,22 +684,21 @@ int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out) {
     return grid;
 }
 
-// the graph and one launch's queries and outputs as the kernel takes them
-static void hnsw_kernel_args(const RowGeom &geom, const void *rows, int64_t n, const int32_t *levels,
-                             const int64_t *nbr_start, const int32_t *nbr, int m, int32_t entry, const HnswSearchArgs &a,
-                             HnswDev *gp, HnswRun *rp) {
-    HnswDev &g = *gp;
-    g.rows = static_cast<const char *>(rows);
-    g.nvec = geom.nvec;
-    g.lpr_log2 = geom.lpr_log2;
-    g.nchunks = geom.nchunks;
-    g.levels = levels;
-    g.nbr_start = nbr_start;
-    g.nbr = nbr;
-    g.m = m;
-    g.entry = entry;
-    g.n = n;
-    HnswRun &run = *rp;
+int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const HnswSearchArgs &a, uint32_t *bitmaps,
+                       int words, int grid, int *counter) {
+    // the rows, the graph and one launch's queries and outputs as the kernel takes them
+    HnswDev g;
+    g.rows = static_cast<const char *>(v.rows);
+    g.nvec = v.geom.nvec;
+    g.lpr_log2 = v.geom.lpr_log2;
+    g.nchunks = v.geom.nchunks;
+    g.levels = graph.levels;
+    g.nbr_start = graph.nbr_start;
+    g.nbr = graph.nbr;
+    g.m = graph.m;
+    g.entry = graph.entry;
+    g.n = v.n;
+    HnswRun run;
     run.queries = static_cast<const char *>(a.queries);
     run.qids = a.qids;
     run.qlevels = a.qlevels;
@@ -732,68 +712,38 @@ static void hnsw_kernel_args(const RowGeom &geom, const void *rows, int64_t n, c
     run.lw_dist = a.lw_dist;
     run.lw_cnt = a.lw_cnt;
     run.lcap = a.lcap;
-    {
-        static const int per_trip = getenv("PGV_HNSW_ROWS_PER_TRIP") ? atoi(getenv("PGV_HNSW_ROWS_PER_TRIP")) : 4;
-        run.rows_per_trip = per_trip >= 4 ? 4 : (per_trip == 1 ? 1 : 2);
-    }
-}
-
-int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &geom, const void *rows,
-                       int64_t n, const int32_t *levels, const int64_t *nbr_start, const int32_t *nbr, int m,
-                       int32_t entry, const HnswSearchArgs &a, uint32_t *bitmaps, int words, int grid, int *counter) {
-    HnswDev g;
-    HnswRun run;
-    hnsw_kernel_args(geom, rows, n, levels, nbr_start, nbr, m, entry, a, &g, &run);
+    static const int per_trip = getenv("PGV_HNSW_ROWS_PER_TRIP") ? atoi(getenv("PGV_HNSW_ROWS_PER_TRIP")) : 4;
+    run.rows_per_trip = per_trip >= 4 ? 4 : (per_trip == 1 ? 1 : 2);
     PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-#define PGV_HNSW_M(T)                                                                      \
-    switch (metric) {                                                                      \
-        case PGV_L2SQ:                                                                     \
-            return launch_hnsw_t<T, 0>(ctx, g, run, bitmaps, words, grid, counter);        \
-        case PGV_NEG_IP:                                                                   \
-            return launch_hnsw_t<T, 1>(ctx, g, run, bitmaps, words, grid, counter);        \
-        case PGV_L1:                                                                       \
-            return launch_hnsw_t<T, 2>(ctx, g, run, bitmaps, words, grid, counter);        \
-    }
-    if (dtype == PGV_F32) {
-        PGV_HNSW_M(float)
-    } else {
-        PGV_HNSW_M(__half)
-    }
-#undef PGV_HNSW_M
-    PGV_FAIL(PGV_ERR_ARG, "hnsw search: unknown metric %d", (int)metric);
+    return dispatch_rows(v, [&](auto *tp, auto mc) {
+        return launch_hnsw_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, g, run, bitmaps, words, grid, counter);
+    });
 }
 
-int launch_hnsw_search_bits(pgv_ctx *ctx, const RowGeom &geom, const void *rows, int64_t n, const int32_t *levels,
-                            const int64_t *nbr_start, const int32_t *nbr, int m, int32_t entry, const HnswSearchArgs &a,
-                            uint32_t *bitmaps, int words, int grid, int *counter) {
-    HnswDev g;
-    HnswRun run;
-    hnsw_kernel_args(geom, rows, n, levels, nbr_start, nbr, m, entry, a, &g, &run);
-    PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
-    return launch_hnsw_t<BitRow, 0>(ctx, g, run, bitmaps, words, grid, counter);  // (the metric slot is unused)
-}
-
-int launch_hnsw_patch(pgv_ctx *ctx, int32_t *nbr, const int64_t *nbr_start, int64_t n, const int32_t *ids,
-                      const int64_t *packed_off, const int32_t *packed, int nupd) {
+int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int32_t *ids, const int64_t *packed_off,
+                      const int32_t *packed, int nupd) {
     if (nupd <= 0) return PGV_OK;
-    hipLaunchKernelGGL(hnsw_patch_kernel, dim3((nupd + 3) / 4), dim3(256), 0, ctx->stream, nbr, nbr_start, n, ids,
+    hipLaunchKernelGGL(hnsw_patch_kernel, dim3((nupd + 3) / 4), dim3(256), 0, ctx->stream, graph.nbr, graph.nbr_start, n, ids,
                        packed_off, packed, nupd);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-// pgv_hnsw_score_groups: the (u, v) pairs of every group written out as the slot arrays score_gather_kernel reads.
+// The (u, v) pairs of every group written out as the slot arrays score_gather_kernel reads (PGV_HNSW_PAIRS_GATHER=1), in
+// the order score_groups_kernel writes their values; the groups are described as they are to that kernel.
 // One workgroup per group (grid-stride), a row u per step, the row's v spread over the threads (coalesced).
-__global__ __launch_bounds__(256) void expand_groups_kernel(const int32_t *__restrict__ ids,
-                                                            const int64_t *__restrict__ ids_start,
-                                                            const int32_t *__restrict__ from,
-                                                            const int64_t *__restrict__ pair_start, int ngroups,
+__global__ __launch_bounds__(256) void expand_groups_kernel(const int32_t *__restrict__ ids, const int64_t *__restrict__ ids_at,
+                                                            int64_t ids_stride, const int32_t *__restrict__ n_arr,
+                                                            const int32_t *__restrict__ from_arr,
+                                                            const int64_t *__restrict__ pair_at, int ngroups,
                                                             int32_t *__restrict__ a, int32_t *__restrict__ b) {
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        const int32_t *gi = ids + ids_start[g];
-        const int n = (int)(ids_start[g + 1] - ids_start[g]);
-        const int f = from[g] < 1 ? 1 : from[g];
-        int64_t at = pair_start[g];
+        int64_t at = pair_at[g];
+        if (pair_at[g + 1] == at) continue;
+        const int64_t i0 = ids_at ? ids_at[g] : (int64_t)g * ids_stride;
+        const int n = n_arr ? n_arr[g] : (int)(ids_at[g + 1] - i0);
+        const int32_t *gi = ids + i0;
+        const int f = from_arr && from_arr[g] > 1 ? from_arr[g] : 1;
         for (int u = f; u < n; u++) {
             const int32_t iu = gi[u];
             for (int v = threadIdx.x; v < u; v += blockDim.x) {
@@ -805,12 +755,12 @@ __global__ __launch_bounds__(256) void expand_groups_kernel(const int32_t *__res
     }
 }
 
-int launch_expand_groups(pgv_ctx *ctx, const int32_t *ids, const int64_t *ids_start, const int32_t *from,
-                         const int64_t *pair_start, int ngroups, int32_t *a, int32_t *b) {
+int launch_expand_groups(pgv_ctx *ctx, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride, const int32_t *n_arr,
+                         const int32_t *from_arr, const int64_t *pair_at, int ngroups, int32_t *a, int32_t *b) {
     if (ngroups <= 0) return PGV_OK;
     const int cap = ctx->num_cus * 16;
-    hipLaunchKernelGGL(expand_groups_kernel, dim3(ngroups < cap ? ngroups : cap), dim3(256), 0, ctx->stream, ids,
-                       ids_start, from, pair_start, ngroups, a, b);
+    hipLaunchKernelGGL(expand_groups_kernel, dim3(ngroups < cap ? ngroups : cap), dim3(256), 0, ctx->stream, ids, ids_at,
+                       ids_stride, n_arr, from_arr, pair_at, ngroups, a, b);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -819,16 +769,6 @@ int launch_expand_groups(pgv_ctx *ctx, const int32_t *ids, const int64_t *ids_st
 int launch_hnsw_select_plan(pgv_ctx *ctx, const int32_t *cnt, int ngroups, int lcap, int m, int64_t *pair_start) {
     if (ngroups <= 0) return PGV_OK;
     hipLaunchKernelGGL(hnsw_select_plan_kernel, dim3(1), dim3(256), 0, ctx->stream, cnt, ngroups, lcap, m, pair_start);
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
-}
-
-int launch_hnsw_select_pairs(pgv_ctx *ctx, const int32_t *lw_ids, const int32_t *cnt, const int64_t *pair_start, int ngroups,
-                             int ef, int32_t *a, int32_t *b) {
-    if (ngroups <= 0) return PGV_OK;
-    const int cap = ctx->num_cus * 16;
-    hipLaunchKernelGGL(hnsw_select_pairs_kernel, dim3(ngroups < cap ? ngroups : cap), dim3(256), 0, ctx->stream, lw_ids, cnt,
-                       pair_start, ngroups, ef, a, b);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -2,7 +2,7 @@
 // the neighbor lists they chose (HnswUpdateNeighborsInMemory -> HnswUpdateConnection, src/hnswbuild.c:376-405,
 // src/hnswutils.c:1183-1231), every list replayed by one lane with the reference's SelectNeighbors (hnsw_link_core.h).
 //
-// The graph state lives next to the mirror's neighbor tuples (pgv_hnsw::nbr, the array the searches read): for every
+// The graph state lives next to the mirror's neighbor tuples (HnswGraph::nbr, the array the searches read): for every
 // tuple slot the neighbor's distance to the owner (nb_dist) and its cached `closer` flag (nb_flag bit 0; bit 1 of a
 // list's first slot = the list's closerSet).  A list's length is its run of non-negative slots.
 //
@@ -553,33 +553,32 @@ __global__ __launch_bounds__(256) void hnsw_link_new_kernel(int32_t *__restrict_
 
 }  // namespace
 
-int launch_hnsw_link_group(pgv_ctx *ctx, int step, const int32_t *elems, const uint8_t *linked, int nq, int lcap, int m,
-                           const int32_t *sel_ids, const float *sel_dist, const int32_t *sel_cnt, const int32_t *levels,
-                           const int64_t *nbr_start, int *list_count, int *list_rec, int *nrec, int32_t *rec_owner,
-                           int32_t *rec_lc, int32_t *rec_list, const int64_t *rec_off, int *rec_fill, int32_t *link_elem,
-                           float *link_dist) {
+int launch_hnsw_link_group(pgv_ctx *ctx, int step, const HnswGraph &graph, const int32_t *elems, const uint8_t *linked, int nq,
+                           int lcap, const int32_t *sel_ids, const float *sel_dist, const int32_t *sel_cnt, int *list_count,
+                           int *list_rec, int *nrec, int32_t *rec_owner, int32_t *rec_lc, int32_t *rec_list,
+                           const int64_t *rec_off, int *rec_fill, int32_t *link_elem, float *link_dist) {
+    const int m = graph.m;
     const int64_t n = (int64_t)nq * lcap * 2 * m;
     if (n <= 0) return PGV_OK;
     const dim3 grid((unsigned)((n + 255) / 256));
     if (step == 0)
         hipLaunchKernelGGL(hnsw_link_count_kernel, grid, dim3(256), 0, ctx->stream, elems, linked, nq, lcap, m, sel_ids, sel_cnt,
-                           levels, nbr_start, list_count, list_rec, nrec, rec_owner, rec_lc, rec_list);
+                           graph.levels, graph.nbr_start, list_count, list_rec, nrec, rec_owner, rec_lc, rec_list);
     else
         hipLaunchKernelGGL(hnsw_link_fill_kernel, grid, dim3(256), 0, ctx->stream, elems, linked, nq, lcap, m, sel_ids, sel_dist,
-                           sel_cnt, levels, nbr_start, list_rec, rec_off, rec_fill, link_elem, link_dist);
+                           sel_cnt, graph.levels, graph.nbr_start, list_rec, rec_off, rec_fill, link_elem, link_dist);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-int launch_hnsw_link_size(pgv_ctx *ctx, const int32_t *nbr, const uint8_t *nb_flag, const int32_t *levels,
-                          const int64_t *nbr_start, int m, const int32_t *rec_owner, const int32_t *rec_lc,
-                          const int32_t *rec_list, const int *list_count, int64_t *rec_off, int nrec, int pass, int64_t *rec_pos,
-                          int32_t *rec_nstart, int32_t *rec_from, const int32_t *rec_wait, int64_t *size_ids,
-                          int64_t *size_pairs) {
+int launch_hnsw_link_size(pgv_ctx *ctx, const HnswGraph &graph, const uint8_t *nb_flag, const int32_t *rec_owner,
+                          const int32_t *rec_lc, const int32_t *rec_list, const int *list_count, int64_t *rec_off, int nrec,
+                          int pass, int64_t *rec_pos, int32_t *rec_nstart, int32_t *rec_from, const int32_t *rec_wait,
+                          int64_t *size_ids, int64_t *size_pairs) {
     if (nrec <= 0) return PGV_OK;
-    hipLaunchKernelGGL(hnsw_link_size_kernel, dim3((nrec + 255) / 256), dim3(256), 0, ctx->stream, nbr, nb_flag, levels,
-                       nbr_start, m, rec_owner, rec_lc, rec_list, list_count, rec_off, nrec, pass, rec_pos, rec_nstart, rec_from,
-                       rec_wait, size_ids, size_pairs);
+    hipLaunchKernelGGL(hnsw_link_size_kernel, dim3((nrec + 255) / 256), dim3(256), 0, ctx->stream, graph.nbr, nb_flag,
+                       graph.levels, graph.nbr_start, graph.m, rec_owner, rec_lc, rec_list, list_count, rec_off, nrec, pass,
+                       rec_pos, rec_nstart, rec_from, rec_wait, size_ids, size_pairs);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -608,14 +607,15 @@ int launch_hnsw_link_pairs(pgv_ctx *ctx, const int32_t *nbr, const int64_t *rec_
     return PGV_OK;
 }
 
-int launch_hnsw_link_replay(pgv_ctx *ctx, int32_t *nbr, float *nb_dist, uint8_t *nb_flag, int m, int nrec, int pass,
+int launch_hnsw_link_replay(pgv_ctx *ctx, const HnswGraph &graph, float *nb_dist, uint8_t *nb_flag, int nrec, int pass,
                             const int32_t *rec_lc, const int64_t *rec_off, const float *link_dist, const int64_t *rec_pos,
                             const int32_t *rec_nstart, const int32_t *rec_from, const int64_t *ids_start, const int32_t *ids,
                             const int64_t *pair_start, const float *tri, const int64_t *mm_start, const float *mm,
                             int32_t *rec_wait, int16_t *loc_save, int *blocked) {
     if (nrec <= 0) return PGV_OK;
+    const int m = graph.m;
     LinkArgs g;
-    g.nbr = nbr;
+    g.nbr = graph.nbr;
     g.nb_dist = nb_dist;
     g.nb_flag = nb_flag;
     g.m = m;
@@ -656,13 +656,13 @@ int launch_hnsw_link_replay(pgv_ctx *ctx, int32_t *nbr, float *nb_dist, uint8_t 
     return PGV_OK;
 }
 
-int launch_hnsw_link_new(pgv_ctx *ctx, int32_t *nbr, float *nb_dist, uint8_t *nb_flag, const int32_t *levels,
-                         const int64_t *nbr_start, int m, const int32_t *elems, const uint8_t *linked, int nq, int lcap,
-                         const int32_t *sel_ids, const float *sel_dist, const uint8_t *sel_closer, const int32_t *sel_cnt) {
+int launch_hnsw_link_new(pgv_ctx *ctx, const HnswGraph &graph, float *nb_dist, uint8_t *nb_flag, const int32_t *elems,
+                         const uint8_t *linked, int nq, int lcap, const int32_t *sel_ids, const float *sel_dist,
+                         const uint8_t *sel_closer, const int32_t *sel_cnt) {
     const int n = nq * lcap;
     if (n <= 0) return PGV_OK;
-    hipLaunchKernelGGL(hnsw_link_new_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, nbr, nb_dist, nb_flag, levels,
-                       nbr_start, m, elems, linked, nq, lcap, sel_ids, sel_dist, sel_closer, sel_cnt);
+    hipLaunchKernelGGL(hnsw_link_new_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, graph.nbr, nb_dist, nb_flag,
+                       graph.levels, graph.nbr_start, graph.m, elems, linked, nq, lcap, sel_ids, sel_dist, sel_closer, sel_cnt);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -754,22 +754,6 @@ template <typename T, int METRIC, typename F> int dispatch_nch(const RowGeom &g,
     return f(std::integral_constant<int, 0>());
 }
 
-template <typename F> int dispatch_metric(pgv_metric metric, pgv_dtype dtype, F f) {
-#define PGV_QM(T)                                                                     \
-    switch (metric) {                                                                 \
-        case PGV_L2SQ: return f((T *)nullptr, std::integral_constant<int, 0>());      \
-        case PGV_NEG_IP: return f((T *)nullptr, std::integral_constant<int, 1>());    \
-        case PGV_L1: return f((T *)nullptr, std::integral_constant<int, 2>());        \
-    }
-    if (dtype == PGV_F32) {
-        PGV_QM(float)
-    } else {
-        PGV_QM(__half)
-    }
-#undef PGV_QM
-    PGV_FAIL(PGV_ERR_ARG, "query: unknown metric %d", (int)metric);
-}
-
 }  // namespace
 
 int query_max_batch_lists() { return kMaxBatchLists; }

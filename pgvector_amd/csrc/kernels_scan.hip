@@ -363,24 +363,6 @@ int launch_scan_m(pgv_ctx *ctx, const RowGeom &g, const void *rows, const void *
 #undef PGV_SCAN
 }
 
-template <typename T>
-int launch_scan_d(pgv_ctx *ctx, pgv_metric metric, const RowGeom &g, const void *rows,
-                  const void *queries, const ScanTask *tasks, const int *ntasks_dev,
-                  int ntasks_bound, const ScanPair *pairs, int qt, float *out) {
-    switch (metric) {
-        case PGV_L2SQ:
-            return launch_scan_m<T, 0>(ctx, g, rows, queries, tasks, ntasks_dev, ntasks_bound,
-                                       pairs, qt, out);
-        case PGV_NEG_IP:
-            return launch_scan_m<T, 1>(ctx, g, rows, queries, tasks, ntasks_dev, ntasks_bound,
-                                       pairs, qt, out);
-        case PGV_L1:
-            return launch_scan_m<T, 2>(ctx, g, rows, queries, tasks, ntasks_dev, ntasks_bound,
-                                       pairs, qt, out);
-    }
-    PGV_FAIL(PGV_ERR_ARG, "scan: unknown metric %d", (int)metric);
-}
-
 template <typename T, int METRIC>
 int launch_gather_t(pgv_ctx *ctx, const RowGeom &g, const void *rows, const void *queries,
                     const int32_t *slot, const int32_t *query_of, int64_t npairs, float *out) {
@@ -453,58 +435,27 @@ int launch_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom 
                 const void *rows, const void *queries, const ScanTask *tasks,
                 const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt,
                 float *out) {
-    if (dtype == PGV_F32)
-        return launch_scan_d<float>(ctx, metric, g, rows, queries, tasks, ntasks_dev,
-                                    ntasks_bound, pairs, qt, out);
-    return launch_scan_d<__half>(ctx, metric, g, rows, queries, tasks, ntasks_dev, ntasks_bound,
-                                 pairs, qt, out);
+    return dispatch_metric(metric, dtype, [&](auto *tp, auto mc) {
+        return launch_scan_m<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, g, rows, queries, tasks, ntasks_dev,
+                                                                                       ntasks_bound, pairs, qt, out);
+    });
 }
 
-int launch_score_gather(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-                        const void *rows, const void *queries, const int32_t *slot,
-                        const int32_t *query_of, int64_t npairs, float *out) {
-#define PGV_GATHER(T)                                                                         \
-    switch (metric) {                                                                         \
-        case PGV_L2SQ:                                                                        \
-            return launch_gather_t<T, 0>(ctx, g, rows, queries, slot, query_of, npairs, out); \
-        case PGV_NEG_IP:                                                                      \
-            return launch_gather_t<T, 1>(ctx, g, rows, queries, slot, query_of, npairs, out); \
-        case PGV_L1:                                                                          \
-            return launch_gather_t<T, 2>(ctx, g, rows, queries, slot, query_of, npairs, out); \
-    }
-    if (dtype == PGV_F32) {
-        PGV_GATHER(float)
-    } else {
-        PGV_GATHER(__half)
-    }
-#undef PGV_GATHER
-    PGV_FAIL(PGV_ERR_ARG, "score: unknown metric %d", (int)metric);
+int launch_score_gather(pgv_ctx *ctx, const RowsView &v, const void *queries, const int32_t *slot, const int32_t *query_of,
+                        int64_t npairs, float *out) {
+    return dispatch_rows(v, [&](auto *tp, auto mc) {
+        return launch_gather_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, v.geom, v.rows, queries, slot,
+                                                                                         query_of, npairs, out);
+    });
 }
 
-int launch_score_gather_bits(pgv_ctx *ctx, const RowGeom &g, const void *rows, const void *queries, const int32_t *slot,
-                             const int32_t *query_of, int64_t npairs, float *out) {
-    return launch_gather_t<BitRow, 0>(ctx, g, rows, queries, slot, query_of, npairs, out);  // (the metric slot is unused)
-}
-
-int launch_score_groups(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,
-                        const int32_t *ids, const int64_t *ids_at, int64_t ids_stride, const int32_t *n_arr,
-                        const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out) {
-#define PGV_GROUPS(T)                                                                                                   \
-    switch (metric) {                                                                                                   \
-        case PGV_L2SQ:                                                                                                  \
-            return launch_groups_t<T, 0>(ctx, g, rows, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out); \
-        case PGV_NEG_IP:                                                                                                \
-            return launch_groups_t<T, 1>(ctx, g, rows, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out); \
-        case PGV_L1:                                                                                                    \
-            return launch_groups_t<T, 2>(ctx, g, rows, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out); \
-    }
-    if (dtype == PGV_F32) {
-        PGV_GROUPS(float)
-    } else {
-        PGV_GROUPS(__half)
-    }
-#undef PGV_GROUPS
-    PGV_FAIL(PGV_ERR_ARG, "score: unknown metric %d", (int)metric);
+int launch_score_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride,
+                        const int32_t *n_arr, const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out) {
+    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "score groups: fp32 / fp16 rows only");
+    return dispatch_metric(v.metric, v.dtype(), [&](auto *tp, auto mc) {
+        return launch_groups_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(
+            ctx, v.geom, v.rows, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out);
+    });
 }
 
 }  // namespace pgv

@@ -270,25 +270,10 @@ int launch_tile_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const Row
     if (!tile_scan_supported(g)) PGV_FAIL(PGV_ERR_ARG, "tile scan: row shape not supported");
     const int nch = g.nvec / kWave;
     const int tr = tile_scan_tile_rows(g);
-#define PGV_TILE_M(T)                                                                           \
-    switch (metric) {                                                                           \
-        case PGV_L2SQ:                                                                          \
-            return launch_tile_n<T, 0>(ctx, nch, rows, queries, tasks, ntasks_dev, ntasks_bound, \
-                                       pairs, tr, out);                                         \
-        case PGV_NEG_IP:                                                                        \
-            return launch_tile_n<T, 1>(ctx, nch, rows, queries, tasks, ntasks_dev, ntasks_bound, \
-                                       pairs, tr, out);                                         \
-        case PGV_L1:                                                                            \
-            return launch_tile_n<T, 2>(ctx, nch, rows, queries, tasks, ntasks_dev, ntasks_bound, \
-                                       pairs, tr, out);                                         \
-    }
-    if (dtype == PGV_F32) {
-        PGV_TILE_M(float)
-    } else {
-        PGV_TILE_M(__half)
-    }
-#undef PGV_TILE_M
-    PGV_FAIL(PGV_ERR_ARG, "tile scan: unknown metric %d", (int)metric);
+    return dispatch_metric(metric, dtype, [&](auto *tp, auto mc) {
+        return launch_tile_n<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, nch, rows, queries, tasks, ntasks_dev,
+                                                                                       ntasks_bound, pairs, tr, out);
+    });
 }
 
 }  // namespace pgv

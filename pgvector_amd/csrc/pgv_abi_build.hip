@@ -332,7 +332,7 @@ int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const 
     int64_t *pos = ctx->plan_c.as<int64_t>();
     if (n > 0) {
         PGV_TRY(launch_rerank_pairs(ctx, cd, total, kc, slot, query_of));
-        PGV_TRY(launch_score_gather(ctx, metric, dtype, g, r_dev, q_dev, slot, query_of, total, vals));
+        PGV_TRY(launch_score_gather(ctx, RowsView{r_dev, n, g, row_kind(dtype), metric}, q_dev, slot, query_of, total, vals));
     }
     PGV_TRY(launch_rerank_mask(ctx, cd, total, vals));  // (n == 0: every entry is "none")
     PGV_TRY(launch_topk_segments(ctx, vals, nullptr, nq, kc, k, od.as<float>(), pos));

@@ -146,16 +146,26 @@ static int hnsw_graph_acquire(pgv_hnsw *h) {
 
 // a view follows its owner: the graph may have been (re)set and the entry point moved since the view was made
 static void hnsw_view_refresh(pgv_hnsw *h) {
-    const pgv_hnsw *o = h->view_of;
-    if (!o) return;
-    h->graph = o->graph;
-    h->levels = o->levels;
-    h->nbr_start = o->nbr_start;
-    h->nbr = o->nbr;
-    h->m = o->m;
-    h->entry = o->entry;
-    h->graph_bytes = o->graph_bytes;
-    h->nbr_total = o->nbr_total;
+    if (h->view_of) h->graph = h->view_of->graph;
+}
+
+// The arrays of a graph over n elements with g->nbr_total neighbor slots in its one allocation, levels | nbr_start |
+// nbr, each rounded to 16 bytes: in g->mem where an importer has opened it, in a fresh exportable allocation otherwise.
+// The process that sets a graph and the ones that import it both come here, so they agree on the layout
+static int hnsw_graph_carve(HnswGraph *g, int64_t n) {
+    const size_t lb = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16;
+    const size_t sb = ((size_t)(n + 1) * sizeof(int64_t) + 15) / 16 * 16;
+    g->bytes = lb + sb + (size_t)(g->nbr_total > 0 ? g->nbr_total : 1) * sizeof(int32_t);
+    if (!g->mem && malloc_exportable(&g->mem, g->bytes) != hipSuccess) {
+        const size_t bytes = g->bytes;
+        *g = HnswGraph();
+        PGV_FAIL(PGV_ERR_NOMEM, "hipMalloc(%zu) for the hnsw graph failed", bytes);
+    }
+    char *base = static_cast<char *>(g->mem);
+    g->levels = reinterpret_cast<const int32_t *>(base);
+    g->nbr_start = reinterpret_cast<const int64_t *>(base + lb);
+    g->nbr = reinterpret_cast<int32_t *>(base + lb + sb);
+    return PGV_OK;
 }
 
 int pgv_hnsw_device(const pgv_hnsw *h) { return h && h->ctx ? h->ctx->device : -1; }
@@ -166,16 +176,8 @@ int pgv_hnsw_share(pgv_hnsw *h, pgv_ctx *ctx, pgv_hnsw **out) {
     if (ctx->device != h->ctx->device) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_share: the mirror lives on another device");
     pgv_hnsw *v = new (std::nothrow) pgv_hnsw();
     if (!v) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
+    static_cast<HnswElements &>(*v) = *h;
     v->ctx = ctx;
-    v->metric = h->metric;
-    v->dtype = h->dtype;
-    v->dim = h->dim;
-    v->nbits = h->nbits;
-    v->n = h->n;
-    v->geom = h->geom;
-    v->elements = h->elements;
-    v->payload = h->payload;
-    v->payload_bytes = h->payload_bytes;
     v->view_of = h->view_of ? h->view_of : h;
     hnsw_view_refresh(v);
     *out = v;
@@ -196,10 +198,10 @@ void pgv_hnsw_free(pgv_hnsw *h) {
     if (h->graph_ev) (void)hipEventDestroy(h->graph_ev);
     if (h->imported) {
         if (h->elements) (void)hipIpcCloseMemHandle(h->elements);
-        if (h->graph) (void)hipIpcCloseMemHandle(h->graph);
+        if (h->graph.mem) (void)hipIpcCloseMemHandle(h->graph.mem);
     } else {
         if (h->elements) (void)hipFree(h->elements);
-        if (h->graph) (void)hipFree(h->graph);
+        if (h->graph.mem) (void)hipFree(h->graph.mem);
     }
     h->bitmaps.release();
     delete h;
@@ -220,7 +222,7 @@ static constexpr uint64_t kHnswHandleMagic = 0x7067765f686e7731ull;  // "pgv_hnw
 int pgv_hnsw_export(pgv_hnsw *h, pgv_index_handle *out) {
     if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_export: handle/out is NULL");
     if (h->imported || h->view_of) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_export: export from the process that uploaded the mirror");
-    if (!h->elements || !h->graph || h->m == 0)
+    if (!h->elements || !h->graph.mem || h->graph.m == 0)
         PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_export: needs a non-empty mirror with its graph set (pgv_hnsw_set_graph)");
     PGV_HIP(hipSetDevice(h->ctx->device));
     PGV_HIP(hipStreamSynchronize(h->ctx->stream));
@@ -233,15 +235,15 @@ int pgv_hnsw_export(pgv_hnsw *h, pgv_index_handle *out) {
     w.metric = h->metric;
     w.dtype = h->dtype;
     w.dim = h->dim;
-    w.m = h->m;
-    w.entry = h->entry;
+    w.m = h->graph.m;
+    w.entry = h->graph.entry;
     w.n = h->n;
-    w.nbr_total = h->nbr_total;
-    w.graph_bytes = h->graph_bytes;
+    w.nbr_total = h->graph.nbr_total;
+    w.graph_bytes = h->graph.bytes;
     w.payload_bytes = h->payload_bytes;
     w.nbits = h->nbits;
     hipError_t e = hipIpcGetMemHandle(&w.elements, h->elements);
-    if (e == hipSuccess) e = hipIpcGetMemHandle(&w.graph, h->graph);
+    if (e == hipSuccess) e = hipIpcGetMemHandle(&w.graph, h->graph.mem);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         PGV_FAIL(PGV_ERR_DEVICE, "hipIpcGetMemHandle failed: %s (HSA_ENABLE_IPC_MODE_LEGACY=0 must be set)", hipGetErrorString(e));
@@ -280,26 +282,19 @@ int pgv_hnsw_import(pgv_ctx *ctx, const pgv_index_handle *handle, pgv_hnsw **out
     h->n = w.n;
     h->nbits = w.nbits;
     h->geom = hnsw_geom(w.dim, h->dtype, w.nbits);
-    h->m = w.m;
-    h->entry = w.entry;
+    h->graph.m = w.m;
+    h->graph.entry = w.entry;
+    h->graph.nbr_total = w.nbr_total;
     h->imported = true;
-    h->nbr_total = w.nbr_total;
-    h->graph_bytes = w.graph_bytes;
     hipError_t e = hipIpcOpenMemHandle(&h->elements, w.elements, hipIpcMemLazyEnablePeerAccess);
-    if (e == hipSuccess) e = hipIpcOpenMemHandle(&h->graph, w.graph, hipIpcMemLazyEnablePeerAccess);
+    if (e == hipSuccess) e = hipIpcOpenMemHandle(&h->graph.mem, w.graph, hipIpcMemLazyEnablePeerAccess);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (h->elements && !h->graph) { (void)hipIpcCloseMemHandle(h->elements); }
-        h->elements = h->graph = nullptr;
+        if (h->elements && !h->graph.mem) { (void)hipIpcCloseMemHandle(h->elements); }
         delete h;
         PGV_FAIL(PGV_ERR_DEVICE, "hipIpcOpenMemHandle failed: %s", hipGetErrorString(e));
     }
-    const size_t lb = ((size_t)h->n * sizeof(int32_t) + 15) / 16 * 16;
-    const size_t sb = ((size_t)(h->n + 1) * sizeof(int64_t) + 15) / 16 * 16;
-    char *base = static_cast<char *>(h->graph);
-    h->levels = reinterpret_cast<const int32_t *>(base);
-    h->nbr_start = reinterpret_cast<const int64_t *>(base + lb);
-    h->nbr = reinterpret_cast<int32_t *>(base + lb + sb);
+    (void)hnsw_graph_carve(&h->graph, h->n);  // (in the opened allocation; its bytes are the exporter's w.graph_bytes)
     h->payload_bytes = w.payload_bytes;
     h->payload = w.payload_bytes > 0
                      ? static_cast<char *>(h->elements) + hnsw_payload_offset(h->n, hnsw_row_bytes(h->geom))
@@ -341,13 +336,8 @@ int pgv_hnsw_score(pgv_hnsw *h, const void *queries, int nq, const int32_t *slot
     if (query_of) PGV_TRY(stage_flat(ctx, query_of, sizeof(int32_t) * (size_t)npairs, ctx->plan_d, &qo_dev));
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
-    if (hnsw_is_bits(h))
-        PGV_TRY(launch_score_gather_bits(ctx, h->geom, h->elements, q_dev, static_cast<const int32_t *>(s_dev),
-                                         static_cast<const int32_t *>(qo_dev), npairs, od.as<float>()));
-    else
-        PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, q_dev,
-                                    static_cast<const int32_t *>(s_dev), static_cast<const int32_t *>(qo_dev),
-                                    npairs, od.as<float>()));
+    PGV_TRY(launch_score_gather(ctx, hnsw_rows(h), q_dev, static_cast<const int32_t *>(s_dev),
+                                static_cast<const int32_t *>(qo_dev), npairs, od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -363,34 +353,52 @@ int pgv_hnsw_set_graph(pgv_hnsw *h, int m, int32_t entry, const int32_t *levels,
     pgv_ctx *ctx = h->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     PGV_HIP(hipStreamSynchronize(ctx->stream));  // no search may still be reading the old graph
-    if (h->graph) {
-        PGV_HIP(hipFree(h->graph));
-        h->graph = nullptr;
-    }
-    h->m = m;
-    h->entry = entry;
+    HnswGraph &g = h->graph;
+    if (g.mem) PGV_HIP(hipFree(g.mem));
+    g = HnswGraph();
+    g.m = m;
+    g.entry = entry;
     if (h->n == 0) return PGV_OK;
     // total neighbor slots: the last offset (it may live on either side)
     int64_t total = 0;
     PGV_HIP(hipMemcpy(&total, nbr_start + h->n, sizeof(int64_t), hipMemcpyDefault));
     if (total < 0) PGV_FAIL(PGV_ERR_ARG, "nbr_start is not an offset array");
-    const size_t lb = ((size_t)h->n * sizeof(int32_t) + 15) / 16 * 16;
-    const size_t sb = ((size_t)(h->n + 1) * sizeof(int64_t) + 15) / 16 * 16;
-    const size_t nb = (size_t)(total > 0 ? total : 1) * sizeof(int32_t);
-    if (malloc_exportable(&h->graph, lb + sb + nb) != hipSuccess)
-        PGV_FAIL(PGV_ERR_NOMEM, "hipMalloc(%zu) for the hnsw graph failed", lb + sb + nb);
-    char *base = static_cast<char *>(h->graph);
-    PGV_HIP(hipMemcpyAsync(base, levels, (size_t)h->n * sizeof(int32_t), hipMemcpyDefault, ctx->stream));
-    PGV_HIP(hipMemcpyAsync(base + lb, nbr_start, (size_t)(h->n + 1) * sizeof(int64_t), hipMemcpyDefault, ctx->stream));
-    if (total > 0)
-        PGV_HIP(hipMemcpyAsync(base + lb + sb, nbr, (size_t)total * sizeof(int32_t), hipMemcpyDefault, ctx->stream));
+    g.nbr_total = total;
+    PGV_TRY(hnsw_graph_carve(&g, h->n));
+    // (the one place that writes levels and nbr_start)
+    PGV_HIP(hipMemcpyAsync(const_cast<int32_t *>(g.levels), levels, (size_t)h->n * sizeof(int32_t), hipMemcpyDefault, ctx->stream));
+    PGV_HIP(hipMemcpyAsync(const_cast<int64_t *>(g.nbr_start), nbr_start, (size_t)(h->n + 1) * sizeof(int64_t), hipMemcpyDefault,
+                           ctx->stream));
+    if (total > 0) PGV_HIP(hipMemcpyAsync(g.nbr, nbr, (size_t)total * sizeof(int32_t), hipMemcpyDefault, ctx->stream));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
-    h->levels = reinterpret_cast<const int32_t *>(base);
-    h->nbr_start = reinterpret_cast<const int64_t *>(base + lb);
-    h->nbr = reinterpret_cast<int32_t *>(base + lb + sb);
-    h->graph_bytes = lb + sb + nb;
-    h->nbr_total = total;
     return PGV_OK;
+}
+
+// one launch of the walk over the mirror as it stands, on its context's stream: the workgroups, their visited sets, the
+// query counter
+static int hnsw_run_search(pgv_hnsw *h, const HnswSearchArgs &a) {
+    pgv_ctx *ctx = h->ctx;
+    int words = 0;
+    const int grid = hnsw_search_grid(ctx, a.nq, h->n, &words);
+    PGV_TRY(h->bitmaps.ensure((size_t)grid * words * sizeof(uint32_t)));
+    PGV_TRY(ctx->counters.ensure(256));
+    return launch_hnsw_search(ctx, hnsw_rows(h), h->graph, a, h->bitmaps.as<uint32_t>(), words, grid, ctx->counters.as<int>());
+}
+
+// the searches of a batch of the build into lw_* (device arrays [nq x layer_cap x ef] / [nq x layer_cap]), on ctx's stream
+static int hnsw_search_into(pgv_hnsw *h, const int32_t *e_dev, const int32_t *l_dev, int nq, int ef_construction, int layer_cap,
+                            int32_t *lw_ids, float *lw_dist, int32_t *lw_cnt) {
+    HnswSearchArgs a;
+    a.qids = e_dev;
+    a.qlevels = l_dev;
+    a.nq = nq;
+    a.ef = ef_construction;
+    a.k = 0;
+    a.lw_ids = lw_ids;
+    a.lw_dist = lw_dist;
+    a.lw_cnt = lw_cnt;
+    a.lcap = layer_cap;
+    return hnsw_run_search(h, a);
 }
 
 int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int k, int64_t *out_elem,
@@ -401,7 +409,7 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
     if (ef_search < 1 || ef_search > 1000)
         PGV_FAIL(PGV_ERR_ARG, "hnsw.ef_search must be 1..1000 (src/hnsw.c:93-94), got %d", ef_search);
     if (k < 1 || k > ef_search) PGV_FAIL(PGV_ERR_ARG, "k must be 1..ef_search, got %d", k);
-    if (h->m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_search needs pgv_hnsw_set_graph first");
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_search needs pgv_hnsw_set_graph first");
     if (nq == 0) return PGV_OK;
     if (!queries) PGV_FAIL(PGV_ERR_ARG, "queries is NULL");
     pgv_ctx *ctx = h->ctx;
@@ -409,10 +417,6 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
     PGV_TRY(hnsw_graph_acquire(h));
     const void *q_dev;
     PGV_TRY(hnsw_stage_queries(h, queries, nq, &q_dev));
-    int words = 0;
-    const int grid = hnsw_search_grid(ctx, nq, h->n, &words);
-    PGV_TRY(h->bitmaps.ensure((size_t)grid * words * sizeof(uint32_t)));
-    PGV_TRY(ctx->counters.ensure(256));
     OutArg oe, od, os;
     PGV_TRY(oe.init(out_elem, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
     PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
@@ -425,13 +429,7 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
     a.out_elem = oe.as<int64_t>();
     a.out_dist = od.as<float>();
     a.out_scored = out_scored ? os.as<int64_t>() : nullptr;
-    if (hnsw_is_bits(h))
-        PGV_TRY(launch_hnsw_search_bits(ctx, h->geom, h->elements, h->n, h->levels, h->nbr_start, h->nbr, h->m, h->entry, a,
-                                        h->bitmaps.as<uint32_t>(), words, grid, ctx->counters.as<int>()));
-    else
-        PGV_TRY(launch_hnsw_search(ctx, h->metric, h->dtype, h->geom, h->elements, h->n, h->levels, h->nbr_start,
-                                   h->nbr, h->m, h->entry, a, h->bitmaps.as<uint32_t>(), words, grid,
-                                   ctx->counters.as<int>()));
+    PGV_TRY(hnsw_run_search(h, a));
     bool need = false;
     PGV_TRY(oe.finish(ctx, &need));
     PGV_TRY(od.finish(ctx, &need));
@@ -447,7 +445,7 @@ int pgv_hnsw_build_search(pgv_hnsw *h, const int32_t *elements, const int32_t *i
     if (nq < 0 || layer_cap < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     if (ef_construction < 4 || ef_construction > 1000)
         PGV_FAIL(PGV_ERR_ARG, "ef_construction must be 4..1000 (src/hnsw.h:58-59), got %d", ef_construction);
-    if (h->m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_search needs pgv_hnsw_set_graph first");
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_search needs pgv_hnsw_set_graph first");
     if (nq == 0) return PGV_OK;
     if (!elements || !insert_levels) PGV_FAIL(PGV_ERR_ARG, "elements/insert_levels is NULL");
     pgv_ctx *ctx = h->ctx;
@@ -456,28 +454,13 @@ int pgv_hnsw_build_search(pgv_hnsw *h, const int32_t *elements, const int32_t *i
     const void *e_dev, *l_dev;
     PGV_TRY(stage_flat(ctx, elements, sizeof(int32_t) * (size_t)nq, ctx->idx_stage, &e_dev));
     PGV_TRY(stage_flat(ctx, insert_levels, sizeof(int32_t) * (size_t)nq, ctx->plan_d, &l_dev));
-    int words = 0;
-    const int grid = hnsw_search_grid(ctx, nq, h->n, &words);
-    PGV_TRY(h->bitmaps.ensure((size_t)grid * words * sizeof(uint32_t)));
-    PGV_TRY(ctx->counters.ensure(256));
     const size_t per = (size_t)nq * layer_cap;
     OutArg oi, od, oc;
     PGV_TRY(oi.init(out_ids, sizeof(int32_t) * per * ef_construction, ctx->out_stage2));
     PGV_TRY(od.init(out_dist, sizeof(float) * per * ef_construction, ctx->out_stage));
     PGV_TRY(oc.init(out_count, sizeof(int32_t) * per, ctx->sel_b));
-    HnswSearchArgs a;
-    a.qids = static_cast<const int32_t *>(e_dev);
-    a.qlevels = static_cast<const int32_t *>(l_dev);
-    a.nq = nq;
-    a.ef = ef_construction;
-    a.k = 0;
-    a.lw_ids = oi.as<int32_t>();
-    a.lw_dist = od.as<float>();
-    a.lw_cnt = oc.as<int32_t>();
-    a.lcap = layer_cap;
-    PGV_TRY(launch_hnsw_search(ctx, h->metric, h->dtype, h->geom, h->elements, h->n, h->levels, h->nbr_start,
-                               h->nbr, h->m, h->entry, a, h->bitmaps.as<uint32_t>(), words, grid,
-                               ctx->counters.as<int>()));
+    PGV_TRY(hnsw_search_into(h, static_cast<const int32_t *>(e_dev), static_cast<const int32_t *>(l_dev), nq, ef_construction,
+                             layer_cap, oi.as<int32_t>(), od.as<float>(), oc.as<int32_t>()));
     bool need = false;
     PGV_TRY(oi.finish(ctx, &need));
     PGV_TRY(od.finish(ctx, &need));
@@ -485,36 +468,15 @@ int pgv_hnsw_build_search(pgv_hnsw *h, const int32_t *elements, const int32_t *i
     return sync_if(ctx, need);
 }
 
-// the searches of a batch into lw_* (device arrays [nq x layer_cap x ef] / [nq x layer_cap]), on ctx's stream
-static int hnsw_search_into(pgv_hnsw *h, const int32_t *e_dev, const int32_t *l_dev, int nq, int ef_construction, int layer_cap,
-                            int32_t *lw_ids, float *lw_dist, int32_t *lw_cnt) {
-    pgv_ctx *ctx = h->ctx;
-    int words = 0;
-    const int grid = hnsw_search_grid(ctx, nq, h->n, &words);
-    PGV_TRY(h->bitmaps.ensure((size_t)grid * words * sizeof(uint32_t)));
-    PGV_TRY(ctx->counters.ensure(256));
-    HnswSearchArgs a;
-    a.qids = e_dev;
-    a.qlevels = l_dev;
-    a.nq = nq;
-    a.ef = ef_construction;
-    a.k = 0;
-    a.lw_ids = lw_ids;
-    a.lw_dist = lw_dist;
-    a.lw_cnt = lw_cnt;
-    a.lcap = layer_cap;
-    return launch_hnsw_search(ctx, h->metric, h->dtype, h->geom, h->elements, h->n, h->levels, h->nbr_start, h->nbr, h->m,
-                              h->entry, a, h->bitmaps.as<uint32_t>(), words, grid, ctx->counters.as<int>());
-}
-
 // SelectNeighbors over the candidate lists lw_* of a batch (device arrays), on ctx's stream; outputs as pgv_hnsw_build_neighbors
 static int hnsw_select_from(pgv_hnsw *h, const int32_t *lw_ids, const float *lw_dist, const int32_t *lw_cnt, const int32_t *l_dev,
                             int nq, int ef_construction, int layer_cap, int32_t *out_ids, float *out_dist, uint8_t *out_closer,
                             int32_t *out_count, int64_t *out_pairs) {
     pgv_ctx *ctx = h->ctx;
-    const int m = h->m, stride = 2 * m;
+    const int m = h->graph.m, stride = 2 * m;
     const size_t per = (size_t)nq * layer_cap;
     const int ngroups = (int)per;
+    const RowsView rows = hnsw_rows(h);
     PGV_TRY(ctx->km_e.ensure(sizeof(int64_t) * (per + 1)));
     int64_t *pair_start = ctx->km_e.as<int64_t>();
     // which lists SelectNeighbors has to thin, and where each one's pair triangle goes; the total comes back (8 bytes:
@@ -531,13 +493,13 @@ static int hnsw_select_from(pgv_hnsw *h, const int32_t *lw_ids, const float *lw_
         if (hnsw_pairs_by_gather()) {
             PGV_TRY(ctx->km_f.ensure(sizeof(int32_t) * (size_t)npairs));
             PGV_TRY(ctx->km_g.ensure(sizeof(int32_t) * (size_t)npairs));
-            PGV_TRY(launch_hnsw_select_pairs(ctx, lw_ids, lw_cnt, pair_start, ngroups, ef_construction, ctx->km_f.as<int32_t>(),
-                                             ctx->km_g.as<int32_t>()));
-            PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements, ctx->km_f.as<int32_t>(),
-                                        ctx->km_g.as<int32_t>(), npairs, ctx->dist_mat.as<float>()));
+            PGV_TRY(launch_expand_groups(ctx, lw_ids, nullptr, ef_construction, lw_cnt, nullptr, pair_start, ngroups,
+                                         ctx->km_f.as<int32_t>(), ctx->km_g.as<int32_t>()));
+            PGV_TRY(launch_score_gather(ctx, rows, rows.rows, ctx->km_f.as<int32_t>(), ctx->km_g.as<int32_t>(), npairs,
+                                        ctx->dist_mat.as<float>()));
         } else
-            PGV_TRY(launch_score_groups(ctx, h->metric, h->dtype, h->geom, h->elements, lw_ids, nullptr, ef_construction, lw_cnt,
-                                        nullptr, pair_start, ngroups, ctx->dist_mat.as<float>()));
+            PGV_TRY(launch_score_groups(ctx, rows, lw_ids, nullptr, ef_construction, lw_cnt, nullptr, pair_start, ngroups,
+                                        ctx->dist_mat.as<float>()));
     } else
         PGV_TRY(ctx->dist_mat.ensure(16));
     OutArg oi, od, oc, on;
@@ -560,8 +522,8 @@ static int hnsw_build_args(pgv_hnsw *h, const char *who, int nq, int ef_construc
     if (nq < 0 || layer_cap < 1) PGV_FAIL(PGV_ERR_ARG, "%s: bad sizes", who);
     if (ef_construction < 4 || ef_construction > 1000)
         PGV_FAIL(PGV_ERR_ARG, "ef_construction must be 4..1000 (src/hnsw.h:58-59), got %d", ef_construction);
-    if (h->m == 0) PGV_FAIL(PGV_ERR_ARG, "%s needs pgv_hnsw_set_graph first", who);
-    const int stride = 2 * h->m;
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "%s needs pgv_hnsw_set_graph first", who);
+    const int stride = 2 * h->graph.m;
     if ((size_t)nq * layer_cap > 0x7fffffff / (size_t)(ef_construction > stride ? ef_construction : stride))
         PGV_FAIL(PGV_ERR_ARG, "%s: batch too large", who);
     return PGV_OK;
@@ -647,7 +609,7 @@ int pgv_hnsw_build_select_kept(pgv_hnsw *h, int slot, int32_t *out_ids, float *o
     const HnswLinkState::Kept &K = o->link->kept[slot];
     if (K.nq == 0) return PGV_OK;
     PGV_HIP(hipSetDevice(h->ctx->device));
-    h->m = o->m;
+    h->graph.m = o->graph.m;
     const int32_t *l_dev = K.elems.as<int32_t>() + K.nq;
     return hnsw_select_from(h, K.ids.as<int32_t>(), K.dist.as<float>(), K.cnt.as<int32_t>(), l_dev, K.nq, K.ef, K.lcap, out_ids,
                             out_dist, out_closer, out_count, out_pairs);
@@ -666,13 +628,8 @@ int pgv_hnsw_score_pairs(pgv_hnsw *h, const int32_t *a, const int32_t *b, int64_
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
     // the element mirror is its own query array: pair i = (row a[i], "query" b[i])
-    if (hnsw_is_bits(h))
-        PGV_TRY(launch_score_gather_bits(ctx, h->geom, h->elements, h->elements, static_cast<const int32_t *>(a_dev),
-                                         static_cast<const int32_t *>(b_dev), npairs, od.as<float>()));
-    else
-        PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements,
-                                    static_cast<const int32_t *>(a_dev), static_cast<const int32_t *>(b_dev), npairs,
-                                    od.as<float>()));
+    PGV_TRY(launch_score_gather(ctx, hnsw_rows(h), h->elements, static_cast<const int32_t *>(a_dev),
+                                static_cast<const int32_t *>(b_dev), npairs, od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -702,23 +659,19 @@ int pgv_hnsw_score_groups(pgv_hnsw *h, const int32_t *ids, const int64_t *ids_st
     PGV_TRY(put(tab + b_ids, ids_start, b_start));
     PGV_TRY(put(tab + b_ids + b_start, pair_start, b_start));
     PGV_TRY(put(tab + b_ids + 2 * b_start, from, sizeof(int32_t) * (size_t)ngroups));
+    const int32_t *g_ids = reinterpret_cast<const int32_t *>(tab), *g_from = reinterpret_cast<const int32_t *>(tab + b_ids + 2 * b_start);
+    const int64_t *g_at = reinterpret_cast<const int64_t *>(tab + b_ids), *g_pair = reinterpret_cast<const int64_t *>(tab + b_ids + b_start);
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
+    const RowsView rows = hnsw_rows(h);
     if (hnsw_pairs_by_gather()) {
         PGV_TRY(ctx->idx_stage.ensure(sizeof(int32_t) * (size_t)npairs));
         PGV_TRY(ctx->plan_d.ensure(sizeof(int32_t) * (size_t)npairs));
         int32_t *a_dev = ctx->idx_stage.as<int32_t>(), *b_dev = ctx->plan_d.as<int32_t>();
-        PGV_TRY(launch_expand_groups(ctx, reinterpret_cast<const int32_t *>(tab),
-                                     reinterpret_cast<const int64_t *>(tab + b_ids),
-                                     reinterpret_cast<const int32_t *>(tab + b_ids + 2 * b_start),
-                                     reinterpret_cast<const int64_t *>(tab + b_ids + b_start), ngroups, a_dev, b_dev));
-        PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements, a_dev, b_dev, npairs,
-                                    od.as<float>()));
+        PGV_TRY(launch_expand_groups(ctx, g_ids, g_at, 0, nullptr, g_from, g_pair, ngroups, a_dev, b_dev));
+        PGV_TRY(launch_score_gather(ctx, rows, rows.rows, a_dev, b_dev, npairs, od.as<float>()));
     } else
-        PGV_TRY(launch_score_groups(ctx, h->metric, h->dtype, h->geom, h->elements, reinterpret_cast<const int32_t *>(tab),
-                                    reinterpret_cast<const int64_t *>(tab + b_ids), 0, nullptr,
-                                    reinterpret_cast<const int32_t *>(tab + b_ids + 2 * b_start),
-                                    reinterpret_cast<const int64_t *>(tab + b_ids + b_start), ngroups, od.as<float>()));
+        PGV_TRY(launch_score_groups(ctx, rows, g_ids, g_at, 0, nullptr, g_from, g_pair, ngroups, od.as<float>()));
     bool need = true;  // the host tables above must have been read before the caller reuses them
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -756,14 +709,14 @@ int pgv_hnsw_link_begin(pgv_hnsw *h) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin: handle is NULL");
     PGV_NO_BITS(h, "pgv_hnsw_link_begin");
     if (h->imported || h->view_of) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_begin: an imported mirror / a view is read-only");
-    if (h->m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin needs pgv_hnsw_set_graph first");
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin needs pgv_hnsw_set_graph first");
     pgv_ctx *ctx = h->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     hnsw_link_free(h);
     HnswLinkState *L = new (std::nothrow) HnswLinkState();
     if (!L) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
-    const size_t total = (size_t)(h->nbr_total > 0 ? h->nbr_total : 1);
-    L->nlists = total / (size_t)h->m + 1;  // every list starts at a multiple of m
+    const size_t total = (size_t)(h->graph.nbr_total > 0 ? h->graph.nbr_total : 1);
+    L->nlists = total / (size_t)h->graph.m + 1;  // every list starts at a multiple of m
     if (hipMalloc(&L->nb_dist, total * sizeof(float)) != hipSuccess || hipMalloc(&L->nb_flag, total) != hipSuccess ||
         hipMalloc(&L->list_count, 2 * L->nlists * sizeof(int)) != hipSuccess) {
         if (L->nb_dist) (void)hipFree(L->nb_dist);
@@ -806,8 +759,9 @@ int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *l
     if (nq == 0) return PGV_OK;
     if (!elements || !linked || !sel_ids || !sel_dist || !sel_closer || !sel_count)
         PGV_FAIL(PGV_ERR_ARG, "the new elements' lists are NULL");
-    const int m = h->m;
-    const size_t per = (size_t)nq * layer_cap, stride = 2 * (size_t)m;
+    const HnswGraph &G = h->graph;
+    const RowsView rows = hnsw_rows(h);
+    const size_t per = (size_t)nq * layer_cap, stride = 2 * (size_t)G.m;
     if (per * stride > 0x7fffffff) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_prepare: batch too large");
     // a searcher on another stream has left the tuples as the last patch / link made them
     PGV_TRY(hnsw_graph_acquire(h));
@@ -854,28 +808,27 @@ int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *l
     L->d_link_elem = L->links.as<int32_t>();
     L->d_link_dist = reinterpret_cast<float *>(L->d_link_elem + cap);
     PGV_HIP(hipMemsetAsync(L->nrec_dev, 0, sizeof(int), ctx->stream));
-    PGV_TRY(launch_hnsw_link_group(ctx, 0, L->d_elems, L->d_linked, nq, layer_cap, m, L->d_sel_ids, L->d_sel_dist, L->d_sel_cnt,
-                                   h->levels, h->nbr_start, L->list_count, L->list_rec, L->nrec_dev, L->rec_owner, L->rec_lc,
-                                   L->rec_list, nullptr, nullptr, nullptr, nullptr));
+    PGV_TRY(launch_hnsw_link_group(ctx, 0, G, L->d_elems, L->d_linked, nq, layer_cap, L->d_sel_ids, L->d_sel_dist, L->d_sel_cnt,
+                                   L->list_count, L->list_rec, L->nrec_dev, L->rec_owner, L->rec_lc, L->rec_list, nullptr,
+                                   nullptr, nullptr, nullptr));
     int nrec = 0;
     PGV_HIP(hipMemcpyAsync(&nrec, L->nrec_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PGV_HIP(hipStreamSynchronize(ctx->stream));  // (also: the caller's arrays have been read)
     if (nrec < 0 || (size_t)nrec > cap) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_prepare: %d records", nrec);
     L->nrec = nrec;
     if (nrec == 0) return PGV_OK;
-    PGV_TRY(launch_hnsw_link_size(ctx, h->nbr, L->nb_flag, h->levels, h->nbr_start, m, L->rec_owner, L->rec_lc, L->rec_list,
-                                  L->list_count, L->rec_off, nrec, 0, L->rec_pos, L->rec_nstart, L->rec_from, nullptr,
-                                  L->ids_start, L->pair_start));
+    PGV_TRY(launch_hnsw_link_size(ctx, G, L->nb_flag, L->rec_owner, L->rec_lc, L->rec_list, L->list_count, L->rec_off, nrec, 0,
+                                  L->rec_pos, L->rec_nstart, L->rec_from, nullptr, L->ids_start, L->pair_start));
     PGV_TRY(launch_hnsw_link_scan(ctx, L->rec_off, L->ids_start, L->pair_start, nrec, L->totals));
     PGV_HIP(hipMemsetAsync(L->rec_fill, 0, sizeof(int) * (size_t)nrec, ctx->stream));
-    PGV_TRY(launch_hnsw_link_group(ctx, 1, L->d_elems, L->d_linked, nq, layer_cap, m, L->d_sel_ids, L->d_sel_dist, L->d_sel_cnt,
-                                   h->levels, h->nbr_start, L->list_count, L->list_rec, L->nrec_dev, L->rec_owner, L->rec_lc,
-                                   L->rec_list, L->rec_off, L->rec_fill, L->d_link_elem, L->d_link_dist));
+    PGV_TRY(launch_hnsw_link_group(ctx, 1, G, L->d_elems, L->d_linked, nq, layer_cap, L->d_sel_ids, L->d_sel_dist, L->d_sel_cnt,
+                                   L->list_count, L->list_rec, L->nrec_dev, L->rec_owner, L->rec_lc, L->rec_list, L->rec_off,
+                                   L->rec_fill, L->d_link_elem, L->d_link_dist));
     int64_t totals[3] = {0, 0, 0};
     PGV_HIP(hipMemcpyAsync(totals, L->totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t nlinks = totals[0], nids = totals[1], npairs = totals[2];
-    const int64_t lm0 = 2 * (int64_t)m;
+    const int64_t lm0 = 2 * (int64_t)G.m;
     if (nlinks < nrec || (size_t)nlinks > cap || nids < nlinks || nids > nlinks + (int64_t)nrec * lm0 || npairs < 0)
         PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_prepare: %lld links / %lld ids / %lld pairs planned for %d records",
                  (long long)nlinks, (long long)nids, (long long)npairs, nrec);
@@ -887,16 +840,15 @@ int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *l
         PGV_TRY(L->pb.ensure(sizeof(int32_t) * (size_t)(npairs > 0 ? npairs : 1)));
     }
     // the id lists (and, for the gathered form, the slot pairs)
-    PGV_TRY(launch_hnsw_link_pairs(ctx, h->nbr, L->rec_pos, L->rec_nstart, L->rec_from, L->rec_off, L->d_link_elem, L->d_link_dist,
+    PGV_TRY(launch_hnsw_link_pairs(ctx, G.nbr, L->rec_pos, L->rec_nstart, L->rec_from, L->rec_off, L->d_link_elem, L->d_link_dist,
                                    L->rec_list, L->list_count, nrec, 0, L->ids_start, L->ids.as<int32_t>(), L->pair_start,
                                    gather ? L->pa.as<int32_t>() : nullptr, gather ? L->pb.as<int32_t>() : nullptr));
     if (npairs > 0) {
         if (gather)
-            PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements, L->pa.as<int32_t>(),
-                                        L->pb.as<int32_t>(), npairs, L->tri.as<float>()));
+            PGV_TRY(launch_score_gather(ctx, rows, rows.rows, L->pa.as<int32_t>(), L->pb.as<int32_t>(), npairs, L->tri.as<float>()));
         else
-            PGV_TRY(launch_score_groups(ctx, h->metric, h->dtype, h->geom, h->elements, L->ids.as<int32_t>(), L->ids_start, 0,
-                                        nullptr, L->rec_from, L->pair_start, nrec, L->tri.as<float>()));
+            PGV_TRY(launch_score_groups(ctx, rows, L->ids.as<int32_t>(), L->ids_start, 0, nullptr, L->rec_from, L->pair_start, nrec,
+                                        L->tri.as<float>()));
     }
     L->npairs = npairs;
     if (out_pairs) *out_pairs = npairs;
@@ -911,11 +863,13 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
     pgv_ctx *ctx = h->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     L->prepared = false;
-    const int nrec = L->nrec, m = h->m;
+    const HnswGraph &G = h->graph;
+    const RowsView rows = hnsw_rows(h);
+    const int nrec = L->nrec, m = G.m;
     if (nrec > 0) {
         PGV_TRY(L->loc.ensure(sizeof(int16_t) * (size_t)nrec * (2 * (size_t)m + 1)));
         PGV_HIP(hipMemsetAsync(L->blocked, 0, 2 * sizeof(int), ctx->stream));  // [0] stopped in the first round, [1] in the second
-        PGV_TRY(launch_hnsw_link_replay(ctx, h->nbr, L->nb_dist, L->nb_flag, m, nrec, 0, L->rec_lc, L->rec_off, L->d_link_dist,
+        PGV_TRY(launch_hnsw_link_replay(ctx, G, L->nb_dist, L->nb_flag, nrec, 0, L->rec_lc, L->rec_off, L->d_link_dist,
                                         L->rec_pos, L->rec_nstart, L->rec_from, L->ids_start, L->ids.as<int32_t>(), L->pair_start,
                                         L->tri.as<float>(), nullptr, nullptr, L->rec_wait, L->loc.as<int16_t>(), L->blocked));
         // The replays that stepped outside the pairs fetched for them: their lists' member-member triangles, then the rest
@@ -925,14 +879,13 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
         // moment the last one is through (hnsw_graph_acquire on their stream).
         const size_t lm0 = 2 * (size_t)m, mm_bound = (size_t)nrec * (lm0 * (lm0 - 1) / 2);
         const bool async = !hnsw_pairs_by_gather() && mm_bound * sizeof(float) <= ((size_t)512 << 20);
-        PGV_TRY(launch_hnsw_link_size(ctx, h->nbr, L->nb_flag, h->levels, h->nbr_start, m, L->rec_owner, L->rec_lc, L->rec_list,
-                                      L->list_count, L->rec_off, nrec, 1, L->rec_pos, L->rec_nstart, L->rec_from, L->rec_wait,
-                                      nullptr, L->mm_start));
+        PGV_TRY(launch_hnsw_link_size(ctx, G, L->nb_flag, L->rec_owner, L->rec_lc, L->rec_list, L->list_count, L->rec_off, nrec, 1,
+                                      L->rec_pos, L->rec_nstart, L->rec_from, L->rec_wait, nullptr, L->mm_start));
         PGV_TRY(launch_hnsw_link_scan(ctx, L->mm_start, nullptr, nullptr, nrec, L->totals));
         if (async) {
             PGV_TRY(L->mm.ensure(sizeof(float) * (mm_bound > 0 ? mm_bound : 1)));
-            PGV_TRY(launch_score_groups(ctx, h->metric, h->dtype, h->geom, h->elements, L->ids.as<int32_t>(), L->ids_start, 0,
-                                        L->rec_nstart, nullptr, L->mm_start, nrec, L->mm.as<float>()));
+            PGV_TRY(launch_score_groups(ctx, rows, L->ids.as<int32_t>(), L->ids_start, 0, L->rec_nstart, nullptr, L->mm_start, nrec,
+                                        L->mm.as<float>()));
         } else {
             int64_t npairs2 = 0;
             PGV_HIP(hipMemcpyAsync(&npairs2, L->totals, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -943,16 +896,16 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
             if (npairs2 > 0 && hnsw_pairs_by_gather()) {
                 PGV_TRY(L->pa.ensure(sizeof(int32_t) * (size_t)npairs2));
                 PGV_TRY(L->pb.ensure(sizeof(int32_t) * (size_t)npairs2));
-                PGV_TRY(launch_hnsw_link_pairs(ctx, h->nbr, L->rec_pos, L->rec_nstart, L->rec_from, L->rec_off, L->d_link_elem,
+                PGV_TRY(launch_hnsw_link_pairs(ctx, G.nbr, L->rec_pos, L->rec_nstart, L->rec_from, L->rec_off, L->d_link_elem,
                                                L->d_link_dist, L->rec_list, L->list_count, nrec, 1, L->ids_start,
                                                L->ids.as<int32_t>(), L->mm_start, L->pa.as<int32_t>(), L->pb.as<int32_t>()));
-                PGV_TRY(launch_score_gather(ctx, h->metric, h->dtype, h->geom, h->elements, h->elements, L->pa.as<int32_t>(),
-                                            L->pb.as<int32_t>(), npairs2, L->mm.as<float>()));
+                PGV_TRY(launch_score_gather(ctx, rows, rows.rows, L->pa.as<int32_t>(), L->pb.as<int32_t>(), npairs2,
+                                            L->mm.as<float>()));
             } else if (npairs2 > 0)
-                PGV_TRY(launch_score_groups(ctx, h->metric, h->dtype, h->geom, h->elements, L->ids.as<int32_t>(), L->ids_start, 0,
-                                            L->rec_nstart, nullptr, L->mm_start, nrec, L->mm.as<float>()));
+                PGV_TRY(launch_score_groups(ctx, rows, L->ids.as<int32_t>(), L->ids_start, 0, L->rec_nstart, nullptr, L->mm_start,
+                                            nrec, L->mm.as<float>()));
         }
-        PGV_TRY(launch_hnsw_link_replay(ctx, h->nbr, L->nb_dist, L->nb_flag, m, nrec, 1, L->rec_lc, L->rec_off, L->d_link_dist,
+        PGV_TRY(launch_hnsw_link_replay(ctx, G, L->nb_dist, L->nb_flag, nrec, 1, L->rec_lc, L->rec_off, L->d_link_dist,
                                         L->rec_pos, L->rec_nstart, L->rec_from, L->ids_start, L->ids.as<int32_t>(), L->pair_start,
                                         L->tri.as<float>(), L->mm_start, L->mm.as<float>(), L->rec_wait, L->loc.as<int16_t>(),
                                         L->blocked + 1));
@@ -962,9 +915,9 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
     }
     // the batch's own elements (their lists were selected with their searches)
     if (L->nq > 0)
-        PGV_TRY(launch_hnsw_link_new(ctx, h->nbr, L->nb_dist, L->nb_flag, h->levels, h->nbr_start, m, L->d_elems, L->d_linked,
-                                     L->nq, L->lcap, L->d_sel_ids, L->d_sel_dist, L->d_sel_closer, L->d_sel_cnt));
-    h->entry = entry;
+        PGV_TRY(launch_hnsw_link_new(ctx, G, L->nb_dist, L->nb_flag, L->d_elems, L->d_linked, L->nq, L->lcap, L->d_sel_ids,
+                                     L->d_sel_dist, L->d_sel_closer, L->d_sel_cnt));
+    h->graph.entry = entry;
     // searches on other streams (the helper's view) wait for this on the device
     if (!h->graph_ev) PGV_HIP(hipEventCreateWithFlags(&h->graph_ev, hipEventDisableTiming));
     PGV_HIP(hipEventRecord(h->graph_ev, ctx->stream));
@@ -981,8 +934,8 @@ int pgv_hnsw_link_end(pgv_hnsw *h, int32_t *out_nbr, int64_t *out_pairs, int64_t
     pgv_ctx *ctx = h->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     PGV_TRY(hnsw_graph_acquire(h));
-    if (out_nbr && h->nbr_total > 0)
-        PGV_HIP(hipMemcpyAsync(out_nbr, h->nbr, sizeof(int32_t) * (size_t)h->nbr_total, hipMemcpyDefault, ctx->stream));
+    if (out_nbr && h->graph.nbr_total > 0)
+        PGV_HIP(hipMemcpyAsync(out_nbr, h->graph.nbr, sizeof(int32_t) * (size_t)h->graph.nbr_total, hipMemcpyDefault, ctx->stream));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
     const int64_t deferred = h->link->stats_host[0], pairs2 = h->link->stats_host[1], still = h->link->stats_host[2];
     hnsw_link_free(h);
@@ -1000,13 +953,13 @@ int pgv_hnsw_update_graph(pgv_hnsw *h, int32_t entry, const int32_t *elements, i
     // through a view (pgv_hnsw_share) the patch lands in the owner's arrays, on the view's stream
     pgv_hnsw *o = h->view_of ? h->view_of : h;
     if (o->imported) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_update_graph: an imported mirror is read-only");
-    if (h->m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_update_graph needs pgv_hnsw_set_graph first");
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_update_graph needs pgv_hnsw_set_graph first");
     if (entry < -1 || entry >= h->n) PGV_FAIL(PGV_ERR_ARG, "entry point %d out of range", (int)entry);
     if (nupd < 0 || (nupd > 0 && (!elements || !tuple_offsets || !tuples))) PGV_FAIL(PGV_ERR_ARG, "bad update");
     pgv_ctx *ctx = h->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
-    h->entry = entry;
-    o->entry = entry;
+    h->graph.entry = entry;
+    o->graph.entry = entry;
     if (nupd == 0) return PGV_OK;
     if (is_device_ptr(tuple_offsets)) PGV_FAIL(PGV_ERR_ARG, "tuple_offsets must be host memory");
     const int64_t total = tuple_offsets[nupd];
@@ -1019,7 +972,7 @@ int pgv_hnsw_update_graph(pgv_hnsw *h, int32_t entry, const int32_t *elements, i
     PGV_TRY(stage_flat(ctx, elements, sizeof(int32_t) * (size_t)nupd, ctx->idx_stage, &id_dev));
     PGV_TRY(stage_flat(ctx, tuples, sizeof(int32_t) * (size_t)(total > 0 ? total : 1), ctx->plan_d, &tp_dev));
     PGV_TRY(stage_flat(ctx, tuple_offsets, sizeof(int64_t) * (size_t)(nupd + 1), ctx->plan_c, &of_dev));
-    PGV_TRY(launch_hnsw_patch(ctx, h->nbr, h->nbr_start, h->n, static_cast<const int32_t *>(id_dev),
+    PGV_TRY(launch_hnsw_patch(ctx, h->graph, h->n, static_cast<const int32_t *>(id_dev),
                               static_cast<const int64_t *>(of_dev), static_cast<const int32_t *>(tp_dev), nupd));
     // later launches on this stream see the patched graph; searches on other streams (the owner's, other views') wait
     // for this event on the device.  The caller keeps searches that READ the old tuples away from the patch: they have

@@ -5,6 +5,7 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pgv_internal.h"
 
@@ -27,6 +28,25 @@ struct BitRow {};
 template <> struct VecTraits<BitRow> {
     static constexpr int N = 128;
 };
+
+// ---- host side: runtime (metric, element type) -> the <T, METRIC> a launcher instantiates -------------------------
+// f((T *)nullptr, std::integral_constant<int, METRIC>()): METRIC 0 L2 squared, 1 negative inner product, 2 L1
+template <typename F> int dispatch_metric(pgv_metric metric, pgv_dtype dtype, F f) {
+    auto by_metric = [&](auto *tp) -> int {
+        switch (metric) {
+            case PGV_L2SQ: return f(tp, std::integral_constant<int, 0>());
+            case PGV_NEG_IP: return f(tp, std::integral_constant<int, 1>());
+            case PGV_L1: return f(tp, std::integral_constant<int, 2>());
+        }
+        PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)metric);
+    };
+    return dtype == PGV_F32 ? by_metric((float *)nullptr) : by_metric((__half *)nullptr);
+}
+// ... for the launchers that serve bit rows as well: <BitRow, 0> (the metric slot is unused)
+template <typename F> int dispatch_rows(const RowsView &v, F f) {
+    if (!v.bits()) return dispatch_metric(v.metric, v.dtype(), f);
+    return f((BitRow *)nullptr, std::integral_constant<int, 0>());
+}
 
 struct alignas(16) Raw16 {
     uint32_t w[4];

@@ -83,6 +83,33 @@ RowGeom row_geom(int dim, pgv_dtype t);
 // mirror (pgv_hnsw::nbits); ld is the padded row length in BYTES
 RowGeom bit_row_geom(int nbits);
 
+// Rows as the scoring kernels and the HNSW walk take them: where they are, how many, how a row is laid out, what an
+// element is and which distance goes with it.  Built where it is needed (hnsw_rows for a mirror), never stored
+enum class RowKind { F32, F16, Bits };  // Bits: packed bit strings scored by xor + popcount; the metric is unused
+struct RowsView {
+    const void *rows;  // [n x geom.nvec] 16-byte vectors
+    int64_t n;
+    RowGeom geom;
+    RowKind kind;
+    pgv_metric metric;
+    bool bits() const { return kind == RowKind::Bits; }
+    pgv_dtype dtype() const { return kind == RowKind::F16 ? PGV_F16 : PGV_F32; }
+};
+inline RowKind row_kind(pgv_dtype t) { return t == PGV_F16 ? RowKind::F16 : RowKind::F32; }
+
+// The graph of an HNSW mirror (pgv_hnsw_set_graph): ONE allocation holding levels | nbr_start | nbr, so that one
+// hipIpcMemHandle carries it; a view (pgv_hnsw_share) copies the whole struct from its owner
+struct HnswGraph {
+    void *mem = nullptr;
+    size_t bytes = 0;
+    const int32_t *levels = nullptr;     // [n]
+    const int64_t *nbr_start = nullptr;  // [n + 1]
+    int32_t *nbr = nullptr;              // [nbr_total] neighbour tuples, HnswNeighborTupleData layout
+    int64_t nbr_total = 0;
+    int m = 0;
+    int32_t entry = -1;
+};
+
 // one unit of streaming work: rows [row0, row0 + nrows) scored against
 // pairs [pair0, pair0 + npairs)
 struct ScanTask {
@@ -221,8 +248,8 @@ struct pgv_query {
     unsigned seq = 0;
 };
 
-struct pgv_hnsw {
-    pgv_ctx *ctx = nullptr;
+// the element rows of a mirror: what a view (pgv_hnsw_share) has in common with its owner, copied as one struct
+struct HnswElements {
     pgv_metric metric = PGV_L2SQ;
     pgv_dtype dtype = PGV_F32;
     int dim = 0;
@@ -232,26 +259,29 @@ struct pgv_hnsw {
     int64_t n = 0;
     pgv::RowGeom geom{};
     void *elements = nullptr;  // [n x ld]
-    // the graph (pgv_hnsw_set_graph): one allocation holding levels | nbr_start | nbr
-    void *graph = nullptr;
-    const int32_t *levels = nullptr;
-    const int64_t *nbr_start = nullptr;
-    int32_t *nbr = nullptr;
-    int m = 0;
-    int32_t entry = -1;
+    char *payload = nullptr;  // [n x payload_bytes] behind the elements, same allocation (pgv_hnsw_upload_payload)
+    int payload_bytes = 0;
+};
+
+struct pgv_hnsw : HnswElements {
+    pgv_ctx *ctx = nullptr;
+    pgv::HnswGraph graph;
     pgv::DBuf bitmaps;  // visited sets of the search workgroups
-    size_t graph_bytes = 0;
-    int64_t nbr_total = 0;
     bool imported = false;  // elements / graph were opened with hipIpcOpenMemHandle (a read-only view)
     pgv_hnsw *view_of = nullptr;  // pgv_hnsw_share: a view of that mirror in the same process (own context / stream)
     // the last pgv_hnsw_update_graph of the mirror (through it or through a view), recorded on the stream that ran it:
     // searches on any other stream wait for it on the device (owner's field; views look at view_of's)
     hipEvent_t graph_ev = nullptr;
     bool graph_ev_set = false;
-    char *payload = nullptr;  // [n x payload_bytes] behind the elements, same allocation (pgv_hnsw_upload_payload)
-    int payload_bytes = 0;
     struct HnswLinkState *link = nullptr;  // pgv_hnsw_link_begin .. _end: the in-memory build's graph state (owner only)
 };
+
+namespace pgv {
+// a mirror's rows as its kernels take them
+inline RowsView hnsw_rows(const pgv_hnsw *h) {
+    return {h->elements, h->n, h->geom, h->nbits > 0 ? RowKind::Bits : row_kind(h->dtype), h->metric};
+}
+}  // namespace pgv
 
 // the state of a build whose graph updates run on the device (kernels_hnsw_link.hip): per tuple slot the neighbor's
 // distance and closer flag, and the scratch of the batch in flight
@@ -424,20 +454,17 @@ int launch_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom 
                 float *out);
 int scan_group_size(const RowGeom &g, pgv_dtype dtype, int wanted);
 // gathered variant (HNSW candidate scoring): pair i = (slot[i], query_of[i])
-int launch_expand_groups(pgv_ctx *ctx, const int32_t *ids, const int64_t *ids_start, const int32_t *from,
-                         const int64_t *pair_start, int ngroups, int32_t *a, int32_t *b);
-int launch_score_gather(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-                        const void *rows, const void *queries, const int32_t *slot,
-                        const int32_t *query_of, int64_t npairs, float *out);
-// ... over packed bit rows (g: bit_row_geom): the Hamming distance of each pair, exact
-int launch_score_gather_bits(pgv_ctx *ctx, const RowGeom &g, const void *rows, const void *queries, const int32_t *slot,
-                             const int32_t *query_of, int64_t npairs, float *out);
-// the pairs (u, v < u), u >= from, inside groups of rows, in 4 x 4 tiles (bit for bit score_gather's values).  Group g is
-// ids[ids_at[g] ..) (ids_at NULL: g * ids_stride), n_arr[g] rows (NULL: ids_at[g + 1] - ids_at[g]), from_arr[g] (NULL: 1);
-// its pairs go to out[pair_at[g] ..); pair_at[g + 1] == pair_at[g]: nothing wanted
-int launch_score_groups(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,
-                        const int32_t *ids, const int64_t *ids_at, int64_t ids_stride, const int32_t *n_arr,
-                        const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out);
+int launch_score_gather(pgv_ctx *ctx, const RowsView &v, const void *queries, const int32_t *slot, const int32_t *query_of,
+                        int64_t npairs, float *out);
+// the pairs (u, v < u), u >= from, inside groups of rows, in 4 x 4 tiles (bit for bit score_gather's values; fp32 / fp16
+// rows only).  Group g is ids[ids_at[g] ..) (ids_at NULL: g * ids_stride), n_arr[g] rows (NULL: ids_at[g + 1] - ids_at[g]),
+// from_arr[g] (NULL: 1); its pairs go to out[pair_at[g] ..), u ascending then v; pair_at[g + 1] == pair_at[g]: nothing wanted
+int launch_score_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride,
+                        const int32_t *n_arr, const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out);
+// kernels_hnsw.hip: the same groups' pairs written out as the (slot, query_of) arrays of launch_score_gather, in the
+// order launch_score_groups writes their values: a[] = slot of u, b[] = slot of v
+int launch_expand_groups(pgv_ctx *ctx, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride, const int32_t *n_arr,
+                         const int32_t *from_arr, const int64_t *pair_at, int ngroups, int32_t *a, int32_t *b);
 
 // kernels_misc.hip: operator-path cosine distance and bit-vector distances, one query x n rows
 int launch_cosine(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void *rows, const void *query, int64_t n,
@@ -474,15 +501,10 @@ struct HnswSearchArgs {
     int32_t *lw_cnt = nullptr;
     int lcap = 0;
 };
-int launch_hnsw_search(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &geom, const void *rows,
-                       int64_t n, const int32_t *levels, const int64_t *nbr_start, const int32_t *nbr, int m,
-                       int32_t entry, const HnswSearchArgs &a, uint32_t *bitmaps, int words, int grid, int *counter);
-// ... over packed bit rows (geom: bit_row_geom; queries in the same layout): the same walk, Hamming distances
-int launch_hnsw_search_bits(pgv_ctx *ctx, const RowGeom &geom, const void *rows, int64_t n, const int32_t *levels,
-                            const int64_t *nbr_start, const int32_t *nbr, int m, int32_t entry, const HnswSearchArgs &a,
-                            uint32_t *bitmaps, int words, int grid, int *counter);
-int launch_hnsw_patch(pgv_ctx *ctx, int32_t *nbr, const int64_t *nbr_start, int64_t n, const int32_t *ids,
-                      const int64_t *packed_off, const int32_t *packed, int nupd);
+int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const HnswSearchArgs &a, uint32_t *bitmaps,
+                       int words, int grid, int *counter);
+int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int32_t *ids, const int64_t *packed_off,
+                      const int32_t *packed, int nupd);
 
 // kernels_tile.hip: row tiles in LDS (async DMA), queries in registers: 16 queries per pass
 bool tile_scan_supported(const RowGeom &g);
@@ -504,38 +526,35 @@ int launch_argmin_mode(pgv_ctx *ctx, int mode, pgv_dtype dtype, const RowGeom &g
 int launch_argmin_listed(pgv_ctx *ctx, int mode, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n,
                          const void *centers, int k, const int32_t *row_list, const int *row_count,
                          unsigned long long *packed);
-// kernels_hnsw.hip: SelectNeighbors of a batch's new elements on the device (plan -> pairs -> [score_gather] -> sweep)
+// kernels_hnsw.hip: SelectNeighbors of a batch's new elements on the device (plan -> score_groups, or expand_groups +
+// score_gather -> sweep)
 int launch_hnsw_select_plan(pgv_ctx *ctx, const int32_t *cnt, int ngroups, int lcap, int m, int64_t *pair_start);
-int launch_hnsw_select_pairs(pgv_ctx *ctx, const int32_t *lw_ids, const int32_t *cnt, const int64_t *pair_start, int ngroups,
-                             int ef, int32_t *a, int32_t *b);
 int launch_hnsw_select(pgv_ctx *ctx, const int32_t *lw_ids, const float *lw_dist, const int32_t *cnt, const int32_t *qlevels,
                        const int64_t *pair_start, const float *tri, int ngroups, int lcap, int ef, int m, int stride,
                        int32_t *out_ids, float *out_dist, uint8_t *out_closer, int32_t *out_cnt);
 // kernels_hnsw_link.hip: a batch linked into the neighbor lists it chose, on the device
-int launch_hnsw_link_group(pgv_ctx *ctx, int step, const int32_t *elems, const uint8_t *linked, int nq, int lcap, int m,
-                           const int32_t *sel_ids, const float *sel_dist, const int32_t *sel_cnt, const int32_t *levels,
-                           const int64_t *nbr_start, int *list_count, int *list_rec, int *nrec, int32_t *rec_owner,
-                           int32_t *rec_lc, int32_t *rec_list, const int64_t *rec_off, int *rec_fill, int32_t *link_elem,
-                           float *link_dist);
-int launch_hnsw_link_size(pgv_ctx *ctx, const int32_t *nbr, const uint8_t *nb_flag, const int32_t *levels,
-                          const int64_t *nbr_start, int m, const int32_t *rec_owner, const int32_t *rec_lc,
-                          const int32_t *rec_list, const int *list_count, int64_t *rec_off, int nrec, int pass, int64_t *rec_pos,
-                          int32_t *rec_nstart, int32_t *rec_from, const int32_t *rec_wait, int64_t *size_ids,
-                          int64_t *size_pairs);
+int launch_hnsw_link_group(pgv_ctx *ctx, int step, const HnswGraph &graph, const int32_t *elems, const uint8_t *linked, int nq,
+                           int lcap, const int32_t *sel_ids, const float *sel_dist, const int32_t *sel_cnt, int *list_count,
+                           int *list_rec, int *nrec, int32_t *rec_owner, int32_t *rec_lc, int32_t *rec_list,
+                           const int64_t *rec_off, int *rec_fill, int32_t *link_elem, float *link_dist);
+int launch_hnsw_link_size(pgv_ctx *ctx, const HnswGraph &graph, const uint8_t *nb_flag, const int32_t *rec_owner,
+                          const int32_t *rec_lc, const int32_t *rec_list, const int *list_count, int64_t *rec_off, int nrec,
+                          int pass, int64_t *rec_pos, int32_t *rec_nstart, int32_t *rec_from, const int32_t *rec_wait,
+                          int64_t *size_ids, int64_t *size_pairs);
 int launch_hnsw_link_scan(pgv_ctx *ctx, int64_t *a, int64_t *b, int64_t *c, int n, int64_t *totals);
 int launch_hnsw_link_stats(pgv_ctx *ctx, const int *blocked, const int64_t *totals, int64_t *stats);
 int launch_hnsw_link_pairs(pgv_ctx *ctx, const int32_t *nbr, const int64_t *rec_pos, const int32_t *rec_nstart,
                            const int32_t *rec_from, const int64_t *rec_off, int32_t *link_elem, float *link_dist,
                            const int32_t *rec_list, int *list_count, int nrec, int pass,
                            const int64_t *ids_start, int32_t *ids, const int64_t *pair_start, int32_t *a, int32_t *b);
-int launch_hnsw_link_replay(pgv_ctx *ctx, int32_t *nbr, float *nb_dist, uint8_t *nb_flag, int m, int nrec, int pass,
+int launch_hnsw_link_replay(pgv_ctx *ctx, const HnswGraph &graph, float *nb_dist, uint8_t *nb_flag, int nrec, int pass,
                             const int32_t *rec_lc, const int64_t *rec_off, const float *link_dist, const int64_t *rec_pos,
                             const int32_t *rec_nstart, const int32_t *rec_from, const int64_t *ids_start, const int32_t *ids,
                             const int64_t *pair_start, const float *tri, const int64_t *mm_start, const float *mm,
                             int32_t *rec_wait, int16_t *loc_save, int *blocked);
-int launch_hnsw_link_new(pgv_ctx *ctx, int32_t *nbr, float *nb_dist, uint8_t *nb_flag, const int32_t *levels,
-                         const int64_t *nbr_start, int m, const int32_t *elems, const uint8_t *linked, int nq, int lcap,
-                         const int32_t *sel_ids, const float *sel_dist, const uint8_t *sel_closer, const int32_t *sel_cnt);
+int launch_hnsw_link_new(pgv_ctx *ctx, const HnswGraph &graph, float *nb_dist, uint8_t *nb_flag, const int32_t *elems,
+                         const uint8_t *linked, int nq, int lcap, const int32_t *sel_ids, const float *sel_dist,
+                         const uint8_t *sel_closer, const int32_t *sel_cnt);
 // kernels_mfma.hip: the same on the matrix cores (ip / spherical directly, L2 as pre-filter + exact recheck)
 bool mfma_argmin_supported(int mode, int64_t n, int k);
 int launch_argmin_mfma(pgv_ctx *ctx, int mode, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n,

@@ -7,6 +7,8 @@ PGV_HNSW_PAIRS_GATHER / PGV_HNSW_SELECT_SERIAL (each read once per process).
       scenarios also the tuples and counts after every batch (each prefix of the batches run on its own: only
       pgv_hnsw_link_end reads the state back, and it ends the build).  Prints 'LINK-OK <scenarios>'.
   mp_hnsw_link_worker.py select                         select_cases() below.  Prints 'SELECT-OK <lists thinned>'.
+  mp_hnsw_link_worker.py groups OUT.npz                 groups_on_device() below: pgv_hnsw_score_groups' and
+      pgv_hnsw_score_pairs' values of every groups_cases() case go into OUT.npz.  Prints 'GROUPS-OK <cases>'.
 
 The parent compares; nothing here looks at the model's results."""
 import ctypes as C
@@ -28,6 +30,7 @@ api.lib.pgv_hnsw_link_begin.argtypes = [P]
 api.lib.pgv_hnsw_link_prepare.argtypes = [P, P, P, I, I, P, P, P, P, C.POINTER(I64)]
 api.lib.pgv_hnsw_link_apply.argtypes = [P, C.c_int32]
 api.lib.pgv_hnsw_link_end.argtypes = [P, P, C.POINTER(I64), C.POINTER(I64)]
+api.lib.pgv_hnsw_score_groups.argtypes = [P, P, P, P, P, I, I64, I64, P]
 
 
 def link_on_device(ctx, sc, nbatches=None):
@@ -165,9 +168,70 @@ def select_cases(ctx):
     return thinned_of
 
 
+# ------------------------------------------------------------------ pair distances inside groups of rows
+GROUP_SIZES = (1, 2, 5, 64, 65, 257, 300)    # across the expand loop's 64 lanes and 256 threads, score_groups' 4 x 4 tiles
+GROUP_ROWS = 320
+GROUP_CASES = [(metric, dtype) for metric in (api.PGV_L2SQ, api.PGV_NEG_IP, api.PGV_L1) for dtype in (api.PGV_F32, api.PGV_F16)]
+
+
+def groups_input():
+    """One call's groups: every size of GROUP_SIZES with from = 0, 1, 3, n - 1 and n (n: no pairs wanted), ids drawn from
+    320 rows with repeats inside a group.  -> ids, ids_start, from, pair_start and the slot pairs (a, b) the call asks for:
+    per group (u, v < u) for u >= max(from, 1), u ascending then v."""
+    rng = np.random.default_rng(1605)
+    ids, frm, a, b = [], [], [], []
+    for n in GROUP_SIZES:
+        for f in (0, 1, 3, n - 1, n):
+            gi = rng.integers(0, GROUP_ROWS, n).astype(np.int32)
+            gi[-1] = gi[0]                    # (a repeated id whatever the draw; a group of one is its own repeat)
+            u, v = np.tril_indices(n, -1)     # row-major: u ascending then v
+            keep = u >= max(f, 1)
+            ids.append(gi)
+            frm.append(f)
+            a.append(gi[u[keep]])
+            b.append(gi[v[keep]])
+    ids_start = np.concatenate([[0], np.cumsum([len(g) for g in ids])]).astype(np.int64)
+    pair_start = np.concatenate([[0], np.cumsum([len(x) for x in a])]).astype(np.int64)
+    return (np.concatenate(ids), ids_start, np.asarray(frm, np.int32), pair_start, np.concatenate(a).astype(np.int32),
+            np.concatenate(b).astype(np.int32))
+
+
+def groups_rows(dtype):
+    """320 rows on an integer grid in [-6, 6]: 4-d fp32, 5-d fp16 (both padded to a 16-byte vector and past one)"""
+    rng = np.random.default_rng(1606)
+    dim = 4 if dtype == api.PGV_F32 else 5
+    return rng.integers(-6, 7, (GROUP_ROWS, dim)).astype(np.float32 if dtype == api.PGV_F32 else np.float16)
+
+
+def groups_on_device(ctx):
+    """-> {"groups/<metric>/<dtype>": pgv_hnsw_score_groups' values, "pairs/<metric>/<dtype>": pgv_hnsw_score_pairs' over
+    the same pairs} for every case"""
+    ids, ids_start, frm, pair_start, a, b = groups_input()
+    res = {}
+    for metric, dtype in GROUP_CASES:
+        rows = groups_rows(dtype)
+        mirror = api.Hnsw(ctx, metric, dtype, rows.shape[1], rows)
+        try:
+            got = np.full(len(a), np.nan, np.float32)
+            api.check(api.lib.pgv_hnsw_score_groups(mirror.h, api.ptr(ids), api.ptr(ids_start), api.ptr(frm), api.ptr(pair_start),
+                                                    len(frm), len(ids), len(a), api.ptr(got)))
+            want = np.full(len(a), np.nan, np.float32)
+            api.check(api.lib.pgv_hnsw_score_pairs(mirror.h, api.ptr(a), api.ptr(b), len(a), api.ptr(want)))
+        finally:
+            mirror.close()
+        res["groups/%d/%d" % (metric, dtype)], res["pairs/%d/%d" % (metric, dtype)] = got, want
+    return res
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "link":
         run_link(sys.argv[2], sys.argv[3:])
+    elif sys.argv[1] == "groups":
+        c = api.Context(0)
+        r = groups_on_device(c)
+        c.close()
+        np.savez(sys.argv[2], **r)
+        print("GROUPS-OK %d" % len(GROUP_CASES))
     else:
         c = api.Context(0)
         t = select_cases(c)

@@ -140,3 +140,12 @@ def test_select_neighbors_at_the_ef_64_switch_serial_form():
                        text=True, timeout=CHILD_SECONDS, env=dict(os.environ, PGV_HNSW_SELECT_SERIAL="1"))
     print(r.stdout)
     assert r.returncode == 0 and "SELECT-OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+
+
+def test_select_neighbors_at_the_ef_64_switch_gathered_pairs():
+    """the same in a child with PGV_HNSW_PAIRS_GATHER=1: the lists' pair triangles by expand_groups_kernel (the candidate
+    lists described as g * ef ids, cnt[g] of them) and score_gather_kernel"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mp_hnsw_link_worker.py"), "select"], capture_output=True,
+                       text=True, timeout=CHILD_SECONDS, env=dict(os.environ, PGV_HNSW_PAIRS_GATHER="1"))
+    print(r.stdout)
+    assert r.returncode == 0 and "SELECT-OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
