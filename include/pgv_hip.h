@@ -620,6 +620,66 @@ int			pgv_binary_quantize(pgv_ctx * ctx, pgv_dtype dtype, int dim, const void *r
 int			pgv_rerank(pgv_ctx * ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *queries, int nq,
 					   const void *rows, int64_t n, const int64_t *cand, int kc, int k, float *out_dist, int64_t *out_idx);
 
+/* ----------------------------------- IVFFlat over bit strings (bit_hamming_ops) */
+
+/*
+ * Device mirror of `USING ivfflat (col bit_hamming_ops)` (sql/vector.sql:894-899, ivfflat_bit_support and its type info
+ * in src/ivfutils.c:295-299, 325-339, 363-370, 411-424): centers [nlists x bytes], rows [n x bytes], bytes =
+ * (nbits + 7) / 8, VARBITS payloads exactly as pgv_bit_topk / pgv_hnsw_upload_bits take them (first bit = top bit of
+ * byte 0, pad bits zero, bytes counted whole); list_offsets / tids as pgv_index_upload.  1 <= nbits <= 64 000
+ * (IVFFLAT_MAX_DIM * 32, src/ivfutils.c:416) else PGV_ERR_DIMS; 1 <= nlists <= 32768.
+ *
+ * On a bit index these entries work, with queries given as [nq x bytes] bit strings and Hamming distances returned as
+ * floats (exact: at most 64 000): pgv_index_free, pgv_index_share, pgv_index_tids, pgv_index_rows, pgv_index_lists,
+ * pgv_rank_lists, pgv_scan_lists, pgv_search_batch, pgv_scan_batch.
+ *   pgv_rank_lists   GetScanLists (src/ivfscan.c:47-118): ascending by (distance, list id).  The SET at the boundary is
+ *                    the reference's (its strict `<` at :92 admits no later list at an equal distance); the ORDER among
+ *                    equal distances, which its pairing heap leaves open, is this library's rule.
+ *   scan heads       ascending by (distance, insertion position); the position counts through the query's lists in
+ *                    probe order and in row order inside a list.  Padding is +inf / -1.
+ *   pgv_scan_lists   a NULL query gives all zeros (ZeroDistance, src/ivfscan.c:192-196).
+ * These return PGV_ERR_ARG on a bit index before any launch: pgv_index_set_overlap, pgv_index_export, pgv_index_drain,
+ * pgv_index_shadow_cast, pgv_query_begin, pgv_search_batch_sharded (the import wire has no field for nbits; the
+ * single-query path and the lanes are float kernels).  pgv_builder_* takes a pgv_dtype and cannot be handed bits: a bit
+ * index is built from pgv_bit_kmeans and pgv_bit_assign plus a stable sort by list on the caller's side.
+ */
+int			pgv_index_upload_bits(pgv_ctx * ctx, int nbits, int nlists, const void *centers, const int64_t *list_offsets,
+								  const void *rows, const uint64_t *tids, pgv_index * *out);
+int			pgv_index_nbits(const pgv_index * index);	/* 0 on a vector / halfvec index, -1 on NULL */
+
+/*
+ * AddTupleToSort's argmin (src/ivfbuild.c:183-192) under hamming_distance: the first strictly-smallest center wins.
+ * centers [k x bytes], rows [n x bytes]; out_list [n], out_dist [n] (or NULL) the distance to it.  Host or device.
+ */
+int			pgv_bit_assign(pgv_ctx * ctx, int nbits, const void *centers, int k, const void *rows, int64_t n,
+						   int32_t *out_list, float *out_dist);
+
+/*
+ * IvfflatKmeans (src/ivfkmeans.c:553-570) for the bit type info.  The reference runs Elkan (:246-485); under Hamming
+ * every bound is an exact small integer or half-integer in fp32 and Hamming is a metric, so its pruning never changes
+ * an outcome and it is exactly this loop: k-means++ (InitCenters, :23-91, weight = min(weight, (float) d^2), sum and
+ * pick in double); iteration 0 assigns every sample to the first strictly-nearest center (:323-344); every later
+ * iteration keeps a sample where it is unless a center is STRICTLY closer (:440), then takes the lowest-indexed center
+ * among the strictly closest; new centers after each assignment (ComputeNewCenters + BitUpdateCenter, :205-231 and
+ * src/ivfutils.c:325-339: bit = (float) sum / (float) count > 0.5, an empty cluster takes nbits RandomDouble() draws,
+ * bit = (float) draw > 0.5, clusters in center order and bits in bit order); the loop stops when an iteration other
+ * than the first moves nothing (:482-483).  out_iters counts like pgv_kmeans.  n == 0 is RandomCenters (:110-133):
+ * every cluster is drawn.  More lists than distinct samples is no error.  n < 2^24, else PGV_ERR_ARG (the reference
+ * sums +1.0f into a float, which stops counting there; below it the integer counts here are the same numbers).
+ * samples [n x bytes], out_centers [k x bytes], out_closest [n] (or NULL).  max_iterations <= 0: 500.
+ */
+int			pgv_bit_kmeans(pgv_ctx * ctx, int nbits, const void *samples, int n, int k, int max_iterations,
+						   const pgv_rng * rng, void *out_centers, int32_t *out_closest, int *out_iters);
+
+/*
+ * One iteration of it, for tests and for callers that drive the loop: io_closest[j] = -1 means "not assigned yet" (plain
+ * first-strict-minimum), >= 0 the center the sample stays with unless one is strictly closer.  out_centers [k x bytes]
+ * the centers after the update, out_counts [k] the cluster sizes, *out_changes the samples whose center changed.
+ */
+int			pgv_bit_lloyd_step(pgv_ctx * ctx, int nbits, const void *samples, int n, const void *centers, int k,
+							   int32_t *io_closest, const pgv_rng * rng, void *out_centers, int32_t *out_counts,
+							   int64_t *out_changes);
+
 /* --------------------------------------------------------------- HNSW side */
 
 /*

@@ -47,7 +47,8 @@ SYMBOLS = [
     "pgv_index_tids", "pgv_hnsw_export", "pgv_hnsw_import", "pgv_hnsw_share", "pgv_hnsw_device", "pgv_exact_topk", "pgv_ctx_set_bound",
     "pgv_hnsw_upload_payload", "pgv_hnsw_get_payload", "pgv_builder_begin", "pgv_builder_add", "pgv_builder_set_centers", "pgv_builder_rows", "pgv_builder_finish", "pgv_builder_free", "pgv_index_drain",
     "pgv_index_set_overlap", "pgv_index_shadow_cast", "pgv_bit_topk", "pgv_binary_quantize", "pgv_rerank",
-    "pgv_hnsw_upload_bits",
+    "pgv_hnsw_upload_bits", "pgv_index_upload_bits", "pgv_index_nbits", "pgv_bit_assign", "pgv_bit_kmeans",
+    "pgv_bit_lloyd_step",
 ]
 
 
@@ -177,6 +178,11 @@ def _load():
     lib.pgv_bit_topk.argtypes = [P, I, P, I, P, I64, I, P, P]
     lib.pgv_binary_quantize.argtypes = [P, I, I, P, I64, P]
     lib.pgv_rerank.argtypes = [P, I, I, I, P, I, P, I64, P, I, I, P, P]
+    lib.pgv_index_upload_bits.argtypes = [P, I, I, P, P, P, P, C.POINTER(P)]
+    lib.pgv_index_nbits.argtypes = [P]
+    lib.pgv_bit_assign.argtypes = [P, I, P, I, P, I64, P, P]
+    lib.pgv_bit_kmeans.argtypes = [P, I, P, I, I, I, C.POINTER(PgvRng), P, P, C.POINTER(I)]
+    lib.pgv_bit_lloyd_step.argtypes = [P, I, P, I, P, I, P, C.POINTER(PgvRng), P, P, P]
     lib.pgv_hnsw_set_graph.argtypes = [P, I, C.c_int32, P, P, P]
     lib.pgv_hnsw_search.argtypes = [P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_build_search.argtypes = [P, P, P, I, I, I, P, P, P]

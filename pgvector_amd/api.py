@@ -576,6 +576,150 @@ def binary_search(ctx, metric, dtype, dim, queries, rows, bits, kc, k, want_cand
     return (dist, idx, hamming, cand) if want_candidates else (dist, idx)
 
 
+class BitIvfIndex(IvfIndex):
+    """device mirror of `USING ivfflat (col bit_hamming_ops)` (pgv_index_upload_bits): centers [nlists x (nbits + 7) // 8]
+    and rows [n x (nbits + 7) // 8] uint8, first bit in the top bit of byte 0 (np.packbits' order), pad bits zero.
+    rank_lists, scan_lists, search_batch and scan_batch take packed queries and return Hamming distances as float32
+    (exact); share, tids, rows and close are IvfIndex's.  set_overlap, export and Query are refused by the library."""
+
+    def __init__(self, ctx, nbits, centers, list_offsets, rows, tids=None):
+        self.ctx, self.metric, self.dtype, self.dim, self.nbits = ctx, None, None, int(nbits), int(nbits)
+        centers, rows = _as_bytes(centers), _as_bytes(rows)
+        if not _is_torch(list_offsets):
+            list_offsets = np.ascontiguousarray(list_offsets, dtype=np.int64)
+        if tids is not None and not _is_torch(tids):
+            tids = np.ascontiguousarray(tids, dtype=np.uint64)
+        self.nlists = int(list_offsets.shape[0]) - 1
+        h = C.c_void_p()
+        check(lib.pgv_index_upload_bits(ctx.h, int(nbits), self.nlists, ptr(centers), ptr(list_offsets),
+                                        ptr(rows) if int(rows.shape[0]) else None, ptr(tids), C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def share(self, ctx):
+        v = BitIvfIndex.__new__(BitIvfIndex)
+        v.ctx, v.metric, v.dtype, v.dim, v.nbits, v.nlists = ctx, None, None, self.dim, self.nbits, self.nlists
+        h = C.c_void_p()
+        check(lib.pgv_index_share(self.h, ctx.h, C.byref(h)))
+        v.h = h
+        ctx._adopt(v)
+        return v
+
+    def rank_lists(self, queries, maxprobes, want_dist=True):
+        queries = _as_bytes(queries)
+        nq = int(queries.shape[0])
+        lists = _empty_like_kind(queries, (nq, maxprobes), np.int32)
+        dist = _empty_like_kind(queries, (nq, maxprobes), np.float32) if want_dist else None
+        check(lib.pgv_rank_lists(self.h, ptr(queries), nq, maxprobes, ptr(lists), ptr(dist)))
+        return lists, dist
+
+    def scan_lists(self, query, lists, capacity=None):
+        """-> (dist [m], slot [m]) in stream order; capacity: the output size offered (default: what the lists hold)"""
+        if query is not None:
+            query = _as_bytes(query)
+        lists = np.ascontiguousarray(lists, dtype=np.int32)
+        count = C.c_int64()
+        if capacity is None:
+            rc = lib.pgv_scan_lists(self.h, ptr(query), ptr(lists), len(lists), None, None, 0, C.byref(count))
+            if rc != _lib.PGV_OK and count.value == 0:
+                check(rc)
+            capacity = count.value
+        dist = np.empty(capacity, dtype=np.float32)
+        slot = np.empty(capacity, dtype=np.int64)
+        check(lib.pgv_scan_lists(self.h, ptr(query), ptr(lists), len(lists), ptr(dist), ptr(slot), int(capacity),
+                                 C.byref(count)))
+        return dist[:count.value], slot[:count.value]
+
+    def _outputs(self, queries, nq, k, want_tid, out):
+        if out is not None:
+            return out
+        return (_empty_like_kind(queries, (nq, k), np.float32), _empty_like_kind(queries, (nq, k), np.int64),
+                _empty_like_kind(queries, (nq, k), np.uint64 if not _on_device(queries) else np.int64) if want_tid else None)
+
+    def search_batch(self, queries, probes, k, want_tid=False, out=None):
+        queries = _as_bytes(queries)
+        nq = int(queries.shape[0])
+        dist, slot, tid = self._outputs(queries, nq, k, want_tid, out)
+        check(lib.pgv_search_batch(self.h, ptr(queries), nq, int(probes), int(k), ptr(dist), ptr(slot), ptr(tid)))
+        return dist, slot, tid
+
+    def scan_batch(self, queries, probe_lists, k, want_tid=False, out=None):
+        queries = _as_bytes(queries)
+        nq = int(queries.shape[0])
+        if not _is_torch(probe_lists):
+            probe_lists = np.ascontiguousarray(probe_lists, dtype=np.int32)
+        dist, slot, tid = self._outputs(queries, nq, k, want_tid, out)
+        check(lib.pgv_scan_batch(self.h, ptr(queries), nq, ptr(probe_lists), int(probe_lists.shape[1]), int(k), ptr(dist),
+                                 ptr(slot), ptr(tid)))
+        return dist, slot, tid
+
+
+def bit_assign(ctx, nbits, centers, rows, want_dist=True):
+    """pgv_bit_assign: the first strictly-nearest center of every packed row under Hamming distance
+    -> (list [n] int32, dist [n] float32 or None)"""
+    centers, rows = _as_bytes(centers), _as_bytes(rows)
+    n = int(rows.shape[0])
+    out = _empty_like_kind(rows, (n,), np.int32)
+    dist = _empty_like_kind(rows, (n,), np.float32) if want_dist else None
+    check(lib.pgv_bit_assign(ctx.h, int(nbits), ptr(centers), int(centers.shape[0]), ptr(rows) if n else None, n, ptr(out),
+                             ptr(dist)))
+    return out, dist
+
+
+def bit_kmeans(ctx, nbits, samples, k, rng=None, max_iterations=500, want_closest=True):
+    """pgv_bit_kmeans: IvfflatKmeans for bit strings -> (centers [k x bytes] uint8, closest [n] int32 or None, iterations)"""
+    samples = _as_bytes(samples)
+    n = int(samples.shape[0])
+    centers = _empty_like_kind(samples, (k, (int(nbits) + 7) // 8), np.uint8)
+    closest = _empty_like_kind(samples, (n,), np.int32) if want_closest and n else None
+    iters = C.c_int()
+    check(lib.pgv_bit_kmeans(ctx.h, int(nbits), ptr(samples) if n else None, n, int(k), int(max_iterations),
+                             C.byref(rng) if rng is not None else None, ptr(centers), ptr(closest), C.byref(iters)))
+    return centers, closest, iters.value
+
+
+def bit_lloyd_step(ctx, nbits, samples, centers, closest, rng=None):
+    """pgv_bit_lloyd_step: one iteration of pgv_bit_kmeans; closest (int32, -1 = not assigned yet) is updated in place
+    -> (new centers [k x bytes] uint8, counts [k] int32, changes)"""
+    samples, centers = _as_bytes(samples), _as_bytes(centers)
+    n, k = int(samples.shape[0]), int(centers.shape[0])
+    new = _empty_like_kind(centers, (k, (int(nbits) + 7) // 8), np.uint8)
+    counts = np.empty(k, dtype=np.int32)
+    changes = np.empty(1, dtype=np.int64)
+    check(lib.pgv_bit_lloyd_step(ctx.h, int(nbits), ptr(samples) if n else None, n, ptr(centers), k, ptr(closest),
+                                 C.byref(rng) if rng is not None else None, ptr(new), ptr(counts), ptr(changes)))
+    return new, counts, int(changes[0])
+
+
+def build_bit_ivf(ctx, nbits, rows, lists, rng=None, samples=None):
+    """`CREATE INDEX ... USING ivfflat (col bit_hamming_ops) WITH (lists = ...)` from the library's pieces: k-means over
+    `samples` (default: all rows), pgv_bit_assign, a stable sort by list (heap order inside a list) and the upload, with
+    the row index as the TID -> (BitIvfIndex, centers [lists x bytes], list_offsets [lists + 1])"""
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    centers, _, _ = bit_kmeans(ctx, nbits, rows if samples is None else samples, lists, rng=rng, want_closest=False)
+    assigned, _ = bit_assign(ctx, nbits, centers, rows, want_dist=False)
+    order = np.argsort(assigned, kind="stable")
+    offsets = np.zeros(lists + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum(np.bincount(assigned, minlength=lists))
+    index = BitIvfIndex(ctx, nbits, centers, offsets, rows[order], tids=order.astype(np.uint64))
+    return index, centers, offsets
+
+
+def binary_search_ivf(ctx, metric, dtype, dim, queries, rows, bit_ivf, probes, kc, k, want_candidates=False):
+    """the two-stage query of binary quantization over an IVFFlat index of the rows' binary_quantize image (a BitIvfIndex
+    whose TIDs are the row indexes, as build_bit_ivf uploads them): quantise the queries, the kc nearest tuples of the
+    `probes` nearest lists by Hamming distance, then the k nearest of those by the exact metric over `rows`
+    -> (dist [nq x k], idx [nq x k]) and, on request, stage one's (hamming [nq x kc], cand [nq x kc])"""
+    qbits = binary_quantize(ctx, dtype, dim, queries)
+    hamming, slot, tid = bit_ivf.search_batch(qbits, probes, kc, want_tid=True)
+    if _is_torch(tid):
+        cand = tid  # (int64 on the device: the "none" TID ~0 reads as -1)
+    else:
+        cand = np.where(slot >= 0, tid.astype(np.int64), -1)
+    dist, idx = rerank(ctx, metric, dtype, dim, queries, rows, cand, k)
+    return (dist, idx, hamming, cand) if want_candidates else (dist, idx)
+
+
 class IvfBuilder:
     """pgv_builder_*: heap rows assigned and kept on the device, finish() = the tuplesort by list as a device gather
     whose result is the mirror itself"""

@@ -6,6 +6,9 @@
 //                            of a tile of rows against a tile of queries, into pgv_bit_topk's distance matrix
 //   binary_quantize_kernel   binary_quantize (src/vector.c:952-979, halfvec_binary_quantize in src/halfvec.c)
 //   rerank_*_kernel          what pgv_rerank needs around score_gather_kernel and topk_kernel
+//   hamming_list_kernel      the list scan of `USING ivfflat (col bit_hamming_ops)`: GetScanItems (src/ivfscan.c:123-187)
+//                            over the batch plan's ScanTask / ScanPair (pgv_index::nbits)
+//   bit_closest_kernel, bit_sums_kernel, bit_centers_kernel   the bit k-means around the Hamming matrix (pgv_bit_kmeans)
 // bit_kernel (kernels_misc.hip) stays the operator path: one query, float8 out, both bit metrics.
 //
 // hamming_tile_kernel: 256 rows x 32 queries per workgroup, one lane per row.
@@ -19,6 +22,26 @@
 //   * stores are coalesced along `row`: lane i writes out[q * n + row0 + i]
 // Rows are padded with zero bytes to whole 16-byte vectors and queries to whole slices (pgv_bit_topk stages them):
 // padding adds nothing to a count.  Tail rows and tail queries clamp their address and are computed, not stored.
+//
+// hamming_list_kernel<QT>: a task of the list-major plan (launch_plan_batch) per trip of a persistent workgroup -- a
+// run of at most 256 rows of one list x the up to QT queries of one group that probes it -- into out[pair.out_rel + row].
+//   * inside a task it is the tile kernel: one lane per row, the cooperative 128-byte fetch, the transpose through LDS
+//     at stride 9, 1024-bit slices with the next slice's loads in flight, integer accumulators converted at the
+//     coalesced store, tail rows and tail pairs clamped and computed but not stored, no predicated load
+//   * around it it is scan_kernel: workgroups pull tasks from the device counter, the last one to finish leaves both
+//     counter words zero, ntasks is read from the device
+//   * QT in {8, 16, 32}: a list is probed by nq x probes / nlists queries on average (about 10 at 1024 queries x 10
+//     probes over 1000 lists), a 1536-bit row costs 192 B of HBM once and 96 vector-ALU operations per (row, query)
+//     pair, so at ~10 pairs a row the two are of the same order and padding every group to 32 would triple the ALU work.
+//     hamming_list_group_size picks the smallest QT the average share stays below; lists probed by more queries are
+//     split into several groups by the plan.  The switch points (8 | 16 | 32 at shares 8 and 16) are arithmetic,
+//     UNMEASURED against each other
+//   * where the query words come from: the task index reaches the lanes through LDS, so the compiler cannot see that
+//     the task's fields and its query ids are the same in every lane.  They are made provably uniform with
+//     __builtin_amdgcn_readfirstlane (the task index, the task's fields, every query id and out_rel): the query words
+//     are then addressed from SGPRs, arrive through the scalar cache and the inner step keeps the tile kernel's
+//     `v_xor_b32 v, s, v` + `v_bcnt_u32_b32` form.  The alternative -- staging the group's query slices in LDS as
+//     scan_kernel does (QT x 128 B per slice, a ds_read per word) -- was not built: UNMEASURED against this one
 #include "pgv_device.h"
 
 namespace pgv {
@@ -150,6 +173,170 @@ __global__ void rerank_map_kernel(const int64_t *__restrict__ cand, int nq, int 
     out_idx[i] = c < 0 ? -1 : c;
 }
 
+
+// a value every lane of the workgroup holds alike, told to the compiler
+__device__ __forceinline__ int uniform32(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uniform64(int64_t v) {
+    const unsigned lo = (unsigned)uniform32((int)(uint32_t)v), hi = (unsigned)uniform32((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+template <int QT>
+__global__ __launch_bounds__(kBitThreads) void hamming_list_kernel(
+    const char *__restrict__ rows, const uint32_t *__restrict__ queries, const ScanTask *__restrict__ tasks,
+    const int *__restrict__ ntasks_ptr, int *__restrict__ task_counter, const ScanPair *__restrict__ pairs,
+    float *__restrict__ out, int nvec, int qwords) {
+    __shared__ Raw16 tile[kBitThreads * kBitLdsStride];
+    __shared__ int lds_task;
+    const int tid = threadIdx.x;
+    const int nslices = (nvec + kBitSliceVecs - 1) / kBitSliceVecs;
+    const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
+    const int lv = tid & (kBitSliceVecs - 1);  // which vector of the slice this lane fetches
+    const int lr = tid >> 3;                   // ... of rows lr, lr + 32, ..
+    const int ntasks = *ntasks_ptr;
+
+    for (;;) {
+        if (tid == 0) lds_task = atomicAdd(task_counter, 1);
+        __syncthreads();
+        const int t = uniform32(lds_task);
+        if (t >= ntasks) {
+            // every workgroup ends here exactly once; the last one leaves both words zero for the next launch
+            if (tid == 0 && atomicAdd(task_counter + 1, 1) == (int)gridDim.x - 1) {
+                atomicExch(task_counter + 1, 0);
+                atomicExch(task_counter, 0);
+            }
+            return;
+        }
+        const int64_t row0 = uniform64(tasks[t].row0);
+        const int nrows = uniform32(tasks[t].nrows);
+        const int pair0 = uniform32(tasks[t].pair0);
+        const int npairs = uniform32(tasks[t].npairs);
+        const char *task_rows = rows + (size_t)row0 * row_bytes;
+
+        Raw16 nxt[kBitSliceVecs];
+        auto fetch = [&](int s) {
+            const int vi = s * kBitSliceVecs + lv;
+            const bool ok = vi < nvec;
+            const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
+#pragma unroll
+            for (int i = 0; i < kBitSliceVecs; i++) {
+                int r = lr + i * kBitRowsPerTrip;
+                r = r < nrows ? r : nrows - 1;  // tail rows are computed, not stored
+                const Raw16 v = load16(task_rows + (size_t)r * row_bytes + (size_t)vc * sizeof(Raw16));
+                nxt[i] = ok ? v : raw16_zero();
+            }
+        };
+
+        int acc[QT];
+#pragma unroll
+        for (int q = 0; q < QT; q++) acc[q] = 0;
+
+        fetch(0);
+        for (int s = 0; s < nslices; s++) {
+            __syncthreads();  // the previous slice (or task) has been read by every lane
+#pragma unroll
+            for (int i = 0; i < kBitSliceVecs; i++) tile[(lr + i * kBitRowsPerTrip) * kBitLdsStride + lv] = nxt[i];
+            __syncthreads();
+            Raw16 rv[kBitSliceVecs];
+#pragma unroll
+            for (int v = 0; v < kBitSliceVecs; v++) rv[v] = tile[tid * kBitLdsStride + v];
+            if (s + 1 < nslices) fetch(s + 1);
+
+            const uint32_t *qs = queries + (size_t)s * kBitSliceWords;
+#pragma unroll
+            for (int q = 0; q < QT; q++) {
+                const int qq = q < npairs ? q : npairs - 1;  // tail pairs are computed, not stored
+                const int qi = uniform32(pairs[pair0 + qq].query);
+                const uint32_t *qp = qs + (size_t)qi * qwords;  // wave-uniform: scalar loads
+#pragma unroll
+                for (int v = 0; v < kBitSliceVecs; v++)
+#pragma unroll
+                    for (int w = 0; w < 4; w++) acc[q] = __popc(rv[v].w[w] ^ qp[v * 4 + w]) + acc[q];
+            }
+        }
+
+        if (tid < nrows) {
+#pragma unroll
+            for (int q = 0; q < QT; q++)
+                if (q < npairs) out[uniform64(pairs[pair0 + q].out_rel) + row0 + tid] = (float)acc[q];
+        }
+        // (lds_task and the tile are rewritten behind the barriers at the top of the next trip: every lane has passed at
+        // least the two barriers of a slice since it read them)
+    }
+}
+
+// ---- the bit k-means around the Hamming matrix ----------------------------------------------------------------------
+// One lane per sample: Elkan's outcome under an exact metric (src/ivfkmeans.c:323-344 for a sample without a center,
+// :401-450 for one that has one) from the sample's row of the distance matrix and that row's first minimum
+__global__ void bit_closest_kernel(const float *__restrict__ mat, int k, const float *__restrict__ best_val,
+                                   const int64_t *__restrict__ best_pos, int n, int sticky, int32_t *__restrict__ closest_io,
+                                   float *__restrict__ out_dist, int32_t *__restrict__ counts,
+                                   unsigned long long *__restrict__ changes) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int cur = sticky ? closest_io[j] : -1;
+    int now = (int)best_pos[j];
+    float d = best_val[j];
+    if (cur >= 0) {
+        const float dc = mat[(size_t)j * (size_t)k + (size_t)cur];
+        if (!(d < dc)) {  // nothing strictly closer: the sample stays (:440)
+            now = cur;
+            d = dc;
+        }
+    }
+    closest_io[j] = now;
+    if (out_dist) out_dist[j] = d;
+    if (counts) atomicAdd(&counts[now], 1);
+    if (changes && now != cur) atomicAdd(changes, 1ull);
+}
+
+// BitSumCenter (src/ivfutils.c:363-370) as integers: one lane per sample byte, an atomic per set bit.  The values are
+// counts below 2^24: the order of addition does not matter and the reference's float sums hold the same numbers
+__global__ void bit_sums_kernel(const uint8_t *__restrict__ samples, int ld, int bytes, int nbits, int n,
+                                const int32_t *__restrict__ closest, int32_t *__restrict__ sums) {
+    const size_t total = (size_t)n * (size_t)bytes;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = i / (size_t)bytes;
+        const int b = (int)(i - j * (size_t)bytes);
+        const unsigned byte = samples[j * (size_t)ld + b];
+        if (!byte) continue;
+        int32_t *dst = sums + (size_t)closest[j] * (size_t)nbits + (size_t)b * 8;
+#pragma unroll
+        for (int e = 0; e < 8; e++)
+            if (((byte >> (7 - e)) & 1u) && b * 8 + e < nbits) atomicAdd(dst + e, 1);
+    }
+}
+
+// ComputeNewCenters' division and BitUpdateCenter (src/ivfkmeans.c:205-231, src/ivfutils.c:325-339): one lane per
+// OUTPUT BYTE of the padded center row; x = (float) sum / (float) count, bit = x > 0.5, first bit in the top bit, pad
+// bits and pad bytes zero.  An empty cluster's bits were drawn on the host (refill)
+__global__ void bit_centers_kernel(const int32_t *__restrict__ sums, const int32_t *__restrict__ counts, int k, int nbits,
+                                   int bytes, int ld, const int32_t *__restrict__ refill_row,
+                                   const uint8_t *__restrict__ refill, uint8_t *__restrict__ centers) {
+    const size_t total = (size_t)k * (size_t)ld;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i / (size_t)ld);
+        const int b = (int)(i - (size_t)c * (size_t)ld);
+        unsigned byte = 0;
+        if (b < bytes) {
+            const int rr = refill_row ? refill_row[c] : -1;
+            if (rr >= 0) {
+                byte = refill[(size_t)rr * (size_t)bytes + b];
+            } else {
+                const float cnt = (float)counts[c];
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    const int d = b * 8 + e;
+                    const bool ok = d < nbits;
+                    const float x = (float)sums[(size_t)c * (size_t)nbits + (ok ? d : nbits - 1)] / cnt;
+                    byte |= (ok && x > 0.5f ? 1u : 0u) << (7 - e);
+                }
+            }
+        }
+        centers[i] = (uint8_t)byte;
+    }
+}
+
 }  // namespace
 
 int bit_topk_slice_bytes() { return kBitSliceVecs * (int)sizeof(Raw16); }
@@ -163,6 +350,72 @@ int launch_hamming_tiles(pgv_ctx *ctx, const void *rows, int nvec, int64_t n, co
     hipLaunchKernelGGL(hamming_tile_kernel, dim3((unsigned)grid), dim3(kBitThreads), 0, ctx->stream,
                        static_cast<const char *>(rows), static_cast<const uint32_t *>(queries), n, nq, nvec, qbytes / 4, nqt,
                        out);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+// queries of one group: the smallest instantiation the average share stays BELOW (see the header) -- the share is a mean,
+// and with a mean of exactly QT about half the lists would need a second group
+int hamming_list_group_size(double queries_per_list) { return queries_per_list < 8.0 ? 8 : (queries_per_list < 16.0 ? 16 : 32); }
+int hamming_list_rows_per_task() { return kBitThreads; }
+
+template <int QT>
+static int launch_hamming_lists_t(pgv_ctx *ctx, const void *rows, int nvec, const void *queries, int qbytes,
+                                  const ScanTask *tasks, const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs,
+                                  float *out) {
+    PGV_TRY(ctx->counters.ensure(256));
+    if (!ctx->counters_clean) {
+        PGV_HIP(hipMemsetAsync(ctx->counters.p, 0, 256, ctx->stream));
+        ctx->counters_clean = true;
+    }
+    int *counter = ctx->counters.as<int>() + 10;  // words 10, 11 as launch_scan: claimed tasks, workgroups done
+    // 36 KB of LDS a workgroup: four of them share a CU
+    int grid = ctx->num_cus * 4;
+    if (grid > ntasks_bound) grid = ntasks_bound;
+    hipLaunchKernelGGL(hamming_list_kernel<QT>, dim3(grid), dim3(kBitThreads), 0, ctx->stream, static_cast<const char *>(rows),
+                       static_cast<const uint32_t *>(queries), tasks, ntasks_dev, counter, pairs, out, nvec, qbytes / 4);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_hamming_lists(pgv_ctx *ctx, const void *rows, int nvec, const void *queries, int qbytes, const ScanTask *tasks,
+                         const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt, float *out) {
+    if (ntasks_bound <= 0) return PGV_OK;
+    switch (qt) {
+        case 8: return launch_hamming_lists_t<8>(ctx, rows, nvec, queries, qbytes, tasks, ntasks_dev, ntasks_bound, pairs, out);
+        case 16: return launch_hamming_lists_t<16>(ctx, rows, nvec, queries, qbytes, tasks, ntasks_dev, ntasks_bound, pairs, out);
+        case 32: return launch_hamming_lists_t<32>(ctx, rows, nvec, queries, qbytes, tasks, ntasks_dev, ntasks_bound, pairs, out);
+    }
+    PGV_FAIL(PGV_ERR_ARG, "bit list scan: unsupported query group size %d", qt);
+}
+
+int launch_bit_closest(pgv_ctx *ctx, const float *mat, int k, const float *best_val, const int64_t *best_pos, int n,
+                       bool sticky, int32_t *closest_io, float *out_dist, int32_t *counts, unsigned long long *changes) {
+    if (n <= 0) return PGV_OK;
+    hipLaunchKernelGGL(bit_closest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, mat, k, best_val,
+                       best_pos, n, sticky ? 1 : 0, closest_io, out_dist, counts, changes);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_bit_sums(pgv_ctx *ctx, const void *samples, int ld, int nbits, int n, const int32_t *closest, int32_t *sums) {
+    if (n <= 0) return PGV_OK;
+    const int bytes = (nbits + 7) / 8;
+    const size_t total = (size_t)n * (size_t)bytes;
+    const size_t want = (total + 255) / 256, cap = (size_t)ctx->num_cus * 64;
+    hipLaunchKernelGGL(bit_sums_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, ctx->stream,
+                       static_cast<const uint8_t *>(samples), ld, bytes, nbits, n, closest, sums);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_bit_centers(pgv_ctx *ctx, const int32_t *sums, const int32_t *counts, int k, int nbits, int ld,
+                       const int32_t *refill_row, const uint8_t *refill, void *centers) {
+    if (k <= 0) return PGV_OK;
+    const size_t total = (size_t)k * (size_t)ld;
+    const size_t want = (total + 255) / 256, cap = (size_t)ctx->num_cus * 64;
+    hipLaunchKernelGGL(bit_centers_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, ctx->stream, sums, counts,
+                       k, nbits, (nbits + 7) / 8, ld, refill_row, refill, static_cast<uint8_t *>(centers));
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

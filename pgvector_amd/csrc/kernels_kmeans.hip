@@ -21,6 +21,7 @@ constexpr int kKmThreads = 256;
 // raw[j] = FUNCTION-1-style kernel value of (sample j, newest center):
 //   spherical == 0: L2 squared          -> distance = sqrt((double) raw)      (vector.c:588)
 //   spherical == 1: negative inner prod -> distance = acos(clamp(ip)) / pi    (vector.c:713-721)
+//   spherical == 2: hamming_distance    -> distance = raw                     (bitvec.c:45-56)
 // weight[j] = min(weight[j], (float) distance^2) (ivfkmeans.c:64-68); per-block sums in double.
 __global__ __launch_bounds__(kKmThreads) void kmpp_update_kernel(
     const float *__restrict__ raw, float *__restrict__ weight, int n, int spherical,
@@ -30,13 +31,15 @@ __global__ __launch_bounds__(kKmThreads) void kmpp_update_kernel(
     double w = 0.0;
     if (j < n) {
         double distance;
-        if (spherical) {
+        if (spherical == 1) {
             double ip = -(double)raw[j];
             if (ip > 1)
                 ip = 1;
             else if (ip < -1)
                 ip = -1;
             distance = acos(ip) / 3.14159265358979323846;
+        } else if (spherical == 2) {
+            distance = (double)raw[j];
         } else {
             distance = sqrt((double)raw[j]);
         }

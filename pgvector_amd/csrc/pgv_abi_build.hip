@@ -343,6 +343,301 @@ int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const 
     return sync_if(ctx, need);
 }
 
+// ------------------------------------------------------ k-means over bit strings
+// `USING ivfflat (col bit_hamming_ops)` on the build side.  The samples are staged as the QUERIES of hamming_tile_kernel
+// (rows of whole register slices, BitGeom::q_ld bytes), the centers as its rows: a chunk's matrix mat[sample][center]
+// then holds a sample's distances side by side, launch_topk_segments(k = 1) finds its first minimum (ties to the lower
+// center) and bit_closest_kernel decides.  During k-means the centers live at the samples' stride as well, so that a
+// center is a row of the assignment, the query of a k-means++ round and the target of launch_kmpp_pick's row copy.
+namespace {
+struct BitGeom {
+    int bytes, row_ld, q_ld;  // VARBITBYTES | padded to 16-byte vectors | padded to the kernels' register slices
+};
+BitGeom bit_geom(int nbits) {
+    BitGeom g;
+    g.bytes = (nbits + 7) / 8;
+    g.row_ld = (g.bytes + 15) / 16 * 16;
+    const int slice = bit_topk_slice_bytes();
+    g.q_ld = (g.bytes + slice - 1) / slice * slice;
+    return g;
+}
+int check_bits(int nbits, const char *who) {
+    // IVFFLAT_MAX_DIM * 32 (src/ivfutils.c:416)
+    if (nbits < 1 || nbits > kIvfMaxBits) PGV_FAIL(PGV_ERR_DIMS, "%s: bit length %d outside 1..%d", who, nbits, kIvfMaxBits);
+    return PGV_OK;
+}
+
+// samples [n x q_ld] (device, staged) to their centers [k x c_ld] (device, staged): closest_io / out_dist / counts /
+// changes as launch_bit_closest takes them (device).  The matrix stays at or under 2^30 floats per chunk of samples
+int bit_closest_dev(pgv_ctx *ctx, const void *s_dev, int q_ld, int64_t n, const void *c_dev, int c_ld, int k, bool sticky,
+                    int32_t *closest_io, float *out_dist, int32_t *counts, unsigned long long *changes) {
+    int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(1, ((int64_t)1 << 30) / k));
+    if (chunk >= 32) chunk = chunk / 32 * 32;
+    PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * std::max<size_t>((size_t)chunk * (size_t)k, 4)));
+    PGV_TRY(ctx->sel_a.ensure(sizeof(int64_t) * (size_t)chunk));
+    PGV_TRY(ctx->sel_b.ensure(sizeof(float) * (size_t)chunk));
+    float *mat = ctx->dist_mat.as<float>(), *best_val = ctx->sel_b.as<float>();
+    int64_t *best_pos = ctx->sel_a.as<int64_t>();
+    for (int64_t j0 = 0; j0 < n; j0 += chunk) {
+        const int cn = (int)std::min<int64_t>(chunk, n - j0);
+        ScanTimer timer{ctx};
+        PGV_TRY(timer.begin((double)cn * k, (double)k * ((cn + 31) / 32), true));
+        PGV_TRY(launch_hamming_tiles(ctx, c_dev, c_ld / 16, k, static_cast<const char *>(s_dev) + (size_t)j0 * q_ld, q_ld, cn,
+                                     mat));
+        PGV_TRY(timer.end());
+        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, k, 1, best_val, best_pos));
+        PGV_TRY(launch_bit_closest(ctx, mat, k, best_val, best_pos, cn, sticky, closest_io + j0, out_dist ? out_dist + j0 : nullptr,
+                                   counts, changes));
+    }
+    return PGV_OK;
+}
+
+// ComputeNewCenters + BitUpdateCenter (src/ivfkmeans.c:205-231, src/ivfutils.c:325-339) from the assignment: per-center
+// bit counts on the device, the empty clusters' draws on the host -- nbits RandomDouble() each, x = (float) draw,
+// bit = x > 0.5, clusters in center order and bits in bit order -- like lloyd_finish_dev.  h_counts: the cluster sizes
+// on the host.  centers_dev [k x c_ld] is rewritten.  km_e: sums | refill_row | refill
+int bit_update_centers_dev(pgv_ctx *ctx, int nbits, const BitGeom &g, const void *s_dev, int n, const int32_t *closest_dev,
+                           const int32_t *counts_dev, const int32_t *h_counts, int k, Rng &rng, void *centers_dev, int c_ld) {
+    int nempty = 0;
+    for (int c = 0; c < k; c++)
+        if (h_counts[c] <= 0) nempty++;
+    const size_t sums_bytes = (sizeof(int32_t) * (size_t)k * (size_t)nbits + 255) & ~(size_t)255;
+    const size_t row_bytes = (sizeof(int32_t) * (size_t)k + 255) & ~(size_t)255;
+    PGV_TRY(ctx->km_e.ensure(sums_bytes + row_bytes + (size_t)nempty * g.bytes + 16));
+    int32_t *sums = ctx->km_e.as<int32_t>();
+    int32_t *refill_row = reinterpret_cast<int32_t *>(ctx->km_e.as<char>() + sums_bytes);
+    uint8_t *refill = reinterpret_cast<uint8_t *>(ctx->km_e.as<char>() + sums_bytes + row_bytes);
+    PGV_HIP(hipMemsetAsync(sums, 0, sums_bytes, ctx->stream));
+    PGV_TRY(launch_bit_sums(ctx, s_dev, g.q_ld, nbits, n, closest_dev, sums));
+    if (nempty > 0) {
+        PGV_TRY(ctx->h_b.ensure(row_bytes + (size_t)nempty * g.bytes));
+        int32_t *h_row = ctx->h_b.as<int32_t>();
+        uint8_t *h_fill = reinterpret_cast<uint8_t *>(ctx->h_b.as<char>() + row_bytes);
+        memset(h_fill, 0, (size_t)nempty * g.bytes);
+        int e = 0;
+        for (int c = 0; c < k; c++) {
+            h_row[c] = -1;
+            if (h_counts[c] <= 0) {
+                for (int i = 0; i < nbits; i++) {
+                    const float x = (float)rng.next_double();
+                    if (x > 0.5f) h_fill[(size_t)e * g.bytes + i / 8] |= (uint8_t)(1u << (7 - i % 8));
+                }
+                h_row[c] = e++;
+            }
+        }
+        PGV_HIP(hipMemcpyAsync(refill_row, h_row, row_bytes + (size_t)nempty * g.bytes, hipMemcpyHostToDevice, ctx->stream));
+        PGV_HIP(hipStreamSynchronize(ctx->stream));  // h_b may be rewritten by the next step
+    }
+    return launch_bit_centers(ctx, sums, counts_dev, k, nbits, c_ld, nempty > 0 ? refill_row : nullptr, refill, centers_dev);
+}
+
+// one iteration on staged samples and centers (both at stride q_ld): assignment, counts, changes, new centers in place.
+// km_f: counts[k] | changes.  *out_changes and h_counts (host, [k]) are valid on return
+int bit_lloyd_dev(pgv_ctx *ctx, int nbits, const BitGeom &g, const void *s_dev, int n, void *centers_dev, int k,
+                  int32_t *closest_dev, Rng &rng, int32_t **counts_dev_out, std::vector<int32_t> &h_counts,
+                  unsigned long long *out_changes) {
+    const size_t cb = (sizeof(int32_t) * (size_t)k + 7) & ~(size_t)7;
+    PGV_TRY(ctx->km_f.ensure(cb + sizeof(unsigned long long)));
+    int32_t *counts = ctx->km_f.as<int32_t>();
+    unsigned long long *changes = reinterpret_cast<unsigned long long *>(ctx->km_f.as<char>() + cb);
+    PGV_HIP(hipMemsetAsync(counts, 0, cb + sizeof(unsigned long long), ctx->stream));
+    if (n > 0) PGV_TRY(bit_closest_dev(ctx, s_dev, g.q_ld, n, centers_dev, g.q_ld, k, true, closest_dev, nullptr, counts, changes));
+    h_counts.assign((size_t)k, 0);
+    PGV_HIP(hipMemcpyAsync(h_counts.data(), counts, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
+    PGV_HIP(hipMemcpyAsync(out_changes, changes, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    PGV_TRY(bit_update_centers_dev(ctx, nbits, g, s_dev, n, closest_dev, counts, h_counts.data(), k, rng, centers_dev, g.q_ld));
+    *counts_dev_out = counts;
+    return PGV_OK;
+}
+
+// packed device rows [cnt x ld] -> the caller's [cnt x bytes] (host or device)
+int unstage_bit_rows(pgv_ctx *ctx, const void *src_dev, int64_t cnt, int bytes, int ld, void *dst) {
+    if (cnt == 0) return PGV_OK;
+    const bool dev = is_device_ptr(dst);
+    PGV_HIP(hipMemcpy2DAsync(dst, (size_t)bytes, src_dev, (size_t)ld, (size_t)bytes, (size_t)cnt,
+                             dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));
+    return PGV_OK;
+}
+// a staging that is a copy even of device rows (the centers of a k-means are rewritten in place)
+int copy_bit_rows(pgv_ctx *ctx, const void *src, int64_t cnt, int bytes, int ld, DBuf &scratch) {
+    PGV_TRY(scratch.ensure(std::max<size_t>((size_t)cnt * ld, 16)));
+    PGV_HIP(hipMemsetAsync(scratch.p, 0, (size_t)cnt * ld, ctx->stream));
+    if (cnt > 0)
+        PGV_HIP(hipMemcpy2DAsync(scratch.p, (size_t)ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt,
+                                 is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    return PGV_OK;
+}
+}  // namespace
+
+// AddTupleToSort's argmin (src/ivfbuild.c:183-192) under hamming_distance: `distance < minDistance` keeps the first
+// strictly-smallest center
+int pgv_bit_assign(pgv_ctx *ctx, int nbits, const void *centers, int k, const void *rows, int64_t n, int32_t *out_list,
+                   float *out_dist) {
+    if (!ctx || !out_list) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_assign: ctx/out_list is NULL");
+    PGV_TRY(check_bits(nbits, "pgv_bit_assign"));
+    if (k < 1 || !centers) PGV_FAIL(PGV_ERR_ARG, "need at least one center");
+    if (n < 0) PGV_FAIL(PGV_ERR_ARG, "n < 0");
+    if (n == 0) return PGV_OK;
+    if (!rows) PGV_FAIL(PGV_ERR_ARG, "rows is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    const BitGeom g = bit_geom(nbits);
+    const void *c_dev;
+    PGV_TRY(stage_bit_rows(ctx, centers, k, g.bytes, g.row_ld, ctx->centers_stage, &c_dev));
+    const bool out_dev = is_device_ptr(out_list), dist_dev = out_dist && is_device_ptr(out_dist);
+    // rows are staged in slabs, like pgv_assign's host rows
+    const int64_t slab = (int64_t)1 << 18;
+    bool need = false;
+    for (int64_t r0 = 0; r0 < n; r0 += slab) {
+        const int64_t cnt = std::min(slab, n - r0);
+        const void *r_dev;
+        PGV_TRY(stage_bit_rows(ctx, static_cast<const char *>(rows) + (size_t)r0 * g.bytes, cnt, g.bytes, g.q_ld, ctx->rows_stage,
+                               &r_dev));
+        int32_t *idx = out_list + r0;
+        float *val = out_dist ? out_dist + r0 : nullptr;
+        if (!out_dev) {
+            PGV_TRY(ctx->out_stage.ensure(sizeof(int32_t) * (size_t)cnt));
+            idx = ctx->out_stage.as<int32_t>();
+        }
+        if (out_dist && !dist_dev) {
+            PGV_TRY(ctx->out_stage2.ensure(sizeof(float) * (size_t)cnt));
+            val = ctx->out_stage2.as<float>();
+        }
+        PGV_TRY(bit_closest_dev(ctx, r_dev, g.q_ld, cnt, c_dev, g.row_ld, k, false, idx, val, nullptr, nullptr));
+        if (!out_dev) {
+            PGV_HIP(hipMemcpyAsync(out_list + r0, idx, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
+            need = true;
+        }
+        if (out_dist && !dist_dev) {
+            PGV_HIP(hipMemcpyAsync(out_dist + r0, val, sizeof(float) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
+            need = true;
+        }
+        if (r0 + slab < n) PGV_HIP(hipStreamSynchronize(ctx->stream));  // the staging is reused
+    }
+    return sync_if(ctx, need);
+}
+
+int pgv_bit_lloyd_step(pgv_ctx *ctx, int nbits, const void *samples, int n, const void *centers, int k, int32_t *io_closest,
+                       const pgv_rng *rng, void *out_centers, int32_t *out_counts, int64_t *out_changes) {
+    if (!ctx || !io_closest || !out_centers || !out_counts || !out_changes)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_bit_lloyd_step: NULL argument");
+    PGV_TRY(check_bits(nbits, "pgv_bit_lloyd_step"));
+    if (k < 1 || k > 32768 || n < 0 || !centers || (n > 0 && !samples)) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
+    if (n >= (1 << 24)) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_lloyd_step: %d samples, at most 2^24 - 1", n);
+    PGV_HIP(hipSetDevice(ctx->device));
+    const BitGeom g = bit_geom(nbits);
+    const void *s_dev = nullptr;
+    if (n > 0) PGV_TRY(stage_bit_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
+    PGV_TRY(copy_bit_rows(ctx, centers, k, g.bytes, g.q_ld, ctx->centers_stage));
+    int32_t *closest_dev = io_closest;
+    const bool closest_is_dev = is_device_ptr(io_closest);
+    if (!closest_is_dev) {
+        // (an assignment on the device is not checked: it comes from an earlier step)
+        for (int j = 0; j < n; j++)
+            if (io_closest[j] < -1 || io_closest[j] >= k)
+                PGV_FAIL(PGV_ERR_ARG, "pgv_bit_lloyd_step: io_closest[%d] = %d outside -1..%d", j, io_closest[j], k - 1);
+        PGV_TRY(ctx->idx_stage.ensure(sizeof(int32_t) * (size_t)(n > 0 ? n : 1)));
+        closest_dev = ctx->idx_stage.as<int32_t>();
+        if (n) PGV_HIP(hipMemcpyAsync(closest_dev, io_closest, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    }
+    Rng r(rng);
+    int32_t *counts_dev = nullptr;
+    std::vector<int32_t> h_counts;
+    unsigned long long changes = 0;
+    PGV_TRY(bit_lloyd_dev(ctx, nbits, g, s_dev, n, ctx->centers_stage.p, k, closest_dev, r, &counts_dev, h_counts, &changes));
+    PGV_TRY(unstage_bit_rows(ctx, ctx->centers_stage.p, k, g.bytes, g.q_ld, out_centers));
+    const int64_t ch = (int64_t)changes;
+    if (is_device_ptr(out_counts))
+        PGV_HIP(hipMemcpyAsync(out_counts, h_counts.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+    else
+        memcpy(out_counts, h_counts.data(), sizeof(int32_t) * (size_t)k);
+    if (is_device_ptr(out_changes))
+        PGV_HIP(hipMemcpyAsync(out_changes, &ch, sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    else
+        *out_changes = ch;
+    if (!closest_is_dev && n)
+        PGV_HIP(hipMemcpyAsync(io_closest, closest_dev, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    return pgv_ctx_sync(ctx);
+}
+
+int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, int max_iterations, const pgv_rng *rng,
+                   void *out_centers, int32_t *out_closest, int *out_iters) {
+    if (!ctx || !out_centers) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_kmeans: ctx/out_centers is NULL");
+    PGV_TRY(check_bits(nbits, "pgv_bit_kmeans"));
+    if (k < 1 || k > 32768) PGV_FAIL(PGV_ERR_ARG, "lists %d outside 1..32768", k);
+    // the reference's float sums stop counting at 2^24 (src/ivfutils.c:369): refused before the samples are touched
+    if (n >= (1 << 24)) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_kmeans: %d samples, at most 2^24 - 1", n);
+    if (n < 0 || (n > 0 && !samples)) PGV_FAIL(PGV_ERR_ARG, "bad samples");
+    if (max_iterations <= 0) max_iterations = 500;  // src/ivfkmeans.c:347
+    PGV_HIP(hipSetDevice(ctx->device));
+    const BitGeom g = bit_geom(nbits);
+    Rng r(rng);
+    PGV_TRY(ctx->centers_stage.ensure((size_t)k * g.q_ld));
+    void *centers_dev = ctx->centers_stage.p;
+    PGV_HIP(hipMemsetAsync(centers_dev, 0, (size_t)k * g.q_ld, ctx->stream));
+    int iters = 0;
+    int32_t *counts_dev = nullptr;
+    std::vector<int32_t> h_counts;
+    unsigned long long changes = 0;
+    if (n == 0) {
+        // RandomCenters (src/ivfkmeans.c:110-133): every cluster is drawn
+        PGV_TRY(bit_lloyd_dev(ctx, nbits, g, nullptr, 0, centers_dev, k, nullptr, r, &counts_dev, h_counts, &changes));
+    } else {
+        const void *s_dev;
+        PGV_TRY(stage_bit_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
+        // InitCenters (src/ivfkmeans.c:23-91), kmeanspp_dev's structure: the distance to the newest center is the Hamming
+        // count, weight = min(weight, (float) d^2), the sum and the pick in double
+        {
+            RowGeom rg{};
+            rg.ld = g.q_ld;
+            rg.nvec = g.q_ld / 16;
+            const int nblocks = kmpp_block_count(n);
+            PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * (size_t)n));
+            PGV_TRY(ctx->km_b.ensure(sizeof(double) * ((size_t)nblocks + (size_t)k)));
+            PGV_TRY(ctx->km_c.ensure(sizeof(int32_t) * (size_t)k));
+            float *weight = ctx->km_a.as<float>(), *raw = weight + n;
+            double *block_sums = ctx->km_b.as<double>(), *draws_dev = block_sums + nblocks;
+            int32_t *picked = ctx->km_c.as<int32_t>();
+            const uint32_t first = r.next_u32() % (uint32_t)n;  // RandomInt() once, then a RandomDouble() per center (:36, :77)
+            PGV_TRY(ctx->h_b.ensure(sizeof(double) * (size_t)k + sizeof(float) * (size_t)n));
+            double *h_draws = ctx->h_b.as<double>();
+            for (int i = 0; i + 1 < k; i++) h_draws[i] = r.next_double();
+            float *h_w = reinterpret_cast<float *>(h_draws + k);
+            for (int j = 0; j < n; j++) h_w[j] = 3.402823466e+38f;  // FLT_MAX (:39-40)
+            PGV_HIP(hipMemcpyAsync(draws_dev, h_draws, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+            PGV_HIP(hipMemcpyAsync(weight, h_w, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+            PGV_HIP(hipMemcpyAsync(centers_dev, static_cast<const char *>(s_dev) + (size_t)first * g.q_ld, (size_t)g.q_ld,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+            const int32_t first_i = (int32_t)first;
+            PGV_HIP(hipMemcpyAsync(picked, &first_i, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+            PGV_HIP(hipStreamSynchronize(ctx->stream));
+            for (int i = 0; i + 1 < k; i++) {
+                const char *center_i = static_cast<const char *>(centers_dev) + (size_t)i * g.q_ld;
+                PGV_TRY(launch_hamming_tiles(ctx, s_dev, rg.nvec, n, center_i, g.q_ld, 1, raw));
+                PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, 2, block_sums));
+                PGV_TRY(launch_kmpp_pick(ctx, rg, s_dev, n, weight, block_sums, draws_dev, i, centers_dev, picked));
+            }
+        }
+        PGV_TRY(ctx->km_g.ensure(sizeof(int32_t) * (size_t)n));
+        int32_t *closest = ctx->km_g.as<int32_t>();
+        PGV_HIP(hipMemsetAsync(closest, 0xff, sizeof(int32_t) * (size_t)n, ctx->stream));  // -1: not assigned yet
+        for (int it = 0; it < max_iterations; it++) {
+            iters = it + 1;
+            PGV_TRY(bit_lloyd_dev(ctx, nbits, g, s_dev, n, centers_dev, k, closest, r, &counts_dev, h_counts, &changes));
+            // stop when an iteration other than the first moves nothing (src/ivfkmeans.c:482-483)
+            if (changes == 0 && it != 0) break;
+        }
+        if (out_closest)
+            PGV_HIP(hipMemcpyAsync(out_closest, closest, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, ctx->stream));
+    }
+    // (CheckCenters, src/ivfkmeans.c:539-547, has nothing to find in bit strings)
+    PGV_TRY(unstage_bit_rows(ctx, centers_dev, k, g.bytes, g.q_ld, out_centers));
+    if (out_iters) *out_iters = iters;
+    return pgv_ctx_sync(ctx);
+}
+
 // --------------------------------------------------------------------- k-means
 
 

@@ -338,6 +338,8 @@ int pgv_kmeans_sharded(pgv_comm *cm, pgv_ops ops, pgv_dtype dtype, int dim, cons
 
 int pgv_search_batch_sharded(pgv_comm *cm, pgv_index *ix, const void *queries, int nq, int probes, int k,
                              float *out_dist, uint64_t *out_tid) {
+    // (a bit index, pgv_index_upload_bits, is refused whatever else is passed: its heads are not merged across ranks)
+    if (ix && ix->nbits > 0) PGV_FAIL(PGV_ERR_ARG, "pgv_search_batch_sharded: not served on a bit index (pgv_index_upload_bits)");
     if (!cm) PGV_FAIL(PGV_ERR_ARG, "pgv_search_batch_sharded: comm is NULL");
     PGV_TRY(check_batch_args(ix, queries, nq, probes, k, out_dist, out_tid, "pgv_search_batch_sharded"));
     if (!ix->tids) PGV_FAIL(PGV_ERR_STATE, "a sharded index needs heap tids (row slots are rank-local)");

@@ -192,9 +192,10 @@ int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool
 
 // The mirror of an index whose list offsets are known: one allocation, host tables, the norms the MFMA paths want.
 // `fill` enqueues (on ctx->stream) whatever brings centers / vectors / tids into the carved arrays.
+// nbits > 0: a bit index (pgv_index_upload_bits) -- rows of bit_row_geom(nbits).ld bytes, no norms, no shadow
 template <typename Fill>
 int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nlists, const std::vector<int64_t> &off,
-                 bool has_tids, Fill fill, pgv_index **out) {
+                 bool has_tids, Fill fill, pgv_index **out, int nbits = 0) {
     const int64_t n = off[nlists];
     pgv_index *ix = new (std::nothrow) pgv_index();
     if (!ix) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
@@ -209,10 +210,11 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
     ix->dim = dim;
     ix->nlists = nlists;
     ix->nrows = n;
-    ix->geom = row_geom(dim, dtype);
+    ix->nbits = nbits;
+    ix->geom = nbits > 0 ? bit_row_geom(nbits) : row_geom(dim, dtype);
     ix->h_offsets = off;
     index_host_tables(ix);
-    const size_t row_bytes = (size_t)ix->geom.ld * elem_size(dtype);
+    const size_t row_bytes = nbits > 0 ? (size_t)ix->geom.ld : (size_t)ix->geom.ld * elem_size(dtype);
 
     auto fail = [&](int rc) {
         pgv_index_free(ix);
@@ -220,7 +222,7 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
     };
     // one allocation for the whole mirror (a single IPC handle exports it): centers | vectors | list_offsets |
     // tids | row_norms | center_norms, each part 256-byte aligned
-    IndexLayout lay = index_layout(nlists, n, row_bytes, has_tids && n > 0, metric == PGV_L2SQ);
+    IndexLayout lay = index_layout(nlists, n, row_bytes, has_tids && n > 0, metric == PGV_L2SQ && nbits == 0);
     if (malloc_exportable(&ix->arena, lay.bytes) != hipSuccess) {
         (void)hipGetLastError();
         set_error("hipMalloc(%zu) for the index mirror failed", lay.bytes);
@@ -248,7 +250,7 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
                                    reinterpret_cast<unsigned *>(ix->center_norms + nlists))) != PGV_OK)
             return fail(rc);
     }
-    if ((rc = shadow_create(ctx, ix)) != PGV_OK) return fail(rc);
+    if (nbits == 0 && (rc = shadow_create(ctx, ix)) != PGV_OK) return fail(rc);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess)
         return fail((set_error("index upload failed: %s", hipGetErrorString(hipGetLastError())), PGV_ERR_DEVICE));
     *out = ix;
@@ -309,6 +311,78 @@ int pgv_index_upload(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, 
                                    is_device_ptr(tids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
         return PGV_OK;
     }, out);
+}
+
+// packed bit rows [cnt x bytes] (host or device) into device rows of `ld` bytes, zero padded
+static int put_bit_rows(pgv_ctx *ctx, void *dst, int ld, const void *src, int bytes, int64_t cnt) {
+    if (cnt == 0) return PGV_OK;
+    const hipMemcpyKind kind = is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (ld == bytes) {
+        PGV_HIP(hipMemcpyAsync(dst, src, (size_t)cnt * (size_t)ld, kind, ctx->stream));
+    } else {
+        PGV_HIP(hipMemsetAsync(dst, 0, (size_t)cnt * (size_t)ld, ctx->stream));
+        PGV_HIP(hipMemcpy2DAsync(dst, (size_t)ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt, kind, ctx->stream));
+    }
+    return PGV_OK;
+}
+
+// `USING ivfflat (col bit_hamming_ops)` (sql/vector.sql:894-899; the bit type info of src/ivfutils.c:411-424): the mirror
+// of pgv_index_upload with packed bit strings for centers and rows.  The element type is recorded as pgv_index::nbits
+int pgv_index_upload_bits(pgv_ctx *ctx, int nbits, int nlists, const void *centers, const int64_t *list_offsets,
+                          const void *rows, const uint64_t *tids, pgv_index **out) {
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_index_upload_bits: ctx/out is NULL");
+    *out = nullptr;
+    // IVFFLAT_MAX_DIM * 32 (src/ivfutils.c:416)
+    if (nbits < 1 || nbits > kIvfMaxBits) PGV_FAIL(PGV_ERR_DIMS, "bit length %d outside 1..%d", nbits, kIvfMaxBits);
+    if (nlists < 1 || nlists > 32768) PGV_FAIL(PGV_ERR_ARG, "lists %d outside 1..32768", nlists);
+    if (!centers || !list_offsets) PGV_FAIL(PGV_ERR_ARG, "centers/list_offsets is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    std::vector<int64_t> off((size_t)nlists + 1);
+    if (is_device_ptr(list_offsets)) {
+        PGV_HIP(hipMemcpy(off.data(), list_offsets, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(off.data(), list_offsets, sizeof(int64_t) * off.size());
+    }
+    if (off[0] != 0) PGV_FAIL(PGV_ERR_ARG, "list_offsets[0] must be 0");
+    for (int l = 0; l < nlists; l++)
+        if (off[l + 1] < off[l]) PGV_FAIL(PGV_ERR_ARG, "list_offsets not ascending at list %d", l);
+    const int64_t n = off[nlists];
+    if (n > 0 && !rows) PGV_FAIL(PGV_ERR_ARG, "rows is NULL");
+    const int bytes = (nbits + 7) / 8;  // VARBITBYTES
+    // (metric / dtype are unused on a bit index; PGV_L1 keeps every L2-only structure away from it)
+    return index_create(ctx, PGV_L1, PGV_F32, nbits, nlists, off, tids != nullptr, [&](pgv_index *ix) -> int {
+        PGV_TRY(put_bit_rows(ctx, ix->centers, ix->geom.ld, centers, bytes, nlists));
+        PGV_TRY(put_bit_rows(ctx, ix->vectors, ix->geom.ld, rows, bytes, n));
+        if (ix->tids)
+            PGV_HIP(hipMemcpyAsync(ix->tids, tids, sizeof(uint64_t) * (size_t)n,
+                                   is_device_ptr(tids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+        return PGV_OK;
+    }, out, nbits);
+}
+
+int pgv_index_nbits(const pgv_index *ix) { return ix ? ix->nbits : -1; }
+
+// the entries that do not serve a bit index (include/pgv_hip.h): refused before anything is launched
+#define PGV_NO_BIT_INDEX(ix, who)                                                                                 \
+    do {                                                                                                          \
+        if ((ix)->nbits > 0) PGV_FAIL(PGV_ERR_ARG, "%s: not served on a bit index (pgv_index_upload_bits)", who); \
+    } while (0)
+
+// the queries of a bit index: [nq x bytes] bit strings into whole register slices of the Hamming kernels
+static int stage_bit_queries(pgv_index *ix, const void *queries, int nq, const void **q_dev, int *q_ld) {
+    const int bytes = (ix->nbits + 7) / 8, slice = bit_topk_slice_bytes();
+    *q_ld = (bytes + slice - 1) / slice * slice;
+    return stage_bit_rows(ix->ctx, queries, nq, bytes, *q_ld, ix->ctx->q_stage, q_dev);
+}
+// ... of a vector / halfvec index or of a bit index
+static int stage_queries(pgv_index *ix, const void *queries, int nq, const void **q_dev) {
+    int q_ld;
+    if (ix->nbits > 0) return stage_bit_queries(ix, queries, nq, q_dev, &q_ld);
+    return stage_rows(ix->ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ix->ctx->q_stage, q_dev);
+}
+static int bit_query_bytes(const pgv_index *ix) {
+    const int bytes = (ix->nbits + 7) / 8, slice = bit_topk_slice_bytes();
+    return (bytes + slice - 1) / slice * slice;
 }
 
 // ------------------------------------------------------------ the build's tuplesort on the device
@@ -540,6 +614,7 @@ int pgv_builder_finish(pgv_builder *b, pgv_index **out_index, int64_t *out_offse
 // for piece i while piece i + 1 is on its way
 int pgv_index_drain(pgv_index *ix, int64_t chunk_rows, pgv_rows_sink sink, void *arg) {
     if (!ix || !sink) PGV_FAIL(PGV_ERR_ARG, "pgv_index_drain: index/sink is NULL");
+    PGV_NO_BIT_INDEX(ix, "pgv_index_drain");
     pgv_ctx *ctx = ix->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     const int64_t n = ix->nrows;
@@ -603,6 +678,7 @@ static void index_drop_lanes(pgv_index *ix);
 
 int pgv_index_set_overlap(pgv_index *ix, int lanes) {
     if (!ix) PGV_FAIL(PGV_ERR_ARG, "pgv_index_set_overlap: index is NULL");
+    PGV_NO_BIT_INDEX(ix, "pgv_index_set_overlap");
     if (lanes < 1 || lanes > 4) PGV_FAIL(PGV_ERR_ARG, "pgv_index_set_overlap: lanes %d outside 1..4", lanes);
     PGV_HIP(hipSetDevice(ix->ctx->device));
     PGV_TRY(pgv_ctx_sync(ix->ctx));
@@ -662,6 +738,7 @@ static constexpr uint64_t kIndexHandleMagic = 0x7067765f69786831ull;  // "pgv_ix
 
 int pgv_index_export(pgv_index *ix, pgv_index_handle *out) {
     if (!ix || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_index_export: index/out is NULL");
+    PGV_NO_BIT_INDEX(ix, "pgv_index_export");
     if (!ix->arena) PGV_FAIL(PGV_ERR_STATE, "pgv_index_export: the index has no device arrays");
     if (ix->imported) PGV_FAIL(PGV_ERR_STATE, "pgv_index_export: export from the process that uploaded the index");
     PGV_HIP(hipSetDevice(ix->ctx->device));
@@ -829,6 +906,16 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
         dist = ctx->sel_b.as<float>();
     }
     int64_t *pos = ctx->sel_a.as<int64_t>();
+    if (ix->nbits > 0) {
+        // GetScanLists (src/ivfscan.c:47-118) under hamming_distance: the dense tile kernel with the centers as rows, then
+        // the maxprobes smallest per query with ties to the lower list id (the reference's strict `<` at :92)
+        ScanTimer timer{ctx};
+        PGV_TRY(timer.begin((double)ix->nlists * nq, (double)ix->nlists * ((nq + 31) / 32), true));
+        PGV_TRY(launch_hamming_tiles(ctx, ix->centers, ix->geom.nvec, ix->nlists, q_dev, bit_query_bytes(ix), nq, mat));
+        PGV_TRY(timer.end());
+        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, maxprobes, dist, pos));
+        return launch_cast_pos_to_i32(ctx, pos, (int64_t)nq * maxprobes, out_lists_dev);
+    }
     // a batch against a few hundred centers or more: the matrix cores.  Inner product: the values are
     // the result.  L2: the expansion picks maxprobes + 16 candidates, their exact distances decide, and a
     // query whose candidates cannot be proven complete is redone exactly (same scheme as the list scan)
@@ -919,7 +1006,7 @@ int pgv_rank_lists(pgv_index *ix, const void *queries, int nq, int maxprobes, in
     pgv_ctx *ctx = ix->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     const void *q_dev;
-    PGV_TRY(stage_rows(ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ctx->q_stage, &q_dev));
+    PGV_TRY(stage_queries(ix, queries, nq, &q_dev));
     OutArg ol, od;
     PGV_TRY(ol.init(out_lists, sizeof(int32_t) * (size_t)nq * maxprobes, ctx->out_stage));
     PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * maxprobes, ctx->out_stage2));
@@ -959,7 +1046,7 @@ int pgv_scan_lists(pgv_index *ix, const void *query, const int32_t *lists, int n
     PGV_TRY(os.init(out_slot, sizeof(int64_t) * (size_t)m, ctx->out_stage2));
 
     // plan on the host: per probed list a run of chunks, all for the one query
-    const int ch = rows_per_task_for(ctx, m, 1);
+    const int ch = ix->nbits > 0 ? hamming_list_rows_per_task() : rows_per_task_for(ctx, m, 1);
     int64_t ntasks = 0;
     for (int p = 0; p < nlists; p++) {
         int64_t len = ix->h_offsets[hl[p] + 1] - ix->h_offsets[hl[p]];
@@ -1007,12 +1094,18 @@ int pgv_scan_lists(pgv_index *ix, const void *query, const int32_t *lists, int n
         PGV_HIP(hipMemsetAsync(od.dev, 0, sizeof(float) * (size_t)m, ctx->stream));
     } else {
         const void *q_dev;
-        PGV_TRY(stage_rows(ctx, query, 1, ix->dim, ix->dtype, ix->geom, ctx->q_stage, &q_dev));
+        PGV_TRY(stage_queries(ix, query, 1, &q_dev));
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin((double)m, (double)m));
-        PGV_TRY(launch_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev,
-                            reinterpret_cast<ScanTask *>(db), reinterpret_cast<int *>(db + tb + pb + ob + lb),
-                            (int)ntasks, reinterpret_cast<ScanPair *>(db + tb), 1, od.as<float>()));
+        if (ix->nbits > 0)  // the batch's kernel with one pair per task
+            PGV_TRY(launch_hamming_lists(ctx, ix->vectors, ix->geom.nvec, q_dev, bit_query_bytes(ix),
+                                         reinterpret_cast<ScanTask *>(db), reinterpret_cast<int *>(db + tb + pb + ob + lb),
+                                         (int)ntasks, reinterpret_cast<ScanPair *>(db + tb), hamming_list_group_size(1.0),
+                                         od.as<float>()));
+        else
+            PGV_TRY(launch_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev,
+                                reinterpret_cast<ScanTask *>(db), reinterpret_cast<int *>(db + tb + pb + ob + lb),
+                                (int)ntasks, reinterpret_cast<ScanPair *>(db + tb), 1, od.as<float>()));
         PGV_TRY(timer.end());
     }
     bool need = true;  // h_a must be consumed before the next call rewrites it
@@ -1035,6 +1128,7 @@ static int scan_turn_end(pgv_ctx *ctx) {
 // What the batched list scan does with nq queries x probes lists and heads of k, decided from the batch's shape before
 // anything is launched: scan_batch_impl follows it, and pgv_search_batch tells the ranking of it ahead of time (`shadow`)
 struct ScanPath {
+    bool bits = false;       // a bit index: always the list-major plan into hamming_list_kernel, nothing else below applies
     bool per_query = false;  // every query scans its own lists: mq_scan_kernel + mq_head_kernel, nothing below applies
     bool use_mfma = false;   // the matrix cores (32 queries per pass)
     bool use_tile = false;   // the tile kernel (16 queries per pass over the rows)
@@ -1048,6 +1142,13 @@ static ScanPath scan_path(const pgv_index *ix, int nq, int probes, int k) {
     // invert to list-major work.  Queries per list on average decides how wide a group is worth.  Lists probed by more
     // than 8 queries go to the tile kernel (16 queries per pass over the rows) when the row shape allows it.
     const double share = (double)nq * probes / (double)ix->nlists;
+    if (ix->nbits > 0) {
+        // integer distances: no per-query mq_* path, no matrix cores, no tile path, no shadow, no exact tail
+        p.bits = true;
+        p.qt = hamming_list_group_size(share);
+        p.rows_per_task = hamming_list_rows_per_task();
+        return p;
+    }
     // Too few queries to share rows between them (every probed list belongs to one query): the list-major plan
     // gains nothing and costs a dozen launches.  Each query scans its own lists (mq_scan_kernel) and selects
     // its own head (mq_head_kernel): two launches, the single-query kernels with one grid row per query.
@@ -1131,7 +1232,10 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
         PGV_TRY(scan_turn_begin(ctx));
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin(0.0, 0.0));  // pairs / rows of this launch are accumulated on the device
-        if (path.shadow)
+        if (path.bits)
+            PGV_TRY(launch_hamming_lists(ctx, ix->vectors, ix->geom.nvec, q_dev, bit_query_bytes(ix), plan.tasks,
+                                         plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, path.qt, seg_vals));
+        else if (path.shadow)
             PGV_TRY(launch_mfma_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->shadow, sb->qcast, plan.tasks,
                                      plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
                                      seg_vals, rows_stream_past_caches(ix->shadow_geom, PGV_F16, ix->nrows), path.qt, sb->qscale));
@@ -1222,7 +1326,7 @@ int pgv_search_batch(pgv_index *ix, const void *queries, int nq, int probes, int
     pgv_ctx *ctx = ix->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     const void *q_dev;
-    PGV_TRY(stage_rows(ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ctx->q_stage, &q_dev));
+    PGV_TRY(stage_queries(ix, queries, nq, &q_dev));
     // GetScanLists for the whole batch
     PGV_TRY(ctx->idx_stage.ensure(sizeof(int32_t) * (size_t)nq * probes));
     int32_t *probe_lists = ctx->idx_stage.as<int32_t>();
@@ -1248,7 +1352,7 @@ int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *pr
                 PGV_FAIL(PGV_ERR_ARG, "probe list id %d out of range 0..%d", probe_lists[i], ix->nlists - 1);
     }
     const void *q_dev, *pl_dev;
-    PGV_TRY(stage_rows(ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ctx->q_stage, &q_dev));
+    PGV_TRY(stage_queries(ix, queries, nq, &q_dev));
     PGV_TRY(stage_flat(ctx, probe_lists, sizeof(int32_t) * (size_t)nq * probes, ctx->idx_stage, &pl_dev));
     return scan_batch_dev(ix, q_dev, nq, static_cast<const int32_t *>(pl_dev), probes, k, out_dist, out_slot,
                           out_tid);
@@ -1258,6 +1362,7 @@ int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *pr
 int pgv_index_shadow_cast(pgv_index *ix, const void *queries, int nq, void *out_qcast, float *out_qscale, float *out_qeps,
                           float *out_cscale, float *out_ceps) {
     if (!ix || !queries || nq < 1) PGV_FAIL(PGV_ERR_ARG, "pgv_index_shadow_cast: index/queries is NULL or nq < 1");
+    PGV_NO_BIT_INDEX(ix, "pgv_index_shadow_cast");
     if (!ix->shadow || !ix->cshadow) PGV_FAIL(PGV_ERR_STATE, "pgv_index_shadow_cast: the index has no fp16 shadow");
     pgv_ctx *ctx = ix->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
@@ -1345,6 +1450,7 @@ static bool query_direct_enabled() {
 int pgv_query_begin(pgv_index *ix, pgv_query **out) {
     if (!ix || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_query_begin: index/out is NULL");
     *out = nullptr;
+    PGV_NO_BIT_INDEX(ix, "pgv_query_begin");
     pgv_ctx *ctx = ix->ctx;
     PGV_HIP(hipSetDevice(ctx->device));
     pgv_query *q = new (std::nothrow) pgv_query();

@@ -63,6 +63,7 @@ bool is_device_ptr(const void *p);
 constexpr int kVecBytes = 16;  // every row is padded to whole 16-byte vectors in HBM
 
 constexpr int kHnswMaxBits = 64000;  // bit rows of an HNSW mirror: HNSW_MAX_DIM * 32 (src/hnswutils.c:1414)
+constexpr int kIvfMaxBits = 64000;   // ... of an IVFFlat mirror: IVFFLAT_MAX_DIM * 32 (src/ivfutils.c:416)
 
 inline int elem_size(pgv_dtype t) { return t == PGV_F32 ? 4 : 2; }
 // padded row length in elements
@@ -188,6 +189,10 @@ struct pgv_index {
     pgv_metric metric = PGV_L2SQ;
     pgv_dtype dtype = PGV_F32;
     int dim = 0;
+    // > 0: a mirror of `USING ivfflat (col bit_hamming_ops)` (pgv_index_upload_bits).  Its element type is not a pgv_dtype:
+    // centers and rows are nbits bits in geom.nvec 16-byte vectors (geom.ld BYTES), scored by xor + popcount; metric and
+    // dtype are unused (dim = nbits), and there are no norms and no shadow
+    int nbits = 0;
     int nlists = 0;
     int64_t nrows = 0;
     pgv::RowGeom geom{};
@@ -478,6 +483,24 @@ int launch_bit_distance(pgv_ctx *ctx, int mode, const RowGeom &g, const void *ro
 int bit_topk_slice_bytes();
 int launch_hamming_tiles(pgv_ctx *ctx, const void *rows, int nvec, int64_t n, const void *queries, int qbytes, int nq,
                          float *out);
+// the list scan of a bit index (pgv_index::nbits): the plan of launch_plan_batch with 256 rows per task and qt queries per
+// group (hamming_list_group_size), the same rows and queries as launch_hamming_tiles; out[pair.out_rel + row]
+int hamming_list_group_size(double queries_per_list);
+int hamming_list_rows_per_task();
+int launch_hamming_lists(pgv_ctx *ctx, const void *rows, int nvec, const void *queries, int qbytes, const ScanTask *tasks,
+                         const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt, float *out);
+// the bit k-means' build side.  launch_bit_closest: row j of a chunk's distance matrix mat[j * k + c] (launch_hamming_tiles
+// with the samples as queries) and its first minimum (best_val / best_pos, launch_topk_segments with k = 1) -> closest_io[j]:
+// sticky and closest_io[j] >= 0: the current center unless best_val is strictly smaller; else best_pos.  counts[new] += 1,
+// *changes += (new != old), out_dist[j] = the distance to the result (each may be null)
+int launch_bit_closest(pgv_ctx *ctx, const float *mat, int k, const float *best_val, const int64_t *best_pos, int n,
+                       bool sticky, int32_t *closest_io, float *out_dist, int32_t *counts, unsigned long long *changes);
+// sums[c * nbits + i] += 1 per sample of center c with bit i set (BitSumCenter, src/ivfutils.c:363-370); sums start zero
+int launch_bit_sums(pgv_ctx *ctx, const void *samples, int ld, int nbits, int n, const int32_t *closest, int32_t *sums);
+// BitUpdateCenter (src/ivfutils.c:325-339) over sums / counts; a cluster with refill_row[c] >= 0 takes that packed row of
+// `refill` [.. x (nbits + 7) / 8] instead.  centers: [k x ld] bytes, zero padded
+int launch_bit_centers(pgv_ctx *ctx, const int32_t *sums, const int32_t *counts, int k, int nbits, int ld,
+                       const int32_t *refill_row, const uint8_t *refill, void *centers);
 // rows [n x dim] tightly packed -> out_bits [n x (dim + 7) / 8], bit i = x[i] > 0, first element in the top bit
 int launch_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *rows, int64_t n, void *out_bits);
 // pgv_rerank around launch_score_gather and launch_topk_segments: cand [nq x kc] -> (slot, query_of) of the pairs
@@ -712,6 +735,7 @@ int launch_cast_pos_to_i32(pgv_ctx *ctx, const int64_t *pos, int64_t n, int32_t 
 
 // kernels_kmeans.hip
 int kmpp_block_count(int n);
+// spherical: 0 raw = L2 squared, 1 raw = negative inner product, 2 raw = the distance itself (Hamming)
 int launch_kmpp_update(pgv_ctx *ctx, const float *raw, float *weight, int n, int spherical,
                        double *block_sums);
 int launch_kmpp_pick(pgv_ctx *ctx, const RowGeom &g, const void *samples, int n,
