@@ -341,15 +341,17 @@ __global__ void bit_centers_kernel(const int32_t *__restrict__ sums, const int32
 
 int bit_topk_slice_bytes() { return kBitSliceVecs * (int)sizeof(Raw16); }
 
-int launch_hamming_tiles(pgv_ctx *ctx, const void *rows, int nvec, int64_t n, const void *queries, int qbytes, int nq,
-                         float *out) {
+int launch_hamming_tiles(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, int nq, float *out) {
+    const int64_t n = v.n;
     if (n <= 0 || nq <= 0) return PGV_OK;
+    if (!v.bits() || qbytes < bit_query_bytes(v.geom.ld * 8))
+        PGV_FAIL(PGV_ERR_ARG, "bit scan: bit rows, queries in whole slices");
     const int nqt = (nq + kBitQueries - 1) / kBitQueries;
     const int64_t grid = (n + kBitThreads - 1) / kBitThreads * nqt;
     if (grid > 0x7fffffff) PGV_FAIL(PGV_ERR_ARG, "bit scan: too many tiles");
     hipLaunchKernelGGL(hamming_tile_kernel, dim3((unsigned)grid), dim3(kBitThreads), 0, ctx->stream,
-                       static_cast<const char *>(rows), static_cast<const uint32_t *>(queries), n, nq, nvec, qbytes / 4, nqt,
-                       out);
+                       static_cast<const char *>(v.rows), static_cast<const uint32_t *>(queries), n, nq, v.geom.nvec, qbytes / 4,
+                       nqt, out);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -360,8 +362,7 @@ int hamming_list_group_size(double queries_per_list) { return queries_per_list <
 int hamming_list_rows_per_task() { return kBitThreads; }
 
 template <int QT>
-static int launch_hamming_lists_t(pgv_ctx *ctx, const void *rows, int nvec, const void *queries, int qbytes,
-                                  const ScanTask *tasks, const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs,
+static int launch_hamming_lists_t(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const ScanWork &w,
                                   float *out) {
     PGV_TRY(ctx->counters.ensure(256));
     if (!ctx->counters_clean) {
@@ -371,20 +372,23 @@ static int launch_hamming_lists_t(pgv_ctx *ctx, const void *rows, int nvec, cons
     int *counter = ctx->counters.as<int>() + 10;  // words 10, 11 as launch_scan: claimed tasks, workgroups done
     // 36 KB of LDS a workgroup: four of them share a CU
     int grid = ctx->num_cus * 4;
-    if (grid > ntasks_bound) grid = ntasks_bound;
-    hipLaunchKernelGGL(hamming_list_kernel<QT>, dim3(grid), dim3(kBitThreads), 0, ctx->stream, static_cast<const char *>(rows),
-                       static_cast<const uint32_t *>(queries), tasks, ntasks_dev, counter, pairs, out, nvec, qbytes / 4);
+    if (grid > w.ntasks_bound) grid = w.ntasks_bound;
+    hipLaunchKernelGGL(hamming_list_kernel<QT>, dim3(grid), dim3(kBitThreads), 0, ctx->stream,
+                       static_cast<const char *>(v.rows), static_cast<const uint32_t *>(queries), w.tasks, w.ntasks_dev, counter,
+                       w.pairs, out, v.geom.nvec, qbytes / 4);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-int launch_hamming_lists(pgv_ctx *ctx, const void *rows, int nvec, const void *queries, int qbytes, const ScanTask *tasks,
-                         const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt, float *out) {
-    if (ntasks_bound <= 0) return PGV_OK;
+int launch_hamming_lists(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const ScanWork &w, int qt,
+                         float *out) {
+    if (w.ntasks_bound <= 0) return PGV_OK;
+    if (!v.bits() || qbytes < bit_query_bytes(v.geom.ld * 8))
+        PGV_FAIL(PGV_ERR_ARG, "bit list scan: bit rows, queries in whole slices");
     switch (qt) {
-        case 8: return launch_hamming_lists_t<8>(ctx, rows, nvec, queries, qbytes, tasks, ntasks_dev, ntasks_bound, pairs, out);
-        case 16: return launch_hamming_lists_t<16>(ctx, rows, nvec, queries, qbytes, tasks, ntasks_dev, ntasks_bound, pairs, out);
-        case 32: return launch_hamming_lists_t<32>(ctx, rows, nvec, queries, qbytes, tasks, ntasks_dev, ntasks_bound, pairs, out);
+        case 8: return launch_hamming_lists_t<8>(ctx, v, queries, qbytes, w, out);
+        case 16: return launch_hamming_lists_t<16>(ctx, v, queries, qbytes, w, out);
+        case 32: return launch_hamming_lists_t<32>(ctx, v, queries, qbytes, w, out);
     }
     PGV_FAIL(PGV_ERR_ARG, "bit list scan: unsupported query group size %d", qt);
 }

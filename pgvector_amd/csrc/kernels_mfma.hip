@@ -815,7 +815,8 @@ int launch_mfma_t(pgv_ctx *ctx, const RowGeom &g, const void *rows, int64_t n, c
         // it from the operands it reads anyway; here 1 / nparts of the workgroups would have to, and wait for it)
         unsigned *max_bits = reinterpret_cast<unsigned *>(part_x2 + n);
         PGV_HIP(hipMemsetAsync(max_bits, 0, sizeof(unsigned), ctx->stream));
-        PGV_TRY(launch_row_norms(ctx, sizeof(T) == 4 ? PGV_F32 : PGV_F16, g, rows, n, part_x2, max_bits));
+        PGV_TRY(launch_row_norms(ctx, RowsView{rows, n, g, sizeof(T) == 4 ? RowKind::F32 : RowKind::F16, PGV_L2SQ}, part_x2,
+                                 max_bits));
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, static_cast<const char *>(rows), n,
                        static_cast<const char *>(centers), k, g.nvec, bias, static_cast<const char *>(ctx->zeros.p),
@@ -1339,25 +1340,28 @@ int scan_chain_length(const RowGeom &g, pgv_dtype dtype, bool wide) {
 // ... or twice that, when the lists of a batch are probed by more than ~12 queries on average (the 64-query form)
 int mfma_scan_queries_per_task_wide() { return 2 * kScanQueries; }
 
-int launch_row_norms(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n, float *out,
-                     unsigned *max_bits) {
-    if (n <= 0) return PGV_OK;
-    const dim3 grid((unsigned)((n + 3) / 4));
-    if (dtype == PGV_F32)
-        hipLaunchKernelGGL(row_norms_kernel<float>, grid, dim3(256), 0, ctx->stream, static_cast<const char *>(rows), n,
-                           g.nvec, out, max_bits);
+int launch_row_norms(pgv_ctx *ctx, const RowsView &v, float *out, unsigned *max_bits) {
+    if (v.n <= 0) return PGV_OK;
+    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "row norms: fp32 / fp16 rows only");
+    const dim3 grid((unsigned)((v.n + 3) / 4));
+    if (v.kind == RowKind::F32)
+        hipLaunchKernelGGL(row_norms_kernel<float>, grid, dim3(256), 0, ctx->stream, static_cast<const char *>(v.rows), v.n,
+                           v.geom.nvec, out, max_bits);
     else
-        hipLaunchKernelGGL(row_norms_kernel<__half>, grid, dim3(256), 0, ctx->stream, static_cast<const char *>(rows), n,
-                           g.nvec, out, max_bits);
+        hipLaunchKernelGGL(row_norms_kernel<__half>, grid, dim3(256), 0, ctx->stream, static_cast<const char *>(v.rows), v.n,
+                           v.geom.nvec, out, max_bits);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,
-                     const void *queries, const ScanTask *tasks, const int *ntasks_dev, int ntasks_bound,
-                     const ScanPair *pairs, const float *row_norms, const float *query_norms, float *out,
-                     bool stream_rows, int queries_per_task, const float *shadow_scale) {
+int launch_mfma_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, const float *row_norms,
+                     const float *query_norms, float *out, bool stream_rows, int queries_per_task,
+                     const float *shadow_scale) {
+    const int ntasks_bound = w.ntasks_bound;
+    const pgv_metric metric = v.metric;
+    const pgv_dtype dtype = v.dtype();
     if (ntasks_bound <= 0) return PGV_OK;
+    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "mfma scan: fp32 / fp16 rows only");
     if (queries_per_task != 32 && queries_per_task != 64) PGV_FAIL(PGV_ERR_ARG, "mfma scan: %d queries per task", queries_per_task);
     if (metric != PGV_L2SQ && metric != PGV_NEG_IP) PGV_FAIL(PGV_ERR_ARG, "mfma scan: L2 / inner product only");
     if (!ctx->zeros.p) {
@@ -1381,8 +1385,9 @@ int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const Row
     const bool deep = queries_per_task == 32 && deep_env != 0 && ntasks_bound <= 2 * ctx->num_cus;
 #define PGV_MSCAN_QS(T, M, NT, Q, S, SH)                                                                                  \
     hipLaunchKernelGGL((mfma_scan_kernel<T, M, kScanWaves, NT, Q, S, SH>), dim3(grid), dim3(kScanWaves * 64), 0,          \
-                       ctx->stream, static_cast<const char *>(rows), static_cast<const char *>(queries), tasks, ntasks_dev, \
-                       counter, pairs, row_norms, g.nvec, static_cast<const char *>(ctx->zeros.p), out, shadow_scale)
+                       ctx->stream, static_cast<const char *>(v.rows), static_cast<const char *>(queries), w.tasks,         \
+                       w.ntasks_dev, counter, w.pairs, row_norms, v.geom.nvec, static_cast<const char *>(ctx->zeros.p), out, \
+                       shadow_scale)
 #define PGV_MSCAN_Q(T, M, NT, Q, S) PGV_MSCAN_QS(T, M, NT, Q, S, false)
 #define PGV_MSCAN_NT(T, M, NT)                   \
     do {                                         \

@@ -775,12 +775,15 @@ int launch_query_iota(pgv_ctx *ctx, int32_t *out, int n) {
 
 // one query against n contiguous rows, out[j] = distance to row j: the streaming form of query_rank_kernel (whole
 // rows in flight per wavefront, the query in registers) -- a k-means++ round over the samples, pgv_distance_batch
-int launch_one_query_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows, int n,
-                          const void *q_dev, float *out) {
-    if (n <= 0) return PGV_OK;
+int launch_one_query_rows(pgv_ctx *ctx, const RowsView &v, const void *q_dev, float *out) {
+    if (v.n <= 0) return PGV_OK;
+    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "one query over rows: fp32 / fp16 rows only");
+    const RowGeom &g = v.geom;
+    const void *rows = v.rows;
+    const int n = (int)v.n;
     int per, grid;
     run_geometry(ctx, g, n, &per, &grid);
-    return dispatch_metric(metric, dtype, [&](auto *tp, auto mc) {
+    return dispatch_metric(v.metric, v.dtype(), [&](auto *tp, auto mc) {
         using T = std::remove_pointer_t<decltype(tp)>;
         constexpr int M = decltype(mc)::value;
         return dispatch_nch<T, M>(g, [&](auto nc) {

@@ -431,13 +431,11 @@ int scan_group_size(const RowGeom &g, pgv_dtype, int wanted) {
     return qt;
 }
 
-int launch_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-                const void *rows, const void *queries, const ScanTask *tasks,
-                const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt,
-                float *out) {
-    return dispatch_metric(metric, dtype, [&](auto *tp, auto mc) {
-        return launch_scan_m<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, g, rows, queries, tasks, ntasks_dev,
-                                                                                       ntasks_bound, pairs, qt, out);
+int launch_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, int qt, float *out) {
+    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "scan: fp32 / fp16 rows only");
+    return dispatch_metric(v.metric, v.dtype(), [&](auto *tp, auto mc) {
+        return launch_scan_m<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(
+            ctx, v.geom, v.rows, queries, w.tasks, w.ntasks_dev, w.ntasks_bound, w.pairs, qt, out);
     });
 }
 

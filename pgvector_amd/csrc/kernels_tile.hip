@@ -264,15 +264,13 @@ int tile_scan_tile_rows(const RowGeom &g) {
     return tr;
 }
 
-int launch_tile_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-                     const void *rows, const void *queries, const ScanTask *tasks,
-                     const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, float *out) {
-    if (!tile_scan_supported(g)) PGV_FAIL(PGV_ERR_ARG, "tile scan: row shape not supported");
-    const int nch = g.nvec / kWave;
-    const int tr = tile_scan_tile_rows(g);
-    return dispatch_metric(metric, dtype, [&](auto *tp, auto mc) {
-        return launch_tile_n<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, nch, rows, queries, tasks, ntasks_dev,
-                                                                                       ntasks_bound, pairs, tr, out);
+int launch_tile_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, float *out) {
+    if (v.bits() || !tile_scan_supported(v.geom)) PGV_FAIL(PGV_ERR_ARG, "tile scan: row shape not supported");
+    const int nch = v.geom.nvec / kWave;
+    const int tr = tile_scan_tile_rows(v.geom);
+    return dispatch_metric(v.metric, v.dtype(), [&](auto *tp, auto mc) {
+        return launch_tile_n<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(
+            ctx, nch, v.rows, queries, w.tasks, w.ntasks_dev, w.ntasks_bound, w.pairs, tr, out);
     });
 }
 

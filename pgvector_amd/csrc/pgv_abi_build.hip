@@ -71,7 +71,7 @@ int pgv_distance_batch(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim
     PGV_TRY(stage_rows(ctx, rows, n, dim, dtype, g, ctx->rows_stage, &r_dev));
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)n, ctx->out_stage));
-    PGV_TRY(dense_scan(ctx, metric, dtype, g, r_dev, n, q_dev, 1, 0, od.as<float>()));
+    PGV_TRY(dense_scan(ctx, RowsView{r_dev, n, g, row_kind(dtype), metric}, q_dev, 1, 0, od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -94,10 +94,11 @@ int pgv_exact_topk(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, co
     if (!queries || (n > 0 && !rows)) PGV_FAIL(PGV_ERR_ARG, "pgv_exact_topk: queries/rows is NULL");
     PGV_HIP(hipSetDevice(ctx->device));
     const RowGeom g = row_geom(dim, dtype);
-    const size_t row_bytes = (size_t)g.ld * elem_size(dtype);
     const void *q_dev, *r_dev = nullptr;
     PGV_TRY(stage_rows(ctx, queries, nq, dim, dtype, g, ctx->q_stage, &q_dev));
     if (n > 0) PGV_TRY(stage_rows(ctx, rows, n, dim, dtype, g, ctx->rows_stage, &r_dev));
+    const RowsView rv{r_dev, n, g, row_kind(dtype), metric};
+    const size_t row_bytes = rv.row_bytes();
     OutArg od, oi;
     PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
     PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
@@ -121,7 +122,7 @@ int pgv_exact_topk(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, co
         PGV_TRY(ctx->xt_norms.ensure(sizeof(float) * ((size_t)n + 1)));
         norms = ctx->xt_norms.as<float>();
         PGV_HIP(hipMemsetAsync(norms + n, 0, sizeof(float), ctx->stream));
-        PGV_TRY(launch_row_norms(ctx, dtype, g, r_dev, n, norms, reinterpret_cast<unsigned *>(norms + n)));
+        PGV_TRY(launch_row_norms(ctx, rv, norms, reinterpret_cast<unsigned *>(norms + n)));
     }
     for (int q0 = 0; q0 < nq; q0 += chunk) {
         const int cn = std::min(chunk, nq - q0);
@@ -151,13 +152,13 @@ int pgv_exact_topk(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, co
             if (dense128)
                 PGV_TRY(launch_mfma_dense(ctx, metric, dtype, g, r_dev, n, qp, cn, norms, mat, n));
             else
-                PGV_TRY(dense_scan(ctx, metric, dtype, g, r_dev, n, qp, cn, n, mat, true, norms, nullptr));
+                PGV_TRY(dense_scan(ctx, rv, qp, cn, n, mat, true, norms, nullptr));
             PGV_TRY(launch_exact_tail(ctx, tail, ctx->ms_b));
         } else {
             if (dense128)
                 PGV_TRY(launch_mfma_dense(ctx, metric, dtype, g, r_dev, n, qp, cn, nullptr, mat, n));
             else
-                PGV_TRY(dense_scan(ctx, metric, dtype, g, r_dev, n, qp, cn, n, mat, mfma, nullptr, nullptr));
+                PGV_TRY(dense_scan(ctx, rv, qp, cn, n, mat, mfma, nullptr, nullptr));
             PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, cd, ci));
         }
     }
@@ -214,14 +215,29 @@ int pgv_bit_distance_batch(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const
         while (g.lpr_log2 > 0 && (1 << (g.lpr_log2 - 1)) >= g.nvec) g.lpr_log2--;
         g.nchunks = (g.nvec + (1 << g.lpr_log2) - 1) >> g.lpr_log2;
         const void *q_dev, *r_dev;
-        PGV_TRY(stage_bit_rows(ctx, query, 1, bytes, g.ld, ctx->q_stage, &q_dev));
-        PGV_TRY(stage_bit_rows(ctx, rows, n, bytes, g.ld, ctx->rows_stage, &r_dev));
+        PGV_TRY(stage_rows(ctx, query, 1, bytes, g.ld, ctx->q_stage, &q_dev));
+        PGV_TRY(stage_rows(ctx, rows, n, bytes, g.ld, ctx->rows_stage, &r_dev));
         PGV_TRY(launch_bit_distance(ctx, metric == PGV_BIT_HAMMING ? 0 : 1, g, r_dev, q_dev, n, od.as<double>()));
     }
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
 }
+
+namespace {
+struct BitGeom {
+    int bytes, row_ld, q_ld;  // VARBITBYTES | padded to 16-byte vectors | padded to the kernels' register slices
+};
+BitGeom bit_geom(int nbits) {
+    BitGeom g;
+    g.bytes = (nbits + 7) / 8;
+    g.row_ld = (g.bytes + 15) / 16 * 16;
+    g.q_ld = bit_query_bytes(nbits);
+    return g;
+}
+// staged bit rows [n x ld bytes] (ld: row_ld or q_ld) as the Hamming kernels take them
+RowsView bit_rows(const void *rows, int64_t n, int ld) { return {rows, n, bit_row_geom(ld * 8), RowKind::Bits, PGV_L1}; }
+}  // namespace
 
 // `ORDER BY b <~> $1 LIMIT k` without an index for a batch of queries: pgv_exact_topk's structure over packed bits.  The
 // scan (hamming_tile_kernel, kernels_bit.hip) fills the chunk's distance matrix mat[q * n + row] with the integer counts
@@ -238,13 +254,12 @@ int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const voi
     PGV_HIP(hipSetDevice(ctx->device));
     const int bytes = (nbits + 7) / 8;  // VARBITBYTES
     // rows in whole 16-byte vectors like pgv_bit_distance_batch's, queries in whole register slices of the scan kernel
-    const int row_ld = (bytes + 15) / 16 * 16;
-    const int slice = bit_topk_slice_bytes();
-    const int q_ld = (bytes + slice - 1) / slice * slice;
+    const BitGeom g = bit_geom(nbits);
+    const int q_ld = g.q_ld;
     const void *q_dev = nullptr, *r_dev = nullptr;
     if (bytes > 0 && n > 0) {
-        PGV_TRY(stage_bit_rows(ctx, queries, nq, bytes, q_ld, ctx->q_stage, &q_dev));
-        PGV_TRY(stage_bit_rows(ctx, rows, n, bytes, row_ld, ctx->rows_stage, &r_dev));
+        PGV_TRY(stage_rows(ctx, queries, nq, bytes, q_ld, ctx->q_stage, &q_dev));
+        PGV_TRY(stage_rows(ctx, rows, n, bytes, g.row_ld, ctx->rows_stage, &r_dev));
     }
     OutArg od, oi;
     PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
@@ -263,8 +278,8 @@ int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const voi
         } else if (n > 0) {
             ScanTimer timer{ctx};
             PGV_TRY(timer.begin((double)n * cn, (double)n * ((cn + 31) / 32), true));
-            PGV_TRY(launch_hamming_tiles(ctx, r_dev, row_ld / 16, n, static_cast<const char *>(q_dev) + (size_t)q0 * q_ld, q_ld,
-                                         cn, mat));
+            PGV_TRY(launch_hamming_tiles(ctx, bit_rows(r_dev, n, g.row_ld), static_cast<const char *>(q_dev) + (size_t)q0 * q_ld,
+                                         q_ld, cn, mat));
             PGV_TRY(timer.end());
         }
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, od.as<float>() + (size_t)q0 * k,
@@ -350,27 +365,17 @@ int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const 
 // center) and bit_closest_kernel decides.  During k-means the centers live at the samples' stride as well, so that a
 // center is a row of the assignment, the query of a k-means++ round and the target of launch_kmpp_pick's row copy.
 namespace {
-struct BitGeom {
-    int bytes, row_ld, q_ld;  // VARBITBYTES | padded to 16-byte vectors | padded to the kernels' register slices
-};
-BitGeom bit_geom(int nbits) {
-    BitGeom g;
-    g.bytes = (nbits + 7) / 8;
-    g.row_ld = (g.bytes + 15) / 16 * 16;
-    const int slice = bit_topk_slice_bytes();
-    g.q_ld = (g.bytes + slice - 1) / slice * slice;
-    return g;
-}
 int check_bits(int nbits, const char *who) {
     // IVFFLAT_MAX_DIM * 32 (src/ivfutils.c:416)
     if (nbits < 1 || nbits > kIvfMaxBits) PGV_FAIL(PGV_ERR_DIMS, "%s: bit length %d outside 1..%d", who, nbits, kIvfMaxBits);
     return PGV_OK;
 }
 
-// samples [n x q_ld] (device, staged) to their centers [k x c_ld] (device, staged): closest_io / out_dist / counts /
+// samples [n x q_ld] (device, staged) to their centers (device, staged; bit_rows): closest_io / out_dist / counts /
 // changes as launch_bit_closest takes them (device).  The matrix stays at or under 2^30 floats per chunk of samples
-int bit_closest_dev(pgv_ctx *ctx, const void *s_dev, int q_ld, int64_t n, const void *c_dev, int c_ld, int k, bool sticky,
+int bit_closest_dev(pgv_ctx *ctx, const void *s_dev, int q_ld, int64_t n, const RowsView &centers, bool sticky,
                     int32_t *closest_io, float *out_dist, int32_t *counts, unsigned long long *changes) {
+    const int k = (int)centers.n;
     int64_t chunk = std::min<int64_t>(n, std::max<int64_t>(1, ((int64_t)1 << 30) / k));
     if (chunk >= 32) chunk = chunk / 32 * 32;
     PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * std::max<size_t>((size_t)chunk * (size_t)k, 4)));
@@ -382,8 +387,7 @@ int bit_closest_dev(pgv_ctx *ctx, const void *s_dev, int q_ld, int64_t n, const 
         const int cn = (int)std::min<int64_t>(chunk, n - j0);
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin((double)cn * k, (double)k * ((cn + 31) / 32), true));
-        PGV_TRY(launch_hamming_tiles(ctx, c_dev, c_ld / 16, k, static_cast<const char *>(s_dev) + (size_t)j0 * q_ld, q_ld, cn,
-                                     mat));
+        PGV_TRY(launch_hamming_tiles(ctx, centers, static_cast<const char *>(s_dev) + (size_t)j0 * q_ld, q_ld, cn, mat));
         PGV_TRY(timer.end());
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, k, 1, best_val, best_pos));
         PGV_TRY(launch_bit_closest(ctx, mat, k, best_val, best_pos, cn, sticky, closest_io + j0, out_dist ? out_dist + j0 : nullptr,
@@ -441,7 +445,8 @@ int bit_lloyd_dev(pgv_ctx *ctx, int nbits, const BitGeom &g, const void *s_dev, 
     int32_t *counts = ctx->km_f.as<int32_t>();
     unsigned long long *changes = reinterpret_cast<unsigned long long *>(ctx->km_f.as<char>() + cb);
     PGV_HIP(hipMemsetAsync(counts, 0, cb + sizeof(unsigned long long), ctx->stream));
-    if (n > 0) PGV_TRY(bit_closest_dev(ctx, s_dev, g.q_ld, n, centers_dev, g.q_ld, k, true, closest_dev, nullptr, counts, changes));
+    if (n > 0) PGV_TRY(bit_closest_dev(ctx, s_dev, g.q_ld, n, bit_rows(centers_dev, k, g.q_ld), true, closest_dev, nullptr, counts,
+                                       changes));
     h_counts.assign((size_t)k, 0);
     PGV_HIP(hipMemcpyAsync(h_counts.data(), counts, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, ctx->stream));
     PGV_HIP(hipMemcpyAsync(out_changes, changes, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -452,7 +457,7 @@ int bit_lloyd_dev(pgv_ctx *ctx, int nbits, const BitGeom &g, const void *s_dev, 
 }
 
 // packed device rows [cnt x ld] -> the caller's [cnt x bytes] (host or device)
-int unstage_bit_rows(pgv_ctx *ctx, const void *src_dev, int64_t cnt, int bytes, int ld, void *dst) {
+int unstage_rows(pgv_ctx *ctx, const void *src_dev, int64_t cnt, int bytes, int ld, void *dst) {
     if (cnt == 0) return PGV_OK;
     const bool dev = is_device_ptr(dst);
     PGV_HIP(hipMemcpy2DAsync(dst, (size_t)bytes, src_dev, (size_t)ld, (size_t)bytes, (size_t)cnt,
@@ -463,10 +468,7 @@ int unstage_bit_rows(pgv_ctx *ctx, const void *src_dev, int64_t cnt, int bytes, 
 // a staging that is a copy even of device rows (the centers of a k-means are rewritten in place)
 int copy_bit_rows(pgv_ctx *ctx, const void *src, int64_t cnt, int bytes, int ld, DBuf &scratch) {
     PGV_TRY(scratch.ensure(std::max<size_t>((size_t)cnt * ld, 16)));
-    PGV_HIP(hipMemsetAsync(scratch.p, 0, (size_t)cnt * ld, ctx->stream));
-    if (cnt > 0)
-        PGV_HIP(hipMemcpy2DAsync(scratch.p, (size_t)ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt,
-                                 is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    PGV_TRY(put_padded_rows(ctx->stream, scratch.p, ld, src, bytes, cnt));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
     return PGV_OK;
 }
@@ -485,7 +487,7 @@ int pgv_bit_assign(pgv_ctx *ctx, int nbits, const void *centers, int k, const vo
     PGV_HIP(hipSetDevice(ctx->device));
     const BitGeom g = bit_geom(nbits);
     const void *c_dev;
-    PGV_TRY(stage_bit_rows(ctx, centers, k, g.bytes, g.row_ld, ctx->centers_stage, &c_dev));
+    PGV_TRY(stage_rows(ctx, centers, k, g.bytes, g.row_ld, ctx->centers_stage, &c_dev));
     const bool out_dev = is_device_ptr(out_list), dist_dev = out_dist && is_device_ptr(out_dist);
     // rows are staged in slabs, like pgv_assign's host rows
     const int64_t slab = (int64_t)1 << 18;
@@ -493,7 +495,7 @@ int pgv_bit_assign(pgv_ctx *ctx, int nbits, const void *centers, int k, const vo
     for (int64_t r0 = 0; r0 < n; r0 += slab) {
         const int64_t cnt = std::min(slab, n - r0);
         const void *r_dev;
-        PGV_TRY(stage_bit_rows(ctx, static_cast<const char *>(rows) + (size_t)r0 * g.bytes, cnt, g.bytes, g.q_ld, ctx->rows_stage,
+        PGV_TRY(stage_rows(ctx, static_cast<const char *>(rows) + (size_t)r0 * g.bytes, cnt, g.bytes, g.q_ld, ctx->rows_stage,
                                &r_dev));
         int32_t *idx = out_list + r0;
         float *val = out_dist ? out_dist + r0 : nullptr;
@@ -505,7 +507,7 @@ int pgv_bit_assign(pgv_ctx *ctx, int nbits, const void *centers, int k, const vo
             PGV_TRY(ctx->out_stage2.ensure(sizeof(float) * (size_t)cnt));
             val = ctx->out_stage2.as<float>();
         }
-        PGV_TRY(bit_closest_dev(ctx, r_dev, g.q_ld, cnt, c_dev, g.row_ld, k, false, idx, val, nullptr, nullptr));
+        PGV_TRY(bit_closest_dev(ctx, r_dev, g.q_ld, cnt, bit_rows(c_dev, k, g.row_ld), false, idx, val, nullptr, nullptr));
         if (!out_dev) {
             PGV_HIP(hipMemcpyAsync(out_list + r0, idx, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
             need = true;
@@ -529,7 +531,7 @@ int pgv_bit_lloyd_step(pgv_ctx *ctx, int nbits, const void *samples, int n, cons
     PGV_HIP(hipSetDevice(ctx->device));
     const BitGeom g = bit_geom(nbits);
     const void *s_dev = nullptr;
-    if (n > 0) PGV_TRY(stage_bit_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
+    if (n > 0) PGV_TRY(stage_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
     PGV_TRY(copy_bit_rows(ctx, centers, k, g.bytes, g.q_ld, ctx->centers_stage));
     int32_t *closest_dev = io_closest;
     const bool closest_is_dev = is_device_ptr(io_closest);
@@ -547,7 +549,7 @@ int pgv_bit_lloyd_step(pgv_ctx *ctx, int nbits, const void *samples, int n, cons
     std::vector<int32_t> h_counts;
     unsigned long long changes = 0;
     PGV_TRY(bit_lloyd_dev(ctx, nbits, g, s_dev, n, ctx->centers_stage.p, k, closest_dev, r, &counts_dev, h_counts, &changes));
-    PGV_TRY(unstage_bit_rows(ctx, ctx->centers_stage.p, k, g.bytes, g.q_ld, out_centers));
+    PGV_TRY(unstage_rows(ctx, ctx->centers_stage.p, k, g.bytes, g.q_ld, out_centers));
     const int64_t ch = (int64_t)changes;
     if (is_device_ptr(out_counts))
         PGV_HIP(hipMemcpyAsync(out_counts, h_counts.data(), sizeof(int32_t) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
@@ -586,13 +588,11 @@ int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, i
         PGV_TRY(bit_lloyd_dev(ctx, nbits, g, nullptr, 0, centers_dev, k, nullptr, r, &counts_dev, h_counts, &changes));
     } else {
         const void *s_dev;
-        PGV_TRY(stage_bit_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
+        PGV_TRY(stage_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
         // InitCenters (src/ivfkmeans.c:23-91), kmeanspp_dev's structure: the distance to the newest center is the Hamming
         // count, weight = min(weight, (float) d^2), the sum and the pick in double
         {
-            RowGeom rg{};
-            rg.ld = g.q_ld;
-            rg.nvec = g.q_ld / 16;
+            const RowsView sv = bit_rows(s_dev, n, g.q_ld);
             const int nblocks = kmpp_block_count(n);
             PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * (size_t)n));
             PGV_TRY(ctx->km_b.ensure(sizeof(double) * ((size_t)nblocks + (size_t)k)));
@@ -615,9 +615,9 @@ int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, i
             PGV_HIP(hipStreamSynchronize(ctx->stream));
             for (int i = 0; i + 1 < k; i++) {
                 const char *center_i = static_cast<const char *>(centers_dev) + (size_t)i * g.q_ld;
-                PGV_TRY(launch_hamming_tiles(ctx, s_dev, rg.nvec, n, center_i, g.q_ld, 1, raw));
+                PGV_TRY(launch_hamming_tiles(ctx, sv, center_i, g.q_ld, 1, raw));
                 PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, 2, block_sums));
-                PGV_TRY(launch_kmpp_pick(ctx, rg, s_dev, n, weight, block_sums, draws_dev, i, centers_dev, picked));
+                PGV_TRY(launch_kmpp_pick(ctx, sv.geom, s_dev, n, weight, block_sums, draws_dev, i, centers_dev, picked));
             }
         }
         PGV_TRY(ctx->km_g.ensure(sizeof(int32_t) * (size_t)n));
@@ -633,7 +633,7 @@ int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, i
             PGV_HIP(hipMemcpyAsync(out_closest, closest, sizeof(int32_t) * (size_t)n, hipMemcpyDefault, ctx->stream));
     }
     // (CheckCenters, src/ivfkmeans.c:539-547, has nothing to find in bit strings)
-    PGV_TRY(unstage_bit_rows(ctx, centers_dev, k, g.bytes, g.q_ld, out_centers));
+    PGV_TRY(unstage_rows(ctx, centers_dev, k, g.bytes, g.q_ld, out_centers));
     if (out_iters) *out_iters = iters;
     return pgv_ctx_sync(ctx);
 }
@@ -645,7 +645,9 @@ int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, i
 // k-means++ on staged (padded, device) samples into padded device centers
 static int kmeanspp_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &g,
                         const void *samples_dev, int n, int k, Rng &rng, void *centers_dev) {
-    const size_t row_bytes = (size_t)g.ld * elem_size(dtype);
+    const pgv_metric km = spherical(ops) ? PGV_NEG_IP : PGV_L2SQ;
+    const RowsView sv{samples_dev, n, g, row_kind(dtype), km};
+    const size_t row_bytes = sv.row_bytes();
     const int nblocks = kmpp_block_count(n);
     // km_a: weight[n] | raw[n]   km_b: block_sums[nblocks] | draws[k]   km_c: picked[k]
     PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * (size_t)n));
@@ -673,11 +675,10 @@ static int kmeanspp_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeo
     PGV_HIP(hipMemcpyAsync(picked, &first_i, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
 
-    const pgv_metric km = spherical(ops) ? PGV_NEG_IP : PGV_L2SQ;
     for (int i = 0; i + 1 < k; i++) {
         // distance of every sample to the newest center only (:52-60)
         const void *center_i = static_cast<const char *>(centers_dev) + (size_t)i * row_bytes;
-        PGV_TRY(dense_scan(ctx, km, dtype, g, samples_dev, n, center_i, 1, 0, raw));
+        PGV_TRY(dense_scan(ctx, sv, center_i, 1, 0, raw));
         PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, spherical(ops) ? 1 : 0, block_sums));
         PGV_TRY(launch_kmpp_pick(ctx, g, samples_dev, n, weight, block_sums, draws_dev, i, centers_dev, picked));
     }

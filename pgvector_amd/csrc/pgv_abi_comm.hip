@@ -273,7 +273,7 @@ int pgv_kmeans_sharded(pgv_comm *cm, pgv_ops ops, pgv_dtype dtype, int dim, cons
         for (int i = 0; i + 1 < k; i++) {
             const void *center_i = static_cast<const char *>(centers_dev) + (size_t)i * row_bytes;
             if (n > 0) {
-                PGV_TRY(dense_scan(ctx, km, dtype, g, s_dev, n, center_i, 1, 0, raw));
+                PGV_TRY(dense_scan(ctx, RowsView{s_dev, n, g, row_kind(dtype), km}, center_i, 1, 0, raw));
                 PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, spherical(ops) ? 1 : 0, block_sums));
                 PGV_TRY(launch_kmpp_total(ctx, block_sums, nblocks, my_total));
             } else {
@@ -351,7 +351,7 @@ int pgv_search_batch_sharded(pgv_comm *cm, pgv_index *ix, const void *queries, i
     PGV_HIP(hipSetDevice(ctx->device));
     const void *q_dev;
     PGV_TRY(stage_rows(ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ctx->q_stage, &q_dev));
-    const size_t row_bytes = (size_t)ix->geom.ld * elem_size(ix->dtype);
+    const size_t row_bytes = ivf_rows(ix).row_bytes();
 
     // GetScanLists: every rank ranks its slice of the batch against the replicated centers
     const int per = (nq + R - 1) / R;

@@ -33,38 +33,39 @@ int check_metric(pgv_metric m) {
 
 // rows that cannot stay in the 256 MB last-level cache between two batches anyway (four times its size and up) are
 // fetched non-temporally by the MFMA scan; smaller sets keep the default policy and the cache residency it gives them
-bool rows_stream_past_caches(const RowGeom &g, pgv_dtype dtype, int64_t nrows) {
-    return (size_t)nrows * (size_t)g.ld * elem_size(dtype) >= ((size_t)1 << 30);
-}
+bool rows_stream_past_caches(const RowsView &v) { return (size_t)v.n * v.row_bytes() >= ((size_t)1 << 30); }
 
-// rows [n x dim] tightly packed (host or device) -> device rows [n x ld], zero padded.
-// When the source already lives on the device with ld == dim it is used in place.
-int stage_rows(pgv_ctx *ctx, const void *src, int64_t n, int dim, pgv_dtype dtype,
-               const RowGeom &g, DBuf &scratch, const void **out) {
-    const size_t es = elem_size(dtype);
+// rows [n x tight] bytes, tightly packed (host or device; vector elements or VARBITS payloads) -> rows of `padded` bytes
+// each at dst (device), zero filled behind the payload
+int put_padded_rows(hipStream_t stream, void *dst, size_t padded, const void *src, size_t tight, int64_t n) {
+    if (n == 0) return PGV_OK;
+    const hipMemcpyKind kind = is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (padded == tight) {
+        PGV_HIP(hipMemcpyAsync(dst, src, (size_t)n * padded, kind, stream));
+    } else {
+        PGV_HIP(hipMemsetAsync(dst, 0, (size_t)n * padded, stream));
+        PGV_HIP(hipMemcpy2DAsync(dst, padded, src, tight, tight, (size_t)n, kind, stream));
+    }
+    return PGV_OK;
+}
+// ... into scratch, for the length of a call.  When the source already lives on the device with padded == tight it is
+// used in place
+int stage_rows(pgv_ctx *ctx, const void *src, int64_t n, size_t tight, size_t padded, DBuf &scratch, const void **out) {
     const bool dev = is_device_ptr(src);
-    if (dev && g.ld == dim) {
+    if (dev && padded == tight) {
         *out = src;
         return PGV_OK;
     }
-    const size_t bytes = (size_t)n * g.ld * es;
-    PGV_TRY(scratch.ensure(bytes ? bytes : 16));
-    if (n == 0) {
-        *out = scratch.p;
-        return PGV_OK;
-    }
-    if (g.ld == dim) {
-        PGV_HIP(hipMemcpyAsync(scratch.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        PGV_HIP(hipMemsetAsync(scratch.p, 0, bytes, ctx->stream));
-        PGV_HIP(hipMemcpy2DAsync(scratch.p, (size_t)g.ld * es, src, (size_t)dim * es,
-                                 (size_t)dim * es, (size_t)n,
-                                 dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                 ctx->stream));
-    }
-    if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));  // the caller may reuse src right away
+    PGV_TRY(scratch.ensure(n ? (size_t)n * padded : 16));
+    PGV_TRY(put_padded_rows(ctx->stream, scratch.p, padded, src, tight, n));
+    if (n && !dev) PGV_HIP(hipStreamSynchronize(ctx->stream));  // the caller may reuse src right away
     *out = scratch.p;
     return PGV_OK;
+}
+// ... rows of dim elements into the rows of g
+int stage_rows(pgv_ctx *ctx, const void *src, int64_t n, int dim, pgv_dtype dtype, const RowGeom &g, DBuf &scratch,
+               const void **out) {
+    return stage_rows(ctx, src, n, (size_t)dim * elem_size(dtype), (size_t)g.ld * elem_size(dtype), scratch, out);
 }
 
 // device rows [n x ld] -> caller rows [n x dim] (host or device)
@@ -92,23 +93,6 @@ int stage_flat(pgv_ctx *ctx, const void *src, size_t bytes, DBuf &scratch, const
         PGV_HIP(hipStreamSynchronize(ctx->stream));
     }
     *out = scratch.p;
-    return PGV_OK;
-}
-
-// packed bit rows [cnt x bytes] (host or device; VARBITS payloads) -> device rows of `ld` bytes each, zero padded.  When
-// the source already lives on the device with ld == bytes it is used in place.  (pgv_bit_distance_batch and pgv_bit_topk)
-int stage_bit_rows(pgv_ctx *ctx, const void *src, int64_t cnt, int bytes, int ld, DBuf &scratch, const void **outp) {
-    const bool dev = is_device_ptr(src);
-    if (dev && ld == bytes) {
-        *outp = src;
-        return PGV_OK;
-    }
-    PGV_TRY(scratch.ensure((size_t)cnt * ld));
-    PGV_HIP(hipMemsetAsync(scratch.p, 0, (size_t)cnt * ld, ctx->stream));
-    PGV_HIP(hipMemcpy2DAsync(scratch.p, (size_t)ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt,
-                             dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-    if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));
-    *outp = scratch.p;
     return PGV_OK;
 }
 
@@ -218,7 +202,7 @@ int resolve_events(pgv_ctx *ctx) {
 }
 
 // --------------------------------------------------- dense scan (host-planned)
-// rows [0, nrows) x queries [0, nq): out[q * out_stride + r].  Used for center
+// rows [0, v.n) x queries [0, nq): out[q * out_stride + r].  Used for center
 // ranking, exact scans and k-means++ rounds; tasks are planned on the host since
 // their shape depends only on sizes.  shadow_scale (mfma, fp16 L2): the shadow form of the kernel over a center
 // shadow and cast queries -- the plan's pairs carry pad = 0, so t = 0 and the value is |c|^2 - shadow_scale[q] acc.
@@ -241,17 +225,18 @@ static bool dense_keep() {
     return v != 0;
 }
 
-int dense_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-               const void *rows_dev, int64_t nrows, const void *queries_dev, int nq,
-               int64_t out_stride, float *out_dev, bool mfma = false, const float *row_norms = nullptr,
-               const float *query_norms = nullptr, const float *shadow_scale = nullptr) {
+int dense_scan(pgv_ctx *ctx, const RowsView &v, const void *queries_dev, int nq, int64_t out_stride, float *out_dev,
+               bool mfma = false, const float *row_norms = nullptr, const float *query_norms = nullptr,
+               const float *shadow_scale = nullptr) {
+    const RowGeom &g = v.geom;
+    const int64_t nrows = v.n;
     if (nrows <= 0 || nq <= 0) return PGV_OK;
     // one query against contiguous rows (a k-means++ round, pgv_distance_batch): no plan, no task counter -- the
     // single-query path's streaming kernel, whole rows in flight (k-means of the headline build: 0.137 -> 0.104 s)
     if (nq == 1 && !mfma && nrows <= 0x7fffffff) {
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin((double)nrows, (double)nrows, true));
-        PGV_TRY(launch_one_query_rows(ctx, metric, dtype, g, rows_dev, (int)nrows, queries_dev, out_dev));
+        PGV_TRY(launch_one_query_rows(ctx, v, queries_dev, out_dev));
         PGV_TRY(timer.end());
         return PGV_OK;
     }
@@ -260,7 +245,7 @@ int dense_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &
     // an approximation the caller rechecks)
     const bool use_tile = !mfma && nq > 8 && tile_scan_supported(g);
     const int qt = mfma ? mfma_scan_queries_per_task()
-                        : (use_tile ? tile_scan_queries_per_task() : scan_group_size(g, dtype, nq));
+                        : (use_tile ? tile_scan_queries_per_task() : scan_group_size(g, v.dtype(), nq));
     const int ngroups = (nq + qt - 1) / qt;
     int ch = mfma ? mfma_scan_rows_per_task() : rows_per_task_for(ctx, nrows, ngroups);
     if (use_tile) {
@@ -316,20 +301,18 @@ int dense_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &
         ctx->dense_plan_stride = out_stride;
         ctx->dense_plan_kind = plan_kind;
     }
-    const ScanTask *dt = plan_buf.as<ScanTask>();
-    const ScanPair *dp = reinterpret_cast<const ScanPair *>(plan_buf.as<char>() + tb);
-    const int *dn = reinterpret_cast<const int *>(plan_buf.as<char>() + tb + pb);
+    const ScanWork w{plan_buf.as<ScanTask>(), reinterpret_cast<const int *>(plan_buf.as<char>() + tb + pb), (int)ntasks,
+                     reinterpret_cast<const ScanPair *>(plan_buf.as<char>() + tb)};
 
     ScanTimer timer{ctx};
     PGV_TRY(timer.begin((double)nrows * nq, (double)nrows * ngroups, true));
     if (mfma)
-        PGV_TRY(launch_mfma_scan(ctx, metric, dtype, g, rows_dev, queries_dev, dt, dn, (int)ntasks, dp, row_norms,
-                                 query_norms, out_dev, rows_stream_past_caches(g, dtype, nrows), qt, shadow_scale));
+        PGV_TRY(launch_mfma_scan(ctx, v, queries_dev, w, row_norms, query_norms, out_dev, rows_stream_past_caches(v), qt,
+                                 shadow_scale));
     else if (use_tile)
-        PGV_TRY(launch_tile_scan(ctx, metric, dtype, g, rows_dev, queries_dev, dt, dn, (int)ntasks, dp, out_dev));
+        PGV_TRY(launch_tile_scan(ctx, v, queries_dev, w, out_dev));
     else
-        PGV_TRY(launch_scan(ctx, metric, dtype, g, rows_dev, queries_dev, dt, dn, (int)ntasks, dp, qt,
-                            out_dev));
+        PGV_TRY(launch_scan(ctx, v, queries_dev, w, qt, out_dev));
     PGV_TRY(timer.end());
     return PGV_OK;
 }

@@ -35,10 +35,8 @@ static size_t hnsw_row_bytes(const RowGeom &g) { return (size_t)g.nvec * kVecByt
 
 // queries [nq x dim] of the mirror's element type -> device rows in the mirror's row layout
 static int hnsw_stage_queries(pgv_hnsw *h, const void *queries, int nq, const void **q_dev) {
-    pgv_ctx *ctx = h->ctx;
-    if (hnsw_is_bits(h))
-        return stage_bit_rows(ctx, queries, nq, (h->nbits + 7) / 8, h->geom.ld, ctx->q_stage, q_dev);
-    return stage_rows(ctx, queries, nq, h->dim, h->dtype, h->geom, ctx->q_stage, q_dev);
+    return stage_rows(h->ctx, queries, nq, hnsw_src_row_bytes(h->dim, h->dtype, h->nbits), hnsw_row_bytes(h->geom),
+                      h->ctx->q_stage, q_dev);
 }
 
 static int hnsw_upload_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nbits, const void *elements,

@@ -81,7 +81,7 @@ int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
     const int env = shadow_env();
     if (env == 0 || ix->metric != PGV_L2SQ || ix->dtype != PGV_F32 || ix->nrows <= 0 || !ix->row_norms || !ix->center_norms)
         return PGV_OK;
-    if (env < 0 && !rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows)) return PGV_OK;
+    if (env < 0 && !rows_stream_past_caches(ivf_rows(ix))) return PGV_OK;
     const RowGeom g16 = row_geom(ix->dim, PGV_F16);
     const size_t bytes = ((size_t)ix->nrows * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
     const size_t cbytes = ((size_t)ix->nlists * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
@@ -190,12 +190,24 @@ int shadow_batch_cast(pgv_index *ix, const void *q_dev, int nq, int probes, bool
     return PGV_OK;
 }
 
+// What a mirror's rows are made of, as the upload entries state it: dim elements of dtype under metric, or nbits bits
+// (pgv_index_upload_bits; metric / dtype are unused there, and PGV_L1 keeps every L2-only structure away from it)
+struct IndexElem {
+    pgv_metric metric;
+    pgv_dtype dtype;
+    int dim, nbits;
+    static IndexElem bits(int nbits) { return {PGV_L1, PGV_F32, nbits, nbits}; }
+    size_t tight_bytes() const { return nbits > 0 ? (size_t)(nbits + 7) / 8 : (size_t)dim * elem_size(dtype); }  // VARBITBYTES
+};
+
 // The mirror of an index whose list offsets are known: one allocation, host tables, the norms the MFMA paths want.
 // `fill` enqueues (on ctx->stream) whatever brings centers / vectors / tids into the carved arrays.
-// nbits > 0: a bit index (pgv_index_upload_bits) -- rows of bit_row_geom(nbits).ld bytes, no norms, no shadow
+// A bit index has rows of bit_row_geom(nbits).ld bytes, no norms and no shadow
 template <typename Fill>
-int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nlists, const std::vector<int64_t> &off,
-                 bool has_tids, Fill fill, pgv_index **out, int nbits = 0) {
+int index_create(pgv_ctx *ctx, const IndexElem &el, int nlists, const std::vector<int64_t> &off, bool has_tids, Fill fill,
+                 pgv_index **out) {
+    const pgv_metric metric = el.metric;
+    const int nbits = el.nbits;
     const int64_t n = off[nlists];
     pgv_index *ix = new (std::nothrow) pgv_index();
     if (!ix) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
@@ -206,15 +218,14 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
         PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
     }
     ix->metric = metric;
-    ix->dtype = dtype;
-    ix->dim = dim;
+    ix->dtype = el.dtype;
+    ix->dim = el.dim;
     ix->nlists = nlists;
     ix->nrows = n;
     ix->nbits = nbits;
-    ix->geom = nbits > 0 ? bit_row_geom(nbits) : row_geom(dim, dtype);
+    ix->geom = nbits > 0 ? bit_row_geom(nbits) : row_geom(el.dim, el.dtype);
     ix->h_offsets = off;
     index_host_tables(ix);
-    const size_t row_bytes = nbits > 0 ? (size_t)ix->geom.ld : (size_t)ix->geom.ld * elem_size(dtype);
 
     auto fail = [&](int rc) {
         pgv_index_free(ix);
@@ -222,7 +233,7 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
     };
     // one allocation for the whole mirror (a single IPC handle exports it): centers | vectors | list_offsets |
     // tids | row_norms | center_norms, each part 256-byte aligned
-    IndexLayout lay = index_layout(nlists, n, row_bytes, has_tids && n > 0, metric == PGV_L2SQ && nbits == 0);
+    IndexLayout lay = index_layout(nlists, n, ivf_rows(ix).row_bytes(), has_tids && n > 0, metric == PGV_L2SQ && nbits == 0);
     if (malloc_exportable(&ix->arena, lay.bytes) != hipSuccess) {
         (void)hipGetLastError();
         set_error("hipMalloc(%zu) for the index mirror failed", lay.bytes);
@@ -239,14 +250,13 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
         // |x|^2 per row and the largest of them: the MFMA scan's expansion of the L2 distance
         if (hipMemsetAsync(ix->row_norms + n, 0, sizeof(float), ctx->stream) != hipSuccess)
             return fail((set_error("memset of row_norms failed"), PGV_ERR_DEVICE));
-        if ((rc = launch_row_norms(ctx, dtype, ix->geom, ix->vectors, n, ix->row_norms,
-                                   reinterpret_cast<unsigned *>(ix->row_norms + n))) != PGV_OK)
+        if ((rc = launch_row_norms(ctx, ivf_rows(ix), ix->row_norms, reinterpret_cast<unsigned *>(ix->row_norms + n))) != PGV_OK)
             return fail(rc);
     }
     if (ix->center_norms) {
         if (hipMemsetAsync(ix->center_norms + nlists, 0, sizeof(float), ctx->stream) != hipSuccess)
             return fail((set_error("memset of center_norms failed"), PGV_ERR_DEVICE));
-        if ((rc = launch_row_norms(ctx, dtype, ix->geom, ix->centers, nlists, ix->center_norms,
+        if ((rc = launch_row_norms(ctx, ivf_centers(ix), ix->center_norms,
                                    reinterpret_cast<unsigned *>(ix->center_norms + nlists))) != PGV_OK)
             return fail(rc);
     }
@@ -257,24 +267,34 @@ int index_create(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int 
     return PGV_OK;
 }
 
-// tightly packed rows (host or device) into padded device rows
-int put_rows_on(hipStream_t stream, const RowGeom &g, pgv_dtype dtype, int dim, void *dst, const void *src, int64_t rows) {
-    if (rows == 0) return PGV_OK;
-    const size_t es = elem_size(dtype), row_bytes = (size_t)g.ld * es;
-    const bool dev = is_device_ptr(src);
-    if (g.ld == dim) {
-        PGV_HIP(hipMemcpyAsync(dst, src, (size_t)rows * row_bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                               stream));
+// What pgv_index_upload and pgv_index_upload_bits share once their own arguments are checked: the offsets read and
+// validated, then the mirror with centers, rows and tids copied in
+int index_upload(pgv_ctx *ctx, const IndexElem &el, int nlists, const void *centers, const int64_t *list_offsets,
+                 const void *rows, const char *rows_name, const uint64_t *tids, pgv_index **out) {
+    // IVFFLAT_MAX_LISTS (src/ivfflat.h:56)
+    if (nlists < 1 || nlists > 32768) PGV_FAIL(PGV_ERR_ARG, "lists %d outside 1..32768", nlists);
+    if (!centers || !list_offsets) PGV_FAIL(PGV_ERR_ARG, "centers/list_offsets is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    std::vector<int64_t> off((size_t)nlists + 1);
+    if (is_device_ptr(list_offsets)) {
+        PGV_HIP(hipMemcpy(off.data(), list_offsets, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost));
     } else {
-        PGV_HIP(hipMemsetAsync(dst, 0, (size_t)rows * row_bytes, stream));
-        PGV_HIP(hipMemcpy2DAsync(dst, row_bytes, src, (size_t)dim * es, (size_t)dim * es, (size_t)rows,
-                                 dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+        memcpy(off.data(), list_offsets, sizeof(int64_t) * off.size());
     }
-    return PGV_OK;
-}
-
-int put_rows(pgv_ctx *ctx, const RowGeom &g, pgv_dtype dtype, int dim, void *dst, const void *src, int64_t rows) {
-    return put_rows_on(ctx->stream, g, dtype, dim, dst, src, rows);
+    if (off[0] != 0) PGV_FAIL(PGV_ERR_ARG, "list_offsets[0] must be 0");
+    for (int l = 0; l < nlists; l++)
+        if (off[l + 1] < off[l]) PGV_FAIL(PGV_ERR_ARG, "list_offsets not ascending at list %d", l);
+    const int64_t n = off[nlists];
+    if (n > 0 && !rows) PGV_FAIL(PGV_ERR_ARG, "%s is NULL", rows_name);
+    return index_create(ctx, el, nlists, off, tids != nullptr, [&](pgv_index *ix) -> int {
+        const size_t padded = ivf_rows(ix).row_bytes();
+        PGV_TRY(put_padded_rows(ctx->stream, ix->centers, padded, centers, el.tight_bytes(), nlists));
+        PGV_TRY(put_padded_rows(ctx->stream, ix->vectors, padded, rows, el.tight_bytes(), n));
+        if (ix->tids)
+            PGV_HIP(hipMemcpyAsync(ix->tids, tids, sizeof(uint64_t) * (size_t)n,
+                                   is_device_ptr(tids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+        return PGV_OK;
+    }, out);
 }
 
 }  // namespace
@@ -287,43 +307,7 @@ int pgv_index_upload(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, 
     *out = nullptr;
     PGV_TRY(check_common(dtype, dim));
     PGV_TRY(check_metric(metric));
-    // IVFFLAT_MAX_LISTS (src/ivfflat.h:56)
-    if (nlists < 1 || nlists > 32768) PGV_FAIL(PGV_ERR_ARG, "lists %d outside 1..32768", nlists);
-    if (!centers || !list_offsets) PGV_FAIL(PGV_ERR_ARG, "centers/list_offsets is NULL");
-    PGV_HIP(hipSetDevice(ctx->device));
-
-    std::vector<int64_t> off((size_t)nlists + 1);
-    if (is_device_ptr(list_offsets)) {
-        PGV_HIP(hipMemcpy(off.data(), list_offsets, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost));
-    } else {
-        memcpy(off.data(), list_offsets, sizeof(int64_t) * off.size());
-    }
-    if (off[0] != 0) PGV_FAIL(PGV_ERR_ARG, "list_offsets[0] must be 0");
-    for (int l = 0; l < nlists; l++)
-        if (off[l + 1] < off[l]) PGV_FAIL(PGV_ERR_ARG, "list_offsets not ascending at list %d", l);
-    const int64_t n = off[nlists];
-    if (n > 0 && !vectors) PGV_FAIL(PGV_ERR_ARG, "vectors is NULL");
-    return index_create(ctx, metric, dtype, dim, nlists, off, tids != nullptr, [&](pgv_index *ix) -> int {
-        PGV_TRY(put_rows(ctx, ix->geom, dtype, dim, ix->centers, centers, nlists));
-        PGV_TRY(put_rows(ctx, ix->geom, dtype, dim, ix->vectors, vectors, n));
-        if (ix->tids)
-            PGV_HIP(hipMemcpyAsync(ix->tids, tids, sizeof(uint64_t) * (size_t)n,
-                                   is_device_ptr(tids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-        return PGV_OK;
-    }, out);
-}
-
-// packed bit rows [cnt x bytes] (host or device) into device rows of `ld` bytes, zero padded
-static int put_bit_rows(pgv_ctx *ctx, void *dst, int ld, const void *src, int bytes, int64_t cnt) {
-    if (cnt == 0) return PGV_OK;
-    const hipMemcpyKind kind = is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (ld == bytes) {
-        PGV_HIP(hipMemcpyAsync(dst, src, (size_t)cnt * (size_t)ld, kind, ctx->stream));
-    } else {
-        PGV_HIP(hipMemsetAsync(dst, 0, (size_t)cnt * (size_t)ld, ctx->stream));
-        PGV_HIP(hipMemcpy2DAsync(dst, (size_t)ld, src, (size_t)bytes, (size_t)bytes, (size_t)cnt, kind, ctx->stream));
-    }
-    return PGV_OK;
+    return index_upload(ctx, IndexElem{metric, dtype, dim, 0}, nlists, centers, list_offsets, vectors, "vectors", tids, out);
 }
 
 // `USING ivfflat (col bit_hamming_ops)` (sql/vector.sql:894-899; the bit type info of src/ivfutils.c:411-424): the mirror
@@ -334,30 +318,7 @@ int pgv_index_upload_bits(pgv_ctx *ctx, int nbits, int nlists, const void *cente
     *out = nullptr;
     // IVFFLAT_MAX_DIM * 32 (src/ivfutils.c:416)
     if (nbits < 1 || nbits > kIvfMaxBits) PGV_FAIL(PGV_ERR_DIMS, "bit length %d outside 1..%d", nbits, kIvfMaxBits);
-    if (nlists < 1 || nlists > 32768) PGV_FAIL(PGV_ERR_ARG, "lists %d outside 1..32768", nlists);
-    if (!centers || !list_offsets) PGV_FAIL(PGV_ERR_ARG, "centers/list_offsets is NULL");
-    PGV_HIP(hipSetDevice(ctx->device));
-    std::vector<int64_t> off((size_t)nlists + 1);
-    if (is_device_ptr(list_offsets)) {
-        PGV_HIP(hipMemcpy(off.data(), list_offsets, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost));
-    } else {
-        memcpy(off.data(), list_offsets, sizeof(int64_t) * off.size());
-    }
-    if (off[0] != 0) PGV_FAIL(PGV_ERR_ARG, "list_offsets[0] must be 0");
-    for (int l = 0; l < nlists; l++)
-        if (off[l + 1] < off[l]) PGV_FAIL(PGV_ERR_ARG, "list_offsets not ascending at list %d", l);
-    const int64_t n = off[nlists];
-    if (n > 0 && !rows) PGV_FAIL(PGV_ERR_ARG, "rows is NULL");
-    const int bytes = (nbits + 7) / 8;  // VARBITBYTES
-    // (metric / dtype are unused on a bit index; PGV_L1 keeps every L2-only structure away from it)
-    return index_create(ctx, PGV_L1, PGV_F32, nbits, nlists, off, tids != nullptr, [&](pgv_index *ix) -> int {
-        PGV_TRY(put_bit_rows(ctx, ix->centers, ix->geom.ld, centers, bytes, nlists));
-        PGV_TRY(put_bit_rows(ctx, ix->vectors, ix->geom.ld, rows, bytes, n));
-        if (ix->tids)
-            PGV_HIP(hipMemcpyAsync(ix->tids, tids, sizeof(uint64_t) * (size_t)n,
-                                   is_device_ptr(tids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-        return PGV_OK;
-    }, out, nbits);
+    return index_upload(ctx, IndexElem::bits(nbits), nlists, centers, list_offsets, rows, "rows", tids, out);
 }
 
 int pgv_index_nbits(const pgv_index *ix) { return ix ? ix->nbits : -1; }
@@ -368,21 +329,13 @@ int pgv_index_nbits(const pgv_index *ix) { return ix ? ix->nbits : -1; }
         if ((ix)->nbits > 0) PGV_FAIL(PGV_ERR_ARG, "%s: not served on a bit index (pgv_index_upload_bits)", who); \
     } while (0)
 
-// the queries of a bit index: [nq x bytes] bit strings into whole register slices of the Hamming kernels
-static int stage_bit_queries(pgv_index *ix, const void *queries, int nq, const void **q_dev, int *q_ld) {
-    const int bytes = (ix->nbits + 7) / 8, slice = bit_topk_slice_bytes();
-    *q_ld = (bytes + slice - 1) / slice * slice;
-    return stage_bit_rows(ix->ctx, queries, nq, bytes, *q_ld, ix->ctx->q_stage, q_dev);
-}
-// ... of a vector / halfvec index or of a bit index
+// the queries of an index in its rows' layout; of a bit index: [nq x VARBITBYTES] bit strings into whole register slices
+// of the Hamming kernels (bit_query_bytes)
 static int stage_queries(pgv_index *ix, const void *queries, int nq, const void **q_dev) {
-    int q_ld;
-    if (ix->nbits > 0) return stage_bit_queries(ix, queries, nq, q_dev, &q_ld);
+    if (ix->nbits > 0)
+        return stage_rows(ix->ctx, queries, nq, (size_t)(ix->nbits + 7) / 8, (size_t)bit_query_bytes(ix->nbits), ix->ctx->q_stage,
+                          q_dev);
     return stage_rows(ix->ctx, queries, nq, ix->dim, ix->dtype, ix->geom, ix->ctx->q_stage, q_dev);
-}
-static int bit_query_bytes(const pgv_index *ix) {
-    const int bytes = (ix->nbits + 7) / 8, slice = bit_topk_slice_bytes();
-    return (bytes + slice - 1) / slice * slice;
 }
 
 // ------------------------------------------------------------ the build's tuplesort on the device
@@ -405,13 +358,20 @@ struct pgv_builder {
     bool deferred = false;
     hipStream_t copy_stream = nullptr;
     hipStream_t stream() const { return deferred ? copy_stream : ctx->stream; }
+    // the heap-order rows as the kernels take them; centers and rows share its row_bytes()
+    RowsView view() const { return {rows.p, n, geom, row_kind(dtype), metric}; }
+    size_t row_bytes() const { return view().row_bytes(); }
+    // tightly packed rows or centers (host or device) into padded ones at dst
+    int put(hipStream_t to, void *dst, const void *src, int64_t cnt) const {
+        return put_padded_rows(to, dst, row_bytes(), src, (size_t)dim * elem_size(dtype), cnt);
+    }
 };
 
 static int builder_reserve(pgv_builder *b, int64_t want) {
     if (want <= b->cap) return PGV_OK;
     int64_t cap = b->cap ? b->cap + b->cap / 2 : want;
     if (cap < want) cap = want;
-    const size_t row_bytes = (size_t)b->geom.ld * elem_size(b->dtype);
+    const size_t row_bytes = b->row_bytes();
     DBuf rows, tids, lists;
     PGV_TRY(rows.ensure(row_bytes * (size_t)cap));
     int rc = tids.ensure(sizeof(uint64_t) * (size_t)cap);
@@ -445,8 +405,7 @@ static int builder_reserve(pgv_builder *b, int64_t want) {
 // rows [assigned, n) to their nearest center
 static int builder_assign_pending(pgv_builder *b) {
     if (b->assigned >= b->n) return PGV_OK;
-    const size_t row_bytes = (size_t)b->geom.ld * elem_size(b->dtype);
-    PGV_TRY(launch_argmin(b->ctx, b->metric, b->dtype, b->geom, b->rows.as<char>() + (size_t)b->assigned * row_bytes,
+    PGV_TRY(launch_argmin(b->ctx, b->metric, b->dtype, b->geom, b->rows.as<char>() + (size_t)b->assigned * b->row_bytes(),
                           b->n - b->assigned, b->centers.p, b->nlists, b->lists.as<int32_t>() + b->assigned, nullptr));
     b->assigned = b->n;
     return PGV_OK;
@@ -469,9 +428,9 @@ int pgv_builder_begin(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim,
     b->dim = dim;
     b->nlists = nlists;
     b->geom = row_geom(dim, dtype);
-    int rc = b->centers.ensure((size_t)b->geom.ld * elem_size(dtype) * (size_t)nlists);
+    int rc = b->centers.ensure(b->row_bytes() * (size_t)nlists);
     if (rc == PGV_OK && centers) {
-        rc = put_rows(ctx, b->geom, dtype, dim, b->centers.p, centers, nlists);
+        rc = b->put(ctx->stream, b->centers.p, centers, nlists);
         if (rc == PGV_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = PGV_ERR_DEVICE;  // the caller may reuse centers
     } else if (rc == PGV_OK) {
         b->deferred = true;
@@ -516,10 +475,8 @@ int pgv_builder_add(pgv_builder *b, const void *rows, const uint64_t *tids, int6
     PGV_HIP(hipSetDevice(ctx->device));
     PGV_TRY(builder_reserve(b, b->n + n));
     b->has_tids = tids != nullptr;
-    const size_t row_bytes = (size_t)b->geom.ld * elem_size(b->dtype);
-    char *dst = b->rows.as<char>() + (size_t)b->n * row_bytes;
     hipStream_t stream = b->stream();
-    PGV_TRY(put_rows_on(stream, b->geom, b->dtype, b->dim, dst, rows, n));
+    PGV_TRY(b->put(stream, b->rows.as<char>() + (size_t)b->n * b->row_bytes(), rows, n));
     if (tids)
         PGV_HIP(hipMemcpyAsync(b->tids.as<uint64_t>() + b->n, tids, sizeof(uint64_t) * (size_t)n,
                                is_device_ptr(tids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
@@ -540,7 +497,7 @@ int pgv_builder_set_centers(pgv_builder *b, const void *centers) {
     PGV_HIP(hipSetDevice(ctx->device));
     PGV_HIP(hipStreamSynchronize(b->copy_stream));  // every row has arrived; from here on the context's stream is used
     b->deferred = false;
-    PGV_TRY(put_rows(ctx, b->geom, b->dtype, b->dim, b->centers.p, centers, b->nlists));
+    PGV_TRY(b->put(ctx->stream, b->centers.p, centers, b->nlists));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
     return PGV_OK;
 }
@@ -592,9 +549,9 @@ int pgv_builder_finish(pgv_builder *b, pgv_index **out_index, int64_t *out_offse
         rc = PGV_ERR_STATE;
     }
     if (rc == PGV_OK)
-        rc = index_create(ctx, b->metric, b->dtype, b->dim, nlists, off, true, [&](pgv_index *ix) -> int {
-            const size_t row_bytes = (size_t)b->geom.ld * elem_size(b->dtype);
-            PGV_HIP(hipMemcpyAsync(ix->centers, b->centers.p, row_bytes * (size_t)nlists, hipMemcpyDeviceToDevice, ctx->stream));
+        rc = index_create(ctx, IndexElem{b->metric, b->dtype, b->dim, 0}, nlists, off, true, [&](pgv_index *ix) -> int {
+            PGV_HIP(hipMemcpyAsync(ix->centers, b->centers.p, b->row_bytes() * (size_t)nlists, hipMemcpyDeviceToDevice,
+                                   ctx->stream));
             // rows and heap TIDs (heap positions when none were given) into list-major order, heap order inside a list
             return launch_build_gather(ctx, b->rows.p, keys_sorted, n, b->geom.nvec, ix->vectors,
                                        b->has_tids ? b->tids.as<uint64_t>() : nullptr, ix->tids);
@@ -619,7 +576,7 @@ int pgv_index_drain(pgv_index *ix, int64_t chunk_rows, pgv_rows_sink sink, void 
     PGV_HIP(hipSetDevice(ctx->device));
     const int64_t n = ix->nrows;
     if (n == 0) return PGV_OK;
-    const size_t es = elem_size(ix->dtype), tight = (size_t)ix->dim * es, padded = (size_t)ix->geom.ld * es;
+    const size_t tight = (size_t)ix->dim * elem_size(ix->dtype), padded = ivf_rows(ix).row_bytes();
     // 64 MB pieces: long enough for the link's full rate, short enough that pinning the two bounce buffers (which
     // costs ~30 ms at 2 x 256 MB) does not show
     if (chunk_rows <= 0) chunk_rows = (int64_t)std::max<size_t>(1, ((size_t)64 << 20) / tight);
@@ -797,8 +754,7 @@ int pgv_index_import(pgv_ctx *ctx, const pgv_index_handle *handle, pgv_index **o
     ix->nrows = w.nrows;
     ix->geom = row_geom(w.dim, ix->dtype);
     ix->imported = true;
-    const size_t row_bytes = (size_t)ix->geom.ld * elem_size(ix->dtype);
-    IndexLayout lay = index_layout(w.nlists, w.nrows, row_bytes, w.has_tids != 0, ix->metric == PGV_L2SQ);
+    IndexLayout lay = index_layout(w.nlists, w.nrows, ivf_rows(ix).row_bytes(), w.has_tids != 0, ix->metric == PGV_L2SQ);
     if (lay.bytes != w.arena_bytes) {
         pgv_index_free(ix);
         PGV_FAIL(PGV_ERR_ARG, "pgv_index_import: handle describes %llu bytes, this library lays the mirror out in %zu",
@@ -911,7 +867,7 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
         // the maxprobes smallest per query with ties to the lower list id (the reference's strict `<` at :92)
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin((double)ix->nlists * nq, (double)ix->nlists * ((nq + 31) / 32), true));
-        PGV_TRY(launch_hamming_tiles(ctx, ix->centers, ix->geom.nvec, ix->nlists, q_dev, bit_query_bytes(ix), nq, mat));
+        PGV_TRY(launch_hamming_tiles(ctx, ivf_centers(ix), q_dev, bit_query_bytes(ix->nbits), nq, mat));
         PGV_TRY(timer.end());
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, maxprobes, dist, pos));
         return launch_cast_pos_to_i32(ctx, pos, (int64_t)nq * maxprobes, out_lists_dev);
@@ -948,11 +904,10 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
         const bool scan_follows = sb->scan_follows;
         if (rank_sh) {
             PGV_TRY(shadow_batch_cast(ix, q_dev, nq, maxprobes, true, scan_follows, sb));
-            PGV_TRY(dense_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->cshadow, ix->nlists, sb->qcast, nq, ix->nlists,
-                               mat, true, ix->center_norms, nullptr, sb->cscale));
+            PGV_TRY(dense_scan(ctx, ivf_shadow_centers(ix), sb->qcast, nq, ix->nlists, mat, true, ix->center_norms, nullptr,
+                               sb->cscale));
         } else {
-            PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
-                               true, ix->center_norms, nullptr));
+            PGV_TRY(dense_scan(ctx, ivf_centers(ix), q_dev, nq, ix->nlists, mat, true, ix->center_norms, nullptr));
         }
         // the pair terms of the shadow scan that follows: q.c of the lists emitted, beside their exact distances
         ExactTail tail;
@@ -983,8 +938,7 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
         sb->pairs_done = tail.pair_t != nullptr;
         return PGV_OK;
     } else {
-        PGV_TRY(dense_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->centers, ix->nlists, q_dev, nq, ix->nlists, mat,
-                           mfma, nullptr, nullptr));
+        PGV_TRY(dense_scan(ctx, ivf_centers(ix), q_dev, nq, ix->nlists, mat, mfma, nullptr, nullptr));
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, nq, ix->nlists, maxprobes, dist, pos));
     }
     PGV_TRY(launch_cast_pos_to_i32(ctx, pos, (int64_t)nq * maxprobes, out_lists_dev));
@@ -1014,103 +968,6 @@ int pgv_rank_lists(pgv_index *ix, const void *queries, int nq, int maxprobes, in
     bool need = false;
     PGV_TRY(ol.finish(ctx, &need));
     PGV_TRY(od.finish(ctx, &need));
-    return sync_if(ctx, need);
-}
-
-int pgv_scan_lists(pgv_index *ix, const void *query, const int32_t *lists, int nlists,
-                   float *out_dist, int64_t *out_slot, int64_t capacity, int64_t *out_count) {
-    if (!ix || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_scan_lists: index/out_count is NULL");
-    if (nlists < 0 || (nlists > 0 && !lists)) PGV_FAIL(PGV_ERR_ARG, "bad list array");
-    pgv_ctx *ctx = ix->ctx;
-    PGV_HIP(hipSetDevice(ctx->device));
-
-    std::vector<int32_t> hl((size_t)nlists);
-    if (nlists) {
-        if (is_device_ptr(lists))
-            PGV_HIP(hipMemcpy(hl.data(), lists, sizeof(int32_t) * (size_t)nlists, hipMemcpyDeviceToHost));
-        else
-            memcpy(hl.data(), lists, sizeof(int32_t) * (size_t)nlists);
-    }
-    int64_t m = 0;
-    for (int p = 0; p < nlists; p++) {
-        if (hl[p] < 0 || hl[p] >= ix->nlists) PGV_FAIL(PGV_ERR_ARG, "list id %d out of range", hl[p]);
-        m += ix->h_offsets[hl[p] + 1] - ix->h_offsets[hl[p]];
-    }
-    *out_count = m;
-    if (m > capacity) PGV_FAIL(PGV_ERR_ARG, "output capacity %lld < %lld tuples", (long long)capacity, (long long)m);
-    if (m == 0) return PGV_OK;
-    if (!out_dist || !out_slot) PGV_FAIL(PGV_ERR_ARG, "out_dist/out_slot is NULL");
-
-    OutArg od, os;
-    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)m, ctx->out_stage));
-    PGV_TRY(os.init(out_slot, sizeof(int64_t) * (size_t)m, ctx->out_stage2));
-
-    // plan on the host: per probed list a run of chunks, all for the one query
-    const int ch = ix->nbits > 0 ? hamming_list_rows_per_task() : rows_per_task_for(ctx, m, 1);
-    int64_t ntasks = 0;
-    for (int p = 0; p < nlists; p++) {
-        int64_t len = ix->h_offsets[hl[p] + 1] - ix->h_offsets[hl[p]];
-        ntasks += (len + ch - 1) / ch;
-    }
-    const size_t tb = sizeof(ScanTask) * (size_t)ntasks, pb = sizeof(ScanPair) * (size_t)nlists,
-                 ob = sizeof(int64_t) * (size_t)nlists, lb = sizeof(int32_t) * (size_t)nlists;
-    PGV_TRY(staging_acquire(ctx));
-    PGV_TRY(ctx->h_a.ensure(tb + pb + ob + lb + 16));
-    char *hb = ctx->h_a.as<char>();
-    ScanTask *ht = reinterpret_cast<ScanTask *>(hb);
-    ScanPair *hp = reinterpret_cast<ScanPair *>(hb + tb);
-    int64_t *hoff = reinterpret_cast<int64_t *>(hb + tb + pb);
-    int32_t *hlist = reinterpret_cast<int32_t *>(hb + tb + pb + ob);
-    int *hn = reinterpret_cast<int *>(hb + tb + pb + ob + lb);
-    int64_t t = 0, run = 0;
-    for (int p = 0; p < nlists; p++) {
-        const int64_t beg = ix->h_offsets[hl[p]], len = ix->h_offsets[hl[p] + 1] - beg;
-        hp[p].out_rel = run - beg;
-        hp[p].query = 0;
-        hp[p].pad = 0;
-        hoff[p] = run;
-        hlist[p] = hl[p];
-        for (int64_t c = 0; c * ch < len; c++) {
-            ht[t].row0 = beg + c * ch;
-            int64_t left = len - c * ch;
-            ht[t].nrows = (int)(left < ch ? left : ch);
-            ht[t].pair0 = p;
-            ht[t].npairs = 1;
-            ht[t].pad = 0;
-            t++;
-        }
-        run += len;
-    }
-    *hn = (int)ntasks;
-    const size_t total = tb + pb + ob + lb + 16;
-    PGV_TRY(ctx->tasks.ensure(total));
-    PGV_HIP(hipMemcpyAsync(ctx->tasks.p, hb, total, hipMemcpyHostToDevice, ctx->stream));
-    char *db = ctx->tasks.as<char>();
-
-    PGV_TRY(launch_iota_slots(ctx, ix, reinterpret_cast<int32_t *>(db + tb + pb + ob), nlists,
-                              reinterpret_cast<int64_t *>(db + tb + pb), os.as<int64_t>()));
-    if (query == nullptr) {
-        // ZeroDistance (src/ivfscan.c:192-196): every tuple at distance 0
-        PGV_HIP(hipMemsetAsync(od.dev, 0, sizeof(float) * (size_t)m, ctx->stream));
-    } else {
-        const void *q_dev;
-        PGV_TRY(stage_queries(ix, query, 1, &q_dev));
-        ScanTimer timer{ctx};
-        PGV_TRY(timer.begin((double)m, (double)m));
-        if (ix->nbits > 0)  // the batch's kernel with one pair per task
-            PGV_TRY(launch_hamming_lists(ctx, ix->vectors, ix->geom.nvec, q_dev, bit_query_bytes(ix),
-                                         reinterpret_cast<ScanTask *>(db), reinterpret_cast<int *>(db + tb + pb + ob + lb),
-                                         (int)ntasks, reinterpret_cast<ScanPair *>(db + tb), hamming_list_group_size(1.0),
-                                         od.as<float>()));
-        else
-            PGV_TRY(launch_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev,
-                                reinterpret_cast<ScanTask *>(db), reinterpret_cast<int *>(db + tb + pb + ob + lb),
-                                (int)ntasks, reinterpret_cast<ScanPair *>(db + tb), 1, od.as<float>()));
-        PGV_TRY(timer.end());
-    }
-    bool need = true;  // h_a must be consumed before the next call rewrites it
-    PGV_TRY(od.finish(ctx, &need));
-    PGV_TRY(os.finish(ctx, &need));
     return sync_if(ctx, need);
 }
 
@@ -1183,6 +1040,29 @@ static ScanPath scan_path(const pgv_index *ix, int nq, int probes, int k) {
     return p;
 }
 
+// One list scan, by the kernel `path` names: its turn among the lanes, the timer, the launch.  out[pair.out_rel + row] of
+// every task of `work`.  queries / qscale: the staged queries -- under path.shadow the shadow batch's cast ones, which
+// go with the shadow rows, and their factors.  counted: (row, query) pairs = rows streamed, where the host knows them
+static int list_scan_step(pgv_index *ix, const ScanPath &path, const ScanWork &work, const void *queries, const float *qscale,
+                          double counted, float *out) {
+    pgv_ctx *ctx = ix->ctx;
+    const RowsView v = path.shadow ? ivf_shadow_rows(ix) : ivf_rows(ix);
+    PGV_TRY(scan_turn_begin(ctx));
+    ScanTimer timer{ctx};
+    PGV_TRY(timer.begin(counted, counted));
+    if (path.bits)
+        PGV_TRY(launch_hamming_lists(ctx, v, queries, bit_query_bytes(ix->nbits), work, path.qt, out));
+    else if (path.use_mfma)
+        PGV_TRY(launch_mfma_scan(ctx, v, queries, work, ix->row_norms, nullptr, out, rows_stream_past_caches(v), path.qt,
+                                 path.shadow ? qscale : nullptr));
+    else if (path.use_tile)
+        PGV_TRY(launch_tile_scan(ctx, v, queries, work, out));
+    else
+        PGV_TRY(launch_scan(ctx, v, queries, work, path.qt, out));
+    PGV_TRY(timer.end());
+    return scan_turn_end(ctx);
+}
+
 static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
                            int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid, ShadowBatch *sb) {
     pgv_ctx *ctx = ix->ctx;
@@ -1228,30 +1108,9 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
     // GetScanItems: one streaming pass
     PGV_TRY(ctx->plan_d.ensure(sizeof(float) * (size_t)(plan.out_bound > 0 ? plan.out_bound : 1)));
     float *seg_vals = ctx->plan_d.as<float>();
-    if (plan.ntasks_bound > 0) {
-        PGV_TRY(scan_turn_begin(ctx));
-        ScanTimer timer{ctx};
-        PGV_TRY(timer.begin(0.0, 0.0));  // pairs / rows of this launch are accumulated on the device
-        if (path.bits)
-            PGV_TRY(launch_hamming_lists(ctx, ix->vectors, ix->geom.nvec, q_dev, bit_query_bytes(ix), plan.tasks,
-                                         plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, path.qt, seg_vals));
-        else if (path.shadow)
-            PGV_TRY(launch_mfma_scan(ctx, ix->metric, PGV_F16, ix->shadow_geom, ix->shadow, sb->qcast, plan.tasks,
-                                     plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
-                                     seg_vals, rows_stream_past_caches(ix->shadow_geom, PGV_F16, ix->nrows), path.qt, sb->qscale));
-        else if (path.use_mfma)
-            PGV_TRY(launch_mfma_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
-                                     plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, ix->row_norms, nullptr,
-                                     seg_vals, rows_stream_past_caches(ix->geom, ix->dtype, ix->nrows), path.qt));
-        else if (path.use_tile)
-            PGV_TRY(launch_tile_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
-                                     plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, seg_vals));
-        else
-            PGV_TRY(launch_scan(ctx, ix->metric, ix->dtype, ix->geom, ix->vectors, q_dev, plan.tasks,
-                                plan.ntasks_dev, (int)plan.ntasks_bound, plan.pairs, path.qt, seg_vals));
-        PGV_TRY(timer.end());
-        PGV_TRY(scan_turn_end(ctx));
-    }
+    // (pairs / rows of this launch are accumulated on the device)
+    if (plan.ntasks_bound > 0)
+        PGV_TRY(list_scan_step(ix, path, plan.work(), path.shadow ? sb->qcast : q_dev, sb->qscale, 0.0, seg_vals));
 
     // head of the sorted stream
     OutArg od, os, ot;
@@ -1297,6 +1156,99 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
 int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes, int k, float *out_dist,
                    int64_t *out_slot, uint64_t *out_tid) {
     return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, nullptr);
+}
+
+int pgv_scan_lists(pgv_index *ix, const void *query, const int32_t *lists, int nlists,
+                   float *out_dist, int64_t *out_slot, int64_t capacity, int64_t *out_count) {
+    if (!ix || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_scan_lists: index/out_count is NULL");
+    if (nlists < 0 || (nlists > 0 && !lists)) PGV_FAIL(PGV_ERR_ARG, "bad list array");
+    pgv_ctx *ctx = ix->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+
+    std::vector<int32_t> hl((size_t)nlists);
+    if (nlists) {
+        if (is_device_ptr(lists))
+            PGV_HIP(hipMemcpy(hl.data(), lists, sizeof(int32_t) * (size_t)nlists, hipMemcpyDeviceToHost));
+        else
+            memcpy(hl.data(), lists, sizeof(int32_t) * (size_t)nlists);
+    }
+    int64_t m = 0;
+    for (int p = 0; p < nlists; p++) {
+        if (hl[p] < 0 || hl[p] >= ix->nlists) PGV_FAIL(PGV_ERR_ARG, "list id %d out of range", hl[p]);
+        m += ix->h_offsets[hl[p] + 1] - ix->h_offsets[hl[p]];
+    }
+    *out_count = m;
+    if (m > capacity) PGV_FAIL(PGV_ERR_ARG, "output capacity %lld < %lld tuples", (long long)capacity, (long long)m);
+    if (m == 0) return PGV_OK;
+    if (!out_dist || !out_slot) PGV_FAIL(PGV_ERR_ARG, "out_dist/out_slot is NULL");
+
+    OutArg od, os;
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)m, ctx->out_stage));
+    PGV_TRY(os.init(out_slot, sizeof(int64_t) * (size_t)m, ctx->out_stage2));
+
+    // plan on the host: per probed list a run of chunks, all for the one query -- the batch's list kernels with one pair
+    // per task
+    ScanPath path;
+    path.bits = ix->nbits > 0;
+    path.qt = path.bits ? hamming_list_group_size(1.0) : 1;
+    path.rows_per_task = path.bits ? hamming_list_rows_per_task() : rows_per_task_for(ctx, m, 1);
+    const int ch = path.rows_per_task;
+    int64_t ntasks = 0;
+    for (int p = 0; p < nlists; p++) {
+        int64_t len = ix->h_offsets[hl[p] + 1] - ix->h_offsets[hl[p]];
+        ntasks += (len + ch - 1) / ch;
+    }
+    const size_t tb = sizeof(ScanTask) * (size_t)ntasks, pb = sizeof(ScanPair) * (size_t)nlists,
+                 ob = sizeof(int64_t) * (size_t)nlists, lb = sizeof(int32_t) * (size_t)nlists;
+    PGV_TRY(staging_acquire(ctx));
+    PGV_TRY(ctx->h_a.ensure(tb + pb + ob + lb + 16));
+    char *hb = ctx->h_a.as<char>();
+    ScanTask *ht = reinterpret_cast<ScanTask *>(hb);
+    ScanPair *hp = reinterpret_cast<ScanPair *>(hb + tb);
+    int64_t *hoff = reinterpret_cast<int64_t *>(hb + tb + pb);
+    int32_t *hlist = reinterpret_cast<int32_t *>(hb + tb + pb + ob);
+    int *hn = reinterpret_cast<int *>(hb + tb + pb + ob + lb);
+    int64_t t = 0, run = 0;
+    for (int p = 0; p < nlists; p++) {
+        const int64_t beg = ix->h_offsets[hl[p]], len = ix->h_offsets[hl[p] + 1] - beg;
+        hp[p].out_rel = run - beg;
+        hp[p].query = 0;
+        hp[p].pad = 0;
+        hoff[p] = run;
+        hlist[p] = hl[p];
+        for (int64_t c = 0; c * ch < len; c++) {
+            ht[t].row0 = beg + c * ch;
+            int64_t left = len - c * ch;
+            ht[t].nrows = (int)(left < ch ? left : ch);
+            ht[t].pair0 = p;
+            ht[t].npairs = 1;
+            ht[t].pad = 0;
+            t++;
+        }
+        run += len;
+    }
+    *hn = (int)ntasks;
+    const size_t total = tb + pb + ob + lb + 16;
+    PGV_TRY(ctx->tasks.ensure(total));
+    PGV_HIP(hipMemcpyAsync(ctx->tasks.p, hb, total, hipMemcpyHostToDevice, ctx->stream));
+    char *db = ctx->tasks.as<char>();
+
+    PGV_TRY(launch_iota_slots(ctx, ix, reinterpret_cast<int32_t *>(db + tb + pb + ob), nlists,
+                              reinterpret_cast<int64_t *>(db + tb + pb), os.as<int64_t>()));
+    if (query == nullptr) {
+        // ZeroDistance (src/ivfscan.c:192-196): every tuple at distance 0
+        PGV_HIP(hipMemsetAsync(od.dev, 0, sizeof(float) * (size_t)m, ctx->stream));
+    } else {
+        const void *q_dev;
+        PGV_TRY(stage_queries(ix, query, 1, &q_dev));
+        const ScanWork work{reinterpret_cast<ScanTask *>(db), reinterpret_cast<int *>(db + tb + pb + ob + lb), (int)ntasks,
+                            reinterpret_cast<ScanPair *>(db + tb)};
+        PGV_TRY(list_scan_step(ix, path, work, q_dev, nullptr, (double)m, od.as<float>()));
+    }
+    bool need = true;  // h_a must be consumed before the next call rewrites it
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(os.finish(ctx, &need));
+    return sync_if(ctx, need);
 }
 
 int check_batch_args(pgv_index *ix, const void *queries, int nq, int probes, int k, float *out_dist,
@@ -1458,7 +1410,7 @@ int pgv_query_begin(pgv_index *ix, pgv_query **out) {
     q->ix = ix;
     const int cap = query_head_cap();
     const size_t state_bytes = sizeof(int32_t) * (size_t)cap + sizeof(float) * ((size_t)ix->nlists + 4);  // + one float4 of slack
-    const size_t row_bytes = (size_t)ix->geom.ld * elem_size(ix->dtype);
+    const size_t row_bytes = ivf_rows(ix).row_bytes();
     q->head_bytes = query_head_bytes(cap);
     int rc = q->state.ensure(state_bytes);
     if (rc == PGV_OK) rc = q->q_dev.ensure(row_bytes);
@@ -1513,19 +1465,18 @@ int pgv_query_rank(pgv_query *q, const void *query, int max_probes) {
     q->is_null = query == nullptr;
     q->cur_n = 0;
     if (q->is_null) return launch_query_iota(ctx, q->lists, max_probes);
-    const size_t es = elem_size(ix->dtype);
-    const size_t row_bytes = (size_t)ix->geom.ld * es;
+    const size_t tight = (size_t)ix->dim * elem_size(ix->dtype), row_bytes = ivf_rows(ix).row_bytes();
     if (is_device_ptr(query)) {
         PGV_HIP(hipMemsetAsync(q->q_dev.p, 0, row_bytes, ctx->stream));
-        PGV_HIP(hipMemcpyAsync(q->q_dev.p, query, (size_t)ix->dim * es, hipMemcpyDeviceToDevice, ctx->stream));
+        PGV_HIP(hipMemcpyAsync(q->q_dev.p, query, tight, hipMemcpyDeviceToDevice, ctx->stream));
         q->q_row = q->q_dev.p;
     } else {
         // the previous query's kernels have finished reading q_pinned: every pgv_query_scan waits for its head
         // (a rank that no scan followed is waited for here)
         if (q->rank_pending) PGV_HIP(hipStreamSynchronize(ctx->stream));
         void *dst = q->q_direct ? q->q_direct : q->q_pinned;
-        memcpy(dst, query, (size_t)ix->dim * es);
-        if (row_bytes > (size_t)ix->dim * es) memset(static_cast<char *>(dst) + (size_t)ix->dim * es, 0, row_bytes - (size_t)ix->dim * es);
+        memcpy(dst, query, tight);
+        if (row_bytes > tight) memset(static_cast<char *>(dst) + tight, 0, row_bytes - tight);
         if (q->q_direct) {
             // the stores drain to the device ahead of the doorbell write of the launch below (posted writes, in order)
             __builtin_ia32_sfence();

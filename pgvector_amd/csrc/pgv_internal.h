@@ -84,8 +84,9 @@ RowGeom row_geom(int dim, pgv_dtype t);
 // mirror (pgv_hnsw::nbits); ld is the padded row length in BYTES
 RowGeom bit_row_geom(int nbits);
 
-// Rows as the scoring kernels and the HNSW walk take them: where they are, how many, how a row is laid out, what an
-// element is and which distance goes with it.  Built where it is needed (hnsw_rows for a mirror), never stored
+// Rows as the scoring and scan kernels and the HNSW walk take them: where they are, how many, how a row is laid out,
+// what an element is and which distance goes with it.  Built where it is needed (hnsw_rows / ivf_rows and its kin for a
+// mirror, in place for a caller's staged rows), never stored
 enum class RowKind { F32, F16, Bits };  // Bits: packed bit strings scored by xor + popcount; the metric is unused
 struct RowsView {
     const void *rows;  // [n x geom.nvec] 16-byte vectors
@@ -95,6 +96,7 @@ struct RowsView {
     pgv_metric metric;
     bool bits() const { return kind == RowKind::Bits; }
     pgv_dtype dtype() const { return kind == RowKind::F16 ? PGV_F16 : PGV_F32; }
+    size_t row_bytes() const { return bits() ? (size_t)geom.ld : (size_t)geom.ld * elem_size(dtype()); }
 };
 inline RowKind row_kind(pgv_dtype t) { return t == PGV_F16 ? RowKind::F16 : RowKind::F32; }
 
@@ -125,6 +127,13 @@ struct ScanPair {
     int64_t out_rel;
     int32_t query;
     int32_t pad;
+};
+// the work of one planned launch (a PlanResult's, the dense plan's, pgv_scan_lists's host plan); all device arrays
+struct ScanWork {
+    const ScanTask *tasks;
+    const int *ntasks_dev;  // how many of them there are
+    int ntasks_bound;       // ... at most, known on the host
+    const ScanPair *pairs;
 };
 
 }  // namespace pgv
@@ -191,7 +200,8 @@ struct pgv_index {
     int dim = 0;
     // > 0: a mirror of `USING ivfflat (col bit_hamming_ops)` (pgv_index_upload_bits).  Its element type is not a pgv_dtype:
     // centers and rows are nbits bits in geom.nvec 16-byte vectors (geom.ld BYTES), scored by xor + popcount; metric and
-    // dtype are unused (dim = nbits), and there are no norms and no shadow
+    // dtype are placeholders (dim = nbits) that stop mattering in ivf_rows: the kernels get RowKind::Bits from there.
+    // There are no norms and no shadow
     int nbits = 0;
     int nlists = 0;
     int64_t nrows = 0;
@@ -285,6 +295,21 @@ namespace pgv {
 // a mirror's rows as its kernels take them
 inline RowsView hnsw_rows(const pgv_hnsw *h) {
     return {h->elements, h->n, h->geom, h->nbits > 0 ? RowKind::Bits : row_kind(h->dtype), h->metric};
+}
+// ... an IVFFlat mirror's: the only place that turns pgv_index::nbits into a row kind
+inline RowsView ivf_rows(const pgv_index *ix) {
+    return {ix->vectors, ix->nrows, ix->geom, ix->nbits > 0 ? RowKind::Bits : row_kind(ix->dtype), ix->metric};
+}
+inline RowsView ivf_centers(const pgv_index *ix) {
+    RowsView v = ivf_rows(ix);
+    v.rows = ix->centers;
+    v.n = ix->nlists;
+    return v;
+}
+// ... and the fp16 residual shadow of its rows and the fp16 copy of its centers (null rows when not built)
+inline RowsView ivf_shadow_rows(const pgv_index *ix) { return {ix->shadow, ix->nrows, ix->shadow_geom, RowKind::F16, ix->metric}; }
+inline RowsView ivf_shadow_centers(const pgv_index *ix) {
+    return {ix->cshadow, ix->nlists, ix->shadow_geom, RowKind::F16, ix->metric};
 }
 }  // namespace pgv
 
@@ -453,10 +478,7 @@ inline ExpansionBound argmin_bound(const pgv_ctx *ctx, int dim) {
 
 // ---------------------------------------------------------------- launchers
 // kernels_scan.hip: stream rows, score them against small groups of queries
-int launch_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-                const void *rows, const void *queries, const ScanTask *tasks,
-                const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt,
-                float *out);
+int launch_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, int qt, float *out);
 int scan_group_size(const RowGeom &g, pgv_dtype dtype, int wanted);
 // gathered variant (HNSW candidate scoring): pair i = (slot[i], query_of[i])
 int launch_score_gather(pgv_ctx *ctx, const RowsView &v, const void *queries, const int32_t *slot, const int32_t *query_of,
@@ -478,17 +500,20 @@ int launch_bit_distance(pgv_ctx *ctx, int mode, const RowGeom &g, const void *ro
                         double *out);
 
 // kernels_bit.hip: binary quantization.  The Hamming distances of every query x every row in 256-row x 32-query tiles
-// (pgv_bit_topk): rows [n x nvec] 16-byte vectors, queries [nq x qbytes] with qbytes a multiple of
-// bit_topk_slice_bytes(), both zero padded; out[q * n + row]
+// (pgv_bit_topk): bit rows, queries [nq x qbytes] with qbytes a multiple of bit_topk_slice_bytes() (bit_query_bytes of
+// the rows' length, or more), both zero padded; out[q * n + row]
 int bit_topk_slice_bytes();
-int launch_hamming_tiles(pgv_ctx *ctx, const void *rows, int nvec, int64_t n, const void *queries, int qbytes, int nq,
-                         float *out);
+inline int bit_query_bytes(int nbits) {
+    const int slice = bit_topk_slice_bytes();
+    return ((nbits + 7) / 8 + slice - 1) / slice * slice;
+}
+int launch_hamming_tiles(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, int nq, float *out);
 // the list scan of a bit index (pgv_index::nbits): the plan of launch_plan_batch with 256 rows per task and qt queries per
 // group (hamming_list_group_size), the same rows and queries as launch_hamming_tiles; out[pair.out_rel + row]
 int hamming_list_group_size(double queries_per_list);
 int hamming_list_rows_per_task();
-int launch_hamming_lists(pgv_ctx *ctx, const void *rows, int nvec, const void *queries, int qbytes, const ScanTask *tasks,
-                         const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, int qt, float *out);
+int launch_hamming_lists(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const ScanWork &w, int qt,
+                         float *out);
 // the bit k-means' build side.  launch_bit_closest: row j of a chunk's distance matrix mat[j * k + c] (launch_hamming_tiles
 // with the samples as queries) and its first minimum (best_val / best_pos, launch_topk_segments with k = 1) -> closest_io[j]:
 // sticky and closest_io[j] >= 0: the current center unless best_val is strictly smaller; else best_pos.  counts[new] += 1,
@@ -533,9 +558,7 @@ int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int
 bool tile_scan_supported(const RowGeom &g);
 int tile_scan_queries_per_task();
 int tile_scan_tile_rows(const RowGeom &g);
-int launch_tile_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
-                     const void *rows, const void *queries, const ScanTask *tasks,
-                     const int *ntasks_dev, int ntasks_bound, const ScanPair *pairs, float *out);
+int launch_tile_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, float *out);
 
 // kernels_pair.hip: n rows x k centers, both large: argmin per row
 int launch_argmin(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g,
@@ -590,12 +613,10 @@ int mfma_scan_queries_per_task();
 int launch_mfma_dense(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n,
                       const void *queries, int nq, const float *row_norms, float *out, int64_t out_stride);
 int dense_chain_length(const RowGeom &g, pgv_dtype dtype);  // products per accumulator chain, at most
-int launch_row_norms(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n, float *out,
-                     unsigned *max_bits);
-int launch_mfma_scan(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows,
-                     const void *queries, const ScanTask *tasks, const int *ntasks_dev, int ntasks_bound,
-                     const ScanPair *pairs, const float *row_norms, const float *query_norms, float *out, bool stream_rows,
-                     int queries_per_task = 32, const float *shadow_scale = nullptr);
+int launch_row_norms(pgv_ctx *ctx, const RowsView &v, float *out, unsigned *max_bits);
+int launch_mfma_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, const float *row_norms,
+                     const float *query_norms, float *out, bool stream_rows, int queries_per_task = 32,
+                     const float *shadow_scale = nullptr);
 // kernels_shadow.hip: the fp16 residual shadow of an fp32 L2 index (pgv_index::shadow) and its per-batch terms.
 // words: 24 device bytes, [0] bits of the largest |x_i - c_i|, [8] / [16] bits of the largest E^2 / P^2 (fp64)
 int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *rows, const void *centers,
@@ -634,6 +655,7 @@ struct PlanResult {
     int64_t *seg_start = nullptr; // device [nq + 1]
     int64_t *probe_off = nullptr; // device [nq x probes]
     int64_t *pair_start = nullptr; // device [nlists + 1]: the first pair of each list
+    ScanWork work() const { return {tasks, ntasks_dev, (int)ntasks_bound, pairs}; }
 };
 // the plan's device scratch of one batch (ctx->plan_a / plan_b, carved)
 struct PlanBuffers {
@@ -718,8 +740,7 @@ int launch_multi_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int 
                       int64_t rows_bound, float *seg, int64_t seg_stride, int k, float *out_dist, int64_t *out_slot,
                       uint64_t *out_tid);
 int launch_query_iota(pgv_ctx *ctx, int32_t *out, int n);
-int launch_one_query_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows, int n,
-                          const void *q_dev, float *out);
+int launch_one_query_rows(pgv_ctx *ctx, const RowsView &v, const void *q_dev, float *out);  // v.n < 2^31
 int launch_query_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, float *cdist, int max_probes,
                       int32_t *out_lists);
 int launch_query_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, const int32_t *probe_lists, int nprobes,

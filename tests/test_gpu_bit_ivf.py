@@ -289,6 +289,47 @@ def test_entries_that_refuse_a_bit_index(ctx):
     fx.close()
 
 
+# ------------------------------------------------------------------------------------------------ both Hamming kernels
+@pytest.mark.parametrize("n", [1, TASK_ROWS - 1, TASK_ROWS, TASK_ROWS + 1, 2 * TASK_ROWS + 1])
+@pytest.mark.parametrize("nbits", [1, SLICE_BITS - 1, SLICE_BITS, SLICE_BITS + 1, 1536])
+def test_tile_and_list_kernels_count_alike(ctx, nbits, n):
+    """hamming_tile_kernel and hamming_list_kernel walk a tile of rows the same way (kernels_bit.hip): over ONE set
+    of packed rows and queries, the distances of pgv_bit_topk's matrix (read back through k = n: the matrix itself
+    is not exposed) equal, as integers, those pgv_scan_lists streams from a bit index that holds the rows in two
+    lists, split at a row count that is no multiple of 256 -- and both equal tests/bit_model.py. One bit, one below
+    / at / one above the register slice and a slice and a half; one row, one below / at / one above the 256-row tile
+    and two tiles and a row; 1, 9 and 33 queries: a lone query, a query group with a clamped tail and two 32-query
+    tiles. pgv_scan_lists scores one query a call (groups of 8, one pair live); the same index's pgv_scan_batch with
+    both lists probed by every query adds the groups of 8, 16 and 32 with live tails (hamming_list_group_size at
+    shares 1, 9 and 33)"""
+    rows = im.rand_bits(n, nbits, 300 + n)
+    queries = im.rand_bits(33, nbits, 400 + nbits % 89)
+    want = np.stack([bm.hamming(q, rows) for q in queries])
+    split = 300 if n > 300 else (n + 1) // 2
+    assert split % TASK_ROWS != 0
+    ix = api.BitIvfIndex(ctx, nbits, im.rand_bits(2, nbits, 301), np.array([0, split, n]), rows)
+
+    def as_matrix(dist, pos):
+        """sorted or streamed (distance, row) pairs of each query -> int64 [nq x n], every row exactly once"""
+        assert np.array_equal(np.sort(pos, axis=1), np.tile(np.arange(n), (pos.shape[0], 1)))
+        assert np.array_equal(dist, np.rint(dist))
+        mat = np.empty(pos.shape, dtype=np.int64)
+        np.put_along_axis(mat, pos, dist.astype(np.int64), axis=1)
+        return mat
+
+    for nq in (1, 9, 33):
+        qs = np.ascontiguousarray(queries[:nq])
+        tiles = as_matrix(*api.bit_topk(ctx, nbits, qs, rows, n))
+        streams = [ix.scan_lists(q, [0, 1]) for q in qs]
+        lists = as_matrix(np.stack([d for d, _ in streams]), np.stack([s for _, s in streams]))
+        dist, slot, _ = ix.scan_batch(qs, np.tile(np.array([0, 1], dtype=np.int32), (nq, 1)), n)
+        groups = as_matrix(dist, slot)
+        assert np.array_equal(tiles, lists), (nq, np.argwhere(tiles != lists)[:5].tolist())
+        assert np.array_equal(tiles, groups), (nq, np.argwhere(tiles != groups)[:5].tolist())
+        assert np.array_equal(tiles, want[:nq]), (nq, np.argwhere(tiles != want[:nq])[:5].tolist())
+    ix.close()
+
+
 # ------------------------------------------------------------------------------------------------ pgv_bit_assign
 @pytest.mark.parametrize("k,n,nbits", [(1, 1, 1), (2, 255, 9), (33, 256, 128), (1000, 257, 1025), (33, 3000, 9), (1000, 3000, 128),
                                        (2, 3000, 1), (1, 257, 1025)])
