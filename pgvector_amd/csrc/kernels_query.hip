@@ -946,7 +946,8 @@ int launch_exact_tail(pgv_ctx *ctx, const ExactTail &t, DBuf &scratch) {
     // flags[nq], the flagged-query count, starts from zero; so do the plan's cnt | fill under emit (one word per list
     // each; the ranking's rows are the centers: fixed_len lists)
     PGV_TRY(launch_topk_segments(ctx, t.approx, seg_start, t.nq, fixed_len, t.kprime, sc.cand_val, sc.cand_pos,
-                                 sc.flags + t.nq, t.emit.cnt, t.emit.cnt ? 2 * (int)fixed_len : 0));
+                                 sc.flags + t.nq, t.emit.cnt, t.emit.cnt ? 2 * (int)fixed_len : 0,
+                                 dense ? 0 : t.seg_bound));
 #define PGV_RECHECK(T, DOT)                                                                                          \
     hipLaunchKernelGGL((batch_recheck_kernel<T, DOT>), dim3(t.nq), dim3(kQThreads), 0, ctx->stream,                   \
                        static_cast<const char *>(xr.vectors), xr.tids, xr.geom.nvec, xr.geom.lpr_log2,                \

@@ -4,7 +4,7 @@
 //     that probe it, cut into ScanTasks, plus where each (query, list) run of
 //     distances lands in the query's output segment -- the order the reference
 //     feeds its tuplesort (src/ivfscan.c:134-179).
-//   * topk_kernel: the head of the ascending tuplesort stream
+//   * topk_kernel<class>: the head of the ascending tuplesort stream
 //     (src/ivfscan.c:182, :238-247) / the bounded heap of GetScanLists
 //     (:76-106): k smallest of a segment by (value, position), exact and
 //     deterministic (radix select on order-preserving keys, then a bitonic sort
@@ -214,8 +214,42 @@ __global__ void plan_pairs_tasks_kernel(const int32_t *__restrict__ probe_lists,
 __device__ __forceinline__ bool dist_before(float a, float b) { return float_to_key(a) < float_to_key(b); }
 
 // ------------------------------------------------------------------- top-k
-// block_topk (pgv_select.h) does the work; this kernel runs it for one segment per workgroup
+// block_topk_small / block_topk (pgv_select.h) do the work; these kernels run them for one segment per workgroup.
+//
+// One kernel per CLASS of segment length.  A batch launches a workgroup per query, a thousand at once, and what
+// counts then is how many of them a CU holds: a kernel is allocated the registers of the largest form it CONTAINS,
+// whether a launch runs that form or not (block_topk_auto's four forms in one kernel: 161 VGPRs, 3 waves per SIMD --
+// right for the lone workgroup of the single-query path, which it still serves).  So every class contains only the
+// forms its segments can take, and the host picks the class from an upper bound on the segment length
+// (launch_topk_segments):
+//   small   m + skip <= 1024    form 1
+//   medium  m + skip <= 4096    forms 1 / 4
+//   long    anything            forms 4 / 12 / 16 resident, and 16 resident + up to 16 transient vectors: 32 768
+// Every class falls back to block_topk (long runs of equal keys, too few finite values, k > 128, a segment longer
+// than its forms), so a wrong bound costs time, never the result.
+enum TopkClass { kTopkSmall = 0, kTopkMedium = 1, kTopkLong = 2 };
+constexpr int kLongVec = 16;   // float4 per thread the long class keeps
+constexpr int kLongTail = 16;  // ... and at most as many again fetched per sweep behind them
+constexpr int kLongMax = (kLongVec + kLongTail) * 4 * kSelThreads;  // 32768
 
+template <int CLS>
+__device__ __forceinline__ bool topk_class_forms(const float *va, int ma, int skip, int k, int kp, int cap,
+                                                 unsigned long long *ent, SelShared *s) {
+    if constexpr (CLS == kTopkSmall) {
+        if (ma <= 4 * kSelThreads) return block_topk_small<1>(va, ma, skip, k, kp, cap, ent, s);
+    } else if constexpr (CLS == kTopkMedium) {
+        if (ma <= 4 * kSelThreads) return block_topk_small<1>(va, ma, skip, k, kp, cap, ent, s);
+        if (ma <= 16 * kSelThreads) return block_topk_small<4>(va, ma, skip, k, kp, cap, ent, s);
+    } else {
+        if (ma <= 16 * kSelThreads) return block_topk_small<4>(va, ma, skip, k, kp, cap, ent, s);
+        if (ma <= kSmallVec * 4 * kSelThreads) return block_topk_small<kSmallVec>(va, ma, skip, k, kp, cap, ent, s);
+        if (ma <= kLongVec * 4 * kSelThreads) return block_topk_small<kLongVec>(va, ma, skip, k, kp, cap, ent, s);
+        if (ma <= kLongMax) return block_topk_small<kLongVec, kLongTail>(va, ma, skip, k, kp, cap, ent, s);
+    }
+    return false;
+}
+
+template <int CLS>
 __global__ __launch_bounds__(kSelThreads) void topk_kernel(
     const float *__restrict__ vals, const int64_t *__restrict__ seg_start, int64_t fixed_len,
     int k, int kp, int cap, float *__restrict__ out_val, int64_t *__restrict__ out_pos,
@@ -235,7 +269,14 @@ __global__ __launch_bounds__(kSelThreads) void topk_kernel(
     const int64_t base = seg_start ? seg_start[seg] : (int64_t)seg * fixed_len;
     const int64_t m = seg_start ? seg_start[seg + 1] - base : fixed_len;
     const float *v = vals + base;
-    block_topk_auto(v, m, k, kp, cap, ent, s);  // segments up to 20 480 values: one trip to memory, selection from registers
+    // v may start anywhere (a segment of a packed stream): the vector loads start at the 16-byte boundary below it
+    // (block_topk_auto's contract: 3 floats in front of a ragged v and (m + 3) & ~3 from the boundary on are readable)
+    bool done = false;  // block-uniform
+    const int skip = (int)((reinterpret_cast<uintptr_t>(v) >> 2) & 3);
+    const int64_t ma = m + skip;
+    if (m > k && ma <= kLongMax && k <= kSelThreads / 2)
+        done = topk_class_forms<CLS>(v - skip, (int)ma, skip, k, kp, cap, ent, s);
+    if (!done) block_topk([v](int64_t i) { return v[i]; }, m, k, kp, cap, ent, s);
 
     for (int i = threadIdx.x; i < k; i += kSelThreads) {
         const unsigned long long e = ent[i];
@@ -468,7 +509,7 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
 
 int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_start, int nseg,
                          int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word,
-                         int32_t *zero_range, int zero_n) {
+                         int32_t *zero_range, int zero_n, int64_t len_bound) {
     if (nseg <= 0 || k <= 0) return PGV_OK;
     if (k > 4096) PGV_FAIL(PGV_ERR_ARG, "top-k: k = %d exceeds the supported 4096", k);
     int kp = 1;
@@ -476,8 +517,20 @@ int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_sta
     if (kp < 2) kp = 2;
     const int cap = kp > kFastCap ? kp : kFastCap;
     const size_t lds = (size_t)cap * 8 + sizeof(SelShared);
-    hipLaunchKernelGGL(topk_kernel, dim3(nseg), dim3(kSelThreads), lds, ctx->stream, vals,
-                       seg_start, fixed_len, k, kp, cap, out_val, out_pos, zero_word, zero_range, zero_n);
+    // the class: from the longest run of values a workgroup may have to load, the ragged front (`skip`) counted in.
+    // Fixed-length segments are their own bound, and start where vals does when their length is whole float4s.
+    int64_t ma_bound = 0;  // 0: not known
+    if (!seg_start)
+        ma_bound = fixed_len + (fixed_len % 4 == 0 ? (int64_t)((reinterpret_cast<uintptr_t>(vals) >> 2) & 3) : 3);
+    else if (len_bound > 0)
+        ma_bound = len_bound + 3;
+    auto kernel = topk_kernel<kTopkLong>;
+    if (ma_bound > 0 && ma_bound <= 4 * kSelThreads)
+        kernel = topk_kernel<kTopkSmall>;
+    else if (ma_bound > 0 && ma_bound <= 16 * kSelThreads)
+        kernel = topk_kernel<kTopkMedium>;
+    hipLaunchKernelGGL(kernel, dim3(nseg), dim3(kSelThreads), lds, ctx->stream, vals, seg_start, fixed_len, k, kp, cap,
+                       out_val, out_pos, zero_word, zero_range, zero_n);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

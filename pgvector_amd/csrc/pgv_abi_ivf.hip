@@ -1134,6 +1134,7 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
         tail.probe_off = plan.probe_off;
         tail.probes = probes;
         tail.seg_start = plan.seg_start;
+        tail.seg_bound = ix->len_prefix[probes];  // rows of the `probes` longest lists
         tail.bound = scan_bound_chain(ctx, ix->geom.ld, scan_chain_length(ix->geom, ix->dtype, path.wide));
         if (path.shadow) tail.bound = shadow_band(ix->geom.ld, tail.bound.g_ref);
         tail.eps_add = path.shadow ? sb->qeps : nullptr;
@@ -1142,7 +1143,8 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
         tail.out_tid = ot.as<uint64_t>();
         PGV_TRY(launch_exact_tail(ctx, tail, ctx->ms_a));
     } else {
-        PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, k, od.as<float>(), pos));
+        PGV_TRY(launch_topk_segments(ctx, seg_vals, plan.seg_start, nq, 0, k, od.as<float>(), pos, nullptr, nullptr, 0,
+                                     ix->len_prefix[probes]));
         PGV_TRY(launch_positions_to_slots(ctx, ix, probe_lists, plan.probe_off, nq, probes, k, pos,
                                           os.as<int64_t>(), ot.as<uint64_t>()));
     }

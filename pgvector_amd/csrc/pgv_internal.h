@@ -680,9 +680,12 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
                       int probes, int qt, int rows_per_task, bool read_totals, PlanResult *res,
                       const float *pair_t = nullptr, bool counted = false);
 // zero_word / zero_range[zero_n]: words that kernels LATER in the stream start from zero, cleared here (or null)
+// len_bound: with seg_start, a length no segment exceeds, known on the host (a list plan: len_prefix[probes]), or 0.
+// It picks the kernel -- small (<= 1024 values), medium (<= 4096) or long -- and nothing else: a segment past its
+// class's forms takes the general path.  fixed_len is its own bound
 int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_start, int nseg,
                          int64_t fixed_len, int k, float *out_val, int64_t *out_pos, int32_t *zero_word = nullptr,
-                         int32_t *zero_range = nullptr, int zero_n = 0);
+                         int32_t *zero_range = nullptr, int zero_n = 0, int64_t len_bound = 0);
 int launch_positions_to_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists,
                               const int64_t *probe_off, int nq, int probes, int k,
                               const int64_t *pos, int64_t *out_slot, uint64_t *out_tid);
@@ -711,6 +714,7 @@ struct ExactTail {
     const int64_t *probe_off = nullptr;    // list plan: [nq x probes] where each list starts inside its query's segment
     int probes = 0;                        // list plan: lists per query
     const int64_t *seg_start = nullptr;    // list plan: [nq + 1] where each query's segment starts in approx
+    int64_t seg_bound = 0;                 // list plan: rows no segment exceeds (len_prefix[probes]), or 0: not known
     int64_t fixed_len = 0;                 // dense run: rows per query; approx is [nq x fixed_len]
     ScanBound bound{};                     // the rounding bound of the kernel that produced approx
     const float *eps_add = nullptr;        // [nq] per-query term added to the band (the shadow paths), or null

@@ -6,8 +6,8 @@
 // deterministic refinement of tuplesort's unspecified tie order; for GetScanLists it IS the
 // reference's rule: the strict `<` at :92 keeps the earlier list).
 //
-// Shared by topk_kernel (kernels_select.hip: one segment per workgroup) and the single-query
-// kernels (kernels_query.hip: the last workgroup to finish selects).
+// Shared by the topk_kernel classes (kernels_select.hip: one segment per workgroup) and the
+// single-query kernels (kernels_query.hip: the last workgroup to finish selects).
 #pragma once
 
 #include "pgv_device.h"
@@ -285,13 +285,18 @@ constexpr int kSmallVec = 12;
 // five were over the old limit and took the general path's two sweeps from memory)
 constexpr int kLargeVec = 20;
 constexpr int kSmallMax = kLargeVec * 4 * kSelThreads;  // 20480
+constexpr int kTailGroup = 2;  // transient float4 in flight per thread and trip of block_topk_small's tail
 constexpr int kExtractMax = 16;  // k up to which the threshold comes from per-wavefront extraction
 
 // NVEC float4 per thread: 1 (m <= 1024: the centers of a typical index), 4 (m <= 4096) or 12.  Returns false when the
 // general path has to run instead (long runs of equal keys, or too few finite values).
 // `skip` (0..3): v is the segment's start rounded DOWN to 16 bytes, its first `skip` floats belong to whoever is in front
 // (they read as +inf and positions are counted from the segment's own first element); m counts them in.
-template <int NVEC>
+// NTAIL > 0 (the batch's long class, kernels_select.hip): up to NTAIL more float4 per thread behind the resident NVEC
+// that are NOT kept -- as many as m needs; each sweep fetches them again (cache hits the second time), kTailGroup at a
+// time, and lets them go, so a segment of up to (NVEC + NTAIL) * 1024 values is selected at the register cost of NVEC.
+// Same clamped addressing, same result.
+template <int NVEC, int NTAIL = 0>
 __device__ __forceinline__ bool block_topk_small(const float *v, int m, int skip, int k, int kp, int cap,
                                                  unsigned long long *ent, SelShared *s) {
     // A lone workgroup runs at whatever clock an otherwise idle chip grants: what counts here is the
@@ -307,8 +312,33 @@ __device__ __forceinline__ bool block_topk_small(const float *v, int m, int skip
         const int at = b * 4 * kSelThreads + 4 * (int)threadIdx.x;
         r[b] = *reinterpret_cast<const float4 *>(v + (at < last4 ? at : last4));
     }
+    // the transient tail: vector NVEC + j of this thread, its ragged end read as +inf
+    auto tail_at = [](int j) { return (NVEC + j) * 4 * kSelThreads + 4 * (int)threadIdx.x; };
+    auto tail_load = [&](int j) {
+        const int at = tail_at(j);
+        float4 t = *reinterpret_cast<const float4 *>(v + (at < last4 ? at : last4));
+        if (at + 0 >= m) t.x = INFINITY;
+        if (at + 1 >= m) t.y = INFINITY;
+        if (at + 2 >= m) t.z = INFINITY;
+        if (at + 3 >= m) t.w = INFINITY;
+        return t;
+    };
+    (void)tail_load;
     // values past m read as +inf from here on; NaN never wins a float minimum (it sorts last anyway)
     float fmine = INFINITY;
+    // tail vectors this segment has (block-uniform; a last group's spare vector is clamped and reads as +inf)
+    const int ntail = NTAIL > 0 ? (m - NVEC * 4 * kSelThreads + 4 * kSelThreads - 1) / (4 * kSelThreads) : 0;
+    if constexpr (NTAIL > 0) {
+        static_assert(NTAIL % kTailGroup == 0 && NTAIL <= 16, "whole groups; one bit of a 64-bit mask per tail value");
+#pragma unroll 1
+        for (int j0 = 0; j0 < ntail; j0 += kTailGroup) {
+            float4 t[kTailGroup];
+#pragma unroll
+            for (int j = 0; j < kTailGroup; j++) t[j] = tail_load(j0 + j);
+#pragma unroll
+            for (int j = 0; j < kTailGroup; j++) fmine = fminf(fminf(fmine, fminf(t[j].x, t[j].y)), fminf(t[j].z, t[j].w));
+        }
+    }
 #pragma unroll
     for (int b = 0; b < NVEC; b++) {
         const int at = b * 4 * kSelThreads + 4 * (int)threadIdx.x;
@@ -382,11 +412,50 @@ __device__ __forceinline__ bool block_topk_small(const float *v, int m, int skip
         // 64 returning atomics on one LDS word, each inside a divergent branch, cost more than the sweep
         const float t0f = key_to_float(t0);
         unsigned cnt = 0;
+        unsigned long long tail_mask = 0;  // bit 4 j + c: value c of tail vector j is a candidate
+        if constexpr (NTAIL > 0) {
+#pragma unroll 1
+            for (int j0 = 0; j0 < ntail; j0 += kTailGroup) {
+                float4 t[kTailGroup];
 #pragma unroll
-        for (int b = 0; b < NVEC; b++)
+                for (int j = 0; j < kTailGroup; j++) t[j] = tail_load(j0 + j);
+#pragma unroll
+                for (int j = 0; j < kTailGroup; j++)
+                    tail_mask |= (unsigned long long)((t[j].x <= t0f ? 1u : 0u) | (t[j].y <= t0f ? 2u : 0u) |
+                                                      (t[j].z <= t0f ? 4u : 0u) | (t[j].w <= t0f ? 8u : 0u))
+                                 << (4 * (j0 + j));
+            }
+            cnt = __popcll(tail_mask);
+        }
+#pragma unroll
+        for (int b = 0; b < NVEC; b++) {
             cnt += (r[b].x <= t0f) + (r[b].y <= t0f) + (r[b].z <= t0f) + (r[b].w <= t0f);
+            // (the tail form's register peak is here: left alone the compiler turns the comparisons into 0 / 1
+            // registers eight at a time before it adds them -- 133 VGPRs, 3 waves per SIMD; with the sum pinned
+            // after every vector 125 and 4)
+            if constexpr (NTAIL > 0) asm volatile("" : "+v"(cnt));
+        }
         if (cnt) {
             unsigned slot = atomicAdd(&s->count, cnt);
+            if constexpr (NTAIL > 0) {
+                // the few threads with a candidate in the tail fetch that vector a third time (rolled: rare, short)
+#pragma unroll 1
+                for (unsigned long long left = tail_mask; left;) {
+                    const int j = (__ffsll(left) - 1) >> 2;
+                    const unsigned bits = (unsigned)(left >> (4 * j)) & 15u;
+                    left &= ~(15ull << (4 * j));
+                    const int at = tail_at(j);
+                    const float4 t = *reinterpret_cast<const float4 *>(v + (at < last4 ? at : last4));
+                    const float e[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                    for (int c = 0; c < 4; c++)
+                        if (bits & (1u << c)) {
+                            if (slot < (unsigned)cap)
+                                ent[slot] = ((unsigned long long)float_to_key(e[c]) << 32) | (unsigned)(at + c - skip);
+                            slot++;
+                        }
+                }
+            }
 #pragma unroll
             for (int b = 0; b < NVEC; b++) {
                 const int at = b * 4 * kSelThreads + 4 * (int)threadIdx.x;
