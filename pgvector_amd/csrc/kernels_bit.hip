@@ -11,25 +11,32 @@
 //   bit_closest_kernel, bit_sums_kernel, bit_centers_kernel   the bit k-means around the Hamming matrix (pgv_bit_kmeans)
 // bit_kernel (kernels_misc.hip) stays the operator path: one query, float8 out, both bit metrics.
 //
-// hamming_tile_kernel: 256 rows x 32 queries per workgroup, one lane per row.
-//   * the rows leave HBM once per 32 queries: 8 adjacent lanes fetch 128 contiguous bytes of one row with 16-byte loads,
+// hamming_tile<QT>: the one Hamming tile -- up to 256 rows x QT queries per workgroup, one lane per row.  Both kernels
+// below are this function and what differs around it: where a tile's first row is, how many rows it has, and where
+// query q's words are (the caller's qrow(q)).
+//   * the rows leave HBM once per QT queries: 8 adjacent lanes fetch 128 contiguous bytes of one row with 16-byte loads,
 //     the slice goes through LDS (row stride 9 vectors: lane i's ds_read_b128 at 36 i words hits 16 distinct 4-bank
 //     slots in each of the instruction's 16-lane groups) and comes back as 32 words of the lane's own row in registers
-//   * the query words are the same for every lane: they are read through the scalar cache into SGPRs, so the inner
-//     step per word is v_xor_b32 with a scalar operand and v_bcnt_u32_b32 accumulating into an integer register
+//   * the query words are the same for every lane: qrow(q) is wave-uniform, they are read through the scalar cache into
+//     SGPRs, so the inner step per word is v_xor_b32 with a scalar operand and v_bcnt_u32_b32 accumulating into an
+//     integer register.  Both halves of that are written down, not left to the compiler: the words come as scalar
+//     loads of 8, each issued before the 8 words ahead of it are counted (a scalar load's latency is otherwise paid
+//     every few words: the wait is lgkmcnt(0)), and the accumulating popcount is popc_add
 //   * rows longer than the register slice (kBitSliceBits) are walked slice by slice, the next slice's global loads in
-//     flight while the current one is counted; the 32 counts per lane are converted to float once, at the store
-//   * stores are coalesced along `row`: lane i writes out[q * n + row0 + i]
+//     flight while the current one is counted; the QT counts per lane are converted to float once, at the caller's store
+//   * tail rows clamp their address inside the tile, tail queries inside qrow: both are computed, not stored, and no
+//     load is predicated
 // Rows are padded with zero bytes to whole 16-byte vectors and queries to whole slices (pgv_bit_topk stages them):
-// padding adds nothing to a count.  Tail rows and tail queries clamp their address and are computed, not stored.
+// padding adds nothing to a count.
+//
+// hamming_tile_kernel: one tile of 256 rows x 32 queries of the dense matrix per workgroup; stores are coalesced along
+// `row`: lane i writes out[q * n + row0 + i].
 //
 // hamming_list_kernel<QT>: a task of the list-major plan (launch_plan_batch) per trip of a persistent workgroup -- a
-// run of at most 256 rows of one list x the up to QT queries of one group that probes it -- into out[pair.out_rel + row].
-//   * inside a task it is the tile kernel: one lane per row, the cooperative 128-byte fetch, the transpose through LDS
-//     at stride 9, 1024-bit slices with the next slice's loads in flight, integer accumulators converted at the
-//     coalesced store, tail rows and tail pairs clamped and computed but not stored, no predicated load
-//   * around it it is scan_kernel: workgroups pull tasks from the device counter, the last one to finish leaves both
-//     counter words zero, ntasks is read from the device
+// run of at most 256 rows of one list x the up to QT queries of one group that probes it -- is one tile, into
+// out[pair.out_rel + row].
+//   * around the tile it is scan_kernel: workgroups pull tasks from the device counter, the last one to finish leaves
+//     both counter words zero, ntasks is read from the device
 //   * QT in {8, 16, 32}: a list is probed by nq x probes / nlists queries on average (about 10 at 1024 queries x 10
 //     probes over 1000 lists), a 1536-bit row costs 192 B of HBM once and 96 vector-ALU operations per (row, query)
 //     pair, so at ~10 pairs a row the two are of the same order and padding every group to 32 would triple the ALU work.
@@ -38,9 +45,9 @@
 //     UNMEASURED against each other
 //   * where the query words come from: the task index reaches the lanes through LDS, so the compiler cannot see that
 //     the task's fields and its query ids are the same in every lane.  They are made provably uniform with
-//     __builtin_amdgcn_readfirstlane (the task index, the task's fields, every query id and out_rel): the query words
-//     are then addressed from SGPRs, arrive through the scalar cache and the inner step keeps the tile kernel's
-//     `v_xor_b32 v, s, v` + `v_bcnt_u32_b32` form.  The alternative -- staging the group's query slices in LDS as
+//     __builtin_amdgcn_readfirstlane (the task index, the task's fields, every query id -- read once per task, ahead
+//     of the tile -- and out_rel): the query words are then addressed from SGPRs, arrive through the scalar cache and
+//     the inner step keeps the `v_xor_b32 v, s, v` + `v_bcnt_u32_b32` form.  The alternative -- staging the group's query slices in LDS as
 //     scan_kernel does (QT x 128 B per slice, a ds_read per word) -- was not built: UNMEASURED against this one
 #include "pgv_device.h"
 
@@ -49,26 +56,36 @@ namespace pgv {
 namespace {
 
 constexpr int kBitThreads = 256;                            // rows per tile
-constexpr int kBitQueries = 32;                             // queries per tile
+constexpr int kBitQueries = 32;                             // queries per tile of the dense matrix
 constexpr int kBitSliceVecs = 8;                            // 16-byte vectors of a row in registers at a time
 constexpr int kBitSliceWords = kBitSliceVecs * 4;           // 32
 constexpr int kBitSliceBits = kBitSliceWords * 32;          // 1024: the register slice
 constexpr int kBitLdsStride = kBitSliceVecs + 1;            // vectors; the pad keeps the transposed read conflict-free
 constexpr int kBitRowsPerTrip = kBitThreads / kBitSliceVecs;  // 32 rows per cooperative load instruction
+constexpr int kBitTileVecs = kBitThreads * kBitLdsStride;   // the tile's LDS
 static_assert(kBitSliceBits == 1024, "tests/test_gpu_bit_topk.py sweeps nbits around the register slice");
 
-__global__ __launch_bounds__(kBitThreads) void hamming_tile_kernel(const char *__restrict__ rows,
-                                                                   const uint32_t *__restrict__ queries, int64_t n, int nq,
-                                                                   int nvec, int qwords, int nqt, float *__restrict__ out) {
-    __shared__ Raw16 tile[kBitThreads * kBitLdsStride];
+typedef uint32_t QWords8 __attribute__((ext_vector_type(8), aligned(4)));  // one s_load_dwordx8 of query words
+
+// popcount(x) + acc, the one instruction it is, written out.  The compiler has the pattern, but selects it only while
+// the count is the add's FIRST operand.  Inside a kernel's own loops it was; now that the nest lives in a function, it
+// is unrolled there before it is inlined, the caller's reassociation pass sees the whole chain of adds and hands it
+// back with the count second, and every two counts cost a v_add3_u32 on top: + 25 % vector-ALU operations, 15 % on
+// the dense scan and 11 % on the 32-query list scan when it was measured (profiles/r19_bit_fold.md)
+__device__ __forceinline__ int popc_add(uint32_t x, int acc) {
+    asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc) : "v"(x));
+    return acc;
+}
+
+// acc[q] += hamming(row tid of the tile, query q) for q < QT.  task_rows: the tile's first row; nrows in 1..256 of them
+// are real; qrow(q): the wave-uniform pointer to query q's words.  Every lane of the workgroup calls it; `tile` is free
+// for the next call once every lane has passed a barrier
+template <int QT, typename QRow>
+__device__ __forceinline__ void hamming_tile(Raw16 *tile, const char *task_rows, int nrows, int nvec, QRow qrow,
+                                             int (&acc)[QT]) {
     const int tid = threadIdx.x;
-    // consecutive workgroups share a row tile: its query tiles run side by side and find the rows in the caches
-    const int qt = (int)(blockIdx.x % (unsigned)nqt);
-    const int64_t row0 = (int64_t)(blockIdx.x / (unsigned)nqt) * kBitThreads;
-    const int q0 = qt * kBitQueries;
     const int nslices = (nvec + kBitSliceVecs - 1) / kBitSliceVecs;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-
     const int lv = tid & (kBitSliceVecs - 1);  // which vector of the slice this lane fetches
     const int lr = tid >> 3;                   // ... of rows lr, lr + 32, ..
     Raw16 nxt[kBitSliceVecs];
@@ -78,20 +95,16 @@ __global__ __launch_bounds__(kBitThreads) void hamming_tile_kernel(const char *_
         const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
 #pragma unroll
         for (int i = 0; i < kBitSliceVecs; i++) {
-            int64_t r = row0 + lr + i * kBitRowsPerTrip;
-            r = r < n ? r : n - 1;  // tail rows are computed, not stored
-            const Raw16 v = load16(rows + (size_t)r * row_bytes + (size_t)vc * sizeof(Raw16));
+            int r = lr + i * kBitRowsPerTrip;
+            r = r < nrows ? r : nrows - 1;  // tail rows are computed, not stored
+            const Raw16 v = load16(task_rows + (size_t)r * row_bytes + (size_t)vc * sizeof(Raw16));
             nxt[i] = ok ? v : raw16_zero();
         }
     };
 
-    int acc[kBitQueries];
-#pragma unroll
-    for (int q = 0; q < kBitQueries; q++) acc[q] = 0;
-
     fetch(0);
     for (int s = 0; s < nslices; s++) {
-        __syncthreads();  // every lane has its words of the slice before
+        __syncthreads();  // the previous slice (or tile) has been read by every lane
 #pragma unroll
         for (int i = 0; i < kBitSliceVecs; i++) tile[(lr + i * kBitRowsPerTrip) * kBitLdsStride + lv] = nxt[i];
         __syncthreads();
@@ -100,23 +113,51 @@ __global__ __launch_bounds__(kBitThreads) void hamming_tile_kernel(const char *_
         for (int v = 0; v < kBitSliceVecs; v++) rv[v] = tile[tid * kBitLdsStride + v];
         if (s + 1 < nslices) fetch(s + 1);
 
-        const uint32_t *qs = queries + (size_t)s * kBitSliceWords;
+        // four scalar loads of 8 words per query, each in flight while the 8 words before it are counted; the last
+        // one of a query is followed by the first one of the next
+        auto part = [&](const uint32_t *p) { return *reinterpret_cast<const QWords8 *>(p); };
+        const uint32_t *qp = qrow(0) + (size_t)s * kBitSliceWords;
+        QWords8 cur = part(qp);
 #pragma unroll
-        for (int q = 0; q < kBitQueries; q++) {
-            const int qi = q0 + q < nq ? q0 + q : nq - 1;  // tail queries are computed, not stored
-            const uint32_t *qp = qs + (size_t)qi * qwords;  // wave-uniform: scalar loads
+        for (int q = 0; q < QT; q++) {
 #pragma unroll
-            for (int v = 0; v < kBitSliceVecs; v++)
+            for (int p = 0; p < 4; p++) {
+                QWords8 ahead = cur;
+                if (p < 3) {
+                    ahead = part(qp + 8 * (p + 1));
+                } else if (q + 1 < QT) {
+                    qp = qrow(q + 1) + (size_t)s * kBitSliceWords;
+                    ahead = part(qp);
+                }
 #pragma unroll
-                for (int w = 0; w < 4; w++) acc[q] = __popc(rv[v].w[w] ^ qp[v * 4 + w]) + acc[q];
+                for (int i = 0; i < 8; i++) acc[q] = popc_add(rv[2 * p + i / 4].w[i % 4] ^ cur[i], acc[q]);
+                cur = ahead;
+            }
         }
     }
+}
 
-    const int64_t row = row0 + tid;
-    if (row < n) {
+__global__ __launch_bounds__(kBitThreads) void hamming_tile_kernel(const char *__restrict__ rows,
+                                                                   const uint32_t *__restrict__ queries, int64_t n, int nq,
+                                                                   int nvec, int qwords, int nqt, float *__restrict__ out) {
+    __shared__ Raw16 tile[kBitTileVecs];
+    // consecutive workgroups share a row tile: its query tiles run side by side and find the rows in the caches
+    const int qt = (int)(blockIdx.x % (unsigned)nqt);
+    const int64_t row0 = (int64_t)(blockIdx.x / (unsigned)nqt) * kBitThreads;
+    const int q0 = qt * kBitQueries;
+    const int nrows = n - row0 < kBitThreads ? (int)(n - row0) : kBitThreads;
+
+    int acc[kBitQueries] = {};
+    hamming_tile<kBitQueries>(
+        tile, rows + (size_t)row0 * ((size_t)nvec * sizeof(Raw16)), nrows, nvec,
+        [&](int q) { return queries + (size_t)(q0 + q < nq ? q0 + q : nq - 1) * qwords; },  // tail queries: not stored
+        acc);
+
+    const int tid = threadIdx.x;
+    if (tid < nrows) {
 #pragma unroll
         for (int q = 0; q < kBitQueries; q++)
-            if (q0 + q < nq) out[(size_t)(q0 + q) * (size_t)n + (size_t)row] = (float)acc[q];
+            if (q0 + q < nq) out[(size_t)(q0 + q) * (size_t)n + (size_t)(row0 + tid)] = (float)acc[q];
     }
 }
 
@@ -186,13 +227,9 @@ __global__ __launch_bounds__(kBitThreads) void hamming_list_kernel(
     const char *__restrict__ rows, const uint32_t *__restrict__ queries, const ScanTask *__restrict__ tasks,
     const int *__restrict__ ntasks_ptr, int *__restrict__ task_counter, const ScanPair *__restrict__ pairs,
     float *__restrict__ out, int nvec, int qwords) {
-    __shared__ Raw16 tile[kBitThreads * kBitLdsStride];
+    __shared__ Raw16 tile[kBitTileVecs];
     __shared__ int lds_task;
     const int tid = threadIdx.x;
-    const int nslices = (nvec + kBitSliceVecs - 1) / kBitSliceVecs;
-    const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    const int lv = tid & (kBitSliceVecs - 1);  // which vector of the slice this lane fetches
-    const int lr = tid >> 3;                   // ... of rows lr, lr + 32, ..
     const int ntasks = *ntasks_ptr;
 
     for (;;) {
@@ -211,49 +248,14 @@ __global__ __launch_bounds__(kBitThreads) void hamming_list_kernel(
         const int nrows = uniform32(tasks[t].nrows);
         const int pair0 = uniform32(tasks[t].pair0);
         const int npairs = uniform32(tasks[t].npairs);
-        const char *task_rows = rows + (size_t)row0 * row_bytes;
 
-        Raw16 nxt[kBitSliceVecs];
-        auto fetch = [&](int s) {
-            const int vi = s * kBitSliceVecs + lv;
-            const bool ok = vi < nvec;
-            const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
+        int qid[QT];  // the group's queries; tail pairs are computed, not stored
 #pragma unroll
-            for (int i = 0; i < kBitSliceVecs; i++) {
-                int r = lr + i * kBitRowsPerTrip;
-                r = r < nrows ? r : nrows - 1;  // tail rows are computed, not stored
-                const Raw16 v = load16(task_rows + (size_t)r * row_bytes + (size_t)vc * sizeof(Raw16));
-                nxt[i] = ok ? v : raw16_zero();
-            }
-        };
+        for (int q = 0; q < QT; q++) qid[q] = uniform32(pairs[pair0 + (q < npairs ? q : npairs - 1)].query);
 
-        int acc[QT];
-#pragma unroll
-        for (int q = 0; q < QT; q++) acc[q] = 0;
-
-        fetch(0);
-        for (int s = 0; s < nslices; s++) {
-            __syncthreads();  // the previous slice (or task) has been read by every lane
-#pragma unroll
-            for (int i = 0; i < kBitSliceVecs; i++) tile[(lr + i * kBitRowsPerTrip) * kBitLdsStride + lv] = nxt[i];
-            __syncthreads();
-            Raw16 rv[kBitSliceVecs];
-#pragma unroll
-            for (int v = 0; v < kBitSliceVecs; v++) rv[v] = tile[tid * kBitLdsStride + v];
-            if (s + 1 < nslices) fetch(s + 1);
-
-            const uint32_t *qs = queries + (size_t)s * kBitSliceWords;
-#pragma unroll
-            for (int q = 0; q < QT; q++) {
-                const int qq = q < npairs ? q : npairs - 1;  // tail pairs are computed, not stored
-                const int qi = uniform32(pairs[pair0 + qq].query);
-                const uint32_t *qp = qs + (size_t)qi * qwords;  // wave-uniform: scalar loads
-#pragma unroll
-                for (int v = 0; v < kBitSliceVecs; v++)
-#pragma unroll
-                    for (int w = 0; w < 4; w++) acc[q] = __popc(rv[v].w[w] ^ qp[v * 4 + w]) + acc[q];
-            }
-        }
+        int acc[QT] = {};
+        hamming_tile<QT>(tile, rows + (size_t)row0 * ((size_t)nvec * sizeof(Raw16)), nrows, nvec,
+                         [&](int q) { return queries + (size_t)qid[q] * qwords; }, acc);
 
         if (tid < nrows) {
 #pragma unroll

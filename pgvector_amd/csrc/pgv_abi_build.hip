@@ -2,6 +2,82 @@
 // Split out of pgv_abi.hip in round 5 (one unit per area, so that an edit recompiles one of them).
 #include "pgv_abi_common.h"
 
+namespace {
+
+// The caller's rows [n x tight bytes] to their centers, for pgv_assign and pgv_bit_assign: host rows are staged in slabs
+// (BuildCallback batches), device rows that need no padding go in one piece; out_list / out_dist are written
+// in place when they are device memory, staged and copied back otherwise.  score(r_dev, cnt, idx, val) scores one
+// staged slab into device idx / val (val may be null)
+template <typename Score>
+int assign_in_slabs(pgv_ctx *ctx, const void *rows, int64_t n, size_t tight, size_t padded, int32_t *out_list,
+                    float *out_dist, Score score) {
+    const bool out_dev = is_device_ptr(out_list);
+    const bool dist_dev = out_dist && is_device_ptr(out_dist);
+    const int64_t slab = (is_device_ptr(rows) && padded == tight) ? n : (int64_t)1 << 18;
+    bool need = false;
+    for (int64_t r0 = 0; r0 < n; r0 += slab) {
+        const int64_t cnt = n - r0 < slab ? n - r0 : slab;
+        const void *r_dev;
+        PGV_TRY(stage_rows(ctx, static_cast<const char *>(rows) + (size_t)r0 * tight, cnt, tight, padded, ctx->rows_stage,
+                           &r_dev));
+        int32_t *idx = out_list + r0;
+        float *val = out_dist ? out_dist + r0 : nullptr;
+        if (!out_dev) {
+            PGV_TRY(ctx->out_stage.ensure(sizeof(int32_t) * (size_t)cnt));
+            idx = ctx->out_stage.as<int32_t>();
+        }
+        if (out_dist && !dist_dev) {
+            PGV_TRY(ctx->out_stage2.ensure(sizeof(float) * (size_t)cnt));
+            val = ctx->out_stage2.as<float>();
+        }
+        PGV_TRY(score(r_dev, cnt, idx, val));
+        if (!out_dev) {
+            PGV_HIP(hipMemcpyAsync(out_list + r0, idx, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
+            need = true;
+        }
+        if (out_dist && !dist_dev) {
+            PGV_HIP(hipMemcpyAsync(out_dist + r0, val, sizeof(float) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
+            need = true;
+        }
+        if (need && r0 + slab < n) PGV_HIP(hipStreamSynchronize(ctx->stream));  // scratch is reused
+    }
+    return sync_if(ctx, need);
+}
+
+// The empty clusters of a Lloyd iteration (counts_host[c] <= 0) take draws from the rng, clusters in center order
+// (src/ivfkmeans.c:222-227).  On the host, in h_b: row[k] (row_bytes; -1, or the cluster's row among the refills) |
+// fill[nempty x fill_bytes], zeroed, then draw(fill row) once per empty cluster.  On the device the same layout goes
+// behind head_bytes of km_e, which is sized here, in one copy and one sync (h_b may be rewritten by the next step).
+// *nempty: how many there were
+template <typename Draw>
+int refill_empty_clusters(pgv_ctx *ctx, const int32_t *counts_host, int k, size_t head_bytes, size_t row_bytes,
+                          size_t fill_bytes, Draw draw, int *nempty) {
+    int ne = 0;
+    for (int c = 0; c < k; c++)
+        if (counts_host[c] <= 0) ne++;
+    *nempty = ne;
+    const size_t bytes = row_bytes + (size_t)ne * fill_bytes;
+    PGV_TRY(ctx->km_e.ensure(head_bytes + bytes + 16));
+    if (ne == 0) return PGV_OK;
+    PGV_TRY(ctx->h_b.ensure(bytes));
+    int32_t *h_row = ctx->h_b.as<int32_t>();
+    char *h_fill = ctx->h_b.as<char>() + row_bytes;
+    memset(h_fill, 0, (size_t)ne * fill_bytes);
+    int e = 0;
+    for (int c = 0; c < k; c++) {
+        h_row[c] = -1;
+        if (counts_host[c] <= 0) {
+            draw(static_cast<void *>(h_fill + (size_t)e * fill_bytes));
+            h_row[c] = e++;
+        }
+    }
+    PGV_HIP(hipMemcpyAsync(ctx->km_e.as<char>() + head_bytes, h_row, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    return PGV_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 // ================================================================= build side
@@ -19,41 +95,11 @@ int pgv_assign(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const 
     const RowGeom g = row_geom(dim, dtype);
     const void *c_dev;
     PGV_TRY(stage_rows(ctx, centers, k, dim, dtype, g, ctx->centers_stage, &c_dev));
-
-    const bool rows_dev = is_device_ptr(rows);
-    const bool out_dev = is_device_ptr(out_list);
-    const bool dist_dev = out_dist && is_device_ptr(out_dist);
     const size_t es = elem_size(dtype);
-    // host rows are staged in slabs (BuildCallback batches); device rows go in one piece
-    const int64_t slab = (rows_dev && g.ld == dim) ? n : (int64_t)1 << 18;
-    bool need = false;
-    for (int64_t r0 = 0; r0 < n; r0 += slab) {
-        const int64_t cnt = n - r0 < slab ? n - r0 : slab;
-        const void *r_dev;
-        PGV_TRY(stage_rows(ctx, static_cast<const char *>(rows) + (size_t)r0 * dim * es, cnt, dim,
-                           dtype, g, ctx->rows_stage, &r_dev));
-        int32_t *idx = out_list + r0;
-        float *val = out_dist ? out_dist + r0 : nullptr;
-        if (!out_dev) {
-            PGV_TRY(ctx->out_stage.ensure(sizeof(int32_t) * (size_t)cnt));
-            idx = ctx->out_stage.as<int32_t>();
-        }
-        if (out_dist && !dist_dev) {
-            PGV_TRY(ctx->out_stage2.ensure(sizeof(float) * (size_t)cnt));
-            val = ctx->out_stage2.as<float>();
-        }
-        PGV_TRY(launch_argmin(ctx, metric, dtype, g, r_dev, cnt, c_dev, k, idx, val));
-        if (!out_dev) {
-            PGV_HIP(hipMemcpyAsync(out_list + r0, idx, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-            need = true;
-        }
-        if (out_dist && !dist_dev) {
-            PGV_HIP(hipMemcpyAsync(out_dist + r0, val, sizeof(float) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-            need = true;
-        }
-        if (need && r0 + slab < n) PGV_HIP(hipStreamSynchronize(ctx->stream));  // scratch is reused
-    }
-    return sync_if(ctx, need);
+    return assign_in_slabs(ctx, rows, n, (size_t)dim * es, (size_t)g.ld * es, out_list, out_dist,
+                           [&](const void *r_dev, int64_t cnt, int32_t *idx, float *val) {
+                               return launch_argmin(ctx, metric, dtype, g, r_dev, cnt, c_dev, k, idx, val);
+                           });
 }
 
 int pgv_distance_batch(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *query,
@@ -208,12 +254,7 @@ int pgv_bit_distance_batch(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const
     } else {
         // bytes are staged like fp16 elements of a (bytes / 2)-dimensional row would be: zero-padded to whole
         // 16-byte vectors (an odd byte count is padded by the 2-D copy as well)
-        RowGeom g;
-        g.ld = (bytes + 15) / 16 * 16;  // padded row length in BYTES
-        g.nvec = g.ld / 16;
-        g.lpr_log2 = 6;
-        while (g.lpr_log2 > 0 && (1 << (g.lpr_log2 - 1)) >= g.nvec) g.lpr_log2--;
-        g.nchunks = (g.nvec + (1 << g.lpr_log2) - 1) >> g.lpr_log2;
+        const RowGeom g = bit_row_geom(nbits);
         const void *q_dev, *r_dev;
         PGV_TRY(stage_rows(ctx, query, 1, bytes, g.ld, ctx->q_stage, &q_dev));
         PGV_TRY(stage_rows(ctx, rows, n, bytes, g.ld, ctx->rows_stage, &r_dev));
@@ -358,6 +399,66 @@ int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const 
     return sync_if(ctx, need);
 }
 
+// ------------------------------------------------------------- k-means++ seeding
+// (prototypes and what the two parts promise: pgv_abi_common.h)
+int kmpp_begin(pgv_ctx *ctx, int n_local, int k, int64_t n_total, Rng &rng, KmppState *state, int64_t *first) {
+    const size_t nw = n_local > 0 ? (size_t)n_local : 1;
+    KmppState &st = *state;
+    st.nblocks = n_local > 0 ? kmpp_block_count(n_local) : 0;
+    PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * nw));
+    PGV_TRY(ctx->km_b.ensure(sizeof(double) * ((size_t)st.nblocks + (size_t)k + 1)));
+    PGV_TRY(ctx->km_c.ensure(sizeof(int32_t) * (size_t)k));
+    st.weight = ctx->km_a.as<float>();
+    st.raw = st.weight + nw;
+    st.block_sums = ctx->km_b.as<double>();
+    st.draws_dev = st.block_sums + st.nblocks;
+    st.picked = ctx->km_c.as<int32_t>();
+
+    // the reference draws RandomInt() once, then one RandomDouble() per further center
+    // (src/ivfkmeans.c:36, :77): pre-draw them in that order
+    *first = (int64_t)(rng.next_u32() % (uint32_t)n_total);
+    PGV_TRY(ctx->h_b.ensure(sizeof(double) * (size_t)k + sizeof(float) * nw));
+    double *h_draws = ctx->h_b.as<double>();
+    for (int i = 0; i + 1 < k; i++) h_draws[i] = rng.next_double();
+    float *h_w = reinterpret_cast<float *>(h_draws + k);
+    for (int j = 0; j < n_local; j++) h_w[j] = 3.402823466e+38f;  // FLT_MAX (:39-40)
+    PGV_HIP(hipMemcpyAsync(st.draws_dev, h_draws, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+    if (n_local > 0)
+        PGV_HIP(hipMemcpyAsync(st.weight, h_w, sizeof(float) * (size_t)n_local, hipMemcpyHostToDevice, ctx->stream));
+    return PGV_OK;
+}
+
+int kmpp_round_weights(pgv_ctx *ctx, const RowsView &sv, const void *center_i, const KmppState &st) {
+    // distance of every sample to the newest center only (:52-60)
+    if (sv.bits())
+        PGV_TRY(launch_hamming_tiles(ctx, sv, center_i, (int)sv.row_bytes(), 1, st.raw));
+    else
+        PGV_TRY(dense_scan(ctx, sv, center_i, 1, 0, st.raw));
+    const int mode = sv.bits() ? 2 : (sv.metric == PGV_NEG_IP ? 1 : 0);
+    return launch_kmpp_update(ctx, st.raw, st.weight, (int)sv.n, mode, st.block_sums);
+}
+
+// k-means++ over staged samples (kmeans_rows, or bit rows at the queries' stride) into device centers at the samples'
+// stride
+static int kmeanspp_dev(pgv_ctx *ctx, const RowsView &sv, int k, Rng &rng, void *centers_dev) {
+    const int n = (int)sv.n;
+    const size_t row_bytes = sv.row_bytes();
+    KmppState st;
+    int64_t first;
+    PGV_TRY(kmpp_begin(ctx, n, k, n, rng, &st, &first));
+    PGV_HIP(hipMemcpyAsync(centers_dev, static_cast<const char *>(sv.rows) + (size_t)first * row_bytes, row_bytes,
+                           hipMemcpyDeviceToDevice, ctx->stream));
+    const int32_t first_i = (int32_t)first;
+    PGV_HIP(hipMemcpyAsync(st.picked, &first_i, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i + 1 < k; i++) {
+        PGV_TRY(kmpp_round_weights(ctx, sv, static_cast<const char *>(centers_dev) + (size_t)i * row_bytes, st));
+        PGV_TRY(launch_kmpp_pick(ctx, sv.geom, sv.rows, n, st.weight, st.block_sums, st.draws_dev, i, centers_dev,
+                                 st.picked));
+    }
+    return PGV_OK;
+}
+
 // ------------------------------------------------------ k-means over bit strings
 // `USING ivfflat (col bit_hamming_ops)` on the build side.  The samples are staged as the QUERIES of hamming_tile_kernel
 // (rows of whole register slices, BitGeom::q_ld bytes), the centers as its rows: a chunk's matrix mat[sample][center]
@@ -402,36 +503,21 @@ int bit_closest_dev(pgv_ctx *ctx, const void *s_dev, int q_ld, int64_t n, const 
 // on the host.  centers_dev [k x c_ld] is rewritten.  km_e: sums | refill_row | refill
 int bit_update_centers_dev(pgv_ctx *ctx, int nbits, const BitGeom &g, const void *s_dev, int n, const int32_t *closest_dev,
                            const int32_t *counts_dev, const int32_t *h_counts, int k, Rng &rng, void *centers_dev, int c_ld) {
-    int nempty = 0;
-    for (int c = 0; c < k; c++)
-        if (h_counts[c] <= 0) nempty++;
     const size_t sums_bytes = (sizeof(int32_t) * (size_t)k * (size_t)nbits + 255) & ~(size_t)255;
     const size_t row_bytes = (sizeof(int32_t) * (size_t)k + 255) & ~(size_t)255;
-    PGV_TRY(ctx->km_e.ensure(sums_bytes + row_bytes + (size_t)nempty * g.bytes + 16));
+    int nempty = 0;
+    PGV_TRY(refill_empty_clusters(ctx, h_counts, k, sums_bytes, row_bytes, (size_t)g.bytes, [&](void *row) {
+        uint8_t *fill = static_cast<uint8_t *>(row);
+        for (int i = 0; i < nbits; i++) {
+            const float x = (float)rng.next_double();
+            if (x > 0.5f) fill[i / 8] |= (uint8_t)(1u << (7 - i % 8));
+        }
+    }, &nempty));
     int32_t *sums = ctx->km_e.as<int32_t>();
     int32_t *refill_row = reinterpret_cast<int32_t *>(ctx->km_e.as<char>() + sums_bytes);
     uint8_t *refill = reinterpret_cast<uint8_t *>(ctx->km_e.as<char>() + sums_bytes + row_bytes);
     PGV_HIP(hipMemsetAsync(sums, 0, sums_bytes, ctx->stream));
     PGV_TRY(launch_bit_sums(ctx, s_dev, g.q_ld, nbits, n, closest_dev, sums));
-    if (nempty > 0) {
-        PGV_TRY(ctx->h_b.ensure(row_bytes + (size_t)nempty * g.bytes));
-        int32_t *h_row = ctx->h_b.as<int32_t>();
-        uint8_t *h_fill = reinterpret_cast<uint8_t *>(ctx->h_b.as<char>() + row_bytes);
-        memset(h_fill, 0, (size_t)nempty * g.bytes);
-        int e = 0;
-        for (int c = 0; c < k; c++) {
-            h_row[c] = -1;
-            if (h_counts[c] <= 0) {
-                for (int i = 0; i < nbits; i++) {
-                    const float x = (float)rng.next_double();
-                    if (x > 0.5f) h_fill[(size_t)e * g.bytes + i / 8] |= (uint8_t)(1u << (7 - i % 8));
-                }
-                h_row[c] = e++;
-            }
-        }
-        PGV_HIP(hipMemcpyAsync(refill_row, h_row, row_bytes + (size_t)nempty * g.bytes, hipMemcpyHostToDevice, ctx->stream));
-        PGV_HIP(hipStreamSynchronize(ctx->stream));  // h_b may be rewritten by the next step
-    }
     return launch_bit_centers(ctx, sums, counts_dev, k, nbits, c_ld, nempty > 0 ? refill_row : nullptr, refill, centers_dev);
 }
 
@@ -456,22 +542,6 @@ int bit_lloyd_dev(pgv_ctx *ctx, int nbits, const BitGeom &g, const void *s_dev, 
     return PGV_OK;
 }
 
-// packed device rows [cnt x ld] -> the caller's [cnt x bytes] (host or device)
-int unstage_rows(pgv_ctx *ctx, const void *src_dev, int64_t cnt, int bytes, int ld, void *dst) {
-    if (cnt == 0) return PGV_OK;
-    const bool dev = is_device_ptr(dst);
-    PGV_HIP(hipMemcpy2DAsync(dst, (size_t)bytes, src_dev, (size_t)ld, (size_t)bytes, (size_t)cnt,
-                             dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));
-    return PGV_OK;
-}
-// a staging that is a copy even of device rows (the centers of a k-means are rewritten in place)
-int copy_bit_rows(pgv_ctx *ctx, const void *src, int64_t cnt, int bytes, int ld, DBuf &scratch) {
-    PGV_TRY(scratch.ensure(std::max<size_t>((size_t)cnt * ld, 16)));
-    PGV_TRY(put_padded_rows(ctx->stream, scratch.p, ld, src, bytes, cnt));
-    PGV_HIP(hipStreamSynchronize(ctx->stream));
-    return PGV_OK;
-}
 }  // namespace
 
 // AddTupleToSort's argmin (src/ivfbuild.c:183-192) under hamming_distance: `distance < minDistance` keeps the first
@@ -488,37 +558,11 @@ int pgv_bit_assign(pgv_ctx *ctx, int nbits, const void *centers, int k, const vo
     const BitGeom g = bit_geom(nbits);
     const void *c_dev;
     PGV_TRY(stage_rows(ctx, centers, k, g.bytes, g.row_ld, ctx->centers_stage, &c_dev));
-    const bool out_dev = is_device_ptr(out_list), dist_dev = out_dist && is_device_ptr(out_dist);
-    // rows are staged in slabs, like pgv_assign's host rows
-    const int64_t slab = (int64_t)1 << 18;
-    bool need = false;
-    for (int64_t r0 = 0; r0 < n; r0 += slab) {
-        const int64_t cnt = std::min(slab, n - r0);
-        const void *r_dev;
-        PGV_TRY(stage_rows(ctx, static_cast<const char *>(rows) + (size_t)r0 * g.bytes, cnt, g.bytes, g.q_ld, ctx->rows_stage,
-                               &r_dev));
-        int32_t *idx = out_list + r0;
-        float *val = out_dist ? out_dist + r0 : nullptr;
-        if (!out_dev) {
-            PGV_TRY(ctx->out_stage.ensure(sizeof(int32_t) * (size_t)cnt));
-            idx = ctx->out_stage.as<int32_t>();
-        }
-        if (out_dist && !dist_dev) {
-            PGV_TRY(ctx->out_stage2.ensure(sizeof(float) * (size_t)cnt));
-            val = ctx->out_stage2.as<float>();
-        }
-        PGV_TRY(bit_closest_dev(ctx, r_dev, g.q_ld, cnt, bit_rows(c_dev, k, g.row_ld), false, idx, val, nullptr, nullptr));
-        if (!out_dev) {
-            PGV_HIP(hipMemcpyAsync(out_list + r0, idx, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-            need = true;
-        }
-        if (out_dist && !dist_dev) {
-            PGV_HIP(hipMemcpyAsync(out_dist + r0, val, sizeof(float) * (size_t)cnt, hipMemcpyDeviceToHost, ctx->stream));
-            need = true;
-        }
-        if (r0 + slab < n) PGV_HIP(hipStreamSynchronize(ctx->stream));  // the staging is reused
-    }
-    return sync_if(ctx, need);
+    const RowsView cv = bit_rows(c_dev, k, g.row_ld);
+    return assign_in_slabs(ctx, rows, n, (size_t)g.bytes, (size_t)g.q_ld, out_list, out_dist,
+                           [&](const void *r_dev, int64_t cnt, int32_t *idx, float *val) {
+                               return bit_closest_dev(ctx, r_dev, g.q_ld, cnt, cv, false, idx, val, nullptr, nullptr);
+                           });
 }
 
 int pgv_bit_lloyd_step(pgv_ctx *ctx, int nbits, const void *samples, int n, const void *centers, int k, int32_t *io_closest,
@@ -532,7 +576,10 @@ int pgv_bit_lloyd_step(pgv_ctx *ctx, int nbits, const void *samples, int n, cons
     const BitGeom g = bit_geom(nbits);
     const void *s_dev = nullptr;
     if (n > 0) PGV_TRY(stage_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
-    PGV_TRY(copy_bit_rows(ctx, centers, k, g.bytes, g.q_ld, ctx->centers_stage));
+    // a staging that is a copy even of device rows: the centers are rewritten in place
+    PGV_TRY(ctx->centers_stage.ensure((size_t)k * g.q_ld));
+    PGV_TRY(put_padded_rows(ctx->stream, ctx->centers_stage.p, g.q_ld, centers, g.bytes, k));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
     int32_t *closest_dev = io_closest;
     const bool closest_is_dev = is_device_ptr(io_closest);
     if (!closest_is_dev) {
@@ -589,37 +636,9 @@ int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, i
     } else {
         const void *s_dev;
         PGV_TRY(stage_rows(ctx, samples, n, g.bytes, g.q_ld, ctx->rows_stage, &s_dev));
-        // InitCenters (src/ivfkmeans.c:23-91), kmeanspp_dev's structure: the distance to the newest center is the Hamming
-        // count, weight = min(weight, (float) d^2), the sum and the pick in double
-        {
-            const RowsView sv = bit_rows(s_dev, n, g.q_ld);
-            const int nblocks = kmpp_block_count(n);
-            PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * (size_t)n));
-            PGV_TRY(ctx->km_b.ensure(sizeof(double) * ((size_t)nblocks + (size_t)k)));
-            PGV_TRY(ctx->km_c.ensure(sizeof(int32_t) * (size_t)k));
-            float *weight = ctx->km_a.as<float>(), *raw = weight + n;
-            double *block_sums = ctx->km_b.as<double>(), *draws_dev = block_sums + nblocks;
-            int32_t *picked = ctx->km_c.as<int32_t>();
-            const uint32_t first = r.next_u32() % (uint32_t)n;  // RandomInt() once, then a RandomDouble() per center (:36, :77)
-            PGV_TRY(ctx->h_b.ensure(sizeof(double) * (size_t)k + sizeof(float) * (size_t)n));
-            double *h_draws = ctx->h_b.as<double>();
-            for (int i = 0; i + 1 < k; i++) h_draws[i] = r.next_double();
-            float *h_w = reinterpret_cast<float *>(h_draws + k);
-            for (int j = 0; j < n; j++) h_w[j] = 3.402823466e+38f;  // FLT_MAX (:39-40)
-            PGV_HIP(hipMemcpyAsync(draws_dev, h_draws, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-            PGV_HIP(hipMemcpyAsync(weight, h_w, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-            PGV_HIP(hipMemcpyAsync(centers_dev, static_cast<const char *>(s_dev) + (size_t)first * g.q_ld, (size_t)g.q_ld,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-            const int32_t first_i = (int32_t)first;
-            PGV_HIP(hipMemcpyAsync(picked, &first_i, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-            PGV_HIP(hipStreamSynchronize(ctx->stream));
-            for (int i = 0; i + 1 < k; i++) {
-                const char *center_i = static_cast<const char *>(centers_dev) + (size_t)i * g.q_ld;
-                PGV_TRY(launch_hamming_tiles(ctx, sv, center_i, g.q_ld, 1, raw));
-                PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, 2, block_sums));
-                PGV_TRY(launch_kmpp_pick(ctx, sv.geom, s_dev, n, weight, block_sums, draws_dev, i, centers_dev, picked));
-            }
-        }
+        // InitCenters (src/ivfkmeans.c:23-91): the distance to the newest center is the Hamming count,
+        // weight = min(weight, (float) d^2), the sum and the pick in double
+        PGV_TRY(kmeanspp_dev(ctx, bit_rows(s_dev, n, g.q_ld), k, r, centers_dev));
         PGV_TRY(ctx->km_g.ensure(sizeof(int32_t) * (size_t)n));
         int32_t *closest = ctx->km_g.as<int32_t>();
         PGV_HIP(hipMemsetAsync(closest, 0xff, sizeof(int32_t) * (size_t)n, ctx->stream));  // -1: not assigned yet
@@ -639,51 +658,6 @@ int pgv_bit_kmeans(pgv_ctx *ctx, int nbits, const void *samples, int n, int k, i
 }
 
 // --------------------------------------------------------------------- k-means
-
-
-
-// k-means++ on staged (padded, device) samples into padded device centers
-static int kmeanspp_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &g,
-                        const void *samples_dev, int n, int k, Rng &rng, void *centers_dev) {
-    const pgv_metric km = spherical(ops) ? PGV_NEG_IP : PGV_L2SQ;
-    const RowsView sv{samples_dev, n, g, row_kind(dtype), km};
-    const size_t row_bytes = sv.row_bytes();
-    const int nblocks = kmpp_block_count(n);
-    // km_a: weight[n] | raw[n]   km_b: block_sums[nblocks] | draws[k]   km_c: picked[k]
-    PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * (size_t)n));
-    PGV_TRY(ctx->km_b.ensure(sizeof(double) * ((size_t)nblocks + (size_t)k)));
-    PGV_TRY(ctx->km_c.ensure(sizeof(int32_t) * (size_t)k));
-    float *weight = ctx->km_a.as<float>();
-    float *raw = weight + n;
-    double *block_sums = ctx->km_b.as<double>();
-    double *draws_dev = block_sums + nblocks;
-    int32_t *picked = ctx->km_c.as<int32_t>();
-
-    // the reference draws RandomInt() once, then one RandomDouble() per further center
-    // (src/ivfkmeans.c:36, :77): pre-draw them in that order
-    const uint32_t first = rng.next_u32() % (uint32_t)n;
-    PGV_TRY(ctx->h_b.ensure(sizeof(double) * (size_t)k + sizeof(float) * (size_t)n));
-    double *h_draws = ctx->h_b.as<double>();
-    for (int i = 0; i + 1 < k; i++) h_draws[i] = rng.next_double();
-    float *h_w = reinterpret_cast<float *>(h_draws + k);
-    for (int j = 0; j < n; j++) h_w[j] = 3.402823466e+38f;  // FLT_MAX (:39-40)
-    PGV_HIP(hipMemcpyAsync(draws_dev, h_draws, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-    PGV_HIP(hipMemcpyAsync(weight, h_w, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    PGV_HIP(hipMemcpyAsync(centers_dev, static_cast<const char *>(samples_dev) + (size_t)first * row_bytes,
-                           row_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    const int32_t first_i = (int32_t)first;
-    PGV_HIP(hipMemcpyAsync(picked, &first_i, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    PGV_HIP(hipStreamSynchronize(ctx->stream));
-
-    for (int i = 0; i + 1 < k; i++) {
-        // distance of every sample to the newest center only (:52-60)
-        const void *center_i = static_cast<const char *>(centers_dev) + (size_t)i * row_bytes;
-        PGV_TRY(dense_scan(ctx, sv, center_i, 1, 0, raw));
-        PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, spherical(ops) ? 1 : 0, block_sums));
-        PGV_TRY(launch_kmpp_pick(ctx, g, samples_dev, n, weight, block_sums, draws_dev, i, centers_dev, picked));
-    }
-    return PGV_OK;
-}
 
 // assignment + per-center sums/counts for staged samples; all outputs device
 int lloyd_partial_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &g,
@@ -713,27 +687,12 @@ int lloyd_finish_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &
                             Rng &rng, void *centers_dev) {
     // empty clusters take dim RandomDouble() draws each, in center order (src/ivfkmeans.c:222-227)
     int nempty = 0;
-    for (int c = 0; c < k; c++)
-        if (counts_host[c] <= 0) nempty++;
-    PGV_TRY(ctx->km_e.ensure(sizeof(int32_t) * (size_t)k + sizeof(float) * ((size_t)nempty * dim + 1)));
+    PGV_TRY(refill_empty_clusters(ctx, counts_host, k, 0, sizeof(int32_t) * (size_t)k, sizeof(float) * (size_t)dim,
+                                  [&](void *row) {
+                                      for (int d = 0; d < dim; d++) static_cast<float *>(row)[d] = (float)rng.next_double();
+                                  }, &nempty));
     int32_t *refill_row = ctx->km_e.as<int32_t>();
     float *refill = reinterpret_cast<float *>(refill_row + k);
-    if (nempty > 0) {
-        PGV_TRY(ctx->h_b.ensure(sizeof(int32_t) * (size_t)k + sizeof(float) * (size_t)nempty * dim));
-        int32_t *h_row = ctx->h_b.as<int32_t>();
-        float *h_fill = reinterpret_cast<float *>(h_row + k);
-        int e = 0;
-        for (int c = 0; c < k; c++) {
-            h_row[c] = -1;
-            if (counts_host[c] <= 0) {
-                for (int d = 0; d < dim; d++) h_fill[(size_t)e * dim + d] = (float)rng.next_double();
-                h_row[c] = e++;
-            }
-        }
-        PGV_HIP(hipMemcpyAsync(refill_row, h_row, sizeof(int32_t) * (size_t)k + sizeof(float) * (size_t)nempty * dim,
-                               hipMemcpyHostToDevice, ctx->stream));
-        PGV_HIP(hipStreamSynchronize(ctx->stream));
-    }
     PGV_TRY(launch_finish_centers(ctx, dtype, g, k, dim, sums_dev, counts_dev, refill, refill_row, centers_dev));
     if (spherical(ops)) {
         PGV_TRY(ctx->km_f.ensure(64));
@@ -773,7 +732,7 @@ int pgv_kmeanspp_init(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, int dim, const
     PGV_TRY(ctx->centers_stage.ensure((size_t)k * g.ld * elem_size(dtype)));
     PGV_HIP(hipMemsetAsync(ctx->centers_stage.p, 0, (size_t)k * g.ld * elem_size(dtype), ctx->stream));
     Rng r(rng);
-    PGV_TRY(kmeanspp_dev(ctx, ops, dtype, g, s_dev, n, k, r, ctx->centers_stage.p));
+    PGV_TRY(kmeanspp_dev(ctx, kmeans_rows(ops, dtype, g, s_dev, n), k, r, ctx->centers_stage.p));
     PGV_TRY(unstage_rows(ctx, ctx->centers_stage.p, k, dim, dtype, g, out_centers));
     return pgv_ctx_sync(ctx);
 }
@@ -886,7 +845,7 @@ int pgv_kmeans(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, int dim, const void *
     } else {
         const void *s_dev;
         PGV_TRY(stage_rows(ctx, samples, n, dim, dtype, g, ctx->rows_stage, &s_dev));
-        PGV_TRY(kmeanspp_dev(ctx, ops, dtype, g, s_dev, n, k, r, centers_dev));
+        PGV_TRY(kmeanspp_dev(ctx, kmeans_rows(ops, dtype, g, s_dev, n), k, r, centers_dev));
 
         // km_g: sums[k x ld] | counts[k] | changes | closest[n]
         PGV_TRY(ctx->km_g.ensure(sizeof(float) * (size_t)k * g.ld + sizeof(int32_t) * ((size_t)k + (size_t)n) + 64));

@@ -230,13 +230,10 @@ int pgv_kmeans_sharded(pgv_comm *cm, pgv_ops ops, pgv_dtype dtype, int dim, cons
         if (n > 0) PGV_TRY(stage_rows(ctx, samples, n, dim, dtype, g, ctx->rows_stage, &s_dev));
 
         // ---- k-means++ (src/ivfkmeans.c:23-91) over the sharded sample
-        const int nblocks = n > 0 ? kmpp_block_count(n) : 0;
-        PGV_TRY(ctx->km_a.ensure(sizeof(float) * 2 * (size_t)(n > 0 ? n : 1)));
-        PGV_TRY(ctx->km_b.ensure(sizeof(double) * ((size_t)nblocks + (size_t)k + 1)));
-        float *weight = ctx->km_a.as<float>();
-        float *raw = weight + (n > 0 ? n : 1);
-        double *block_sums = ctx->km_b.as<double>();
-        double *draws_dev = block_sums + nblocks;
+        const RowsView sv = kmeans_rows(ops, dtype, g, s_dev, n);
+        KmppState st;
+        int64_t first;
+        PGV_TRY(kmpp_begin(ctx, n, k, n_total, r, &st, &first));
         // cm->b: my total | totals[R]      cm->c: my candidate row | gathered rows [R]      cm->d: owner
         PGV_TRY(cm->b.ensure(sizeof(double) * (size_t)(R + 1)));
         PGV_TRY(cm->c.ensure(row_bytes * (size_t)(R + 1)));
@@ -247,14 +244,6 @@ int pgv_kmeans_sharded(pgv_comm *cm, pgv_ops ops, pgv_dtype dtype, int dim, cons
         char *rows_all = send_row + row_bytes;
         int32_t *owner = cm->d.as<int32_t>();
 
-        const int64_t first = (int64_t)(r.next_u32() % (uint32_t)n_total);
-        PGV_TRY(ctx->h_b.ensure(sizeof(double) * (size_t)k + sizeof(float) * (size_t)(n > 0 ? n : 1)));
-        double *h_draws = ctx->h_b.as<double>();
-        for (int i = 0; i + 1 < k; i++) h_draws[i] = r.next_double();
-        float *h_w = reinterpret_cast<float *>(h_draws + k);
-        for (int j = 0; j < n; j++) h_w[j] = 3.402823466e+38f;  // FLT_MAX (:39-40)
-        PGV_HIP(hipMemcpyAsync(draws_dev, h_draws, sizeof(double) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
-        if (n > 0) PGV_HIP(hipMemcpyAsync(weight, h_w, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
         // the first center: the sample RandomInt() % numSamples names, wherever it lives
         int first_owner = 0;
         int64_t at = first;
@@ -269,19 +258,16 @@ int pgv_kmeans_sharded(pgv_comm *cm, pgv_ops ops, pgv_dtype dtype, int dim, cons
         PGV_TRY(comm_all_gather(cm, send_row, rows_all, row_bytes));
         PGV_TRY(launch_kmpp_take_row(ctx, g, rows_all, owner, centers_dev, -1));
 
-        const pgv_metric km = spherical(ops) ? PGV_NEG_IP : PGV_L2SQ;
         for (int i = 0; i + 1 < k; i++) {
-            const void *center_i = static_cast<const char *>(centers_dev) + (size_t)i * row_bytes;
             if (n > 0) {
-                PGV_TRY(dense_scan(ctx, RowsView{s_dev, n, g, row_kind(dtype), km}, center_i, 1, 0, raw));
-                PGV_TRY(launch_kmpp_update(ctx, raw, weight, n, spherical(ops) ? 1 : 0, block_sums));
-                PGV_TRY(launch_kmpp_total(ctx, block_sums, nblocks, my_total));
+                PGV_TRY(kmpp_round_weights(ctx, sv, static_cast<const char *>(centers_dev) + (size_t)i * row_bytes, st));
+                PGV_TRY(launch_kmpp_total(ctx, st.block_sums, st.nblocks, my_total));
             } else {
                 PGV_HIP(hipMemsetAsync(my_total, 0, sizeof(double), ctx->stream));
             }
             PGV_TRY(comm_all_gather(cm, my_total, totals, sizeof(double)));
-            PGV_TRY(launch_kmpp_pick_sharded(ctx, g, s_dev, n, weight, block_sums, totals, cnt_dev, R, cm->rank, draws_dev, i,
-                                             send_row, owner));
+            PGV_TRY(launch_kmpp_pick_sharded(ctx, g, s_dev, n, st.weight, st.block_sums, totals, cnt_dev, R, cm->rank,
+                                             st.draws_dev, i, send_row, owner));
             PGV_TRY(comm_all_gather(cm, send_row, rows_all, row_bytes));
             PGV_TRY(launch_kmpp_take_row(ctx, g, rows_all, owner, centers_dev, i));
         }

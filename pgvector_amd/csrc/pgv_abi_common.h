@@ -68,17 +68,19 @@ int stage_rows(pgv_ctx *ctx, const void *src, int64_t n, int dim, pgv_dtype dtyp
     return stage_rows(ctx, src, n, (size_t)dim * elem_size(dtype), (size_t)g.ld * elem_size(dtype), scratch, out);
 }
 
-// device rows [n x ld] -> caller rows [n x dim] (host or device)
-int unstage_rows(pgv_ctx *ctx, const void *src_dev, int64_t n, int dim, pgv_dtype dtype,
-                 const RowGeom &g, void *dst) {
-    const size_t es = elem_size(dtype);
+// device rows [n x padded] bytes -> the caller's [n x tight] (host or device)
+int unstage_rows(pgv_ctx *ctx, const void *src_dev, int64_t n, size_t tight, size_t padded, void *dst) {
     if (n == 0) return PGV_OK;
     const bool dev = is_device_ptr(dst);
-    PGV_HIP(hipMemcpy2DAsync(dst, (size_t)dim * es, src_dev, (size_t)g.ld * es, (size_t)dim * es,
-                             (size_t)n, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                             ctx->stream));
+    PGV_HIP(hipMemcpy2DAsync(dst, tight, src_dev, padded, tight, (size_t)n,
+                             dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
     if (!dev) PGV_HIP(hipStreamSynchronize(ctx->stream));
     return PGV_OK;
+}
+// ... the rows of g -> rows of dim elements
+int unstage_rows(pgv_ctx *ctx, const void *src_dev, int64_t n, int dim, pgv_dtype dtype,
+                 const RowGeom &g, void *dst) {
+    return unstage_rows(ctx, src_dev, n, (size_t)dim * elem_size(dtype), (size_t)g.ld * elem_size(dtype), dst);
 }
 
 // flat array host-or-device -> device
@@ -354,6 +356,14 @@ struct Rng {
     }
 };
 
+// what a k-means++ seeding keeps on the device between its rounds (kmpp_begin carves it)
+struct KmppState {
+    float *weight, *raw;             // km_a: weight[n] | raw[n] -- the newest center's distances
+    double *block_sums, *draws_dev;  // km_b: block_sums[nblocks] | draws[k]
+    int nblocks;
+    int32_t *picked;                 // km_c: picked[k]
+};
+
 }  // namespace
 
 // ---- shared by the IVFFlat scans and the exact scan
@@ -386,6 +396,11 @@ static int approx_candidates(int k) {
 
 static bool spherical(pgv_ops ops) { return ops == PGV_OPS_IP || ops == PGV_OPS_COSINE; }
 
+// the staged samples of a float k-means as the scans take them: the spherical opclasses seed by inner product
+static RowsView kmeans_rows(pgv_ops ops, pgv_dtype dtype, const RowGeom &g, const void *s_dev, int n) {
+    return {s_dev, n, g, row_kind(dtype), spherical(ops) ? PGV_NEG_IP : PGV_L2SQ};
+}
+
 static int check_ops(pgv_ops ops) {
     if (ops != PGV_OPS_L2 && ops != PGV_OPS_IP && ops != PGV_OPS_COSINE)
         PGV_FAIL(PGV_ERR_ARG, "unknown opclass family %d", (int)ops);
@@ -403,6 +418,15 @@ int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *prob
 int check_batch_args(pgv_index *ix, const void *queries, int nq, int probes, int k, float *out_dist, uint64_t *out_tid,
                      const char *who);
 // pgv_abi_build.hip
+// The k-means++ seeding (InitCenters, src/ivfkmeans.c:23-91) in the two parts every driver has.  kmpp_begin: the buffers
+// of a seeding over n_local staged samples of n_total (0 local samples: an empty rank), the draws in the reference's
+// order -- RandomInt() % n_total into *first, then one RandomDouble() per further center, before anything else touches
+// rng -- and the draws and the FLT_MAX weights on their way to the device.  Nothing is waited for: the caller places the
+// first center and synchronises once before h_b is used again.  kmpp_round_weights: the distances of sv's rows (fp32,
+// fp16 or bits) to the newest center, weight = min(weight, that distance as the element kind squares it) and the
+// weights' block sums
+int kmpp_begin(pgv_ctx *ctx, int n_local, int k, int64_t n_total, Rng &rng, KmppState *state, int64_t *first);
+int kmpp_round_weights(pgv_ctx *ctx, const RowsView &sv, const void *center_i, const KmppState &state);
 int lloyd_partial_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &g, const void *samples_dev, int n,
                       const void *centers_dev, int k, int32_t *closest_io, float *sums, int32_t *counts,
                       unsigned long long *changes);
