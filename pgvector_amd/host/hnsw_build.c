@@ -27,6 +27,12 @@
  * re-check earlier rejects against the whole selection) is put aside, the missing pairs of its
  * list are fetched in a second launch, and it is replayed then; lists are independent, so that
  * changes nothing.
+ *
+ * The file from top to bottom: the lists and SelectNeighbors; stage A of a batch (its searches) and the helper threads
+ * that run it ahead; what the two forms of the build share (plan_batch, find_duplicate, the first element, the cancel
+ * poll); build_linked_on_device, the graph updates on the GPU; the host replay of the same updates -- its state in one
+ * struct (host_link), one function per numbered step of a batch, build_linked_on_host as the loop over them; and
+ * pgv_host_hnsw_build, which draws the levels, decides the form and calls one of the two.
  */
 #include "pgv_host.h"
 
@@ -152,6 +158,22 @@ rng_double(rng_state * r)
 	return ldexp((double) (out >> 12), -52);
 }
 
+/* room for one more item in an array that grows by doubling (`first` items to begin with): the array, moved if it had
+ * to grow, or NULL when out of memory (the old one stays as it was) */
+static inline void *
+room_for_one(void *arr, int64_t used, int64_t *cap, size_t item_bytes, int64_t first)
+{
+	const int64_t ncap = *cap ? *cap * 2 : first;
+	void	   *grown;
+
+	if (used < *cap)
+		return arr;
+	grown = realloc(arr, item_bytes * (size_t) ncap);
+	if (grown)
+		*cap = ncap;
+	return grown;
+}
+
 /* per-thread bump allocator for a batch's records (ids, distance matrices): reset at the end of the batch instead of
  * a malloc/free pair per list -- a 100 k x 1536 build touched 4.3 M lists and spent 15 % of its time in free() */
 typedef struct
@@ -161,8 +183,8 @@ typedef struct
 				cur;
 	size_t		used;
 	void	  **big;			/* requests larger than a chunk */
-	int			nbig,
-				bigcap;
+	int			nbig;
+	int64_t		bigcap;
 }			arena;
 
 #define ARENA_CHUNK ((size_t) 1 << 20)
@@ -175,23 +197,13 @@ arena_alloc(arena * a, size_t bytes)
 	bytes = (bytes + 15) & ~(size_t) 15;
 	if (bytes > ARENA_CHUNK)
 	{
-		if (a->nbig == a->bigcap)
-		{
-			void	  **grown = realloc(a->big, sizeof(void *) * (size_t) (a->bigcap ? a->bigcap * 2 : 8));
+		void	  **big = room_for_one(a->big, a->nbig, &a->bigcap, sizeof(void *), 8);
 
-			if (!grown)
-				return NULL;
-			a->big = grown;
-			a->bigcap = a->bigcap ? a->bigcap * 2 : 8;
-		}
-		p = malloc(bytes);
-		if (p && a->big)
+		if (!big)
+			return NULL;
+		a->big = big;
+		if ((p = malloc(bytes)) != NULL)
 			a->big[a->nbig++] = p;
-		else
-		{
-			free(p);
-			p = NULL;
-		}
 		return p;
 	}
 	if (a->nchunks == 0 || a->used + bytes > ARENA_CHUNK)
@@ -253,16 +265,16 @@ typedef struct
 typedef struct
 {
 	record	   *recs;
-	int			nrec,
-				cap;
+	int			nrec;
+	int64_t		cap;
 	link_req   *links;
 	int64_t		nlinks,
 				links_cap;
-	int32_t    *tab;			/* hash: (owner, lc) -> own record index + 1 */
+	int32_t    *tab;			/* hash: (owner, lc) -> own record index + 1; grows by doubling at load factor 1/2 */
 	int64_t		tab_cap;
 	int32_t    *dirty;			/* owners whose tuples this batch rewrites, first seen by this thread */
-	int			ndirty,
-				dirty_cap;
+	int			ndirty;
+	int64_t		dirty_cap;
 	int			oom;
 	int64_t		rec_base,		/* where its records / requests start in the batch's arrays */
 				link_base;
@@ -282,7 +294,24 @@ enum
 {
 	PH_SEARCH, PH_PAIRS, PH_SELECT, PH_RECORDS, PH_UPDATE, PH_PATCH, PH_PAIRLIST, PH_FREE, PH_COUNT
 };
-#define PHASE(p) do { double t_ = now_secs(); out->phase_secs[cur_phase] += t_ - phase_t0; phase_t0 = t_; cur_phase = (p); } while (0)
+
+typedef struct
+{
+	double	   *secs;			/* out->phase_secs */
+	double		t0;				/* when the phase that is running began */
+	int			cur;
+}			phase_clock;
+
+/* the time since the last switch goes to the phase that was running; p runs from now on */
+static void
+phase(phase_clock * clk, int p)
+{
+	double		t = now_secs();
+
+	clk->secs[clk->cur] += t - clk->t0;
+	clk->t0 = t;
+	clk->cur = p;
+}
 
 static inline int
 layer_m(int m, int lc)
@@ -363,6 +392,47 @@ group_pairs(int n, int from)
 	if (from < 1)
 		from = 1;
 	return n > from ? ((int64_t) n * (n - 1) - (int64_t) from * (from - 1)) / 2 : 0;
+}
+
+/* the request is complete: npairs pairs in all */
+static void
+groups_end(groupbuf * gb, int64_t npairs)
+{
+	if (gb->ngroups > 0)
+		gb->pair_start[gb->ngroups] = npairs;
+}
+
+static void
+groups_free(groupbuf * gb)
+{
+	free(gb->ids);
+	free(gb->ids_start);
+	free(gb->from);
+	free(gb->pair_start);
+	memset(gb, 0, sizeof(*gb));
+}
+
+/* the distances a request asks for, on `handle` (the mirror, or a helper's view of it) */
+static int
+score_groups(pgv_hnsw * handle, const groupbuf * gb, int64_t npairs, float *out)
+{
+	return pgv_hnsw_score_groups(handle, gb->ids, gb->ids_start, gb->from, gb->pair_start, gb->ngroups, gb->nids, npairs, out);
+}
+
+/* pinned room for n floats: grown to twice what is asked for, what it held is not kept */
+static int
+pinned_room(float **buf, int64_t *cap, int64_t n)
+{
+	int			rc;
+
+	if (n <= *cap)
+		return PGV_OK;
+	pgv_pinned_free(*buf);
+	*buf = NULL;
+	*cap = n * 2;
+	if ((rc = pgv_pinned_alloc(sizeof(float) * (size_t) *cap, (void **) buf)) != PGV_OK)
+		*cap = 0;
+	return rc;
 }
 
 /*
@@ -609,28 +679,8 @@ pgv_host_hnsw_built_free(pgv_hnsw_built * b)
 	memset(b, 0, sizeof(*b));
 }
 
-/* rewrite element e's neighbor tuple (HnswNeighborTupleData: layer lc at (level - lc) * m) in the flat image */
-static void
-write_tuple(const elem * el, int32_t e, int m, const int64_t *nbr_start, int32_t *nbr)
-{
-	const elem *x = &el[e];
-	int64_t		base = nbr_start[e];
-
-	for (int64_t j = base; j < nbr_start[e + 1]; j++)
-		nbr[j] = -1;
-	if (!x->layers)
-		return;
-	for (int lc = 0; lc <= x->level; lc++)
-	{
-		const nlist *l = &x->layers[lc];
-		int64_t		o = base + (int64_t) (x->level - lc) * m;
-
-		for (int i = 0; i < l->length; i++)
-			nbr[o + i] = l->items[i].element;
-	}
-}
-
-/* one layer's part of that tuple, from the list as it stands (the replay writes it while the list is in its cache) */
+/* one layer's part of element e's neighbor tuple in the flat image (HnswNeighborTupleData: layer lc at (level - lc) * m),
+ * from the list as it stands (the replay writes it while the list is in its cache) */
 static inline void
 write_segment(const elem * x, int32_t e, int lc, int m, const int64_t *nbr_start, int32_t *nbr)
 {
@@ -643,6 +693,25 @@ write_segment(const elem * x, int32_t e, int lc, int m, const int64_t *nbr_start
 		o[i] = l->items[i].element;
 	for (; i < lm; i++)
 		o[i] = -1;
+}
+
+/* the whole tuple of an element that has lists: its layers' parts fill it exactly */
+static void
+write_tuple(const elem * el, int32_t e, int m, const int64_t *nbr_start, int32_t *nbr)
+{
+	for (int lc = 0; lc <= el[e].level; lc++)
+		write_segment(&el[e], e, lc, m, nbr_start, nbr);
+}
+
+static void
+layers_free(elem * x)
+{
+	if (!x->layers)
+		return;
+	for (int lc = 0; lc <= x->level; lc++)
+		free(x->layers[lc].items);
+	free(x->layers);
+	x->layers = NULL;
 }
 
 /* ------------------------------------------------------------ stage A of a batch
@@ -659,10 +728,14 @@ write_segment(const elem * x, int32_t e, int lc, int m, const int64_t *nbr_start
  */
 typedef struct
 {
-	/* the batch */
-	int64_t		i0;
-	int			B,
-				lcap;
+	int64_t		i0;				/* its first element */
+	int			B,				/* its elements */
+				lcap;			/* the layers the tallest of them searches: 1 + its level, the entry point's at the most */
+}			batch_plan;
+
+typedef struct
+{
+	batch_plan	plan;			/* the batch */
 	/* what stage A yields */
 	int32_t    *sw_ids;
 	float	   *sw_dist;
@@ -681,7 +754,6 @@ typedef struct
 	int64_t		npairs;
 	int			rc;
 	char		err[200];
-	double		secs[2];		/* search, pairs */
 	uint64_t	seq;			/* the helper's job that computes it (run ahead) */
 	/* the device-link build's two-step form: searches kept on the device in `slot`, the selection a job of its own */
 	int			slot;
@@ -702,25 +774,58 @@ stage_a_free(stage_a * a)
 	free(a->sel_dist);
 	free(a->sel_closer);
 	free(a->sel_cnt);
-	free(a->gb.ids);
-	free(a->gb.ids_start);
-	free(a->gb.from);
-	free(a->gb.pair_start);
+	groups_free(&a->gb);
 	pgv_pinned_free(a->pdist);
 	memset(a, 0, sizeof(*a));
+}
+
+/* the request of a batch's searches: its elements' slots and, behind them, their levels ([2 x B]; NULL: no memory) */
+static int32_t *
+stage_request(const stage_a * a, const elem * el)
+{
+	const int	B = a->plan.B;
+	int32_t    *ids = malloc(sizeof(int32_t) * (size_t) B * 2);
+
+	for (int b = 0; ids && b < B; b++)
+	{
+		ids[b] = (int32_t) (a->plan.i0 + b);
+		ids[B + b] = el[a->plan.i0 + b].level;
+	}
+	return ids;
+}
+
+/* room for the lists SelectNeighbors on the device sends back, [B x lcap x 2m]; 0 = out of memory */
+static int
+stage_sel_room(stage_a * a, int m)
+{
+	const size_t per = (size_t) a->plan.B * a->plan.lcap,
+				stride = 2 * (size_t) m;
+
+	a->sel_ids = realloc(a->sel_ids, sizeof(int32_t) * per * stride);
+	a->sel_dist = realloc(a->sel_dist, sizeof(float) * per * stride);
+	a->sel_closer = realloc(a->sel_closer, per * stride);
+	a->sel_cnt = realloc(a->sel_cnt, sizeof(int32_t) * per);
+	return a->sel_ids && a->sel_dist && a->sel_closer && a->sel_cnt;
+}
+
+/* the stage failed on this thread: the code and the text (a device call's: pgv_last_error(), which is per thread) stay
+ * with it for the main thread */
+static int
+stage_fail(stage_a * a, int rc, const char *why)
+{
+	snprintf(a->err, sizeof(a->err), "%s", why);
+	return a->rc = rc;
 }
 
 /* steps 1 and 2 of a batch on `handle` (the mirror itself, or the helper's view of it) */
 static int
 run_stage_a(pgv_hnsw * handle, stage_a * a, const elem * el, int m, int ef_construction)
 {
-	const int	B = a->B,
-				lcap = a->lcap;
+	const int	B = a->plan.B,
+				lcap = a->plan.lcap;
 	size_t		per = (size_t) B * lcap;
-	int32_t    *ids = malloc(sizeof(int32_t) * (size_t) B);
-	int32_t    *lv = malloc(sizeof(int32_t) * (size_t) B);
+	int32_t    *ids = stage_request(a, el);
 	int64_t		total = 0;
-	double		t0 = now_secs();
 	int			rc;
 
 	a->rc = PGV_OK;
@@ -728,60 +833,33 @@ run_stage_a(pgv_hnsw * handle, stage_a * a, const elem * el, int m, int ef_const
 	if (a->device_select)
 	{
 		/* searches + SelectNeighbors in one call: what comes back is the lists themselves */
-		const size_t stride = 2 * (size_t) m;
 		int64_t		pairs = 0;
 
-		a->sel_ids = realloc(a->sel_ids, sizeof(int32_t) * per * stride);
-		a->sel_dist = realloc(a->sel_dist, sizeof(float) * per * stride);
-		a->sel_closer = realloc(a->sel_closer, per * stride);
-		a->sel_cnt = realloc(a->sel_cnt, sizeof(int32_t) * per);
-		if (!ids || !lv || !a->sel_ids || !a->sel_dist || !a->sel_closer || !a->sel_cnt)
+		if (!stage_sel_room(a, m) || !ids)
 		{
 			free(ids);
-			free(lv);
-			snprintf(a->err, sizeof(a->err), "out of memory");
-			return a->rc = PGV_ERR_NOMEM;
+			return stage_fail(a, PGV_ERR_NOMEM, "out of memory");
 		}
-		for (int b = 0; b < B; b++)
-		{
-			ids[b] = (int32_t) (a->i0 + b);
-			lv[b] = el[a->i0 + b].level;
-		}
-		rc = pgv_hnsw_build_neighbors(handle, ids, lv, B, ef_construction, lcap, a->sel_ids, a->sel_dist, a->sel_closer,
+		rc = pgv_hnsw_build_neighbors(handle, ids, ids + B, B, ef_construction, lcap, a->sel_ids, a->sel_dist, a->sel_closer,
 									  a->sel_cnt, &pairs);
 		free(ids);
-		free(lv);
 		a->npairs = pairs;
-		a->secs[0] = now_secs() - t0;
-		a->secs[1] = 0;
-		if (rc != PGV_OK)
-			goto dev_fail;
-		return PGV_OK;
+		return rc == PGV_OK ? PGV_OK : stage_fail(a, rc, pgv_last_error());
 	}
 	a->sw_ids = realloc(a->sw_ids, sizeof(int32_t) * per * ef_construction);
 	a->sw_dist = realloc(a->sw_dist, sizeof(float) * per * ef_construction);
 	a->sw_cnt = realloc(a->sw_cnt, sizeof(int32_t) * per);
 	a->tri_off = realloc(a->tri_off, sizeof(int64_t) * per);
-	if (!ids || !lv || !a->sw_ids || !a->sw_dist || !a->sw_cnt || !a->tri_off)
+	if (!ids || !a->sw_ids || !a->sw_dist || !a->sw_cnt || !a->tri_off)
 	{
 		free(ids);
-		free(lv);
-		snprintf(a->err, sizeof(a->err), "out of memory");
-		return a->rc = PGV_ERR_NOMEM;
+		return stage_fail(a, PGV_ERR_NOMEM, "out of memory");
 	}
 	/* ---- 1. the searches of HnswFindElementNeighbors for the whole batch */
-	for (int b = 0; b < B; b++)
-	{
-		ids[b] = (int32_t) (a->i0 + b);
-		lv[b] = el[a->i0 + b].level;
-	}
-	rc = pgv_hnsw_build_search(handle, ids, lv, B, ef_construction, lcap, a->sw_ids, a->sw_dist, a->sw_cnt);
+	rc = pgv_hnsw_build_search(handle, ids, ids + B, B, ef_construction, lcap, a->sw_ids, a->sw_dist, a->sw_cnt);
 	free(ids);
-	free(lv);
-	a->secs[0] = now_secs() - t0;
-	t0 = now_secs();
 	if (rc != PGV_OK)
-		goto dev_fail;
+		return stage_fail(a, rc, pgv_last_error());
 	/* ---- 2. pairwise distances inside every candidate list that has to be thinned */
 	groups_reset(&a->gb);
 	for (int b = 0; b < B; b++)
@@ -794,95 +872,56 @@ run_stage_a(pgv_hnsw * handle, stage_a * a, const elem * el, int m, int ef_const
 			{
 				/* the candidates as one group, the whole triangle: expanded on the device */
 				if (!groups_add(&a->gb, a->sw_ids + ((size_t) b * lcap + lc) * ef_construction, nw, 1, total))
-				{
-					snprintf(a->err, sizeof(a->err), "out of memory");
-					return a->rc = PGV_ERR_NOMEM;
-				}
+					return stage_fail(a, PGV_ERR_NOMEM, "out of memory");
 				total += group_pairs(nw, 1);
 			}
 		}
 	a->npairs = total;
-	if (a->gb.ngroups > 0)
-		a->gb.pair_start[a->gb.ngroups] = total;
-	if (total > a->pdist_cap)
-	{
-		pgv_pinned_free(a->pdist);
-		a->pdist = NULL;
-		a->pdist_cap = total * 2;
-		if ((rc = pgv_pinned_alloc(sizeof(float) * (size_t) a->pdist_cap, (void **) &a->pdist)) != PGV_OK)
-		{
-			a->pdist_cap = 0;
-			goto dev_fail;
-		}
-	}
-	if (total > 0)
-	{
-		rc = pgv_hnsw_score_groups(handle, a->gb.ids, a->gb.ids_start, a->gb.from, a->gb.pair_start, a->gb.ngroups, a->gb.nids,
-								   total, a->pdist);
-		if (rc != PGV_OK)
-			goto dev_fail;
-	}
-	a->secs[1] = now_secs() - t0;
+	groups_end(&a->gb, total);
+	if ((rc = pinned_room(&a->pdist, &a->pdist_cap, total)) != PGV_OK)
+		return stage_fail(a, rc, pgv_last_error());
+	if (total > 0 && (rc = score_groups(handle, &a->gb, total, a->pdist)) != PGV_OK)
+		return stage_fail(a, rc, pgv_last_error());
 	return PGV_OK;
-dev_fail:
-	snprintf(a->err, sizeof(a->err), "%s", pgv_last_error());
-	return a->rc = rc;
 }
 
 /* stage A in two jobs (the device-link build): the searches, their candidate lists kept on the device ... */
 static void
 run_search_keep(pgv_hnsw * handle, stage_a * a, const elem * el, int ef_construction)
 {
-	const int	B = a->B;
-	int32_t    *ids = malloc(sizeof(int32_t) * (size_t) B * 2);
-	double		t0 = now_secs();
+	const int	B = a->plan.B;
+	int32_t    *ids = stage_request(a, el);
+	int			rc;
 
 	a->rc = PGV_OK;
 	a->err[0] = 0;
 	if (!ids)
 	{
-		snprintf(a->err, sizeof(a->err), "out of memory");
-		a->rc = PGV_ERR_NOMEM;
+		stage_fail(a, PGV_ERR_NOMEM, "out of memory");
 		return;
 	}
-	for (int b = 0; b < B; b++)
-	{
-		ids[b] = (int32_t) (a->i0 + b);
-		ids[B + b] = el[a->i0 + b].level;
-	}
-	a->rc = pgv_hnsw_build_search_keep(handle, ids, ids + B, B, ef_construction, a->lcap, a->slot);
-	if (a->rc != PGV_OK)
-		snprintf(a->err, sizeof(a->err), "%s", pgv_last_error());
+	if ((rc = pgv_hnsw_build_search_keep(handle, ids, ids + B, B, ef_construction, a->plan.lcap, a->slot)) != PGV_OK)
+		stage_fail(a, rc, pgv_last_error());
 	free(ids);
-	a->secs[0] = now_secs() - t0;
 }
 
 /* ... and SelectNeighbors over them: the lists as AddConnections stores them come back */
 static void
 run_select_kept(pgv_hnsw * handle, stage_a * a, int m)
 {
-	const size_t per = (size_t) a->B * a->lcap,
-				stride = 2 * (size_t) m;
 	int64_t		pairs = 0;
-	double		t0 = now_secs();
+	int			rc;
 
 	if (a->rc != PGV_OK)		/* (the searches failed: nothing to select from) */
 		return;
-	a->sel_ids = realloc(a->sel_ids, sizeof(int32_t) * per * stride);
-	a->sel_dist = realloc(a->sel_dist, sizeof(float) * per * stride);
-	a->sel_closer = realloc(a->sel_closer, per * stride);
-	a->sel_cnt = realloc(a->sel_cnt, sizeof(int32_t) * per);
-	if (!a->sel_ids || !a->sel_dist || !a->sel_closer || !a->sel_cnt)
+	if (!stage_sel_room(a, m))
 	{
-		snprintf(a->err, sizeof(a->err), "out of memory");
-		a->rc = PGV_ERR_NOMEM;
+		stage_fail(a, PGV_ERR_NOMEM, "out of memory");
 		return;
 	}
-	a->rc = pgv_hnsw_build_select_kept(handle, a->slot, a->sel_ids, a->sel_dist, a->sel_closer, a->sel_cnt, &pairs);
-	if (a->rc != PGV_OK)
-		snprintf(a->err, sizeof(a->err), "%s", pgv_last_error());
+	if ((rc = pgv_hnsw_build_select_kept(handle, a->slot, a->sel_ids, a->sel_dist, a->sel_closer, a->sel_cnt, &pairs)) != PGV_OK)
+		stage_fail(a, rc, pgv_last_error());
 	a->npairs = pairs;
-	a->secs[1] = now_secs() - t0;
 }
 
 /* a graph patch handed to the helper (step 6): its arrays stay untouched until the job is over */
@@ -982,8 +1021,7 @@ worker_main(void *arg)
 		{
 			score_job  *sj = ja;
 
-			sj->rc = sj->npairs > 0 ? pgv_hnsw_score_groups(w->view, sj->gb.ids, sj->gb.ids_start, sj->gb.from, sj->gb.pair_start,
-															  sj->gb.ngroups, sj->gb.nids, sj->npairs, sj->out) : PGV_OK;
+			sj->rc = sj->npairs > 0 ? score_groups(w->view, &sj->gb, sj->npairs, sj->out) : PGV_OK;
 			if (sj->rc != PGV_OK)
 				snprintf(sj->err, sizeof(sj->err), "%s", pgv_last_error());
 		}
@@ -1112,35 +1150,14 @@ worker_stop(worker * w)
 	w->started = 0;
 }
 
-/*
- * The batches with the graph updates ON THE DEVICE (pgv_hnsw_link_*): the host keeps the order of things and
- * FindDuplicateInMemory; SelectNeighbors for the new elements runs on the device behind their searches, the lists they
- * chose are replayed by GPU wavefronts (csrc/hnsw_link_core.h: the reference's HnswUpdateConnection), and the tuples the
- * next batch searches are rewritten in place -- no list state, no pair distance and no neighbor tuple crosses PCIe until
- * the finished graph comes back.
- *
- * Three streams share the GPU once batches are full (each a context of its own; S and T are helper threads):
- *   S  searches of batch n + 2            (pgv_hnsw_build_search_keep: posted when batch n has been applied, so they see
- *                                          the graph without batch n + 1 -- the blindness of the host-side form)
- *   T  SelectNeighbors of batch n + 1     (pgv_hnsw_build_select_kept, over the lists S kept on the device)
- *   main  duplicates of batch n, pgv_hnsw_link_prepare (n) -- requests grouped by list, the lists' pair distances --,
- *         then, once the searches that read the old tuples are over (S of n + 1), pgv_hnsw_link_apply (n)
- * The searches are the longest step and run back to back but for the apply in between.  Batches that are not full, or
- * that move the entry point, are done in turn (pgv_hnsw_build_neighbors on the mirror itself); max_batch = 1 is the
- * reference's serial loop.
- */
-typedef struct
-{
-	int64_t		i0;
-	int			B,
-				lcap;
-}			batch_plan;
+/* ------------------------------------------------------------ what the two forms of the build share */
 
 /* the batch that starts at i0 when `linked` elements are in the graph and the entry point stands at entry_level */
 static batch_plan
 plan_batch(const elem * el, int64_t n, int64_t i0, int64_t linked, int entry_level, int max_batch)
 {
 	batch_plan	p;
+	/* as many concurrent inserts as the graph can absorb without the newcomers missing each other much */
 	int			B = (int) (linked / 16);
 
 	if (B < 1)
@@ -1149,7 +1166,9 @@ plan_batch(const elem * el, int64_t n, int64_t i0, int64_t linked, int entry_lev
 		B = max_batch;
 	if (B > n - i0)
 		B = (int) (n - i0);
-	/* the batch ends at (and includes) the first element taller than the entry point (src/hnswbuild.c:398-431) */
+	/* An element taller than the entry point becomes the new entry under the reference's exclusive entry lock
+	 * (src/hnswbuild.c:398-431): the next tall element links to it on the new top layers.  The batch therefore ends at
+	 * (and includes) the first such element -- later ones search from the new entry. */
 	for (int b = 0; b < B; b++)
 		if (el[i0 + b].level > entry_level)
 		{
@@ -1179,8 +1198,80 @@ batch_has_tall(const elem * el, const batch_plan * p, int entry_level)
 }
 
 static int
+same_plan(const batch_plan * a, const batch_plan * b)
+{
+	return a->i0 == b->i0 && a->B == b->B && a->lcap == b->lcap;
+}
+
+/* CREATE INDEX can be cancelled between batches (a batch is milliseconds) */
+static int
+poll_cancel(int64_t i0, int64_t n)
+{
+	if (cancel_check != NULL && cancel_check(cancel_arg))
+		return pgv_host_fail(PGV_ERR_STATE, "pgv_host_hnsw_build: cancelled after %lld of %lld rows", (long long) i0, (long long) n);
+	return PGV_OK;
+}
+
+/* the first element has nothing to search: it becomes the entry point (with_lists: the host replay keeps its lists) */
+static int
+link_first_element(pgv_hnsw * mirror, elem * el, int32_t e, int m, int with_lists)
+{
+	if (with_lists)
+	{
+		el[e].layers = calloc((size_t) el[e].level + 1, sizeof(nlist));
+		for (int lc = 0; lc <= el[e].level; lc++)
+			el[e].layers[lc].items = items_alloc(layer_m(m, lc));
+	}
+	return pgv_hnsw_update_graph(mirror, e, NULL, 0, NULL, NULL);
+}
+
+/*
+ * FindDuplicateInMemory, src/hnswbuild.c:313-364, for element e (called in heap order) with its layer-0 list, `count`
+ * elements `stride` bytes apart: an element's neighbors are ordered by distance, the identical ones first, so the walk
+ * stops at the first neighbor that is not byte for byte e's row.  An identical one with room for another heap TID
+ * takes e's: returns that element, or -1 when e has to be linked.
+ */
+static int32_t
+find_duplicate(elem * el, const void *rows, size_t item_bytes, int32_t e, const int32_t *list, size_t stride, int count)
+{
+	const char *v = (const char *) rows + (size_t) e * item_bytes;
+
+	for (int i = 0; i < count; i++)
+	{
+		int32_t		ne = *(const int32_t *) ((const char *) list + (size_t) i * stride);
+
+		if (memcmp(v, (const char *) rows + (size_t) ne * item_bytes, item_bytes) != 0)
+			break;
+		if (el[ne].heaptids < HNSW_HEAPTIDS)
+		{
+			el[ne].heaptids++;
+			return ne;
+		}
+	}
+	return -1;
+}
+
+/*
+ * The batches with the graph updates ON THE DEVICE (pgv_hnsw_link_*): the host keeps the order of things and
+ * FindDuplicateInMemory; SelectNeighbors for the new elements runs on the device behind their searches, the lists they
+ * chose are replayed by GPU wavefronts (csrc/hnsw_link_core.h: the reference's HnswUpdateConnection), and the tuples the
+ * next batch searches are rewritten in place -- no list state, no pair distance and no neighbor tuple crosses PCIe until
+ * the finished graph comes back.
+ *
+ * Three streams share the GPU once batches are full (each a context of its own; S and T are helper threads):
+ *   S  searches of batch n + 2            (pgv_hnsw_build_search_keep: posted when batch n has been applied, so they see
+ *                                          the graph without batch n + 1 -- the blindness of the host-side form)
+ *   T  SelectNeighbors of batch n + 1     (pgv_hnsw_build_select_kept, over the lists S kept on the device)
+ *   main  duplicates of batch n, pgv_hnsw_link_prepare (n) -- requests grouped by list, the lists' pair distances --,
+ *         then, once the searches that read the old tuples are over (S of n + 1), pgv_hnsw_link_apply (n)
+ * The searches are the longest step and run back to back but for the apply in between.  Batches that are not full, or
+ * that move the entry point, are done in turn (pgv_hnsw_build_neighbors on the mirror itself); max_batch = 1 is the
+ * reference's serial loop.
+ */
+static int
 build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, int m, int ef_construction,
-					   int max_batch, elem * el, pgv_hnsw_built * out, int32_t *entry_io, int64_t *linked_io)
+					   int max_batch, elem * el, pgv_hnsw_built * out, phase_clock * clk, int32_t *entry_io,
+					   int64_t *linked_io)
 {
 	stage_a		stages[3];		/* batch number % 3 */
 	worker		srch,
@@ -1191,8 +1282,6 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 	int32_t    *ids = malloc(sizeof(int32_t) * (size_t) max_batch);
 	uint8_t    *is_linked = malloc((size_t) max_batch);
 	int			rc = PGV_OK;
-	double		phase_t0 = now_secs();
-	int			cur_phase = PH_RECORDS;
 	const int	pipelined = max_batch >= 64;
 
 	memset(stages, 0, sizeof(stages));
@@ -1213,17 +1302,13 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 		stage_a    *a,
 				   *nx;
 
-		if (cancel_check != NULL && cancel_check(cancel_arg))
-		{
-			rc = pgv_host_fail(PGV_ERR_STATE, "pgv_host_hnsw_build: cancelled after %lld of %lld rows", (long long) i0, (long long) n);
+		if ((rc = poll_cancel(i0, n)) != PGV_OK)
 			goto done;
-		}
 		if (entry < 0)
 		{
-			/* the first element has nothing to search: it becomes the entry point */
 			entry = (int32_t) i0;
 			linked = 1;
-			if ((rc = pgv_hnsw_update_graph(mirror, entry, NULL, 0, NULL, NULL)) != PGV_OK)
+			if ((rc = link_first_element(mirror, el, entry, m, 0)) != PGV_OK)
 				goto dev_fail;
 			i0++;
 			out->batches++;
@@ -1234,8 +1319,8 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 		a = &stages[seqno % 3];
 		nx = &stages[(seqno + 1) % 3];
 
-		PHASE(PH_SEARCH);
-		if (a->s_posted && a->i0 == p.i0 && a->B == p.B && a->lcap == p.lcap)
+		phase(clk, PH_SEARCH);
+		if (a->s_posted && same_plan(&a->plan, &p))
 		{
 			/* its searches ran ahead; so did its selection unless the batch before was the first of the pipeline */
 			worker_wait(&srch, a->seq_s);
@@ -1253,9 +1338,7 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 			worker_drain(&sel);
 			for (int i = 0; i < 3; i++)
 				stages[i].s_posted = stages[i].t_posted = 0;
-			a->i0 = p.i0;
-			a->B = p.B;
-			a->lcap = p.lcap;
+			a->plan = p;
 			run_stage_a(mirror, a, el, m, ef_construction);
 		}
 		a->s_posted = a->t_posted = 0;
@@ -1276,9 +1359,7 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 				worker_start(&sel, mirror, el, m, ef_construction);
 			if (srch.started && sel.started)
 			{
-				nx->i0 = q.i0;
-				nx->B = q.B;
-				nx->lcap = q.lcap;
+				nx->plan = q;
 				nx->slot = (int) ((seqno + 1) & 1);
 				nx->seq_s = worker_post(&srch, JOB_SEARCH_KEEP, nx);
 				nx->s_posted = 1;
@@ -1286,31 +1367,15 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 			}
 		}
 
-		PHASE(PH_SELECT);
-		/* FindDuplicateInMemory, src/hnswbuild.c:313-364, in heap order: an element's layer-0 neighbors are ordered by
-		 * distance, the identical ones first */
+		phase(clk, PH_SELECT);
 		for (int b = 0; b < p.B; b++)
 		{
 			int32_t		e = (int32_t) (i0 + b);
-			const size_t g = (size_t) b * p.lcap;
-			const char *v = (const char *) rows + (size_t) e * item_bytes;
+			const size_t g = (size_t) b * p.lcap;	/* its layer-0 list */
 
 			ids[b] = e;
-			is_linked[b] = 1;
-			for (int i = 0; i < a->sel_cnt[g]; i++)
-			{
-				int32_t		ne = a->sel_ids[g * 2 * (size_t) m + i];
-
-				if (memcmp(v, (const char *) rows + (size_t) ne * item_bytes, item_bytes) != 0)
-					break;
-				if (el[ne].heaptids < HNSW_HEAPTIDS)
-				{
-					el[ne].heaptids++;
-					out->dup_of[e] = ne;
-					is_linked[b] = 0;
-					break;
-				}
-			}
+			out->dup_of[e] = find_duplicate(el, rows, item_bytes, e, a->sel_ids + g * 2 * (size_t) m, sizeof(int32_t), a->sel_cnt[g]);
+			is_linked[b] = out->dup_of[e] < 0;
 			if (is_linked[b])
 			{
 				linked++;
@@ -1320,11 +1385,11 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 			}
 		}
 
-		PHASE(PH_RECORDS);
+		phase(clk, PH_RECORDS);
 		if ((rc = pgv_hnsw_link_prepare(mirror, ids, is_linked, p.B, p.lcap, a->sel_ids, a->sel_dist, a->sel_closer, a->sel_cnt,
 										&pairs)) != PGV_OK)
 			goto dev_fail;
-		PHASE(PH_PAIRS);
+		phase(clk, PH_PAIRS);
 		/* the searches that run ahead read the tuples this batch is about to rewrite: they have to be over; their
 		 * selection does not touch the graph and runs on */
 		if (nx->s_posted)
@@ -1336,23 +1401,21 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 				nx->t_posted = 1;
 			}
 		}
-		PHASE(PH_UPDATE);
+		phase(clk, PH_UPDATE);
 		/* (returns with everything enqueued: the searches posted below start on the device when it is through) */
 		if ((rc = pgv_hnsw_link_apply(mirror, entry)) != PGV_OK)
 			goto dev_fail;
 		out->device_pairs += pairs;
-		PHASE(PH_RECORDS);
+		phase(clk, PH_RECORDS);
 		/* the searches of the batch after the next: they see the graph with this batch in it, without the next (whose
 		 * composition has to be certain, full and without a change of the entry point, for the one behind it to be) */
-		if (nx->s_posted && nx->B == max_batch && !batch_has_tall(el, &(batch_plan){nx->i0, nx->B, nx->lcap}, el[entry].level) &&
-			linked / 16 >= max_batch && nx->i0 + nx->B < n && entry_level == el[entry].level)
+		if (nx->s_posted && nx->plan.B == max_batch && !batch_has_tall(el, &nx->plan, el[entry].level) &&
+			linked / 16 >= max_batch && nx->plan.i0 + nx->plan.B < n && entry_level == el[entry].level)
 		{
 			stage_a    *n2 = &stages[(seqno + 2) % 3];
-			batch_plan	q = plan_batch(el, n, nx->i0 + nx->B, linked, entry_level, max_batch);
+			batch_plan	q = plan_batch(el, n, nx->plan.i0 + nx->plan.B, linked, entry_level, max_batch);
 
-			n2->i0 = q.i0;
-			n2->B = q.B;
-			n2->lcap = q.lcap;
+			n2->plan = q;
 			n2->slot = (int) ((seqno + 2) & 1);
 			n2->seq_s = worker_post(&srch, JOB_SEARCH_KEEP, n2);
 			n2->s_posted = 1;
@@ -1364,7 +1427,7 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 	}
 	worker_drain(&srch);
 	worker_drain(&sel);
-	PHASE(PH_PATCH);
+	phase(clk, PH_PATCH);
 	{
 		int64_t		pairs2 = 0,
 					deferred = 0;
@@ -1374,7 +1437,7 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 		out->device_pairs += pairs2;
 		out->deferred_updates += deferred;
 	}
-	PHASE(PH_RECORDS);
+	phase(clk, PH_RECORDS);
 	goto done;
 
 dev_fail:
@@ -1393,83 +1456,949 @@ done:
 	return rc;
 }
 
-int
-pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *rows, int64_t n, int m,
-					int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
+/* ------------------------------------------------------------ the host replay
+ * The batches with the graph updates replayed HERE, on OpenMP threads (PGV_HNSW_HOST_LINK=1; whenever the new elements'
+ * selection is the host's; and when the device has no room for the link state): the form the device's replay is tested
+ * against.  Every distance is still the GPU's.  A batch goes through the numbered steps below, one function each:
+ *   1 + 2  stage A (run_stage_a), on the helper while the batch before is replayed, or in turn       host_stage_a
+ *   3      SelectNeighbors + AddConnections for the new elements, then FindDuplicateInMemory         store_new_lists
+ *   4a-c   a record per neighbor list the batch links into                                           make_records, fill_records
+ *          the records in slices, their pair distances requested                                     request_pairs
+ *   5, 5b  HnswUpdateConnection list by list; the updates that ran out of distances, a second time   replay_lists
+ *   6      the rewritten tuples, handed to the device                                                patch_graph
+ * Each step switches the clock to its phase; all of them work on one host_link.
+ */
+typedef struct
 {
-	const size_t item_bytes = (size_t) dim * (dtype == PGV_F32 ? 4 : 2);
+	/* the build, as pgv_host_hnsw_build was asked for it */
+	pgv_hnsw   *mirror;
+	const void *rows;
+	size_t		item_bytes;
+	int64_t		n;
+	int			m,
+				ef_construction,
+				max_batch;
+	elem	   *el;
+	pgv_hnsw_built *out;
+	phase_clock *clk;
+	int			nthreads;
+	int32_t		entry;
+	int64_t		linked;
+	/* stage A: stages[cur] is the current batch's, stages[cur ^ 1] the one running ahead */
+	stage_a		stages[2];
+	int			cur;
+	int			ahead_valid;	/* stages[cur] was computed ahead for exactly this batch */
+	worker		helper,			/* stage A of the batch that runs ahead and the graph patches, in posting order */
+				scorer;			/* the pair distances of the batch's list records, slice by slice */
+	/* the records of the batch in flight (forgotten at its end, or on the way out) */
+	recpart    *parts;			/* [nthreads] step 4a's per-thread records and requests */
+	arena	   *arenas;			/* [nthreads] */
+	record	   *recs;
+	int			nrec,
+				recs_cap;
+	int32_t    *grp_elem;		/* the newcomers grouped by list (4b): list k's are [grp_off[k], grp_off[k + 1]) */
+	float	   *grp_dist;
+	int64_t    *grp_off;
+	int64_t		links_cap;
+	uint8_t    *is_dirty;		/* [n] the element's tuple is rewritten by this batch */
+	int			ndirty;
+	/* their pair distances */
+	score_job	slices[SCORE_SLICES];
+	int			nslices;
+	float	   *pdist,			/* the list records' pairs (first request) */
+			   *pdist2;			/* the member-member pairs of the lists whose cached flags did not suffice (second request) */
+	int64_t		pdist_cap,
+				pdist2_cap;
+	groupbuf	gb2;			/* the second request */
+	/* step 6 */
+	patch_job	patches[2];
+	int			pcur;
+}			host_link;
+
+static int
+host_link_init(host_link * h)
+{
+	sigset_t	old;
+	int			team = 0;
+
+	h->nthreads = omp_get_max_threads() < 16 ? omp_get_max_threads() : 16;	/* 32: twice as slow (measured) */
+	h->is_dirty = calloc((size_t) h->n, 1);
+	h->parts = calloc((size_t) h->nthreads, sizeof(recpart));
+	h->arenas = calloc((size_t) h->nthreads, sizeof(arena));
+	if (!h->is_dirty || !h->parts || !h->arenas)
+		return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
+	/* the OpenMP team is created by the first parallel region and keeps the mask of the thread that opened it: open one
+	 * now, with every signal blocked, so that the pool's threads never take the backend's signals */
+	block_signals(&old);
+#pragma omp parallel num_threads(h->nthreads) reduction(+:team)
+	team += 1;
+	pthread_sigmask(SIG_SETMASK, &old, NULL);
+	(void) team;
+	return PGV_OK;
+}
+
+/* everything the replay holds but the elements' lists; safe on a struct that is zeroed or half set up */
+static void
+host_link_release(host_link * h)
+{
+	worker_stop(&h->helper);
+	worker_stop(&h->scorer);
+	for (int i = 0; i < 2; i++)
+	{
+		free(h->patches[i].dirty);
+		free(h->patches[i].packed_off);
+		free(h->patches[i].packed);
+		stage_a_free(&h->stages[i]);
+	}
+	for (int i = 0; i < SCORE_SLICES; i++)
+		groups_free(&h->slices[i].gb);
+	for (int t = 0; t < h->nthreads && h->arenas; t++)	/* incl. a batch cut short by an error */
+		arena_free(&h->arenas[t]);
+	free(h->arenas);
+	for (int t = 0; t < h->nthreads && h->parts; t++)
+	{
+		free(h->parts[t].recs);
+		free(h->parts[t].dirty);
+		free(h->parts[t].links);
+		free(h->parts[t].tab);
+	}
+	free(h->parts);
+	free(h->recs);
+	free(h->grp_elem);
+	free(h->grp_dist);
+	free(h->grp_off);
+	free(h->is_dirty);
+	groups_free(&h->gb2);
+	pgv_pinned_free(h->pdist);
+	pgv_pinned_free(h->pdist2);
+}
+
+/* ---- 1 + 2. stage A: the batch's searches and its candidate lists' pair distances -- computed ahead by the helper
+ * while the previous batch was replayed, or here; then the NEXT batch's is started */
+static int
+host_stage_a(host_link * h, const batch_plan * p, int entry_level)
+{
+	stage_a    *a = &h->stages[h->cur];
+
+	phase(h->clk, PH_SEARCH);
+	if (h->ahead_valid && same_plan(&a->plan, p))
+		worker_wait(&h->helper, a->seq);	/* (usually long over) */
+	else
+	{
+		/* every patch handed to the helper has been issued (a batch that ran ahead for nothing cannot happen by
+		 * construction); the device orders this search behind the patch */
+		worker_drain(&h->helper);
+		a->plan = *p;
+		run_stage_a(h->mirror, a, h->el, h->m, h->ef_construction);
+	}
+	h->ahead_valid = 0;
+	if (a->rc != PGV_OK)
+		return pgv_host_fail(a->rc, "%s", a->err);
+	h->out->device_pairs += a->npairs;
+	/* the NEXT batch runs ahead when its composition is already certain: a full batch follows a full batch
+	 * (linked / 16 >= max_batch holds from here on), the entry point does not change in this one, and batches are large
+	 * enough for the overlap to matter */
+	if (h->max_batch >= 64 && p->B == h->max_batch && h->linked / 16 >= h->max_batch && p->i0 + p->B < h->n &&
+		!batch_has_tall(h->el, p, entry_level))
+	{
+		stage_a    *nx = &h->stages[h->cur ^ 1];
+		/* planned before this batch is linked, and still the plan the loop makes for it afterwards: with
+		 * linked / 16 >= max_batch, now and then, B is max_batch cut to the rows that are left and at the first tall
+		 * element, and lcap follows from B -- against an entry level that this batch, without a tall element, leaves as
+		 * it is */
+		batch_plan	q = plan_batch(h->el, h->n, p->i0 + p->B, h->linked, entry_level, h->max_batch);
+
+		if (!h->helper.started && worker_start(&h->helper, h->mirror, h->el, h->m, h->ef_construction))
+			worker_start(&h->scorer, h->mirror, h->el, h->m, h->ef_construction);
+		if (h->helper.started)
+		{
+			nx->plan = q;
+			/* posted at once: queued behind this batch's own scoring requests instead, the build was 1.7 s slower
+			 * (measured, profiles/r04/hnsw_build_pipeline.md) */
+			nx->seq = worker_post(&h->helper, JOB_STAGE_A, nx);
+			h->ahead_valid = 1;
+		}
+	}
+	return PGV_OK;
+}
+
+/* ---- 3. SelectNeighbors + AddConnections per element and layer (independent: one thread each), then
+ * FindDuplicateInMemory in heap order: a duplicate's lists are dropped again */
+static void
+store_new_lists(host_link * h, const batch_plan * p)
+{
+	const stage_a *const a = &h->stages[h->cur];
+	elem	   *const el = h->el;
+	const int	m = h->m,
+				ef_construction = h->ef_construction,
+				B = p->B,
+				lcap = p->lcap;
+	const int64_t i0 = p->i0;
+
+	phase(h->clk, PH_SELECT);
+#pragma omp parallel if (B >= 8) num_threads(h->nthreads)
+	{
+		cand	   *lw = malloc(sizeof(cand) * (size_t) ef_construction);
+		cand	  **c = malloc(sizeof(cand *) * (size_t) ef_construction * 5);
+		cand	  **r = c + ef_construction,
+				  **w = c + 2 * ef_construction,
+				  **wd = c + 3 * ef_construction,
+				  **added = c + 4 * ef_construction;
+		uint8_t    *flag = malloc((size_t) ef_construction);
+
+#pragma omp for schedule(dynamic, 4)
+		for (int b = 0; b < B; b++)
+		{
+			elem	   *x = &el[i0 + b];
+
+			x->layers = calloc((size_t) x->level + 1, sizeof(nlist));
+			for (int lc = lcap - 1; lc >= 0; lc--)
+			{
+				const size_t g = (size_t) b * lcap + lc;
+				const int	lm = layer_m(m, lc);
+				nlist	   *l = &x->layers[lc];
+
+				if (lc > x->level)
+					continue;
+				if (a->device_select)
+				{
+					/* SelectNeighbors ran on the device (pgv_hnsw_build_neighbors): the list is AddConnections' to store */
+					const int	rn = a->sel_cnt[g];
+
+					if (rn == 0)
+						continue;
+					l->closer_set = 0;	/* not sorted deterministically (:1143-1144) */
+					l->items = items_alloc(lm);
+					l->length = rn;
+					for (int i = 0; i < rn; i++)
+					{
+						cand	   *it = &l->items[i];
+
+						it->element = a->sel_ids[g * 2 * (size_t) m + i];
+						it->distance = a->sel_dist[g * 2 * (size_t) m + i];
+						it->local = 0;
+						it->closer = a->sel_closer[g * 2 * (size_t) m + i];
+					}
+				}
+				else
+				{
+					const int	nw = a->sw_cnt[g];
+					const int32_t *wi = a->sw_ids + g * ef_construction;
+					const float *wdist = a->sw_dist + g * ef_construction;
+					/* (the triangle is only there, and only looked at, when the list has to be thinned) */
+					pairsrc		ps = pairs_of(a->pdist + a->tri_off[g], 1, NULL);
+					/* not sorted deterministically: the flags of this selection are not reusable (:1143-1144) */
+					uint8_t		closer_set = 0;
+					int			rn;
+
+					if (nw == 0)
+						continue;
+					/* the reference's list `w` is furthest first; the device returns nearest first */
+					for (int i = 0; i < nw; i++)
+					{
+						lw[i].element = wi[nw - 1 - i];
+						lw[i].distance = wdist[nw - 1 - i];
+						lw[i].local = nw - 1 - i;
+						lw[i].closer = 0;
+						c[i] = &lw[i];
+					}
+					rn = select_neighbors(c, nw, lm, &ps, &closer_set, NULL, r, NULL, 0, NULL, w, wd, added, flag);
+					l->closer_set = closer_set;
+					l->items = items_alloc(lm);
+					l->length = rn;
+					for (int i = 0; i < rn; i++)
+						l->items[i] = *r[i];
+				}
+			}
+			for (int lc = 0; lc <= x->level; lc++)
+				if (!x->layers[lc].items)
+					x->layers[lc].items = items_alloc(layer_m(m, lc));
+		}
+		free(lw);
+		free(c);
+		free(flag);
+	}
+	for (int b = 0; b < B; b++)
+	{
+		int32_t		e = (int32_t) (i0 + b);
+		const nlist *l0 = &el[e].layers[0];
+
+		h->out->dup_of[e] = find_duplicate(el, h->rows, h->item_bytes, e, &l0->items[0].element, sizeof(cand), l0->length);
+		if (h->out->dup_of[e] >= 0)
+			layers_free(&el[e]);
+	}
+}
+
+/* where list (owner, lc) goes in a hash table of cap (a power of two) slots */
+static inline int64_t
+list_hash(int32_t owner, int lc, int64_t cap)
+{
+	const uint64_t key = ((uint64_t) owner << 6) | (uint64_t) lc;
+
+	return (int64_t) ((key * 0x9E3779B97F4A7C15ull) >> 40) & (cap - 1);
+}
+
+/* load factor 1/2 reached (a batch touches up to B * (2m + level * m) lists; m up to 100, src/hnsw.h:50): double the
+ * table and rehash the records made so far.  0 = out of memory */
+static int
+part_tab_grow(recpart * rp)
+{
+	const int64_t ncap = rp->tab_cap * 2;
+	int32_t    *nt = calloc((size_t) ncap, sizeof(int32_t));
+
+	if (!nt)
+		return 0;
+	for (int r = 0; r < rp->nrec; r++)
+	{
+		int64_t		h = list_hash(rp->recs[r].owner, rp->recs[r].lc, ncap);
+
+		while (nt[h] != 0)
+			h = (h + 1) & (ncap - 1);
+		nt[h] = r + 1;
+	}
+	free(rp->tab);
+	rp->tab = nt;
+	rp->tab_cap = ncap;
+	return 1;
+}
+
+/* the record of list (owner, lc) among a thread's own, a bare one made at first sight (its owner's tuple is dirty from
+ * then on): its index + 1, or 0 when out of memory */
+static inline int32_t
+part_record(recpart * rp, int32_t owner, int lc, uint8_t *is_dirty)
+{
+	int64_t		h = list_hash(owner, lc, rp->tab_cap);
+	record	   *recs;
+
+	while (rp->tab[h] != 0 && !(rp->recs[rp->tab[h] - 1].owner == owner && rp->recs[rp->tab[h] - 1].lc == lc))
+		h = (h + 1) & (rp->tab_cap - 1);
+	if (rp->tab[h] != 0)
+		return rp->tab[h];
+	if (!(recs = room_for_one(rp->recs, rp->nrec, &rp->cap, sizeof(record), 1024)))
+		return 0;
+	rp->recs = recs;
+	recs[rp->nrec].owner = owner;
+	recs[rp->nrec].lc = lc;
+	recs[rp->nrec].newcap = 0;	/* newcomers, counted by the caller */
+	rp->tab[h] = ++rp->nrec;
+	if ((int64_t) rp->nrec * 2 > rp->tab_cap && !part_tab_grow(rp))
+		return 0;
+	if (!is_dirty[owner])		/* (owners are dealt to threads: no two write one flag) */
+	{
+		int32_t    *dirty = room_for_one(rp->dirty, rp->ndirty, &rp->dirty_cap, sizeof(int32_t), 1024);
+
+		if (!dirty)
+			return 0;
+		rp->dirty = dirty;
+		is_dirty[owner] = 1;
+		rp->dirty[rp->ndirty++] = owner;
+	}
+	return rp->nrec;
+}
+
+/*
+ * ---- 4. the lists this batch links into, and every distance their re-selections can look up.
+ * 4a: one request per (batch element, chosen neighbor, layer) in the order the reference's loop would link them, and a
+ * bare record per distinct list.  The lists are dealt to the threads by owner: every thread walks all requests (they
+ * are the batch's fresh lists, a few hundred KB) and keeps its own, in its own small hash table -- the order inside a
+ * list is the walk's, whatever the number of threads.
+ * 4b: the requests grouped by list, link order kept inside a list (counting sort, thread by thread).
+ */
+static int
+make_records(host_link * h, const batch_plan * p)
+{
+	elem	   *const el = h->el;
+	recpart    *const parts = h->parts;
+	uint8_t    *const is_dirty = h->is_dirty;
+	const int	B = p->B;
+	const int64_t i0 = p->i0;
+	int			oom = 0;
+
+	phase(h->clk, PH_RECORDS);
+	h->ndirty = 0;
+	for (int b = 0; b < B; b++)
+	{
+		int32_t		e = (int32_t) (i0 + b);
+
+		if (!el[e].layers)
+			continue;
+		h->linked++;
+		if (!is_dirty[e])
+		{
+			is_dirty[e] = 1;
+			h->ndirty++;
+		}
+		/* the entry point moves up with the tallest element (src/hnswbuild.c:425-430) */
+		if (el[e].level > el[h->entry].level)
+			h->entry = e;
+	}
+	for (int t = 0; t < h->nthreads; t++)	/* (a short batch runs the walk on one thread: the others' stay empty) */
+		parts[t].ndirty = 0;
+#pragma omp parallel if (B >= 8) num_threads(h->nthreads)
+	{
+		const int	T = omp_get_num_threads(),
+					me = omp_get_thread_num();
+		recpart    *rp = &parts[me];
+
+		rp->nrec = 0;
+		rp->nlinks = 0;
+		if (rp->tab_cap == 0)
+		{
+			rp->tab_cap = 1 << 10;
+			rp->tab = malloc(sizeof(int32_t) * (size_t) rp->tab_cap);
+		}
+		if (!rp->tab)
+			rp->oom = 1;
+		else
+			memset(rp->tab, 0, sizeof(int32_t) * (size_t) rp->tab_cap);
+		for (int b = 0; b < B && !rp->oom; b++)
+		{
+			int32_t		e = (int32_t) (i0 + b);
+			elem	   *x = &el[e];
+
+			if (!x->layers)
+				continue;
+			for (int lc = x->level; lc >= 0 && !rp->oom; lc--)
+				for (int i = 0; i < x->layers[lc].length; i++)
+				{
+					int32_t		owner = x->layers[lc].items[i].element;
+					int32_t		ri;		/* record index + 1 */
+					link_req   *links;
+
+					if ((int) (((uint64_t) ((uint32_t) owner * 2654435761u) * (uint64_t) T) >> 32) != me)
+						continue;
+					ri = part_record(rp, owner, lc, is_dirty);
+					links = room_for_one(rp->links, rp->nlinks, &rp->links_cap, sizeof(link_req), 4096);
+					if (links)
+						rp->links = links;
+					if (ri == 0 || !links)
+					{
+						rp->oom = 1;
+						break;
+					}
+					links[rp->nlinks].rec = ri - 1;
+					links[rp->nlinks].element = e;
+					links[rp->nlinks].distance = x->layers[lc].items[i].distance;
+					rp->nlinks++;
+					rp->recs[ri - 1].newcap++;
+				}
+		}
+#pragma omp barrier
+#pragma omp single
+		{
+			/* where each thread's records and requests go in the batch's arrays */
+			int64_t		nr = 0,
+						nl = 0;
+
+			for (int t = 0; t < T; t++)
+			{
+				parts[t].rec_base = nr;
+				parts[t].link_base = nl;
+				nr += parts[t].nrec;
+				nl += parts[t].nlinks;
+				h->ndirty += parts[t].ndirty;
+				oom |= parts[t].oom;
+			}
+			if (nr + 1 > h->recs_cap)
+			{
+				h->recs_cap = (int) (nr + 1) * 2;
+				h->recs = realloc(h->recs, sizeof(record) * (size_t) h->recs_cap);
+				h->grp_off = realloc(h->grp_off, sizeof(int64_t) * (size_t) (h->recs_cap + 1));
+			}
+			if (nl + 1 > h->links_cap)
+			{
+				h->links_cap = (nl + 1) * 2;
+				h->grp_elem = realloc(h->grp_elem, sizeof(int32_t) * (size_t) h->links_cap);
+				h->grp_dist = realloc(h->grp_dist, sizeof(float) * (size_t) h->links_cap);
+			}
+			if (!h->recs || !h->grp_off || !h->grp_elem || !h->grp_dist)
+				oom = 1;
+			else
+				h->grp_off[nr] = nl;
+			h->nrec = (int) nr;
+		}
+		if (!oom)
+		{
+			int64_t    *const grp_off = h->grp_off;
+			int64_t		at = rp->link_base;
+
+			for (int k = 0; k < rp->nrec; k++)
+			{
+				grp_off[rp->rec_base + k] = at;
+				at += rp->recs[k].newcap;
+				rp->recs[k].nlocal = 0;		/* fill cursor */
+			}
+			for (int64_t t = 0; t < rp->nlinks; t++)
+			{
+				record	   *rcd = &rp->recs[rp->links[t].rec];
+				int64_t		to = grp_off[rp->rec_base + rp->links[t].rec] + rcd->nlocal++;
+
+				h->grp_elem[to] = rp->links[t].element;
+				h->grp_dist[to] = rp->links[t].distance;
+			}
+			if (rp->nrec > 0)
+				memcpy(h->recs + rp->rec_base, rp->recs, sizeof(record) * (size_t) rp->nrec);
+		}
+	}
+	return oom ? pgv_host_fail(PGV_ERR_NOMEM, "out of memory for the batch's list records") : PGV_OK;
+}
+
+/* 4c (parallel: this is where the owners' lists, cold in the cache, are read): members + newcomers */
+static int
+fill_records(host_link * h, const batch_plan * p)
+{
+	elem	   *const el = h->el;
+	record	   *const recs = h->recs;
+	const int64_t *const grp_off = h->grp_off;
+	const int	nrec = h->nrec;
+	int			oom = 0;
+
+#pragma omp parallel for if (p->B >= 8) num_threads(h->nthreads) schedule(static)
+	for (int k = 0; k < nrec; k++)
+	{
+		record	   *rcd = &recs[k];
+		nlist	   *l = &el[rcd->owner].layers[rcd->lc];
+		int			nnew = rcd->newcap;
+
+		/* element -> its layers -> the list's items: three dependent misses per record, fetched ahead (a neighbouring
+		 * thread's records at the chunk's end: harmless) */
+		if (k + 12 < nrec)
+			__builtin_prefetch(&el[recs[k + 12].owner]);
+		if (k + 8 < nrec)
+			__builtin_prefetch(&el[recs[k + 8].owner].layers[recs[k + 8].lc]);
+		if (k + 4 < nrec)
+		{
+			const char *it = (const char *) el[recs[k + 4].owner].layers[recs[k + 4].lc].items;
+
+			__builtin_prefetch(it);
+			__builtin_prefetch(it + 64);
+			__builtin_prefetch(it + 128);
+			__builtin_prefetch(it + 192);
+		}
+
+		rcd->nstart = l->length;
+		rcd->nlocal = l->length + nnew;
+		rcd->ids = arena_alloc(&h->arenas[omp_get_thread_num()], sizeof(int32_t) * (size_t) rcd->nlocal);
+		if (!rcd->ids)
+		{
+#pragma omp atomic write
+			oom = 1;
+			rcd->nlocal = rcd->nstart = 0;
+			continue;
+		}
+		rcd->newdist = h->grp_dist + grp_off[k];
+		rcd->items = l->items;
+		rcd->full = !l->closer_set;	/* no cached flags: its next selection computes everything */
+		rcd->blocked = 0;
+		rcd->wait_from = -1;
+		for (int j = 0; j < l->length; j++)
+		{
+			rcd->ids[j] = l->items[j].element;
+			l->items[j].local = j;
+		}
+		memcpy(rcd->ids + l->length, h->grp_elem + grp_off[k], sizeof(int32_t) * (size_t) nnew);
+	}
+	return oom ? pgv_host_fail(PGV_ERR_NOMEM, "out of memory for the batch's list records") : PGV_OK;
+}
+
+/* the records' pair distances, requested in slices: with the scorer running, slice s + 1's pairs are scored while slice s
+ * is replayed; without, the one slice is fetched here */
+static int
+request_pairs(host_link * h)
+{
+	record	   *const recs = h->recs;
+	const int	nrec = h->nrec,
+				m = h->m;
+	const int	nslices = h->scorer.started && nrec >= 64 * SCORE_SLICES ? SCORE_SLICES : 1;
+	int64_t		npairs = 0;
+	int			rc;
+
+	phase(h->clk, PH_PAIRLIST);
+	h->nslices = nslices;
+	/* (one thread per slice; pair offsets are the slice's own: its reply starts at slices[.].out) */
+#pragma omp parallel for if (nslices > 1) num_threads(nslices) schedule(static, 1)
+	for (int sl = 0; sl < nslices; sl++)
+	{
+		score_job  *sj = &h->slices[sl];
+		int64_t		mine = 0;
+
+		/* a short first slice (it is the one waited for with nothing to do), the rest in equal parts */
+		sj->klo = sl == 0 ? 0 : (int) (((int64_t) nrec * (1 + (sl - 1) * 7 / (nslices - 1))) / 8);
+		sj->khi = sl == nslices - 1 ? nrec : (int) (((int64_t) nrec * (1 + sl * 7 / (nslices - 1))) / 8);
+		sj->rc = PGV_OK;
+		sj->seq = 0;
+		groups_reset(&sj->gb);
+		for (int k = sj->klo; k < sj->khi; k++)
+		{
+			record	   *rcd = &recs[k];
+			int			from = rcd->full ? 1 : rcd->nstart;	/* cached flags: only the pairs that involve a newcomer */
+
+			rcd->pair0 = mine;
+			rcd->slice = sl;
+			rcd->from = from < 1 ? 1 : from;
+			/* a list that cannot overflow in this batch never runs a selection */
+			if (rcd->nlocal <= layer_m(m, rcd->lc))
+				continue;
+			if (!groups_add(&sj->gb, rcd->ids, rcd->nlocal, from, mine))
+			{
+				sj->rc = PGV_ERR_NOMEM;
+				break;
+			}
+			mine += group_pairs(rcd->nlocal, from);
+		}
+		sj->npairs = mine;
+		groups_end(&sj->gb, mine);
+	}
+	for (int sl = 0; sl < nslices; sl++)
+	{
+		if (h->slices[sl].rc != PGV_OK)
+			return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
+		npairs += h->slices[sl].npairs;
+	}
+	phase(h->clk, PH_PAIRS);
+	if ((rc = pinned_room(&h->pdist, &h->pdist_cap, npairs)) != PGV_OK)
+		return pgv_host_fail(rc, "%s", pgv_last_error());
+	for (int64_t sl = 0, base = 0; sl < nslices; sl++)
+	{
+		score_job  *sj = &h->slices[sl];
+
+		sj->out = h->pdist + base;
+		base += sj->npairs;
+		if (sj->npairs == 0)
+			continue;
+		if (nslices > 1)
+			sj->seq = worker_post(&h->scorer, JOB_SCORE, sj);
+		else if ((rc = score_groups(h->mirror, &sj->gb, sj->npairs, sj->out)) != PGV_OK)
+			return pgv_host_fail(rc, "%s", pgv_last_error());
+	}
+	h->out->device_pairs += npairs;
+	return PGV_OK;
+}
+
+/*
+ * HnswUpdateConnection (src/hnswutils.c:1183-1231) for the records [klo, khi), each list with its newcomers in heap
+ * order.  pass 0: every list, from its first newcomer; an update that needs member-member distances that were not
+ * fetched blocks its list.  pass 1: the blocked lists, from the update that waited.  Returns the lists newly blocked.
+ */
+static int
+replay_range(host_link * h, int B, int klo, int khi, int pass)
+{
+	elem	   *const el = h->el;
+	record	   *const recs = h->recs;
+	const score_job *const slices = h->slices;
+	const float *const pdist2 = h->pdist2;
+	const int64_t *const nbr_start = h->out->nbr_start;
+	int32_t    *const nbr = h->out->nbr;
+	const int	m = h->m;
+	int			nblocked = 0;
+
+#pragma omp parallel if (B >= 8) num_threads(h->nthreads)
+	{
+		int			lm0 = layer_m(m, 0);
+		cand	  **c = malloc(sizeof(cand *) * (size_t) (lm0 + 1) * 5);
+		cand	  **r = c + (lm0 + 1),
+				  **w = c + 2 * (lm0 + 1),
+				  **wd = c + 3 * (lm0 + 1),
+				  **added = c + 4 * (lm0 + 1);
+		uint8_t    *flag = malloc((size_t) lm0 + 1);
+
+#pragma omp for schedule(dynamic, 16) reduction(+:nblocked)
+		for (int k = klo; k < khi; k++)
+		{
+			record	   *rcd = &recs[k];
+			nlist	   *l = &el[rcd->owner].layers[rcd->lc];
+			int			lm = layer_m(m, rcd->lc);
+			int			from = rcd->nstart;
+			pairsrc		ps;
+
+			if (pass == 1)
+			{
+				if (!rcd->blocked)
+					continue;
+				from = rcd->wait_from;
+			}
+			else if (k + 4 < khi)
+			{
+				/* a later record's list (last touched by another thread in step 4) and its pairs (fresh from the
+				 * device: in no cache) */
+				const record *nx = &recs[k + 4];
+				const char *it = nx->items,
+						   *tr = (const char *) (slices[nx->slice].out + nx->pair0);
+				const int	nlm = layer_m(m, nx->lc);
+
+				for (int o = 0; o < nlm * (int) sizeof(cand); o += 64)
+					__builtin_prefetch(it + o);
+				__builtin_prefetch(tr);
+				__builtin_prefetch(tr + 64);
+				/* the cached sort order behind the items, and where the list's tuple part goes */
+				__builtin_prefetch(it + nlm * (int) sizeof(cand));
+				__builtin_prefetch(nbr + nbr_start[nx->owner] + (int64_t) (el[nx->owner].level - nx->lc) * m, 1);
+				__builtin_prefetch(nx->newdist);
+			}
+			ps = pairs_of(slices[rcd->slice].out + rcd->pair0, rcd->from, pass ? pdist2 + rcd->pair0b : NULL);
+			for (int u = from; u < rcd->nlocal; u++)
+			{
+				cand		new_hc;
+				cand	   *pruned = NULL;
+				int			nc,
+							rn;
+
+				new_hc.element = rcd->ids[u];
+				new_hc.distance = rcd->newdist[u - rcd->nstart];
+				new_hc.local = u;
+				new_hc.closer = 0;
+				if (l->length < lm)
+				{
+					l->items[l->length++] = new_hc;
+					l->ord_valid = 0;
+					continue;
+				}
+				nc = l->length + 1;
+				for (int j = 0; j < l->length; j++)
+					c[j] = &l->items[j];
+				c[nc - 1] = &new_hc;
+				rn = select_neighbors(c, nc, lm, &ps, &l->closer_set, &new_hc, r, &pruned, 1,
+									  l->ord_valid ? items_ord(l, lm) : NULL, w, wd, added, flag);
+				if (rn < 0)
+				{
+					/* needs member-member distances that were not fetched: this and every later update of the list wait
+					 * for the second launch */
+					rcd->blocked = 1;
+					rcd->wait_from = u;
+					nblocked++;
+					break;
+				}
+				{
+					/* the list keeps its members' places, the newcomer takes the dropped one's
+					 * (src/hnswutils.c:1211-1227); the sorted order w, less the dropped candidate, is kept for the list's
+					 * next selection */
+					uint8_t    *ord = items_ord(l, lm);
+					int			slot = -1,
+								o = 0;
+
+					if (pruned != NULL && pruned != &new_hc)
+						slot = (int) (pruned - l->items);
+					for (int i = 0; i < nc; i++)
+						if (w[i] != pruned)
+							ord[o++] = (uint8_t) (w[i] == &new_hc ? slot : (int) (w[i] - l->items));
+					l->ord_valid = 1;
+					if (slot >= 0)
+						l->items[slot] = new_hc;
+				}
+			}
+			/* the list's part of its owner's neighbor tuple, for step 6 */
+			write_segment(&el[rcd->owner], rcd->owner, rcd->lc, m, nbr_start, nbr);
+		}
+		free(c);
+		free(flag);
+	}
+	return nblocked;
+}
+
+/* ---- 5. HnswUpdateNeighborsInMemory (src/hnswbuild.c:376-405).  The reference links one element after the other;
+ * updates of different lists do not see each other, so the lists are replayed in parallel, slice by slice as the
+ * slices' distances arrive */
+static int
+replay_lists(host_link * h, const batch_plan * p)
+{
+	record	   *const recs = h->recs;
+	int			nblocked = 0;
+	int64_t		npairs = 0;
+	int			rc;
+
+	phase(h->clk, PH_UPDATE);
+	for (int sl = 0; sl < h->nslices; sl++)
+	{
+		score_job  *sj = &h->slices[sl];
+
+		if (sj->seq != 0)
+		{
+			phase(h->clk, PH_PAIRS);
+			worker_wait(&h->scorer, sj->seq);
+			phase(h->clk, PH_UPDATE);
+			if (sj->rc != PGV_OK)
+				return pgv_host_fail(sj->rc, "%s", sj->err);
+		}
+		nblocked += replay_range(h, p->B, sj->klo, sj->khi, 0);
+	}
+	if (nblocked == 0)
+		return PGV_OK;
+	/* ---- 5b. the updates that were put aside: their lists' member-member pairs, then the replay (the first request's
+	 * reply stays: the newcomers' pairs are looked up there) */
+	groups_reset(&h->gb2);
+	for (int k = 0; k < h->nrec; k++)
+		if (recs[k].blocked)
+		{
+			recs[k].pair0b = npairs;
+			if (!groups_add(&h->gb2, recs[k].ids, recs[k].nstart, 1, npairs))
+				return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
+			npairs += group_pairs(recs[k].nstart, 1);
+		}
+	groups_end(&h->gb2, npairs);
+	if ((rc = pinned_room(&h->pdist2, &h->pdist2_cap, npairs)) != PGV_OK ||
+		(rc = score_groups(h->mirror, &h->gb2, npairs, h->pdist2)) != PGV_OK)
+		return pgv_host_fail(rc, "%s", pgv_last_error());
+	h->out->device_pairs += npairs;
+	h->out->deferred_updates += nblocked;
+	replay_range(h, p->B, 0, h->nrec, 1);
+	return PGV_OK;
+}
+
+/* ---- 6. the graph the next batch searches.  With the helper running, the patch is its job: posted behind the stage A
+ * that runs ahead (whose kernels read the tuples this step overwrites) and in front of the next one; the arrays of the
+ * job before last are free again by now. */
+static int
+patch_graph(host_link * h, const batch_plan * p)
+{
+	patch_job  *pj = &h->patches[h->pcur];
+	pgv_hnsw_built *const out = h->out;
+	uint8_t    *const is_dirty = h->is_dirty;
+	const int64_t i0 = p->i0;
+	int			ndirty = 0;
+	int64_t		ntuple = 0;
+	int			rc;
+
+	phase(h->clk, PH_PATCH);
+	worker_wait(&h->helper, pj->seq);
+	if (pj->rc != PGV_OK)
+		return pgv_host_fail(pj->rc, "%s", pj->err);
+	if (h->ndirty + 1 > pj->dirty_cap)
+	{
+		pj->dirty_cap = (int64_t) (h->ndirty + 1) * 2;
+		pj->dirty = realloc(pj->dirty, sizeof(int32_t) * (size_t) pj->dirty_cap);
+		pj->packed_off = realloc(pj->packed_off, sizeof(int64_t) * (size_t) pj->dirty_cap);
+	}
+	if (!pj->dirty || !pj->packed_off)
+		return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
+	/* dirty elements: the batch itself and the owners of the touched lists */
+	for (int b = 0; b < p->B; b++)
+		if (is_dirty[i0 + b])
+		{
+			pj->dirty[ndirty++] = (int32_t) (i0 + b);
+			is_dirty[i0 + b] = 0;
+		}
+	for (int t = 0; t < h->nthreads; t++)	/* the owners, as step 4a's threads met them */
+		for (int q = 0; q < h->parts[t].ndirty; q++)
+		{
+			pj->dirty[ndirty++] = h->parts[t].dirty[q];
+			is_dirty[h->parts[t].dirty[q]] = 0;
+		}
+	for (int q = 0; q < ndirty; q++)
+	{
+		pj->packed_off[q] = ntuple;
+		ntuple += out->nbr_start[pj->dirty[q] + 1] - out->nbr_start[pj->dirty[q]];
+	}
+	pj->packed_off[ndirty] = ntuple;
+	if (ntuple + 1 > pj->packed_cap)
+	{
+		pj->packed_cap = (ntuple + 1) * 2;
+		free(pj->packed);
+		pj->packed = malloc(sizeof(int32_t) * (size_t) pj->packed_cap);
+		if (!pj->packed)
+			return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
+	}
+#pragma omp parallel for if (p->B >= 8) num_threads(h->nthreads) schedule(static)
+	for (int q = 0; q < ndirty; q++)
+	{
+		/* (the lists touched by the replay wrote their parts in step 5; the batch's own elements are new) */
+		if (pj->dirty[q] >= i0)
+			write_tuple(h->el, pj->dirty[q], h->m, out->nbr_start, out->nbr);
+		memcpy(pj->packed + pj->packed_off[q], out->nbr + out->nbr_start[pj->dirty[q]],
+			   sizeof(int32_t) * (size_t) (pj->packed_off[q + 1] - pj->packed_off[q]));
+	}
+	pj->entry = h->entry;
+	pj->ndirty = ndirty;
+	if (h->helper.started)
+	{
+		pj->seq = worker_post(&h->helper, JOB_PATCH, pj);
+		h->pcur ^= 1;
+	}
+	else if ((rc = pgv_hnsw_update_graph(h->mirror, h->entry, pj->dirty, ndirty, pj->packed_off, pj->packed)) != PGV_OK)
+		return pgv_host_fail(rc, "%s", pgv_last_error());
+	return PGV_OK;
+}
+
+static int
+build_linked_on_host(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, int m, int ef_construction,
+					 int max_batch, int device_select, elem * el, pgv_hnsw_built * out, phase_clock * clk,
+					 int32_t *entry_io, int64_t *linked_io)
+{
+	host_link	h = {.mirror = mirror, .rows = rows, .item_bytes = item_bytes, .n = n, .m = m, .ef_construction = ef_construction,
+		.max_batch = max_batch, .el = el, .out = out, .clk = clk, .entry = -1, .nslices = 1};
+	int			rc;
+
+	h.stages[0].device_select = h.stages[1].device_select = device_select;
+	rc = host_link_init(&h);
+	for (int64_t i0 = 0; rc == PGV_OK && i0 < n;)
+	{
+		batch_plan	p;
+		int			entry_level;
+
+		if ((rc = poll_cancel(i0, n)) != PGV_OK)
+			break;
+		if (h.entry < 0)
+		{
+			h.entry = (int32_t) i0;
+			h.linked = 1;
+			if ((rc = link_first_element(mirror, el, h.entry, m, 1)) != PGV_OK)
+			{
+				rc = pgv_host_fail(rc, "%s", pgv_last_error());
+				break;
+			}
+			i0++;
+			out->batches++;
+			continue;
+		}
+		entry_level = el[h.entry].level;
+		p = plan_batch(el, n, i0, h.linked, entry_level, max_batch);
+		/* (each step switches the clock to its own phase) */
+		if ((rc = host_stage_a(&h, &p, entry_level)) != PGV_OK)
+			break;
+		store_new_lists(&h, &p);
+		if ((rc = make_records(&h, &p)) != PGV_OK || (rc = fill_records(&h, &p)) != PGV_OK ||
+			(rc = request_pairs(&h)) != PGV_OK || (rc = replay_lists(&h, &p)) != PGV_OK || (rc = patch_graph(&h, &p)) != PGV_OK)
+			break;
+		phase(clk, PH_FREE);
+		/* forget the batch's records */
+		for (int t = 0; t < h.nthreads; t++)
+			arena_reset(&h.arenas[t]);
+		h.nrec = 0;
+		phase(clk, PH_RECORDS);
+		i0 += p.B;
+		out->batches++;
+		if (h.ahead_valid)
+			h.cur ^= 1;
+	}
+	if (rc == PGV_OK)
+	{
+		/* the last patches are on the device before the caller searches the mirror */
+		worker_drain(&h.helper);
+		for (int i = 0; i < 2 && rc == PGV_OK; i++)
+			if (h.patches[i].rc != PGV_OK)
+				rc = pgv_host_fail(h.patches[i].rc, "%s", h.patches[i].err);
+	}
+	host_link_release(&h);
+	*entry_io = h.entry;
+	*linked_io = h.linked;
+	return rc;
+}
+
+/*
+ * The empty graph of n elements: a level for each (HnswInitElement, src/hnswutils.c:243-270: one draw per heap tuple, in
+ * heap order), out's arrays and the elements, every neighbor slot -1, and the whole handed to the mirror for the first
+ * batch to search.  On failure what was allocated stays with out and *el_out for the caller to free.
+ */
+static int
+start_graph(pgv_hnsw * mirror, int64_t n, int m, const pgv_rng * rng, pgv_hnsw_built * out, elem * *el_out)
+{
 	/* HnswGetMaxLevel, src/hnsw.h:133 with BLCKSZ 8192 */
 	const int	by_page = (int) ((8192 - 24 - 8 - 4 - 4) / 6 / m) - 2;
 	const int	max_level = by_page < 63 ? by_page : 63;
 	const double ml = 1.0 / log((double) m);	/* HnswGetMl */
 	rng_state	rs;
-	elem	   *el = NULL;
-	int32_t		entry = -1;
-	int64_t		linked = 0;
-	int			rc = PGV_OK;
-	groupbuf	gb = {0};
-	int64_t		npairs = 0;
-	float	   *pdist = NULL,	/* the list records' pairs (first request) */
-			   *pdist2 = NULL;	/* the member-member pairs of the lists whose cached flags did not suffice (second request) */
-	int64_t		pdist_cap = 0,
-				pdist2_cap = 0;
-	int32_t    *sw_ids = NULL,	/* (aliases of the current batch's stage A) */
-			   *sw_cnt = NULL;
-	float	   *sw_dist = NULL;
-	const float *cdist = NULL;	/* the candidate lists' pair distances of the current batch (stage A's) */
-	stage_a		stages[2];
-	int			cur = 0;		/* stages[cur]: the current batch's; stages[cur ^ 1]: the one running ahead */
-	int			ahead_valid = 0;	/* stages[cur] was computed ahead for exactly this batch */
-	worker		helper,			/* stage A of the batch that runs ahead and the graph patches, in posting order */
-				scorer;			/* the pair distances of the batch's list records, slice by slice */
-	patch_job	patches[2];
-	int			pcur = 0;
-	score_job	slices[SCORE_SLICES];
-	int			nslices = 1;
-	uint8_t    *is_dirty = NULL;
-	record	   *recs = NULL;
-	int			recs_cap = 0;
-	recpart    *parts = NULL;	/* [nthreads] step 4a's per-thread records and requests */
-	int64_t		links_cap = 0;
-	int32_t    *grp_elem = NULL;
-	float	   *grp_dist = NULL;
-	int64_t    *grp_off = NULL;
-	arena	   *arenas = NULL;	/* [nthreads] */
-	int			oom = 0;
-	int64_t    *tri_off = NULL;
-	int			nrec = 0;		/* records of the batch in flight (freed at its end, or on the way out) */
-	int			nthreads = omp_get_max_threads() < 16 ? omp_get_max_threads() : 16;	/* 32: twice as slow (measured) */
-	double		phase_t0 = now_secs();
-	int			cur_phase = PH_RECORDS;
-	/* SelectNeighbors of the new elements' candidate lists: on the device with the searches (the default), or here from
-	 * the lists and their pair triangles (PGV_HNSW_HOST_SELECT=1: the form the device's is tested against) */
-	const int	device_select = !(getenv("PGV_HNSW_HOST_SELECT") && atoi(getenv("PGV_HNSW_HOST_SELECT")) != 0);
-	/* the graph updates (HnswUpdateConnection for every list a batch links into): on the device (the default;
-	 * build_linked_on_device), or replayed here on OpenMP threads (PGV_HNSW_HOST_LINK=1, and whenever the new elements'
-	 * selection is the host's) -- the two build the same graph */
-	const int	device_link = device_select && !(getenv("PGV_HNSW_HOST_LINK") && atoi(getenv("PGV_HNSW_HOST_LINK")) != 0);
+	elem	   *el;
+	int			rc;
 
-	memset(stages, 0, sizeof(stages));
-	stages[0].device_select = stages[1].device_select = device_select;
-	memset(&helper, 0, sizeof(helper));
-	memset(&scorer, 0, sizeof(scorer));
-	memset(patches, 0, sizeof(patches));
-	memset(slices, 0, sizeof(slices));
-	if (!mirror || !out || (n > 0 && !rows))
-		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build: mirror/rows/out is NULL");
-	if (m < 2 || m > 100 || ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)
-		return pgv_host_fail(PGV_ERR_ARG, "m must be 2..100, ef_construction 4..1000 and >= 2 * m (src/hnsw.c:114-125)");
-	if (n >= INT32_MAX)
-		return pgv_host_fail(PGV_ERR_ARG, "too many elements");
-	if (max_batch < 1)
-		max_batch = 1;
-	/* a list can receive every element of a batch as a newcomer (degenerate data: thousands of identical rows): the link
-	 * replay's record locals are int16 and its pair triangle is indexed in int (csrc/hnsw_link_core.h) -- a batch never
-	 * brings more than 16384 newcomers to one list */
-	if (max_batch > 16384)
-		max_batch = 16384;
-	if (max_batch > 2048)
-		max_batch = 2048;
 	memset(out, 0, sizeof(*out));
 	out->n = n;
 	out->m = m;
@@ -1477,14 +2406,9 @@ pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *row
 	out->levels = malloc(sizeof(int32_t) * (size_t) (n > 0 ? n : 1));
 	out->nbr_start = malloc(sizeof(int64_t) * (size_t) (n + 1));
 	out->dup_of = malloc(sizeof(int32_t) * (size_t) (n > 0 ? n : 1));
-	el = calloc((size_t) (n > 0 ? n : 1), sizeof(elem));
+	*el_out = el = calloc((size_t) (n > 0 ? n : 1), sizeof(elem));
 	if (!out->levels || !out->nbr_start || !out->dup_of || !el)
-	{
-		rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
-		goto done;
-	}
-
-	/* HnswInitElement, src/hnswutils.c:243-270: one draw per heap tuple, in heap order */
+		return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
 	rng_init(&rs, rng);
 	out->nbr_start[0] = 0;
 	for (int64_t i = 0; i < n; i++)
@@ -1501,997 +2425,72 @@ pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *row
 	}
 	out->nbr = malloc(sizeof(int32_t) * (size_t) (out->nbr_start[n] > 0 ? out->nbr_start[n] : 1));
 	if (!out->nbr)
-	{
-		rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
-		goto done;
-	}
+		return pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
 	for (int64_t j = 0; j < out->nbr_start[n]; j++)
 		out->nbr[j] = -1;
-	if (n == 0)
-		goto done;
-	rc = pgv_hnsw_set_graph(mirror, m, -1, out->levels, out->nbr_start, out->nbr);
-	if (rc != PGV_OK)
-	{
-		rc = pgv_host_fail(rc, "%s", pgv_last_error());
-		goto done;
-	}
-	if (device_link)
+	if (n > 0 && (rc = pgv_hnsw_set_graph(mirror, m, -1, out->levels, out->nbr_start, out->nbr)) != PGV_OK)
+		return pgv_host_fail(rc, "%s", pgv_last_error());
+	return PGV_OK;
+}
+
+int
+pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *rows, int64_t n, int m,
+					int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
+{
+	const size_t item_bytes = (size_t) dim * (dtype == PGV_F32 ? 4 : 2);
+	/* SelectNeighbors of the new elements' candidate lists: on the device with the searches (the default), or here from
+	 * the lists and their pair triangles (PGV_HNSW_HOST_SELECT=1: the form the device's is tested against) */
+	const int	device_select = !(getenv("PGV_HNSW_HOST_SELECT") && atoi(getenv("PGV_HNSW_HOST_SELECT")) != 0);
+	/* the graph updates (HnswUpdateConnection for every list a batch links into): on the device (the default;
+	 * build_linked_on_device), or replayed here on OpenMP threads (PGV_HNSW_HOST_LINK=1, and whenever the new elements'
+	 * selection is the host's; build_linked_on_host) -- the two build the same graph */
+	int			device_link = device_select && !(getenv("PGV_HNSW_HOST_LINK") && atoi(getenv("PGV_HNSW_HOST_LINK")) != 0);
+	phase_clock clk;
+	elem	   *el = NULL;
+	int32_t		entry = -1;
+	int64_t		linked = 0;
+	int			rc;
+
+	if (!mirror || !out || (n > 0 && !rows))
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build: mirror/rows/out is NULL");
+	if (m < 2 || m > 100 || ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)
+		return pgv_host_fail(PGV_ERR_ARG, "m must be 2..100, ef_construction 4..1000 and >= 2 * m (src/hnsw.c:114-125)");
+	if (n >= INT32_MAX)
+		return pgv_host_fail(PGV_ERR_ARG, "too many elements");
+	if (max_batch < 1)
+		max_batch = 1;
+	/* a list can receive every element of a batch as a newcomer (degenerate data: thousands of identical rows): the link
+	 * replay's record locals are int16 and its pair triangle is indexed in int (csrc/hnsw_link_core.h) -- a batch must
+	 * never bring more than 16384 newcomers to one list, and with this cap it never can */
+	if (max_batch > 2048)
+		max_batch = 2048;
+	clk = (phase_clock) {out->phase_secs, now_secs(), PH_RECORDS};
+	rc = start_graph(mirror, n, m, rng, out, &el);
+	if (rc == PGV_OK && n > 0 && device_link)
 	{
 		/* the graph state beside the tuples (5 bytes a slot + a counter pair a list): when the device has no room for it
 		 * the lists are replayed on the host instead -- distances still the GPU's, the same graph */
 		rc = pgv_hnsw_link_begin(mirror);
-		if (rc == PGV_OK)
+		if (rc == PGV_ERR_NOMEM)
 		{
-			PHASE(PH_RECORDS);
-			rc = build_linked_on_device(mirror, item_bytes, rows, n, m, ef_construction, max_batch, el, out, &entry, &linked);
-			goto done;
+			device_link = 0;
+			rc = PGV_OK;
 		}
-		if (rc != PGV_ERR_NOMEM)
-			goto dev_fail;
-		rc = PGV_OK;
+		else if (rc != PGV_OK)
+			rc = pgv_host_fail(rc, "%s", pgv_last_error());
 	}
-	is_dirty = calloc((size_t) n, 1);
-	parts = calloc((size_t) nthreads, sizeof(recpart));
-	arenas = calloc((size_t) nthreads, sizeof(arena));
-	{
-		/* the OpenMP team is created by the first parallel region and keeps the mask of the thread that opened it:
-		 * open one now, with every signal blocked, so that the pool's threads never take the backend's signals */
-		sigset_t	old;
-		int			team = 0;
-
-		block_signals(&old);
-#pragma omp parallel num_threads(nthreads) reduction(+:team)
-		team += 1;
-		pthread_sigmask(SIG_SETMASK, &old, NULL);
-		(void) team;
-	}
-
-	for (int64_t i0 = 0; i0 < n;)
-	{
-		int			B;
-		int			lcap = 1;
-		int			entry_level;
-		int			ndirty = 0;
-		int64_t		ntuple = 0;
-
-		/* CREATE INDEX can be cancelled between batches (a batch is milliseconds) */
-		if (cancel_check != NULL && cancel_check(cancel_arg))
-		{
-			rc = pgv_host_fail(PGV_ERR_STATE, "pgv_host_hnsw_build: cancelled after %lld of %lld rows", (long long) i0, (long long) n);
-			goto done;
-		}
-		if (entry < 0)
-		{
-			/* the first element has nothing to search: it becomes the entry point */
-			el[i0].layers = calloc((size_t) el[i0].level + 1, sizeof(nlist));
-			for (int lc = 0; lc <= el[i0].level; lc++)
-				el[i0].layers[lc].items = items_alloc(layer_m(m, lc));
-			entry = (int32_t) i0;
-			linked = 1;
-			rc = pgv_hnsw_update_graph(mirror, entry, NULL, 0, NULL, NULL);
-			if (rc != PGV_OK)
-				goto dev_fail;
-			i0++;
-			out->batches++;
-			continue;
-		}
-		/* as many concurrent inserts as the graph can absorb without the newcomers missing each other much */
-		B = (int) (linked / 16);
-		if (B < 1)
-			B = 1;
-		if (B > max_batch)
-			B = max_batch;
-		if (B > n - i0)
-			B = (int) (n - i0);
-		entry_level = el[entry].level;
-		/* An element taller than the entry point becomes the new entry under the reference's exclusive entry
-		 * lock (src/hnswbuild.c:398-431): the next tall element links to it on the new top layers.  The batch
-		 * therefore ends at (and includes) the first such element -- later ones search from the new entry. */
-		for (int b = 0; b < B; b++)
-			if (el[i0 + b].level > entry_level)
-			{
-				B = b + 1;
-				break;
-			}
-		for (int b = 0; b < B; b++)
-		{
-			int			l = el[i0 + b].level < entry_level ? el[i0 + b].level : entry_level;
-
-			if (l + 1 > lcap)
-				lcap = l + 1;
-		}
-
-		PHASE(PH_SEARCH);
-		/* ---- 1 + 2. stage A: the batch's searches and its candidate lists' pair distances -- computed ahead by the
-		 * helper while the previous batch was replayed, or here */
-		{
-			stage_a    *a = &stages[cur];
-
-			if (ahead_valid && a->i0 == i0 && a->B == B && a->lcap == lcap)
-				worker_wait(&helper, a->seq);	/* (usually long over) */
-			else
-			{
-				/* every patch handed to the helper has been issued (a batch that ran ahead for nothing cannot happen
-				 * by construction); the device orders this search behind the patch */
-				worker_drain(&helper);
-				a->i0 = i0;
-				a->B = B;
-				a->lcap = lcap;
-				run_stage_a(mirror, a, el, m, ef_construction);
-			}
-			ahead_valid = 0;
-			if (a->rc != PGV_OK)
-			{
-				rc = pgv_host_fail(a->rc, "%s", a->err);
-				goto done;
-			}
-			out->device_pairs += a->npairs;
-			sw_ids = a->sw_ids;
-			sw_dist = a->sw_dist;
-			sw_cnt = a->sw_cnt;
-			tri_off = a->tri_off;
-			cdist = a->pdist;
-			/* the NEXT batch runs ahead when its composition is already certain: a full batch follows a full batch
-			 * (linked / 16 >= max_batch holds from here on), the entry point does not change in this one, and batches
-			 * are large enough for the overlap to matter */
-			if (max_batch >= 64 && B == max_batch && linked / 16 >= max_batch && i0 + B < n)
-			{
-				int			tall = 0;
-
-				for (int b = 0; b < B; b++)
-					tall |= el[i0 + b].level > entry_level;
-				if (!tall)
-				{
-					stage_a    *nx = &stages[cur ^ 1];
-					int64_t		n0 = i0 + B;
-					int			nB = (int) (n - n0 < max_batch ? n - n0 : max_batch);
-					int			nlcap = 1;
-
-					for (int b = 0; b < nB; b++)
-						if (el[n0 + b].level > entry_level)
-						{
-							nB = b + 1;
-							break;
-						}
-					for (int b = 0; b < nB; b++)
-					{
-						int			l = el[n0 + b].level < entry_level ? el[n0 + b].level : entry_level;
-
-						if (l + 1 > nlcap)
-							nlcap = l + 1;
-					}
-					if (!helper.started && worker_start(&helper, mirror, el, m, ef_construction))
-						worker_start(&scorer, mirror, el, m, ef_construction);
-					if (helper.started)
-					{
-						nx->i0 = n0;
-						nx->B = nB;
-						nx->lcap = nlcap;
-						/* posted at once: queued behind this batch's own scoring requests instead, the build was 1.7 s
-						 * slower (measured, profiles/r04/hnsw_build_pipeline.md) */
-						nx->seq = worker_post(&helper, JOB_STAGE_A, nx);
-						ahead_valid = 1;
-					}
-				}
-			}
-		}
-
-		PHASE(PH_SELECT);
-		/* ---- 3. SelectNeighbors + AddConnections per element and layer (independent: one thread each) */
-#pragma omp parallel if (B >= 8) num_threads(nthreads)
-		{
-			cand	   *lw = malloc(sizeof(cand) * (size_t) ef_construction);
-			cand	  **c = malloc(sizeof(cand *) * (size_t) ef_construction * 5);
-			cand	  **r = c + ef_construction,
-					  **w = c + 2 * ef_construction,
-					  **wd = c + 3 * ef_construction,
-					  **added = c + 4 * ef_construction;
-			uint8_t    *flag = malloc((size_t) ef_construction);
-
-#pragma omp for schedule(dynamic, 4)
-			for (int b = 0; b < B; b++)
-			{
-				int32_t		e = (int32_t) (i0 + b);
-				elem	   *x = &el[e];
-
-				x->layers = calloc((size_t) x->level + 1, sizeof(nlist));
-				if (device_select)
-				{
-					/* SelectNeighbors ran on the device (pgv_hnsw_build_neighbors): the lists are AddConnections' to store */
-					const stage_a *a = &stages[cur];
-
-					for (int lc = lcap - 1; lc >= 0; lc--)
-					{
-						const size_t g = (size_t) b * lcap + lc;
-						const int	rn = a->sel_cnt[g];
-						const int	lm = layer_m(m, lc);
-
-						if (rn == 0 || lc > x->level)
-							continue;
-						x->layers[lc].closer_set = 0;	/* not sorted deterministically (:1143-1144) */
-						x->layers[lc].items = items_alloc(lm);
-						x->layers[lc].length = rn;
-						for (int i = 0; i < rn; i++)
-						{
-							cand	   *it = &x->layers[lc].items[i];
-
-							it->element = a->sel_ids[g * 2 * (size_t) m + i];
-							it->distance = a->sel_dist[g * 2 * (size_t) m + i];
-							it->local = 0;
-							it->closer = a->sel_closer[g * 2 * (size_t) m + i];
-						}
-					}
-					for (int lc = 0; lc <= x->level; lc++)
-						if (!x->layers[lc].items)
-							x->layers[lc].items = items_alloc(layer_m(m, lc));
-					continue;
-				}
-				for (int lc = lcap - 1; lc >= 0; lc--)
-				{
-					int			nw = sw_cnt[(size_t) b * lcap + lc];
-					int			lm = layer_m(m, lc);
-					const int32_t *wi = sw_ids + ((size_t) b * lcap + lc) * ef_construction;
-					const float *wdist = sw_dist + ((size_t) b * lcap + lc) * ef_construction;
-					int			rn;
-					/* not sorted deterministically: the flags of this selection are not reusable (:1143-1144) */
-					uint8_t		closer_set = 0;
-
-					if (nw == 0 || lc > x->level)
-						continue;
-					/* the reference's list `w` is furthest first; the device returns nearest first */
-					for (int i = 0; i < nw; i++)
-					{
-						lw[i].element = wi[nw - 1 - i];
-						lw[i].distance = wdist[nw - 1 - i];
-						lw[i].local = nw - 1 - i;
-						lw[i].closer = 0;
-						c[i] = &lw[i];
-					}
-					{
-						/* (the triangle is only there, and only looked at, when the list has to be thinned) */
-						pairsrc		ps = pairs_of(cdist + tri_off[(size_t) b * lcap + lc], 1, NULL);
-
-						rn = select_neighbors(c, nw, lm, &ps, &closer_set, NULL, r, NULL, 0, NULL, w, wd, added, flag);
-					}
-					x->layers[lc].closer_set = closer_set;
-					x->layers[lc].items = items_alloc(lm);
-					x->layers[lc].length = rn;
-					for (int i = 0; i < rn; i++)
-						x->layers[lc].items[i] = *r[i];
-				}
-				for (int lc = 0; lc <= x->level; lc++)
-					if (!x->layers[lc].items)
-						x->layers[lc].items = items_alloc(layer_m(m, lc));
-			}
-			free(lw);
-			free(c);
-			free(flag);
-		}
-		/* FindDuplicateInMemory, src/hnswbuild.c:313-364, in heap order: neighbors are ordered by distance */
-		for (int b = 0; b < B; b++)
-		{
-			int32_t		e = (int32_t) (i0 + b);
-			elem	   *x = &el[e];
-			const nlist *l0 = &x->layers[0];
-			const char *v = (const char *) rows + (size_t) e * item_bytes;
-
-			for (int i = 0; i < l0->length; i++)
-			{
-				int32_t		ne = l0->items[i].element;
-
-				if (memcmp(v, (const char *) rows + (size_t) ne * item_bytes, item_bytes) != 0)
-					break;
-				if (el[ne].heaptids < HNSW_HEAPTIDS)
-				{
-					el[ne].heaptids++;
-					out->dup_of[e] = ne;
-					break;
-				}
-			}
-			if (out->dup_of[e] >= 0)
-			{
-				for (int lc = 0; lc <= x->level; lc++)
-					free(x->layers[lc].items);
-				free(x->layers);
-				x->layers = NULL;
-			}
-		}
-
-		PHASE(PH_RECORDS);
-		/* ---- 4. the lists this batch links into, and every distance their re-selections can look up.
-		 * 4a: one request per (batch element, chosen neighbor, layer) in the order the reference's loop would link
-		 * them, and a bare record per distinct list.  The lists are dealt to the threads by owner: every thread walks
-		 * all requests (they are the batch's fresh lists, a few hundred KB) and keeps its own, in its own small hash
-		 * table -- the order inside a list is the walk's, whatever the number of threads. */
-		{
-			int64_t		nlinks = 0;
-
-			for (int b = 0; b < B; b++)
-			{
-				int32_t		e = (int32_t) (i0 + b);
-
-				if (!el[e].layers)
-					continue;
-				linked++;
-				if (!is_dirty[e])
-				{
-					is_dirty[e] = 1;
-					ndirty++;
-				}
-				/* the entry point moves up with the tallest element (src/hnswbuild.c:425-430) */
-				if (el[e].level > el[entry].level)
-					entry = e;
-			}
-			for (int t = 0; t < nthreads; t++)	/* (a short batch runs the walk on one thread: the others' stay empty) */
-				parts[t].ndirty = 0;
-#pragma omp parallel if (B >= 8) num_threads(nthreads)
-			{
-				const int	T = omp_get_num_threads(),
-							me = omp_get_thread_num();
-				recpart    *rp = &parts[me];
-
-				rp->nrec = 0;
-				rp->nlinks = 0;
-				rp->ndirty = 0;
-				if (rp->tab_cap == 0)
-				{
-					rp->tab_cap = 1 << 10;	/* grows by doubling at load factor 1/2 */
-					rp->tab = malloc(sizeof(int32_t) * (size_t) rp->tab_cap);
-				}
-				if (!rp->tab)
-					rp->oom = 1;
-				else
-					memset(rp->tab, 0, sizeof(int32_t) * (size_t) rp->tab_cap);
-				for (int b = 0; b < B && !rp->oom; b++)
-				{
-					int32_t		e = (int32_t) (i0 + b);
-					elem	   *x = &el[e];
-
-					if (!x->layers)
-						continue;
-					for (int lc = x->level; lc >= 0; lc--)
-						for (int i = 0; i < x->layers[lc].length; i++)
-						{
-							int32_t		owner = x->layers[lc].items[i].element;
-							uint64_t	key,
-										hv;
-							int64_t		h;
-							int32_t		ri;		/* record index + 1 (the table may be rebuilt below: h is not kept) */
-
-							if ((int) (((uint64_t) ((uint32_t) owner * 2654435761u) * (uint64_t) T) >> 32) != me)
-								continue;
-							key = ((uint64_t) owner << 6) | (uint64_t) lc;
-							hv = key * 0x9E3779B97F4A7C15ull;
-							h = (int64_t) (hv >> 40) & (rp->tab_cap - 1);
-							while (rp->tab[h] != 0 && !(rp->recs[rp->tab[h] - 1].owner == owner && rp->recs[rp->tab[h] - 1].lc == lc))
-								h = (h + 1) & (rp->tab_cap - 1);
-							ri = rp->tab[h];
-							if (ri == 0)
-							{
-								record	   *rcd;
-
-								if (rp->nrec == rp->cap)
-								{
-									int			cap = rp->cap ? rp->cap * 2 : 1024;
-									record	   *grown = realloc(rp->recs, sizeof(record) * (size_t) cap);
-
-									if (!grown)
-									{
-										rp->oom = 1;
-										break;
-									}
-									rp->recs = grown;
-									rp->cap = cap;
-								}
-								rcd = &rp->recs[rp->nrec];
-								rcd->owner = owner;
-								rcd->lc = lc;
-								rcd->newcap = 0;	/* newcomers, counted here */
-								rp->tab[h] = ++rp->nrec;
-								ri = rp->nrec;
-								if ((int64_t) rp->nrec * 2 > rp->tab_cap)
-								{
-									/* load factor 1/2 reached (a batch touches up to B * (2m + level * m) lists; m up to
-									 * 100, src/hnsw.h:50): double the table and rehash the records made so far */
-									int64_t		ncap = rp->tab_cap * 2;
-									int32_t    *nt = calloc((size_t) ncap, sizeof(int32_t));
-
-									if (!nt)
-									{
-										rp->oom = 1;
-										break;
-									}
-									for (int r = 0; r < rp->nrec; r++)
-									{
-										uint64_t	k2 = ((uint64_t) rp->recs[r].owner << 6) | (uint64_t) rp->recs[r].lc;
-										int64_t		h2 = (int64_t) ((k2 * 0x9E3779B97F4A7C15ull) >> 40) & (ncap - 1);
-
-										while (nt[h2] != 0)
-											h2 = (h2 + 1) & (ncap - 1);
-										nt[h2] = r + 1;
-									}
-									free(rp->tab);
-									rp->tab = nt;
-									rp->tab_cap = ncap;
-								}
-								if (!is_dirty[owner])	/* (owners are dealt to threads: no two write one flag) */
-								{
-									if (rp->ndirty == rp->dirty_cap)
-									{
-										int			cap = rp->dirty_cap ? rp->dirty_cap * 2 : 1024;
-										int32_t    *grown = realloc(rp->dirty, sizeof(int32_t) * (size_t) cap);
-
-										if (!grown)
-										{
-											rp->oom = 1;
-											break;
-										}
-										rp->dirty = grown;
-										rp->dirty_cap = cap;
-									}
-									is_dirty[owner] = 1;
-									rp->dirty[rp->ndirty++] = owner;
-								}
-							}
-							if (rp->nlinks == rp->links_cap)
-							{
-								int64_t		cap = rp->links_cap ? rp->links_cap * 2 : 4096;
-								link_req   *grown = realloc(rp->links, sizeof(link_req) * (size_t) cap);
-
-								if (!grown)
-								{
-									rp->oom = 1;
-									break;
-								}
-								rp->links = grown;
-								rp->links_cap = cap;
-							}
-							rp->links[rp->nlinks].rec = ri - 1;
-							rp->links[rp->nlinks].element = e;
-							rp->links[rp->nlinks].distance = x->layers[lc].items[i].distance;
-							rp->nlinks++;
-							rp->recs[ri - 1].newcap++;
-						}
-				}
-#pragma omp barrier
-#pragma omp single
-				{
-					/* where each thread's records and requests go in the batch's arrays */
-					int64_t		nr = 0,
-								nl = 0;
-
-					for (int t = 0; t < T; t++)
-					{
-						parts[t].rec_base = nr;
-						parts[t].link_base = nl;
-						nr += parts[t].nrec;
-						nl += parts[t].nlinks;
-						ndirty += parts[t].ndirty;
-						oom |= parts[t].oom;
-					}
-					if (nr + 1 > recs_cap)
-					{
-						recs_cap = (int) (nr + 1) * 2;
-						recs = realloc(recs, sizeof(record) * (size_t) recs_cap);
-						grp_off = realloc(grp_off, sizeof(int64_t) * (size_t) (recs_cap + 1));
-					}
-					if (nl + 1 > links_cap)
-					{
-						links_cap = (nl + 1) * 2;
-						grp_elem = realloc(grp_elem, sizeof(int32_t) * (size_t) links_cap);
-						grp_dist = realloc(grp_dist, sizeof(float) * (size_t) links_cap);
-					}
-					if (!recs || !grp_off || !grp_elem || !grp_dist)
-						oom = 1;
-					else
-						grp_off[nr] = nl;
-					nrec = (int) nr;
-					nlinks = nl;
-				}
-				/* 4b: the requests grouped by list, link order kept inside a list (counting sort, thread by thread) */
-				if (!oom)
-				{
-					int64_t		at = rp->link_base;
-
-					for (int k = 0; k < rp->nrec; k++)
-					{
-						grp_off[rp->rec_base + k] = at;
-						at += rp->recs[k].newcap;
-						rp->recs[k].nlocal = 0;		/* fill cursor */
-					}
-					for (int64_t t = 0; t < rp->nlinks; t++)
-					{
-						record	   *rcd = &rp->recs[rp->links[t].rec];
-						int64_t		to = grp_off[rp->rec_base + rp->links[t].rec] + rcd->nlocal++;
-
-						grp_elem[to] = rp->links[t].element;
-						grp_dist[to] = rp->links[t].distance;
-					}
-					if (rp->nrec > 0)
-						memcpy(recs + rp->rec_base, rp->recs, sizeof(record) * (size_t) rp->nrec);
-				}
-			}
-			(void) nlinks;
-			if (oom)
-			{
-				rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory for the batch's list records");
-				goto done;
-			}
-			/* 4c (parallel: this is where the owners' lists, cold in the cache, are read): members + newcomers */
-#pragma omp parallel for if (B >= 8) num_threads(nthreads) schedule(static)
-			for (int k = 0; k < nrec; k++)
-			{
-				record	   *rcd = &recs[k];
-				nlist	   *l = &el[rcd->owner].layers[rcd->lc];
-				int			nnew = rcd->newcap;
-
-				/* element -> its layers -> the list's items: three dependent misses per record, fetched ahead (a
-				 * neighbouring thread's records at the chunk's end: harmless) */
-				if (k + 12 < nrec)
-					__builtin_prefetch(&el[recs[k + 12].owner]);
-				if (k + 8 < nrec)
-					__builtin_prefetch(&el[recs[k + 8].owner].layers[recs[k + 8].lc]);
-				if (k + 4 < nrec)
-				{
-					const char *it = (const char *) el[recs[k + 4].owner].layers[recs[k + 4].lc].items;
-
-					__builtin_prefetch(it);
-					__builtin_prefetch(it + 64);
-					__builtin_prefetch(it + 128);
-					__builtin_prefetch(it + 192);
-				}
-
-				rcd->nstart = l->length;
-				rcd->nlocal = l->length + nnew;
-				rcd->ids = arena_alloc(&arenas[omp_get_thread_num()], sizeof(int32_t) * (size_t) rcd->nlocal);
-				if (!rcd->ids)
-				{
-#pragma omp atomic write
-					oom = 1;
-					rcd->nlocal = rcd->nstart = 0;
-					continue;
-				}
-				rcd->newdist = grp_dist + grp_off[k];
-				rcd->items = l->items;
-				rcd->full = !l->closer_set;	/* no cached flags: its next selection computes everything */
-				rcd->blocked = 0;
-				rcd->wait_from = -1;
-				for (int j = 0; j < l->length; j++)
-				{
-					rcd->ids[j] = l->items[j].element;
-					l->items[j].local = j;
-				}
-				memcpy(rcd->ids + l->length, grp_elem + grp_off[k], sizeof(int32_t) * (size_t) nnew);
-			}
-			if (oom)
-			{
-				rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory for the batch's list records");
-				goto done;
-			}
-		}
-		PHASE(PH_PAIRLIST);
-		/* the records in slices: with the scorer running, slice s + 1's pairs are scored while slice s is replayed */
-		nslices = scorer.started && nrec >= 64 * SCORE_SLICES ? SCORE_SLICES : 1;
-		{
-			int64_t		total = 0;
-
-			/* (one thread per slice; pair offsets are the slice's own: its reply starts at slices[.].out) */
-#pragma omp parallel for if (nslices > 1) num_threads(nslices) schedule(static, 1)
-			for (int sl = 0; sl < nslices; sl++)
-			{
-				score_job  *sj = &slices[sl];
-				int64_t		mine = 0;
-
-				/* a short first slice (it is the one waited for with nothing to do), the rest in equal parts */
-				sj->klo = sl == 0 ? 0 : (int) (((int64_t) nrec * (1 + (sl - 1) * 7 / (nslices - 1))) / 8);
-				sj->khi = sl == nslices - 1 ? nrec : (int) (((int64_t) nrec * (1 + sl * 7 / (nslices - 1))) / 8);
-				sj->rc = PGV_OK;
-				sj->seq = 0;
-				groups_reset(&sj->gb);
-				for (int k = sj->klo; k < sj->khi; k++)
-				{
-					record	   *rcd = &recs[k];
-					int			from = rcd->full ? 1 : rcd->nstart;	/* cached flags: only the pairs that involve a newcomer */
-
-					rcd->pair0 = mine;
-					rcd->slice = sl;
-					rcd->from = from < 1 ? 1 : from;
-					/* a list that cannot overflow in this batch never runs a selection */
-					if (rcd->nlocal <= layer_m(m, rcd->lc))
-						continue;
-					if (!groups_add(&sj->gb, rcd->ids, rcd->nlocal, from, mine))
-					{
-						sj->rc = PGV_ERR_NOMEM;
-						break;
-					}
-					mine += group_pairs(rcd->nlocal, from);
-				}
-				sj->npairs = mine;
-				if (sj->gb.ngroups > 0)
-					sj->gb.pair_start[sj->gb.ngroups] = mine;
-			}
-			for (int sl = 0; sl < nslices; sl++)
-			{
-				if (slices[sl].rc != PGV_OK)
-				{
-					rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
-					goto done;
-				}
-				total += slices[sl].npairs;
-			}
-			npairs = total;
-		}
-		PHASE(PH_PAIRS);
-		if (npairs > pdist_cap)
-		{
-			pgv_pinned_free(pdist);
-			pdist = NULL;
-			pdist_cap = npairs * 2;
-			if ((rc = pgv_pinned_alloc(sizeof(float) * (size_t) pdist_cap, (void **) &pdist)) != PGV_OK)
-			{
-				pdist_cap = 0;
-				goto dev_fail;
-			}
-		}
-		{
-			int64_t		base = 0;
-
-			for (int sl = 0; sl < nslices; sl++)
-			{
-				score_job  *sj = &slices[sl];
-
-				sj->out = pdist + base;
-				base += sj->npairs;
-				if (sj->npairs == 0)
-					continue;
-				if (nslices > 1)
-					sj->seq = worker_post(&scorer, JOB_SCORE, sj);
-				else
-				{
-					rc = pgv_hnsw_score_groups(mirror, sj->gb.ids, sj->gb.ids_start, sj->gb.from, sj->gb.pair_start, sj->gb.ngroups,
-											   sj->gb.nids, sj->npairs, sj->out);
-					if (rc != PGV_OK)
-						goto dev_fail;
-				}
-			}
-			out->device_pairs += npairs;
-		}
-		PHASE(PH_UPDATE);
-
-		/* ---- 5. HnswUpdateNeighborsInMemory (src/hnswbuild.c:376-405).  The reference links one element after
-		 * the other; updates of different lists do not see each other, so the lists are replayed in parallel,
-		 * each with its newcomers in heap order. */
-		{
-			int			nblocked = 0;
-
-			/* steps 0 .. nslices - 1: the first replay of slice `step`'s lists; step nslices: the second pass over all */
-			for (int step = 0; step <= nslices; step++)
-			{
-				const int	pass = step == nslices;
-				const int	klo = pass ? 0 : slices[step].klo,
-							khi = pass ? nrec : slices[step].khi;
-
-				if (!pass && slices[step].seq != 0)
-				{
-					PHASE(PH_PAIRS);
-					worker_wait(&scorer, slices[step].seq);
-					PHASE(PH_UPDATE);
-					if (slices[step].rc != PGV_OK)
-					{
-						rc = pgv_host_fail(slices[step].rc, "%s", slices[step].err);
-						goto done;
-					}
-				}
-				if (pass == 1)
-				{
-					/* ---- 5b. the updates that were put aside: their lists' member-member pairs, then the replay */
-					if (nblocked == 0)
-						break;
-					groups_reset(&gb);
-					npairs = 0;
-					for (int k = 0; k < nrec; k++)
-						if (recs[k].blocked)
-						{
-							recs[k].pair0b = npairs;
-							if (!groups_add(&gb, recs[k].ids, recs[k].nstart, 1, npairs))
-							{
-								rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
-								goto done;
-							}
-							npairs += group_pairs(recs[k].nstart, 1);
-						}
-					gb.pair_start[gb.ngroups] = npairs;
-					/* (the first request's reply stays: the newcomers' pairs are looked up there) */
-					if (npairs > pdist2_cap)
-					{
-						pgv_pinned_free(pdist2);
-						pdist2 = NULL;
-						pdist2_cap = npairs * 2;
-						if ((rc = pgv_pinned_alloc(sizeof(float) * (size_t) pdist2_cap, (void **) &pdist2)) != PGV_OK)
-						{
-							pdist2_cap = 0;
-							goto dev_fail;
-						}
-					}
-					rc = pgv_hnsw_score_groups(mirror, gb.ids, gb.ids_start, gb.from, gb.pair_start, gb.ngroups, gb.nids, npairs, pdist2);
-					if (rc != PGV_OK)
-						goto dev_fail;
-					out->device_pairs += npairs;
-					out->deferred_updates += nblocked;
-				}
-#pragma omp parallel if (B >= 8) num_threads(nthreads)
-				{
-					int			lm0 = layer_m(m, 0);
-					cand	  **c = malloc(sizeof(cand *) * (size_t) (lm0 + 1) * 5);
-					cand	  **r = c + (lm0 + 1),
-							  **w = c + 2 * (lm0 + 1),
-							  **wd = c + 3 * (lm0 + 1),
-							  **added = c + 4 * (lm0 + 1);
-					uint8_t    *flag = malloc((size_t) lm0 + 1);
-
-#pragma omp for schedule(dynamic, 16) reduction(+:nblocked)
-					for (int k = klo; k < khi; k++)
-					{
-						record	   *rcd = &recs[k];
-						nlist	   *l = &el[rcd->owner].layers[rcd->lc];
-						int			lm = layer_m(m, rcd->lc);
-						int			from = rcd->nstart;
-						pairsrc		ps;
-
-						if (pass == 1)
-						{
-							if (!rcd->blocked)
-								continue;
-							from = rcd->wait_from;
-						}
-						else if (k + 4 < khi)
-						{
-							/* a later record's list (last touched by another thread in step 4) and its pairs (fresh
-							 * from the device: in no cache) */
-							const record *nx = &recs[k + 4];
-							const char *it = nx->items,
-									   *tr = (const char *) (slices[nx->slice].out + nx->pair0);
-							const int	nlm = layer_m(m, nx->lc);
-
-							for (int o = 0; o < nlm * (int) sizeof(cand); o += 64)
-								__builtin_prefetch(it + o);
-							__builtin_prefetch(tr);
-							__builtin_prefetch(tr + 64);
-							/* the cached sort order behind the items, and where the list's tuple part goes */
-							__builtin_prefetch(it + nlm * (int) sizeof(cand));
-							__builtin_prefetch(out->nbr + out->nbr_start[nx->owner] + (int64_t) (el[nx->owner].level - nx->lc) * m, 1);
-							__builtin_prefetch(nx->newdist);
-						}
-						ps = pairs_of(slices[rcd->slice].out + rcd->pair0, rcd->from, pass ? pdist2 + rcd->pair0b : NULL);
-						for (int u = from; u < rcd->nlocal; u++)
-						{
-							cand		new_hc;
-							cand	   *pruned = NULL;
-							int			nc,
-										rn;
-
-							new_hc.element = rcd->ids[u];
-							new_hc.distance = rcd->newdist[u - rcd->nstart];
-							new_hc.local = u;
-							new_hc.closer = 0;
-							/* HnswUpdateConnection, src/hnswutils.c:1183-1231 */
-							if (l->length < lm)
-							{
-								l->items[l->length++] = new_hc;
-								l->ord_valid = 0;
-								continue;
-							}
-							nc = l->length + 1;
-							for (int j = 0; j < l->length; j++)
-								c[j] = &l->items[j];
-							c[nc - 1] = &new_hc;
-							rn = select_neighbors(c, nc, lm, &ps, &l->closer_set, &new_hc, r, &pruned, 1,
-												  l->ord_valid ? items_ord(l, lm) : NULL, w, wd, added, flag);
-							if (rn < 0)
-							{
-								/* needs member-member distances that were not fetched: this and every later
-								 * update of the list wait for the second launch */
-								rcd->blocked = 1;
-								rcd->wait_from = u;
-								nblocked++;
-								break;
-							}
-							{
-								/* the list keeps its members' places, the newcomer takes the dropped one's
-								 * (src/hnswutils.c:1211-1227); the sorted order w, less the dropped candidate, is kept
-								 * for the list's next selection */
-								uint8_t    *ord = items_ord(l, lm);
-								int			slot = -1,
-											o = 0;
-
-								if (pruned != NULL && pruned != &new_hc)
-									slot = (int) (pruned - l->items);
-								for (int i = 0; i < nc; i++)
-									if (w[i] != pruned)
-										ord[o++] = (uint8_t) (w[i] == &new_hc ? slot : (int) (w[i] - l->items));
-								l->ord_valid = 1;
-								if (slot >= 0)
-									l->items[slot] = new_hc;
-							}
-						}
-						/* the list's part of its owner's neighbor tuple, for step 6 */
-						write_segment(&el[rcd->owner], rcd->owner, rcd->lc, m, out->nbr_start, out->nbr);
-					}
-					free(c);
-					free(flag);
-				}
-			}
-		}
-
-		if (oom)
-		{
-			rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory for the batch's list records");
-			goto done;
-		}
-		PHASE(PH_PATCH);
-		/* ---- 6. the graph the next batch searches.  With the helper running, the patch is its job: posted behind the
-		 * stage A that runs ahead (whose kernels read the tuples this step overwrites) and in front of the next one;
-		 * the arrays of the job before last are free again by now. */
-		{
-			patch_job  *pj = &patches[pcur];
-			int			k = 0;
-
-			worker_wait(&helper, pj->seq);
-			if (pj->rc != PGV_OK)
-			{
-				rc = pgv_host_fail(pj->rc, "%s", pj->err);
-				goto done;
-			}
-			if (ndirty + 1 > pj->dirty_cap)
-			{
-				pj->dirty_cap = (int64_t) (ndirty + 1) * 2;
-				pj->dirty = realloc(pj->dirty, sizeof(int32_t) * (size_t) pj->dirty_cap);
-				pj->packed_off = realloc(pj->packed_off, sizeof(int64_t) * (size_t) pj->dirty_cap);
-			}
-			if (!pj->dirty || !pj->packed_off)
-			{
-				rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
-				goto done;
-			}
-			/* dirty elements: the batch itself and the owners of the touched lists */
-			for (int b = 0; b < B; b++)
-				if (is_dirty[i0 + b])
-				{
-					pj->dirty[k++] = (int32_t) (i0 + b);
-					is_dirty[i0 + b] = 0;
-				}
-			for (int t = 0; t < nthreads; t++)	/* the owners, as step 4a's threads met them */
-				for (int q = 0; q < parts[t].ndirty; q++)
-				{
-					pj->dirty[k++] = parts[t].dirty[q];
-					is_dirty[parts[t].dirty[q]] = 0;
-				}
-			ndirty = k;
-			ntuple = 0;
-			for (int q = 0; q < ndirty; q++)
-			{
-				pj->packed_off[q] = ntuple;
-				ntuple += out->nbr_start[pj->dirty[q] + 1] - out->nbr_start[pj->dirty[q]];
-			}
-			pj->packed_off[ndirty] = ntuple;
-			if (ntuple + 1 > pj->packed_cap)
-			{
-				pj->packed_cap = (ntuple + 1) * 2;
-				free(pj->packed);
-				pj->packed = malloc(sizeof(int32_t) * (size_t) pj->packed_cap);
-				if (!pj->packed)
-				{
-					rc = pgv_host_fail(PGV_ERR_NOMEM, "out of memory");
-					goto done;
-				}
-			}
-#pragma omp parallel for if (B >= 8) num_threads(nthreads) schedule(static)
-			for (int q = 0; q < ndirty; q++)
-			{
-				/* (the lists touched by the replay wrote their parts in step 5; the batch's own elements are new) */
-				if (pj->dirty[q] >= i0)
-					write_tuple(el, pj->dirty[q], m, out->nbr_start, out->nbr);
-				memcpy(pj->packed + pj->packed_off[q], out->nbr + out->nbr_start[pj->dirty[q]],
-					   sizeof(int32_t) * (size_t) (pj->packed_off[q + 1] - pj->packed_off[q]));
-			}
-			pj->entry = entry;
-			pj->ndirty = ndirty;
-			if (helper.started)
-			{
-				pj->seq = worker_post(&helper, JOB_PATCH, pj);
-				pcur ^= 1;
-			}
-			else
-			{
-				rc = pgv_hnsw_update_graph(mirror, entry, pj->dirty, ndirty, pj->packed_off, pj->packed);
-				if (rc != PGV_OK)
-					goto dev_fail;
-			}
-		}
-
-		PHASE(PH_FREE);
-		/* forget the batch's records */
-		for (int t = 0; t < nthreads; t++)
-			arena_reset(&arenas[t]);
-		nrec = 0;
-		PHASE(PH_RECORDS);
-		i0 += B;
-		out->batches++;
-		if (ahead_valid)
-			cur ^= 1;
-	}
-	/* the last patches are on the device before the caller searches the mirror */
-	worker_drain(&helper);
-	for (int i = 0; i < 2; i++)
-		if (patches[i].rc != PGV_OK)
-		{
-			rc = pgv_host_fail(patches[i].rc, "%s", patches[i].err);
-			break;
-		}
-	goto done;
-
-dev_fail:
-	rc = pgv_host_fail(rc, "%s", pgv_last_error());
-done:
-	worker_stop(&helper);
-	worker_stop(&scorer);
-	for (int i = 0; i < 2; i++)
-	{
-		free(patches[i].dirty);
-		free(patches[i].packed_off);
-		free(patches[i].packed);
-	}
-	for (int i = 0; i < SCORE_SLICES; i++)
-	{
-		free(slices[i].gb.ids);
-		free(slices[i].gb.ids_start);
-		free(slices[i].gb.from);
-		free(slices[i].gb.pair_start);
-	}
-	stage_a_free(&stages[0]);
-	stage_a_free(&stages[1]);
+	if (rc == PGV_OK && n > 0)
+		rc = device_link
+			? build_linked_on_device(mirror, item_bytes, rows, n, m, ef_construction, max_batch, el, out, &clk, &entry, &linked)
+			: build_linked_on_host(mirror, item_bytes, rows, n, m, ef_construction, max_batch, device_select, el, out, &clk,
+								   &entry, &linked);
 	out->entry = entry;
 	out->nelements = linked;
-	if (el)
-	{
-		for (int64_t i = 0; i < n; i++)
-			if (el[i].layers)
-			{
-				for (int lc = 0; lc <= el[i].level; lc++)
-					free(el[i].layers[lc].items);
-				free(el[i].layers);
-			}
-		free(el);
-	}
-	if (arenas)					/* incl. a batch cut short by an error */
-	{
-		for (int t = 0; t < nthreads; t++)
-			arena_free(&arenas[t]);
-		free(arenas);
-	}
-	free(grp_elem);
-	free(grp_dist);
-	free(grp_off);
-	free(gb.ids);
-	free(gb.ids_start);
-	free(gb.from);
-	free(gb.pair_start);
-	pgv_pinned_free(pdist);
-	pgv_pinned_free(pdist2);
-	free(is_dirty);
-	free(recs);
-	if (parts)
-	{
-		for (int t = 0; t < nthreads; t++)
-		{
-			free(parts[t].recs);
-			free(parts[t].dirty);
-			free(parts[t].links);
-			free(parts[t].tab);
-		}
-		free(parts);
-	}
+	for (int64_t i = 0; el && i < n; i++)
+		layers_free(&el[i]);
+	free(el);
 	if (rc != PGV_OK)
 		pgv_host_hnsw_built_free(out);
 	return rc;
 }
+

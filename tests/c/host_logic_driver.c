@@ -167,9 +167,10 @@ test_hnsw_build(void)
 		EXPECT(found >= 15);
 	}
 	/* the graph updates on the "device" (csrc/hnsw_link_core.h through the stand-in: the source the GPU kernel is compiled
-	 * from) and replayed on the host build the SAME graph, at batch 32 and with the pipeline running (batch 64 from 1024
-	 * linked elements on: searches, selection and linking on three threads) -- whichever of the two this process runs by
-	 * default, the other one is asked for here */
+	 * from) and replayed on the host build the SAME graph, at batch 32 and at batch 64 -- whichever of the two this process
+	 * runs by default, the other one is asked for here.  (With 900 elements linked / 16 never reaches 64: every batch is
+	 * done in turn, nothing runs ahead and no helper thread starts.  The forms with their pipelines running are compared
+	 * further down, at 3000 elements.) */
 	{
 		const char *was = getenv("PGV_HNSW_HOST_LINK");
 		const int	host_default = (was && atoi(was) != 0) || (getenv("PGV_HNSW_HOST_SELECT") && atoi(getenv("PGV_HNSW_HOST_SELECT")) != 0);
@@ -349,6 +350,69 @@ test_hnsw_build(void)
 		pgv_host_hnsw_built_free(&built);
 		pgv_hnsw_free(m2);
 		free(d2);
+	}
+	/* the three forms of the build with their pipelines RUNNING: 3000 elements in batches of 64 are full batches from
+	 * 1024 linked elements on, so the host replay has stage A running ahead on its helper, the records' pairs scored in
+	 * slices and the patches posted as jobs, and the device form its searches and selections on two threads -- the same
+	 * graph tuple for tuple, duplicates included (30 copies of one row, ten rows apart: further than the two batches a
+	 * search that ran ahead is blind for), and a cancel that arrives while the helpers run ends them cleanly */
+	{
+		enum { N3 = 3000, COPIES = 30, MB3 = 64 };
+		static const char *const form[3][2] = {{NULL, NULL}, {"PGV_HNSW_HOST_LINK", "1"}, {"PGV_HNSW_HOST_SELECT", "1"}};
+		float	   *d3 = malloc(sizeof(float) * N3 * DIM);
+		char	   *was_link = getenv("PGV_HNSW_HOST_LINK") ? strdup(getenv("PGV_HNSW_HOST_LINK")) : NULL,
+				   *was_select = getenv("PGV_HNSW_HOST_SELECT") ? strdup(getenv("PGV_HNSW_HOST_SELECT")) : NULL;
+		pgv_hnsw   *m3;
+		pgv_hnsw_built f[3];
+		int			dups = 0;
+
+		for (int i = 0; i < N3 * DIM; i++)
+			d3[i] = (float) (urand() % 1024);
+		for (int i = 1; i < COPIES; i++)
+			memcpy(d3 + (N3 / 2 + 10 * i) * DIM, d3 + (N3 / 2) * DIM, sizeof(float) * DIM);
+		CHECK(pgv_hnsw_upload(ctx, PGV_L2SQ, PGV_F32, DIM, d3, N3, &m3));
+		for (int k = 0; k < 3; k++)
+		{
+			unsetenv("PGV_HNSW_HOST_LINK");
+			unsetenv("PGV_HNSW_HOST_SELECT");
+			if (form[k][0])
+				setenv(form[k][0], form[k][1], 1);
+			CHECK(pgv_host_hnsw_build(m3, PGV_F32, DIM, d3, N3, M, EFC, NULL, MB3, &f[k]));
+			EXPECT(f[k].deferred_updates > 0);
+			EXPECT(f[k].entry == f[0].entry && f[k].batches == f[0].batches && f[k].nelements == f[0].nelements);
+			EXPECT(memcmp(f[k].levels, f[0].levels, sizeof(int32_t) * N3) == 0);
+			EXPECT(memcmp(f[k].dup_of, f[0].dup_of, sizeof(int32_t) * N3) == 0);
+			EXPECT(memcmp(f[k].nbr, f[0].nbr, sizeof(int32_t) * (size_t) f[0].nbr_start[N3]) == 0);
+			if (k < 2)
+			{
+				/* the poll that says "cancel" comes ten polls (one a batch) before the build's last */
+				int			rc;
+
+				cancel_after = (int) f[k].batches - 10;
+				cancel_polls = 0;
+				pgv_host_hnsw_set_cancel_check(cancel_cb, NULL);
+				rc = pgv_host_hnsw_build(m3, PGV_F32, DIM, d3, N3, M, EFC, NULL, MB3, &built);
+				pgv_host_hnsw_set_cancel_check(NULL, NULL);
+				EXPECT(rc == PGV_ERR_STATE && strstr(pgv_host_last_error(), "cancelled") != NULL);
+				EXPECT(built.levels == NULL);
+			}
+		}
+		for (int e = 0; e < N3; e++)
+			dups += f[0].dup_of[e] >= 0;
+		EXPECT(dups > 0 && f[0].nelements == N3 - dups);
+		EXPECT(f[0].batches < N3 / MB3 + 100);	/* (full batches from 1024 elements on: the pipelines had something to do) */
+		for (int k = 0; k < 3; k++)
+			pgv_host_hnsw_built_free(&f[k]);
+		unsetenv("PGV_HNSW_HOST_LINK");
+		unsetenv("PGV_HNSW_HOST_SELECT");
+		if (was_link)
+			setenv("PGV_HNSW_HOST_LINK", was_link, 1);
+		if (was_select)
+			setenv("PGV_HNSW_HOST_SELECT", was_select, 1);
+		free(was_link);
+		free(was_select);
+		pgv_hnsw_free(m3);
+		free(d3);
 	}
 	pgv_ctx_destroy(ctx);
 	free(data);

@@ -5,7 +5,8 @@
  *
  *   gcc -O2 -rdynamic -I include -I pgvector_amd/host tools/hnsw_host_bench.c tests/c/mock_hip.c \
  *       -o hnsw_host_bench -L pgvector_amd/lib -lpgv_host -lm -lpthread -Wl,-rpath,$PWD/pgvector_amd/lib
- *   hnsw_host_bench [rows [max_batch]]        (8-d uniform rows, m 16, ef_construction 64)
+ *   hnsw_host_bench [rows [max_batch [dim [m [ef_construction]]]]]     (200000 uniform rows, 1024, 8-d, m 16, 64)
+ * The "search" and "pairs" phases are the stand-in's time and to be ignored; the others are pure host work.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -28,10 +29,10 @@ int
 main(int argc, char **argv)
 {
 	const int	n = argc > 1 ? atoi(argv[1]) : 200000,
-				dim = 8,
-				m = 16,
-				efc = 64,
-				max_batch = argc > 2 ? atoi(argv[2]) : 1024;
+				max_batch = argc > 2 ? atoi(argv[2]) : 1024,
+				dim = argc > 3 ? atoi(argv[3]) : 8,
+				m = argc > 4 ? atoi(argv[4]) : 16,
+				efc = argc > 5 ? atoi(argv[5]) : 64;
 	static const char *names[8] = {"search", "pairs", "select", "records", "update", "patch", "pairlist", "free"};
 	float	   *data = malloc(sizeof(float) * (size_t) n * dim);
 	pgv_ctx    *ctx;
