@@ -620,6 +620,71 @@ int			pgv_binary_quantize(pgv_ctx * ctx, pgv_dtype dtype, int dim, const void *r
 int			pgv_rerank(pgv_ctx * ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *queries, int nq,
 					   const void *rows, int64_t n, const int64_t *cand, int kc, int k, float *out_dist, int64_t *out_idx);
 
+/* ------------------------------------------------ sparsevec: exact distances */
+
+/*
+ * Sparse vectors travel as CSR, which is what a SparseVector datum stores (src/sparsevec.h:22-47: sorted 0-based int32
+ * indices, then float values), vector after vector:
+ *   ptr [n + 1]    int64_t, ptr[0] = 0, monotone; vector v owns elements ptr[v] .. ptr[v + 1] - 1
+ *   idx [ptr[n]]   int32_t, strictly ascending inside a vector, 0 <= idx < dim
+ *   val [ptr[n]]   float, finite
+ * 1 <= dim <= 1 000 000 000 (SPARSEVEC_MAX_DIM) and at most 16 000 stored elements per vector (SPARSEVEC_MAX_NNZ), else
+ * PGV_ERR_DIMS.  A vector with no stored element is legal ('{}/2'), and so is a stored 0.0.  Every array may be host or
+ * device memory.  HOST arrays are validated before any launch (a ptr that is not monotone, an index out of range or
+ * not ascending, a value that is not finite: PGV_ERR_ARG; too many stored elements: PGV_ERR_DIMS; the text names the
+ * vector and the position); DEVICE arrays are NOT checked and the behaviour is undefined (pgv_rerank's rule for cand).
+ * Host idx / val under a DEVICE row_ptr count as unchecked too: their vectors' bounds are not on the host.  (A device
+ * q_ptr is copied to the host, where the queries' tiles are planned, and checked there.)
+ *
+ * Every value is an fp32 sum of exactly the terms the reference adds, each computed as the reference computes it;
+ * only the order of the additions differs from its index order (no |a|^2 + |b|^2 - 2ab expansion): a vector's L2 /
+ * L1 distance to itself is exactly 0, integer-valued data gives the reference's bits, and a sum that overflows with
+ * terms of one sign is +-inf like the reference's.
+ *
+ * Not served: HNSW over sparse elements (hnsw_sparsevec_support, HNSW_MAX_NNZ 1000, src/hnswutils.c:1361-1430) -- the
+ * follow-up on top of these kernels --, a device-side sparsevec_l2_normalize, the ext/ glue.  bench.py does not measure
+ * these entries; tools/bench_sparse_topk.py does.
+ */
+
+/*
+ * One sparse query (q_nnz stored elements at q_idx / q_val) against n sparse rows: one fmgr call per heap row in the
+ * reference.  out [n] = kernel value:
+ *   PGV_L2SQ    SparsevecL2SquaredDistance (src/sparsevec.c:826-869); the sqrt stays the caller's float8 post-op
+ *   PGV_NEG_IP  -SparsevecInnerProduct (src/sparsevec.c:905-936, :958-966)
+ *   PGV_L1      the loop of sparsevec_l1_distance (src/sparsevec.c:1018-1060)
+ */
+int			pgv_sparse_distance_batch(pgv_ctx * ctx, pgv_metric metric, int dim,
+									  int q_nnz, const int32_t *q_idx, const float *q_val,
+									  const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+									  float *out);
+
+/*
+ * sparsevec_cosine_distance (src/sparsevec.c:972-1011): the inner product and the two squared norms as three fp32
+ * sums, `(double) ip / sqrt((double) na * (double) nb)`, clamped to [-1, 1], 1 - similarity.  An empty or all-zero
+ * vector gives NaN like the reference (test/expected/sparsevec.out, cosine_distance('{}/1', '{}/1')).  out [n] float8,
+ * like pgv_cosine_distance_batch.
+ */
+int			pgv_sparse_cosine_distance_batch(pgv_ctx * ctx, int dim,
+											 int q_nnz, const int32_t *q_idx, const float *q_val,
+											 const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+											 double *out);
+
+/*
+ * `ORDER BY emb <op> $1 LIMIT k` over a sparsevec column without an index, for a BATCH of queries: one
+ * sparsevec_l2_distance / sparsevec_negative_inner_product / sparsevec_l1_distance call per heap row (the merge loops
+ * of src/sparsevec.c:826-869, :905-936, :1018-1060) feeding the executor's top-N sort.  nq queries (q_ptr [nq + 1],
+ * q_idx, q_val) against the same n rows: out_dist [nq x k] ascending kernel values (pgv_sparse_distance_batch's, bit for
+ * bit: the same kernel), out_idx [nq x k] row indexes, ties by lower index (pgv_exact_topk's rule); entries beyond n are
+ * +inf / -1.  1 <= k <= 4096, n <= 2^32.  The queries are served in chunks of min(nq, max(1, 2^30 / n)), so that a
+ * chunk's distance matrix stays at or under 2^30 floats (the environment variable PGV_SPARSE_MATRIX_FLOATS, read at
+ * every call, replaces the 2^30: tests reach the split with it).  For cosine the caller passes normalised vectors with
+ * PGV_NEG_IP, as elsewhere in this ABI.
+ */
+int			pgv_sparse_topk(pgv_ctx * ctx, pgv_metric metric, int dim,
+							const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq,
+							const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+							int k, float *out_dist, int64_t *out_idx);
+
 /* ----------------------------------- IVFFlat over bit strings (bit_hamming_ops) */
 
 /*

@@ -48,7 +48,7 @@ SYMBOLS = [
     "pgv_hnsw_upload_payload", "pgv_hnsw_get_payload", "pgv_builder_begin", "pgv_builder_add", "pgv_builder_set_centers", "pgv_builder_rows", "pgv_builder_finish", "pgv_builder_free", "pgv_index_drain",
     "pgv_index_set_overlap", "pgv_index_shadow_cast", "pgv_bit_topk", "pgv_binary_quantize", "pgv_rerank",
     "pgv_hnsw_upload_bits", "pgv_index_upload_bits", "pgv_index_nbits", "pgv_bit_assign", "pgv_bit_kmeans",
-    "pgv_bit_lloyd_step",
+    "pgv_bit_lloyd_step", "pgv_sparse_distance_batch", "pgv_sparse_cosine_distance_batch", "pgv_sparse_topk",
 ]
 
 
@@ -183,6 +183,9 @@ def _load():
     lib.pgv_bit_assign.argtypes = [P, I, P, I, P, I64, P, P]
     lib.pgv_bit_kmeans.argtypes = [P, I, P, I, I, I, C.POINTER(PgvRng), P, P, C.POINTER(I)]
     lib.pgv_bit_lloyd_step.argtypes = [P, I, P, I, P, I, P, C.POINTER(PgvRng), P, P, P]
+    lib.pgv_sparse_distance_batch.argtypes = [P, I, I, I, P, P, P, P, P, I64, P]
+    lib.pgv_sparse_cosine_distance_batch.argtypes = [P, I, I, P, P, P, P, P, I64, P]
+    lib.pgv_sparse_topk.argtypes = [P, I, I, P, P, P, I, P, P, P, I64, I, P, P]
     lib.pgv_hnsw_set_graph.argtypes = [P, I, C.c_int32, P, P, P]
     lib.pgv_hnsw_search.argtypes = [P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_build_search.argtypes = [P, P, P, I, I, I, P, P, P]

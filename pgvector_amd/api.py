@@ -543,6 +543,59 @@ def bit_topk(ctx, nbits, queries, rows, k, out=None):
     return dist, idx
 
 
+_CSR_DTYPES = (np.int64, np.int32, np.float32)
+
+
+def _csr(triple):
+    """a CSR triple (ptr [n + 1], idx [ptr[n]], val [ptr[n]]) as the ABI reads it: int64, int32, float32.  Host arrays are
+    converted; tensors must already have those element types"""
+    out = []
+    for x, dt in zip(triple, _CSR_DTYPES):
+        if _is_torch(x):
+            assert str(x.dtype) == "torch." + np.dtype(dt).name, "CSR tensors: int64 ptr, int32 idx, float32 val"
+            out.append(x.contiguous())
+        else:
+            out.append(np.ascontiguousarray(x, dtype=dt))
+    return out
+
+
+def sparse_distance_batch(ctx, metric, dim, query, rows):
+    """pgv_sparse_distance_batch: one sparse query (idx [nnz], val [nnz]) against CSR rows (ptr, idx, val) -> [n] float32
+    kernel values (L2 squared / negative inner product / L1), living where the rows' values live"""
+    _, q_idx, q_val = _csr((np.zeros(1, dtype=np.int64),) + tuple(query))
+    r_ptr, r_idx, r_val = _csr(rows)
+    n = int(r_ptr.shape[0]) - 1
+    out = _empty_like_kind(r_val, (n,), np.float32)
+    check(lib.pgv_sparse_distance_batch(ctx.h, metric, int(dim), int(q_idx.shape[0]), ptr(q_idx), ptr(q_val), ptr(r_ptr),
+                                        ptr(r_idx), ptr(r_val), n, ptr(out)))
+    return out
+
+
+def sparse_cosine_distance_batch(ctx, dim, query, rows):
+    """pgv_sparse_cosine_distance_batch: cosine_distance of one sparse query against CSR rows, float8 like the operator"""
+    _, q_idx, q_val = _csr((np.zeros(1, dtype=np.int64),) + tuple(query))
+    r_ptr, r_idx, r_val = _csr(rows)
+    n = int(r_ptr.shape[0]) - 1
+    out = _empty_like_kind(r_val, (n,), np.float64)
+    check(lib.pgv_sparse_cosine_distance_batch(ctx.h, int(dim), int(q_idx.shape[0]), ptr(q_idx), ptr(q_val), ptr(r_ptr),
+                                               ptr(r_idx), ptr(r_val), n, ptr(out)))
+    return out
+
+
+def sparse_topk(ctx, metric, dim, queries, rows, k, out=None):
+    """pgv_sparse_topk: the index-less `ORDER BY <op> LIMIT k` over sparsevec for a batch: CSR queries and CSR rows
+    (ptr, idx, val) -> (dist [nq x k] float32, idx [nq x k] int64), ties to the lower row, living where the queries'
+    values live"""
+    q_ptr, q_idx, q_val = _csr(queries)
+    r_ptr, r_idx, r_val = _csr(rows)
+    nq, n = int(q_ptr.shape[0]) - 1, int(r_ptr.shape[0]) - 1
+    dist, idx = out if out is not None else (_empty_like_kind(q_val, (nq, k), np.float32),
+                                            _empty_like_kind(q_val, (nq, k), np.int64))
+    check(lib.pgv_sparse_topk(ctx.h, metric, int(dim), ptr(q_ptr), ptr(q_idx), ptr(q_val), nq, ptr(r_ptr), ptr(r_idx),
+                              ptr(r_val), n, int(k), ptr(dist), ptr(idx)))
+    return dist, idx
+
+
 def binary_quantize(ctx, dtype, dim, rows):
     """pgv_binary_quantize: rows [n x dim] -> packed bits [n x (dim + 7) // 8] uint8, bit i = rows[:, i] > 0, first element
     in the top bit of byte 0 (np.packbits' order)"""

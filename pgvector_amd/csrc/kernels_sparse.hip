@@ -1,0 +1,323 @@
+// kernels_sparse.hip -- the sparsevec distances on the device: every distance the reference computes as a scalar,
+// branchy merge of two sorted index lists,
+//   SparsevecL2SquaredDistance   src/sparsevec.c:826-869     (`<->` before its float8 sqrt)
+//   SparsevecInnerProduct        src/sparsevec.c:905-936     (`<#>`: negated, :958-966)
+//   sparsevec_cosine_distance    src/sparsevec.c:972-1011    (`<=>`)
+//   sparsevec_l1_distance        src/sparsevec.c:1018-1060   (`<+>`)
+// for a tile of queries against a block of rows, both in CSR (sorted 0-based int32 indices, then float values: what a
+// SparseVector datum stores, src/sparsevec.h:22-47).  One kernel, sparse_tile_kernel<MODE>, serves pgv_sparse_topk's
+// distance matrix (mat[q * n + row], then launch_topk_segments), pgv_sparse_distance_batch (a tile of one query, out[row])
+// and pgv_sparse_cosine_distance_batch (MODE 3, float8 out).
+//
+// The arithmetic.  Every value is an fp32 sum of exactly the terms the reference adds, each computed
+// the way the reference computes it -- (a - b)^2 on a shared index and a^2, b^2 on an index only one side stores (L2),
+// a * b on shared indices only (inner product), |a - b|, |a|, |b| (L1), a^2 / b^2 for the cosine norms -- and only the
+// ORDER of the additions differs from the reference's index order: lane l of a wavefront adds elements l, l + 64, ..
+// of the row, then the unmatched elements l, l + 64, .. of the query, and a 64-lane butterfly finishes the pair.  No
+// |a|^2 + |b|^2 - 2ab expansion and no "total minus matched" shortcut, so a vector's L2 / L1 distance to itself is
+// exactly 0 and integer-valued data gives the reference's bits.  The order depends on the pair alone, never on the
+// tile, the grid or the entry point: pgv_sparse_topk's heads equal pgv_sparse_distance_batch's values bit for bit.
+//
+// The shape.
+//   * a workgroup (4 wavefronts) stages its query tile in LDS once, as (index, value) pairs -- a tile is a run of
+//     consecutive queries planned on the host (sparse_plan_tiles): as many as fit kSparseTileNnz = 2048 stored
+//     elements (16 KB: eight workgroups, the CU's 32 wavefronts, share its 160 KiB; tiles of 4096, five workgroups a CU,
+//     measured 1.7 x slower at 1024 queries, profiles/r21_sparse_topk.md) and at most kSparseTileQueries = 128; a
+//     query with more stored elements than that is a tile of its own, up to the reference's 16 000 (128 000 bytes plus
+//     8 000 of bitmaps: the raised dynamic-LDS attribute, one workgroup per CU)
+//   * each wavefront takes rows of the workgroup's row block (row, row + 4, ..); lanes stride the row's stored
+//     elements and binary-search the query's indices in LDS (a branch-free descent whose trip count depends on the
+//     query's length alone, so no lane diverges; each step reads the pair, and the last element not above the row's
+//     index is kept, so a match and its value are known when the descent ends).  Rows of at most 256 stored elements (kSparseRegChunks chunks of 64)
+//     are read from HBM once per TILE and stay in registers across the tile's queries, and their up to four searches
+//     per lane descend together; longer rows are read again per query, from the caches, one search after the other
+//   * the query-side unmatched terms of L2 and L1 come from a per-wavefront matched bitmap in LDS: cleared, set by
+//     the lanes that find their index (LDS atomic or), then swept by the lanes striding the query.  The inner product
+//     and the cosine need no bitmap (an index only one side stores adds nothing); the cosine's query norm is summed
+//     once per wavefront, not once per row
+// HBM traffic per batch: the row CSR (8 bytes per stored element, plus the row pointers) is read once per query TILE,
+// i.e. ceil(sum of query nnz / 2048) times at least and nq / 128 times at least; consecutive workgroups share a row
+// block and differ in the tile, so the re-reads of a block mostly hit the caches.  The query CSR is read once per
+// (tile, row block).
+//
+// Not here (include/pgv_hip.h says the same): HNSW over sparse elements (hnsw_sparsevec_support, HNSW_MAX_NNZ 1000,
+// src/hnswutils.c:1361-1430) -- the follow-up on top of this kernel --, a device-side sparsevec_l2_normalize, ext/ glue;
+// bench.py does not measure any of this (tools/bench_sparse_topk.py does).
+#include "pgv_device.h"
+
+namespace pgv {
+
+namespace {
+
+constexpr int kSpThreads = 256;
+constexpr int kSpWaves = kSpThreads / kWave;
+constexpr int kSparseTileNnz = 2048;     // stored query elements a shared tile holds at most
+constexpr int kSparseTileQueries = 128;  // queries of a tile at most
+constexpr int kSparseRegChunks = 4;      // a row of up to 4 x 64 stored elements stays in registers
+static_assert(kSparseRegChunks == 4, "sparse_tile_kernel instantiates row_side_reg for 1 .. 4 chunks");
+constexpr int kSparseMaxNnz = 16000;     // SPARSEVEC_MAX_NNZ (src/sparsevec.h)
+
+__host__ __device__ constexpr int pad4(int x) { return (x + 3) & ~3; }
+__host__ __device__ constexpr int bitmap_words(int nnz) { return pad4((nnz + 31) / 32); }
+
+// LDS ordering inside ONE wavefront (bitmap clear -> set -> sweep): the wavefront's LDS operations complete in order,
+// the fence keeps the compiler from moving them across and waits for the ones in flight
+__device__ __forceinline__ void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// A query element in LDS: index and value side by side, so that one 8-byte read of the search brings both
+struct alignas(8) QElem {
+    int32_t i;
+    float v;
+};
+typedef int QPair __attribute__((ext_vector_type(2)));
+
+// Where index x stands among the n ascending indices at q: a descent by powers of two, `top` the largest one <= n (0 for
+// n = 0), so every lane makes the same trips.  pos counts the elements <= x and `last` is the last of them (index -1: none);
+// the query stores x iff last.i == x, at pos - 1, with last.v its value: nothing is read after the descent
+struct Found {
+    int pos;
+    QElem last;
+    __device__ __forceinline__ bool hit(int32_t x) const { return last.i == x; }
+};
+__device__ __forceinline__ void descend(Found &f, const QElem *q, int n, int s, int32_t x) {
+    const int t = f.pos + s;
+    // one 8-byte LDS read, made whether or not the step counts: never predicated
+    const QPair raw = *reinterpret_cast<const QPair *>(q + ((t <= n ? t : n) - 1));
+    const QElem e{raw.x, __int_as_float(raw.y)};
+    if (t <= n && e.i <= x) {
+        f.pos = t;
+        f.last = e;
+    }
+}
+
+// One stored row element against the query: its term into a0 (a1: the row's squared norm, cosine).  MODE 0: L2 squared,
+// 1: inner product, 2: L1, 3: cosine.  hit: the query stores the index too, at pos
+template <int MODE>
+__device__ __forceinline__ void add_term(const Found &f, int32_t ri, float rv, uint32_t *bm, float &a0, float &a1) {
+    const bool hit = f.hit(ri);
+    // an index the query does not store: (rv - 0)^2 = rv^2 and |rv - 0| = |rv|, the reference's own terms
+    const float b = hit ? f.last.v : 0.f;
+    if ((MODE == 0 || MODE == 2) && hit) atomicOr(&bm[(f.pos - 1) >> 5], 1u << ((f.pos - 1) & 31));
+    if (MODE == 0) {
+        const float d = rv - b;
+        a0 = __builtin_fmaf(d, d, a0);
+    } else if (MODE == 2) {
+        a0 += fabsf(rv - b);
+    } else {
+        if (hit) a0 = __builtin_fmaf(rv, b, a0);
+        if (MODE == 3) a1 = __builtin_fmaf(rv, rv, a1);
+    }
+}
+
+// A row of up to kSparseRegChunks x 64 stored elements, read once and kept across the tile's queries: lane l holds
+// elements l, l + 64, ..  Its NC = ceil(rn / 64) searches descend TOGETHER, so that NC LDS reads are in flight per step
+// instead of one (1.2 x at the learned-sparse shape against one search after the other, profiles/r21_sparse_topk.md)
+struct RegRow {
+    int32_t i[kSparseRegChunks];
+    float v[kSparseRegChunks];
+};
+template <int MODE, int NC>
+__device__ __forceinline__ void row_side_reg(const RegRow &row, int rn, const QElem *q, int qn, int top, uint32_t *bm,
+                                             int lane, float &a0, float &a1) {
+    Found f[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) f[c] = {0, {-1, 0.f}};
+    for (int s = top; s > 0; s >>= 1) {  // (top > 0 only when qn > 0)
+#pragma unroll
+        for (int c = 0; c < NC; c++) descend(f[c], q, qn, s, row.i[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++)
+        if (c * kWave + lane < rn) add_term<MODE>(f[c], row.i[c], row.v[c], bm, a0, a1);
+}
+// A longer row: read again per query (from the caches), one search after the other
+template <int MODE>
+__device__ __forceinline__ void row_side_mem(const int32_t *ri, const float *rv, int rn, const QElem *q, int qn, int top,
+                                             uint32_t *bm, int lane, float &a0, float &a1) {
+    for (int e = lane; e < rn; e += kWave) {
+        const int32_t x = ri[e];
+        Found f{0, {-1, 0.f}};
+        for (int s = top; s > 0; s >>= 1) descend(f, q, qn, s, x);
+        add_term<MODE>(f, x, rv[e], bm, a0, a1);
+    }
+}
+
+// One (row, query) pair, this lane's share: row_side(top) adds the row's elements, then the query's unmatched ones (L2,
+// L1) come from the wavefront's bitmap.  q: the query's qn elements in LDS
+template <int MODE, typename RowSide>
+__device__ __forceinline__ void score_pair(RowSide row_side, const QElem *q, int qn, uint32_t *bm, int lane, float &a0) {
+    constexpr bool kBitmap = MODE == 0 || MODE == 2;
+    if (kBitmap) {
+        for (int w = lane; w < (qn + 31) / 32; w += kWave) bm[w] = 0u;
+        wave_lds_fence();
+    }
+    row_side(qn > 0 ? 1 << (31 - __clz(qn)) : 0);
+    if (kBitmap) {
+        wave_lds_fence();
+        for (int j = lane; j < qn; j += kWave) {
+            if (!((bm[j >> 5] >> (j & 31)) & 1u)) {
+                const float a = q[j].v;
+                if (MODE == 0)
+                    a0 = __builtin_fmaf(a, a, a0);
+                else
+                    a0 += fabsf(a);
+            }
+        }
+        wave_lds_fence();  // the sweep has read the bitmap before the next pair clears it
+    }
+}
+
+// grid: (row blocks) x (tiles), consecutive workgroups sharing a row block.  out: float mat[(q - 0) * out_stride + row]
+// for MODE 0..2 (q counts through the launch's queries), double out[row] for MODE 3 (one query)
+template <int MODE>
+__global__ __launch_bounds__(kSpThreads) void sparse_tile_kernel(
+    const SparseTile *__restrict__ tiles, int ntiles, const int64_t *__restrict__ q_ptr, const int32_t *__restrict__ q_idx,
+    const float *__restrict__ q_val, const int64_t *__restrict__ r_ptr, const int32_t *__restrict__ r_idx,
+    const float *__restrict__ r_val, int64_t n, int rows_per_block, int bm_words, void *__restrict__ out_v,
+    int64_t out_stride) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const SparseTile t = tiles[blockIdx.x % (unsigned)ntiles];
+    const int64_t row0 = (int64_t)(blockIdx.x / (unsigned)ntiles) * rows_per_block;
+    const int64_t row_end = row0 + rows_per_block < n ? row0 + rows_per_block : n;
+
+    // LDS: elem[pad4(nnz)] (index, value) | off[pad4(nq + 1)] | bitmap[waves x bm_words]
+    QElem *s_elem = reinterpret_cast<QElem *>(smem);
+    int32_t *s_off = reinterpret_cast<int32_t *>(s_elem + pad4(t.nnz));
+    uint32_t *bm = reinterpret_cast<uint32_t *>(s_off + pad4(t.nq + 1)) + wave * bm_words;
+    for (int i = tid; i < t.nnz; i += kSpThreads) s_elem[i] = {q_idx[t.elem0 + i], q_val[t.elem0 + i]};
+    for (int i = tid; i <= t.nq; i += kSpThreads) s_off[i] = (int32_t)(q_ptr[t.q0 + i] - t.elem0);
+    __syncthreads();
+
+    float qnorm = 0.f;  // cosine: the query's squared norm, the same for every row
+    if (MODE == 3) {
+        for (int j = lane; j < s_off[1]; j += kWave) qnorm = __builtin_fmaf(s_elem[j].v, s_elem[j].v, qnorm);
+        qnorm = __shfl(group_sum_to_last(qnorm, 6), kWave - 1, kWave);
+    }
+
+    for (int64_t r = row0 + wave; r < row_end; r += kSpWaves) {
+        const int64_t rb = r_ptr[r];
+        const int rn = (int)(r_ptr[r + 1] - rb);
+        // side(q's elements, top, a0, a1): the row's share of one pair.  The 64 lanes' sums land in the LAST lane (the same
+        // tree for every pair), which stores
+        auto pairs = [&](auto side) {
+            for (int q = 0; q < t.nq; q++) {
+                const int qb = s_off[q], qn = s_off[q + 1] - qb;
+                const QElem *qe = s_elem + qb;
+                float a0 = 0.f, a1 = 0.f;
+                score_pair<MODE>([&](int top) { side(qe, qn, top, a0, a1); }, qe, qn, bm, lane, a0);
+                a0 = group_sum_to_last(a0, 6);
+                if (MODE == 3) {
+                    a1 = group_sum_to_last(a1, 6);
+                    if (lane == kWave - 1) {
+                        // Use sqrt(a * b) over sqrt(a) * sqrt(b), keep in range (src/sparsevec.c:995-1010); NaN (an empty or
+                        // all-zero vector: 0 / 0) passes through both comparisons
+                        double similarity = (double)a0 / sqrt((double)qnorm * (double)a1);
+                        if (similarity > 1.0)
+                            similarity = 1.0;
+                        else if (similarity < -1.0)
+                            similarity = -1.0;
+                        static_cast<double *>(out_v)[r] = 1.0 - similarity;
+                    }
+                } else if (lane == kWave - 1) {
+                    // the negative inner product as 0 - ip: an empty intersection is +0.0 here as it is in the heads the
+                    // selection returns (its keys do not tell the two zeros apart)
+                    static_cast<float *>(out_v)[(size_t)(t.q0 + q) * (size_t)out_stride + (size_t)r] = MODE == 1 ? 0.f - a0 : a0;
+                }
+            }
+        };
+        if (rn <= kSparseRegChunks * kWave) {
+            RegRow row;
+#pragma unroll
+            for (int c = 0; c < kSparseRegChunks; c++) {
+                const bool ok = c * kWave + lane < rn;
+                row.i[c] = ok ? r_idx[rb + c * kWave + lane] : 0;
+                row.v[c] = ok ? r_val[rb + c * kWave + lane] : 0.f;
+            }
+#define PGV_SPARSE_REG(NC)                                                                                        \
+    pairs([&](const QElem *qe, int qn, int top, float &a0, float &a1) {                                           \
+        row_side_reg<MODE, NC>(row, rn, qe, qn, top, bm, lane, a0, a1);                                           \
+    })
+            switch ((rn + kWave - 1) / kWave) {
+                case 0:
+                case 1: PGV_SPARSE_REG(1); break;
+                case 2: PGV_SPARSE_REG(2); break;
+                case 3: PGV_SPARSE_REG(3); break;
+                default: PGV_SPARSE_REG(4); break;
+            }
+#undef PGV_SPARSE_REG
+        } else {
+            pairs([&](const QElem *qe, int qn, int top, float &a0, float &a1) {
+                row_side_mem<MODE>(r_idx + rb, r_val + rb, rn, qe, qn, top, bm, lane, a0, a1);
+            });
+        }
+    }
+}
+
+}  // namespace
+
+int sparse_tile_nnz() { return kSparseTileNnz; }
+int sparse_tile_queries() { return kSparseTileQueries; }
+int sparse_reg_row_nnz() { return kSparseRegChunks * kWave; }
+
+// consecutive queries into tiles: as many as fit kSparseTileNnz stored elements and kSparseTileQueries queries; a longer
+// query alone.  q_ptr: host, monotone, every query within kSparseMaxNnz (the caller has checked)
+void sparse_plan_tiles(const int64_t *q_ptr, int nq, std::vector<SparseTile> *tiles, int *max_q_nnz) {
+    tiles->clear();
+    *max_q_nnz = 0;
+    for (int q = 0; q < nq;) {
+        SparseTile t{q_ptr[q], q, 0, 0, 0};
+        while (q < nq && t.nq < kSparseTileQueries) {
+            const int qn = (int)(q_ptr[q + 1] - q_ptr[q]);
+            if (t.nq > 0 && t.nnz + qn > kSparseTileNnz) break;
+            t.nnz += qn;
+            t.nq++;
+            q++;
+            if (qn > *max_q_nnz) *max_q_nnz = qn;
+        }
+        tiles->push_back(t);
+    }
+}
+
+template <int MODE>
+static int launch_sparse_tiles_t(pgv_ctx *ctx, const SparseTile *tiles_dev, int ntiles, size_t lds, int bm_words,
+                                 const SparseCsr &q, const SparseCsr &r, void *out, int64_t out_stride) {
+    // enough workgroups for every CU to hold several, blocks long enough to amortise staging the tile
+    int64_t rows_per_block = (r.n * ntiles + (int64_t)ctx->num_cus * 16 - 1) / ((int64_t)ctx->num_cus * 16);
+    rows_per_block = (rows_per_block + kSpWaves - 1) / kSpWaves * kSpWaves;
+    if (rows_per_block < 32) rows_per_block = 32;
+    if (rows_per_block > 1024) rows_per_block = 1024;
+    const int64_t grid = (r.n + rows_per_block - 1) / rows_per_block * ntiles;
+    if (grid > 0x7fffffff) PGV_FAIL(PGV_ERR_ARG, "sparse scan: too many tiles");
+    auto kern = sparse_tile_kernel<MODE>;
+    if (lds > 64 * 1024)
+        PGV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kSpThreads), lds, ctx->stream, tiles_dev, ntiles, q.ptr, q.idx, q.val,
+                       r.ptr, r.idx, r.val, r.n, (int)rows_per_block, bm_words, out, out_stride);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_sparse_tiles(pgv_ctx *ctx, int mode, const SparseTile *tiles_dev, int ntiles, int max_tile_nnz, int max_tile_nq,
+                        int max_q_nnz, const SparseCsr &q, const SparseCsr &r, void *out, int64_t out_stride) {
+    if (r.n <= 0 || ntiles <= 0) return PGV_OK;
+    if (max_q_nnz > kSparseMaxNnz || max_tile_nnz > kSparseMaxNnz || max_tile_nq > kSparseTileQueries)
+        PGV_FAIL(PGV_ERR_ARG, "sparse scan: a tile of %d queries / %d elements is over the kernel's limits", max_tile_nq,
+                 max_tile_nnz);
+    const int bm_words = (mode == 0 || mode == 2) ? bitmap_words(max_q_nnz) : 0;
+    const size_t lds = sizeof(int32_t) * ((size_t)2 * pad4(max_tile_nnz) + pad4(max_tile_nq + 1) + (size_t)kSpWaves * bm_words);
+    switch (mode) {
+        case 0: return launch_sparse_tiles_t<0>(ctx, tiles_dev, ntiles, lds, bm_words, q, r, out, out_stride);
+        case 1: return launch_sparse_tiles_t<1>(ctx, tiles_dev, ntiles, lds, bm_words, q, r, out, out_stride);
+        case 2: return launch_sparse_tiles_t<2>(ctx, tiles_dev, ntiles, lds, bm_words, q, r, out, out_stride);
+        case 3:
+            if (ntiles != 1 || max_tile_nq != 1) PGV_FAIL(PGV_ERR_ARG, "sparse cosine: one query");
+            return launch_sparse_tiles_t<3>(ctx, tiles_dev, ntiles, lds, bm_words, q, r, out, out_stride);
+    }
+    PGV_FAIL(PGV_ERR_ARG, "sparse scan: unknown mode %d", mode);
+}
+
+}  // namespace pgv

@@ -534,6 +534,28 @@ int launch_rerank_pairs(pgv_ctx *ctx, const int64_t *cand, int64_t total, int kc
 int launch_rerank_mask(pgv_ctx *ctx, const int64_t *cand, int64_t total, float *vals);
 int launch_rerank_map(pgv_ctx *ctx, const int64_t *cand, int nq, int kc, int k, const int64_t *pos, int64_t *out_idx);
 
+// kernels_sparse.hip: the sparsevec distances of a tile of queries against every row, both CSR on the device
+struct SparseCsr {
+    const int64_t *ptr;  // [n + 1]
+    const int32_t *idx;  // [ptr[n]] ascending inside a vector
+    const float *val;    // [ptr[n]]
+    int64_t n;
+};
+// a run of consecutive queries a workgroup stages in LDS: queries [q0, q0 + nq), their nnz stored elements from elem0
+struct SparseTile {
+    int64_t elem0;
+    int32_t q0, nq, nnz, pad;
+};
+int sparse_tile_nnz();      // stored elements a tile of several queries holds at most (a longer query is its own tile)
+int sparse_tile_queries();  // queries of a tile at most
+int sparse_reg_row_nnz();   // rows up to this many stored elements are read once per tile, longer ones once per query
+// q_ptr: host, validated; the tiles of queries [0, nq) in order and the longest query's stored elements
+void sparse_plan_tiles(const int64_t *q_ptr, int nq, std::vector<SparseTile> *tiles, int *max_q_nnz);
+// mode 0 L2 squared | 1 negative inner product | 2 L1: float out[q * out_stride + row], q counting from q.ptr's first
+// query; mode 3 cosine distance (one tile of one query): double out[row].  max_*: over the tiles, for the LDS size
+int launch_sparse_tiles(pgv_ctx *ctx, int mode, const SparseTile *tiles_dev, int ntiles, int max_tile_nnz, int max_tile_nq,
+                        int max_q_nnz, const SparseCsr &q, const SparseCsr &r, void *out, int64_t out_stride);
+
 // kernels_hnsw.hip: the whole first batch of an HNSW scan, one workgroup per query
 int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out);
 struct HnswSearchArgs {
