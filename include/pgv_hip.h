@@ -192,6 +192,9 @@ typedef struct pgv_stats
 	/* ... and those that a wider candidate set (256 instead of k') did settle, without the exact pass
 	 * (list scan and center ranking alike) */
 	double		scan_widened_queries;
+	/* batches over the fp16 residual shadow: probed (query, list) pairs that were not scanned because every
+	 * row of the list is provably farther than k rows of the lists probed before it (PGV_PROBE_PRUNE) */
+	double		scan_pruned_probes;
 	/* fp32 L2 batches scanned on the matrix cores: queries whose pre-filter read the fp16 residual shadow
 	 * of the index instead of its fp32 rows (counted whether or not profiling is on) */
 	double		scan_shadow_queries;

@@ -64,6 +64,7 @@ class PgvStats(C.Structure):
                 ("scan_pairs", C.c_double), ("scan_rows", C.c_double),
                 ("aux_ms", C.c_double), ("aux_launches", C.c_int64), ("aux_pairs", C.c_double),
                 ("assign_redo_rows", C.c_double), ("assign_rows", C.c_double), ("assign_recheck_rows", C.c_double), ("scan_unique_rows", C.c_double), ("scan_redo_queries", C.c_double), ("scan_widened_queries", C.c_double),
+                ("scan_pruned_probes", C.c_double),
                 ("scan_shadow_queries", C.c_double)]
 
 

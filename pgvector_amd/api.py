@@ -131,7 +131,8 @@ class Context:
                 "aux_ms": s.aux_ms, "aux_launches": s.aux_launches, "aux_pairs": s.aux_pairs,
                 "assign_redo_rows": s.assign_redo_rows, "assign_rows": s.assign_rows,
                 "assign_recheck_rows": s.assign_recheck_rows, "scan_unique_rows": s.scan_unique_rows, "scan_redo_queries": s.scan_redo_queries,
-                "scan_widened_queries": s.scan_widened_queries, "scan_shadow_queries": s.scan_shadow_queries}
+                "scan_widened_queries": s.scan_widened_queries, "scan_pruned_probes": s.scan_pruned_probes,
+                "scan_shadow_queries": s.scan_shadow_queries}
 
 
 class IvfIndex:

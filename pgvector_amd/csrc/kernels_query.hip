@@ -394,6 +394,26 @@ __global__ __launch_bounds__(kQThreads) void mq_head_kernel(
 // unless no row outside the candidates can belong to the head.
 constexpr int kRecheckCap = 256;  // k' <= 256: rank_sort_entries' reach
 
+// Probe pruning (the rule and its proof: pgv_internal.h, beside ScanBound) as the workgroup of one query runs it, called
+// by every thread: the thread of probe j (j < 0: none; !live: a fill entry, no list) brings the probe's exact center
+// distance d and its list's radius r, lens[0 .. n) hold the probed lists' rows in probe order (written before the call,
+// 0 for a fill entry), near[n] is scratch.  Returns
+// 2 * (probes dropped in the workgroup) + (this thread's probe is dropped)
+__device__ __forceinline__ int probe_prune_step(const int64_t *lens, double *near, int n, int j, bool live, float d, float r,
+                                                int need, int ld) {
+    const ProbeMargins pm = probe_margins(ld);
+    if (j >= 0) near[j] = live ? probe_near(d, r, pm) : 0.0;
+    __syncthreads();
+    const bool drop = j >= 0 && live && probe_dropped(lens, near, n, j, need, probe_far(d, r, pm), pm);
+    return 2 * __syncthreads_count(drop) + (drop ? 1 : 0);
+}
+// ... out of line for batch_fix_kernel, whose registers its selection forms fill: inlined twice (both ends of a flagged
+// query), the fp64 square roots and divisions cost it a wave per SIMD
+__device__ __attribute__((noinline)) int probe_prune_step_call(const int64_t *lens, double *near, int n, int j, bool live,
+                                                               float d, float r, int need, int ld) {
+    return probe_prune_step(lens, near, n, j, live, d, r, need, ld);
+}
+
 // DOT (fp32 rows; the center ranking in front of a shadow scan): q.row is accumulated beside the exact distance over the
 // same loads, and the threads that emit the k rows also write t = -2 q.row to pair_t[q * k + rank] -- the pair terms of
 // the list scan that follows, in probe order, for one more accumulator instead of a kernel of 10 240 dot products.
@@ -417,7 +437,9 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     __shared__ __attribute__((aligned(16))) unsigned long long ent[kRecheckCap];
     const int q = blockIdx.x;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    const int64_t m = seg_start ? seg_start[q + 1] - seg_start[q] : fixed_len;  // rows the candidates were picked from
+    // rows the candidates were picked from (DOT: the ranking, always one dense run -- launch_exact_tail checks it -- whose
+    // positions are the slots: the list plan's arguments are not looked at, and cost the instantiation no registers)
+    const int64_t m = (!DOT && seg_start) ? seg_start[q + 1] - seg_start[q] : fixed_len;
     const int ncand = (int)(m < kprime ? m : (int64_t)kprime);
     const int kk = ncand < k ? ncand : k;
     // Only candidates within 2 eps of the k-th approximate value can be in the head: the k smallest-approx rows have
@@ -459,7 +481,8 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     if ((int)threadIdx.x < cnt) {
         const int64_t p = cand_pos[(size_t)q * kprime + threadIdx.x];
         int64_t slot = p;
-        if (cand_slot) {
+        if constexpr (DOT) {
+        } else if (cand_slot) {
             slot = cand_slot[(size_t)q * kprime + threadIdx.x];
         } else {
             const int64_t *off = probe_off + (size_t)q * probes;
@@ -506,27 +529,45 @@ __global__ __launch_bounds__(kQThreads) void batch_recheck_kernel(
     if ((int)threadIdx.x < cnt && rank < k) {
         const size_t o = (size_t)q * k + rank;
         out_dist[o] = key_to_float((unsigned)(mine >> 32));
-        if (out_slot) out_slot[o] = my_slot;
+        if constexpr (!DOT) {
+            if (out_slot) out_slot[o] = my_slot;
+            if (out_tid) out_tid[o] = tids ? tids[my_slot] : ~0ull;
+        }
         if (out_i32) out_i32[o] = (int32_t)my_slot;
-        if (out_tid) out_tid[o] = tids ? tids[my_slot] : ~0ull;
         if constexpr (DOT) pair_t[o] = -2.f * dots[threadIdx.x];
     }
     if ((int)threadIdx.x >= kk && (int)threadIdx.x < k) {  // fewer tuples than the head asked for
         const size_t o = (size_t)q * k + threadIdx.x;
         out_dist[o] = INFINITY;
-        if (out_slot) out_slot[o] = -1;
+        if constexpr (!DOT) {
+            if (out_slot) out_slot[o] = -1;
+            if (out_tid) out_tid[o] = ~0ull;
+        }
         if (out_i32) out_i32[o] = -1;
-        if (out_tid) out_tid[o] = ~0ull;
         if constexpr (DOT) pair_t[o] = 0.f;
     }
     if constexpr (DOT) {
         if (emit.cnt) {  // (block-uniform; k <= kRecheckCap)
-            __syncthreads();  // every thread has read its slot and ranked itself: slots[] is free
-            if ((int)threadIdx.x < cnt && rank < k) {
-                atomicAdd(&emit.cnt[my_slot], 1);
-                slots[rank] = emit.list_off[my_slot + 1] - emit.list_off[my_slot];
+            __syncthreads();  // every thread has read its slot and ranked itself: slots[] and ent[] are free
+            const bool emits = (int)threadIdx.x < cnt && rank < k;
+            const bool fills = (int)threadIdx.x >= kk && (int)threadIdx.x < k;  // (a fill entry: no rows, near side 0)
+            if (emits) slots[rank] = emit.list_off[my_slot + 1] - emit.list_off[my_slot];
+            if (fills) slots[threadIdx.x] = 0;
+            bool drop = false;
+            if (emit.radius) {  // (block-uniform) probe pruning, by the threads that emit
+                const int res = probe_prune_step(slots, reinterpret_cast<double *>(ent), k,
+                                                 emits ? rank : (fills ? (int)threadIdx.x : -1), emits,
+                                                 key_to_float((unsigned)(mine >> 32)), emits ? emit.radius[my_slot] : 0.f,
+                                                 emit.need, nvec * 4);
+                drop = (res & 1) != 0;  // (every thread has read the lengths it needs: a barrier lies behind them)
+                if (drop) {
+                    const size_t o = (size_t)q * k + rank;
+                    slots[rank] = 0;
+                    out_i32[o] = -1;
+                    pair_t[o] = 0.f;
+                }
             }
-            if ((int)threadIdx.x >= kk && (int)threadIdx.x < k) slots[threadIdx.x] = 0;
+            if (emits && !drop) atomicAdd(&emit.cnt[my_slot], 1);
             __syncthreads();
             if ((int)threadIdx.x < k) {
                 int64_t run = 0;
@@ -607,12 +648,27 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
                     fill_pair_terms(vectors, row_bytes, qrow, nvec * 4, out_i32 ? out_i32 + (size_t)q * k : nullptr,
                                     out_slot ? out_slot + (size_t)q * k : nullptr, k, pair_t + (size_t)q * k);
                     if (emit.cnt) {  // the new row's lists into the plan (slots[] is free: a barrier lies behind its readers)
-                        if ((int)threadIdx.x < k) {
-                            const int l = __hip_atomic_load(out_i32 + (size_t)q * k + threadIdx.x, __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_AGENT);
-                            if (l >= 0) atomicAdd(&emit.cnt[l], 1);
+                        // (ent[] is free as well: probe_prune_step's scratch, as in batch_recheck_kernel's emit)
+                        const bool mine_k = (int)threadIdx.x < k;
+                        const size_t o = (size_t)q * k + threadIdx.x;
+                        int l = -1;
+                        if (mine_k) {
+                            l = __hip_atomic_load(out_i32 + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             slots[threadIdx.x] = l >= 0 ? emit.list_off[l + 1] - emit.list_off[l] : 0;
                         }
+                        if (emit.radius) {  // (block-uniform) probe pruning of the new row
+                            const int res = probe_prune_step_call(
+                                slots, reinterpret_cast<double *>(ent), k, mine_k ? (int)threadIdx.x : -1, l >= 0,
+                                mine_k ? __hip_atomic_load(out_dist + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f,
+                                l >= 0 ? emit.radius[l] : 0.f, emit.need, nvec * 4);
+                            if (res & 1) {  // (every thread has read the lengths it needs: a barrier lies behind them)
+                                slots[threadIdx.x] = 0;
+                                out_i32[o] = -1;
+                                pair_t[o] = 0.f;
+                                l = -1;
+                            }
+                        }
+                        if (mine_k && l >= 0) atomicAdd(&emit.cnt[l], 1);
                         __syncthreads();
                         if ((int)threadIdx.x < k) {
                             int64_t run = 0;
@@ -718,6 +774,40 @@ __global__ __launch_bounds__(kQThreads) void batch_fix_kernel(
         }
         pair_terms();
         __syncthreads();  // ent / sel are reused by the next flagged query
+    }
+}
+
+// Probe pruning for probe lists that were GIVEN (pgv_scan_batch over the row shadow; pgv_internal.h, beside ScanBound): one
+// workgroup per query, in front of the plan, does for the query's lists what the ranking's recheck does for the lists it
+// emits -- the exact center distances and q.c_l by the same score_rows_dot (the same bits), the rule by the same
+// probe_dropped -- and leaves the lists with the dropped ones as -1 and every pair's t = -2 q.c_l (0 where there is no
+// list).  A list id < 0 in the input is a fill entry: no rows, nothing to drop.  probes <= kRecheckCap
+static_assert(kRecheckCap <= kQThreads, "a thread per probe");
+__global__ __launch_bounds__(kQThreads) void probe_prune_kernel(
+    const char *__restrict__ centers, const float *__restrict__ radius, const int64_t *__restrict__ list_off, int nvec,
+    int lg, const char *__restrict__ queries, const int32_t *__restrict__ probe_lists, int probes, int need,
+    int32_t *__restrict__ out_lists, float *__restrict__ pair_t) {
+    __shared__ float exact[kRecheckCap], dots[kRecheckCap];
+    __shared__ int64_t lens[kRecheckCap];
+    __shared__ double near[kRecheckCap];
+    __shared__ int32_t lists[kRecheckCap];
+    const int q = blockIdx.x;
+    const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
+    const bool mine = (int)threadIdx.x < probes;
+    if (mine) lists[threadIdx.x] = probe_lists[(size_t)q * probes + threadIdx.x];
+    __syncthreads();
+    score_rows_dot([&](int64_t j) { return centers + (size_t)(lists[j] < 0 ? 0 : lists[j]) * row_bytes; }, 0, probes,
+                   queries + (size_t)q * row_bytes, nvec, lg, exact, dots);
+    __syncthreads();
+    const int l = mine ? lists[threadIdx.x] : -1;
+    if (mine) lens[threadIdx.x] = l >= 0 ? list_off[l + 1] - list_off[l] : 0;
+    const int res = probe_prune_step(lens, near, probes, mine ? (int)threadIdx.x : -1, l >= 0, mine ? exact[threadIdx.x] : 0.f,
+                                     l >= 0 ? radius[l] : 0.f, need, nvec * 4);
+    const bool drop = (res & 1) != 0;
+    if (mine) {
+        const size_t o = (size_t)q * probes + threadIdx.x;
+        out_lists[o] = drop ? -1 : l;
+        pair_t[o] = (drop || l < 0) ? 0.f : -2.f * dots[threadIdx.x];
     }
 }
 
@@ -908,6 +998,20 @@ int launch_multi_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int 
     return PGV_OK;
 }
 
+int probe_prune_max_probes() { return kRecheckCap; }
+
+int launch_probe_prune(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
+                       int need, int32_t *out_lists, float *pair_t) {
+    if (nq <= 0) return PGV_OK;
+    if (probes < 1 || probes > kRecheckCap || !ix->list_radius || ix->dtype != PGV_F32)
+        PGV_FAIL(PGV_ERR_ARG, "probe pruning: fp32 rows with list radii, 1..%d probes", kRecheckCap);
+    hipLaunchKernelGGL(probe_prune_kernel, dim3(nq), dim3(kQThreads), 0, ctx->stream, static_cast<const char *>(ix->centers),
+                       ix->list_radius, ix->list_offsets, ix->geom.nvec, ix->geom.lpr_log2, static_cast<const char *>(q_dev),
+                       probe_lists, probes, need, out_lists, pair_t);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
 namespace {
 struct ApproxScratch {  // the tail's candidates and flags, carved from the caller's buffer
     float *cand_val = nullptr;   // [nq x kprime] approximate values, ascending
@@ -934,7 +1038,8 @@ int launch_exact_tail(pgv_ctx *ctx, const ExactTail &t, DBuf &scratch) {
         PGV_FAIL(PGV_ERR_ARG, "exact tail: a list plan or one dense run");
     if (t.kprime > kRecheckCap || t.k > t.kprime)
         PGV_FAIL(PGV_ERR_ARG, "exact tail: k' = %d outside k..%d", t.kprime, kRecheckCap);
-    if (t.pair_t && xr.dtype != PGV_F32) PGV_FAIL(PGV_ERR_ARG, "exact tail: pair terms are for fp32 rows");
+    if (t.pair_t && (xr.dtype != PGV_F32 || !dense || t.out_slot || t.out_tid || !t.out_i32))
+        PGV_FAIL(PGV_ERR_ARG, "exact tail: pair terms are for one dense run of fp32 rows whose slots leave as int32");
     static_assert(kWide >= kRecheckCap, "k <= k' <= kWide: batch_fix_kernel's emit");
     if (t.emit.cnt && !(dense && t.pair_t && t.out_i32 && t.emit.probe_off && t.emit.seg_len && t.emit.list_off))
         PGV_FAIL(PGV_ERR_ARG, "exact tail: the plan is counted where the pair terms are written");

@@ -28,6 +28,7 @@ __global__ void plan_count_kernel(const int32_t *__restrict__ probe_lists,
     for (int p = 0; p < probes; p++) {
         const int l = probe_lists[(size_t)q * probes + p];
         probe_off[(size_t)q * probes + p] = run;
+        if (l < 0) continue;  // a dropped probe (probe pruning): no rows, no pair
         run += list_off[l + 1] - list_off[l];
         atomicAdd(&cnt[l], 1);
     }
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(1024) void plan_scan_kernel(
     const int64_t *__restrict__ seg_len, int nq, int nlists, int qt, int rows_per_task,
     int64_t *__restrict__ seg_start, int64_t *__restrict__ pair_start,
     int64_t *__restrict__ task_start, int64_t *__restrict__ totals /*[2]: out elems, tasks*/,
-    double *__restrict__ acc) {
+    double *__restrict__ acc, int64_t given /*probes handed to the plan: those without a list (-1) were pruned*/) {
     __shared__ int64_t scratch[1024 / 64 + 1];
     __shared__ double red[2][1024 / 64];
     block_exclusive_scan(nq, [&](int i) { return seg_len[i]; }, seg_start, scratch);
@@ -116,6 +117,7 @@ __global__ __launch_bounds__(1024) void plan_scan_kernel(
             acc[0] += (double)seg_start[nq];  // (row, query) pairs
             acc[1] += r;                      // rows streamed
             acc[5] += u;                      // rows of the lists at least one query probes
+            acc[8] += (double)(given - pair_start[nlists]);  // probes that probe pruning dropped
         }
     }
 }
@@ -130,6 +132,7 @@ __device__ __forceinline__ void plan_pairs_body(int64_t i, const int32_t *__rest
     if (i >= (int64_t)nq * probes) return;
     const int q = (int)(i / probes);
     const int l = probe_lists[i];
+    if (l < 0) return;  // a dropped probe (probe pruning): it was not counted either
     const int64_t pos = pair_start[l] + atomicAdd(&fill[l], 1);
     ScanPair pr;
     pr.out_rel = seg_start[q] + probe_off[i] - list_off[l];
@@ -331,7 +334,8 @@ __global__ void iota_slots_kernel(const int32_t *__restrict__ lists,
 __global__ __launch_bounds__(256) void plan_stats_kernel(const int *__restrict__ cnt,
                                                          const int64_t *__restrict__ list_off,
                                                          const int64_t *__restrict__ totals, int nlists,
-                                                         int qt, double *__restrict__ acc) {
+                                                         int qt, double *__restrict__ acc,
+                                                         const int64_t *__restrict__ pair_start, int64_t given) {
     __shared__ double red[256], red_u[256];
     double rows = 0.0, uniq = 0.0;
     for (int l = threadIdx.x; l < nlists; l += 256) {
@@ -353,6 +357,7 @@ __global__ __launch_bounds__(256) void plan_stats_kernel(const int *__restrict__
         acc[0] += (double)totals[0];  // (row, query) pairs
         acc[1] += red[0];             // rows streamed
         acc[5] += red_u[0];           // rows of the lists at least one query probes (what one pass would stream)
+        acc[8] += (double)(given - pair_start[nlists]);  // probes handed to the plan without a list: pruned
     }
 }
 
@@ -469,11 +474,11 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
         // and the pairs and tasks in one grid.
         double *acc = nullptr;
         if (read_totals) {
-            PGV_TRY(ctx->stats_dev.ensure(8 * sizeof(double)));
+            PGV_TRY(ctx->stats_dev.ensure(pgv::kStatsWords * sizeof(double)));
             acc = ctx->stats_dev.as<double>();
         }
         hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt, ix->list_offsets, seg_len, nq, nlists,
-                           qt, rows_per_task, seg_start, pair_start, task_start, totals, acc);
+                           qt, rows_per_task, seg_start, pair_start, task_start, totals, acc, (int64_t)npairs);
         hipLaunchKernelGGL(plan_pairs_tasks_kernel, dim3(pair_blocks + task_blocks), dim3(256), 0, ctx->stream, probe_lists,
                            ix->list_offsets, probe_off, seg_start, pair_start, task_start, cnt, fill, nq, probes, nlists, qt,
                            rows_per_task, pair_t, (int)pair_blocks, ctx->pairs.as<ScanPair>(), tasks);
@@ -484,7 +489,7 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
                            probe_lists, ix->list_offsets, nq, probes, cnt, probe_off, seg_len);
         hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, cnt,
                            ix->list_offsets, seg_len, nq, nlists, qt, rows_per_task, seg_start,
-                           pair_start, task_start, totals, static_cast<double *>(nullptr));
+                           pair_start, task_start, totals, static_cast<double *>(nullptr), (int64_t)npairs);
         hipLaunchKernelGGL(plan_pairs_kernel, dim3(pair_blocks), dim3(256), 0,
                            ctx->stream, probe_lists, ix->list_offsets, probe_off, seg_start,
                            pair_start, fill, nq, probes, pair_t, ctx->pairs.as<ScanPair>());
@@ -492,9 +497,10 @@ int launch_plan_batch(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_li
                            ctx->stream, cnt, ix->list_offsets, pair_start, task_start, nlists, qt, rows_per_task, tasks);
         PGV_HIP(hipGetLastError());
         if (read_totals) {  // profiling: exact pair / streamed-row counts, accumulated on the device
-            PGV_TRY(ctx->stats_dev.ensure(8 * sizeof(double)));
+            PGV_TRY(ctx->stats_dev.ensure(pgv::kStatsWords * sizeof(double)));
             hipLaunchKernelGGL(plan_stats_kernel, dim3(1), dim3(256), 0, ctx->stream, cnt,
-                               ix->list_offsets, totals, nlists, qt, ctx->stats_dev.as<double>());
+                               ix->list_offsets, totals, nlists, qt, ctx->stats_dev.as<double>(), pair_start,
+                               (int64_t)npairs);
             PGV_HIP(hipGetLastError());
         }
     }

@@ -73,23 +73,27 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
                                                            const int64_t *__restrict__ list_off, int nlists, int64_t n,
                                                            int ld, int ld16, const unsigned *__restrict__ max_bits,
                                                            __half *__restrict__ shadow,
-                                                           unsigned long long *__restrict__ ep_bits) {
+                                                           unsigned long long *__restrict__ ep_bits,
+                                                           unsigned long long *__restrict__ radius_bits) {
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n) return;
     const int lane = threadIdx.x & (kWave - 1);
     const int s = scale_for(__uint_as_float(*max_bits));
     const float *x = rows + (size_t)r * ld;
-    const float *c = centers ? centers + (size_t)list_of_row(list_off, nlists, r) * ld : nullptr;
+    const int list = centers ? list_of_row(list_off, nlists, r) : 0;
+    const float *c = centers ? centers + (size_t)list * ld : nullptr;
     __half *h = shadow + (size_t)r * ld16;
     const double up = ldexp(1.0, s);  // (exact: |s| stays far inside fp64's exponent range)
-    double e2 = 0.0, p2 = 0.0;
+    double e2 = 0.0, p2 = 0.0, r2 = 0.0;  // r2 = |x - c_l|^2: the list's radius (probe pruning, pgv_internal.h)
     for (int i = lane; i < ld16; i += kWave) {
         __half v = __float2half(0.f);
         if (i < ld) {
             const float ci = c ? c[i] : 0.f;
             v = __float2half(ldexpf(x[i] - ci, -s));
             const double back = (double)__half2float(v) * up;
-            const double d = ((double)x[i] - (double)ci) - back;
+            const double rho = (double)x[i] - (double)ci;
+            const double d = rho - back;
+            r2 = fma(rho, rho, r2);
             e2 = fma(d, d, e2);
             p2 = fma(back, back, p2);
         }
@@ -98,6 +102,7 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
     for (int o = 32; o > 0; o >>= 1) {
         e2 += __shfl_xor(e2, o);
         p2 += __shfl_xor(p2, o);
+        r2 += __shfl_xor(r2, o);
     }
     if (lane == 0) {
         // (NaN / inf rows: the host finds a non-finite E or P and drops the shadow).  A million atomics on one word take
@@ -106,6 +111,11 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
                                  pb = (unsigned long long)__double_as_longlong(p2 != p2 ? INFINITY : p2);
         if (eb > __hip_atomic_load(&ep_bits[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&ep_bits[0], eb);
         if (pb > __hip_atomic_load(&ep_bits[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&ep_bits[1], pb);
+        if (radius_bits) {  // one word per list, the same way
+            const unsigned long long rb = (unsigned long long)__double_as_longlong(r2 != r2 ? INFINITY : r2);
+            if (rb > __hip_atomic_load(&radius_bits[list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                atomicMax(&radius_bits[list], rb);
+        }
     }
 }
 
@@ -290,8 +300,10 @@ __global__ __launch_bounds__(256) void shadow_pair_kernel(const float *__restric
 }  // namespace
 
 int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *rows, const void *centers,
-                        const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words) {
+                        const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words, void *radius_bits) {
     if (n <= 0) return PGV_OK;
+    // radius_bits (with centers; or null): [nlists] bits of the largest |x - c_l|^2 (fp64) of each list's rows
+    if (radius_bits) PGV_HIP(hipMemsetAsync(radius_bits, 0, sizeof(unsigned long long) * (size_t)nlists, ctx->stream));
     // (centers null: the rows themselves are cast -- the shadow of an index's centers, E_c and P_c in the same words)
     // words: [0] max |rho_i| bits (u32) | [1..2] E^2, P^2 bits (u64 at byte 8)
     PGV_HIP(hipMemsetAsync(words, 0, 24, ctx->stream));
@@ -301,7 +313,8 @@ int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, co
     hipLaunchKernelGGL(shadow_absmax_kernel, grid, dim3(256), 0, ctx->stream, static_cast<const float *>(rows),
                        static_cast<const float *>(centers), list_off, nlists, n, g32.ld, max_bits);
     hipLaunchKernelGGL(shadow_build_kernel, grid, dim3(256), 0, ctx->stream, static_cast<const float *>(rows),
-                       static_cast<const float *>(centers), list_off, nlists, n, g32.ld, g16.ld, max_bits, static_cast<__half *>(shadow), ep);
+                       static_cast<const float *>(centers), list_off, nlists, n, g32.ld, g16.ld, max_bits, static_cast<__half *>(shadow), ep,
+                       centers ? static_cast<unsigned long long *>(radius_bits) : nullptr);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

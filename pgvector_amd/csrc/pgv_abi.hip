@@ -234,8 +234,8 @@ int pgv_ctx_set_profiling(pgv_ctx *ctx, int on) {
     PGV_TRY(resolve_events(ctx));
     ctx->profiling = on != 0;
     if (ctx->profiling && !ctx->stats_dev.p) {
-        PGV_TRY(ctx->stats_dev.ensure(8 * sizeof(double)));
-        PGV_HIP(hipMemsetAsync(ctx->stats_dev.p, 0, 8 * sizeof(double), ctx->stream));
+        PGV_TRY(ctx->stats_dev.ensure(pgv::kStatsWords * sizeof(double)));
+        PGV_HIP(hipMemsetAsync(ctx->stats_dev.p, 0, pgv::kStatsWords * sizeof(double), ctx->stream));
     }
     for (pgv_ctx *c : ctx->children) PGV_TRY(pgv_ctx_set_profiling(c, on));
     return PGV_OK;
@@ -265,7 +265,7 @@ int pgv_ctx_reset_stats(pgv_ctx *ctx) {
     ctx->scan_launches = 0;
     ctx->scan_pairs = 0;
     ctx->scan_rows = 0;
-    if (ctx->stats_dev.p) PGV_HIP(hipMemsetAsync(ctx->stats_dev.p, 0, 8 * sizeof(double), ctx->stream));
+    if (ctx->stats_dev.p) PGV_HIP(hipMemsetAsync(ctx->stats_dev.p, 0, pgv::kStatsWords * sizeof(double), ctx->stream));
     ctx->aux_ms = 0;
     ctx->aux_launches = 0;
     ctx->aux_pairs = 0;
@@ -277,7 +277,7 @@ int pgv_ctx_reset_stats(pgv_ctx *ctx) {
 int pgv_ctx_get_stats(pgv_ctx *ctx, pgv_stats *out) {
     if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "ctx/out is NULL");
     PGV_TRY(resolve_events(ctx));
-    double dev_acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double dev_acc[pgv::kStatsWords] = {};
     if (ctx->stats_dev.p) {
         PGV_HIP(hipMemcpyAsync(dev_acc, ctx->stats_dev.p, sizeof(dev_acc), hipMemcpyDeviceToHost, ctx->stream));
         PGV_HIP(hipStreamSynchronize(ctx->stream));
@@ -295,6 +295,7 @@ int pgv_ctx_get_stats(pgv_ctx *ctx, pgv_stats *out) {
     out->scan_unique_rows = dev_acc[5];
     out->scan_redo_queries = dev_acc[6];
     out->scan_widened_queries = dev_acc[7];
+    out->scan_pruned_probes = dev_acc[8];
     out->scan_shadow_queries = ctx->scan_shadow_queries;
     for (pgv_ctx *c : ctx->children) {  // what the lanes of overlapping batches did counts as this context's
         pgv_stats cs;
@@ -312,6 +313,7 @@ int pgv_ctx_get_stats(pgv_ctx *ctx, pgv_stats *out) {
         out->scan_unique_rows += cs.scan_unique_rows;
         out->scan_redo_queries += cs.scan_redo_queries;
         out->scan_widened_queries += cs.scan_widened_queries;
+        out->scan_pruned_probes += cs.scan_pruned_probes;
         out->scan_shadow_queries += cs.scan_shadow_queries;
     }
     return PGV_OK;

@@ -414,7 +414,7 @@ extern "C" {
 // pgv_abi_ivf.hip
 int rank_lists_dev(pgv_index *ix, const void *q_dev, int nq, int maxprobes, int32_t *out_lists_dev, float *out_dist_dev);
 int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes, int k, float *out_dist,
-                   int64_t *out_slot, uint64_t *out_tid);
+                   int64_t *out_slot, uint64_t *out_tid, bool prune = false);  // prune: probe pruning allowed (pgv_internal.h)
 int check_batch_args(pgv_index *ix, const void *queries, int nq, int probes, int k, float *out_dist, uint64_t *out_tid,
                      const char *who);
 // pgv_abi_build.hip

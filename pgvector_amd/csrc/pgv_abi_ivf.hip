@@ -73,6 +73,14 @@ int rank_shadow_env() {
     return e ? atoi(e) : 1;
 }
 
+// PGV_PROBE_PRUNE: 0 = every probed list is scanned, otherwise (default) a batch over the row shadow drops the probed
+// lists that provably hold none of a query's k nearest rows (pgv_internal.h, beside ScanBound).  Read at every batch, like
+// PGV_SCAN_SHADOW: one process compares both
+bool probe_prune_on(const pgv_index *ix, int probes) {
+    const char *e = getenv("PGV_PROBE_PRUNE");
+    return (e ? atoi(e) != 0 : true) && ix->list_radius && probes <= probe_prune_max_probes();
+}
+
 // The fp16 residual shadow of an fp32 L2 index (kernels_shadow.hip; the bound: pgv_internal.h, ScanBound), built once
 // with the index -- its rows never change afterwards.  Its own allocation (+50 % of the fp32 row bytes), outside the
 // exportable arena; no device memory for it is no error: the list scan keeps the fp32 rows.  The same allocation holds
@@ -85,16 +93,19 @@ int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
     const RowGeom g16 = row_geom(ix->dim, PGV_F16);
     const size_t bytes = ((size_t)ix->nrows * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
     const size_t cbytes = ((size_t)ix->nlists * g16.ld * sizeof(uint16_t) + 255) & ~(size_t)255;
+    // ... and behind them the lists' radii (probe pruning): the build's fp64 bits, then the fp32 values in their place
+    const size_t rbytes = sizeof(unsigned long long) * (size_t)ix->nlists;
     void *sh = nullptr;
-    if (hipMalloc(&sh, bytes + 256 + cbytes) != hipSuccess) {
+    if (hipMalloc(&sh, bytes + 256 + cbytes + rbytes) != hipSuccess) {
         (void)hipGetLastError();
         return PGV_OK;
     }
     // [0] max |x_i - c_i| | [8] E^2 | [16] P^2 of the rows; at byte 32 the same of the centers (max |c_i|, E_c^2, P_c^2)
     void *words = static_cast<char *>(sh) + bytes;
     void *csh = static_cast<char *>(sh) + bytes + 256;
+    void *rad = static_cast<char *>(sh) + bytes + 256 + cbytes;
     int rc = launch_shadow_build(ctx, ix->geom, g16, ix->vectors, ix->centers, ix->list_offsets, ix->nlists, ix->nrows, sh,
-                                 words);
+                                 words, rad);
     if (rc == PGV_OK)
         rc = launch_shadow_build(ctx, ix->geom, g16, ix->centers, nullptr, nullptr, 0, ix->nlists, csh,
                                  static_cast<char *>(words) + 32);
@@ -125,6 +136,26 @@ int shadow_create(pgv_ctx *ctx, pgv_index *ix) {
     ix->shadow_s = shadow_scale_of(max_abs);
     ix->shadow_E = (E + 1e-12 * (P + E)) * (1.0 + 1e-9);
     ix->shadow_P = P * (1.0 + 1e-9);
+    // the lists' radii: sqrt of the fp64 maxima, rounded up like E (x_i - c_i and the sum in fp64: 1e-9 covers them) and
+    // once more into fp32; a non-finite one is +inf (its list is never dropped, and nothing behind it), an empty list 0.
+    // A failed copy leaves the index without radii: nothing is pruned
+    {
+        std::vector<unsigned long long> rb((size_t)ix->nlists);
+        std::vector<float> rf((size_t)ix->nlists);
+        if (hipMemcpy(rb.data(), rad, rbytes, hipMemcpyDeviceToHost) == hipSuccess) {
+            for (int l = 0; l < ix->nlists; l++) {
+                double r2;
+                memcpy(&r2, &rb[l], 8);
+                const double R = std::sqrt(r2) * (1.0 + 1e-9);
+                float f = (float)R;
+                if (std::isfinite(f) && (double)f < R) f = std::nextafterf(f, INFINITY);
+                rf[l] = std::isfinite(R) ? f : INFINITY;
+            }
+            if (hipMemcpy(rad, rf.data(), sizeof(float) * rf.size(), hipMemcpyHostToDevice) == hipSuccess)
+                ix->list_radius = static_cast<float *>(rad);
+        }
+        (void)hipGetLastError();
+    }
     // the centers' copy, rounded up the same way; a non-finite E_c or P_c (NaN / inf in a center) drops it alone: the
     // ranking stays on the fp32 centers
     float cmax_abs;
@@ -152,6 +183,7 @@ struct ShadowBatch {
     float *cscale = nullptr, *ceps = nullptr;  // the ranking's 2^(1 + s_c + s_q) and band terms
     float *pair_t = nullptr;                   // [nq x probes]
     bool scan_follows = false;                 // set by the caller: the shadow scan will run on the ranking's lists
+    int need = 0;                              // ... for heads of this many rows (the search's k: probe pruning)
     bool cast_for_scan = false;                // qscale / qeps are written
     // the ranking left pair_t, cleared the plan's counters and counted the lists it emitted into them (PlanEmit)
     bool pairs_done = false;
@@ -919,6 +951,10 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
         if (tail.pair_t) {
             PGV_TRY(plan_batch_reserve(ctx, ix->nlists, nq, maxprobes, &pbuf));
             tail.emit = {pbuf.cnt, pbuf.probe_off, pbuf.seg_len, ix->list_offsets};
+            if (sb->need > 0 && probe_prune_on(ix, maxprobes)) {
+                tail.emit.radius = ix->list_radius;
+                tail.emit.need = sb->need;
+            }
         }
         tail.rows = {ix->centers, nullptr, nullptr, ix->geom, ix->dtype,
                      reinterpret_cast<const unsigned *>(ix->center_norms + ix->nlists)};
@@ -1064,7 +1100,7 @@ static int list_scan_step(pgv_index *ix, const ScanPath &path, const ScanWork &w
 }
 
 static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
-                           int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid, ShadowBatch *sb) {
+                           int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid, ShadowBatch *sb, bool prune) {
     pgv_ctx *ctx = ix->ctx;
     const ScanPath path = scan_path(ix, nq, probes, k);
     if (path.per_query) {
@@ -1094,12 +1130,22 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
     if (!sb) sb = &own;
     if (path.shadow && !sb->cast_for_scan) PGV_TRY(shadow_batch_cast(ix, q_dev, nq, probes, false, true, sb));
     const float *pair_t = (path.shadow && sb->pairs_done) ? sb->pair_t : nullptr;
+    // lists that did not come from this batch's ranking over the center shadow: what that ranking's recheck would have
+    // done to them is done here, in front of the plan -- the pairs' t, and the probes that cannot reach the head dropped
+    // (-1 in a copy of the lists: the plan, the scan and the tail see the lists the fused route would have emitted)
+    const bool counted = pair_t != nullptr;
+    if (path.shadow && !pair_t && prune && probe_prune_on(ix, probes)) {
+        PGV_TRY(ctx->plan_c.ensure(sizeof(int32_t) * (size_t)nq * probes));
+        PGV_TRY(launch_probe_prune(ctx, ix, q_dev, nq, probe_lists, probes, k, ctx->plan_c.as<int32_t>(), sb->pair_t));
+        probe_lists = ctx->plan_c.as<int32_t>();
+        pair_t = sb->pair_t;
+    }
     PlanResult plan;
     // (pair_t set: the ranking of this very batch also counted into the plan's buffers -- the plan is two launches)
     PGV_TRY(launch_plan_batch(ctx, ix, probe_lists, nq, probes, path.qt, path.rows_per_task, ctx->profiling, &plan, pair_t,
-                              pair_t != nullptr));
+                              counted));
     if (path.shadow) {
-        if (!pair_t)  // lists that did not come from this batch's ranking over the center shadow
+        if (!pair_t)  // ... and every probe is kept (the sharded search, PGV_PROBE_PRUNE=0, an index without radii)
             PGV_TRY(launch_shadow_pairs(ctx, ix->geom, q_dev, ix->centers, plan.pair_start, ix->nlists, (int64_t)nq * probes,
                                         plan.pairs));
         ctx->scan_shadow_queries += nq;
@@ -1156,8 +1202,8 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
 }
 
 int scan_batch_dev(pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes, int k, float *out_dist,
-                   int64_t *out_slot, uint64_t *out_tid) {
-    return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, nullptr);
+                   int64_t *out_slot, uint64_t *out_tid, bool prune) {
+    return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, nullptr, prune);
 }
 
 int pgv_scan_lists(pgv_index *ix, const void *query, const int32_t *lists, int nlists,
@@ -1287,8 +1333,9 @@ int pgv_search_batch(pgv_index *ix, const void *queries, int nq, int probes, int
     // one query cast for the batch where both halves read fp16, and the ranking's q.c_l for the scan
     ShadowBatch sb;
     sb.scan_follows = scan_path(ix, nq, probes, k).shadow;
+    sb.need = k;
     PGV_TRY(rank_lists_impl(ix, q_dev, nq, probes, probe_lists, nullptr, &sb));
-    return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, &sb);
+    return scan_batch_impl(ix, q_dev, nq, probe_lists, probes, k, out_dist, out_slot, out_tid, &sb, true);
 }
 
 int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *probe_lists, int probes, int k,
@@ -1309,7 +1356,7 @@ int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *pr
     PGV_TRY(stage_queries(ix, queries, nq, &q_dev));
     PGV_TRY(stage_flat(ctx, probe_lists, sizeof(int32_t) * (size_t)nq * probes, ctx->idx_stage, &pl_dev));
     return scan_batch_dev(ix, q_dev, nq, static_cast<const int32_t *>(pl_dev), probes, k, out_dist, out_slot,
-                          out_tid);
+                          out_tid, true);
 }
 
 // the query cast of the shadow paths on its own (tests: shadow_query_kernel's outputs against a host model)

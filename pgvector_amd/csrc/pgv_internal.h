@@ -128,6 +128,7 @@ struct ScanPair {
     int32_t query;
     int32_t pad;
 };
+constexpr int kStatsWords = 9;  // pgv_ctx::stats_dev: the device-side accumulators of pgv_stats ([8]: scan_pruned_probes)
 // the work of one planned launch (a PlanResult's, the dense plan's, pgv_scan_lists's host plan); all device arrays
 struct ScanWork {
     const ScanTask *tasks;
@@ -160,7 +161,7 @@ struct pgv_ctx {
     pgv::DBuf sh_q;
     pgv::DBuf mf_d;  // MFMA assignment split over center parts: the parts' candidates per row
     pgv::DBuf mf_a, mf_b, mf_c, zeros;  // MFMA assignment: norms, pre-filter candidates, redo list; 16 zero bytes
-    pgv::DBuf stats_dev;  // profiling: {pairs, rows streamed} of the batched list scans, as doubles
+    pgv::DBuf stats_dev;  // profiling: pgv::kStatsWords doubles ({pairs, rows streamed} of the batched list scans, ...)
     // scratch (pinned host); h_a_busy marks the last async copy out of h_a (waited before reuse)
     pgv::HBuf h_a, h_b, h_c;
     hipEvent_t h_a_busy = nullptr;
@@ -226,6 +227,9 @@ struct pgv_index {
     int shadow_s = 0;
     double shadow_E = 0.0;            // max over rows |(x - c_l) - 2^s shadow|, rounded up
     double shadow_P = 0.0;            // max over rows |2^s shadow|, rounded up
+    // [nlists] R_l >= max |x - c_l| over the list's rows (probe pruning, the rule beside ScanBound): measured by the
+    // shadow's build, inside its allocation, shared like it; null without a row shadow: nothing is pruned
+    float *list_radius = nullptr;
     // ... and the fp16 copy of its centers that the batch ranking multiplies instead of `centers`:
     // [nlists x shadow_geom.ld] fp16(c 2^-cshadow_s), inside the shadow's allocation; null when not built
     void *cshadow = nullptr;
@@ -465,6 +469,63 @@ inline ScanBound scan_bound_chain(const pgv_ctx *ctx, int dim, int chain) {
 inline ScanBound shadow_band(int ld, float g_ref, double u = 5.9604645e-8) {
     return {0.f, 0.f, gamma_n(ld / 64.0 + 10.0, u), g_ref};
 }
+// Probe pruning (PGV_PROBE_PRUNE) -- a probed list whose every row is provably farther than k rows of the
+// lists in front of it is not scanned.  Per list l the index keeps R_l >= max |x - c_l| over its rows (list_radius:
+// measured in fp64 where the row shadow is built, rounded up; 0 for an empty list, +inf where not finite).  For one query
+// the probed lists come in probe order with d_j, the fp32 sum((q - c_j)^2) in the reference's arithmetic.
+//     m     the smallest count such that lists 0 .. m-1 hold >= k rows together (none: nothing is dropped)
+//     tau   max over i < m of sqrt(d_i) + R_i
+//     probe j >= m is dropped iff sqrt(d_j) - R_j > tau
+// Proof.  Write D_j = |q - c_j| (exact).  A row x of list i < m has |q - x| <= D_i + R_i, a row y of list j has
+// |q - y| >= D_j - R_j (triangle inequality).  The distances the search orders by are fp32 sums of n = ld squares of
+// rounded differences, all terms non-negative: fl = T^2 (1 + e) + e_a with |e| <= g = gamma_(ld + 4) in any order of
+// summation (Higham 3.5; the subtraction's and the product's roundings are three of the n + 3), |e_a| <= a = (ld + 4)
+// 2^-149 for products that underflowed.  The same holds between d_j and D_j^2.  Hence
+//     every row of lists i < m:  fl <= H^2 (1 + g) + a,   H = max_i sqrt((d_i + a) / (1 - g)) + R_i          (probe_near)
+//     every row of list j:       fl >= L^2 (1 - g) - a,   L = sqrt(max(d_j - a, 0) / (1 + g)) - R_j, if L > 0 (probe_far)
+// and j is dropped only if L^2 (1 - g) - a > (H^2 (1 + g) + a)(1 + 2^-40) in fp64 (the factor covers the fp64 roundings of
+// both sides many times over) with the right side below FLT_MAX (no kept row's distance has overflowed into a tie with
+// the dropped ones).  Then >= k kept rows have a STRICTLY smaller distance than any row of list j: none of its rows is in
+// the head, whatever the order among ties.  With g = a = 0 this is the rule above; the margins only keep more.  Equality
+// keeps.  Anything non-finite (a NaN / inf query, an overflowed d, an infinite radius) among the first m lists drops
+// nothing for the query; a non-finite far side keeps its list.  tests/prune_model.py is the host model.
+#if defined(__HIPCC__)
+#define PGV_HD __host__ __device__
+#else
+#define PGV_HD
+#endif
+struct ProbeMargins {
+    double g = 0.0, a = 0.0;
+};
+PGV_HD inline ProbeMargins probe_margins(int ld) {  // ld: the fp32 row length
+    const double n = (ld + 4.0) * 5.9604644775390625e-8;
+    return {n / (1.0 - n), (ld + 4.0) * 1.401298464324817e-45};
+}
+PGV_HD inline double probe_near(float d, float R, ProbeMargins pm) { return sqrt(((double)d + pm.a) / (1.0 - pm.g)) + (double)R; }
+PGV_HD inline double probe_far(float d, float R, ProbeMargins pm) {
+    const double e = (double)d - pm.a;
+    return sqrt((e > 0.0 ? e : 0.0) / (1.0 + pm.g)) - (double)R;
+}
+// lens / near [n]: the probed lists' rows and probe_near in probe order (a fill entry: 0 rows, near 0); far: probe_far of
+// probe j
+PGV_HD inline bool probe_dropped(const int64_t *lens, const double *near, int n, int j, int need, double far, ProbeMargins pm) {
+    int64_t rows = 0;
+    double tau = 0.0;
+    bool finite = true;
+    int m = 0;
+    while (m < n && rows < need) {
+        rows += lens[m];
+        const double h = near[m];
+        finite = finite && h < (double)INFINITY;  // (false for NaN)
+        tau = h > tau ? h : tau;
+        m++;
+    }
+    if (rows < need || j < m || !finite) return false;
+    if (!(far > 0.0) || !(far < (double)INFINITY)) return false;
+    const double lo2 = far * far * (1.0 - pm.g) - pm.a, hi2 = tau * tau * (1.0 + pm.g) + pm.a;
+    return hi2 < 3.0e38 && lo2 > hi2 * (1.0 + 9.094947017729282e-13);
+}
+
 struct ExpansionBound {
     float gamma;        // of |x|^2 + 2 |q||x| (expansion terms)
     float gamma_exact;  // of (|q| + |x|)^2 (the exact value's own rounding; 0 in the statistical model)
@@ -642,7 +703,8 @@ int launch_mfma_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const
 // kernels_shadow.hip: the fp16 residual shadow of an fp32 L2 index (pgv_index::shadow) and its per-batch terms.
 // words: 24 device bytes, [0] bits of the largest |x_i - c_i|, [8] / [16] bits of the largest E^2 / P^2 (fp64)
 int launch_shadow_build(pgv_ctx *ctx, const RowGeom &g32, const RowGeom &g16, const void *rows, const void *centers,
-                        const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words);
+                        const int64_t *list_off, int nlists, int64_t n, void *shadow, void *words,
+                        void *radius_bits = nullptr);
 int shadow_scale_of(float max_abs);  // s of the largest |x_i - c_i|
 int shadow_chain_length(const RowGeom &g16);  // kernels_mfma.hip: products per accumulator chain of any scan form, at most
 int scan_chain_length(const RowGeom &g, pgv_dtype dtype, bool wide);  // ... of a plain scan: the forms a launch may use
@@ -694,7 +756,17 @@ struct PlanEmit {
     int *cnt = nullptr;
     int64_t *probe_off = nullptr, *seg_len = nullptr;
     const int64_t *list_off = nullptr;  // the INDEX's list offsets (the ranking's rows are the centers)
+    // probe pruning (the rule above): radius null = off.  A dropped list leaves as -1 with t = 0, counts nothing and has
+    // length 0 -- cnt, probe_off and seg_len come out as if it had never been ranked
+    const float *radius = nullptr;      // the index's list_radius
+    int need = 0;                       // the SEARCH's k (the tail's k is the ranking's maxprobes)
 };
+// kernels_query.hip: the same rule for probe lists that were given (pgv_scan_batch), one workgroup per query in front of
+// the plan: out_lists = the lists with the dropped ones as -1, pair_t = every pair's -2 q.c_l (0 where dropped) by the
+// chain of the ranking's recheck.  probes <= probe_prune_max_probes()
+int probe_prune_max_probes();
+int launch_probe_prune(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int probes,
+                       int need, int32_t *out_lists, float *pair_t);
 // pair_t: [nq x probes] the pairs' t = -2 q.c_l in probe order (the shadow scan; from the ranking), or null: t = 0
 // counted: cnt | fill were cleared and cnt, probe_off and seg_len written by the ranking of this batch (PlanEmit) --
 // no memset, no plan_count_kernel, pairs and tasks in one launch, the profiling totals inside plan_scan_kernel
