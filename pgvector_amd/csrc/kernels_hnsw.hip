@@ -23,11 +23,18 @@
 //                     the merged order as well.
 // One refinement keeps this exact for distance ties: an element that was admitted and
 // then evicted from W at a distance EQUAL to W's new furthest is still a live
-// candidate in the reference (its stop test is strict).  Such elements go to a small
+// candidate in the reference (its stop test is strict).  Such elements go to a
 // tie list T (they all share one distance); T is dropped as soon as W's furthest
 // gets nearer, and its members are expanded after W's own unexpanded entries.  The
 // ORDER among equal distances is the one thing left open -- it is unspecified in the
 // reference as well (pairing-heap internals).
+// T has ef slots and never fills them.  When the first entry leaves W at K while K is
+// W's furthest key, W is full of keys <= K, and from then on nothing at K is admitted
+// (`eDistance < f->distance` fails).  So everything that ever enters T at K was among
+// the at most ef entries not farther than K at that moment -- W's old entries
+// and the batch entries admitted in their turn -- and at least one of those stays in
+// W for K to remain its furthest key: |T| <= ef - 1.  (tests/hnsw_walk_model.py
+// asserts the bound on every batch of every walk it models.)
 #include "pgv_device.h"
 
 #include <type_traits>
@@ -41,7 +48,6 @@ namespace {
 constexpr int kHnswThreads = 256;
 constexpr int kHnswWaves = kHnswThreads / kWave;
 constexpr uint32_t kExpanded = 0x80000000u;
-constexpr int kTieCap = 64;  // evicted candidates tied with W's furthest that are remembered
 
 struct HnswDev {
     const char *rows;  // [n x nvec] 16-byte vectors
@@ -84,14 +90,14 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     constexpr bool kBits = std::is_same_v<T, BitRow>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lm0 = 2 * g.m;
-    // layout: query row | W keys [2][ef] | W ids [2][ef] | batch keys [lm0] | batch ids [lm0] | scalars
+    // layout: query row | W keys [2][ef] | W ids [2][ef] | batch keys [lm0] | batch ids [lm0] | T ids [ef] | scalars
     Raw16 *lq = reinterpret_cast<Raw16 *>(smem);
     uint32_t *wk = reinterpret_cast<uint32_t *>(smem + (size_t)g.nvec * sizeof(Raw16));
     uint32_t *wi = wk + 2 * ef;
     uint32_t *bk = wi + 2 * ef;
     int32_t *bi = reinterpret_cast<int32_t *>(bk + lm0);
-    uint32_t *ti = reinterpret_cast<uint32_t *>(bi + lm0);  // tie list ids [kTieCap]
-    int *sc = reinterpret_cast<int *>(ti + kTieCap);
+    uint32_t *ti = reinterpret_cast<uint32_t *>(bi + lm0);  // tie list ids [ef]: |T| < ef, see the header
+    int *sc = reinterpret_cast<int *>(ti + ef);
     // sc: [0] query, [1] |W|, [2] batch size, [3] candidate element (-1: none), [4] W buffer,
     //     [5] |T|, [6] next unread entry of T, [7] key shared by T's entries
 
@@ -359,7 +365,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                             }
                             const unsigned long long bal = __ballot(tie);
                             const int at = tn + __popcll(bal & ((1ull << lane) - 1ull));
-                            if (tie && at < kTieCap) ti[at] = id;
+                            if (tie && at < ef) ti[at] = id;  // (at < ef always: the guard only keeps a write inside T)
                             tn += __popcll(bal);
                         }
                         for (int base = 0; base < nb; base += kWave) {
@@ -383,11 +389,11 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                             }
                             const unsigned long long bal = __ballot(tie);
                             const int at = tn + __popcll(bal & ((1ull << lane) - 1ull));
-                            if (tie && at < kTieCap) ti[at] = (uint32_t)bi[i];
+                            if (tie && at < ef) ti[at] = (uint32_t)bi[i];  // (as above: never past T)
                             tn += __popcll(bal);
                         }
                         if (lane == 0) {
-                            sc[5] = tn < kTieCap ? tn : kTieCap;
+                            sc[5] = tn < ef ? tn : ef;  // (tn < ef always: nothing is truncated)
                             sc[6] = t0;
                             sc[7] = (int)K;
                         }
@@ -443,7 +449,7 @@ __global__ __launch_bounds__(256) void hnsw_patch_kernel(int32_t *__restrict__ n
 template <typename T, int METRIC>
 int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *bitmaps, int words, int grid,
                   int *counter) {
-    const size_t lds = (size_t)g.nvec * sizeof(Raw16) + (size_t)run.ef * 16 + (size_t)g.m * 16 + kTieCap * 4 + 64;
+    const size_t lds = (size_t)g.nvec * sizeof(Raw16) + (size_t)run.ef * 16 + (size_t)g.m * 16 + (size_t)run.ef * 4 + 64;
     if (lds > 150 * 1024)
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
     auto kern = hnsw_search_kernel<T, METRIC>;
