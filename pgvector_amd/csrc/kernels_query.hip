@@ -21,6 +21,9 @@
 // A dependent kernel boundary costs ~1.5 us on this chip (MI355X_MICROARCH.md price list), less
 // than an in-kernel "last workgroup selects" hand-off (write-through stores, drain, ~1500 tickets,
 // acquire: ~5 us measured), and it keeps the scan kernel a clean streaming kernel.
+//
+// pgv_rank_lists / pgv_search_batch for a few queries launch the same rank, lists and scan kernels with a grid row per
+// query, and mq_head_kernel in place of query_head_kernel: heads into device arrays, no pinned record.
 #include "pgv_device.h"
 #include "pgv_select.h"
 
@@ -168,36 +171,42 @@ __device__ __forceinline__ void score_rows(RowPtr row_ptr, int64_t first, int64_
     }
 }
 
+// The rank, lists and scan kernels take one query per grid row: the single-query entry points launch one row, a batch
+// too small to share rows between its queries (nq * probes well below the list count: every probed list belongs to one
+// query, the list-major plan of the batched path gains nothing and pays its dozen launches) launches nq of them.
 // ------------------------------------------------------------------- GetScanLists
+// grid row q (blockIdx.y): query q of `queries` against every center, distances to cdist[q * cd_stride + list]
 template <typename T, int METRIC, int NCH>
 __global__ __launch_bounds__(kQThreads) void query_rank_kernel(const char *__restrict__ centers, int nlists, int nvec,
-                                                               int lg, const char *__restrict__ qp,
-                                                               float *__restrict__ cdist, int per) {
+                                                               int lg, const char *__restrict__ queries,
+                                                               float *__restrict__ cdist, int64_t cd_stride, int per) {
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
+    const char *qp = queries + (size_t)blockIdx.y * row_bytes;
+    float *cd = cdist + (size_t)blockIdx.y * cd_stride;
     for (int64_t first = (int64_t)blockIdx.x * per; first < nlists; first += (int64_t)gridDim.x * per) {
         const int64_t end = first + per < nlists ? first + per : nlists;
-        score_rows<T, METRIC, NCH>([&](int64_t j) { return centers + (size_t)j * row_bytes; }, first, end, qp, nvec, lg,
-                                   cdist);
+        score_rows<T, METRIC, NCH>([&](int64_t j) { return centers + (size_t)j * row_bytes; }, first, end, qp, nvec, lg, cd);
     }
 }
 
-// the bounded heap of GetScanLists (src/ivfscan.c:76-106): max_probes nearest centers, ascending
-__global__ __launch_bounds__(kQThreads) void query_lists_kernel(const float *__restrict__ cdist, int nlists,
-                                                                int max_probes, int kp, int32_t *__restrict__ out_lists) {
+// the bounded heap of GetScanLists (src/ivfscan.c:76-106): max_probes nearest centers, ascending; one workgroup per
+// query (blockIdx.x), out_dist optional
+__global__ __launch_bounds__(kQThreads) void query_lists_kernel(const float *__restrict__ cdist, int64_t cd_stride,
+                                                                int nlists, int max_probes, int kp,
+                                                                int32_t *__restrict__ out_lists,
+                                                                float *__restrict__ out_dist) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);
     SelShared *s = reinterpret_cast<SelShared *>(smem + (size_t)kHeadCap * 8);
-    block_topk_auto(cdist, nlists, max_probes, kp, kHeadCap, ent, s);
-    for (int i = threadIdx.x; i < max_probes; i += kQThreads) out_lists[i] = (int32_t)(unsigned)(ent[i] & 0xffffffffu);
+    const int q = blockIdx.x;
+    block_topk_auto(cdist + (size_t)q * cd_stride, nlists, max_probes, kp, kHeadCap, ent, s);
+    for (int i = threadIdx.x; i < max_probes; i += kQThreads) {
+        out_lists[(size_t)q * max_probes + i] = (int32_t)(unsigned)(ent[i] & 0xffffffffu);
+        if (out_dist) out_dist[(size_t)q * max_probes + i] = key_to_float((unsigned)(ent[i] >> 32));
+    }
 }
 
 // ------------------------------------------------------------------- GetScanItems
-struct QueryHead {        // what the host reads back (pinned host memory)
-    long long total;      // tuples in this batch (= tuplesort's input count)
-    int count;            // entries below: min(head, total)
-    unsigned seq;         // written last: the call this record answers
-};
-
 // where each probed list starts in the batch (offs) and its first row slot (lbeg): lists in probe
 // order, page-chain order inside -- the order the reference feeds its tuplesort
 struct BatchMap {
@@ -229,26 +238,43 @@ struct BatchMap {
     }
 };
 
+// grid row q (blockIdx.y): query q over its own nprobes lists, distances to seg[q * seg_stride + position in the batch]
 template <typename T, int METRIC, int NCH>
 __global__ __launch_bounds__(kQThreads) void query_scan_kernel(
     const char *__restrict__ vectors, const int64_t *__restrict__ list_off, const int32_t *__restrict__ probe_lists,
-    int nprobes, int nvec, int lg, const char *__restrict__ qp, float *__restrict__ seg, int per) {
+    int nprobes, int nvec, int lg, const char *__restrict__ queries, float *__restrict__ seg, int64_t seg_stride, int per) {
     __shared__ BatchMap map;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    map.build(probe_lists, nprobes, list_off);
+    const int q = blockIdx.y;
+    map.build(probe_lists + (size_t)q * nprobes, nprobes, list_off);
     const int64_t m = map.offs[nprobes];
+    const char *qp = queries + (size_t)q * row_bytes;
+    float *sg = seg + (size_t)q * seg_stride;
+    if (!queries) {
+        // NULL query (pgv_query_scan alone hands one in): ZeroDistance (src/ivfscan.c:192-196), every tuple at distance
+        // 0.  In front of the scoring loop: as a branch inside it, this cost the six-slice kernel 10 VGPRs and a wave
+        // per SIMD
+        for (int64_t j = (int64_t)blockIdx.x * kQThreads + threadIdx.x; j < m; j += (int64_t)gridDim.x * kQThreads) sg[j] = 0.f;
+        return;
+    }
     // runs of `per` rows per workgroup, round-robin until the batch is covered (the grid was sized
     // from the host's upper bound of m)
     for (int64_t first = (int64_t)blockIdx.x * per; first < m; first += (int64_t)gridDim.x * per) {
         const int64_t end = first + per < m ? first + per : m;
-        if (qp) {
-            score_rows<T, METRIC, NCH>([&](int64_t j) { return vectors + (size_t)map.slot_of(j, nprobes) * row_bytes; },
-                                       first, end, qp, nvec, lg, seg);
-        } else {
-            // NULL query: ZeroDistance (src/ivfscan.c:192-196), every tuple at distance 0
-            for (int64_t j = first + threadIdx.x; j < end; j += kQThreads) seg[j] = 0.f;
-        }
+        score_rows<T, METRIC, NCH>([&](int64_t j) { return vectors + (size_t)map.slot_of(j, nprobes) * row_bytes; }, first,
+                                   end, qp, nvec, lg, sg);
     }
+}
+
+// What the two head kernels share: the map of the batch and the first k entries of its ascending tuplesort stream
+// (distance, then position) into ent[0, min(k, m)) at the start of smem.  Returns m, the tuples of the batch.
+__device__ __forceinline__ int64_t select_head(BatchMap &map, char *smem, const float *seg, const int64_t *list_off,
+                                               const int32_t *probe_lists, int nprobes, int k, int kp) {
+    map.build(probe_lists, nprobes, list_off);
+    const int64_t m = map.offs[nprobes];
+    block_topk_auto(seg, m, k, kp, kHeadCap, reinterpret_cast<unsigned long long *>(smem),
+                    reinterpret_cast<SelShared *>(smem + (size_t)kHeadCap * 8));
+    return m;
 }
 
 // entries [skip, skip + count) of the ascending tuplesort stream of the batch whose distances are
@@ -261,12 +287,9 @@ __global__ __launch_bounds__(kQThreads) void query_head_kernel(
     float *__restrict__ head_dist, int64_t *__restrict__ head_slot, uint64_t *__restrict__ head_tid, unsigned seq) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ BatchMap map;
-    map.build(probe_lists, nprobes, list_off);
-    const int64_t m = map.offs[nprobes];
-    unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);
-    SelShared *s = reinterpret_cast<SelShared *>(smem + (size_t)kHeadCap * 8);
     const int k = skip + count;
-    block_topk_auto(seg, m, k, kp, kHeadCap, ent, s);
+    const int64_t m = select_head(map, smem, seg, list_off, probe_lists, nprobes, k, kp);
+    const unsigned long long *ent = reinterpret_cast<const unsigned long long *>(smem);
     const int have = (int)(m < k ? m : k) - skip;
     for (int i = threadIdx.x; i < have; i += kQThreads) {
         const unsigned long long e = ent[skip + i];
@@ -298,57 +321,9 @@ __global__ void query_iota_kernel(int32_t *__restrict__ out, int n) {
     if (i < n) out[i] = i;
 }
 
-// ------------------------------------------------------------------- a few queries at a time
-// A batch too small to share rows between its queries (nq * probes well below the list count: every probed list
-// belongs to one query) gains nothing from the list-major plan of the batched path and pays its dozen launches.
-// The same four kernels as above, one grid row (blockIdx.y) per query, results into the caller's device arrays:
-// rank, lists, scan, head -- pgv_search_batch for 16 queries in four launches.
-template <typename T, int METRIC, int NCH>
-__global__ __launch_bounds__(kQThreads) void mq_rank_kernel(const char *__restrict__ centers, int nlists, int nvec, int lg,
-                                                            const char *__restrict__ queries, float *__restrict__ cdist,
-                                                            int64_t cd_stride, int per) {
-    const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    const char *qp = queries + (size_t)blockIdx.y * row_bytes;
-    float *cd = cdist + (size_t)blockIdx.y * cd_stride;
-    for (int64_t first = (int64_t)blockIdx.x * per; first < nlists; first += (int64_t)gridDim.x * per) {
-        const int64_t end = first + per < nlists ? first + per : nlists;
-        score_rows<T, METRIC, NCH>([&](int64_t j) { return centers + (size_t)j * row_bytes; }, first, end, qp, nvec, lg, cd);
-    }
-}
-
-__global__ __launch_bounds__(kQThreads) void mq_lists_kernel(const float *__restrict__ cdist, int64_t cd_stride, int nlists,
-                                                             int max_probes, int kp, int32_t *__restrict__ out_lists,
-                                                             float *__restrict__ out_dist) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);
-    SelShared *s = reinterpret_cast<SelShared *>(smem + (size_t)kHeadCap * 8);
-    const int q = blockIdx.x;
-    block_topk_auto(cdist + (size_t)q * cd_stride, nlists, max_probes, kp, kHeadCap, ent, s);
-    for (int i = threadIdx.x; i < max_probes; i += kQThreads) {
-        out_lists[(size_t)q * max_probes + i] = (int32_t)(unsigned)(ent[i] & 0xffffffffu);
-        if (out_dist) out_dist[(size_t)q * max_probes + i] = key_to_float((unsigned)(ent[i] >> 32));
-    }
-}
-
-template <typename T, int METRIC, int NCH>
-__global__ __launch_bounds__(kQThreads) void mq_scan_kernel(
-    const char *__restrict__ vectors, const int64_t *__restrict__ list_off, const int32_t *__restrict__ probe_lists,
-    int nprobes, int nvec, int lg, const char *__restrict__ queries, float *__restrict__ seg, int64_t seg_stride, int per) {
-    __shared__ BatchMap map;
-    const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    const int q = blockIdx.y;
-    map.build(probe_lists + (size_t)q * nprobes, nprobes, list_off);
-    const int64_t m = map.offs[nprobes];
-    const char *qp = queries + (size_t)q * row_bytes;
-    float *sg = seg + (size_t)q * seg_stride;
-    for (int64_t first = (int64_t)blockIdx.x * per; first < m; first += (int64_t)gridDim.x * per) {
-        const int64_t end = first + per < m ? first + per : m;
-        score_rows<T, METRIC, NCH>([&](int64_t j) { return vectors + (size_t)map.slot_of(j, nprobes) * row_bytes; },
-                                   first, end, qp, nvec, lg, sg);
-    }
-}
-
-// the head of each query's stream into the caller's [nq x k] arrays (+inf / -1 / ~0 past the tuples there are)
+// a few queries at a time: the head of each query's stream (one workgroup per query) into the caller's [nq x k] device
+// arrays (+inf / -1 / ~0 past the tuples there are) -- with rank, lists and scan pgv_search_batch for 16 queries in
+// four launches
 __global__ __launch_bounds__(kQThreads) void mq_head_kernel(
     const float *__restrict__ seg, int64_t seg_stride, const int64_t *__restrict__ list_off,
     const uint64_t *__restrict__ tids, const int32_t *__restrict__ probe_lists, int nprobes, int k, int kp,
@@ -357,11 +332,9 @@ __global__ __launch_bounds__(kQThreads) void mq_head_kernel(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ BatchMap map;
     const int q = blockIdx.x;
-    map.build(probe_lists + (size_t)q * nprobes, nprobes, list_off);
-    const int64_t m = map.offs[nprobes];
-    unsigned long long *ent = reinterpret_cast<unsigned long long *>(smem);
-    SelShared *s = reinterpret_cast<SelShared *>(smem + (size_t)kHeadCap * 8);
-    block_topk_auto(seg + (size_t)q * seg_stride, m, k, kp, kHeadCap, ent, s);
+    const int64_t m = select_head(map, smem, seg + (size_t)q * seg_stride, list_off, probe_lists + (size_t)q * nprobes,
+                                  nprobes, k, kp);
+    const unsigned long long *ent = reinterpret_cast<const unsigned long long *>(smem);
     const int have = (int)(m < k ? m : k);
     for (int i = threadIdx.x; i < k; i += kQThreads) {
         const size_t o = (size_t)q * k + i;
@@ -848,7 +821,6 @@ template <typename T, int METRIC, typename F> int dispatch_nch(const RowGeom &g,
 
 int query_max_batch_lists() { return kMaxBatchLists; }
 int query_head_cap() { return kHeadCap; }
-size_t query_head_bytes(int head) { return sizeof(QueryHead) + (size_t)head * (4 + 8 + 8) + 64; }
 
 int launch_query_stage(pgv_ctx *ctx, const void *src_pinned, void *dst_dev, int nvec) {
     hipLaunchKernelGGL(query_stage_kernel, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const Raw16 *>(src_pinned),
@@ -863,67 +835,57 @@ int launch_query_iota(pgv_ctx *ctx, int32_t *out, int n) {
     return PGV_OK;
 }
 
-// one query against n contiguous rows, out[j] = distance to row j: the streaming form of query_rank_kernel (whole
-// rows in flight per wavefront, the query in registers) -- a k-means++ round over the samples, pgv_distance_batch
-int launch_one_query_rows(pgv_ctx *ctx, const RowsView &v, const void *q_dev, float *out) {
-    if (v.n <= 0) return PGV_OK;
-    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "one query over rows: fp32 / fp16 rows only");
+// nq queries (the rows of q_dev) against v's contiguous rows, out[q * out_stride + j] = distance of query q to row j:
+// query_rank_kernel, the streaming form (whole rows in flight per wavefront, the query in registers) -- the centers of
+// GetScanLists for one query or a few, a k-means++ round over the samples, pgv_distance_batch
+int launch_query_rows(pgv_ctx *ctx, const RowsView &v, const void *q_dev, int nq, float *out, int64_t out_stride) {
+    if (v.n <= 0 || nq <= 0) return PGV_OK;
+    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "queries over rows: fp32 / fp16 rows only");
     const RowGeom &g = v.geom;
-    const void *rows = v.rows;
-    const int n = (int)v.n;
     int per, grid;
-    run_geometry(ctx, g, n, &per, &grid);
+    run_geometry(ctx, g, v.n, &per, &grid);
     return dispatch_metric(v.metric, v.dtype(), [&](auto *tp, auto mc) {
         using T = std::remove_pointer_t<decltype(tp)>;
         constexpr int M = decltype(mc)::value;
         return dispatch_nch<T, M>(g, [&](auto nc) {
             constexpr int NCH = decltype(nc)::value;
-            hipLaunchKernelGGL((query_rank_kernel<T, M, NCH>), dim3(grid), dim3(kQThreads), 0, ctx->stream,
-                               static_cast<const char *>(rows), n, g.nvec, g.lpr_log2, static_cast<const char *>(q_dev),
-                               out, per);
+            hipLaunchKernelGGL((query_rank_kernel<T, M, NCH>), dim3(grid, nq), dim3(kQThreads), 0, ctx->stream,
+                               static_cast<const char *>(v.rows), (int)v.n, g.nvec, g.lpr_log2,
+                               static_cast<const char *>(q_dev), out, out_stride, per);
             PGV_HIP(hipGetLastError());
             return PGV_OK;
         });
     });
 }
 
-int launch_query_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, float *cdist, int max_probes,
-                      int32_t *out_lists) {
-    const RowGeom &g = ix->geom;
-    int per, grid;
-    run_geometry(ctx, g, ix->nlists, &per, &grid);
-    const int kp = pow2_at_least(max_probes);
-    PGV_TRY(dispatch_metric(ix->metric, ix->dtype, [&](auto *tp, auto mc) {
-        using T = std::remove_pointer_t<decltype(tp)>;
-        constexpr int M = decltype(mc)::value;
-        return dispatch_nch<T, M>(g, [&](auto nc) {
-            constexpr int NCH = decltype(nc)::value;
-            hipLaunchKernelGGL((query_rank_kernel<T, M, NCH>), dim3(grid), dim3(kQThreads), 0, ctx->stream,
-                               static_cast<const char *>(ix->centers), ix->nlists, g.nvec, g.lpr_log2,
-                               static_cast<const char *>(q_dev), cdist, per);
-            PGV_HIP(hipGetLastError());
-            return PGV_OK;
-        });
-    }));
-    hipLaunchKernelGGL(query_lists_kernel, dim3(1), dim3(kQThreads), kQueryLds, ctx->stream, cdist, ix->nlists,
-                       max_probes, kp, out_lists);
+// GetScanLists for nq staged queries: cdist[q * cd_stride + list], then the max_probes nearest of each query
+int launch_query_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, float *cdist, int64_t cd_stride,
+                      int max_probes, int32_t *out_lists, float *out_dist) {
+    PGV_TRY(launch_query_rows(ctx, ivf_centers(ix), q_dev, nq, cdist, cd_stride));
+    hipLaunchKernelGGL(query_lists_kernel, dim3(nq), dim3(kQThreads), kQueryLds, ctx->stream, cdist, cd_stride, ix->nlists,
+                       max_probes, pow2_at_least(max_probes), out_lists, out_dist);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-int launch_query_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, const int32_t *probe_lists, int nprobes,
-                      int64_t rows_bound, float *seg) {
+// GetScanItems for nq staged queries (q_dev null: one NULL query), query q over probe_lists[q * nprobes ..] into
+// seg[q * seg_stride ..]; rows_bound: rows no query's lists exceed
+int launch_query_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists,
+                      int nprobes, int64_t rows_bound, float *seg, int64_t seg_stride) {
     const RowGeom &g = ix->geom;
     int per, grid;
     run_geometry(ctx, g, rows_bound, &per, &grid);
+    // nq grid rows share the device: a row needs no more workgroups than keep every CU busy (one row: run_geometry's cap)
+    const int cap = (ctx->num_cus * 8 + nq - 1) / nq;
+    if (grid > cap) grid = cap < 1 ? 1 : cap;
     return dispatch_metric(ix->metric, ix->dtype, [&](auto *tp, auto mc) {
         using T = std::remove_pointer_t<decltype(tp)>;
         constexpr int M = decltype(mc)::value;
         return dispatch_nch<T, M>(g, [&](auto nc) {
             constexpr int NCH = decltype(nc)::value;
-            hipLaunchKernelGGL((query_scan_kernel<T, M, NCH>), dim3(grid), dim3(kQThreads), 0, ctx->stream,
+            hipLaunchKernelGGL((query_scan_kernel<T, M, NCH>), dim3(grid, nq), dim3(kQThreads), 0, ctx->stream,
                                static_cast<const char *>(ix->vectors), ix->list_offsets, probe_lists, nprobes, g.nvec,
-                               g.lpr_log2, static_cast<const char *>(q_dev), seg, per);
+                               g.lpr_log2, static_cast<const char *>(q_dev), seg, seg_stride, per);
             PGV_HIP(hipGetLastError());
             return PGV_OK;
         });
@@ -932,65 +894,18 @@ int launch_query_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, cons
 
 int launch_query_head(pgv_ctx *ctx, const pgv_index *ix, const float *seg, const int32_t *probe_lists, int nprobes,
                       int skip, int count, void *head_rec, unsigned seq) {
-    const int kp = pow2_at_least(skip + count);
-    QueryHead *hdr = static_cast<QueryHead *>(head_rec);
-    char *base = static_cast<char *>(head_rec) + 64;
-    int64_t *h_slot = reinterpret_cast<int64_t *>(base);
-    uint64_t *h_tid = reinterpret_cast<uint64_t *>(base + (size_t)count * 8);
-    float *h_dist = reinterpret_cast<float *>(base + (size_t)count * 16);
     hipLaunchKernelGGL(query_head_kernel, dim3(1), dim3(kQThreads), kQueryLds, ctx->stream, seg, ix->list_offsets,
-                       ix->tids, probe_lists, nprobes, skip, count, kp, hdr, h_dist, h_slot, h_tid, seq);
+                       ix->tids, probe_lists, nprobes, skip, count, pow2_at_least(skip + count),
+                       static_cast<QueryHead *>(head_rec), query_head_dists(head_rec, count), query_head_slots(head_rec),
+                       query_head_tids(head_rec, count), seq);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-// a few queries at a time (see mq_*_kernel): GetScanLists for nq staged queries
-int launch_multi_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, float *cdist, int64_t cd_stride,
-                      int max_probes, int32_t *out_lists, float *out_dist) {
-    const RowGeom &g = ix->geom;
-    int per, grid;
-    run_geometry(ctx, g, ix->nlists, &per, &grid);
-    const int kp = pow2_at_least(max_probes);
-    PGV_TRY(dispatch_metric(ix->metric, ix->dtype, [&](auto *tp, auto mc) {
-        using T = std::remove_pointer_t<decltype(tp)>;
-        constexpr int M = decltype(mc)::value;
-        return dispatch_nch<T, M>(g, [&](auto nc) {
-            constexpr int NCH = decltype(nc)::value;
-            hipLaunchKernelGGL((mq_rank_kernel<T, M, NCH>), dim3(grid, nq), dim3(kQThreads), 0, ctx->stream,
-                               static_cast<const char *>(ix->centers), ix->nlists, g.nvec, g.lpr_log2,
-                               static_cast<const char *>(q_dev), cdist, cd_stride, per);
-            PGV_HIP(hipGetLastError());
-            return PGV_OK;
-        });
-    }));
-    hipLaunchKernelGGL(mq_lists_kernel, dim3(nq), dim3(kQThreads), kQueryLds, ctx->stream, cdist, cd_stride, ix->nlists,
-                       max_probes, kp, out_lists, out_dist);
-    PGV_HIP(hipGetLastError());
-    return PGV_OK;
-}
-
-// ... and GetScanItems + the head of the sorted stream, every query over its own lists
-int launch_multi_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int nprobes,
-                      int64_t rows_bound, float *seg, int64_t seg_stride, int k, float *out_dist, int64_t *out_slot,
+// a few queries at a time: the head of every query's sorted stream into the caller's [nq x k] device arrays
+int launch_multi_head(pgv_ctx *ctx, const pgv_index *ix, int nq, const float *seg, int64_t seg_stride,
+                      const int32_t *probe_lists, int nprobes, int k, float *out_dist, int64_t *out_slot,
                       uint64_t *out_tid) {
-    const RowGeom &g = ix->geom;
-    int per, grid;
-    run_geometry(ctx, g, rows_bound, &per, &grid);
-    // nq grid rows share the device: a row needs no more workgroups than keep every CU busy
-    const int cap = (ctx->num_cus * 8 + nq - 1) / nq;
-    if (grid > cap) grid = cap < 1 ? 1 : cap;
-    PGV_TRY(dispatch_metric(ix->metric, ix->dtype, [&](auto *tp, auto mc) {
-        using T = std::remove_pointer_t<decltype(tp)>;
-        constexpr int M = decltype(mc)::value;
-        return dispatch_nch<T, M>(g, [&](auto nc) {
-            constexpr int NCH = decltype(nc)::value;
-            hipLaunchKernelGGL((mq_scan_kernel<T, M, NCH>), dim3(grid, nq), dim3(kQThreads), 0, ctx->stream,
-                               static_cast<const char *>(ix->vectors), ix->list_offsets, probe_lists, nprobes, g.nvec,
-                               g.lpr_log2, static_cast<const char *>(q_dev), seg, seg_stride, per);
-            PGV_HIP(hipGetLastError());
-            return PGV_OK;
-        });
-    }));
     double *stats = (ctx->profiling && ctx->stats_dev.p) ? ctx->stats_dev.as<double>() : nullptr;
     hipLaunchKernelGGL(mq_head_kernel, dim3(nq), dim3(kQThreads), kQueryLds, ctx->stream, seg, seg_stride, ix->list_offsets,
                        ix->tids, probe_lists, nprobes, k, pow2_at_least(k), out_dist, out_slot, out_tid, stats);

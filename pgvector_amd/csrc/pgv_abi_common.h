@@ -238,7 +238,7 @@ int dense_scan(pgv_ctx *ctx, const RowsView &v, const void *queries_dev, int nq,
     if (nq == 1 && !mfma && nrows <= 0x7fffffff) {
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin((double)nrows, (double)nrows, true));
-        PGV_TRY(launch_one_query_rows(ctx, v, queries_dev, out_dev));
+        PGV_TRY(launch_query_rows(ctx, v, queries_dev, 1, out_dev, out_stride));
         PGV_TRY(timer.end());
         return PGV_OK;
     }

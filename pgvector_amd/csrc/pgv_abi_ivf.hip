@@ -910,9 +910,9 @@ static int rank_lists_impl(pgv_index *ix, const void *q_dev, int nq, int maxprob
     // a handful of queries: one grid row per query over the centers, selection per query (two launches)
     // (measured on 1000 centers x 1536: ahead of the dense plan + top-k + position cast up to ~24 queries, level at 32)
     if (nq <= 24 && maxprobes <= query_head_cap()) {
-        const int64_t cd_stride = ((int64_t)ix->nlists + 7) / 4 * 4;  // 16-byte aligned rows + a float4 of slack
+        const int64_t cd_stride = query_row_stride(ix->nlists);
         PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * (size_t)nq * cd_stride));
-        return launch_multi_rank(ctx, ix, q_dev, nq, ctx->dist_mat.as<float>(), cd_stride, maxprobes, out_lists_dev,
+        return launch_query_rank(ctx, ix, q_dev, nq, ctx->dist_mat.as<float>(), cd_stride, maxprobes, out_lists_dev,
                                  out_dist_dev);
     }
     int cand = maxprobes + 16 < ix->nlists ? maxprobes + 16 : ix->nlists;
@@ -1022,7 +1022,7 @@ static int scan_turn_end(pgv_ctx *ctx) {
 // anything is launched: scan_batch_impl follows it, and pgv_search_batch tells the ranking of it ahead of time (`shadow`)
 struct ScanPath {
     bool bits = false;       // a bit index: always the list-major plan into hamming_list_kernel, nothing else below applies
-    bool per_query = false;  // every query scans its own lists: mq_scan_kernel + mq_head_kernel, nothing below applies
+    bool per_query = false;  // every query scans its own lists: query_scan_kernel + mq_head_kernel, nothing below applies
     bool use_mfma = false;   // the matrix cores (32 queries per pass)
     bool use_tile = false;   // the tile kernel (16 queries per pass over the rows)
     bool wide = false;       // the 64-query form of the matrix-core kernel
@@ -1036,15 +1036,15 @@ static ScanPath scan_path(const pgv_index *ix, int nq, int probes, int k) {
     // than 8 queries go to the tile kernel (16 queries per pass over the rows) when the row shape allows it.
     const double share = (double)nq * probes / (double)ix->nlists;
     if (ix->nbits > 0) {
-        // integer distances: no per-query mq_* path, no matrix cores, no tile path, no shadow, no exact tail
+        // integer distances: no per-query path, no matrix cores, no tile path, no shadow, no exact tail
         p.bits = true;
         p.qt = hamming_list_group_size(share);
         p.rows_per_task = hamming_list_rows_per_task();
         return p;
     }
     // Too few queries to share rows between them (every probed list belongs to one query): the list-major plan
-    // gains nothing and costs a dozen launches.  Each query scans its own lists (mq_scan_kernel) and selects
-    // its own head (mq_head_kernel): two launches, the single-query kernels with one grid row per query.
+    // gains nothing and costs a dozen launches.  Each query scans its own lists (query_scan_kernel, one grid row per
+    // query) and selects its own head (mq_head_kernel): two launches.
     p.per_query = (share <= 0.4 || nq <= 4) && nq <= 1024 && probes <= query_max_batch_lists() && k <= query_head_cap();
     if (p.per_query) return p;
     // ... and to the matrix cores (32 queries per pass) for L2 / inner product heads of up to 192
@@ -1105,7 +1105,7 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
     const ScanPath path = scan_path(ix, nq, probes, k);
     if (path.per_query) {
         const int64_t bound = ix->len_prefix[probes];  // rows of the `probes` longest lists
-        const int64_t seg_stride = (bound + 7) / 4 * 4;
+        const int64_t seg_stride = query_row_stride(bound);
         PGV_TRY(ctx->plan_d.ensure(sizeof(float) * (size_t)nq * seg_stride));
         OutArg od, os, ot;
         PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
@@ -1114,8 +1114,10 @@ static int scan_batch_impl(pgv_index *ix, const void *q_dev, int nq, const int32
         PGV_TRY(scan_turn_begin(ctx));
         ScanTimer timer{ctx};
         PGV_TRY(timer.begin(0.0, 0.0));  // pairs / rows are added up on the device by mq_head_kernel
-        PGV_TRY(launch_multi_scan(ctx, ix, q_dev, nq, probe_lists, probes, bound, ctx->plan_d.as<float>(), seg_stride, k,
-                                  od.as<float>(), os.as<int64_t>(), ot.as<uint64_t>()));
+        float *seg = ctx->plan_d.as<float>();
+        PGV_TRY(launch_query_scan(ctx, ix, q_dev, nq, probe_lists, probes, bound, seg, seg_stride));
+        PGV_TRY(launch_multi_head(ctx, ix, nq, seg, seg_stride, probe_lists, probes, k, od.as<float>(), os.as<int64_t>(),
+                                  ot.as<uint64_t>()));
         PGV_TRY(timer.end());
         PGV_TRY(scan_turn_end(ctx));
         bool need = false;
@@ -1389,12 +1391,6 @@ int pgv_index_shadow_cast(pgv_index *ix, const void *queries, int nq, void *out_
 // ------------------------------------------------------- one query at a time
 namespace {
 
-struct QueryHeadHost {  // mirrors QueryHead of kernels_query.hip
-    long long total;
-    int count;
-    unsigned seq;
-};
-
 // Admission of single-query scans (threads of ONE process; a Postgres backend is a process of its own and has one
 // scan in flight at most).  Measured on MI355X (profiles/r03_single_query_concurrency.md): the device runs ~2.5
 // kernels of different streams at a time (4 hardware queues), 16 backends reach 48 k QPS and every backend beyond
@@ -1420,7 +1416,7 @@ struct ScanGate {
 // while (the kernel's own stores are the fastest completion signal there is), then fall back to
 // a stream synchronise.
 int wait_head(pgv_ctx *ctx, pgv_query *q, unsigned seq) {
-    volatile QueryHeadHost *h = static_cast<volatile QueryHeadHost *>(q->head_pinned);
+    volatile QueryHead *h = static_cast<volatile QueryHead *>(q->head_pinned);
     for (int spin = 0; spin < 200000; spin++) {
         if (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) == seq) return PGV_OK;
         __builtin_ia32_pause();
@@ -1431,10 +1427,9 @@ int wait_head(pgv_ctx *ctx, pgv_query *q, unsigned seq) {
 }
 
 void copy_head(pgv_query *q, int stride, int n, float *out_dist, int64_t *out_slot, uint64_t *out_tid) {
-    const char *base = static_cast<const char *>(q->head_pinned) + 64;
-    if (out_slot) memcpy(out_slot, base, sizeof(int64_t) * (size_t)n);
-    if (out_tid) memcpy(out_tid, base + (size_t)stride * 8, sizeof(uint64_t) * (size_t)n);
-    if (out_dist) memcpy(out_dist, base + (size_t)stride * 16, sizeof(float) * (size_t)n);
+    if (out_slot) memcpy(out_slot, query_head_slots(q->head_pinned), sizeof(int64_t) * (size_t)n);
+    if (out_tid) memcpy(out_tid, query_head_tids(q->head_pinned, stride), sizeof(uint64_t) * (size_t)n);
+    if (out_dist) memcpy(out_dist, query_head_dists(q->head_pinned, stride), sizeof(float) * (size_t)n);
 }
 
 }  // namespace
@@ -1536,7 +1531,7 @@ int pgv_query_rank(pgv_query *q, const void *query, int max_probes) {
         }
     }
     q->rank_pending = true;
-    return launch_query_rank(ctx, ix, q->q_row, q->cdist, max_probes, q->lists);
+    return launch_query_rank(ctx, ix, q->q_row, 1, q->cdist, 0, max_probes, q->lists, nullptr);
 }
 
 int pgv_query_scan(pgv_query *q, int first, int nprobes, int head, float *out_dist, int64_t *out_slot,
@@ -1553,17 +1548,17 @@ int pgv_query_scan(pgv_query *q, int first, int nprobes, int head, float *out_di
     if (out_tid && !ix->tids) PGV_FAIL(PGV_ERR_STATE, "index was uploaded without tids");
     PGV_HIP(hipSetDevice(ctx->device));
     const int64_t bound = ix->len_prefix[nprobes];  // rows of the nprobes longest lists
-    PGV_TRY(q->seg.ensure(sizeof(float) * (size_t)(bound + 4)));  // + one float4 of slack for the vector loads of the selection
+    PGV_TRY(q->seg.ensure(sizeof(float) * (size_t)query_row_stride(bound)));
     const unsigned seq = ++q->seq ? q->seq : ++q->seq;  // never 0: the cleared record's value
     ScanGate gate;  // held until the head is back (every return below)
-    PGV_TRY(launch_query_scan(ctx, ix, q->is_null ? nullptr : q->q_row, q->lists + first, nprobes, bound,
-                              q->seg.as<float>()));
+    PGV_TRY(launch_query_scan(ctx, ix, q->is_null ? nullptr : q->q_row, 1, q->lists + first, nprobes, bound,
+                              q->seg.as<float>(), 0));
     PGV_TRY(launch_query_head(ctx, ix, q->seg.as<float>(), q->lists + first, nprobes, 0, head, q->head_pinned, seq));
     q->cur_first = first;
     q->cur_n = nprobes;
     PGV_TRY(wait_head(ctx, q, seq));
     q->rank_pending = false;
-    const QueryHeadHost *h = static_cast<const QueryHeadHost *>(q->head_pinned);
+    const QueryHead *h = static_cast<const QueryHead *>(q->head_pinned);
     *out_count = h->count;
     if (out_total) *out_total = h->total;
     copy_head(q, head, h->count, out_dist, out_slot, out_tid);
@@ -1585,7 +1580,7 @@ int pgv_query_more(pgv_query *q, int skip, int count, float *out_dist, int64_t *
     PGV_TRY(launch_query_head(ctx, ix, q->seg.as<float>(), q->lists + q->cur_first, q->cur_n, skip, count,
                               q->head_pinned, seq));
     PGV_TRY(wait_head(ctx, q, seq));
-    const QueryHeadHost *h = static_cast<const QueryHeadHost *>(q->head_pinned);
+    const QueryHead *h = static_cast<const QueryHead *>(q->head_pinned);
     *out_count = h->count;
     copy_head(q, count, h->count, out_dist, out_slot, out_tid);
     return PGV_OK;

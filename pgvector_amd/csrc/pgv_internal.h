@@ -827,24 +827,38 @@ int launch_iota_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *lists_de
                       const int64_t *probe_off, int64_t *out_slot);
 
 // kernels_query.hip: one query at a time ([stage,] rank, lists, scan, head: four or five launches, no host round trip)
+// ... and the same rank, lists and scan kernels for a few queries at a time, one grid row per query
 int query_max_batch_lists();
 int query_head_cap();
-size_t query_head_bytes(int head);
+// The record query_head_kernel writes into pinned host memory and the host reads back: this header, then three arrays
+// of `stride` entries each (the count the launch asked for), the widest first so that each stays aligned
+struct QueryHead {
+    long long total;  // tuples in this batch (= tuplesort's input count)
+    int count;        // entries in the arrays: min(asked, what the batch has past `skip`)
+    unsigned seq;     // written last (release, system scope): the call this record answers
+};
+constexpr size_t kQueryHeadArrays = 64;  // the arrays start on the cache line after the header's
+static_assert(sizeof(QueryHead) <= kQueryHeadArrays, "the header overtakes the arrays");
+inline int64_t *query_head_slots(void *rec) { return reinterpret_cast<int64_t *>(static_cast<char *>(rec) + kQueryHeadArrays); }
+inline uint64_t *query_head_tids(void *rec, int stride) { return reinterpret_cast<uint64_t *>(query_head_slots(rec) + stride); }
+inline float *query_head_dists(void *rec, int stride) { return reinterpret_cast<float *>(query_head_tids(rec, stride) + stride); }
+inline size_t query_head_bytes(int stride) { return kQueryHeadArrays + (size_t)stride * (8 + 8 + 4); }
+// floats between the distance rows of consecutive queries (scan segments of `n` rows, center distances of n lists):
+// 16-byte aligned rows, each with a float4 of slack behind it for the vector loads of the selection
+inline int64_t query_row_stride(int64_t n) { return (n + 7) / 4 * 4; }
 int launch_query_stage(pgv_ctx *ctx, const void *src_pinned, void *dst_dev, int nvec);
-// the same kernels for a few queries at a time (one grid row per query, results in device arrays)
-int launch_multi_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, float *cdist, int64_t cd_stride,
-                      int max_probes, int32_t *out_lists, float *out_dist);
-int launch_multi_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists, int nprobes,
-                      int64_t rows_bound, float *seg, int64_t seg_stride, int k, float *out_dist, int64_t *out_slot,
-                      uint64_t *out_tid);
 int launch_query_iota(pgv_ctx *ctx, int32_t *out, int n);
-int launch_one_query_rows(pgv_ctx *ctx, const RowsView &v, const void *q_dev, float *out);  // v.n < 2^31
-int launch_query_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, float *cdist, int max_probes,
-                      int32_t *out_lists);
-int launch_query_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, const int32_t *probe_lists, int nprobes,
-                      int64_t rows_bound, float *seg);
+// out[q * out_stride + j] = distance of query q to row j of v (v.n < 2^31): query_rank_kernel's only launcher
+int launch_query_rows(pgv_ctx *ctx, const RowsView &v, const void *q_dev, int nq, float *out, int64_t out_stride);
+int launch_query_rank(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, float *cdist, int64_t cd_stride,
+                      int max_probes, int32_t *out_lists, float *out_dist);
+int launch_query_scan(pgv_ctx *ctx, const pgv_index *ix, const void *q_dev, int nq, const int32_t *probe_lists,
+                      int nprobes, int64_t rows_bound, float *seg, int64_t seg_stride);
 int launch_query_head(pgv_ctx *ctx, const pgv_index *ix, const float *seg, const int32_t *probe_lists, int nprobes,
                       int skip, int count, void *head_rec, unsigned seq);
+int launch_multi_head(pgv_ctx *ctx, const pgv_index *ix, int nq, const float *seg, int64_t seg_stride,
+                      const int32_t *probe_lists, int nprobes, int k, float *out_dist, int64_t *out_slot,
+                      uint64_t *out_tid);
 
 int launch_merge_heads(pgv_ctx *ctx, const float *dist_all, const uint64_t *tid_all, int nranks, int nq, int k,
                        float *out_dist, uint64_t *out_tid);
