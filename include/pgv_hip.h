@@ -644,8 +644,9 @@ int			pgv_rerank(pgv_ctx * ctx, pgv_metric metric, pgv_dtype dtype, int dim, con
  * L1 distance to itself is exactly 0, integer-valued data gives the reference's bits, and a sum that overflows with
  * terms of one sign is +-inf like the reference's.
  *
- * Not served: HNSW over sparse elements (hnsw_sparsevec_support, HNSW_MAX_NNZ 1000, src/hnswutils.c:1361-1430) -- the
- * follow-up on top of these kernels --, a device-side sparsevec_l2_normalize, the ext/ glue.  bench.py does not measure
+ * An HNSW index over sparsevec is walked through pgv_hnsw_upload_sparse / pgv_hnsw_search_sparse (the HNSW side, below),
+ * with these values as its distances.  Not served: a device-side sparsevec_l2_normalize (it drops the elements that
+ * round to zero and so changes the CSR: the caller normalises for cosine), the ext/ glue.  bench.py does not measure
  * these entries; tools/bench_sparse_topk.py does.
  */
 
@@ -789,6 +790,56 @@ int			pgv_hnsw_get_payload(pgv_hnsw * h, const int64_t *elements, int n, void *o
  */
 int			pgv_hnsw_upload_bits(pgv_ctx * ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
 								 const void *payload, int payload_bytes, pgv_hnsw * *out);
+
+/*
+ * ---- HNSW over sparsevec elements.
+ * The mirror of `USING hnsw (col sparsevec_l2_ops | sparsevec_ip_ops | sparsevec_cosine_ops | sparsevec_l1_ops)`
+ * (sql/vector.sql:1189-1212; type info hnsw_sparsevec_support, src/hnswutils.c:1361-1433), the only index the reference
+ * has for the type.  It replaces what hnswgettuple's first batch (GetScanItems, src/hnswscan.c:25-56) does on such an
+ * index: the same walk, every candidate scored with FUNCTION 1 of the opclass -- sparsevec_l2_squared_distance,
+ * sparsevec_negative_inner_product, sparsevec_l1_distance (src/sparsevec.c:826-899, :905-966, :1018-1060), each the
+ * (double) of an fp32 sum, so the walk's fp32 keys are exact images of the reference's float8 distances.
+ *   row_ptr / row_idx / row_val: the n elements in CSR under the rules of the sparsevec section above (host or device
+ *   memory; 1 <= dim <= 1e9); metric PGV_L2SQ, PGV_NEG_IP or PGV_L1 -- cosine is PGV_NEG_IP over vectors the caller
+ *   normalised, as elsewhere; payload / payload_bytes as pgv_hnsw_upload_payload (NULL / 0: none).
+ * An element with more than 1000 stored elements (HNSW_MAX_NNZ, src/hnsw.h:34; HnswCheckValue's sparsevec check,
+ * src/hnswutils.c:1361-1372) is PGV_ERR_DIMS; the text carries the reference's message and names the element.  Host
+ * arrays are validated before any launch; a device row_ptr is copied to the host and checked there (monotone, the
+ * limit); device row_idx / row_val are used unchecked (pgv_rerank's rule).  The mirror keeps index and value of a
+ * stored element side by side, 8 bytes: a row the walk gathers is one contiguous run.
+ *
+ * On such a mirror pgv_hnsw_free, pgv_hnsw_set_graph, pgv_hnsw_update_graph, pgv_hnsw_get_payload, pgv_hnsw_device and
+ * pgv_hnsw_share (a view has its own stream, scratch and visited bitmaps; the element CSR stays the owner's) work as on
+ * any mirror, and pgv_hnsw_score_pairs scores element a[i] against element b[i] (b as the query).  These return
+ * PGV_ERR_ARG before any launch: pgv_hnsw_search and pgv_hnsw_score (they take dense queries: use the _sparse twins),
+ * pgv_hnsw_export (the handle has no fields for a second allocation; nothing can be imported), every pgv_hnsw_build_* and
+ * pgv_hnsw_link_* entry and pgv_hnsw_score_groups (sparse graphs are not built here, like bit graphs).  The _sparse
+ * entries on any other mirror are PGV_ERR_ARG too.
+ * Not served: a device-side sparsevec_l2_normalize, the build, the ext/ glue (ext/ returns every sparsevec opclass to
+ * the CPU path); bench.py does not measure these entries, tools/bench_sparse_hnsw.py does.
+ */
+int			pgv_hnsw_upload_sparse(pgv_ctx * ctx, pgv_metric metric, int dim,
+								   const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+								   const void *payload, int payload_bytes, pgv_hnsw * *out);
+/*
+ * pgv_hnsw_score over a sparse mirror (HnswSearchLayer's candidate scoring, src/hnswutils.c:908-934, with the sparsevec
+ * FUNCTION 1): pair i scores element slot[i] against query query_of[i] (NULL: query 0) of the nq queries in CSR.  The
+ * values are pgv_sparse_distance_batch's for the same two vectors, bit for bit: the same terms in the same order of
+ * additions, an empty intersection's negative inner product +0.0.  Queries are not elements: a query may store up to
+ * 16 000 elements (SPARSEVEC_MAX_NNZ; HnswCheckValue, src/hnswutils.c:413, is the index-value path); host query arrays
+ * are validated like pgv_sparse_topk's.
+ */
+int			pgv_hnsw_score_sparse(pgv_hnsw * h, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq,
+								  const int32_t *slot, const int32_t *query_of, int64_t npairs, float *out);
+/*
+ * pgv_hnsw_search over a sparse mirror, word for word (GetScanItems, src/hnswscan.c:25-56; HnswSearchLayer,
+ * src/hnswutils.c:824-987): greedy descent, layer 0 with ef_search, out_scored = so->tuples; queries in CSR as
+ * pgv_hnsw_score_sparse takes them.  The query's pairs sit in LDS next to the walk's state: ef_search, m and the
+ * batch's longest query together may need at most 150 KiB, else PGV_ERR_ARG before any launch (the text names the
+ * three); a 16 000-element query fits with ef_search 40 and m 16.
+ */
+int			pgv_hnsw_search_sparse(pgv_hnsw * h, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq,
+								   int ef_search, int k, int64_t *out_elem, float *out_dist, int64_t *out_scored);
 
 /*
  * The HNSW mirror across processes, like pgv_index_export / pgv_index_import: the element vectors and the graph

@@ -49,6 +49,7 @@ SYMBOLS = [
     "pgv_index_set_overlap", "pgv_index_shadow_cast", "pgv_bit_topk", "pgv_binary_quantize", "pgv_rerank",
     "pgv_hnsw_upload_bits", "pgv_index_upload_bits", "pgv_index_nbits", "pgv_bit_assign", "pgv_bit_kmeans",
     "pgv_bit_lloyd_step", "pgv_sparse_distance_batch", "pgv_sparse_cosine_distance_batch", "pgv_sparse_topk",
+    "pgv_hnsw_upload_sparse", "pgv_hnsw_score_sparse", "pgv_hnsw_search_sparse",
 ]
 
 
@@ -193,6 +194,9 @@ def _load():
     lib.pgv_hnsw_build_neighbors.argtypes = [P, P, P, I, I, I, P, P, P, P, P]
     lib.pgv_hnsw_score_pairs.argtypes = [P, P, P, I64, P]
     lib.pgv_hnsw_update_graph.argtypes = [P, C.c_int32, P, I, P, P]
+    lib.pgv_hnsw_upload_sparse.argtypes = [P, I, I, P, P, P, I64, P, I, C.POINTER(P)]
+    lib.pgv_hnsw_score_sparse.argtypes = [P, P, P, P, I, P, P, I64, P]
+    lib.pgv_hnsw_search_sparse.argtypes = [P, P, P, P, I, I, I, P, P, P]
     return lib
 
 

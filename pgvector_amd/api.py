@@ -1029,6 +1029,69 @@ class BitHnsw(Hnsw):
         return out
 
 
+class SparseHnsw(Hnsw):
+    """device mirror of an HNSW index over sparsevec elements, `USING hnsw (... sparsevec_l2_ops / _ip_ops / _cosine_ops /
+    _l1_ops)` (pgv_hnsw_upload_sparse): rows_csr = (ptr [n + 1], idx, val) as sparse_topk takes them, at most 1000 stored
+    elements per element; metric PGV_L2SQ / PGV_NEG_IP / PGV_L1 (cosine: PGV_NEG_IP over normalised vectors).
+    set_graph, update_graph, get_payload and close are Hnsw's; search, score and score_pairs take CSR queries / element
+    slots and return sparse_distance_batch's values.  No export: the mirror is not shared across processes."""
+
+    def __init__(self, ctx, metric, dim, rows_csr, payload=None):
+        self.ctx, self.metric, self.dtype, self.dim = ctx, metric, None, int(dim)
+        r_ptr, r_idx, r_val = _csr(rows_csr)
+        n = int(r_ptr.shape[0]) - 1
+        h = C.c_void_p()
+        self.payload_words = 0
+        if payload is not None:
+            payload = np.ascontiguousarray(payload, dtype=np.uint32)
+            self.payload_words = int(payload.shape[1])
+        check(lib.pgv_hnsw_upload_sparse(ctx.h, int(metric), int(dim), ptr(r_ptr), ptr(r_idx), ptr(r_val), n, ptr(payload),
+                                         4 * self.payload_words, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def share(self, ctx):
+        v = SparseHnsw.__new__(SparseHnsw)
+        h = C.c_void_p()
+        check(lib.pgv_hnsw_share(self.h, ctx.h, C.byref(h)))
+        v.ctx, v.metric, v.dtype, v.dim, v.h = ctx, self.metric, None, self.dim, h
+        v.payload_words = self.payload_words
+        v._owner = self   # keeps the owner alive
+        ctx._adopt(v)
+        return v
+
+    def search(self, queries_csr, ef_search, k, want_scored=True):
+        """pgv_hnsw_search_sparse: CSR queries (a query may store up to 16 000 elements) ->
+        (element slots [nq x k] nearest first / -1, distances [nq x k] float32 / +inf, scored [nq] or None)"""
+        q_ptr, q_idx, q_val = _csr(queries_csr)
+        nq = int(q_ptr.shape[0]) - 1
+        elem = _empty_like_kind(q_val, (nq, k), np.int64)
+        dist = _empty_like_kind(q_val, (nq, k), np.float32)
+        scored = _empty_like_kind(q_val, (nq,), np.int64) if want_scored else None
+        check(lib.pgv_hnsw_search_sparse(self.h, ptr(q_ptr), ptr(q_idx), ptr(q_val), nq, int(ef_search), int(k), ptr(elem),
+                                         ptr(dist), ptr(scored)))
+        return elem, dist, scored
+
+    def score(self, queries_csr, slot, query_of=None):
+        """pgv_hnsw_score_sparse: the distance of element slot[i] to query query_of[i] (None: query 0) of the CSR queries"""
+        q_ptr, q_idx, q_val = _csr(queries_csr)
+        slot = np.ascontiguousarray(slot, dtype=np.int32) if not _is_torch(slot) else slot
+        if query_of is not None and not _is_torch(query_of):
+            query_of = np.ascontiguousarray(query_of, dtype=np.int32)
+        n = int(slot.shape[0])
+        out = _empty_like_kind(slot, (n,), np.float32)
+        check(lib.pgv_hnsw_score_sparse(self.h, ptr(q_ptr), ptr(q_idx), ptr(q_val), int(q_ptr.shape[0]) - 1, ptr(slot),
+                                        ptr(query_of), n, ptr(out)))
+        return out
+
+    def score_pairs(self, a, b):
+        """pgv_hnsw_score_pairs: the distance of element a[i] to element b[i], b[i] taken as the query"""
+        a, b = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32)
+        out = np.empty((a.size,), dtype=np.float32)
+        check(lib.pgv_hnsw_score_pairs(self.h, ptr(a), ptr(b), int(a.size), ptr(out)))
+        return out
+
+
 def binary_search_hnsw(ctx, metric, dtype, dim, queries, rows, bit_hnsw, ef_search, kc, k, want_candidates=False):
     """the INDEXED two-stage query of binary quantization (the reference README's `USING hnsw (... bit_hamming_ops)`
     form): quantise the queries, the kc <= ef_search nearest elements of `bit_hnsw` (a BitHnsw over the rows'

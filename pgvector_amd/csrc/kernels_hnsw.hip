@@ -36,6 +36,7 @@
 // W for K to remain its furthest key: |T| <= ef - 1.  (tests/hnsw_walk_model.py
 // asserts the bound on every batch of every walk it models.)
 #include "pgv_device.h"
+#include "sparse_pair.h"
 
 #include <type_traits>
 
@@ -50,7 +51,7 @@ constexpr int kHnswWaves = kHnswThreads / kWave;
 constexpr uint32_t kExpanded = 0x80000000u;
 
 struct HnswDev {
-    const char *rows;  // [n x nvec] 16-byte vectors
+    const char *rows;  // [n x nvec] 16-byte vectors; a sparse mirror: the rows' (index, value) pairs, row after row
     int nvec, lpr_log2, nchunks;
     const int32_t *levels;     // [n]
     const int64_t *nbr_start;  // [n + 1]
@@ -79,20 +80,44 @@ struct HnswRun {
     int rows_per_trip;        // rows a lane group scores at once: 1, 2 or 4 (PGV_HNSW_ROWS_PER_TRIP, for A/B runs)
 };
 
+// What a walk over sparse rows takes on top (the kernel's LAST argument, so that the other kinds' arguments stay where they
+// were): where each row's pairs start, the queries in CSR, the pairs the LDS query region holds (the batch's longest
+// query, padded), the words of one wavefront's matched bitmap (0: inner product) and whether a wavefront fetches its next
+// row while it searches the current one (PGV_HNSW_SPARSE_PREFETCH, for A/B runs)
+struct HnswSparse {
+    const int64_t *row_ptr;  // [n + 1]
+    const int64_t *q_ptr;
+    const int32_t *q_idx;
+    const float *q_val;
+    int q_cap, bm_words, prefetch;
+};
+
+// bytes of the query region of a sparse walk's LDS: the query's pairs, then one matched bitmap per wavefront
+__host__ __device__ inline size_t sparse_query_bytes(int sq_cap, int bm_words) {
+    return (size_t)sq_cap * sizeof(QElem) + (size_t)kHnswWaves * bm_words * sizeof(uint32_t);
+}
+
 template <typename T, int METRIC>
 __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
-    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter) {
+    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter, HnswSparse sp) {
     const int nq = run.nq, ef = run.ef, k = run.k;
     int64_t *__restrict__ out_elem = run.out_elem;
     float *__restrict__ out_dist = run.out_dist;
     int64_t *__restrict__ out_scored = run.out_scored;
     constexpr int N = VecTraits<T>::N;
     constexpr bool kBits = std::is_same_v<T, BitRow>;
+    constexpr bool kSparse = std::is_same_v<T, SparseRow>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lm0 = 2 * g.m;
     // layout: query row | W keys [2][ef] | W ids [2][ef] | batch keys [lm0] | batch ids [lm0] | T ids [ef] | scalars
+    // (a sparse walk's query region: the query's (index, value) pairs [sq_cap] | matched bitmaps [waves][bm_words])
     Raw16 *lq = reinterpret_cast<Raw16 *>(smem);
-    uint32_t *wk = reinterpret_cast<uint32_t *>(smem + (size_t)g.nvec * sizeof(Raw16));
+    size_t query_bytes;
+    if constexpr (kSparse)
+        query_bytes = sparse_query_bytes(sp.q_cap, sp.bm_words);
+    else
+        query_bytes = (size_t)g.nvec * sizeof(Raw16);
+    uint32_t *wk = reinterpret_cast<uint32_t *>(smem + query_bytes);
     uint32_t *wi = wk + 2 * ef;
     uint32_t *bk = wi + 2 * ef;
     int32_t *bi = reinterpret_cast<int32_t *>(bk + lm0);
@@ -146,7 +171,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                 if constexpr (kBits) {
 #pragma unroll
                     for (int r = 0; r < R; r++) acc[r] += ok ? hamming16(rv[r], qv) : 0;
-                } else {
+                } else if constexpr (!kSparse) {  // (a sparse walk never comes here: score_sparse below)
                     Unpacked<T> uq(qv);
 #pragma unroll
                     for (int r = 0; r < R; r++) {
@@ -163,15 +188,64 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             }
         }
     };
+    // A sparse mirror (T = SparseRow; hnsw_sparsevec_support, src/hnswutils.c:1361-1433: FUNCTION 1 is
+    // sparsevec_l2_squared_distance / _negative_inner_product / _l1_distance, src/sparsevec.c:826-869, :905-966, :1018-1060)
+    // scores a whole row per wavefront with sparse_pair.h's score_element -- pgv_sparse_distance_batch's value for the pair,
+    // bit for bit -- against the query's pairs in LDS.  Wavefront w takes rows w, w + 4, .. of the batch (at most 2 m / 4 <=
+    // 50).  A batch is a dependent chain bi[] -> the row's bounds -> the row's pairs: lane j first loads the bounds of the
+    // wavefront's j-th row, all rows at once, and with PREFETCH the pairs of the next row are requested before the current
+    // one is searched (rows of up to 256 pairs: the register copy; a longer row is read inside its search).
+    int sqn = 0;  // the current query's stored elements
+    auto score_sparse = [&](auto pf, int nb) __attribute__((always_inline)) {
+        constexpr bool PREFETCH = decltype(pf)::value;
+        const QElem *sq = reinterpret_cast<const QElem *>(smem);
+        uint32_t *bm = reinterpret_cast<uint32_t *>(smem + (size_t)sp.q_cap * sizeof(QElem)) + wave * sp.bm_words;
+        const QElem *re = reinterpret_cast<const QElem *>(g.rows);
+        const int mine = nb > wave ? (nb - wave + kHnswWaves - 1) / kHnswWaves : 0;  // <= 50 < 64: one lane per row
+        if (mine == 0) return;
+        const int ij = wave + kHnswWaves * lane;
+        const int32_t ej = bi[ij < nb ? ij : nb - 1];  // never predicate a load (see scan_kernel)
+        const int64_t rbj = sp.row_ptr[ej];
+        const int rnj = (int)(sp.row_ptr[ej + 1] - rbj);
+        RegRow cur;
+        if constexpr (PREFETCH) load_reg_row(cur, re + __shfl(rbj, 0), __shfl(rnj, 0), lane);
+        for (int j = 0; j < mine; j++) {
+            const int64_t rb = __shfl(rbj, j);
+            const int rn = __shfl(rnj, j);
+            RegRow nxt;
+            if constexpr (PREFETCH) {
+                const int jn = j + 1 < mine ? j + 1 : j;  // (the last trip asks for its own row again)
+                load_reg_row(nxt, re + __shfl(rbj, jn), __shfl(rnj, jn), lane);
+            } else {
+                load_reg_row(cur, re + rb, rn, lane);
+            }
+            float v;
+            if constexpr (METRIC == 0)
+                v = score_element<0>(cur, re + rb, rn, sq, sqn, bm, lane);
+            else if constexpr (METRIC == 1)
+                v = score_element<1>(cur, re + rb, rn, sq, sqn, bm, lane);
+            else
+                v = score_element<2>(cur, re + rb, rn, sq, sqn, bm, lane);
+            if (lane == kWave - 1) bk[wave + kHnswWaves * j] = float_to_key(v);
+            if constexpr (PREFETCH) cur = nxt;
+        }
+    };
     // (always inlined: as a called function -- what the fp16 instantiations got -- every batch of a walk saved and
     // restored registers through 208 bytes of scratch)
     auto score_batch = [&](int nb) __attribute__((always_inline)) {
-        if (run.rows_per_trip >= 4)
-            score_rows(std::integral_constant<int, 4>{}, nb);
-        else if (run.rows_per_trip == 2)
-            score_rows(std::integral_constant<int, 2>{}, nb);
-        else
-            score_rows(std::integral_constant<int, 1>{}, nb);
+        if constexpr (kSparse) {
+            if (sp.prefetch)
+                score_sparse(std::true_type{}, nb);
+            else
+                score_sparse(std::false_type{}, nb);
+        } else {
+            if (run.rows_per_trip >= 4)
+                score_rows(std::integral_constant<int, 4>{}, nb);
+            else if (run.rows_per_trip == 2)
+                score_rows(std::integral_constant<int, 2>{}, nb);
+            else
+                score_rows(std::integral_constant<int, 1>{}, nb);
+        }
     };
 
     for (;;) {
@@ -196,7 +270,12 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         }
 
         // query into LDS; the entry point is the first batch
-        {
+        if constexpr (kSparse) {
+            const int64_t qb = sp.q_ptr[qi];
+            sqn = (int)(sp.q_ptr[qi + 1] - qb);
+            QElem *sq = reinterpret_cast<QElem *>(smem);
+            for (int v = tid; v < sqn; v += kHnswThreads) sq[v] = {sp.q_idx[qb + v], sp.q_val[qb + v]};
+        } else {
             const char *qrow = run.qids ? g.rows + (size_t)run.qids[qi] * row_bytes : run.queries + (size_t)qi * row_bytes;
             for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
         }
@@ -448,13 +527,19 @@ __global__ __launch_bounds__(256) void hnsw_patch_kernel(int32_t *__restrict__ n
 
 template <typename T, int METRIC>
 int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *bitmaps, int words, int grid,
-                  int *counter) {
-    const size_t lds = (size_t)g.nvec * sizeof(Raw16) + (size_t)run.ef * 16 + (size_t)g.m * 16 + (size_t)run.ef * 4 + 64;
-    if (lds > 150 * 1024)
+                  int *counter, const HnswSparse &sp = HnswSparse{}) {
+    constexpr bool kSparse = std::is_same_v<T, SparseRow>;
+    const size_t query_bytes = kSparse ? sparse_query_bytes(sp.q_cap, sp.bm_words) : (size_t)g.nvec * sizeof(Raw16);
+    const size_t lds = query_bytes + (size_t)run.ef * 16 + (size_t)g.m * 16 + (size_t)run.ef * 4 + 64;
+    if (lds > 150 * 1024) {
+        if (kSparse)
+            PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d / a query of %d stored elements need %zu bytes of LDS (limit %d)",
+                     run.ef, g.m, sp.q_cap, lds, 150 * 1024);
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
+    }
     auto kern = hnsw_search_kernel<T, METRIC>;
     PGV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kHnswThreads), lds, ctx->stream, g, run, bitmaps, words, counter);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kHnswThreads), lds, ctx->stream, g, run, bitmaps, words, counter, sp);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
@@ -720,7 +805,27 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
     run.lcap = a.lcap;
     static const int per_trip = getenv("PGV_HNSW_ROWS_PER_TRIP") ? atoi(getenv("PGV_HNSW_ROWS_PER_TRIP")) : 4;
     run.rows_per_trip = per_trip >= 4 ? 4 : (per_trip == 1 ? 1 : 2);
+    static const int prefetch = getenv("PGV_HNSW_SPARSE_PREFETCH") ? atoi(getenv("PGV_HNSW_SPARSE_PREFETCH")) : 1;
     PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+    if (v.sparse()) {
+        HnswSparse sp;
+        sp.row_ptr = v.ptr;
+        sp.q_ptr = a.sparse_queries.ptr;
+        sp.q_idx = a.sparse_queries.idx;
+        sp.q_val = a.sparse_queries.val;
+        sp.q_cap = pad4(a.max_q_nnz);
+        sp.bm_words = v.metric == PGV_NEG_IP ? 0 : bitmap_words(a.max_q_nnz);
+        sp.prefetch = prefetch != 0;
+        // (the queries of a sparse walk are sparse vectors: the build's element-slot queries do not reach here)
+        if (!a.sparse_queries.ptr || a.qids) PGV_FAIL(PGV_ERR_ARG, "hnsw search: a sparse mirror takes sparse queries");
+        if (a.max_q_nnz > kSparseMaxNnz) PGV_FAIL(PGV_ERR_DIMS, "hnsw search: a query of %d stored elements", a.max_q_nnz);
+        switch (v.metric) {
+            case PGV_L2SQ: return launch_hnsw_t<SparseRow, 0>(ctx, g, run, bitmaps, words, grid, counter, sp);
+            case PGV_NEG_IP: return launch_hnsw_t<SparseRow, 1>(ctx, g, run, bitmaps, words, grid, counter, sp);
+            case PGV_L1: return launch_hnsw_t<SparseRow, 2>(ctx, g, run, bitmaps, words, grid, counter, sp);
+        }
+        PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
+    }
     return dispatch_rows(v, [&](auto *tp, auto mc) {
         return launch_hnsw_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, g, run, bitmaps, words, grid, counter);
     });

@@ -40,10 +40,16 @@
 // block and differ in the tile, so the re-reads of a block mostly hit the caches.  The query CSR is read once per
 // (tile, row block).
 //
-// Not here (include/pgv_hip.h says the same): HNSW over sparse elements (hnsw_sparsevec_support, HNSW_MAX_NNZ 1000,
-// src/hnswutils.c:1361-1430) -- the follow-up on top of this kernel --, a device-side sparsevec_l2_normalize, ext/ glue;
-// bench.py does not measure any of this (tools/bench_sparse_topk.py does).
+// The pair arithmetic itself (QElem, descend, add_term, row_side_*, score_pair) lives in sparse_pair.h: the HNSW walk over
+// a sparse mirror (hnsw_sparsevec_support, HNSW_MAX_NNZ 1000, src/hnswutils.c:1361-1433; kernels_hnsw.hip) scores its
+// batches with it, and so does sparse_pair_kernel below, which serves pgv_hnsw_score_sparse and pgv_hnsw_score_pairs over
+// such a mirror: one wavefront per (element, query) pair, the element row as the walk reads it, the query's elements
+// read from the caches (sparse_pack_kernel has laid them side by side).  DESIGN.md 4.6c.
+//
+// Not here (include/pgv_hip.h says the same): a device-side sparsevec_l2_normalize, building a graph over sparse
+// elements, ext/ glue; bench.py does not measure any of this (tools/bench_sparse_topk.py and tools/bench_sparse_hnsw.py do).
 #include "pgv_device.h"
+#include "sparse_pair.h"
 
 namespace pgv {
 
@@ -53,122 +59,7 @@ constexpr int kSpThreads = 256;
 constexpr int kSpWaves = kSpThreads / kWave;
 constexpr int kSparseTileNnz = 2048;     // stored query elements a shared tile holds at most
 constexpr int kSparseTileQueries = 128;  // queries of a tile at most
-constexpr int kSparseRegChunks = 4;      // a row of up to 4 x 64 stored elements stays in registers
 static_assert(kSparseRegChunks == 4, "sparse_tile_kernel instantiates row_side_reg for 1 .. 4 chunks");
-constexpr int kSparseMaxNnz = 16000;     // SPARSEVEC_MAX_NNZ (src/sparsevec.h)
-
-__host__ __device__ constexpr int pad4(int x) { return (x + 3) & ~3; }
-__host__ __device__ constexpr int bitmap_words(int nnz) { return pad4((nnz + 31) / 32); }
-
-// LDS ordering inside ONE wavefront (bitmap clear -> set -> sweep): the wavefront's LDS operations complete in order,
-// the fence keeps the compiler from moving them across and waits for the ones in flight
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// A query element in LDS: index and value side by side, so that one 8-byte read of the search brings both
-struct alignas(8) QElem {
-    int32_t i;
-    float v;
-};
-typedef int QPair __attribute__((ext_vector_type(2)));
-
-// Where index x stands among the n ascending indices at q: a descent by powers of two, `top` the largest one <= n (0 for
-// n = 0), so every lane makes the same trips.  pos counts the elements <= x and `last` is the last of them (index -1: none);
-// the query stores x iff last.i == x, at pos - 1, with last.v its value: nothing is read after the descent
-struct Found {
-    int pos;
-    QElem last;
-    __device__ __forceinline__ bool hit(int32_t x) const { return last.i == x; }
-};
-__device__ __forceinline__ void descend(Found &f, const QElem *q, int n, int s, int32_t x) {
-    const int t = f.pos + s;
-    // one 8-byte LDS read, made whether or not the step counts: never predicated
-    const QPair raw = *reinterpret_cast<const QPair *>(q + ((t <= n ? t : n) - 1));
-    const QElem e{raw.x, __int_as_float(raw.y)};
-    if (t <= n && e.i <= x) {
-        f.pos = t;
-        f.last = e;
-    }
-}
-
-// One stored row element against the query: its term into a0 (a1: the row's squared norm, cosine).  MODE 0: L2 squared,
-// 1: inner product, 2: L1, 3: cosine.  hit: the query stores the index too, at pos
-template <int MODE>
-__device__ __forceinline__ void add_term(const Found &f, int32_t ri, float rv, uint32_t *bm, float &a0, float &a1) {
-    const bool hit = f.hit(ri);
-    // an index the query does not store: (rv - 0)^2 = rv^2 and |rv - 0| = |rv|, the reference's own terms
-    const float b = hit ? f.last.v : 0.f;
-    if ((MODE == 0 || MODE == 2) && hit) atomicOr(&bm[(f.pos - 1) >> 5], 1u << ((f.pos - 1) & 31));
-    if (MODE == 0) {
-        const float d = rv - b;
-        a0 = __builtin_fmaf(d, d, a0);
-    } else if (MODE == 2) {
-        a0 += fabsf(rv - b);
-    } else {
-        if (hit) a0 = __builtin_fmaf(rv, b, a0);
-        if (MODE == 3) a1 = __builtin_fmaf(rv, rv, a1);
-    }
-}
-
-// A row of up to kSparseRegChunks x 64 stored elements, read once and kept across the tile's queries: lane l holds
-// elements l, l + 64, ..  Its NC = ceil(rn / 64) searches descend TOGETHER, so that NC LDS reads are in flight per step
-// instead of one (1.2 x at the learned-sparse shape against one search after the other, profiles/r21_sparse_topk.md)
-struct RegRow {
-    int32_t i[kSparseRegChunks];
-    float v[kSparseRegChunks];
-};
-template <int MODE, int NC>
-__device__ __forceinline__ void row_side_reg(const RegRow &row, int rn, const QElem *q, int qn, int top, uint32_t *bm,
-                                             int lane, float &a0, float &a1) {
-    Found f[NC];
-#pragma unroll
-    for (int c = 0; c < NC; c++) f[c] = {0, {-1, 0.f}};
-    for (int s = top; s > 0; s >>= 1) {  // (top > 0 only when qn > 0)
-#pragma unroll
-        for (int c = 0; c < NC; c++) descend(f[c], q, qn, s, row.i[c]);
-    }
-#pragma unroll
-    for (int c = 0; c < NC; c++)
-        if (c * kWave + lane < rn) add_term<MODE>(f[c], row.i[c], row.v[c], bm, a0, a1);
-}
-// A longer row: read again per query (from the caches), one search after the other
-template <int MODE>
-__device__ __forceinline__ void row_side_mem(const int32_t *ri, const float *rv, int rn, const QElem *q, int qn, int top,
-                                             uint32_t *bm, int lane, float &a0, float &a1) {
-    for (int e = lane; e < rn; e += kWave) {
-        const int32_t x = ri[e];
-        Found f{0, {-1, 0.f}};
-        for (int s = top; s > 0; s >>= 1) descend(f, q, qn, s, x);
-        add_term<MODE>(f, x, rv[e], bm, a0, a1);
-    }
-}
-
-// One (row, query) pair, this lane's share: row_side(top) adds the row's elements, then the query's unmatched ones (L2,
-// L1) come from the wavefront's bitmap.  q: the query's qn elements in LDS
-template <int MODE, typename RowSide>
-__device__ __forceinline__ void score_pair(RowSide row_side, const QElem *q, int qn, uint32_t *bm, int lane, float &a0) {
-    constexpr bool kBitmap = MODE == 0 || MODE == 2;
-    if (kBitmap) {
-        for (int w = lane; w < (qn + 31) / 32; w += kWave) bm[w] = 0u;
-        wave_lds_fence();
-    }
-    row_side(qn > 0 ? 1 << (31 - __clz(qn)) : 0);
-    if (kBitmap) {
-        wave_lds_fence();
-        for (int j = lane; j < qn; j += kWave) {
-            if (!((bm[j >> 5] >> (j & 31)) & 1u)) {
-                const float a = q[j].v;
-                if (MODE == 0)
-                    a0 = __builtin_fmaf(a, a, a0);
-                else
-                    a0 += fabsf(a);
-            }
-        }
-        wave_lds_fence();  // the sweep has read the bitmap before the next pair clears it
-    }
-}
 
 // grid: (row blocks) x (tiles), consecutive workgroups sharing a row block.  out: float mat[(q - 0) * out_stride + row]
 // for MODE 0..2 (q counts through the launch's queries), double out[row] for MODE 3 (one query)
@@ -257,6 +148,34 @@ __global__ __launch_bounds__(kSpThreads) void sparse_tile_kernel(
     }
 }
 
+// idx[i], val[i] -> elem[i] = (idx[i], val[i]): the element rows of a sparse HNSW mirror and the staged queries of its
+// pair scorer
+__global__ __launch_bounds__(256) void sparse_pack_kernel(const int32_t *__restrict__ idx, const float *__restrict__ val,
+                                                          int64_t total, QElem *__restrict__ elem) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
+        elem[i] = {idx[i], val[i]};
+}
+
+// pair i = (element slot[i] of the mirror, query query_of[i] -- NULL: query 0 -- of the packed queries): one wavefront per pair,
+// grid-stride.  The value is score_element's: sparse_tile_kernel's for the same two vectors, bit for bit
+template <int MODE>
+__global__ __launch_bounds__(kSpThreads) void sparse_pair_kernel(const int64_t *__restrict__ r_ptr, const QElem *__restrict__ r_elem,
+                                                                 const int64_t *__restrict__ q_ptr, const QElem *__restrict__ q_elem,
+                                                                 const int32_t *__restrict__ slot, const int32_t *__restrict__ query_of,
+                                                                 int64_t npairs, float *__restrict__ out) {
+    __shared__ uint32_t s_bm[kSpWaves][bitmap_words(kSparseMaxNnz)];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    for (int64_t p = (int64_t)blockIdx.x * kSpWaves + wave; p < npairs; p += (int64_t)gridDim.x * kSpWaves) {
+        const int64_t r = slot[p], q = query_of ? query_of[p] : 0;
+        const int64_t rb = r_ptr[r], qb = q_ptr[q];
+        const int rn = (int)(r_ptr[r + 1] - rb), qn = (int)(q_ptr[q + 1] - qb);
+        RegRow row;
+        load_reg_row(row, r_elem + rb, rn, lane);
+        const float v = score_element<MODE>(row, r_elem + rb, rn, q_elem + qb, qn, s_bm[wave], lane);
+        if (lane == kWave - 1) out[p] = v;
+    }
+}
+
 }  // namespace
 
 int sparse_tile_nnz() { return kSparseTileNnz; }
@@ -318,6 +237,38 @@ int launch_sparse_tiles(pgv_ctx *ctx, int mode, const SparseTile *tiles_dev, int
             return launch_sparse_tiles_t<3>(ctx, tiles_dev, ntiles, lds, bm_words, q, r, out, out_stride);
     }
     PGV_FAIL(PGV_ERR_ARG, "sparse scan: unknown mode %d", mode);
+}
+
+int launch_sparse_pack(pgv_ctx *ctx, const int32_t *idx, const float *val, int64_t total, void *elem) {
+    if (total <= 0) return PGV_OK;
+    const int64_t want = (total + 255) / 256, cap = (int64_t)ctx->num_cus * 32;
+    hipLaunchKernelGGL(sparse_pack_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, ctx->stream, idx, val, total,
+                       static_cast<QElem *>(elem));
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_sparse_pairs(pgv_ctx *ctx, const RowsView &v, const int64_t *q_ptr, const void *q_elem, const int32_t *slot,
+                        const int32_t *query_of, int64_t npairs, float *out) {
+    if (npairs <= 0) return PGV_OK;
+    if (!v.sparse()) PGV_FAIL(PGV_ERR_ARG, "sparse pairs: not a sparse mirror");
+    const int64_t want = (npairs + kSpWaves - 1) / kSpWaves, cap = (int64_t)ctx->num_cus * 32;
+    const dim3 grid((unsigned)(want < cap ? want : cap));
+    const QElem *re = static_cast<const QElem *>(v.rows), *qe = static_cast<const QElem *>(q_elem);
+    switch (v.metric) {
+        case PGV_L2SQ:
+            hipLaunchKernelGGL(sparse_pair_kernel<0>, grid, dim3(kSpThreads), 0, ctx->stream, v.ptr, re, q_ptr, qe, slot, query_of, npairs, out);
+            break;
+        case PGV_NEG_IP:
+            hipLaunchKernelGGL(sparse_pair_kernel<1>, grid, dim3(kSpThreads), 0, ctx->stream, v.ptr, re, q_ptr, qe, slot, query_of, npairs, out);
+            break;
+        case PGV_L1:
+            hipLaunchKernelGGL(sparse_pair_kernel<2>, grid, dim3(kSpThreads), 0, ctx->stream, v.ptr, re, q_ptr, qe, slot, query_of, npairs, out);
+            break;
+        default: PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
+    }
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
 }
 
 }  // namespace pgv

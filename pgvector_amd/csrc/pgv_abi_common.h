@@ -434,3 +434,14 @@ int lloyd_finish_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &
                      const int32_t *counts_dev, const int32_t *counts_host, Rng &rng, void *centers_dev);
 int check_centers_dev(pgv_ctx *ctx, pgv_ops ops, pgv_dtype dtype, const RowGeom &g, int dim, int k, const void *centers_dev);
 }
+
+// pgv_abi_sparse.hip: a caller's CSR triple (ptr [n + 1], idx, val; each host or device memory) checked and on the device.
+// host_ptr: ptr on the host -- the caller's, or with want_host_ptr the checked copy of a device ptr; null: not known
+struct StagedCsr {
+    SparseCsr dev{nullptr, nullptr, nullptr, 0};
+    std::vector<int64_t> ptr_copy;
+    const int64_t *host_ptr = nullptr;
+};
+int check_sparse_dim(const char *who, int dim);
+int stage_csr(pgv_ctx *ctx, const char *who, const char *what, int dim, const int64_t *ptr, const int32_t *idx, const float *val,
+              int64_t n, bool want_host_ptr, DBuf &buf_ptr, DBuf &buf_idx, DBuf &buf_val, StagedCsr *out);

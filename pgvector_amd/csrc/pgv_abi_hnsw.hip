@@ -19,10 +19,28 @@ static size_t hnsw_payload_offset(int64_t n, size_t row_bytes) {
 // a bit mirror (pgv_hnsw_upload_bits): rows of whole bytes scored by xor + popcount; no build-side entry serves it
 static bool hnsw_is_bits(const pgv_hnsw *h) { return h->nbits > 0; }
 
-#define PGV_NO_BITS(h, who)                                                                                      \
+// ... and a sparse mirror (pgv_hnsw_upload_sparse): CSR rows scored by sparse_pair.h; searched and scored through the
+// _sparse entries, not built on either
+static bool hnsw_is_sparse(const pgv_hnsw *h) { return h->sparse; }
+
+#define PGV_NO_BUILD(h, who)                                                                                      \
     do {                                                                                                         \
         if ((h) && hnsw_is_bits(h))                                                                              \
             PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits) is searched and scored, not built on", who); \
+        if ((h) && hnsw_is_sparse(h))                                                                            \
+            PGV_FAIL(PGV_ERR_ARG, "%s: a sparse mirror (pgv_hnsw_upload_sparse) is searched and scored, not built on", who); \
+    } while (0)
+
+// the entries that take dense queries or rows, on a sparse mirror; the _sparse entries on any other mirror
+#define PGV_NO_SPARSE(h, who, twin)                                                                              \
+    do {                                                                                                         \
+        if ((h) && hnsw_is_sparse(h))                                                                            \
+            PGV_FAIL(PGV_ERR_ARG, "%s: a sparse mirror (pgv_hnsw_upload_sparse) takes sparse queries: use %s", who, twin); \
+    } while (0)
+#define PGV_ONLY_SPARSE(h, who)                                                                                  \
+    do {                                                                                                         \
+        if ((h) && !hnsw_is_sparse(h))                                                                           \
+            PGV_FAIL(PGV_ERR_ARG, "%s: not a sparse mirror (pgv_hnsw_upload_sparse)", who);                      \
     } while (0)
 
 // the geometry of a mirror's rows: dim elements of dtype, or nbits bits
@@ -219,6 +237,9 @@ static constexpr uint64_t kHnswHandleMagic = 0x7067765f686e7731ull;  // "pgv_hnw
 
 int pgv_hnsw_export(pgv_hnsw *h, pgv_index_handle *out) {
     if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_export: handle/out is NULL");
+    if (hnsw_is_sparse(h))
+        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_export: a sparse mirror (pgv_hnsw_upload_sparse) is not exported: the handle carries one "
+                              "allocation of fixed-width rows");
     if (h->imported || h->view_of) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_export: export from the process that uploaded the mirror");
     if (!h->elements || !h->graph.mem || h->graph.m == 0)
         PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_export: needs a non-empty mirror with its graph set (pgv_hnsw_set_graph)");
@@ -323,6 +344,7 @@ int pgv_hnsw_get_payload(pgv_hnsw *h, const int64_t *elements, int n, void *out)
 int pgv_hnsw_score(pgv_hnsw *h, const void *queries, int nq, const int32_t *slot, const int32_t *query_of,
                    int64_t npairs, float *out) {
     if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_score: handle/out is NULL");
+    PGV_NO_SPARSE(h, "pgv_hnsw_score", "pgv_hnsw_score_sparse");
     if (npairs < 0 || nq < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     if (npairs == 0) return PGV_OK;
     if (!queries || !slot) PGV_FAIL(PGV_ERR_ARG, "queries/slot is NULL");
@@ -402,6 +424,7 @@ static int hnsw_search_into(pgv_hnsw *h, const int32_t *e_dev, const int32_t *l_
 int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int k, int64_t *out_elem,
                     float *out_dist, int64_t *out_scored) {
     if (!h || !out_elem || !out_dist) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_search: handle/out is NULL");
+    PGV_NO_SPARSE(h, "pgv_hnsw_search", "pgv_hnsw_search_sparse");
     hnsw_view_refresh(h);
     if (nq < 0) PGV_FAIL(PGV_ERR_ARG, "bad query count");
     if (ef_search < 1 || ef_search > 1000)
@@ -435,10 +458,155 @@ int pgv_hnsw_search(pgv_hnsw *h, const void *queries, int nq, int ef_search, int
     return sync_if(ctx, need);
 }
 
+// ------------------------------------------------------------------ HNSW over sparsevec elements
+constexpr int kHnswMaxNnz = 1000;  // HNSW_MAX_NNZ (src/hnsw.h:34)
+
+// The element rows of an HNSW index over sparsevec (`USING hnsw (... sparsevec_l2_ops / _ip_ops / _cosine_ops / _l1_ops)`,
+// sql/vector.sql:1189-1212; type info hnsw_sparsevec_support, src/hnswutils.c:1361-1433).  One allocation: the rows'
+// (index, value) pairs, row after row, plus one slack pair (a lane past an empty last row reads it) | ptr [n + 1] | payload
+int pgv_hnsw_upload_sparse(pgv_ctx *ctx, pgv_metric metric, int dim, const int64_t *row_ptr, const int32_t *row_idx,
+                           const float *row_val, int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {
+    const char *who = "pgv_hnsw_upload_sparse";
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_sparse: ctx/out is NULL");
+    *out = nullptr;
+    PGV_TRY(check_metric(metric));
+    PGV_TRY(check_sparse_dim(who, dim));
+    if (n < 0 || n > 0x7fffffff || (n > 0 && !row_ptr)) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_sparse: bad n / row_ptr is NULL");
+    if (payload_bytes < 0 || payload_bytes > 4096 || (payload_bytes & 3) || (payload_bytes > 0 && n > 0 && !payload))
+        PGV_FAIL(PGV_ERR_ARG, "payload: 0..4096 bytes per element in whole words, got %d", payload_bytes);
+    PGV_HIP(hipSetDevice(ctx->device));
+    const int64_t none[1] = {0};
+    StagedCsr r;
+    // (the host copy of a device row_ptr is checked like a host one: the walk's register rows are sized from it)
+    PGV_TRY(stage_csr(ctx, who, "elements", dim, n > 0 ? row_ptr : none, row_idx, row_val, n, true, ctx->plan_b, ctx->rows_stage,
+                      ctx->idx_stage, &r));
+    for (int64_t v = 0; v < n; v++)
+        if (r.host_ptr[v + 1] - r.host_ptr[v] > kHnswMaxNnz)
+            PGV_FAIL(PGV_ERR_DIMS, "pgv_hnsw_upload_sparse: element %lld has %lld stored elements: sparsevec cannot have more than %d "
+                                   "non-zero elements for hnsw index (src/hnswutils.c:1371)",
+                     (long long)v, (long long)(r.host_ptr[v + 1] - r.host_ptr[v]), kHnswMaxNnz);
+    const int64_t total = r.host_ptr[n];
+    pgv_hnsw *h = new (std::nothrow) pgv_hnsw();
+    if (!h) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
+    h->ctx = ctx;
+    h->metric = metric;
+    h->dtype = PGV_F32;
+    h->dim = dim;
+    h->sparse = true;
+    h->n = n;
+    const size_t elem_bytes = (((size_t)total + 1) * 8 + 255) & ~(size_t)255;
+    const size_t ptr_bytes = (((size_t)n + 1) * sizeof(int64_t) + 255) & ~(size_t)255;
+    const size_t pay_total = (size_t)payload_bytes * (size_t)n;
+    const size_t bytes = elem_bytes + ptr_bytes + (pay_total ? pay_total : 4);
+    if (malloc_exportable(&h->elements, bytes) != hipSuccess) {
+        delete h;
+        PGV_FAIL(PGV_ERR_NOMEM, "hipMalloc(%zu) for sparse hnsw elements failed", bytes);
+    }
+    char *base = static_cast<char *>(h->elements);
+    h->sparse_ptr = reinterpret_cast<const int64_t *>(base + elem_bytes);
+    h->payload_bytes = payload_bytes;
+    h->payload = payload_bytes > 0 ? base + elem_bytes + ptr_bytes : nullptr;
+    hipError_t e = hipMemsetAsync(base + (size_t)total * 8, 0, 8, ctx->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(base + elem_bytes, r.dev.ptr, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && pay_total)
+        e = hipMemcpyAsync(h->payload, payload, pay_total, is_device_ptr(payload) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                           ctx->stream);
+    int rc = PGV_OK;
+    if (e == hipSuccess) rc = launch_sparse_pack(ctx, r.dev.idx, r.dev.val, total, h->elements);
+    if (e == hipSuccess && rc == PGV_OK) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess || rc != PGV_OK) {
+        pgv_hnsw_free(h);
+        if (rc != PGV_OK) return rc;
+        PGV_FAIL(PGV_ERR_DEVICE, "sparse hnsw upload failed: %s", hipGetErrorString(e));
+    }
+    *out = h;
+    return PGV_OK;
+}
+
+// queries in CSR -> the device, validated like pgv_sparse_topk's; *max_nnz: the longest one's stored elements
+static int hnsw_stage_sparse_queries(pgv_hnsw *h, const char *who, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val,
+                                     int nq, StagedCsr *q, int *max_nnz) {
+    pgv_ctx *ctx = h->ctx;
+    PGV_TRY(stage_csr(ctx, who, "queries", h->dim, q_ptr, q_idx, q_val, nq, true, ctx->plan_c, ctx->q_stage, ctx->centers_stage, q));
+    *max_nnz = 0;
+    for (int i = 0; i < nq; i++) *max_nnz = std::max(*max_nnz, (int)(q->host_ptr[i + 1] - q->host_ptr[i]));
+    return PGV_OK;
+}
+
+// HnswGetDistance over sparse elements for the caller's (element, query) pairs: pgv_hnsw_score with sparse queries
+int pgv_hnsw_score_sparse(pgv_hnsw *h, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq,
+                          const int32_t *slot, const int32_t *query_of, int64_t npairs, float *out) {
+    const char *who = "pgv_hnsw_score_sparse";
+    if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_score_sparse: handle/out is NULL");
+    PGV_ONLY_SPARSE(h, who);
+    if (npairs < 0 || nq < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
+    if (npairs == 0) return PGV_OK;
+    if (!q_ptr || !slot) PGV_FAIL(PGV_ERR_ARG, "q_ptr/slot is NULL");
+    pgv_ctx *ctx = h->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    StagedCsr q;
+    int max_nnz = 0;
+    PGV_TRY(hnsw_stage_sparse_queries(h, who, q_ptr, q_idx, q_val, nq, &q, &max_nnz));
+    // the queries' pairs side by side, as the elements are kept
+    const int64_t qtotal = q.host_ptr[nq];
+    PGV_TRY(ctx->dist_mat.ensure((size_t)(qtotal > 0 ? qtotal : 1) * 8));
+    PGV_TRY(launch_sparse_pack(ctx, q.dev.idx, q.dev.val, qtotal, ctx->dist_mat.p));
+    const void *s_dev, *qo_dev = nullptr;
+    PGV_TRY(stage_flat(ctx, slot, sizeof(int32_t) * (size_t)npairs, ctx->idx_stage, &s_dev));
+    if (query_of) PGV_TRY(stage_flat(ctx, query_of, sizeof(int32_t) * (size_t)npairs, ctx->plan_d, &qo_dev));
+    OutArg od;
+    PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
+    PGV_TRY(launch_sparse_pairs(ctx, hnsw_rows(h), q.dev.ptr, ctx->dist_mat.p, static_cast<const int32_t *>(s_dev),
+                                static_cast<const int32_t *>(qo_dev), npairs, od.as<float>()));
+    bool need = false;
+    PGV_TRY(od.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
+// pgv_hnsw_search over a sparse mirror: hnswgettuple's first batch (src/hnswscan.c:25-56) with sparsevec queries
+int pgv_hnsw_search_sparse(pgv_hnsw *h, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq, int ef_search,
+                           int k, int64_t *out_elem, float *out_dist, int64_t *out_scored) {
+    const char *who = "pgv_hnsw_search_sparse";
+    if (!h || !out_elem || !out_dist) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_search_sparse: handle/out is NULL");
+    PGV_ONLY_SPARSE(h, who);
+    hnsw_view_refresh(h);
+    if (nq < 0) PGV_FAIL(PGV_ERR_ARG, "bad query count");
+    if (ef_search < 1 || ef_search > 1000)
+        PGV_FAIL(PGV_ERR_ARG, "hnsw.ef_search must be 1..1000 (src/hnsw.c:93-94), got %d", ef_search);
+    if (k < 1 || k > ef_search) PGV_FAIL(PGV_ERR_ARG, "k must be 1..ef_search, got %d", k);
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_search_sparse needs pgv_hnsw_set_graph first");
+    if (nq == 0) return PGV_OK;
+    if (!q_ptr) PGV_FAIL(PGV_ERR_ARG, "q_ptr is NULL");
+    pgv_ctx *ctx = h->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    PGV_TRY(hnsw_graph_acquire(h));
+    StagedCsr q;
+    HnswSearchArgs a;
+    PGV_TRY(hnsw_stage_sparse_queries(h, who, q_ptr, q_idx, q_val, nq, &q, &a.max_q_nnz));
+    OutArg oe, od, os;
+    PGV_TRY(oe.init(out_elem, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
+    PGV_TRY(os.init(out_scored, sizeof(int64_t) * (size_t)nq, ctx->sel_b));
+    a.sparse_queries = q.dev;
+    a.nq = nq;
+    a.ef = ef_search;
+    a.k = k;
+    a.out_elem = oe.as<int64_t>();
+    a.out_dist = od.as<float>();
+    a.out_scored = out_scored ? os.as<int64_t>() : nullptr;
+    PGV_TRY(hnsw_run_search(h, a));
+    bool need = false;
+    PGV_TRY(oe.finish(ctx, &need));
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(os.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
 int pgv_hnsw_build_search(pgv_hnsw *h, const int32_t *elements, const int32_t *insert_levels, int nq,
                           int ef_construction, int layer_cap, int32_t *out_ids, float *out_dist, int32_t *out_count) {
     if (!h || !out_ids || !out_dist || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_search: handle/out is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_build_search");
+    PGV_NO_BUILD(h, "pgv_hnsw_build_search");
     hnsw_view_refresh(h);
     if (nq < 0 || layer_cap < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     if (ef_construction < 4 || ef_construction > 1000)
@@ -532,7 +700,7 @@ int pgv_hnsw_build_neighbors(pgv_hnsw *h, const int32_t *elements, const int32_t
                              int32_t *out_count, int64_t *out_pairs) {
     if (!h || !out_ids || !out_dist || !out_closer || !out_count)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_neighbors: handle/out is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_build_neighbors");
+    PGV_NO_BUILD(h, "pgv_hnsw_build_neighbors");
     hnsw_view_refresh(h);
     PGV_TRY(hnsw_build_args(h, "pgv_hnsw_build_neighbors", nq, ef_construction, layer_cap));
     if (out_pairs) *out_pairs = 0;
@@ -563,7 +731,7 @@ int pgv_hnsw_build_neighbors(pgv_hnsw *h, const int32_t *elements, const int32_t
 int pgv_hnsw_build_search_keep(pgv_hnsw *h, const int32_t *elements, const int32_t *insert_levels, int nq, int ef_construction,
                                int layer_cap, int slot) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_search_keep: handle is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_build_search_keep");
+    PGV_NO_BUILD(h, "pgv_hnsw_build_search_keep");
     hnsw_view_refresh(h);
     pgv_hnsw *o = h->view_of ? h->view_of : h;
     if (!o->link) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_build_search_keep needs pgv_hnsw_link_begin");
@@ -597,7 +765,7 @@ int pgv_hnsw_build_select_kept(pgv_hnsw *h, int slot, int32_t *out_ids, float *o
                                int64_t *out_pairs) {
     if (!h || !out_ids || !out_dist || !out_closer || !out_count)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_build_select_kept: handle/out is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_build_select_kept");
+    PGV_NO_BUILD(h, "pgv_hnsw_build_select_kept");
     // (no view refresh: the entry point may be moving under pgv_hnsw_link_apply on another thread, and nothing here looks
     // at the graph -- the kept lists, the element rows and m, which is fixed for the build)
     pgv_hnsw *o = h->view_of ? h->view_of : h;
@@ -626,8 +794,12 @@ int pgv_hnsw_score_pairs(pgv_hnsw *h, const int32_t *a, const int32_t *b, int64_
     OutArg od;
     PGV_TRY(od.init(out, sizeof(float) * (size_t)npairs, ctx->out_stage));
     // the element mirror is its own query array: pair i = (row a[i], "query" b[i])
-    PGV_TRY(launch_score_gather(ctx, hnsw_rows(h), h->elements, static_cast<const int32_t *>(a_dev),
-                                static_cast<const int32_t *>(b_dev), npairs, od.as<float>()));
+    if (hnsw_is_sparse(h))
+        PGV_TRY(launch_sparse_pairs(ctx, hnsw_rows(h), h->sparse_ptr, h->elements, static_cast<const int32_t *>(a_dev),
+                                    static_cast<const int32_t *>(b_dev), npairs, od.as<float>()));
+    else
+        PGV_TRY(launch_score_gather(ctx, hnsw_rows(h), h->elements, static_cast<const int32_t *>(a_dev),
+                                    static_cast<const int32_t *>(b_dev), npairs, od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     return sync_if(ctx, need);
@@ -636,7 +808,7 @@ int pgv_hnsw_score_pairs(pgv_hnsw *h, const int32_t *a, const int32_t *b, int64_
 int pgv_hnsw_score_groups(pgv_hnsw *h, const int32_t *ids, const int64_t *ids_start, const int32_t *from,
                           const int64_t *pair_start, int ngroups, int64_t nids, int64_t npairs, float *out) {
     if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_score_groups: handle/out is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_score_groups");
+    PGV_NO_BUILD(h, "pgv_hnsw_score_groups");
     if (ngroups < 0 || nids < 0 || npairs < 0) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     if (ngroups == 0 || npairs == 0) return PGV_OK;
     if (!ids || !ids_start || !from || !pair_start) PGV_FAIL(PGV_ERR_ARG, "ids/ids_start/from/pair_start is NULL");
@@ -705,7 +877,7 @@ static void hnsw_link_free(pgv_hnsw *o) {
 
 int pgv_hnsw_link_begin(pgv_hnsw *h) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin: handle is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_link_begin");
+    PGV_NO_BUILD(h, "pgv_hnsw_link_begin");
     if (h->imported || h->view_of) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_begin: an imported mirror / a view is read-only");
     if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_begin needs pgv_hnsw_set_graph first");
     pgv_ctx *ctx = h->ctx;
@@ -742,7 +914,7 @@ int pgv_hnsw_link_begin(pgv_hnsw *h) {
 int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *linked, int nq, int layer_cap,
                           const int32_t *sel_ids, const float *sel_dist, const uint8_t *sel_closer, const int32_t *sel_count,
                           int64_t *out_pairs) {
-    PGV_NO_BITS(h, "pgv_hnsw_link_prepare");
+    PGV_NO_BUILD(h, "pgv_hnsw_link_prepare");
     if (!h || !h->link) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_prepare needs pgv_hnsw_link_begin");
     if (nq < 0 || layer_cap < 1) PGV_FAIL(PGV_ERR_ARG, "bad sizes");
     HnswLinkState *L = h->link;
@@ -854,7 +1026,7 @@ int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *l
 }
 
 int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
-    PGV_NO_BITS(h, "pgv_hnsw_link_apply");
+    PGV_NO_BUILD(h, "pgv_hnsw_link_apply");
     if (!h || !h->link || !h->link->prepared) PGV_FAIL(PGV_ERR_STATE, "pgv_hnsw_link_apply needs pgv_hnsw_link_prepare");
     if (entry < -1 || entry >= h->n) PGV_FAIL(PGV_ERR_ARG, "entry point %d out of range", (int)entry);
     HnswLinkState *L = h->link;
@@ -925,7 +1097,7 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
 
 int pgv_hnsw_link_end(pgv_hnsw *h, int32_t *out_nbr, int64_t *out_pairs, int64_t *out_deferred) {
     if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_link_end: handle is NULL");
-    PGV_NO_BITS(h, "pgv_hnsw_link_end");
+    PGV_NO_BUILD(h, "pgv_hnsw_link_end");
     if (out_pairs) *out_pairs = 0;
     if (out_deferred) *out_deferred = 0;
     if (!h->link) return PGV_OK;

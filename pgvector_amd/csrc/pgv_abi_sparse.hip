@@ -7,10 +7,16 @@ namespace {
 constexpr int kSparseMaxDim = 1000000000;  // SPARSEVEC_MAX_DIM (src/sparsevec.h:8)
 constexpr int kSparseMaxNnz = 16000;       // SPARSEVEC_MAX_NNZ (src/sparsevec.h:9)
 
+}  // namespace
+
+// (check_sparse_dim and stage_csr are declared in pgv_abi_common.h: the sparse HNSW entries of pgv_abi_hnsw.hip validate
+// and stage their CSR arguments with them)
 int check_sparse_dim(const char *who, int dim) {
     if (dim < 1 || dim > kSparseMaxDim) PGV_FAIL(PGV_ERR_DIMS, "%s: dimensions %d outside 1..%d", who, dim, kSparseMaxDim);
     return PGV_OK;
 }
+
+namespace {
 
 // ptr [n + 1] on the host: starts at 0, monotone, no vector above the reference's limit of stored elements
 int check_sparse_ptr(const char *who, const char *what, const int64_t *ptr, int64_t n) {
@@ -49,14 +55,12 @@ int check_sparse_elements(const char *who, const char *what, int dim, const int6
     return PGV_OK;
 }
 
-// A caller's CSR triple on the device.  Host arrays are validated before anything is launched; device arrays are used
-// in place, unchecked (pgv_rerank's rule for cand) -- except ptr when the host needs it anyway (want_host_ptr: the
-// queries' tiles are planned from it), whose copy is checked like a host ptr, since the kernel's LDS is sized from it
-struct StagedCsr {
-    SparseCsr dev{nullptr, nullptr, nullptr, 0};
-    std::vector<int64_t> ptr_copy;     // ptr on the host when it came from the device
-    const int64_t *host_ptr = nullptr;  // ... or the caller's; null: not known
-};
+}  // namespace
+
+// A caller's CSR triple on the device (StagedCsr: pgv_abi_common.h).  Host arrays are validated before anything is
+// launched; device arrays are used in place, unchecked (pgv_rerank's rule for cand) -- except ptr when the host needs it
+// anyway (want_host_ptr: the queries' tiles are planned from it), whose copy is checked like a host ptr, since the
+// kernel's LDS is sized from it
 int stage_csr(pgv_ctx *ctx, const char *who, const char *what, int dim, const int64_t *ptr, const int32_t *idx, const float *val,
               int64_t n, bool want_host_ptr, DBuf &buf_ptr, DBuf &buf_idx, DBuf &buf_val, StagedCsr *out) {
     out->dev.n = n;
@@ -90,6 +94,8 @@ int stage_csr(pgv_ctx *ctx, const char *who, const char *what, int dim, const in
     out->dev.val = static_cast<const float *>(p);
     return PGV_OK;
 }
+
+namespace {
 
 // the tiles of one launch: queries [q0, q0 + nq) of the staged query CSR
 struct TileRun {

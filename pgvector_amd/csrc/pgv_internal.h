@@ -87,14 +87,18 @@ RowGeom bit_row_geom(int nbits);
 // Rows as the scoring and scan kernels and the HNSW walk take them: where they are, how many, how a row is laid out,
 // what an element is and which distance goes with it.  Built where it is needed (hnsw_rows / ivf_rows and its kin for a
 // mirror, in place for a caller's staged rows), never stored
-enum class RowKind { F32, F16, Bits };  // Bits: packed bit strings scored by xor + popcount; the metric is unused
+// Bits: packed bit strings scored by xor + popcount; the metric is unused.  Sparse: sparsevec elements in CSR, a row's
+// (index, value) pairs side by side (sparse_pair.h's QElem) from rows[ptr[r]] on; geom is unused
+enum class RowKind { F32, F16, Bits, Sparse };
 struct RowsView {
-    const void *rows;  // [n x geom.nvec] 16-byte vectors
+    const void *rows;  // [n x geom.nvec] 16-byte vectors; Sparse: [ptr[n] + 1] 8-byte (index, value) pairs
     int64_t n;
     RowGeom geom;
     RowKind kind;
     pgv_metric metric;
+    const int64_t *ptr = nullptr;  // Sparse: [n + 1] where each row's pairs start
     bool bits() const { return kind == RowKind::Bits; }
+    bool sparse() const { return kind == RowKind::Sparse; }
     pgv_dtype dtype() const { return kind == RowKind::F16 ? PGV_F16 : PGV_F32; }
     size_t row_bytes() const { return bits() ? (size_t)geom.ld : (size_t)geom.ld * elem_size(dtype()); }
 };
@@ -275,6 +279,11 @@ struct HnswElements {
     // > 0: a mirror of packed bit strings (pgv_hnsw_upload_bits).  Its element type is not a pgv_dtype: rows are nbits
     // bits in geom.nvec 16-byte vectors, scored by xor + popcount; metric, dtype and dim are unused (dim = nbits)
     int nbits = 0;
+    // a mirror of sparsevec elements (pgv_hnsw_upload_sparse): `elements` holds the rows' (index, value) pairs one row
+    // after the other (and one slack pair), sparse_ptr [n + 1] where each row starts -- in the same allocation, like the
+    // payload; dtype and geom are unused, dim is the vectors' dimension
+    bool sparse = false;
+    const int64_t *sparse_ptr = nullptr;
     int64_t n = 0;
     pgv::RowGeom geom{};
     void *elements = nullptr;  // [n x ld]
@@ -298,6 +307,7 @@ struct pgv_hnsw : HnswElements {
 namespace pgv {
 // a mirror's rows as its kernels take them
 inline RowsView hnsw_rows(const pgv_hnsw *h) {
+    if (h->sparse) return {h->elements, h->n, h->geom, RowKind::Sparse, h->metric, h->sparse_ptr};
     return {h->elements, h->n, h->geom, h->nbits > 0 ? RowKind::Bits : row_kind(h->dtype), h->metric};
 }
 // ... an IVFFlat mirror's: the only place that turns pgv_index::nbits into a row kind
@@ -616,11 +626,19 @@ void sparse_plan_tiles(const int64_t *q_ptr, int nq, std::vector<SparseTile> *ti
 // query; mode 3 cosine distance (one tile of one query): double out[row].  max_*: over the tiles, for the LDS size
 int launch_sparse_tiles(pgv_ctx *ctx, int mode, const SparseTile *tiles_dev, int ntiles, int max_tile_nnz, int max_tile_nq,
                         int max_q_nnz, const SparseCsr &q, const SparseCsr &r, void *out, int64_t out_stride);
+// elem[i] = (idx[i], val[i]), 8 bytes each: how a sparse HNSW mirror keeps its rows and its pair scorer takes queries
+int launch_sparse_pack(pgv_ctx *ctx, const int32_t *idx, const float *val, int64_t total, void *elem);
+// pair i = (row slot[i] of the sparse rows v, query query_of[i] -- NULL: query 0 -- of the packed queries q_ptr / q_elem): the
+// values of launch_sparse_tiles for the same two vectors, bit for bit
+int launch_sparse_pairs(pgv_ctx *ctx, const RowsView &v, const int64_t *q_ptr, const void *q_elem, const int32_t *slot,
+                        const int32_t *query_of, int64_t npairs, float *out);
 
 // kernels_hnsw.hip: the whole first batch of an HNSW scan, one workgroup per query
 int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out);
 struct HnswSearchArgs {
     const void *queries = nullptr;     // staged query rows, or
+    SparseCsr sparse_queries{nullptr, nullptr, nullptr, 0};  // the staged queries of a walk over sparse rows, and
+    int max_q_nnz = 0;                 // ... the longest one's stored elements (the launch's LDS is sized by it), or
     const int32_t *qids = nullptr;     // element slots used as queries (build)
     const int32_t *qlevels = nullptr;  // insert level per query (build)
     int nq = 0, ef = 0, k = 0;
