@@ -896,6 +896,67 @@ int			pgv_hnsw_set_graph(pgv_hnsw * h, int m, int32_t entry, const int32_t *leve
 int			pgv_hnsw_search(pgv_hnsw * h, const void *queries, int nq, int ef_search, int k,
 							int64_t *out_elem, float *out_dist, int64_t *out_scored);
 
+/* ------------------------------------------------------ HNSW iterative scans */
+
+/*
+ * hnsw.iterative_scan on the device (hnswgettuple's loop, src/hnswscan.c:242-327): a scan over a batch of queries whose
+ * batches are fetched one launch at a time.  A query's first batch is GetScanItems (src/hnswscan.c:25-56) -- the walk of
+ * pgv_hnsw_search, tie handling included -- and every later one is ResumeScanItems (:61-87): HnswSearchLayer on layer 0
+ * (src/hnswutils.c:824-987) from the ef_search nearest of the candidates the earlier batches discarded (`discarded`,
+ * :936-946, :967-973), with the visited set carried over (initVisited == false, :867-874).  The scan keeps per QUERY a
+ * visited bitmap over the mirror's elements, the pool of discarded candidates and so->tuples.
+ *
+ * The order among equal distances is unspecified in the reference (pairing-heap internals); here the pool keeps its
+ * entries in the order they were discarded (per merged batch: the entries pushed out of W, in W's order, then the batch's
+ * own that did not fit, in batch order) and "nearest" is by (distance, position in the pool).  Without ties every batch
+ * holds the reference's elements, distances and so->tuples.
+ *
+ * The caller's to do: end every scan of a mirror (or of its views) before pgv_hnsw_free of that handle; the reference's
+ * memory limit (hnsw.scan_mem_multiplier x work_mem, src/hnswscan.c:153-156, :259) has no counterpart: discard_cap takes its
+ * place, and a pool that would outgrow it ends the scan with PGV_ERR_NOMEM.
+ */
+typedef struct pgv_hnsw_scan pgv_hnsw_scan;
+
+/*
+ * hnswbeginscan / hnswrescan's part (src/hnswscan.c:130-184): stages the queries as pgv_hnsw_search takes them (fp32 / fp16
+ * rows, bit strings on a bit mirror) and allocates the state; launches nothing.  Works on views (pgv_hnsw_share) and
+ * imported mirrors, on that handle's context and stream.  Several scans may be open on one mirror and pgv_hnsw_search
+ * may run between their batches: the scan owns its visited sets.
+ *   ef_search    1..1000 (src/hnsw.c:93-94)
+ *   discard_cap  pool entries per query; 0 = min(n, 65536).  State per query: 8 * discard_cap + 4 * (n / 32 + 2) + 16
+ *                bytes and the query row
+ * PGV_ERR_ARG: a sparse mirror (its queries are staged per call: pgv_hnsw_search_sparse), no graph set, ef_search out
+ * of range.  PGV_ERR_NOMEM: the state does not fit (the text has the byte count).
+ */
+int			pgv_hnsw_scan_begin(pgv_hnsw * h, const void *queries, int nq, int ef_search, int64_t discard_cap,
+								pgv_hnsw_scan * *out);
+/*
+ * The next batch of every query with want[q] != 0 (want == NULL: all of them), one launch, one workgroup per query:
+ * GetScanItems for a query's first batch, ResumeScanItems (src/hnswscan.c:61-87) afterwards.  The graph is read as it
+ * stands at the call: a pgv_hnsw_update_graph between two batches is seen by the later one (the reference takes its
+ * lock per batch as well, src/hnswscan.c:278-282).
+ *   want        [nq] bytes or NULL
+ *   out_elem    [nq x ef_search] element slots nearest first, -1 padded
+ *   out_dist    [nq x ef_search] FUNCTION 1 distances, +inf padded
+ *   out_count   [nq] entries of the batch; 0: the query is exhausted, was not wanted, or the index is empty
+ *   out_scored  [nq] or NULL: so->tuples so far
+ *   out_left    [nq] or NULL: candidates left in the pool
+ * PGV_ERR_NOMEM when a query's pool would overflow (never written past; the text names the query and the capacity);
+ * every later call on the scan returns the same error.  The mirror is unaffected.
+ */
+int			pgv_hnsw_scan_next(pgv_hnsw_scan * s, const uint8_t *want, int64_t *out_elem, float *out_dist,
+							   int32_t *out_count, int64_t *out_scored, int64_t *out_left);
+/*
+ * The hnsw.max_scan_tuples branch of hnswgettuple (src/hnswscan.c:259-266: past the limit the discarded candidates are
+ * returned nearest first, the graph is not walked any more), in bulk: removes and returns the `count` (1..1000) nearest
+ * remaining pool entries of every wanted query, by (distance, position).
+ *   out_elem / out_dist [nq x count], out_count [nq]
+ */
+int			pgv_hnsw_scan_drain(pgv_hnsw_scan * s, const uint8_t *want, int count, int64_t *out_elem, float *out_dist,
+								int32_t *out_count);
+/* hnswendscan (src/hnswscan.c:336-345): waits for the handle's stream and frees the state; before pgv_hnsw_free */
+void		pgv_hnsw_scan_end(pgv_hnsw_scan * s);
+
 /* ------------------------------------------------------ HNSW build side */
 
 /*

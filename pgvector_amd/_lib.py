@@ -50,6 +50,7 @@ SYMBOLS = [
     "pgv_hnsw_upload_bits", "pgv_index_upload_bits", "pgv_index_nbits", "pgv_bit_assign", "pgv_bit_kmeans",
     "pgv_bit_lloyd_step", "pgv_sparse_distance_batch", "pgv_sparse_cosine_distance_batch", "pgv_sparse_topk",
     "pgv_hnsw_upload_sparse", "pgv_hnsw_score_sparse", "pgv_hnsw_search_sparse",
+    "pgv_hnsw_scan_begin", "pgv_hnsw_scan_next", "pgv_hnsw_scan_drain", "pgv_hnsw_scan_end",
 ]
 
 
@@ -197,6 +198,11 @@ def _load():
     lib.pgv_hnsw_upload_sparse.argtypes = [P, I, I, P, P, P, I64, P, I, C.POINTER(P)]
     lib.pgv_hnsw_score_sparse.argtypes = [P, P, P, P, I, P, P, I64, P]
     lib.pgv_hnsw_search_sparse.argtypes = [P, P, P, P, I, I, I, P, P, P]
+    lib.pgv_hnsw_scan_begin.argtypes = [P, P, I, I, I64, C.POINTER(P)]
+    lib.pgv_hnsw_scan_next.argtypes = [P, P, P, P, P, P, P]
+    lib.pgv_hnsw_scan_drain.argtypes = [P, P, I, P, P, P]
+    lib.pgv_hnsw_scan_end.argtypes = [P]
+    lib.pgv_hnsw_scan_end.restype = None
     return lib
 
 

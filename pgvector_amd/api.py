@@ -950,6 +950,10 @@ class Hnsw:
                                   ptr(scored)))
         return elem, dist, scored
 
+    def scan(self, queries, ef_search, discard_cap=0):
+        """pgv_hnsw_scan_begin: a resumable scan of these queries (hnsw.iterative_scan) -> HnswScan"""
+        return HnswScan(self, as_dtype(queries, self.dtype), ef_search, discard_cap)
+
     def score(self, queries, slot, query_of=None):
         queries = as_dtype(queries, self.dtype)
         slot = np.ascontiguousarray(slot, dtype=np.int32) if not _is_torch(slot) else slot
@@ -1009,6 +1013,10 @@ class BitHnsw(Hnsw):
         scored = _empty_like_kind(queries, (nq,), np.int64) if want_scored else None
         check(lib.pgv_hnsw_search(self.h, ptr(queries), nq, int(ef_search), int(k), ptr(elem), ptr(dist), ptr(scored)))
         return elem, dist, scored
+
+    def scan(self, queries, ef_search, discard_cap=0):
+        """pgv_hnsw_scan_begin on a bit mirror: packed queries as search takes them -> HnswScan"""
+        return HnswScan(self, _as_bytes(queries), ef_search, discard_cap)
 
     def score(self, queries, slot, query_of=None):
         """pgv_hnsw_score on a bit mirror: Hamming distance of element slot[i] to packed query query_of[i]"""
@@ -1072,6 +1080,9 @@ class SparseHnsw(Hnsw):
                                          ptr(dist), ptr(scored)))
         return elem, dist, scored
 
+    def scan(self, queries_csr, ef_search, discard_cap=0):
+        raise PgvError(PGV_ERR_ARG, "a sparse mirror is not scanned iteratively (pgv_hnsw_scan_begin): use search")
+
     def score(self, queries_csr, slot, query_of=None):
         """pgv_hnsw_score_sparse: the distance of element slot[i] to query query_of[i] (None: query 0) of the CSR queries"""
         q_ptr, q_idx, q_val = _csr(queries_csr)
@@ -1090,6 +1101,115 @@ class SparseHnsw(Hnsw):
         out = np.empty((a.size,), dtype=np.float32)
         check(lib.pgv_hnsw_score_pairs(self.h, ptr(a), ptr(b), int(a.size), ptr(out)))
         return out
+
+
+def _host_array(x):
+    return x.cpu().numpy() if _is_torch(x) else np.asarray(x)
+
+
+class HnswScan:
+    """a resumable scan over a batch of queries (pgv_hnsw_scan_*): hnswgettuple's batches, one launch each.  Close it
+    before the mirror it scans."""
+
+    def __init__(self, mirror, queries, ef_search, discard_cap=0):
+        self.mirror, self.nq, self.ef = mirror, int(queries.shape[0]), int(ef_search)
+        self._like = queries
+        s = C.c_void_p()
+        check(lib.pgv_hnsw_scan_begin(mirror.h, ptr(queries) if self.nq else None, self.nq, self.ef, int(discard_cap),
+                                      C.byref(s)))
+        self.s = s
+
+    def _want(self, want):
+        if want is None:
+            return None
+        want = np.ascontiguousarray(np.asarray(want) != 0, dtype=np.uint8)
+        assert want.shape == (self.nq,)
+        return want
+
+    def next(self, want=None):
+        """pgv_hnsw_scan_next: the next batch of the wanted queries (None: all) -> (element slots [nq x ef] nearest
+        first / -1, distances [nq x ef] / +inf, count [nq], scored [nq]: so->tuples so far, left [nq]: pool entries)"""
+        want = self._want(want)
+        elem = _empty_like_kind(self._like, (self.nq, self.ef), np.int64)
+        dist = _empty_like_kind(self._like, (self.nq, self.ef), np.float32)
+        count = _empty_like_kind(self._like, (self.nq,), np.int32)
+        scored = _empty_like_kind(self._like, (self.nq,), np.int64)
+        left = _empty_like_kind(self._like, (self.nq,), np.int64)
+        check(lib.pgv_hnsw_scan_next(self.s, ptr(want), ptr(elem), ptr(dist), ptr(count), ptr(scored), ptr(left)))
+        return elem, dist, count, scored, left
+
+    def drain(self, count, want=None):
+        """pgv_hnsw_scan_drain: the `count` nearest pool entries of the wanted queries, removed from their pools ->
+        (element slots [nq x count] / -1, distances / +inf, count [nq])"""
+        want = self._want(want)
+        count = int(count)
+        shape = (self.nq, max(count, 1))
+        elem = _empty_like_kind(self._like, shape, np.int64)
+        dist = _empty_like_kind(self._like, shape, np.float32)
+        got = _empty_like_kind(self._like, (self.nq,), np.int32)
+        check(lib.pgv_hnsw_scan_drain(self.s, ptr(want), count, ptr(elem), ptr(dist), ptr(got)))
+        return elem, dist, got
+
+    def close(self):
+        if self.s:
+            lib.pgv_hnsw_scan_end(self.s)
+            self.s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def hnsw_iterative_search(h, queries, k, keep, ef_search, max_scan_tuples=20000, strict=False, discard_cap=0):
+    """hnswgettuple's loop (src/hnswscan.c:242-327) under hnsw.iterative_scan over a batch of queries: batches nearest
+    first, `keep` (a boolean array over element slots, the executor's filter) applied to each, with `strict` an element
+    nearer than the last one emitted dropped (:313-319), a query stopped at k kept elements; once its so->tuples
+    reaches max_scan_tuples a query takes the remaining discarded candidates instead of walking on (:259-266).  Only the
+    queries that still want more advance.  -> (ids: per query the kept element slots in emission order, dist: their
+    distances, scored [nq]: so->tuples at the end)"""
+    keep = np.asarray(keep, dtype=bool)
+    with h.scan(queries, ef_search, discard_cap) as s:
+        nq = s.nq
+        ids, dist = [[] for _ in range(nq)], [[] for _ in range(nq)]
+        prev = np.full(nq, -np.inf)
+        scored = np.zeros(nq, dtype=np.int64)
+        walking, draining = np.ones(nq, dtype=bool), np.zeros(nq, dtype=bool)
+
+        def emit(q, elems, dists):
+            ok = keep[elems]
+            if strict:  # an element nearer than the last one emitted is dropped: `prev` is the largest distance seen
+                seen = np.maximum.accumulate(np.concatenate([prev[q:q + 1], dists]))
+                ok &= dists >= seen[:-1]
+                prev[q] = seen[-1]
+            room = k - len(ids[q])
+            ids[q] += elems[ok][:room].tolist()
+            dist[q] += dists[ok][:room].tolist()
+
+        while walking.any() or draining.any():
+            if walking.any():
+                e, d, c, sc, _left = (_host_array(x) for x in s.next(walking))
+                for q in np.flatnonzero(walking):
+                    scored[q] = sc[q]
+                    emit(q, e[q, :c[q]], d[q, :c[q]])
+                    if c[q] == 0 or len(ids[q]) >= k:
+                        walking[q] = False
+                    elif sc[q] >= max_scan_tuples:
+                        walking[q], draining[q] = False, True
+            if draining.any():
+                e, d, c = (_host_array(x) for x in s.drain(ef_search, draining))
+                for q in np.flatnonzero(draining):
+                    emit(q, e[q, :c[q]], d[q, :c[q]])
+                    if c[q] == 0 or len(ids[q]) >= k:
+                        draining[q] = False
+    return ids, dist, scored
 
 
 def binary_search_hnsw(ctx, metric, dtype, dim, queries, rows, bit_hnsw, ef_search, kc, k, want_candidates=False):

@@ -35,6 +35,10 @@
 // and the batch entries admitted in their turn -- and at least one of those stays in
 // W for K to remain its furthest key: |T| <= ef - 1.  (tests/hnsw_walk_model.py
 // asserts the bound on every batch of every walk it models.)
+//
+// A resumable scan (pgv_hnsw_scan_*, hnsw.iterative_scan) is the same kernel with SCAN = true: the visited bitmap belongs
+// to the query, what the merge leaves past position ef goes to a per-query pool, and a later batch starts layer 0 from
+// the pool's nearest entries (ResumeScanItems, src/hnswscan.c:61-87) -- see HnswScanDev and scan_entry_step.
 #include "pgv_device.h"
 #include "sparse_pair.h"
 
@@ -97,9 +101,127 @@ __host__ __device__ inline size_t sparse_query_bytes(int sq_cap, int bm_words) {
     return (size_t)sq_cap * sizeof(QElem) + (size_t)kHnswWaves * bm_words * sizeof(uint32_t);
 }
 
-template <typename T, int METRIC>
+// What a resumable scan (pgv_hnsw_scan_*, SCAN = true) takes in the place of HnswSparse -- sparse mirrors are not scanned,
+// so the last argument is one or the other and the plain walks' arguments stay where they were.  Per query: its visited
+// bitmap (bitmaps[q * words ..), never shared between workgroups), the pool of discarded candidates in the order they were
+// discarded ((key, element) pairs, pool[q * cap ..)), and HnswScanQuery.  A query is one workgroup's for a whole launch.
+struct HnswScanQuery {
+    int64_t tuples;   // so->tuples so far
+    int32_t pool_n;   // live pool entries
+    int32_t flags;    // kScanStarted | kScanOverflow
+};
+constexpr int kScanStarted = 1, kScanOverflow = 2;
+static_assert(sizeof(HnswScanQuery) == kHnswScanQueryBytes, "the host sizes a scan's per-query state by kHnswScanQueryBytes");
+struct HnswScanDev {
+    uint2 *pool;
+    int cap;                // pool entries per query
+    HnswScanQuery *qs;      // [nq]
+    const uint8_t *want;    // [nq] or NULL = every query
+    int32_t *out_count;     // [nq]
+    int64_t *out_left;      // [nq] or NULL
+    int *overflow;          // 0, or 1 + the first query seen to overflow its pool
+    int drain;              // pgv_hnsw_scan_drain: the entry step alone
+};
+constexpr int kScanLdsWords = 256 + 16;  // the entry step's histogram and its scalars, behind sc
+
+// The entry step of a resumed batch (ResumeScanItems' pairingheap_remove_first loop, src/hnswscan.c:61-87, in bulk): the
+// `take` smallest of pool[0 .. pn) by (key, position) into wk0 / wi0 in that order; the rest of the pool closes up, order
+// kept.  stage_k / stage_i: room for `take` entries (W's other buffer).  256 threads, all of them call.
+//   1. the take-th smallest key K by an 8-bit radix descent over the keys (four passes over the pool), and how many of
+//      the entries at exactly K are taken: the first `need` of them by position;
+//   2. one pass in chunks of 256: a chunk is read into registers, __syncthreads(), then its taken entries go to the
+//      stage in position order and its others back into the pool at or below the chunk's own reads;
+//   3. rank-by-counting of the <= 1000 staged entries by (key, stage position) -- stage order is pool order.
+__device__ __forceinline__ void scan_entry_step(uint2 *__restrict__ pool, int pn, int take, uint32_t *wk0, uint32_t *wi0,
+                                                uint32_t *stage_k, uint32_t *stage_i, uint32_t *hist, int *es) {
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    uint32_t K = 0xffffffffu;
+    int need = pn;  // pn <= take: everything goes, whatever its key
+    if (pn > take) {
+        uint32_t prefix = 0, mask = 0;
+        int r = take;  // the r-th smallest of the keys that match prefix under mask
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < pn; i += kHnswThreads) {
+                const uint32_t key = pool[i].x;
+                if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int acc = 0, b = 0;
+                for (; b < 255; b++) {
+                    const int c = (int)hist[b];
+                    if (acc + c >= r) break;
+                    acc += c;
+                }
+                es[0] = b;
+                es[1] = r - acc;
+            }
+            __syncthreads();
+            prefix |= (uint32_t)es[0] << shift;
+            mask |= 255u << shift;
+            r = es[1];
+            __syncthreads();
+        }
+        K = prefix;
+        need = r;
+    }
+    int lt_run = 0, eq_run = 0;
+    for (int base = 0; base < pn; base += kHnswThreads) {
+        const int i = base + tid;
+        const bool valid = i < pn;
+        const uint2 e = pool[valid ? i : pn - 1];  // never predicate a load
+        const bool is_lt = valid && e.x < K, is_eq = valid && e.x == K;
+        const unsigned long long bl = __ballot(is_lt), be = __ballot(is_eq);
+        if (lane == 0) {
+            es[2 + wave] = __popcll(bl);
+            es[2 + kHnswWaves + wave] = __popcll(be);
+        }
+        __syncthreads();  // (the whole chunk is in registers from here on)
+        int lt_before = lt_run + __popcll(bl & ((1ull << lane) - 1ull));
+        int eq_before = eq_run + __popcll(be & ((1ull << lane) - 1ull));
+        for (int w = 0; w < kHnswWaves; w++) {
+            const int l = es[2 + w], q = es[2 + kHnswWaves + w];
+            if (w < wave) {
+                lt_before += l;
+                eq_before += q;
+            }
+            lt_run += l;
+            eq_run += q;
+        }
+        const int sel_before = lt_before + (eq_before < need ? eq_before : need);
+        const bool sel = is_lt || (is_eq && eq_before < need);
+        if (sel) {
+            if (sel_before < take) {  // (always: fewer than take entries are nearer than K, need of them at K)
+                stage_k[sel_before] = e.x;
+                stage_i[sel_before] = e.y;
+            }
+        } else if (valid) {
+            pool[i - sel_before] = e;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < take; i += kHnswThreads) {
+        const uint32_t key = stage_k[i];
+        int rank = 0;
+        for (int j = 0; j < take; j++) rank += (stage_k[j] < key) || (stage_k[j] == key && j < i);
+        wk0[rank] = key;
+        wi0[rank] = stage_i[i];
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSparse &sp, const HnswSparse &) { return sp; }
+__device__ __forceinline__ const HnswSparse &sparse_extras(const HnswScanDev &, const HnswSparse &none) { return none; }
+
+template <typename T, int METRIC, bool SCAN = false>
 __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
-    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter, HnswSparse sp) {
+    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter,
+    std::conditional_t<SCAN, HnswScanDev, HnswSparse> last) {
+    const HnswSparse none{};
+    const HnswSparse &sp = sparse_extras(last, none);  // a sparse walk's extras (a scan has none)
+    const auto &ss = last;                             // a resumable scan's state (SCAN)
     const int nq = run.nq, ef = run.ef, k = run.k;
     int64_t *__restrict__ out_elem = run.out_elem;
     float *__restrict__ out_dist = run.out_dist;
@@ -134,7 +256,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     const int rsub = lane >> g.lpr_log2;
     const int rpw = kWave >> g.lpr_log2;
     const size_t row_bytes = (size_t)g.nvec * sizeof(Raw16);
-    uint32_t *bitmap = bitmaps + (size_t)blockIdx.x * words;
+    uint32_t *bitmap = bitmaps + (size_t)blockIdx.x * words;  // (a scan's: the query's own, set below)
 
     // distance of the query (in LDS) to the rows bi[0 .. nb): every wavefront takes R x rpw rows per trip -- R rows' loads
     // in flight per lane group.  A walk is a chain of ~100 such batches, each waiting for its rows: with one row per trip
@@ -255,6 +377,59 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         if (qi >= nq) return;
 
         int64_t scored = 0;
+        // A scan's query (SCAN): not wanted, exhausted, over an empty index or flagged -> no batch, its state stays as it
+        // is.  A started one resumes: the entry step lays the pool's nearest into W, the visited set carries over, the
+        // upper layers are not walked again (ResumeScanItems, src/hnswscan.c:61-87).  A drain is the entry step alone.
+        bool resumed = false;
+        if constexpr (SCAN) {
+            bitmap = bitmaps + (size_t)qi * words;
+            const HnswScanQuery st = ss.qs[qi];
+            const bool started = st.flags & kScanStarted;
+            const bool wanted = (!ss.want || ss.want[qi]) && !(st.flags & kScanOverflow) && g.entry >= 0;
+            const bool live = wanted && (ss.drain ? st.pool_n > 0 : (!started || st.pool_n > 0));
+            if (!live) {
+                for (int j = tid; j < k; j += kHnswThreads) {
+                    out_elem[(size_t)qi * k + j] = -1;
+                    out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
+                }
+                if (tid == 0) {
+                    ss.out_count[qi] = 0;
+                    if (out_scored) out_scored[qi] = st.tuples;
+                    if (ss.out_left) ss.out_left[qi] = st.pool_n;
+                }
+                __syncthreads();
+                continue;
+            }
+            resumed = started;
+            scored = st.tuples;
+            if (tid == 0) sc[8] = st.pool_n;  // the pool's count lives here for the batch
+            if (resumed) {
+                const int take = st.pool_n < ef ? st.pool_n : ef;
+                uint32_t *hist = reinterpret_cast<uint32_t *>(sc + 16);
+                scan_entry_step(ss.pool + (size_t)qi * ss.cap, st.pool_n, take, wk, wi, wk + ef, wi + ef, hist,
+                                reinterpret_cast<int *>(hist + 256));
+                if (tid == 0) {
+                    sc[1] = take;
+                    sc[4] = 0;
+                    sc[8] = st.pool_n - take;
+                }
+                __syncthreads();
+                if (ss.drain) {
+                    for (int j = tid; j < k; j += kHnswThreads) {
+                        const bool have = j < take;
+                        out_elem[(size_t)qi * k + j] = have ? (int64_t)wi[j] : -1;
+                        out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[j]) : __uint_as_float(0x7f800000u);
+                    }
+                    if (tid == 0) {
+                        ss.out_count[qi] = take;
+                        if (ss.out_left) ss.out_left[qi] = st.pool_n - take;
+                        ss.qs[qi].pool_n = st.pool_n - take;
+                    }
+                    __syncthreads();
+                    continue;
+                }
+            }
+        }
         const int qlevel = run.qlevels ? run.qlevels[qi] : 0;
         if (run.lw_cnt)
             for (int l = tid; l < run.lcap; l += kHnswThreads) run.lw_cnt[(size_t)qi * run.lcap + l] = 0;
@@ -279,36 +454,42 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             const char *qrow = run.qids ? g.rows + (size_t)run.qids[qi] * row_bytes : run.queries + (size_t)qi * row_bytes;
             for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
         }
-        if (tid == 0) bi[0] = g.entry;
-        __syncthreads();
-        score_batch(1);
-        __syncthreads();
-        if (tid == 0) {
-            wk[0] = bk[0];
-            wi[0] = (uint32_t)g.entry;
-            sc[1] = 1;
-            sc[4] = 0;
+        if (!SCAN || !resumed) {
+            if (tid == 0) bi[0] = g.entry;
+            __syncthreads();
+            score_batch(1);
+            __syncthreads();
+            if (tid == 0) {
+                wk[0] = bk[0];
+                wi[0] = (uint32_t)g.entry;
+                sc[1] = 1;
+                sc[4] = 0;
+            }
         }
-        const int top = g.levels[g.entry];
+        const int top = SCAN && resumed ? 0 : g.levels[g.entry];
 
         for (int lc = top; lc >= 0; lc--) {
             const int ef_l = lc <= qlevel ? ef : 1;
             const int lm = lc == 0 ? lm0 : g.m;
             // a fresh visited set holding the entry points (src/hnswutils.c:866-885); the entry
             // points are the previous layer's W, all unexpanded again
-            for (int w = tid; w < words; w += kHnswThreads) bitmap[w] = 0u;
-            __syncthreads();
-            {
-                const int cur = sc[4], wn = sc[1];
-                for (int j = tid; j < wn; j += kHnswThreads) {
-                    const uint32_t id = wi[cur * ef + j] & ~kExpanded;
-                    wi[cur * ef + j] = id;
-                    atomicOr(&bitmap[id >> 5], 1u << (id & 31));
+            // (a resumed batch of a scan keeps its visited set; its entry points are in it and were counted when they
+            // were scored: initVisited == false, src/hnswutils.c:867-874)
+            if (!SCAN || !resumed) {
+                for (int w = tid; w < words; w += kHnswThreads) bitmap[w] = 0u;
+                __syncthreads();
+                {
+                    const int cur = sc[4], wn = sc[1];
+                    for (int j = tid; j < wn; j += kHnswThreads) {
+                        const uint32_t id = wi[cur * ef + j] & ~kExpanded;
+                        wi[cur * ef + j] = id;
+                        atomicOr(&bitmap[id >> 5], 1u << (id & 31));
+                    }
                 }
             }
             if (tid == 0) sc[5] = sc[6] = 0;
             __syncthreads();
-            if (lc == 0) scored += sc[1];  // its entry points count too (src/hnswutils.c:872-873)
+            if (lc == 0 && (!SCAN || !resumed)) scored += sc[1];  // its entry points count too (src/hnswutils.c:872-873)
 
             for (;;) {
                 // ---- wavefront 0: next candidate and its unvisited neighbours, in tuple order
@@ -477,6 +658,58 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                             sc[7] = (int)K;
                         }
                     }
+                    // A scan keeps what the merge leaves past position ef (`discarded`, src/hnswutils.c:936-946, :967-973;
+                    // layer 0 only, src/hnswscan.c:55): the old entries pushed out, in W's order, then the batch entries
+                    // that did not fit, in batch order -- whether or not they also went to T.  Never written past the
+                    // pool: the count goes on, and the batch ends flagged.
+                    if constexpr (SCAN) {
+                        if (lc == 0 && wn + nb > ef_l) {
+                            uint2 *pool = ss.pool + (size_t)qi * ss.cap;
+                            int pn = sc[8];
+                            // (an old entry moves up by at most nb: only W's last nb entries can leave)
+                            for (int base = ef_l > nb ? ef_l - nb : 0; base < wn; base += kWave) {
+                                const int j = base + lane;
+                                bool out = false;
+                                uint2 e = {0u, 0u};
+                                if (j < wn) {
+                                    e.x = ck[j];
+                                    e.y = ci[j] & ~kExpanded;
+                                    int s = 0;
+                                    for (int b = 0; b < nb; b++) s += bk[b] < e.x;
+                                    out = j + s >= ef_l;
+                                }
+                                const unsigned long long bal = __ballot(out);
+                                const int at = pn + __popcll(bal & ((1ull << lane) - 1ull));
+                                if (out && at < ss.cap) pool[at] = e;
+                                pn += __popcll(bal);
+                            }
+                            for (int base = 0; base < nb; base += kWave) {
+                                const int i = base + lane;
+                                bool out = false;
+                                uint2 e = {0u, 0u};
+                                if (i < nb) {
+                                    e.x = bk[i];
+                                    e.y = (uint32_t)bi[i];
+                                    int lo = 0, hi = wn;  // first old entry with key > this one
+                                    while (lo < hi) {
+                                        const int mid = (lo + hi) >> 1;
+                                        if (ck[mid] <= e.x)
+                                            lo = mid + 1;
+                                        else
+                                            hi = mid;
+                                    }
+                                    int s = lo;
+                                    for (int b = 0; b < nb; b++) s += (bk[b] < e.x) || (bk[b] == e.x && b < i);
+                                    out = s >= ef_l;
+                                }
+                                const unsigned long long bal = __ballot(out);
+                                const int at = pn + __popcll(bal & ((1ull << lane) - 1ull));
+                                if (out && at < ss.cap) pool[at] = e;
+                                pn += __popcll(bal);
+                            }
+                            if (lane == 0) sc[8] = pn;
+                        }
+                    }
                     if (lane == 0) {
                         sc[1] = wn_new;
                         sc[4] = nxt;
@@ -506,6 +739,16 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             }
         }
         if (tid == 0 && out_scored) out_scored[qi] = scored;
+        if constexpr (SCAN) {
+            if (tid == 0) {
+                const int pn = sc[8];
+                const bool over = pn > ss.cap;
+                ss.out_count[qi] = sc[1];
+                if (ss.out_left) ss.out_left[qi] = over ? ss.cap : pn;
+                ss.qs[qi] = {scored, over ? ss.cap : pn, kScanStarted | (over ? kScanOverflow : 0)};
+                if (over) atomicCAS(ss.overflow, 0, qi + 1);
+            }
+        }
         __syncthreads();
     }
 }
@@ -525,19 +768,22 @@ __global__ __launch_bounds__(256) void hnsw_patch_kernel(int32_t *__restrict__ n
     for (int64_t j = lane; j < len; j += 64) nbr[dst + j] = packed[src + j];
 }
 
-template <typename T, int METRIC>
+template <typename T, int METRIC, typename Last = HnswSparse>
 int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *bitmaps, int words, int grid,
-                  int *counter, const HnswSparse &sp = HnswSparse{}) {
+                  int *counter, const Last &sp = Last{}) {
     constexpr bool kSparse = std::is_same_v<T, SparseRow>;
-    const size_t query_bytes = kSparse ? sparse_query_bytes(sp.q_cap, sp.bm_words) : (size_t)g.nvec * sizeof(Raw16);
-    const size_t lds = query_bytes + (size_t)run.ef * 16 + (size_t)g.m * 16 + (size_t)run.ef * 4 + 64;
+    constexpr bool kScan = std::is_same_v<Last, HnswScanDev>;
+    size_t query_bytes = (size_t)g.nvec * sizeof(Raw16);
+    if constexpr (kSparse) query_bytes = sparse_query_bytes(sp.q_cap, sp.bm_words);
+    const size_t lds = query_bytes + (size_t)run.ef * 16 + (size_t)g.m * 16 + (size_t)run.ef * 4 + 64 +
+                       (kScan ? kScanLdsWords * sizeof(uint32_t) : 0);
     if (lds > 150 * 1024) {
-        if (kSparse)
+        if constexpr (kSparse)
             PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d / a query of %d stored elements need %zu bytes of LDS (limit %d)",
                      run.ef, g.m, sp.q_cap, lds, 150 * 1024);
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
     }
-    auto kern = hnsw_search_kernel<T, METRIC>;
+    auto kern = hnsw_search_kernel<T, METRIC, kScan>;
     PGV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kHnswThreads), lds, ctx->stream, g, run, bitmaps, words, counter, sp);
     PGV_HIP(hipGetLastError());
@@ -776,7 +1022,7 @@ int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out) {
 }
 
 int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const HnswSearchArgs &a, uint32_t *bitmaps,
-                       int words, int grid, int *counter) {
+                       int words, int grid, int *counter, const HnswScanArgs *scan) {
     // the rows, the graph and one launch's queries and outputs as the kernel takes them
     HnswDev g;
     g.rows = static_cast<const char *>(v.rows);
@@ -807,6 +1053,23 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
     run.rows_per_trip = per_trip >= 4 ? 4 : (per_trip == 1 ? 1 : 2);
     static const int prefetch = getenv("PGV_HNSW_SPARSE_PREFETCH") ? atoi(getenv("PGV_HNSW_SPARSE_PREFETCH")) : 1;
     PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+    if (scan) {  // a batch of a resumable scan, or its drain: the walk's SCAN form over the scan's own state
+        if (v.sparse() || a.qids || !a.out_elem || !a.out_dist || a.k != a.ef)
+            PGV_FAIL(PGV_ERR_ARG, "hnsw scan: dense or bit rows, query vectors, k = ef");
+        HnswScanDev sd;
+        sd.pool = static_cast<uint2 *>(scan->pool);
+        sd.cap = scan->cap;
+        sd.qs = static_cast<HnswScanQuery *>(scan->qstate);
+        sd.want = scan->want;
+        sd.out_count = scan->out_count;
+        sd.out_left = scan->out_left;
+        sd.overflow = scan->overflow;
+        sd.drain = scan->drain ? 1 : 0;
+        return dispatch_rows(v, [&](auto *tp, auto mc) {
+            return launch_hnsw_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value, HnswScanDev>(ctx, g, run, bitmaps, words,
+                                                                                                        grid, counter, sd);
+        });
+    }
     if (v.sparse()) {
         HnswSparse sp;
         sp.row_ptr = v.ptr;

@@ -1153,4 +1153,161 @@ int pgv_hnsw_update_graph(pgv_hnsw *h, int32_t entry, const int32_t *elements, i
     return PGV_OK;
 }
 
+// ------------------------------------------------------------------ resumable scans: hnsw.iterative_scan on the device
+// GetScanItems (src/hnswscan.c:25-56) for a query's first batch, ResumeScanItems (:61-87) for the later ones: what the
+// reference keeps in so->v and so->discarded lives here, per query, between the launches.
+
+struct pgv_hnsw_scan {
+    pgv_hnsw *h = nullptr;
+    int nq = 0, ef = 0, cap = 0, words = 0;
+    void *queries = nullptr;  // [nq] rows in the mirror's layout (the scan's own copy: the caller's may go away)
+    void *bitmaps = nullptr;  // [nq x words] one visited set per query
+    void *pool = nullptr;     // [nq x cap] (key, element)
+    void *qstate = nullptr;   // [nq x kHnswScanQueryBytes], then the overflow word
+    int failed_query = -1;    // a pool overflowed: every later call repeats the error
+};
+
+static int hnsw_scan_overflowed(const pgv_hnsw_scan *s) {
+    PGV_FAIL(PGV_ERR_NOMEM,
+             "pgv_hnsw_scan: the discarded candidates of query %d outgrew the scan's capacity of %d entries per query "
+             "(discard_cap); the scan is over, the mirror is unaffected",
+             s->failed_query, s->cap);
+}
+
+int pgv_hnsw_scan_begin(pgv_hnsw *h, const void *queries, int nq, int ef_search, int64_t discard_cap, pgv_hnsw_scan **out) {
+    if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin: handle/out is NULL");
+    *out = nullptr;
+    if (hnsw_is_sparse(h))
+        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin: a sparse mirror (pgv_hnsw_upload_sparse) is not scanned iteratively: its "
+                              "queries are staged per call; use pgv_hnsw_search_sparse");
+    hnsw_view_refresh(h);
+    if (nq < 0) PGV_FAIL(PGV_ERR_ARG, "bad query count");
+    if (ef_search < 1 || ef_search > 1000)
+        PGV_FAIL(PGV_ERR_ARG, "hnsw.ef_search must be 1..1000 (src/hnsw.c:93-94), got %d", ef_search);
+    if (discard_cap < 0) PGV_FAIL(PGV_ERR_ARG, "discard_cap must be >= 0, got %lld", (long long)discard_cap);
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin needs pgv_hnsw_set_graph first");
+    if (nq > 0 && !queries) PGV_FAIL(PGV_ERR_ARG, "queries is NULL");
+    pgv_ctx *ctx = h->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    pgv_hnsw_scan *s = new (std::nothrow) pgv_hnsw_scan();
+    if (!s) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
+    s->h = h;
+    s->nq = nq;
+    s->ef = ef_search;
+    if (discard_cap == 0) discard_cap = h->n < 65536 ? h->n : 65536;
+    if (discard_cap < 1) discard_cap = 1;
+    if (discard_cap > 0x7fffffff / 2) discard_cap = 0x7fffffff / 2;
+    s->cap = (int)discard_cap;
+    s->words = (int)((h->n + 31) / 32) + 1;
+    const size_t rows = (size_t)(nq > 0 ? nq : 1);
+    const size_t qbytes = rows * hnsw_row_bytes(h->geom), bbytes = rows * (size_t)s->words * sizeof(uint32_t),
+                 pbytes = rows * (size_t)s->cap * 8, sbytes = rows * kHnswScanQueryBytes + 16;
+    void **bufs[4] = {&s->queries, &s->bitmaps, &s->pool, &s->qstate};
+    const size_t sizes[4] = {qbytes, bbytes, pbytes, sbytes};
+    for (int i = 0; i < 4; i++)
+        if (hipMalloc(bufs[i], sizes[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            *bufs[i] = nullptr;
+            pgv_hnsw_scan_end(s);
+            PGV_FAIL(PGV_ERR_NOMEM, "pgv_hnsw_scan_begin: hipMalloc(%zu) failed; the state of %d queries takes %zu bytes "
+                                    "(discard_cap %d, %d bitmap words per query)",
+                     sizes[i], nq, qbytes + bbytes + pbytes + sbytes, s->cap, s->words);
+        }
+    int rc = put_padded_rows(ctx->stream, s->queries, hnsw_row_bytes(h->geom), queries,
+                             hnsw_src_row_bytes(h->dim, h->dtype, h->nbits), nq);
+    hipError_t e = rc == PGV_OK ? hipMemsetAsync(s->qstate, 0, sbytes, ctx->stream) : hipSuccess;
+    if (rc == PGV_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller may reuse queries right away
+    if (rc != PGV_OK || e != hipSuccess) {
+        pgv_hnsw_scan_end(s);
+        if (rc != PGV_OK) return rc;
+        PGV_FAIL(PGV_ERR_DEVICE, "pgv_hnsw_scan_begin: staging failed: %s", hipGetErrorString(e));
+    }
+    *out = s;
+    return PGV_OK;
+}
+
+// one launch over the scan's state: a batch of every wanted query (ef = the scan's) or the drain of their pools
+static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool drain, int64_t *out_elem, float *out_dist,
+                            int32_t *out_count, int64_t *out_scored, int64_t *out_left) {
+    pgv_hnsw *h = s->h;
+    pgv_ctx *ctx = h->ctx;
+    hnsw_view_refresh(h);
+    if (s->nq == 0) return PGV_OK;
+    PGV_HIP(hipSetDevice(ctx->device));
+    PGV_TRY(hnsw_graph_acquire(h));
+    const void *w_dev = nullptr;
+    if (want) PGV_TRY(stage_flat(ctx, want, (size_t)s->nq, ctx->idx_stage, &w_dev));
+    OutArg oe, od, oc, os, ol;
+    PGV_TRY(oe.init(out_elem, sizeof(int64_t) * (size_t)s->nq * ef, ctx->out_stage2));
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)s->nq * ef, ctx->out_stage));
+    PGV_TRY(oc.init(out_count, sizeof(int32_t) * (size_t)s->nq, ctx->sel_a));
+    PGV_TRY(os.init(out_scored, sizeof(int64_t) * (size_t)s->nq, ctx->sel_b));
+    PGV_TRY(ol.init(out_left, sizeof(int64_t) * (size_t)s->nq, ctx->plan_a));
+    PGV_TRY(ctx->counters.ensure(256));
+    HnswSearchArgs a;
+    a.queries = s->queries;
+    a.nq = s->nq;
+    a.ef = ef;
+    a.k = ef;
+    a.out_elem = oe.as<int64_t>();
+    a.out_dist = od.as<float>();
+    a.out_scored = out_scored ? os.as<int64_t>() : nullptr;
+    HnswScanArgs sa;
+    sa.pool = s->pool;
+    sa.cap = s->cap;
+    sa.qstate = s->qstate;
+    sa.want = static_cast<const uint8_t *>(w_dev);
+    sa.out_count = oc.as<int32_t>();
+    sa.out_left = out_left ? ol.as<int64_t>() : nullptr;
+    sa.overflow = reinterpret_cast<int *>(static_cast<char *>(s->qstate) + (size_t)s->nq * kHnswScanQueryBytes);
+    sa.drain = drain;
+    // one workgroup per query (an unwanted or exhausted one's only writes its empty outputs): each has its own visited
+    // set, so nothing caps the grid but the queries
+    const int grid = s->nq < ctx->num_cus * 8 ? s->nq : ctx->num_cus * 8;
+    PGV_TRY(launch_hnsw_search(ctx, hnsw_rows(h), h->graph, a, static_cast<uint32_t *>(s->bitmaps), s->words, grid,
+                               ctx->counters.as<int>(), &sa));
+    int over = 0;
+    PGV_HIP(hipMemcpyAsync(&over, sa.overflow, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    bool need = false;
+    PGV_TRY(oe.finish(ctx, &need));
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(oc.finish(ctx, &need));
+    PGV_TRY(os.finish(ctx, &need));
+    PGV_TRY(ol.finish(ctx, &need));
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    if (over > 0) {
+        s->failed_query = over - 1;
+        return hnsw_scan_overflowed(s);
+    }
+    return PGV_OK;
+}
+
+int pgv_hnsw_scan_next(pgv_hnsw_scan *s, const uint8_t *want, int64_t *out_elem, float *out_dist, int32_t *out_count,
+                       int64_t *out_scored, int64_t *out_left) {
+    if (!s || !out_elem || !out_dist || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_next: scan/out is NULL");
+    if (s->failed_query >= 0) return hnsw_scan_overflowed(s);
+    return hnsw_scan_launch(s, want, s->ef, false, out_elem, out_dist, out_count, out_scored, out_left);
+}
+
+int pgv_hnsw_scan_drain(pgv_hnsw_scan *s, const uint8_t *want, int count, int64_t *out_elem, float *out_dist,
+                        int32_t *out_count) {
+    if (!s || !out_elem || !out_dist || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_drain: scan/out is NULL");
+    if (count < 1 || count > 1000) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_drain: count must be 1..1000, got %d", count);
+    if (s->failed_query >= 0) return hnsw_scan_overflowed(s);
+    return hnsw_scan_launch(s, want, count, true, out_elem, out_dist, out_count, nullptr, nullptr);
+}
+
+void pgv_hnsw_scan_end(pgv_hnsw_scan *s) {
+    if (!s) return;
+    if (s->h && s->h->ctx) {
+        (void)hipSetDevice(s->h->ctx->device);
+        (void)hipStreamSynchronize(s->h->ctx->stream);
+    }
+    if (s->queries) (void)hipFree(s->queries);
+    if (s->bitmaps) (void)hipFree(s->bitmaps);
+    if (s->pool) (void)hipFree(s->pool);
+    if (s->qstate) (void)hipFree(s->qstate);
+    delete s;
+}
+
 }  // extern "C"

@@ -650,8 +650,22 @@ struct HnswSearchArgs {
     int32_t *lw_cnt = nullptr;
     int lcap = 0;
 };
+// ... and a resumable scan's state on top (pgv_hnsw_scan_*): with it the launch is one batch of every wanted query --
+// the first (GetScanItems) or a resumed one (ResumeScanItems, src/hnswscan.c:61-87) -- or the drain of their pools.
+// bitmaps / words are then the scan's: one visited set per QUERY.  Dense and bit rows only, k = ef
+constexpr size_t kHnswScanQueryBytes = 16;  // per query: tuples so far, live pool entries, flags
+struct HnswScanArgs {
+    void *pool = nullptr;              // [nq x cap] (key, element) pairs: the discarded candidates, in discard order
+    int cap = 0;
+    void *qstate = nullptr;            // [nq x kHnswScanQueryBytes], zero before the first batch
+    const uint8_t *want = nullptr;     // [nq] or NULL = every query
+    int32_t *out_count = nullptr;      // [nq]
+    int64_t *out_left = nullptr;       // [nq] or NULL
+    int *overflow = nullptr;           // zero before the first batch; 1 + a query whose pool overflowed
+    bool drain = false;
+};
 int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const HnswSearchArgs &a, uint32_t *bitmaps,
-                       int words, int grid, int *counter);
+                       int words, int grid, int *counter, const HnswScanArgs *scan = nullptr);
 int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int32_t *ids, const int64_t *packed_off,
                       const int32_t *packed, int nupd);
 
