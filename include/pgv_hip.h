@@ -780,8 +780,9 @@ int			pgv_hnsw_get_payload(pgv_hnsw * h, const int64_t *elements, int n, void *o
  *   first bit = most significant bit of byte 0, the caller's pad bits zero (bytes are counted whole, like the reference);
  *   1 <= nbits <= 64 000 (HNSW_MAX_DIM * 32), else PGV_ERR_DIMS; payload / payload_bytes as pgv_hnsw_upload_payload
  *   (NULL / 0: none).
- * metric must be PGV_BIT_HAMMING.  PGV_BIT_JACCARD is PGV_ERR_ARG: jaccard_distance is a float8 ratio, the walk's keys
- * are fp32 and would merge distinct distances, and the reference's stop test is strict on the float8 value.
+ * metric must be PGV_BIT_HAMMING.  PGV_BIT_JACCARD is PGV_ERR_ARG here, and the text names pgv_hnsw_upload_jaccard below:
+ * jaccard_distance is a float8 ratio, fp32 keys would merge distinct distances, and the reference's stop test is strict
+ * on the float8 value -- so a Jaccard mirror ranks by a 32-bit INTEGER key and has an entry of its own.
  * On such a mirror pgv_hnsw_search / pgv_hnsw_score take queries [nq x (nbits + 7) / 8] in the same layout and return
  * the Hamming distances as floats (exact: at most 64 000); pgv_hnsw_score_pairs likewise; pgv_hnsw_set_graph,
  * pgv_hnsw_update_graph, pgv_hnsw_get_payload, pgv_hnsw_share and pgv_hnsw_export / pgv_hnsw_import work as on any
@@ -790,6 +791,38 @@ int			pgv_hnsw_get_payload(pgv_hnsw * h, const int64_t *elements, int n, void *o
  */
 int			pgv_hnsw_upload_bits(pgv_ctx * ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
 								 const void *payload, int payload_bytes, pgv_hnsw * *out);
+
+/*
+ * The mirror of `USING hnsw (col bit_jaccard_ops)` (opclass sql/vector.sql:907-911, FUNCTION 1 jaccard_distance; the same
+ * type info hnsw_bit_support): the walk of pgv_hnsw_upload_bits with every candidate scored by jaccard_distance
+ * (src/bitvec.c:60-70 over BitJaccardDistanceDefault, src/bitutils.c:99-131).  Layout, limits and errors are
+ * pgv_hnsw_upload_bits': elements [n x (nbits + 7) / 8] bytes, 1 <= nbits <= 64 000 else PGV_ERR_DIMS, payload the same.
+ *
+ * The key.  With x = popcount(a ^ b) and u = popcount(a | b) the reference's value is 1 when u - x = 0 and
+ * 1 - (double) (u - x) / (double) u otherwise: the rational x / u pushed through two monotone roundings.  Two different
+ * rationals with denominators <= 64 000 differ by at least 1 / 64 000^2 ~ 2.4e-10, far above a double's spacing near 1,
+ * so the doubles order exactly like the rationals and equal rationals give equal doubles.  The walk ranks by
+ * floor(x * S / u) in 64-bit integer arithmetic, S = 0xFFFFFF00: since 64 000^2 = 4 096 000 000 < S, two different
+ * rationals are more than 1 apart after scaling, and the key is strictly monotone and injective on them.  u = 0 (two
+ * empty strings) and x = u (no common bit) are distance 1: key S.  No key is 0xffffffff.  An fp32 key would merge
+ * neighbouring ratios (x / u near 1 / 2 with u near 64 000 are 2.4e-10 apart, fp32 resolves 3e-8 there).
+ * Ties: equal rationals -- (x, u) and (g x, g u) -- are equal keys, as they are equal float8 values in the reference, and
+ * are ordered as on every other mirror (the walk's tie list; pgv_hnsw_search's note on equal distances).
+ *
+ * Distances handed back (pgv_hnsw_search, the scan entries and their drain, pgv_hnsw_score, pgv_hnsw_score_pairs) are
+ * the (float) of the reference's float8 for the pair, bit for bit, 1.0 for no common bit included: a key does not carry
+ * (x, u), so a launch scores its at most ef result elements once more and divides in IEEE double.
+ *
+ * On such a mirror pgv_hnsw_search, pgv_hnsw_score, pgv_hnsw_score_pairs, pgv_hnsw_set_graph, pgv_hnsw_update_graph,
+ * pgv_hnsw_get_payload, pgv_hnsw_share, pgv_hnsw_export / pgv_hnsw_import (the handle carries the bit metric: an
+ * importer walks with the exporter's keys) and pgv_hnsw_scan_begin / _next / _drain / _end work as on a Hamming mirror.
+ * Every build-side entry returns PGV_ERR_ARG before any launch, as on any bit mirror.
+ * Not served: the graph build (a Jaccard graph comes from the reference's build); ext/, which keeps handing the bit
+ * opclasses to the CPU path; an IVFFlat index (the reference has no ivfflat Jaccard opclass).  bench.py does not measure
+ * this entry, tools/bench_jaccard_hnsw.py does.
+ */
+int			pgv_hnsw_upload_jaccard(pgv_ctx * ctx, int nbits, const void *elements, int64_t n, const void *payload,
+									int payload_bytes, pgv_hnsw * *out);
 
 /*
  * ---- HNSW over sparsevec elements.

@@ -51,6 +51,7 @@ SYMBOLS = [
     "pgv_bit_lloyd_step", "pgv_sparse_distance_batch", "pgv_sparse_cosine_distance_batch", "pgv_sparse_topk",
     "pgv_hnsw_upload_sparse", "pgv_hnsw_score_sparse", "pgv_hnsw_search_sparse",
     "pgv_hnsw_scan_begin", "pgv_hnsw_scan_next", "pgv_hnsw_scan_drain", "pgv_hnsw_scan_end",
+    "pgv_hnsw_upload_jaccard",
 ]
 
 
@@ -127,6 +128,7 @@ def _load():
     lib.pgv_hnsw_upload_payload.argtypes = [P, I, I, I, P, I64, P, I, C.POINTER(P)]
     lib.pgv_hnsw_get_payload.argtypes = [P, P, I, P]
     lib.pgv_hnsw_upload_bits.argtypes = [P, I, I, P, I64, P, I, C.POINTER(P)]
+    lib.pgv_hnsw_upload_jaccard.argtypes = [P, I, P, I64, P, I, C.POINTER(P)]
     lib.pgv_exact_topk.argtypes = [P, I, I, I, P, I, P, I64, I, P, P]
     lib.pgv_ctx_set_bound.argtypes = [P, I]
     lib.pgv_builder_begin.argtypes = [P, I, I, I, I, P, I64, C.POINTER(P)]

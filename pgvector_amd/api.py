@@ -994,7 +994,7 @@ class BitHnsw(Hnsw):
         return v
 
     def share(self, ctx):
-        v = BitHnsw.__new__(BitHnsw)
+        v = type(self).__new__(type(self))
         h = C.c_void_p()
         check(lib.pgv_hnsw_share(self.h, ctx.h, C.byref(h)))
         v.ctx, v.metric, v.dtype, v.dim, v.nbits, v.h = ctx, self.metric, None, self.dim, self.nbits, h
@@ -1035,6 +1035,40 @@ class BitHnsw(Hnsw):
         out = np.empty((a.size,), dtype=np.float32)
         check(lib.pgv_hnsw_score_pairs(self.h, ptr(a), ptr(b), int(a.size), ptr(out)))
         return out
+
+
+class JaccardHnsw(BitHnsw):
+    """device mirror of an HNSW index over packed bit strings under `USING hnsw (... bit_jaccard_ops)`
+    (pgv_hnsw_upload_jaccard): elements as BitHnsw takes them.  The walk ranks by an integer key of the Jaccard ratio that
+    orders and ties exactly as the reference's float8 does; search, scan, score and score_pairs return Jaccard distances,
+    each the float32 of the reference's float8 for the pair (1.0 when the strings share no bit).  set_graph, update_graph,
+    get_payload, export and close are Hnsw's; the graph comes from the reference's build."""
+
+    def __init__(self, ctx, nbits, elements, payload=None):
+        self.ctx, self.metric, self.dtype, self.dim, self.nbits = ctx, PGV_BIT_JACCARD, None, int(nbits), int(nbits)
+        elements = _as_bytes(elements)
+        n = int(elements.shape[0])
+        h = C.c_void_p()
+        self.payload_words = 0
+        if payload is not None:
+            payload = np.ascontiguousarray(payload, dtype=np.uint32)
+            self.payload_words = int(payload.shape[1])
+        check(lib.pgv_hnsw_upload_jaccard(ctx.h, int(nbits), ptr(elements) if n else None, n, ptr(payload),
+                                          4 * self.payload_words, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    @classmethod
+    def from_handle(cls, ctx, handle, nbits=None):
+        """pgv_hnsw_import of a Jaccard mirror's export: the handle carries nbits and the bit metric, so the importer
+        walks with Jaccard keys whichever bit class opens it"""
+        v = super().from_handle(ctx, handle, nbits)
+        v.metric = PGV_BIT_JACCARD
+        return v
+
+    def share(self, ctx):
+        """pgv_hnsw_share: a view of this Jaccard mirror for another context of the same process"""
+        return super().share(ctx)
 
 
 class SparseHnsw(Hnsw):

@@ -39,6 +39,10 @@
 // A resumable scan (pgv_hnsw_scan_*, hnsw.iterative_scan) is the same kernel with SCAN = true: the visited bitmap belongs
 // to the query, what the merge leaves past position ef goes to a per-query pool, and a later batch starts layer 0 from
 // the pool's nearest entries (ResumeScanItems, src/hnswscan.c:61-87) -- see HnswScanDev and scan_entry_step.
+//
+// Keys are uint32 throughout and only ever compared.  fp32 and fp16 mirrors, Hamming bit mirrors and sparse mirrors rank by
+// float_to_key of an fp32 distance that is the reference's float8 exactly; a Jaccard bit mirror (<BitRow, 1>,
+// pgv_hnsw_upload_jaccard) ranks by jaccard_key, an integer image of the ratio that orders and ties as its float8 does.
 #include "pgv_device.h"
 #include "sparse_pair.h"
 
@@ -228,6 +232,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     int64_t *__restrict__ out_scored = run.out_scored;
     constexpr int N = VecTraits<T>::N;
     constexpr bool kBits = std::is_same_v<T, BitRow>;
+    constexpr bool kJaccard = kBits && METRIC == 1;  // bit_jaccard_ops: see score_rows
     constexpr bool kSparse = std::is_same_v<T, SparseRow>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lm0 = 2 * g.m;
@@ -266,20 +271,35 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     // depend on R.
     // A bit mirror (T = BitRow, bit_hamming_ops: hamming_distance, src/bitvec.c:45-56) counts the differing bits of the
     // same 16-byte vectors in an integer; the count (<= 64 000) and every partial sum of the reduction are exact in fp32.
-    auto score_rows = [&](auto rc, int nb) __attribute__((always_inline)) {
+    // A Jaccard mirror (<BitRow, 1>, bit_jaccard_ops: jaccard_distance, src/bitvec.c:60-70 over BitJaccardDistanceDefault,
+    // src/bitutils.c:99-131) counts two integers in the same loop, x = popcount(a ^ b) and u = popcount(a | b), both exact
+    // like the Hamming count, and one lane forms jaccard_key(x, u): an integer that orders and ties exactly as the
+    // reference's float8 does (pgv_device.h), so everything that compares keys serves it unchanged.  A key does not carry
+    // (x, u): where distances are handed back (OUT), the result elements jids[0 .. nb) -- at most ef -- are scored once
+    // more by this loop and jout[i] = jaccard_value(x, u), the (float) of the reference's float8.
+    const uint32_t *jids = nullptr;
+    float *jout = nullptr;
+    auto score_rows = [&](auto rc, auto oc, int nb) __attribute__((always_inline)) {
         constexpr int R = decltype(rc)::value;
+        constexpr bool OUT = decltype(oc)::value;
+        static_assert(!OUT || kJaccard, "only a Jaccard walk scores its results again");
         const int step = kHnswWaves * rpw;
         for (int base = wave * rpw; base < nb; base += R * step) {
             int idx[R];
             bool valid[R];
             const char *rp[R];
             std::conditional_t<kBits, int, float> acc[R];
+            [[maybe_unused]] int uni[R];
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 idx[r] = base + rsub + r * step;
                 valid[r] = idx[r] < nb;
-                rp[r] = g.rows + (size_t)bi[valid[r] ? idx[r] : nb - 1] * row_bytes;
+                if constexpr (OUT)
+                    rp[r] = g.rows + (size_t)(jids[valid[r] ? idx[r] : nb - 1] & ~kExpanded) * row_bytes;
+                else
+                    rp[r] = g.rows + (size_t)bi[valid[r] ? idx[r] : nb - 1] * row_bytes;
                 acc[r] = 0;
+                if constexpr (kJaccard) uni[r] = 0;
             }
 #pragma unroll 2
             for (int c = 0; c < g.nchunks; c++) {
@@ -290,7 +310,13 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
 #pragma unroll
                 for (int r = 0; r < R; r++) rv[r] = load16(rp[r] + (size_t)vc * sizeof(Raw16));
                 const Raw16 qv = lq[vc];
-                if constexpr (kBits) {
+                if constexpr (kJaccard) {
+#pragma unroll
+                    for (int r = 0; r < R; r++) {
+                        acc[r] += ok ? hamming16(rv[r], qv) : 0;
+                        uni[r] += ok ? union16(rv[r], qv) : 0;
+                    }
+                } else if constexpr (kBits) {
 #pragma unroll
                     for (int r = 0; r < R; r++) acc[r] += ok ? hamming16(rv[r], qv) : 0;
                 } else if constexpr (!kSparse) {  // (a sparse walk never comes here: score_sparse below)
@@ -306,8 +332,26 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
 #pragma unroll
             for (int r = 0; r < R; r++) {
                 const float sum = group_sum_to_last((float)acc[r], g.lpr_log2);
-                if (sub == lpr - 1 && valid[r]) bk[idx[r]] = float_to_key(finish<METRIC>(sum));
+                if constexpr (kJaccard) {
+                    const int x = (int)sum, u = (int)group_sum_to_last((float)uni[r], g.lpr_log2);
+                    if (sub == lpr - 1 && valid[r]) {
+                        if constexpr (OUT)
+                            jout[idx[r]] = jaccard_value(x, u);
+                        else
+                            bk[idx[r]] = jaccard_key(x, u);
+                    }
+                } else {
+                    if (sub == lpr - 1 && valid[r]) bk[idx[r]] = float_to_key(finish<METRIC>(sum));
+                }
             }
+        }
+    };
+    // the distances of a Jaccard walk's results ids[0 .. cnt) into dst[0 .. cnt); the query is in LDS
+    auto jaccard_out = [&](const uint32_t *ids, int cnt, float *dst) __attribute__((always_inline)) {
+        if constexpr (kJaccard) {
+            jids = ids;
+            jout = dst;
+            score_rows(std::integral_constant<int, 4>{}, std::true_type{}, cnt);
         }
     };
     // A sparse mirror (T = SparseRow; hnsw_sparsevec_support, src/hnswutils.c:1361-1433: FUNCTION 1 is
@@ -362,11 +406,11 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                 score_sparse(std::false_type{}, nb);
         } else {
             if (run.rows_per_trip >= 4)
-                score_rows(std::integral_constant<int, 4>{}, nb);
+                score_rows(std::integral_constant<int, 4>{}, std::false_type{}, nb);
             else if (run.rows_per_trip == 2)
-                score_rows(std::integral_constant<int, 2>{}, nb);
+                score_rows(std::integral_constant<int, 2>{}, std::false_type{}, nb);
             else
-                score_rows(std::integral_constant<int, 1>{}, nb);
+                score_rows(std::integral_constant<int, 1>{}, std::false_type{}, nb);
         }
     };
 
@@ -415,11 +459,20 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                 }
                 __syncthreads();
                 if (ss.drain) {
+                    if constexpr (kJaccard) {  // (the pool keeps keys: the drained elements meet the query once more)
+                        const char *qrow = run.queries + (size_t)qi * row_bytes;
+                        for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
+                        __syncthreads();
+                    }
                     for (int j = tid; j < k; j += kHnswThreads) {
                         const bool have = j < take;
                         out_elem[(size_t)qi * k + j] = have ? (int64_t)wi[j] : -1;
-                        out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[j]) : __uint_as_float(0x7f800000u);
+                        if constexpr (kJaccard) {
+                            if (!have) out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
+                        } else
+                            out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[j]) : __uint_as_float(0x7f800000u);
                     }
+                    jaccard_out(wi, take < k ? take : k, out_dist + (size_t)qi * k);
                     if (tid == 0) {
                         ss.out_count[qi] = take;
                         if (ss.out_left) ss.out_left[qi] = st.pool_n - take;
@@ -735,8 +788,12 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             for (int j = tid; j < k; j += kHnswThreads) {
                 const bool have = j < wn;
                 out_elem[(size_t)qi * k + j] = have ? (int64_t)(wi[cur * ef + j] & ~kExpanded) : -1;
-                out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[cur * ef + j]) : __uint_as_float(0x7f800000u);
+                if constexpr (kJaccard) {
+                    if (!have) out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
+                } else
+                    out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[cur * ef + j]) : __uint_as_float(0x7f800000u);
             }
+            jaccard_out(wi + cur * ef, wn < k ? wn : k, out_dist + (size_t)qi * k);
         }
         if (tid == 0 && out_scored) out_scored[qi] = scored;
         if constexpr (SCAN) {

@@ -183,7 +183,10 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
     if (base >= npairs) return;
 
     constexpr bool kBits = std::is_same_v<T, BitRow>;  // packed bit rows: the differing bits, counted in an integer
+    // ... <BitRow, 1>, a Jaccard mirror: the bits set in either row as well, and the value is jaccard_distance's
+    constexpr bool kJaccard = kBits && METRIC == 1;
     std::conditional_t<kBits, int, float> acc[R];
+    [[maybe_unused]] int uni[R];
     const char *rp[R];
     const char *qp[R];
 #pragma unroll
@@ -191,6 +194,7 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
         int64_t p = base + r * rpw + rsub;
         p = p < npairs ? p : npairs - 1;
         acc[r] = 0;
+        if constexpr (kJaccard) uni[r] = 0;
         rp[r] = rows + (size_t)slot[p] * row_bytes;
         qp[r] = queries + (size_t)(query_of ? query_of[p] : 0) * row_bytes;
     }
@@ -204,7 +208,13 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
             rv[r] = load16(rp[r] + (size_t)vc * sizeof(Raw16));
             qv[r] = load16(qp[r] + (size_t)vc * sizeof(Raw16));
         }
-        if constexpr (kBits) {
+        if constexpr (kJaccard) {
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                acc[r] += ok ? hamming16(rv[r], qv[r]) : 0;
+                uni[r] += ok ? union16(rv[r], qv[r]) : 0;
+            }
+        } else if constexpr (kBits) {
 #pragma unroll
             for (int r = 0; r < R; r++) acc[r] += ok ? hamming16(rv[r], qv[r]) : 0;
         } else {
@@ -222,7 +232,12 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
     for (int r = 0; r < R; r++) {
         const int64_t p = base + r * rpw + rsub;
         float s = group_sum_to_last((float)acc[r], lpr_log2);  // (a bit count and its partial sums are exact in fp32)
-        if (sub == lpr - 1 && p < npairs) out[p] = finish<METRIC>(s);
+        if constexpr (kJaccard) {
+            const int u = (int)group_sum_to_last((float)uni[r], lpr_log2);
+            if (sub == lpr - 1 && p < npairs) out[p] = jaccard_value((int)s, u);
+        } else {
+            if (sub == lpr - 1 && p < npairs) out[p] = finish<METRIC>(s);
+        }
     }
 }
 

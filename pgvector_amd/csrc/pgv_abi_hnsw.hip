@@ -16,7 +16,8 @@ static size_t hnsw_payload_offset(int64_t n, size_t row_bytes) {
     return ((size_t)(n > 0 ? n : 1) * row_bytes + 255) & ~(size_t)255;
 }
 
-// a bit mirror (pgv_hnsw_upload_bits): rows of whole bytes scored by xor + popcount; no build-side entry serves it
+// a bit mirror (pgv_hnsw_upload_bits, pgv_hnsw_upload_jaccard): rows of whole bytes scored by popcounts; no build-side entry
+// serves it
 static bool hnsw_is_bits(const pgv_hnsw *h) { return h->nbits > 0; }
 
 // ... and a sparse mirror (pgv_hnsw_upload_sparse): CSR rows scored by sparse_pair.h; searched and scored through the
@@ -26,7 +27,7 @@ static bool hnsw_is_sparse(const pgv_hnsw *h) { return h->sparse; }
 #define PGV_NO_BUILD(h, who)                                                                                      \
     do {                                                                                                         \
         if ((h) && hnsw_is_bits(h))                                                                              \
-            PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits) is searched and scored, not built on", who); \
+            PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits / _jaccard) is searched and scored, not built on", who); \
         if ((h) && hnsw_is_sparse(h))                                                                            \
             PGV_FAIL(PGV_ERR_ARG, "%s: a sparse mirror (pgv_hnsw_upload_sparse) is searched and scored, not built on", who); \
     } while (0)
@@ -78,12 +79,24 @@ int pgv_hnsw_upload_bits(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const v
     *out = nullptr;
     if (metric == PGV_BIT_JACCARD)
         PGV_FAIL(PGV_ERR_ARG,
-                 "pgv_hnsw_upload_bits: bit_jaccard_ops is not served: jaccard_distance is a float8 ratio, and the walk's "
-                 "fp32 keys would merge distances that the reference's strict stop test tells apart");
+                 "pgv_hnsw_upload_bits: this entry uploads bit_hamming_ops mirrors, whose distances are the walk's fp32 keys; a "
+                 "bit_jaccard_ops mirror ranks by an integer key of the jaccard ratio: use pgv_hnsw_upload_jaccard");
     if (metric != PGV_BIT_HAMMING) PGV_FAIL(PGV_ERR_ARG, "unknown bit metric %d", (int)metric);
     if (nbits < 1 || nbits > kHnswMaxBits)
         PGV_FAIL(PGV_ERR_DIMS, "bit dimensions %d outside 1..%d (HNSW_MAX_DIM * 32, src/hnswutils.c:1414)", nbits, kHnswMaxBits);
-    return hnsw_upload_rows(ctx, PGV_L2SQ, PGV_F32, nbits, nbits, elements, n, payload, payload_bytes, out);
+    return hnsw_upload_rows(ctx, bit_metric_slot(PGV_BIT_HAMMING), PGV_F32, nbits, nbits, elements, n, payload, payload_bytes, out);
+}
+
+// ... over bit strings under bit_jaccard_ops (sql/vector.sql:907-911, the same type info): the same rows, scored with
+// jaccard_distance (src/bitvec.c:60-70 over BitJaccardDistanceDefault, src/bitutils.c:99-131).  The mirror's metric slot
+// says so, and with it every view, every exported handle and every launch (RowsView::jaccard, dispatch_rows).
+int pgv_hnsw_upload_jaccard(pgv_ctx *ctx, int nbits, const void *elements, int64_t n, const void *payload, int payload_bytes,
+                            pgv_hnsw **out) {
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_jaccard: ctx/out is NULL");
+    *out = nullptr;
+    if (nbits < 1 || nbits > kHnswMaxBits)
+        PGV_FAIL(PGV_ERR_DIMS, "bit dimensions %d outside 1..%d (HNSW_MAX_DIM * 32, src/hnswutils.c:1414)", nbits, kHnswMaxBits);
+    return hnsw_upload_rows(ctx, bit_metric_slot(PGV_BIT_JACCARD), PGV_F32, nbits, nbits, elements, n, payload, payload_bytes, out);
 }
 
 static int hnsw_upload_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nbits, const void *elements,
@@ -229,7 +242,9 @@ struct HnswHandleWire {
     int32_t device, metric, dtype, dim, m, entry;
     int64_t n, nbr_total;
     uint64_t graph_bytes;
-    int32_t payload_bytes, nbits;  // nbits > 0: a bit mirror (pgv_hnsw_upload_bits); 0 otherwise, as the word always was
+    // nbits > 0: a bit mirror, and `metric` above is its pgv_bit_metric (0 Hamming -- what the word always held for a bit
+    // mirror -- or 1 Jaccard: an importer walks with the exporter's keys); 0 otherwise, as the word always was
+    int32_t payload_bytes, nbits;
     hipIpcMemHandle_t elements, graph;
 };
 static_assert(sizeof(HnswHandleWire) <= PGV_INDEX_HANDLE_BYTES, "pgv_index_handle too small for an HNSW mirror");
@@ -284,10 +299,12 @@ int pgv_hnsw_import(pgv_ctx *ctx, const pgv_index_handle *handle, pgv_hnsw **out
     if (w.device != ctx->device)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_import: the mirror lives on device %d, the context on %d", w.device, ctx->device);
     if (w.nbits != 0) {
-        if (w.nbits < 1 || w.nbits > kHnswMaxBits || w.dim != w.nbits) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_import: corrupt handle");
-    } else
+        if (w.nbits < 1 || w.nbits > kHnswMaxBits || w.dim != w.nbits || (w.metric != PGV_BIT_HAMMING && w.metric != PGV_BIT_JACCARD))
+            PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_import: corrupt handle");
+    } else {
         PGV_TRY(check_common((pgv_dtype)w.dtype, w.dim));
-    PGV_TRY(check_metric((pgv_metric)w.metric));
+        PGV_TRY(check_metric((pgv_metric)w.metric));
+    }
     if (w.n < 1 || w.m < 2 || w.m > 100 || w.entry < -1 || w.entry >= w.n || w.nbr_total < 0 || w.payload_bytes < 0 ||
         w.payload_bytes > 4096)
         PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_import: corrupt handle");

@@ -42,9 +42,11 @@ template <typename F> int dispatch_metric(pgv_metric metric, pgv_dtype dtype, F 
     };
     return dtype == PGV_F32 ? by_metric((float *)nullptr) : by_metric((__half *)nullptr);
 }
-// ... for the launchers that serve bit rows as well: <BitRow, 0> (the metric slot is unused)
+// ... for the launchers that serve bit rows as well (the HNSW walk and its pair scorer): <BitRow, 0> Hamming distance,
+// <BitRow, 1> Jaccard distance (RowsView::jaccard: the metric slot of a bit mirror)
 template <typename F> int dispatch_rows(const RowsView &v, F f) {
     if (!v.bits()) return dispatch_metric(v.metric, v.dtype(), f);
+    if (v.jaccard()) return f((BitRow *)nullptr, std::integral_constant<int, 1>());
     return f((BitRow *)nullptr, std::integral_constant<int, 0>());
 }
 
@@ -66,6 +68,38 @@ __device__ __forceinline__ Raw16 load16(const void *p) {
 // bytes; zero padding adds nothing)
 __device__ __forceinline__ int hamming16(const Raw16 &a, const Raw16 &b) {
     return __popc(a.w[0] ^ b.w[0]) + __popc(a.w[1] ^ b.w[1]) + __popc(a.w[2] ^ b.w[2]) + __popc(a.w[3] ^ b.w[3]);
+}
+
+// bits set in either of two 16-byte slices: with hamming16, what jaccard_distance needs of a pair of rows
+// (BitJaccardDistanceDefault, src/bitutils.c:99-131: ab = |a & b| = u - x, aa + bb - ab = |a | b| = u)
+__device__ __forceinline__ int union16(const Raw16 &a, const Raw16 &b) {
+    return __popc(a.w[0] | b.w[0]) + __popc(a.w[1] | b.w[1]) + __popc(a.w[2] | b.w[2]) + __popc(a.w[3] | b.w[3]);
+}
+
+// The walk's 32-bit key of a Jaccard distance, from x = popcount(a ^ b) and u = popcount(a | b), 0 <= x <= u <= 64 000.
+// The reference's float8 is the rational x / u through two monotone roundings (1 when u - x is 0, else 1 - (u - x) / u);
+// two different rationals with denominators <= 64 000 are at least 1 / 64 000^2 apart, so floor(x * S / u) with
+// 64 000^2 < S is strictly monotone and injective on them: the keys order and tie exactly as the reference's doubles do.
+// u = 0 (two empty strings) and x = u (nothing in common) are both distance 1: key S.  Keys never reach 0xffffffff.
+constexpr uint32_t kJaccardScale = 0xFFFFFF00u;
+static_assert(kJaccardScale > 64000ull * 64000ull, "the Jaccard key must separate any two ratios of bit counts");
+__device__ __forceinline__ uint32_t jaccard_key(int x, int u) {
+    if (x >= u) return kJaccardScale;
+    // floor(x * S / u) by long division in 16-bit digits: u < 2^16 and the top digit of x * S is below u (x < u), so two
+    // 32-bit divisions give the two digits of the quotient -- a 64-bit division is several times the instructions
+    const uint64_t n = (uint64_t)(uint32_t)x * kJaccardScale;
+    const uint32_t d = (uint32_t)u;
+    const uint32_t t1 = ((uint32_t)(n >> 32) << 16) | ((uint32_t)(n >> 16) & 0xffffu);
+    const uint32_t q1 = t1 / d, r1 = t1 - q1 * d;
+    const uint32_t t0 = (r1 << 16) | ((uint32_t)n & 0xffffu);
+    return (q1 << 16) | (t0 / d);
+}
+// ... and the value handed back: (float) of the reference's float8 for the pair, bit for bit (IEEE double division: the
+// build has no fast-math flag)
+__device__ __forceinline__ float jaccard_value(int x, int u) {
+    const int ab = u - x;
+    if (ab <= 0) return 1.0f;
+    return (float)(1.0 - (double)ab / (double)u);
 }
 
 // unpack to fp32 lanes (exact for binary16: src/halfutils.h:62-141)

@@ -98,10 +98,15 @@ struct RowsView {
     pgv_metric metric;
     const int64_t *ptr = nullptr;  // Sparse: [n + 1] where each row's pairs start
     bool bits() const { return kind == RowKind::Bits; }
+    // bit rows ranked by jaccard_distance (an HNSW mirror of pgv_hnsw_upload_jaccard): their metric slot holds
+    // bit_metric_slot(PGV_BIT_JACCARD) = 1; a Hamming mirror's holds 0 and a bit IVFFlat index's PGV_L1, the placeholders
+    // they always held, so no view of an index can say Jaccard
+    bool jaccard() const { return bits() && (int)metric == (int)PGV_BIT_JACCARD; }
     bool sparse() const { return kind == RowKind::Sparse; }
     pgv_dtype dtype() const { return kind == RowKind::F16 ? PGV_F16 : PGV_F32; }
     size_t row_bytes() const { return bits() ? (size_t)geom.ld : (size_t)geom.ld * elem_size(dtype()); }
 };
+inline pgv_metric bit_metric_slot(pgv_bit_metric m) { return static_cast<pgv_metric>((int)m); }
 inline RowKind row_kind(pgv_dtype t) { return t == PGV_F16 ? RowKind::F16 : RowKind::F32; }
 
 // The graph of an HNSW mirror (pgv_hnsw_set_graph): ONE allocation holding levels | nbr_start | nbr, so that one
@@ -276,8 +281,9 @@ struct HnswElements {
     pgv_metric metric = PGV_L2SQ;
     pgv_dtype dtype = PGV_F32;
     int dim = 0;
-    // > 0: a mirror of packed bit strings (pgv_hnsw_upload_bits).  Its element type is not a pgv_dtype: rows are nbits
-    // bits in geom.nvec 16-byte vectors, scored by xor + popcount; metric, dtype and dim are unused (dim = nbits)
+    // > 0: a mirror of packed bit strings (pgv_hnsw_upload_bits / _jaccard).  Its element type is not a pgv_dtype: rows are
+    // nbits bits in geom.nvec 16-byte vectors, scored by popcounts; dtype and dim are unused (dim = nbits), and metric is
+    // bit_metric_slot() of the mirror's pgv_bit_metric: 0 (what it always held) bit_hamming_ops, 1 bit_jaccard_ops
     int nbits = 0;
     // a mirror of sparsevec elements (pgv_hnsw_upload_sparse): `elements` holds the rows' (index, value) pairs one row
     // after the other (and one slack pair), sparse_ptr [n + 1] where each row starts -- in the same allocation, like the
