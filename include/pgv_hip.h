@@ -787,7 +787,8 @@ int			pgv_hnsw_get_payload(pgv_hnsw * h, const int64_t *elements, int n, void *o
  * the Hamming distances as floats (exact: at most 64 000); pgv_hnsw_score_pairs likewise; pgv_hnsw_set_graph,
  * pgv_hnsw_update_graph, pgv_hnsw_get_payload, pgv_hnsw_share and pgv_hnsw_export / pgv_hnsw_import work as on any
  * mirror (views and importers know the element type and nbits).  Every build-side entry (pgv_hnsw_build_*,
- * pgv_hnsw_link_*, pgv_hnsw_score_groups) returns PGV_ERR_ARG before any launch: bit graphs are not built here.
+ * pgv_hnsw_link_*, pgv_hnsw_score_groups) returns PGV_ERR_ARG before any launch on a mirror of THIS entry: a bit graph is
+ * built on a mirror of pgv_hnsw_upload_bits_buildable below.
  */
 int			pgv_hnsw_upload_bits(pgv_ctx * ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
 								 const void *payload, int payload_bytes, pgv_hnsw * *out);
@@ -816,13 +817,36 @@ int			pgv_hnsw_upload_bits(pgv_ctx * ctx, pgv_bit_metric metric, int nbits, cons
  * On such a mirror pgv_hnsw_search, pgv_hnsw_score, pgv_hnsw_score_pairs, pgv_hnsw_set_graph, pgv_hnsw_update_graph,
  * pgv_hnsw_get_payload, pgv_hnsw_share, pgv_hnsw_export / pgv_hnsw_import (the handle carries the bit metric: an
  * importer walks with the exporter's keys) and pgv_hnsw_scan_begin / _next / _drain / _end work as on a Hamming mirror.
- * Every build-side entry returns PGV_ERR_ARG before any launch, as on any bit mirror.
- * Not served: the graph build (a Jaccard graph comes from the reference's build); ext/, which keeps handing the bit
+ * Every build-side entry returns PGV_ERR_ARG before any launch, as on a mirror of pgv_hnsw_upload_bits: a Jaccard graph
+ * is built on a mirror of pgv_hnsw_upload_bits_buildable below (or comes from the reference's build).
+ * Not served: ext/, which keeps handing the bit
  * opclasses to the CPU path; an IVFFlat index (the reference has no ivfflat Jaccard opclass).  bench.py does not measure
  * this entry, tools/bench_jaccard_hnsw.py does.
  */
 int			pgv_hnsw_upload_jaccard(pgv_ctx * ctx, int nbits, const void *elements, int64_t n, const void *payload,
 									int payload_bytes, pgv_hnsw * *out);
+
+/*
+ * A bit mirror to BUILD on: `CREATE INDEX ... USING hnsw (... bit_hamming_ops | bit_jaccard_ops)`.  metric is
+ * PGV_BIT_HAMMING or PGV_BIT_JACCARD; layout, limits and errors are pgv_hnsw_upload_bits'.  The mirror behaves in every
+ * entry the two mirrors above serve exactly as they do (search, score, score_pairs, scan_*, set / update_graph, payload,
+ * share, export), and IN ADDITION pgv_hnsw_build_search, _build_neighbors, _build_search_keep, _build_select_kept,
+ * pgv_hnsw_link_begin / _prepare / _apply / _end and pgv_hnsw_score_groups serve it with the semantics they have on a
+ * dense mirror.  Distances they return and compare are floats, as HnswCandidate.distance is (the casts at
+ * src/hnswutils.c:1052 and :1336): Hamming counts, or the (float) of jaccard_distance's float8 as pgv_hnsw_score_pairs
+ * returns it.  Under Jaccard the SEARCH still ranks by the integer key, so every candidate list W is in the float8's order;
+ * its distances are then formed from (x, u) once more.  Distinct float8 values may round to one float: the list keeps W's
+ * order (the reference does not sort a new element's list again, :1351), and selection and HnswUpdateConnection compare
+ * the floats, `<=` at :1052 included.
+ * A view (pgv_hnsw_share) inherits the property: the host build runs on views.  An importer of its export does NOT: the
+ * handle's wire format has no field for it and importers do not build -- there the build-side entries are PGV_ERR_ARG
+ * as on any bit mirror.  Sparse mirrors keep rejecting.
+ * pgv_hnsw_buildable_bits: nbits of a mirror (or view) uploaded here, 0 for every other mirror and for NULL.
+ * pgv_host_hnsw_build_bits (pgv_host.h) is the build; tools/bench_bit_hnsw_build.py measures it.
+ */
+int			pgv_hnsw_upload_bits_buildable(pgv_ctx * ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
+										   const void *payload, int payload_bytes, pgv_hnsw * *out);
+int			pgv_hnsw_buildable_bits(const pgv_hnsw * h);
 
 /*
  * ---- HNSW over sparsevec elements.
@@ -846,7 +870,7 @@ int			pgv_hnsw_upload_jaccard(pgv_ctx * ctx, int nbits, const void *elements, in
  * any mirror, and pgv_hnsw_score_pairs scores element a[i] against element b[i] (b as the query).  These return
  * PGV_ERR_ARG before any launch: pgv_hnsw_search and pgv_hnsw_score (they take dense queries: use the _sparse twins),
  * pgv_hnsw_export (the handle has no fields for a second allocation; nothing can be imported), every pgv_hnsw_build_* and
- * pgv_hnsw_link_* entry and pgv_hnsw_score_groups (sparse graphs are not built here, like bit graphs).  The _sparse
+ * pgv_hnsw_link_* entry and pgv_hnsw_score_groups (sparse graphs are not built here).  The _sparse
  * entries on any other mirror are PGV_ERR_ARG too.
  * Not served: a device-side sparsevec_l2_normalize, the build, the ext/ glue (ext/ returns every sparsevec opclass to
  * the CPU path); bench.py does not measure these entries, tools/bench_sparse_hnsw.py does.

@@ -55,6 +55,7 @@ def _load():
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     P, I, I64 = C.c_void_p, C.c_int, C.c_int64
     lib.pgv_host_hnsw_build.argtypes = [P, I, I, P, I64, I, I, P, I, C.POINTER(HnswBuilt)]
+    lib.pgv_host_hnsw_build_bits.argtypes = [P, I, P, I64, I, I, P, I, C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_built_free.argtypes = [C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_built_free.restype = None
     lib.pgv_host_hnsw_write_index.argtypes = [C.POINTER(Rel), I, I, I, I, I64, P, P, P, P, P, P, C.c_int32]
@@ -136,12 +137,21 @@ _NP = {0: np.float32, 1: np.float16}
 
 def hnsw_build(mirror, rows, m, ef_construction, rng=None, max_batch=1024):
     """pgv_host_hnsw_build: mirror = api.Hnsw holding exactly `rows`; returns a dict with levels,
-    nbr_start, nbr, entry, dup_of (numpy copies) and the counters"""
-    rows = np.ascontiguousarray(rows, dtype=_NP[mirror.dtype])
+    nbr_start, nbr, entry, dup_of (numpy copies) and the counters.  A bit mirror (api.BitHnsw / api.JaccardHnsw with
+    buildable=True) takes its packed rows [n x (nbits + 7) // 8] uint8: pgv_host_hnsw_build_bits."""
     b = HnswBuilt()
-    host_check(lib.pgv_host_hnsw_build(mirror.h, mirror.dtype, rows.shape[1], C.c_void_p(rows.ctypes.data),
-                                       rows.shape[0], m, ef_construction,
-                                       C.byref(rng) if rng is not None else None, max_batch, C.byref(b)))
+    if getattr(mirror, "nbits", None):
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        if rows.ndim != 2 or rows.shape[1] != (mirror.nbits + 7) // 8:
+            raise _lib.PgvError(_lib.PGV_ERR_ARG, "hnsw_build: a bit mirror takes rows [n x (nbits + 7) // 8] uint8")
+        host_check(lib.pgv_host_hnsw_build_bits(mirror.h, mirror.nbits, C.c_void_p(rows.ctypes.data), rows.shape[0], m,
+                                                ef_construction, C.byref(rng) if rng is not None else None, max_batch,
+                                                C.byref(b)))
+    else:
+        rows = np.ascontiguousarray(rows, dtype=_NP[mirror.dtype])
+        host_check(lib.pgv_host_hnsw_build(mirror.h, mirror.dtype, rows.shape[1], C.c_void_p(rows.ctypes.data),
+                                           rows.shape[0], m, ef_construction,
+                                           C.byref(rng) if rng is not None else None, max_batch, C.byref(b)))
     n = b.n
 
     def copy(ptr, ctype, count):

@@ -52,6 +52,7 @@ SYMBOLS = [
     "pgv_hnsw_upload_sparse", "pgv_hnsw_score_sparse", "pgv_hnsw_search_sparse",
     "pgv_hnsw_scan_begin", "pgv_hnsw_scan_next", "pgv_hnsw_scan_drain", "pgv_hnsw_scan_end",
     "pgv_hnsw_upload_jaccard",
+    "pgv_hnsw_upload_bits_buildable", "pgv_hnsw_buildable_bits",
 ]
 
 
@@ -129,6 +130,8 @@ def _load():
     lib.pgv_hnsw_get_payload.argtypes = [P, P, I, P]
     lib.pgv_hnsw_upload_bits.argtypes = [P, I, I, P, I64, P, I, C.POINTER(P)]
     lib.pgv_hnsw_upload_jaccard.argtypes = [P, I, P, I64, P, I, C.POINTER(P)]
+    lib.pgv_hnsw_upload_bits_buildable.argtypes = [P, I, I, P, I64, P, I, C.POINTER(P)]
+    lib.pgv_hnsw_buildable_bits.argtypes = [P]
     lib.pgv_exact_topk.argtypes = [P, I, I, I, P, I, P, I64, I, P, P]
     lib.pgv_ctx_set_bound.argtypes = [P, I]
     lib.pgv_builder_begin.argtypes = [P, I, I, I, I, P, I64, C.POINTER(P)]
@@ -196,6 +199,7 @@ def _load():
     lib.pgv_hnsw_build_search.argtypes = [P, P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_build_neighbors.argtypes = [P, P, P, I, I, I, P, P, P, P, P]
     lib.pgv_hnsw_score_pairs.argtypes = [P, P, P, I64, P]
+    lib.pgv_hnsw_score_groups.argtypes = [P, P, P, P, P, I, I64, I64, P]
     lib.pgv_hnsw_update_graph.argtypes = [P, C.c_int32, P, I, P, P]
     lib.pgv_hnsw_upload_sparse.argtypes = [P, I, I, P, P, P, I64, P, I, C.POINTER(P)]
     lib.pgv_hnsw_score_sparse.argtypes = [P, P, P, P, I, P, P, I64, P]

@@ -970,10 +970,12 @@ class BitHnsw(Hnsw):
     """device mirror of an HNSW index over packed bit strings, `USING hnsw (... bit_hamming_ops)` (pgv_hnsw_upload_bits):
     elements [n x (nbits + 7) // 8] uint8, first bit in the top bit of byte 0 (np.packbits' order), pad bits zero.
     set_graph, update_graph, get_payload, export and close are Hnsw's; search and score take packed queries and return
-    Hamming distances as float32 (exact)."""
+    Hamming distances as float32 (exact).  buildable=True uploads through pgv_hnsw_upload_bits_buildable: the same mirror,
+    which the build-side entries serve as well (_host.hnsw_build builds its graph)."""
 
-    def __init__(self, ctx, nbits, elements, payload=None, metric=PGV_BIT_HAMMING):
+    def __init__(self, ctx, nbits, elements, payload=None, metric=PGV_BIT_HAMMING, buildable=False):
         self.ctx, self.metric, self.dtype, self.dim, self.nbits = ctx, metric, None, int(nbits), int(nbits)
+        self.buildable = bool(buildable)
         elements = _as_bytes(elements)
         n = int(elements.shape[0])
         h = C.c_void_p()
@@ -981,8 +983,9 @@ class BitHnsw(Hnsw):
         if payload is not None:
             payload = np.ascontiguousarray(payload, dtype=np.uint32)
             self.payload_words = int(payload.shape[1])
-        check(lib.pgv_hnsw_upload_bits(ctx.h, int(metric), int(nbits), ptr(elements) if n else None, n, ptr(payload),
-                                       4 * self.payload_words, C.byref(h)))
+        upload = lib.pgv_hnsw_upload_bits_buildable if buildable else lib.pgv_hnsw_upload_bits
+        check(upload(ctx.h, int(metric), int(nbits), ptr(elements) if n else None, n, ptr(payload), 4 * self.payload_words,
+                     C.byref(h)))
         self.h = h
         ctx._adopt(self)
 
@@ -991,6 +994,7 @@ class BitHnsw(Hnsw):
         """pgv_hnsw_import of a bit mirror's export: the handle carries the element type and nbits"""
         v = super().from_handle(ctx, handle, None)
         v.nbits = nbits
+        v.buildable = False  # (the handle does not carry it: importers do not build)
         return v
 
     def share(self, ctx):
@@ -998,6 +1002,7 @@ class BitHnsw(Hnsw):
         h = C.c_void_p()
         check(lib.pgv_hnsw_share(self.h, ctx.h, C.byref(h)))
         v.ctx, v.metric, v.dtype, v.dim, v.nbits, v.h = ctx, self.metric, None, self.dim, self.nbits, h
+        v.buildable = getattr(self, "buildable", False)
         v.payload_words = self.payload_words
         v._owner = self   # keeps the owner alive
         ctx._adopt(v)
@@ -1042,10 +1047,15 @@ class JaccardHnsw(BitHnsw):
     (pgv_hnsw_upload_jaccard): elements as BitHnsw takes them.  The walk ranks by an integer key of the Jaccard ratio that
     orders and ties exactly as the reference's float8 does; search, scan, score and score_pairs return Jaccard distances,
     each the float32 of the reference's float8 for the pair (1.0 when the strings share no bit).  set_graph, update_graph,
-    get_payload, export and close are Hnsw's; the graph comes from the reference's build."""
+    get_payload, export and close are Hnsw's.  The graph comes from the reference's build, or, with buildable=True
+    (pgv_hnsw_upload_bits_buildable under PGV_BIT_JACCARD), from _host.hnsw_build on this mirror."""
 
-    def __init__(self, ctx, nbits, elements, payload=None):
+    def __init__(self, ctx, nbits, elements, payload=None, buildable=False):
+        if buildable:
+            BitHnsw.__init__(self, ctx, nbits, elements, payload=payload, metric=PGV_BIT_JACCARD, buildable=True)
+            return
         self.ctx, self.metric, self.dtype, self.dim, self.nbits = ctx, PGV_BIT_JACCARD, None, int(nbits), int(nbits)
+        self.buildable = False
         elements = _as_bytes(elements)
         n = int(elements.shape[0])
         h = C.c_void_p()

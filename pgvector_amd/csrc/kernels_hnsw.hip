@@ -275,8 +275,9 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     // src/bitutils.c:99-131) counts two integers in the same loop, x = popcount(a ^ b) and u = popcount(a | b), both exact
     // like the Hamming count, and one lane forms jaccard_key(x, u): an integer that orders and ties exactly as the
     // reference's float8 does (pgv_device.h), so everything that compares keys serves it unchanged.  A key does not carry
-    // (x, u): where distances are handed back (OUT), the result elements jids[0 .. nb) -- at most ef -- are scored once
-    // more by this loop and jout[i] = jaccard_value(x, u), the (float) of the reference's float8.
+    // (x, u): where distances are handed back (OUT: a search's results, a build's W of every searched layer), the elements
+    // jids[0 .. nb) -- at most ef -- are scored once more by this loop and jout[i] = jaccard_value(x, u), the (float) of the
+    // reference's float8.
     const uint32_t *jids = nullptr;
     float *jout = nullptr;
     auto score_rows = [&](auto rc, auto oc, int nb) __attribute__((always_inline)) {
@@ -776,8 +777,12 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
                 const size_t o = ((size_t)qi * run.lcap + lc) * ef;
                 for (int j = tid; j < wn; j += kHnswThreads) {
                     run.lw_ids[o + j] = (int32_t)(wi[cur * ef + j] & ~kExpanded);
-                    run.lw_dist[o + j] = key_to_float(wk[cur * ef + j]);
+                    if constexpr (!kJaccard) run.lw_dist[o + j] = key_to_float(wk[cur * ef + j]);
                 }
+                // a Jaccard build: W is ordered by the key (the float8's order, what HnswSearchLayer leaves), the list's
+                // distances are the (float) of the float8 (HnswCandidate.distance, src/hnswutils.c:1336), which the key
+                // does not carry -- W meets the query once more.  Distinct keys may give equal floats; the order stays.
+                jaccard_out(wi + cur * ef, wn, run.lw_dist + o);
                 if (tid == 0) run.lw_cnt[(size_t)qi * run.lcap + lc] = wn;
             }
         }

@@ -255,6 +255,10 @@ __global__ __launch_bounds__(kScanThreads) void score_groups_kernel(
     float *__restrict__ out, int nvec, int lpr_log2, int nchunks) {
     constexpr int N = VecTraits<T>::N;
     constexpr int TU = 4, TV = 4;
+    // packed bit rows (a buildable bit mirror, pgv_hnsw_upload_bits_buildable): 16 counts of differing bits, and under
+    // bit_jaccard_ops (<BitRow, 1>) 16 counts of the bits set in either row as well -- score_gather_kernel's integers
+    constexpr bool kBits = std::is_same_v<T, BitRow>;
+    constexpr bool kJaccard = kBits && METRIC == 1;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const int lpr = 1 << lpr_log2;
@@ -283,11 +287,15 @@ __global__ __launch_bounds__(kScanThreads) void score_groups_kernel(
                 for (int i = 0; i < TU; i++) up[i] = rows + (size_t)gi[u0 + i < n ? u0 + i : n - 1] * row_bytes;
 #pragma unroll
                 for (int j = 0; j < TV; j++) vp[j] = rows + (size_t)gi[v0 + j < n ? v0 + j : n - 1] * row_bytes;
-                float acc[TU][TV];
+                std::conditional_t<kBits, int, float> acc[TU][TV];
+                [[maybe_unused]] int uni[TU][TV];
 #pragma unroll
                 for (int i = 0; i < TU; i++)
 #pragma unroll
-                    for (int j = 0; j < TV; j++) acc[i][j] = 0.f;
+                    for (int j = 0; j < TV; j++) {
+                        acc[i][j] = 0;
+                        if constexpr (kJaccard) uni[i][j] = 0;
+                    }
                 for (int c = 0; c < nchunks; c++) {
                     const int vi = c * lpr + sub;
                     const bool ok = vi < nvec;
@@ -297,14 +305,25 @@ __global__ __launch_bounds__(kScanThreads) void score_groups_kernel(
                     for (int i = 0; i < TU; i++) ur[i] = load16(up[i] + (size_t)vc * sizeof(Raw16));
 #pragma unroll
                     for (int j = 0; j < TV; j++) vr[j] = load16(vp[j] + (size_t)vc * sizeof(Raw16));
+                    if constexpr (kBits) {
 #pragma unroll
-                    for (int i = 0; i < TU; i++) {
-                        Unpacked<T> a(ur[i]);
+                        for (int i = 0; i < TU; i++)
 #pragma unroll
-                        for (int j = 0; j < TV; j++) {
-                            Unpacked<T> b(vr[j]);
+                            for (int j = 0; j < TV; j++) {
+                                acc[i][j] += ok ? hamming16(ur[i], vr[j]) : 0;
+                                if constexpr (kJaccard) uni[i][j] += ok ? union16(ur[i], vr[j]) : 0;
+                            }
+                    } else {
 #pragma unroll
-                            for (int e = 0; e < N; e++) acc[i][j] = accum<METRIC>(acc[i][j], ok ? a.v[e] : 0.f, ok ? b.v[e] : 0.f);
+                        for (int i = 0; i < TU; i++) {
+                            Unpacked<T> a(ur[i]);
+#pragma unroll
+                            for (int j = 0; j < TV; j++) {
+                                Unpacked<T> b(vr[j]);
+#pragma unroll
+                                for (int e = 0; e < N; e++)
+                                    acc[i][j] = accum<METRIC>(acc[i][j], ok ? a.v[e] : 0.f, ok ? b.v[e] : 0.f);
+                            }
                         }
                     }
                 }
@@ -312,9 +331,16 @@ __global__ __launch_bounds__(kScanThreads) void score_groups_kernel(
                 for (int i = 0; i < TU; i++)
 #pragma unroll
                     for (int j = 0; j < TV; j++) {
-                        const float sum = group_sum_to_last(acc[i][j], lpr_log2);
+                        const float sum = group_sum_to_last((float)acc[i][j], lpr_log2);  // (a bit count: exact in fp32)
                         const int u = u0 + i, v = v0 + j;
-                        if (sub == lpr - 1 && u < n && v < u) out[p0 + (int64_t)u * (u - 1) / 2 - base + v] = finish<METRIC>(sum);
+                        const bool mine = sub == lpr - 1 && u < n && v < u;
+                        const int64_t at = p0 + (int64_t)u * (u - 1) / 2 - base + v;
+                        if constexpr (kJaccard) {
+                            const int bits = (int)group_sum_to_last((float)uni[i][j], lpr_log2);
+                            if (mine) out[at] = jaccard_value((int)sum, bits);
+                        } else {
+                            if (mine) out[at] = finish<METRIC>(sum);
+                        }
                     }
             }
         }
@@ -464,8 +490,8 @@ int launch_score_gather(pgv_ctx *ctx, const RowsView &v, const void *queries, co
 
 int launch_score_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride,
                         const int32_t *n_arr, const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out) {
-    if (v.bits()) PGV_FAIL(PGV_ERR_ARG, "score groups: fp32 / fp16 rows only");
-    return dispatch_metric(v.metric, v.dtype(), [&](auto *tp, auto mc) {
+    if (v.sparse()) PGV_FAIL(PGV_ERR_ARG, "score groups: fixed-width rows only");
+    return dispatch_rows(v, [&](auto *tp, auto mc) {
         return launch_groups_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(
             ctx, v.geom, v.rows, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out);
     });

@@ -16,8 +16,8 @@ static size_t hnsw_payload_offset(int64_t n, size_t row_bytes) {
     return ((size_t)(n > 0 ? n : 1) * row_bytes + 255) & ~(size_t)255;
 }
 
-// a bit mirror (pgv_hnsw_upload_bits, pgv_hnsw_upload_jaccard): rows of whole bytes scored by popcounts; no build-side entry
-// serves it
+// a bit mirror (pgv_hnsw_upload_bits, pgv_hnsw_upload_jaccard): rows of whole bytes scored by popcounts; the build-side
+// entries serve it only where it was uploaded for that (pgv_hnsw_upload_bits_buildable)
 static bool hnsw_is_bits(const pgv_hnsw *h) { return h->nbits > 0; }
 
 // ... and a sparse mirror (pgv_hnsw_upload_sparse): CSR rows scored by sparse_pair.h; searched and scored through the
@@ -26,7 +26,7 @@ static bool hnsw_is_sparse(const pgv_hnsw *h) { return h->sparse; }
 
 #define PGV_NO_BUILD(h, who)                                                                                      \
     do {                                                                                                         \
-        if ((h) && hnsw_is_bits(h))                                                                              \
+        if ((h) && hnsw_is_bits(h) && !(h)->buildable)                                                           \
             PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits / _jaccard) is searched and scored, not built on", who); \
         if ((h) && hnsw_is_sparse(h))                                                                            \
             PGV_FAIL(PGV_ERR_ARG, "%s: a sparse mirror (pgv_hnsw_upload_sparse) is searched and scored, not built on", who); \
@@ -98,6 +98,25 @@ int pgv_hnsw_upload_jaccard(pgv_ctx *ctx, int nbits, const void *elements, int64
         PGV_FAIL(PGV_ERR_DIMS, "bit dimensions %d outside 1..%d (HNSW_MAX_DIM * 32, src/hnswutils.c:1414)", nbits, kHnswMaxBits);
     return hnsw_upload_rows(ctx, bit_metric_slot(PGV_BIT_JACCARD), PGV_F32, nbits, nbits, elements, n, payload, payload_bytes, out);
 }
+
+// The same rows under either bit metric, uploaded to be BUILT on as well (`CREATE INDEX ... USING hnsw (... bit_hamming_ops /
+// bit_jaccard_ops)`, HnswFindElementNeighbors and HnswUpdateNeighborsInMemory over bit elements): everything the two
+// entries above give, and the build-side entries (pgv_hnsw_build_*, pgv_hnsw_link_*, pgv_hnsw_score_groups) serve the
+// mirror and its views.  Their distances are floats, as HnswCandidate.distance is: Hamming counts, or the (float) of
+// jaccard_distance's float8.
+int pgv_hnsw_upload_bits_buildable(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const void *elements, int64_t n,
+                                   const void *payload, int payload_bytes, pgv_hnsw **out) {
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_bits_buildable: ctx/out is NULL");
+    *out = nullptr;
+    if (metric != PGV_BIT_HAMMING && metric != PGV_BIT_JACCARD) PGV_FAIL(PGV_ERR_ARG, "unknown bit metric %d", (int)metric);
+    if (nbits < 1 || nbits > kHnswMaxBits)
+        PGV_FAIL(PGV_ERR_DIMS, "bit dimensions %d outside 1..%d (HNSW_MAX_DIM * 32, src/hnswutils.c:1414)", nbits, kHnswMaxBits);
+    PGV_TRY(hnsw_upload_rows(ctx, bit_metric_slot(metric), PGV_F32, nbits, nbits, elements, n, payload, payload_bytes, out));
+    (*out)->buildable = true;
+    return PGV_OK;
+}
+
+int pgv_hnsw_buildable_bits(const pgv_hnsw *h) { return h && hnsw_is_bits(h) && h->buildable ? h->nbits : 0; }
 
 static int hnsw_upload_rows(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, int nbits, const void *elements,
                             int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {

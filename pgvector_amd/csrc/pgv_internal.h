@@ -285,6 +285,9 @@ struct HnswElements {
     // nbits bits in geom.nvec 16-byte vectors, scored by popcounts; dtype and dim are unused (dim = nbits), and metric is
     // bit_metric_slot() of the mirror's pgv_bit_metric: 0 (what it always held) bit_hamming_ops, 1 bit_jaccard_ops
     int nbits = 0;
+    // a bit mirror uploaded by pgv_hnsw_upload_bits_buildable: the build-side entries serve it.  A view has it from its
+    // owner; an importer does not (the exported handle has no field for it, and importers do not build)
+    bool buildable = false;
     // a mirror of sparsevec elements (pgv_hnsw_upload_sparse): `elements` holds the rows' (index, value) pairs one row
     // after the other (and one slack pair), sparse_ptr [n + 1] where each row starts -- in the same allocation, like the
     // payload; dtype and geom are unused, dim is the vectors' dimension

@@ -2433,11 +2433,12 @@ start_graph(pgv_hnsw * mirror, int64_t n, int m, const pgv_rng * rng, pgv_hnsw_b
 	return PGV_OK;
 }
 
-int
-pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *rows, int64_t n, int m,
-					int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
+/* The build over rows of item_bytes each, whatever they hold: the mirror scores them, this side copies nothing out of
+ * them and compares them as bytes (find_duplicate).  pgv_host_hnsw_build and pgv_host_hnsw_build_bits are this. */
+static int
+build_items(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, int m, int ef_construction,
+			const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
 {
-	const size_t item_bytes = (size_t) dim * (dtype == PGV_F32 ? 4 : 2);
 	/* SelectNeighbors of the new elements' candidate lists: on the device with the searches (the default), or here from
 	 * the lists and their pair triangles (PGV_HNSW_HOST_SELECT=1: the form the device's is tested against) */
 	const int	device_select = !(getenv("PGV_HNSW_HOST_SELECT") && atoi(getenv("PGV_HNSW_HOST_SELECT")) != 0);
@@ -2494,3 +2495,31 @@ pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *row
 	return rc;
 }
 
+int
+pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *rows, int64_t n, int m,
+					int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
+{
+	return build_items(mirror, (size_t) dim * (dtype == PGV_F32 ? 4 : 2), rows, n, m, ef_construction, rng, max_batch, out);
+}
+
+/* (a weak reference: this file is also linked against stand-ins of the device library that have no bit mirrors, and
+ * against such a library the bits entry says so instead of failing to link) */
+#pragma weak pgv_hnsw_buildable_bits
+
+/* ... over packed bit strings: rows of (nbits + 7) / 8 bytes, VARBITBYTES, the caller's pad bits zero -- so that equal
+ * strings are equal bytes (the duplicate check compares whole bytes, as datumIsEqual compares the varbit datums) */
+int
+pgv_host_hnsw_build_bits(pgv_hnsw * mirror, int nbits, const void *rows, int64_t n, int m, int ef_construction,
+						 const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
+{
+	if (!mirror || !out || (n > 0 && !rows))
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: mirror/rows/out is NULL");
+	if (nbits < 1 || nbits > 64000)
+		return pgv_host_fail(PGV_ERR_DIMS, "pgv_host_hnsw_build_bits: bit dimensions %d outside 1..64000", nbits);
+	if (!pgv_hnsw_buildable_bits)
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: the device library has no pgv_hnsw_upload_bits_buildable");
+	if (pgv_hnsw_buildable_bits(mirror) != nbits)
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: not a mirror of %d-bit rows uploaded by "
+							 "pgv_hnsw_upload_bits_buildable", nbits);
+	return build_items(mirror, (size_t) (nbits + 7) / 8, rows, n, m, ef_construction, rng, max_batch, out);
+}

@@ -101,6 +101,15 @@ typedef struct pgv_hnsw_built
 
 int			pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *rows, int64_t n, int m,
 								int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out);
+/*
+ * The same build over packed BIT strings (`USING hnsw (... bit_hamming_ops / bit_jaccard_ops)`): mirror is
+ * pgv_hnsw_upload_bits_buildable of all n rows under either bit metric, rows the same [n x (nbits + 7) / 8] bytes in host
+ * memory, pad bits zero (duplicates are equal bytes).  One body with pgv_host_hnsw_build -- the batches, the three forms
+ * (device link, PGV_HNSW_HOST_LINK=1, PGV_HNSW_HOST_SELECT=1) and the result are its.  Any other mirror, or one of another
+ * nbits, is PGV_ERR_ARG before any launch.
+ */
+int			pgv_host_hnsw_build_bits(pgv_hnsw * mirror, int nbits, const void *rows, int64_t n, int m, int ef_construction,
+									 const pgv_rng * rng, int max_batch, pgv_hnsw_built * out);
 void		pgv_host_hnsw_built_free(pgv_hnsw_built * built);
 /*
  * Inside a server: a callback pgv_host_hnsw_build polls between batches, on the calling thread (per thread; NULL
