@@ -126,7 +126,82 @@ struct HnswScanDev {
     int *overflow;          // 0, or 1 + the first query seen to overflow its pool
     int drain;              // pgv_hnsw_scan_drain: the entry step alone
 };
-constexpr int kScanLdsWords = 256 + 16;  // the entry step's histogram and its scalars, behind sc
+
+// A walk's scalars in LDS, one workgroup's
+struct WalkScalars {
+    int query, wn, nb;  // the query being walked; |W|; the size of the batch being scored
+    int cand, cur;      // the candidate being expanded (-1: none left); which of W's two buffers is live
+    int tn, tread;      // |T|; T's next unread entry
+    uint32_t tkey;      // the key T's entries share
+    int pool_n;         // a scan's live pool entries, for the batch
+};
+// what a scan's entry step keeps in LDS on top: the radix descent's histogram, its verdict, and each wavefront's counts
+struct ScanEntryLds {
+    uint32_t hist[256];
+    int bucket, rank;  // the pass's digit and the rank left inside it
+    int lt[kHnswWaves], eq[kHnswWaves];
+};
+constexpr size_t kWalkScalarBytes = 64, kScanEntryBytes = (256 + 16) * sizeof(uint32_t), kHnswLdsLimit = 150 * 1024;
+static_assert(sizeof(WalkScalars) <= kWalkScalarBytes && sizeof(ScanEntryLds) <= kScanEntryBytes, "LDS regions too small");
+
+// The walk's dynamic LDS, byte offsets (the query region starts at 0): what the launcher sizes and the kernel carves.
+//   query row | W keys [2][ef] | W ids [2][ef] | batch keys [2 m] | batch ids [2 m] | T ids [ef] | WalkScalars | ScanEntryLds
+// (a sparse walk's query region: the query's (index, value) pairs [sq_cap] | matched bitmaps [waves][bm_words])
+struct HnswLds {
+    size_t wk, wi, bk, bi, ti, sc, entry, total;
+    __host__ __device__ constexpr HnswLds(size_t query_bytes, int ef, int m, bool scan)
+        : wk(query_bytes), wi(wk + 2 * (size_t)ef * 4), bk(wi + 2 * (size_t)ef * 4), bi(bk + 2 * (size_t)m * 4),
+          ti(bi + 2 * (size_t)m * 4), sc(ti + (size_t)ef * 4), entry(sc + kWalkScalarBytes),
+          total(entry + (scan ? kScanEntryBytes : 0)) {}
+};
+static_assert(HnswLds(6144, 1000, 100, false).total == 6144 + 1000 * 16 + 100 * 16 + 1000 * 4 + 64 &&
+                  HnswLds(16, 1, 2, true).total == 16 + 16 + 32 + 4 + 64 + 1088,
+              "a walk takes query_bytes + ef * 16 + m * 16 + ef * 4 + 64 bytes of LDS, a scan 1088 more");
+
+// Wavefront compaction: the lanes whose `take` holds get consecutive slots from `count` on, in lane order.  Returns this
+// lane's slot (to be used where take holds; the caller guards its store) and moves count past the takers.  A whole
+// wavefront calls.
+__device__ __forceinline__ int wave_append(bool take, int lane, int &count) {
+    const unsigned long long bal = __ballot(take);
+    const int at = count + __popcll(bal & ((1ull << lane) - 1ull));
+    count += __popcll(bal);
+    return at;
+}
+
+// Where the stable merge of a scored batch (keys bk[0 .. nb), batch order) into W (keys ck[0 .. wn), ascending) puts an
+// entry.  The new W, the tie list and a scan's pool all ask here: |T| <= ef - 1 and the pool's discard order rest on
+// their agreeing.
+struct MergePos {
+    const uint32_t *ck, *bk;
+    int wn, nb;
+    // old entry j (key = ck[j]) moves up by the batch entries strictly nearer
+    __device__ __forceinline__ int old_slot(int j, uint32_t key) const {
+        int s = j;
+        for (int b = 0; b < nb; b++) s += bk[b] < key;
+        return s;
+    }
+    // batch entry i (key = bk[i]) goes after every old entry that is not farther and after the batch entries that are
+    // nearer or equal-and-earlier.  T's own quantity comes out of the same pass: `before`, the entries not farther
+    // that are there when its turn comes -- those old entries, and the batch entries ahead of it.
+    __device__ __forceinline__ int batch_slot(int i, uint32_t key, int &before) const {
+        int lo = 0, hi = wn;  // first old entry with key > this one
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ck[mid] <= key)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        int s = lo;
+        before = lo;
+        for (int b = 0; b < nb; b++) {
+            before += b < i && bk[b] <= key;
+            s += (bk[b] < key) || (bk[b] == key && b < i);
+        }
+        return s;
+    }
+    __device__ __forceinline__ int batch_slot(int i, uint32_t key) const { int unused; return batch_slot(i, key, unused); }
+};
 
 // The entry step of a resumed batch (ResumeScanItems' pairingheap_remove_first loop, src/hnswscan.c:61-87, in bulk): the
 // `take` smallest of pool[0 .. pn) by (key, position) into wk0 / wi0 in that order; the rest of the pool closes up, order
@@ -137,7 +212,7 @@ constexpr int kScanLdsWords = 256 + 16;  // the entry step's histogram and its s
 //      stage in position order and its others back into the pool at or below the chunk's own reads;
 //   3. rank-by-counting of the <= 1000 staged entries by (key, stage position) -- stage order is pool order.
 __device__ __forceinline__ void scan_entry_step(uint2 *__restrict__ pool, int pn, int take, uint32_t *wk0, uint32_t *wi0,
-                                                uint32_t *stage_k, uint32_t *stage_i, uint32_t *hist, int *es) {
+                                                uint32_t *stage_k, uint32_t *stage_i, ScanEntryLds &el) {
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
     uint32_t K = 0xffffffffu;
     int need = pn;  // pn <= take: everything goes, whatever its key
@@ -145,27 +220,27 @@ __device__ __forceinline__ void scan_entry_step(uint2 *__restrict__ pool, int pn
         uint32_t prefix = 0, mask = 0;
         int r = take;  // the r-th smallest of the keys that match prefix under mask
         for (int shift = 24; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
+            el.hist[tid] = 0;
             __syncthreads();
             for (int i = tid; i < pn; i += kHnswThreads) {
                 const uint32_t key = pool[i].x;
-                if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+                if ((key & mask) == prefix) atomicAdd(&el.hist[(key >> shift) & 255u], 1u);
             }
             __syncthreads();
             if (tid == 0) {
                 int acc = 0, b = 0;
                 for (; b < 255; b++) {
-                    const int c = (int)hist[b];
+                    const int c = (int)el.hist[b];
                     if (acc + c >= r) break;
                     acc += c;
                 }
-                es[0] = b;
-                es[1] = r - acc;
+                el.bucket = b;
+                el.rank = r - acc;
             }
             __syncthreads();
-            prefix |= (uint32_t)es[0] << shift;
+            prefix |= (uint32_t)el.bucket << shift;
             mask |= 255u << shift;
-            r = es[1];
+            r = el.rank;
             __syncthreads();
         }
         K = prefix;
@@ -177,16 +252,16 @@ __device__ __forceinline__ void scan_entry_step(uint2 *__restrict__ pool, int pn
         const bool valid = i < pn;
         const uint2 e = pool[valid ? i : pn - 1];  // never predicate a load
         const bool is_lt = valid && e.x < K, is_eq = valid && e.x == K;
-        const unsigned long long bl = __ballot(is_lt), be = __ballot(is_eq);
+        int lt_mine = 0, eq_mine = 0;  // this wavefront's counts; the chunk's come from LDS
+        int lt_before = lt_run + wave_append(is_lt, lane, lt_mine);
+        int eq_before = eq_run + wave_append(is_eq, lane, eq_mine);
         if (lane == 0) {
-            es[2 + wave] = __popcll(bl);
-            es[2 + kHnswWaves + wave] = __popcll(be);
+            el.lt[wave] = lt_mine;
+            el.eq[wave] = eq_mine;
         }
         __syncthreads();  // (the whole chunk is in registers from here on)
-        int lt_before = lt_run + __popcll(bl & ((1ull << lane) - 1ull));
-        int eq_before = eq_run + __popcll(be & ((1ull << lane) - 1ull));
         for (int w = 0; w < kHnswWaves; w++) {
-            const int l = es[2 + w], q = es[2 + kHnswWaves + w];
+            const int l = el.lt[w], q = el.eq[w];
             if (w < wave) {
                 lt_before += l;
                 eq_before += q;
@@ -236,22 +311,14 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     constexpr bool kSparse = std::is_same_v<T, SparseRow>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lm0 = 2 * g.m;
-    // layout: query row | W keys [2][ef] | W ids [2][ef] | batch keys [lm0] | batch ids [lm0] | T ids [ef] | scalars
-    // (a sparse walk's query region: the query's (index, value) pairs [sq_cap] | matched bitmaps [waves][bm_words])
     Raw16 *lq = reinterpret_cast<Raw16 *>(smem);
-    size_t query_bytes;
-    if constexpr (kSparse)
-        query_bytes = sparse_query_bytes(sp.q_cap, sp.bm_words);
-    else
-        query_bytes = (size_t)g.nvec * sizeof(Raw16);
-    uint32_t *wk = reinterpret_cast<uint32_t *>(smem + query_bytes);
-    uint32_t *wi = wk + 2 * ef;
-    uint32_t *bk = wi + 2 * ef;
-    int32_t *bi = reinterpret_cast<int32_t *>(bk + lm0);
-    uint32_t *ti = reinterpret_cast<uint32_t *>(bi + lm0);  // tie list ids [ef]: |T| < ef, see the header
-    int *sc = reinterpret_cast<int *>(ti + ef);
-    // sc: [0] query, [1] |W|, [2] batch size, [3] candidate element (-1: none), [4] W buffer,
-    //     [5] |T|, [6] next unread entry of T, [7] key shared by T's entries
+    const HnswLds at(kSparse ? sparse_query_bytes(sp.q_cap, sp.bm_words) : (size_t)g.nvec * sizeof(Raw16), ef, g.m, SCAN);
+    uint32_t *wk = reinterpret_cast<uint32_t *>(smem + at.wk);
+    uint32_t *wi = reinterpret_cast<uint32_t *>(smem + at.wi);
+    uint32_t *bk = reinterpret_cast<uint32_t *>(smem + at.bk);
+    int32_t *bi = reinterpret_cast<int32_t *>(smem + at.bi);
+    uint32_t *ti = reinterpret_cast<uint32_t *>(smem + at.ti);  // tie list ids [ef]: |T| < ef, see the header
+    WalkScalars &sc = *reinterpret_cast<WalkScalars *>(smem + at.sc);
 
     const int tid = threadIdx.x;
     const int lane = tid & (kWave - 1);
@@ -415,10 +482,220 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         }
     };
 
-    for (;;) {
-        if (tid == 0) sc[0] = atomicAdd(qcounter, 1);
+    // ---- The steps of a walk, in the order the query loop below takes them.  Always inlined, like score_batch.  The two
+    // marked "wavefront 0" run under wave == 0 and hold no barrier; all 256 threads call the others.
+
+    // the query into LDS (the caller's next barrier publishes it)
+    auto stage_query = [&](int qi) __attribute__((always_inline)) {
+        if constexpr (kSparse) {
+            const int64_t qb = sp.q_ptr[qi];
+            sqn = (int)(sp.q_ptr[qi + 1] - qb);
+            QElem *sq = reinterpret_cast<QElem *>(smem);
+            for (int v = tid; v < sqn; v += kHnswThreads) sq[v] = {sp.q_idx[qb + v], sp.q_val[qb + v]};
+        } else {
+            const char *qrow = run.qids ? g.rows + (size_t)run.qids[qi] * row_bytes : run.queries + (size_t)qi * row_bytes;
+            for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
+        }
+    };
+    // the entry point is the first batch, and W to begin with
+    auto enter_graph = [&]() __attribute__((always_inline)) {
+        if (tid == 0) bi[0] = g.entry;
         __syncthreads();
-        const int qi = sc[0];
+        score_batch(1);
+        __syncthreads();
+        if (tid == 0) {
+            wk[0] = bk[0];
+            wi[0] = (uint32_t)g.entry;
+            sc.wn = 1;
+            sc.cur = 0;
+        }
+    };
+    // a fresh visited set holding the layer's entry points (src/hnswutils.c:866-885): the previous layer's W, all
+    // unexpanded again
+    auto reset_visited = [&]() __attribute__((always_inline)) {
+        for (int w = tid; w < words; w += kHnswThreads) bitmap[w] = 0u;
+        __syncthreads();
+        const int cur = sc.cur, wn = sc.wn;
+        for (int j = tid; j < wn; j += kHnswThreads) {
+            const uint32_t id = wi[cur * ef + j] & ~kExpanded;
+            wi[cur * ef + j] = id;
+            atomicOr(&bitmap[id >> 5], 1u << (id & 31));
+        }
+    };
+    // wavefront 0: the next candidate -- W's first unexpanded entry, or with W exhausted an evicted one tied with its
+    // furthest -- into sc.cand, and its unvisited neighbours at layer lc, in tuple order, into bi[0 .. sc.nb)
+    auto next_candidate = [&](int lc, int lm) __attribute__((always_inline)) {
+        uint32_t *ci = wi + sc.cur * ef;
+        const int wn = sc.wn;
+        int found = -1;
+        for (int base = 0; base < wn && found < 0; base += kWave) {
+            const int j = base + lane;
+            const bool open = j < wn && !(ci[j] & kExpanded);
+            const unsigned long long bal = __ballot(open);
+            if (bal) found = base + __ffsll((long long)bal) - 1;
+        }
+        int nb = 0, cand = -1;
+        if (found >= 0) {
+            cand = (int)ci[found];
+            if (lane == 0) ci[found] = (uint32_t)cand | kExpanded;
+        } else if (sc.tread < sc.tn) {
+            cand = (int)ti[sc.tread];
+            if (lane == 0) sc.tread = sc.tread + 1;
+        }
+        if (cand >= 0) {
+            const uint32_t c = (uint32_t)cand;
+            // neighbour tuple slice of layer lc (src/hnswutils.c:786)
+            const int64_t start = g.nbr_start[c] + (int64_t)(g.levels[c] - lc) * g.m;
+            for (int base = 0; base < lm; base += kWave) {
+                const int j = base + lane;
+                const int32_t e = j < lm ? g.nbr[start + j] : -1;
+                bool fresh = false;
+                if (e >= 0) {
+                    const uint32_t bit = 1u << (e & 31);
+                    fresh = !(atomicOr(&bitmap[e >> 5], bit) & bit);
+                }
+                const int slot = wave_append(fresh, lane, nb);
+                if (fresh) bi[slot] = e;
+            }
+        }
+        if (lane == 0) {
+            sc.nb = nb;
+            sc.cand = cand;
+        }
+    };
+    // wavefront 0: the stable merge of the scored batch into W's other buffer, truncated to ef_l; what leaves W at its
+    // furthest key goes to T, and what leaves a scan's layer 0 to the query's pool.  Every slot comes from MergePos.
+    auto merge_batch = [&](int qi, int lc, int ef_l, int nb) __attribute__((always_inline)) {
+        const int cur = sc.cur, nxt = cur ^ 1, wn = sc.wn;
+        const uint32_t *ck = wk + cur * ef, *ci = wi + cur * ef;
+        uint32_t *nk = wk + nxt * ef, *ni = wi + nxt * ef;
+        // "make robust to issues" (src/hnswutils.c:947-949): an element below this layer is scored and stays visited
+        // but is never admitted; only upper layers can see one.  They leave the batch here, the order kept.
+        if (lc > 0) {
+            int kept = 0;
+            for (int base = 0; base < nb; base += kWave) {
+                const int i = base + lane;
+                const bool keep = i < nb && g.levels[bi[i < nb ? i : 0]] >= lc;
+                const uint32_t key = i < nb ? bk[i] : 0u;
+                const int32_t id = i < nb ? bi[i] : 0;
+                const int slot = wave_append(keep, lane, kept);
+                // in-place compaction is safe: a chunk only writes at or below its own reads
+                if (keep) {
+                    bk[slot] = key;
+                    bi[slot] = id;
+                }
+            }
+            nb = kept;
+        }
+        const MergePos pos{ck, bk, wn, nb};
+        const int wn_new = wn + nb < ef_l ? wn + nb : ef_l;
+        auto to_w = [&](int s, uint32_t key, uint32_t id) __attribute__((always_inline)) {
+            if (s < ef_l) {
+                nk[s] = key;
+                ni[s] = id;
+            }
+        };
+        for (int j = lane; j < wn; j += kWave) to_w(pos.old_slot(j, ck[j]), ck[j], ci[j]);
+        for (int i = lane; i < nb; i += kWave) to_w(pos.batch_slot(i, bk[i]), bk[i], (uint32_t)bi[i]);
+        // The tie list.  With W full, its furthest key K is nk[ef_l - 1].  T keeps the unexpanded candidates that were
+        // pushed out of W at exactly K: old entries, and batch entries that had been admitted when their turn came (fewer
+        // than ef_l entries not farther among W and the batch entries before them).  Entries of an older T stay only if K
+        // has not moved.
+        if (wn_new == ef_l && wn + nb > ef_l) {
+            const uint32_t K = nk[ef_l - 1];
+            int tn = sc.tn;
+            if (tn > 0 && sc.tkey != K) tn = 0;
+            const int t0 = tn > 0 ? sc.tread : 0;
+            auto to_t = [&](bool tie, uint32_t id) __attribute__((always_inline)) {
+                const int slot = wave_append(tie, lane, tn);
+                if (tie && slot < ef) ti[slot] = id;  // (slot < ef always: the guard only keeps a write inside T)
+            };
+            for (int base = 0; base < wn; base += kWave) {
+                const int j = base + lane;
+                const bool live = j < wn && ck[j] == K && !(ci[j] & kExpanded);
+                to_t(live && pos.old_slot(j, K) >= ef_l, live ? ci[j] : 0u);
+            }
+            for (int base = 0; base < nb; base += kWave) {
+                const int i = base + lane;
+                const bool at_k = i < nb && bk[i] == K;
+                int before = 0;  // admitted in its turn, pushed out later:
+                to_t(at_k && pos.batch_slot(i, K, before) >= ef_l && before < ef_l, at_k ? (uint32_t)bi[i] : 0u);
+            }
+            if (lane == 0) {
+                sc.tn = tn < ef ? tn : ef;  // (tn < ef always: nothing is truncated)
+                sc.tread = t0;
+                sc.tkey = K;
+            }
+        }
+        // A scan keeps what the merge leaves past position ef (`discarded`, src/hnswutils.c:936-946, :967-973; layer 0
+        // only, src/hnswscan.c:55): the old entries pushed out, in W's order, then the batch entries that did not fit,
+        // in batch order -- whether or not they also went to T.  Never written past the pool: the count goes on, and
+        // the batch ends flagged.
+        if constexpr (SCAN) {
+            if (lc == 0 && wn + nb > ef_l) {
+                uint2 *pool = ss.pool + (size_t)qi * ss.cap;
+                int pn = sc.pool_n;
+                auto to_pool = [&](bool out, uint2 e) __attribute__((always_inline)) {
+                    const int slot = wave_append(out, lane, pn);
+                    if (out && slot < ss.cap) pool[slot] = e;
+                };
+                // (an old entry moves up by at most nb: only W's last nb entries can leave)
+                for (int base = ef_l > nb ? ef_l - nb : 0; base < wn; base += kWave) {
+                    const int j = base + lane;
+                    const uint2 e = {j < wn ? ck[j] : 0u, j < wn ? ci[j] & ~kExpanded : 0u};
+                    to_pool(j < wn && pos.old_slot(j, e.x) >= ef_l, e);
+                }
+                for (int base = 0; base < nb; base += kWave) {
+                    const int i = base + lane;
+                    const uint2 e = {i < nb ? bk[i] : 0u, i < nb ? (uint32_t)bi[i] : 0u};
+                    to_pool(i < nb && pos.batch_slot(i, e.x) >= ef_l, e);
+                }
+                if (lane == 0) sc.pool_n = pn;
+            }
+        }
+        if (lane == 0) {
+            sc.wn = wn_new;
+            sc.cur = nxt;
+        }
+    };
+    // a build's query: layer lc's W, the candidates SelectNeighbors sees
+    auto hand_out_w = [&](int qi, int lc) __attribute__((always_inline)) {
+        const int cur = sc.cur, wn = sc.wn;
+        const size_t o = ((size_t)qi * run.lcap + lc) * ef;
+        for (int j = tid; j < wn; j += kHnswThreads) {
+            run.lw_ids[o + j] = (int32_t)(wi[cur * ef + j] & ~kExpanded);
+            if constexpr (!kJaccard) run.lw_dist[o + j] = key_to_float(wk[cur * ef + j]);
+        }
+        // a Jaccard build: W is ordered by the key (the float8's order, what HnswSearchLayer leaves), the list's
+        // distances are the (float) of the float8 (HnswCandidate.distance, src/hnswutils.c:1336), which the key does
+        // not carry -- W meets the query once more.  Distinct keys may give equal floats; the order stays.
+        jaccard_out(wi + cur * ef, wn, run.lw_dist + o);
+        if (tid == 0) run.lw_cnt[(size_t)qi * run.lcap + lc] = wn;
+    };
+    // The epilogue: query qi's results are ids[0 .. cnt) (expanded flags off), nearest first (src/hnswscan.c:293-311),
+    // and the distances their keys stand for; -1 / +inf from cnt on.  A Jaccard walk scores them once more against the
+    // query, which is in LDS.  cnt == 0: ids and keys are not read.
+    auto write_results = [&](int qi, const uint32_t *ids, const uint32_t *keys, int cnt) __attribute__((always_inline)) {
+        if (!out_elem) return;
+        if (cnt > k) cnt = k;
+        // (a signed row offset: with (size_t)qi * k + j in this lambda every instantiation took six more VGPRs than with
+        // the same statements written out at each site, and seven of them lost a wavefront per SIMD)
+        const int64_t row = (int64_t)qi * k;
+        for (int j = tid; j < k; j += kHnswThreads) {
+            const bool have = j < cnt;
+            out_elem[row + j] = have ? (int64_t)(ids[j] & ~kExpanded) : -1;
+            if (!have)
+                out_dist[row + j] = __uint_as_float(0x7f800000u);
+            else if constexpr (!kJaccard)
+                out_dist[row + j] = key_to_float(keys[j]);
+        }
+        jaccard_out(ids, cnt, out_dist + row);
+    };
+
+    for (;;) {
+        if (tid == 0) sc.query = atomicAdd(qcounter, 1);
+        __syncthreads();
+        const int qi = sc.query;
         if (qi >= nq) return;
 
         int64_t scored = 0;
@@ -433,10 +710,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             const bool wanted = (!ss.want || ss.want[qi]) && !(st.flags & kScanOverflow) && g.entry >= 0;
             const bool live = wanted && (ss.drain ? st.pool_n > 0 : (!started || st.pool_n > 0));
             if (!live) {
-                for (int j = tid; j < k; j += kHnswThreads) {
-                    out_elem[(size_t)qi * k + j] = -1;
-                    out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
-                }
+                write_results(qi, nullptr, nullptr, 0);
                 if (tid == 0) {
                     ss.out_count[qi] = 0;
                     if (out_scored) out_scored[qi] = st.tuples;
@@ -447,33 +721,23 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             }
             resumed = started;
             scored = st.tuples;
-            if (tid == 0) sc[8] = st.pool_n;  // the pool's count lives here for the batch
+            if (tid == 0) sc.pool_n = st.pool_n;
             if (resumed) {
                 const int take = st.pool_n < ef ? st.pool_n : ef;
-                uint32_t *hist = reinterpret_cast<uint32_t *>(sc + 16);
-                scan_entry_step(ss.pool + (size_t)qi * ss.cap, st.pool_n, take, wk, wi, wk + ef, wi + ef, hist,
-                                reinterpret_cast<int *>(hist + 256));
+                scan_entry_step(ss.pool + (size_t)qi * ss.cap, st.pool_n, take, wk, wi, wk + ef, wi + ef,
+                                *reinterpret_cast<ScanEntryLds *>(smem + at.entry));
                 if (tid == 0) {
-                    sc[1] = take;
-                    sc[4] = 0;
-                    sc[8] = st.pool_n - take;
+                    sc.wn = take;
+                    sc.cur = 0;
+                    sc.pool_n = st.pool_n - take;
                 }
                 __syncthreads();
                 if (ss.drain) {
                     if constexpr (kJaccard) {  // (the pool keeps keys: the drained elements meet the query once more)
-                        const char *qrow = run.queries + (size_t)qi * row_bytes;
-                        for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
+                        stage_query(qi);
                         __syncthreads();
                     }
-                    for (int j = tid; j < k; j += kHnswThreads) {
-                        const bool have = j < take;
-                        out_elem[(size_t)qi * k + j] = have ? (int64_t)wi[j] : -1;
-                        if constexpr (kJaccard) {
-                            if (!have) out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
-                        } else
-                            out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[j]) : __uint_as_float(0x7f800000u);
-                    }
-                    jaccard_out(wi, take < k ? take : k, out_dist + (size_t)qi * k);
+                    write_results(qi, wi, wk, take);
                     if (tid == 0) {
                         ss.out_count[qi] = take;
                         if (ss.out_left) ss.out_left[qi] = st.pool_n - take;
@@ -488,324 +752,52 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         if (run.lw_cnt)
             for (int l = tid; l < run.lcap; l += kHnswThreads) run.lw_cnt[(size_t)qi * run.lcap + l] = 0;
         if (g.entry < 0) {  // empty index
-            if (out_elem)
-                for (int j = tid; j < k; j += kHnswThreads) {
-                    out_elem[(size_t)qi * k + j] = -1;
-                    out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
-                }
+            write_results(qi, nullptr, nullptr, 0);
             if (tid == 0 && out_scored) out_scored[qi] = 0;
             __syncthreads();
             continue;
         }
 
-        // query into LDS; the entry point is the first batch
-        if constexpr (kSparse) {
-            const int64_t qb = sp.q_ptr[qi];
-            sqn = (int)(sp.q_ptr[qi + 1] - qb);
-            QElem *sq = reinterpret_cast<QElem *>(smem);
-            for (int v = tid; v < sqn; v += kHnswThreads) sq[v] = {sp.q_idx[qb + v], sp.q_val[qb + v]};
-        } else {
-            const char *qrow = run.qids ? g.rows + (size_t)run.qids[qi] * row_bytes : run.queries + (size_t)qi * row_bytes;
-            for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
-        }
-        if (!SCAN || !resumed) {
-            if (tid == 0) bi[0] = g.entry;
-            __syncthreads();
-            score_batch(1);
-            __syncthreads();
-            if (tid == 0) {
-                wk[0] = bk[0];
-                wi[0] = (uint32_t)g.entry;
-                sc[1] = 1;
-                sc[4] = 0;
-            }
-        }
+        stage_query(qi);
+        if (!SCAN || !resumed) enter_graph();
         const int top = SCAN && resumed ? 0 : g.levels[g.entry];
 
         for (int lc = top; lc >= 0; lc--) {
             const int ef_l = lc <= qlevel ? ef : 1;
             const int lm = lc == 0 ? lm0 : g.m;
-            // a fresh visited set holding the entry points (src/hnswutils.c:866-885); the entry
-            // points are the previous layer's W, all unexpanded again
             // (a resumed batch of a scan keeps its visited set; its entry points are in it and were counted when they
             // were scored: initVisited == false, src/hnswutils.c:867-874)
-            if (!SCAN || !resumed) {
-                for (int w = tid; w < words; w += kHnswThreads) bitmap[w] = 0u;
-                __syncthreads();
-                {
-                    const int cur = sc[4], wn = sc[1];
-                    for (int j = tid; j < wn; j += kHnswThreads) {
-                        const uint32_t id = wi[cur * ef + j] & ~kExpanded;
-                        wi[cur * ef + j] = id;
-                        atomicOr(&bitmap[id >> 5], 1u << (id & 31));
-                    }
-                }
-            }
-            if (tid == 0) sc[5] = sc[6] = 0;
+            if (!SCAN || !resumed) reset_visited();
+            if (tid == 0) sc.tn = sc.tread = 0;
             __syncthreads();
-            if (lc == 0 && (!SCAN || !resumed)) scored += sc[1];  // its entry points count too (src/hnswutils.c:872-873)
+            if (lc == 0 && (!SCAN || !resumed)) scored += sc.wn;  // its entry points count too (src/hnswutils.c:872-873)
 
             for (;;) {
-                // ---- wavefront 0: next candidate and its unvisited neighbours, in tuple order
-                if (wave == 0) {
-                    const int cur = sc[4], wn = sc[1];
-                    int found = -1;
-                    for (int base = 0; base < wn && found < 0; base += kWave) {
-                        const int j = base + lane;
-                        const bool open = j < wn && !(wi[cur * ef + j] & kExpanded);
-                        const unsigned long long bal = __ballot(open);
-                        if (bal) found = base + __ffsll((long long)bal) - 1;
-                    }
-                    int nb = 0;
-                    int cand = -1;
-                    if (found >= 0) {
-                        cand = (int)wi[cur * ef + found];
-                        if (lane == 0) wi[cur * ef + found] = (uint32_t)cand | kExpanded;
-                    } else if (sc[6] < sc[5]) {  // W exhausted: an evicted candidate tied with its furthest
-                        cand = (int)ti[sc[6]];
-                        if (lane == 0) sc[6] = sc[6] + 1;
-                    }
-                    if (cand >= 0) {
-                        const uint32_t c = (uint32_t)cand;
-                        // neighbour tuple slice of layer lc (src/hnswutils.c:786)
-                        const int64_t start = g.nbr_start[c] + (int64_t)(g.levels[c] - lc) * g.m;
-                        for (int base = 0; base < lm; base += kWave) {
-                            const int j = base + lane;
-                            const int32_t e = j < lm ? g.nbr[start + j] : -1;
-                            bool fresh = false;
-                            if (e >= 0) {
-                                const uint32_t bit = 1u << (e & 31);
-                                fresh = !(atomicOr(&bitmap[e >> 5], bit) & bit);
-                            }
-                            const unsigned long long bal = __ballot(fresh);
-                            if (fresh) bi[nb + __popcll(bal & ((1ull << lane) - 1ull))] = e;
-                            nb += __popcll(bal);
-                        }
-                    }
-                    // "make robust to issues" (src/hnswutils.c:947-949): an element below this layer
-                    // is scored and stays visited but is never admitted; only upper layers can see one
-                    if (lane == 0) {
-                        sc[2] = nb;
-                        sc[3] = cand;
-                    }
-                }
+                if (wave == 0) next_candidate(lc, lm);
                 __syncthreads();
-                const int nb = sc[2];
-                if (sc[3] < 0) break;  // every entry of W expanded: the reference's C is exhausted or too far
+                const int nb = sc.nb;
+                if (sc.cand < 0) break;  // every entry of W expanded: the reference's C is exhausted or too far
                 if (nb == 0) {
                     __syncthreads();
                     continue;
                 }
                 if (lc == 0) scored += nb;  // so->tuples: only the layer-0 search counts (src/hnswscan.c:52-55)
-
-                // ---- everyone: score the batch
                 score_batch(nb);
                 __syncthreads();
-
-                // ---- wavefront 0: stable merge of the batch into W, truncated to ef_l
-                if (wave == 0) {
-                    const int cur = sc[4], nxt = cur ^ 1, wn = sc[1];
-                    const uint32_t *ck = wk + cur * ef, *ci = wi + cur * ef;
-                    uint32_t *nk = wk + nxt * ef, *ni = wi + nxt * ef;
-                    int nbv = nb;
-                    if (lc > 0) {  // drop batch entries that do not reach this layer, keeping the order
-                        int kept = 0;
-                        for (int base = 0; base < nb; base += kWave) {
-                            const int i = base + lane;
-                            const bool keep = i < nb && g.levels[bi[i < nb ? i : 0]] >= lc;
-                            const uint32_t key = i < nb ? bk[i] : 0u;
-                            const int32_t id = i < nb ? bi[i] : 0;
-                            const unsigned long long bal = __ballot(keep);
-                            const int at = kept + __popcll(bal & ((1ull << lane) - 1ull));
-                            // in-place compaction is safe: a chunk only writes at or below its own reads
-                            if (keep) {
-                                bk[at] = key;
-                                bi[at] = id;
-                            }
-                            kept += __popcll(bal);
-                        }
-                        nbv = kept;
-                    }
-                    const int nb = nbv;
-                    const int wn_new = wn + nb < ef_l ? wn + nb : ef_l;
-                    // old entries move up by the number of batch entries strictly nearer
-                    for (int j = lane; j < wn; j += kWave) {
-                        const uint32_t key = ck[j];
-                        int s = 0;
-                        for (int b = 0; b < nb; b++) s += bk[b] < key;
-                        if (j + s < ef_l) {
-                            nk[j + s] = key;
-                            ni[j + s] = ci[j];
-                        }
-                    }
-                    // batch entries go after every old entry that is not farther and after the
-                    // batch entries that are nearer or equal-and-earlier
-                    for (int i = lane; i < nb; i += kWave) {
-                        const uint32_t key = bk[i];
-                        int lo = 0, hi = wn;  // first old entry with key > this one
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            if (ck[mid] <= key)
-                                lo = mid + 1;
-                            else
-                                hi = mid;
-                        }
-                        int s = lo;
-                        for (int b = 0; b < nb; b++) s += (bk[b] < key) || (bk[b] == key && b < i);
-                        if (s < ef_l) {
-                            nk[s] = key;
-                            ni[s] = (uint32_t)bi[i];
-                        }
-                    }
-                    // The tie list.  With W full, its furthest key K is nk[ef_l - 1].  T keeps the
-                    // unexpanded candidates that were pushed out of W at exactly K: old entries, and
-                    // batch entries that had been admitted when their turn came (fewer than ef_l
-                    // entries not farther among W and the batch entries before them).  Entries of an
-                    // older T stay only if K has not moved.
-                    if (wn_new == ef_l && wn + nb > ef_l) {
-                        const uint32_t K = nk[ef_l - 1];
-                        int tn = sc[5];
-                        if (tn > 0 && (uint32_t)sc[7] != K) tn = 0;
-                        const int t0 = tn > 0 ? sc[6] : 0;
-                        for (int base = 0; base < wn; base += kWave) {
-                            const int j = base + lane;
-                            bool tie = false;
-                            uint32_t id = 0;
-                            if (j < wn && ck[j] == K && !(ci[j] & kExpanded)) {
-                                int sft = 0;
-                                for (int b = 0; b < nb; b++) sft += bk[b] < K;
-                                tie = j + sft >= ef_l;
-                                id = ci[j];
-                            }
-                            const unsigned long long bal = __ballot(tie);
-                            const int at = tn + __popcll(bal & ((1ull << lane) - 1ull));
-                            if (tie && at < ef) ti[at] = id;  // (at < ef always: the guard only keeps a write inside T)
-                            tn += __popcll(bal);
-                        }
-                        for (int base = 0; base < nb; base += kWave) {
-                            const int i = base + lane;
-                            bool tie = false;
-                            if (i < nb && bk[i] == K) {
-                                int lo = 0, hi = wn;
-                                while (lo < hi) {
-                                    const int mid = (lo + hi) >> 1;
-                                    if (ck[mid] <= K)
-                                        lo = mid + 1;
-                                    else
-                                        hi = mid;
-                                }
-                                int before = lo, pos = lo;
-                                for (int b = 0; b < nb; b++) {
-                                    before += b < i && bk[b] <= K;
-                                    pos += (bk[b] < K) || (bk[b] == K && b < i);
-                                }
-                                tie = before < ef_l && pos >= ef_l;  // admitted in its turn, pushed out later
-                            }
-                            const unsigned long long bal = __ballot(tie);
-                            const int at = tn + __popcll(bal & ((1ull << lane) - 1ull));
-                            if (tie && at < ef) ti[at] = (uint32_t)bi[i];  // (as above: never past T)
-                            tn += __popcll(bal);
-                        }
-                        if (lane == 0) {
-                            sc[5] = tn < ef ? tn : ef;  // (tn < ef always: nothing is truncated)
-                            sc[6] = t0;
-                            sc[7] = (int)K;
-                        }
-                    }
-                    // A scan keeps what the merge leaves past position ef (`discarded`, src/hnswutils.c:936-946, :967-973;
-                    // layer 0 only, src/hnswscan.c:55): the old entries pushed out, in W's order, then the batch entries
-                    // that did not fit, in batch order -- whether or not they also went to T.  Never written past the
-                    // pool: the count goes on, and the batch ends flagged.
-                    if constexpr (SCAN) {
-                        if (lc == 0 && wn + nb > ef_l) {
-                            uint2 *pool = ss.pool + (size_t)qi * ss.cap;
-                            int pn = sc[8];
-                            // (an old entry moves up by at most nb: only W's last nb entries can leave)
-                            for (int base = ef_l > nb ? ef_l - nb : 0; base < wn; base += kWave) {
-                                const int j = base + lane;
-                                bool out = false;
-                                uint2 e = {0u, 0u};
-                                if (j < wn) {
-                                    e.x = ck[j];
-                                    e.y = ci[j] & ~kExpanded;
-                                    int s = 0;
-                                    for (int b = 0; b < nb; b++) s += bk[b] < e.x;
-                                    out = j + s >= ef_l;
-                                }
-                                const unsigned long long bal = __ballot(out);
-                                const int at = pn + __popcll(bal & ((1ull << lane) - 1ull));
-                                if (out && at < ss.cap) pool[at] = e;
-                                pn += __popcll(bal);
-                            }
-                            for (int base = 0; base < nb; base += kWave) {
-                                const int i = base + lane;
-                                bool out = false;
-                                uint2 e = {0u, 0u};
-                                if (i < nb) {
-                                    e.x = bk[i];
-                                    e.y = (uint32_t)bi[i];
-                                    int lo = 0, hi = wn;  // first old entry with key > this one
-                                    while (lo < hi) {
-                                        const int mid = (lo + hi) >> 1;
-                                        if (ck[mid] <= e.x)
-                                            lo = mid + 1;
-                                        else
-                                            hi = mid;
-                                    }
-                                    int s = lo;
-                                    for (int b = 0; b < nb; b++) s += (bk[b] < e.x) || (bk[b] == e.x && b < i);
-                                    out = s >= ef_l;
-                                }
-                                const unsigned long long bal = __ballot(out);
-                                const int at = pn + __popcll(bal & ((1ull << lane) - 1ull));
-                                if (out && at < ss.cap) pool[at] = e;
-                                pn += __popcll(bal);
-                            }
-                            if (lane == 0) sc[8] = pn;
-                        }
-                    }
-                    if (lane == 0) {
-                        sc[1] = wn_new;
-                        sc[4] = nxt;
-                    }
-                }
+                if (wave == 0) merge_batch(qi, lc, ef_l, nb);
                 __syncthreads();
             }
             __syncthreads();
-            if (run.lw_ids && lc <= qlevel && lc < run.lcap) {  // this layer's W: the candidates SelectNeighbors sees
-                const int cur = sc[4], wn = sc[1];
-                const size_t o = ((size_t)qi * run.lcap + lc) * ef;
-                for (int j = tid; j < wn; j += kHnswThreads) {
-                    run.lw_ids[o + j] = (int32_t)(wi[cur * ef + j] & ~kExpanded);
-                    if constexpr (!kJaccard) run.lw_dist[o + j] = key_to_float(wk[cur * ef + j]);
-                }
-                // a Jaccard build: W is ordered by the key (the float8's order, what HnswSearchLayer leaves), the list's
-                // distances are the (float) of the float8 (HnswCandidate.distance, src/hnswutils.c:1336), which the key
-                // does not carry -- W meets the query once more.  Distinct keys may give equal floats; the order stays.
-                jaccard_out(wi + cur * ef, wn, run.lw_dist + o);
-                if (tid == 0) run.lw_cnt[(size_t)qi * run.lcap + lc] = wn;
-            }
+            if (run.lw_ids && lc <= qlevel && lc < run.lcap) hand_out_w(qi, lc);
         }
 
-        // nearest first (src/hnswscan.c:293-311)
-        if (out_elem) {
-            const int cur = sc[4], wn = sc[1];
-            for (int j = tid; j < k; j += kHnswThreads) {
-                const bool have = j < wn;
-                out_elem[(size_t)qi * k + j] = have ? (int64_t)(wi[cur * ef + j] & ~kExpanded) : -1;
-                if constexpr (kJaccard) {
-                    if (!have) out_dist[(size_t)qi * k + j] = __uint_as_float(0x7f800000u);
-                } else
-                    out_dist[(size_t)qi * k + j] = have ? key_to_float(wk[cur * ef + j]) : __uint_as_float(0x7f800000u);
-            }
-            jaccard_out(wi + cur * ef, wn < k ? wn : k, out_dist + (size_t)qi * k);
-        }
+        write_results(qi, wi + sc.cur * ef, wk + sc.cur * ef, sc.wn);
         if (tid == 0 && out_scored) out_scored[qi] = scored;
         if constexpr (SCAN) {
             if (tid == 0) {
-                const int pn = sc[8];
+                const int pn = sc.pool_n;
                 const bool over = pn > ss.cap;
-                ss.out_count[qi] = sc[1];
+                ss.out_count[qi] = sc.wn;
                 if (ss.out_left) ss.out_left[qi] = over ? ss.cap : pn;
                 ss.qs[qi] = {scored, over ? ss.cap : pn, kScanStarted | (over ? kScanOverflow : 0)};
                 if (over) atomicCAS(ss.overflow, 0, qi + 1);
@@ -837,12 +829,11 @@ int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *
     constexpr bool kScan = std::is_same_v<Last, HnswScanDev>;
     size_t query_bytes = (size_t)g.nvec * sizeof(Raw16);
     if constexpr (kSparse) query_bytes = sparse_query_bytes(sp.q_cap, sp.bm_words);
-    const size_t lds = query_bytes + (size_t)run.ef * 16 + (size_t)g.m * 16 + (size_t)run.ef * 4 + 64 +
-                       (kScan ? kScanLdsWords * sizeof(uint32_t) : 0);
-    if (lds > 150 * 1024) {
+    const size_t lds = HnswLds(query_bytes, run.ef, g.m, kScan).total;  // the layout the kernel carves
+    if (lds > kHnswLdsLimit) {
         if constexpr (kSparse)
             PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d / a query of %d stored elements need %zu bytes of LDS (limit %d)",
-                     run.ef, g.m, sp.q_cap, lds, 150 * 1024);
+                     run.ef, g.m, sp.q_cap, lds, (int)kHnswLdsLimit);
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
     }
     auto kern = hnsw_search_kernel<T, METRIC, kScan>;
