@@ -840,7 +840,7 @@ int			pgv_hnsw_upload_jaccard(pgv_ctx * ctx, int nbits, const void *elements, in
  * the floats, `<=` at :1052 included.
  * A view (pgv_hnsw_share) inherits the property: the host build runs on views.  An importer of its export does NOT: the
  * handle's wire format has no field for it and importers do not build -- there the build-side entries are PGV_ERR_ARG
- * as on any bit mirror.  Sparse mirrors keep rejecting.
+ * as on any bit mirror.  A sparse mirror is built on through pgv_hnsw_upload_sparse_buildable, below.
  * pgv_hnsw_buildable_bits: nbits of a mirror (or view) uploaded here, 0 for every other mirror and for NULL.
  * pgv_host_hnsw_build_bits (pgv_host.h) is the build; tools/bench_bit_hnsw_build.py measures it.
  */
@@ -869,15 +869,44 @@ int			pgv_hnsw_buildable_bits(const pgv_hnsw * h);
  * pgv_hnsw_share (a view has its own stream, scratch and visited bitmaps; the element CSR stays the owner's) work as on
  * any mirror, and pgv_hnsw_score_pairs scores element a[i] against element b[i] (b as the query).  These return
  * PGV_ERR_ARG before any launch: pgv_hnsw_search and pgv_hnsw_score (they take dense queries: use the _sparse twins),
- * pgv_hnsw_export (the handle has no fields for a second allocation; nothing can be imported), every pgv_hnsw_build_* and
- * pgv_hnsw_link_* entry and pgv_hnsw_score_groups (sparse graphs are not built here).  The _sparse
- * entries on any other mirror are PGV_ERR_ARG too.
- * Not served: a device-side sparsevec_l2_normalize, the build, the ext/ glue (ext/ returns every sparsevec opclass to
+ * pgv_hnsw_export (the handle has no fields for a second allocation; nothing can be imported), pgv_hnsw_scan_begin, and
+ * on a mirror of THIS entry every pgv_hnsw_build_* and pgv_hnsw_link_* entry and pgv_hnsw_score_groups (a sparse graph is
+ * built on a mirror of pgv_hnsw_upload_sparse_buildable below).  The _sparse entries on any other mirror are
+ * PGV_ERR_ARG too.
+ * Not served: a device-side sparsevec_l2_normalize, the ext/ glue (ext/ returns every sparsevec opclass to
  * the CPU path); bench.py does not measure these entries, tools/bench_sparse_hnsw.py does.
  */
 int			pgv_hnsw_upload_sparse(pgv_ctx * ctx, pgv_metric metric, int dim,
 								   const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
 								   const void *payload, int payload_bytes, pgv_hnsw * *out);
+/*
+ * A sparse mirror to BUILD on: `CREATE INDEX ... USING hnsw (... sparsevec_l2_ops | _ip_ops | _cosine_ops | _l1_ops)`.
+ * Arguments, layout, limits and errors are pgv_hnsw_upload_sparse's (an element of more than 1000 stored elements is
+ * PGV_ERR_DIMS with the reference's message).  The mirror behaves in every entry the plain sparse mirror serves exactly
+ * as that one does (search_sparse, score_sparse, score_pairs, set / update_graph, payload, share), and IN ADDITION
+ * pgv_hnsw_build_search, _build_neighbors, _build_search_keep, _build_select_kept, pgv_hnsw_link_begin / _prepare /
+ * _apply / _end and pgv_hnsw_score_groups serve it with the semantics they have on a dense mirror.  Export and iterative
+ * scans stay refused.  A view (pgv_hnsw_share) inherits the property: the host build runs on views.
+ *
+ * WHICH SIDE IS THE QUERY.  A pair's value is an fp32 sum whose order of additions depends on which vector is the row
+ * and which the query (the row's terms first, then the query's unmatched ones), so on float data swapping the two can
+ * change the last bit -- dense and bit rows have no such asymmetry, and the reference's HnswGetDistance is symmetric.
+ * The build compares and caches distances of one pair that reach it by different routes (a search's candidate list, the
+ * pair triangles of a selection, the replays of the lists a batch links into, the host forms), so on a buildable sparse
+ * mirror the BUILD-SIDE value of the pair {a, b} of element slots is always
+ *     row = the element in the smaller slot, query = the element in the larger slot,
+ * i.e. pgv_hnsw_score_pairs(a = min, b = max) bit for bit.  pgv_hnsw_score_groups and every triangle the build-side
+ * entries score follow it (with PGV_HNSW_PAIRS_GATHER=1 too).  pgv_hnsw_score_pairs itself keeps "b is the query",
+ * whatever the slots.  pgv_hnsw_build_search scores with the inserted element as the query, as every walk does; see there.
+ * pgv_hnsw_buildable_sparse: dim of a mirror (or view) uploaded here, 0 for every other mirror and for NULL.
+ * pgv_host_hnsw_build_sparse (pgv_host.h) is the build; tools/bench_sparse_hnsw_build.py measures it.
+ */
+int			pgv_hnsw_upload_sparse_buildable(pgv_ctx * ctx, pgv_metric metric, int dim,
+											 const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+											 const void *payload, int payload_bytes, pgv_hnsw * *out);
+int			pgv_hnsw_buildable_sparse(const pgv_hnsw * h);
+/* the element slots of a mirror of any kind or of a view (-1: NULL): what a host build checks its rows against */
+int64_t		pgv_hnsw_elements(const pgv_hnsw * h);
 /*
  * pgv_hnsw_score over a sparse mirror (HnswSearchLayer's candidate scoring, src/hnswutils.c:908-934, with the sparsevec
  * FUNCTION 1): pair i scores element slot[i] against query query_of[i] (NULL: query 0) of the nq queries in CSR.  The
@@ -1025,6 +1054,12 @@ void		pgv_hnsw_scan_end(pgv_hnsw_scan * s);
  * searched layer's W -- the candidate list SelectNeighbors works on -- nearest first.
  *   elements [nq], insert_levels [nq]
  *   out_ids / out_dist [nq x layer_cap x ef_construction], out_count [nq x layer_cap] (0 = layer not searched)
+ * On a buildable SPARSE mirror the search scores with the inserted element as the query, as every walk does:
+ * out_dist = pgv_hnsw_score_pairs(candidate, element).  pgv_host_hnsw_build_sparse inserts in slot order and a batch does
+ * not see itself, so every candidate sits in a smaller slot than the element and these are the build-side values of the
+ * orientation rule (pgv_hnsw_upload_sparse_buildable: the smaller slot is the row).  A direct caller who inserts out of
+ * slot order gets (row = candidate, query = element) all the same, which for a candidate in a LARGER slot may differ in
+ * the last bit from what pgv_hnsw_score_groups gives the pair.
  */
 int			pgv_hnsw_build_search(pgv_hnsw * h, const int32_t *elements, const int32_t *insert_levels, int nq,
 								  int ef_construction, int layer_cap,

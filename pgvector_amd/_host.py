@@ -56,6 +56,7 @@ def _load():
     P, I, I64 = C.c_void_p, C.c_int, C.c_int64
     lib.pgv_host_hnsw_build.argtypes = [P, I, I, P, I64, I, I, P, I, C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_build_bits.argtypes = [P, I, P, I64, I, I, P, I, C.POINTER(HnswBuilt)]
+    lib.pgv_host_hnsw_build_sparse.argtypes = [P, I, P, P, P, I64, I, I, P, I, C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_built_free.argtypes = [C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_built_free.restype = None
     lib.pgv_host_hnsw_write_index.argtypes = [C.POINTER(Rel), I, I, I, I, I64, P, P, P, P, P, P, C.c_int32]
@@ -135,12 +136,26 @@ def hnsw_search(mirror, graph, queries, ef_search, k):
 _NP = {0: np.float32, 1: np.float16}
 
 
-def hnsw_build(mirror, rows, m, ef_construction, rng=None, max_batch=1024):
+def hnsw_build(mirror, rows, m, ef_construction, rng=None, max_batch=1024, rows_csr=None, dim=None):
     """pgv_host_hnsw_build: mirror = api.Hnsw holding exactly `rows`; returns a dict with levels,
     nbr_start, nbr, entry, dup_of (numpy copies) and the counters.  A bit mirror (api.BitHnsw / api.JaccardHnsw with
-    buildable=True) takes its packed rows [n x (nbits + 7) // 8] uint8: pgv_host_hnsw_build_bits."""
+    buildable=True) takes its packed rows [n x (nbits + 7) // 8] uint8: pgv_host_hnsw_build_bits.  A sparse mirror
+    (api.SparseHnsw with buildable=True) takes rows=None and rows_csr = (ptr [n + 1], idx, val), the rows it was uploaded
+    from: pgv_host_hnsw_build_sparse (dim: the mirror's, unless given)."""
     b = HnswBuilt()
-    if getattr(mirror, "nbits", None):
+    if rows_csr is not None or getattr(mirror, "sparse", False):
+        if rows_csr is None or rows is not None:
+            raise _lib.PgvError(_lib.PGV_ERR_ARG, "hnsw_build: a sparse mirror takes rows=None and rows_csr = (ptr, idx, val)")
+        ptr = np.ascontiguousarray(rows_csr[0], dtype=np.int64)
+        idx = np.ascontiguousarray(rows_csr[1], dtype=np.int32)
+        val = np.ascontiguousarray(rows_csr[2], dtype=np.float32)
+        if ptr.ndim != 1 or ptr.size < 1 or idx.size != val.size or idx.size < int(ptr[-1]):
+            raise _lib.PgvError(_lib.PGV_ERR_ARG, "hnsw_build: rows_csr = (ptr [n + 1], idx [ptr[n]], val [ptr[n]])")
+        host_check(lib.pgv_host_hnsw_build_sparse(mirror.h, int(mirror.dim if dim is None else dim), C.c_void_p(ptr.ctypes.data),
+                                                  C.c_void_p(idx.ctypes.data), C.c_void_p(val.ctypes.data), ptr.size - 1, m,
+                                                  ef_construction, C.byref(rng) if rng is not None else None, max_batch,
+                                                  C.byref(b)))
+    elif getattr(mirror, "nbits", None):
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
         if rows.ndim != 2 or rows.shape[1] != (mirror.nbits + 7) // 8:
             raise _lib.PgvError(_lib.PGV_ERR_ARG, "hnsw_build: a bit mirror takes rows [n x (nbits + 7) // 8] uint8")

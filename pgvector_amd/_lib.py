@@ -53,6 +53,7 @@ SYMBOLS = [
     "pgv_hnsw_scan_begin", "pgv_hnsw_scan_next", "pgv_hnsw_scan_drain", "pgv_hnsw_scan_end",
     "pgv_hnsw_upload_jaccard",
     "pgv_hnsw_upload_bits_buildable", "pgv_hnsw_buildable_bits",
+    "pgv_hnsw_upload_sparse_buildable", "pgv_hnsw_buildable_sparse", "pgv_hnsw_elements",
 ]
 
 
@@ -202,6 +203,10 @@ def _load():
     lib.pgv_hnsw_score_groups.argtypes = [P, P, P, P, P, I, I64, I64, P]
     lib.pgv_hnsw_update_graph.argtypes = [P, C.c_int32, P, I, P, P]
     lib.pgv_hnsw_upload_sparse.argtypes = [P, I, I, P, P, P, I64, P, I, C.POINTER(P)]
+    lib.pgv_hnsw_upload_sparse_buildable.argtypes = [P, I, I, P, P, P, I64, P, I, C.POINTER(P)]
+    lib.pgv_hnsw_buildable_sparse.argtypes = [P]
+    lib.pgv_hnsw_elements.argtypes = [P]
+    lib.pgv_hnsw_elements.restype = I64
     lib.pgv_hnsw_score_sparse.argtypes = [P, P, P, P, I, P, P, I64, P]
     lib.pgv_hnsw_search_sparse.argtypes = [P, P, P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_scan_begin.argtypes = [P, P, I, I, I64, C.POINTER(P)]

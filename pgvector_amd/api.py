@@ -1086,10 +1086,15 @@ class SparseHnsw(Hnsw):
     _l1_ops)` (pgv_hnsw_upload_sparse): rows_csr = (ptr [n + 1], idx, val) as sparse_topk takes them, at most 1000 stored
     elements per element; metric PGV_L2SQ / PGV_NEG_IP / PGV_L1 (cosine: PGV_NEG_IP over normalised vectors).
     set_graph, update_graph, get_payload and close are Hnsw's; search, score and score_pairs take CSR queries / element
-    slots and return sparse_distance_batch's values.  No export: the mirror is not shared across processes."""
+    slots and return sparse_distance_batch's values.  No export: the mirror is not shared across processes.
+    buildable=True uploads through pgv_hnsw_upload_sparse_buildable: the same mirror, which the build-side entries serve as
+    well (_host.hnsw_build(mirror, None, m, ef_construction, rows_csr=...) builds its graph); views inherit it."""
 
-    def __init__(self, ctx, metric, dim, rows_csr, payload=None):
+    sparse = True
+
+    def __init__(self, ctx, metric, dim, rows_csr, payload=None, buildable=False):
         self.ctx, self.metric, self.dtype, self.dim = ctx, metric, None, int(dim)
+        self.buildable = bool(buildable)
         r_ptr, r_idx, r_val = _csr(rows_csr)
         n = int(r_ptr.shape[0]) - 1
         h = C.c_void_p()
@@ -1097,8 +1102,9 @@ class SparseHnsw(Hnsw):
         if payload is not None:
             payload = np.ascontiguousarray(payload, dtype=np.uint32)
             self.payload_words = int(payload.shape[1])
-        check(lib.pgv_hnsw_upload_sparse(ctx.h, int(metric), int(dim), ptr(r_ptr), ptr(r_idx), ptr(r_val), n, ptr(payload),
-                                         4 * self.payload_words, C.byref(h)))
+        upload = lib.pgv_hnsw_upload_sparse_buildable if buildable else lib.pgv_hnsw_upload_sparse
+        check(upload(ctx.h, int(metric), int(dim), ptr(r_ptr), ptr(r_idx), ptr(r_val), n, ptr(payload), 4 * self.payload_words,
+                     C.byref(h)))
         self.h = h
         ctx._adopt(self)
 
@@ -1107,6 +1113,7 @@ class SparseHnsw(Hnsw):
         h = C.c_void_p()
         check(lib.pgv_hnsw_share(self.h, ctx.h, C.byref(h)))
         v.ctx, v.metric, v.dtype, v.dim, v.h = ctx, self.metric, None, self.dim, h
+        v.buildable = getattr(self, "buildable", False)
         v.payload_words = self.payload_words
         v._owner = self   # keeps the owner alive
         ctx._adopt(v)

@@ -94,7 +94,7 @@ struct HnswRun {
 // row while it searches the current one (PGV_HNSW_SPARSE_PREFETCH, for A/B runs)
 struct HnswSparse {
     const int64_t *row_ptr;  // [n + 1]
-    const int64_t *q_ptr;
+    const int64_t *q_ptr;    // the queries in CSR; NULL with run.qids (the build: query i is element qids[i], read at row_ptr)
     const int32_t *q_idx;
     const float *q_val;
     int q_cap, bm_words, prefetch;
@@ -294,7 +294,9 @@ __device__ __forceinline__ void scan_entry_step(uint2 *__restrict__ pool, int pn
 __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSparse &sp, const HnswSparse &) { return sp; }
 __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswScanDev &, const HnswSparse &none) { return none; }
 
-template <typename T, int METRIC, bool SCAN = false>
+// ELEMQ (sparse rows only): the queries are element slots of the mirror, the build's form of a sparse walk.  An
+// instantiation of its own, so that the plain sparse walks compile to what they were
+template <typename T, int METRIC, bool SCAN = false, bool ELEMQ = false>
 __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter,
     std::conditional_t<SCAN, HnswScanDev, HnswSparse> last) {
@@ -488,10 +490,22 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     // the query into LDS (the caller's next barrier publishes it)
     auto stage_query = [&](int qi) __attribute__((always_inline)) {
         if constexpr (kSparse) {
-            const int64_t qb = sp.q_ptr[qi];
-            sqn = (int)(sp.q_ptr[qi + 1] - qb);
             QElem *sq = reinterpret_cast<QElem *>(smem);
-            for (int v = tid; v < sqn; v += kHnswThreads) sq[v] = {sp.q_idx[qb + v], sp.q_val[qb + v]};
+            if constexpr (ELEMQ) {
+                // the build: the query is an element of the mirror, its pairs already side by side at g.rows
+                const int32_t e = run.qids[qi];
+                const int64_t qb = sp.row_ptr[e];
+                sqn = (int)(sp.row_ptr[e + 1] - qb);
+                const QElem *src = reinterpret_cast<const QElem *>(g.rows) + qb;
+                for (int v = tid; v < sqn; v += kHnswThreads) {
+                    const QPair raw = *reinterpret_cast<const QPair *>(src + v);
+                    sq[v] = {raw.x, __int_as_float(raw.y)};
+                }
+            } else {
+                const int64_t qb = sp.q_ptr[qi];
+                sqn = (int)(sp.q_ptr[qi + 1] - qb);
+                for (int v = tid; v < sqn; v += kHnswThreads) sq[v] = {sp.q_idx[qb + v], sp.q_val[qb + v]};
+            }
         } else {
             const char *qrow = run.qids ? g.rows + (size_t)run.qids[qi] * row_bytes : run.queries + (size_t)qi * row_bytes;
             for (int v = tid; v < g.nvec; v += kHnswThreads) lq[v] = load16(qrow + (size_t)v * sizeof(Raw16));
@@ -822,7 +836,7 @@ __global__ __launch_bounds__(256) void hnsw_patch_kernel(int32_t *__restrict__ n
     for (int64_t j = lane; j < len; j += 64) nbr[dst + j] = packed[src + j];
 }
 
-template <typename T, int METRIC, typename Last = HnswSparse>
+template <typename T, int METRIC, typename Last = HnswSparse, bool ELEMQ = false>
 int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *bitmaps, int words, int grid,
                   int *counter, const Last &sp = Last{}) {
     constexpr bool kSparse = std::is_same_v<T, SparseRow>;
@@ -836,7 +850,7 @@ int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *
                      run.ef, g.m, sp.q_cap, lds, (int)kHnswLdsLimit);
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
     }
-    auto kern = hnsw_search_kernel<T, METRIC, kScan>;
+    auto kern = hnsw_search_kernel<T, METRIC, kScan, ELEMQ>;
     PGV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kHnswThreads), lds, ctx->stream, g, run, bitmaps, words, counter, sp);
     PGV_HIP(hipGetLastError());
@@ -1132,9 +1146,18 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
         sp.q_cap = pad4(a.max_q_nnz);
         sp.bm_words = v.metric == PGV_NEG_IP ? 0 : bitmap_words(a.max_q_nnz);
         sp.prefetch = prefetch != 0;
-        // (the queries of a sparse walk are sparse vectors: the build's element-slot queries do not reach here)
-        if (!a.sparse_queries.ptr || a.qids) PGV_FAIL(PGV_ERR_ARG, "hnsw search: a sparse mirror takes sparse queries");
-        if (a.max_q_nnz > kSparseMaxNnz) PGV_FAIL(PGV_ERR_DIMS, "hnsw search: a query of %d stored elements", a.max_q_nnz);
+        // the queries of a sparse walk are sparse vectors, or -- the build, which the entry points let through for a mirror
+        // of pgv_hnsw_upload_sparse_buildable only -- element slots: then max_q_nnz is the mirror's longest element
+        if ((a.sparse_queries.ptr != nullptr) == (a.qids != nullptr))
+            PGV_FAIL(PGV_ERR_ARG, "hnsw search: a sparse mirror takes sparse queries, or a build's element slots");
+        if (a.max_q_nnz > (a.qids ? kSparseHnswMaxNnz : kSparseMaxNnz))
+            PGV_FAIL(PGV_ERR_DIMS, "hnsw search: a query of %d stored elements", a.max_q_nnz);
+        if (a.qids) switch (v.metric) {
+                case PGV_L2SQ: return launch_hnsw_t<SparseRow, 0, HnswSparse, true>(ctx, g, run, bitmaps, words, grid, counter, sp);
+                case PGV_NEG_IP: return launch_hnsw_t<SparseRow, 1, HnswSparse, true>(ctx, g, run, bitmaps, words, grid, counter, sp);
+                case PGV_L1: return launch_hnsw_t<SparseRow, 2, HnswSparse, true>(ctx, g, run, bitmaps, words, grid, counter, sp);
+                default: PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
+            }
         switch (v.metric) {
             case PGV_L2SQ: return launch_hnsw_t<SparseRow, 0>(ctx, g, run, bitmaps, words, grid, counter, sp);
             case PGV_NEG_IP: return launch_hnsw_t<SparseRow, 1>(ctx, g, run, bitmaps, words, grid, counter, sp);

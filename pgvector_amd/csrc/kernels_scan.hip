@@ -490,7 +490,8 @@ int launch_score_gather(pgv_ctx *ctx, const RowsView &v, const void *queries, co
 
 int launch_score_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride,
                         const int32_t *n_arr, const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out) {
-    if (v.sparse()) PGV_FAIL(PGV_ERR_ARG, "score groups: fixed-width rows only");
+    // (sparse rows: one wavefront a pair over CSR rows, kernels_sparse.hip)
+    if (v.sparse()) return launch_sparse_groups(ctx, v, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out);
     return dispatch_rows(v, [&](auto *tp, auto mc) {
         return launch_groups_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(
             ctx, v.geom, v.rows, ids, ids_at, ids_stride, n_arr, from_arr, pair_at, ngroups, out);

@@ -44,10 +44,12 @@
 // a sparse mirror (hnsw_sparsevec_support, HNSW_MAX_NNZ 1000, src/hnswutils.c:1361-1433; kernels_hnsw.hip) scores its
 // batches with it, and so does sparse_pair_kernel below, which serves pgv_hnsw_score_sparse and pgv_hnsw_score_pairs over
 // such a mirror: one wavefront per (element, query) pair, the element row as the walk reads it, the query's elements
-// read from the caches (sparse_pack_kernel has laid them side by side).  DESIGN.md 4.6c.
+// read from the caches (sparse_pack_kernel has laid them side by side).  DESIGN.md 4.6c.  sparse_groups_kernel is the
+// build's group scorer over such a mirror (launch_score_groups dispatches to it): the pairs inside a neighbor list, each
+// with the element of the smaller slot as the row.
 //
-// Not here (include/pgv_hip.h says the same): a device-side sparsevec_l2_normalize, building a graph over sparse
-// elements, ext/ glue; bench.py does not measure any of this (tools/bench_sparse_topk.py and tools/bench_sparse_hnsw.py do).
+// Not here (include/pgv_hip.h says the same): a device-side sparsevec_l2_normalize, ext/ glue; bench.py does not measure
+// any of this (tools/bench_sparse_topk.py, tools/bench_sparse_hnsw.py and tools/bench_sparse_hnsw_build.py do).
 #include "pgv_device.h"
 #include "sparse_pair.h"
 
@@ -176,6 +178,111 @@ __global__ __launch_bounds__(kSpThreads) void sparse_pair_kernel(const int64_t *
     }
 }
 
+// Pair distances inside groups of element slots of a sparse HNSW mirror (the build: CheckElementCloser's distances between
+// the candidates of one neighbor list, src/hnswutils.c:1040-1059) -- score_groups_kernel's interface and output order:
+// group g is the slots ids[at .. at + n), wanted are the pairs (u, v < u) of its locals for u >= from, written u ascending
+// then v from pair_at[g] on.
+// score_element is not symmetric in its last bit on float data (the row's terms are added first, then the query's
+// unmatched ones), and the build compares distances of one pair that reach it by different routes, so a pair has ONE
+// orientation here: the element in the smaller SLOT is the row, the one in the larger slot the query -- what the walk's
+// build form gives a build that inserts in slot order, and launch_sparse_pairs(a = min, b = max) bit for bit (DESIGN.md
+// 4.6g; equal slots, which no list of the build holds, fall to the local order).
+// A work item is (group, member c): the workgroup stages element ids[c] in LDS once, as the query, and its wavefronts take
+// the partners r of c whose pair is wanted and whose slot is smaller, round-robin in r's order; the value goes where
+// (u, v) = (max(c, r), min(c, r)) stands in the output, so every wanted pair is scored exactly once, by the item of its
+// larger slot.  A member without such a partner (the smallest slot of its group; every old member of a list that one
+// newer element joins) is left before anything is staged: every wavefront counts the partners itself, from the same ids,
+// so the four agree without a barrier.  A wavefront requests its next partner's row before it searches the current one,
+// like the walk.  grid: x strides the groups, y a group's members.
+template <int MODE>
+__global__ __launch_bounds__(kSpThreads) void sparse_groups_kernel(
+    const int64_t *__restrict__ r_ptr, const QElem *__restrict__ r_elem, const int32_t *__restrict__ ids,
+    const int64_t *__restrict__ ids_at, int64_t ids_stride, const int32_t *__restrict__ n_arr,
+    const int32_t *__restrict__ from_arr, const int64_t *__restrict__ pair_at, int ngroups, float *__restrict__ out) {
+    __shared__ QElem s_q[kSparseHnswMaxNnz];
+    __shared__ uint32_t s_bm[kSpWaves][bitmap_words(kSparseHnswMaxNnz)];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int64_t p0 = pair_at[g];
+        if (pair_at[g + 1] == p0) continue;
+        const int64_t at = ids_at ? ids_at[g] : (int64_t)g * ids_stride;
+        const int n = n_arr ? n_arr[g] : (int)(ids_at[g + 1] - at);
+        int from = from_arr ? from_arr[g] : 1;
+        if (from < 1) from = 1;
+        if (n <= from) continue;
+        const int32_t *gi = ids + at;
+        const int64_t base = (int64_t)from * (from - 1) / 2;
+        for (int c = blockIdx.y; c < n; c += gridDim.y) {
+            const int32_t ec = gi[c];
+            // a pair is wanted when its larger local is >= from: a member below `from` pairs with the locals from there on
+            const int r0 = c < from ? from : 0;
+            // lane l looks at local rbase + l: is it a partner of c, and which slot does it hold
+            auto partner = [&](int rbase, int32_t &er) {
+                const int r = rbase + lane;
+                er = gi[r < n ? r : n - 1];  // never predicate a load
+                return r < n && r != c && (er < ec || (er == ec && r < c));
+            };
+            int npart = 0;
+            for (int rbase = r0; rbase < n; rbase += kWave) {
+                int32_t er;
+                npart += __popcll(__ballot(partner(rbase, er)));
+            }
+            if (npart == 0) continue;  // (the same count in every wavefront)
+            const int64_t qb = r_ptr[ec];
+            const int qn = (int)(r_ptr[ec + 1] - qb);
+            __syncthreads();  // the item before this one has been scored: its query may go
+            for (int j = tid; j < qn; j += kSpThreads) {
+                const QPair raw = *reinterpret_cast<const QPair *>(r_elem + qb + j);
+                s_q[j] = {raw.x, __int_as_float(raw.y)};
+            }
+            __syncthreads();
+            int seen = 0;
+            for (int rbase = r0; rbase < n; rbase += kWave) {
+                int32_t er;
+                const bool is = partner(rbase, er);
+                const unsigned long long bal = __ballot(is);
+                const int rank = seen + __popcll(bal & ((1ull << lane) - 1ull));
+                seen += __popcll(bal);
+                unsigned long long mb = __ballot(is && (rank & (kSpWaves - 1)) == wave);  // this wavefront's partners
+                if (mb == 0ull) continue;
+                // a partner is a dependent chain slot -> the row's bounds -> the row's pairs: every lane fetches the bounds
+                // of its own local at once
+                const int64_t rbl = r_ptr[er];
+                const int rnl = (int)(r_ptr[er + 1] - rbl);
+                int l = __ffsll(mb) - 1;
+                RegRow cur;
+                load_reg_row(cur, r_elem + __shfl(rbl, l), __shfl(rnl, l), lane);
+                while (mb != 0ull) {
+                    l = __ffsll(mb) - 1;
+                    mb &= mb - 1ull;
+                    const int64_t rb = __shfl(rbl, l);
+                    const int rn = __shfl(rnl, l);
+                    const int ln = mb != 0ull ? __ffsll(mb) - 1 : l;  // (the last trip asks for its own row again)
+                    RegRow nxt;
+                    load_reg_row(nxt, r_elem + __shfl(rbl, ln), __shfl(rnl, ln), lane);
+                    const float v = score_element<MODE>(cur, r_elem + rb, rn, s_q, qn, s_bm[wave], lane);
+                    const int r = rbase + l;
+                    const int u = c > r ? c : r, w = c > r ? r : c;
+                    if (lane == kWave - 1) out[p0 + (int64_t)u * (u - 1) / 2 - base + w] = v;
+                    cur = nxt;
+                }
+            }
+        }
+    }
+}
+
+// (a[i], b[i]) -> (min, max): the slot pairs expand_groups_kernel / hnsw_link_pairs_kernel emit, oriented as
+// sparse_groups_kernel scores them (PGV_HNSW_PAIRS_GATHER=1 over a sparse mirror)
+__global__ __launch_bounds__(256) void sparse_orient_pairs_kernel(int32_t *__restrict__ a, int32_t *__restrict__ b, int64_t npairs) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npairs; i += (int64_t)gridDim.x * 256) {
+        const int32_t x = a[i], y = b[i];
+        if (x > y) {
+            a[i] = y;
+            b[i] = x;
+        }
+    }
+}
+
 }  // namespace
 
 int sparse_tile_nnz() { return kSparseTileNnz; }
@@ -267,6 +374,46 @@ int launch_sparse_pairs(pgv_ctx *ctx, const RowsView &v, const int64_t *q_ptr, c
             break;
         default: PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
     }
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_sparse_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride,
+                         const int32_t *n_arr, const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out) {
+    if (ngroups <= 0) return PGV_OK;
+    if (!v.sparse()) PGV_FAIL(PGV_ERR_ARG, "sparse groups: not a sparse mirror");
+    // a batch of the build brings thousands of groups, a serial build one or two of up to ef_construction members: the
+    // groups fill x, and y spreads a group's members while x alone leaves CUs idle.  An item with nothing to score costs a
+    // pass over its group's ids, so y stays small
+    const int cap = ctx->num_cus * 16;
+    const int gx = ngroups < cap ? ngroups : cap;
+    int gy = (cap + gx - 1) / gx;
+    if (gy > 32) gy = 32;
+    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const QElem *re = static_cast<const QElem *>(v.rows);
+    switch (v.metric) {
+        case PGV_L2SQ:
+            hipLaunchKernelGGL(sparse_groups_kernel<0>, grid, dim3(kSpThreads), 0, ctx->stream, v.ptr, re, ids, ids_at, ids_stride,
+                               n_arr, from_arr, pair_at, ngroups, out);
+            break;
+        case PGV_NEG_IP:
+            hipLaunchKernelGGL(sparse_groups_kernel<1>, grid, dim3(kSpThreads), 0, ctx->stream, v.ptr, re, ids, ids_at, ids_stride,
+                               n_arr, from_arr, pair_at, ngroups, out);
+            break;
+        case PGV_L1:
+            hipLaunchKernelGGL(sparse_groups_kernel<2>, grid, dim3(kSpThreads), 0, ctx->stream, v.ptr, re, ids, ids_at, ids_stride,
+                               n_arr, from_arr, pair_at, ngroups, out);
+            break;
+        default: PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
+    }
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_sparse_orient_pairs(pgv_ctx *ctx, int32_t *a, int32_t *b, int64_t npairs) {
+    if (npairs <= 0) return PGV_OK;
+    const int64_t want = (npairs + 255) / 256, cap = (int64_t)ctx->num_cus * 32;
+    hipLaunchKernelGGL(sparse_orient_pairs_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, ctx->stream, a, b, npairs);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -21,14 +21,14 @@ static size_t hnsw_payload_offset(int64_t n, size_t row_bytes) {
 static bool hnsw_is_bits(const pgv_hnsw *h) { return h->nbits > 0; }
 
 // ... and a sparse mirror (pgv_hnsw_upload_sparse): CSR rows scored by sparse_pair.h; searched and scored through the
-// _sparse entries, not built on either
+// _sparse entries, and built on only where it was uploaded for that (pgv_hnsw_upload_sparse_buildable)
 static bool hnsw_is_sparse(const pgv_hnsw *h) { return h->sparse; }
 
 #define PGV_NO_BUILD(h, who)                                                                                      \
     do {                                                                                                         \
         if ((h) && hnsw_is_bits(h) && !(h)->buildable)                                                           \
             PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits / _jaccard) is searched and scored, not built on", who); \
-        if ((h) && hnsw_is_sparse(h))                                                                            \
+        if ((h) && hnsw_is_sparse(h) && !(h)->buildable)                                                         \
             PGV_FAIL(PGV_ERR_ARG, "%s: a sparse mirror (pgv_hnsw_upload_sparse) is searched and scored, not built on", who); \
     } while (0)
 
@@ -183,6 +183,15 @@ static bool hnsw_pairs_by_gather() {
         v = e && atoi(e) != 0 ? 1 : 0;
     }
     return v != 0;
+}
+
+// The gathered route's pair distances, pair i = (a[i], b[i]) of element slots.  Over sparse rows the pairs are oriented
+// first -- the smaller slot is the row, the larger the query, sparse_groups_kernel's rule -- and scored as
+// pgv_hnsw_score_pairs scores them, the mirror its own query array
+static int hnsw_score_gathered(pgv_ctx *ctx, const RowsView &rows, int32_t *a, int32_t *b, int64_t npairs, float *out) {
+    if (!rows.sparse()) return launch_score_gather(ctx, rows, rows.rows, a, b, npairs, out);
+    PGV_TRY(launch_sparse_orient_pairs(ctx, a, b, npairs));
+    return launch_sparse_pairs(ctx, rows, rows.ptr, rows.rows, a, b, npairs, out);
 }
 
 // Searches on this handle's stream see the mirror's last patch, whichever stream ran it (a device-side wait).
@@ -454,6 +463,7 @@ static int hnsw_search_into(pgv_hnsw *h, const int32_t *e_dev, const int32_t *l_
     a.lw_dist = lw_dist;
     a.lw_cnt = lw_cnt;
     a.lcap = layer_cap;
+    if (hnsw_is_sparse(h)) a.max_q_nnz = h->sparse_max_nnz;  // (a query is an element: the LDS query region holds the longest)
     return hnsw_run_search(h, a);
 }
 
@@ -500,14 +510,14 @@ constexpr int kHnswMaxNnz = 1000;  // HNSW_MAX_NNZ (src/hnsw.h:34)
 // The element rows of an HNSW index over sparsevec (`USING hnsw (... sparsevec_l2_ops / _ip_ops / _cosine_ops / _l1_ops)`,
 // sql/vector.sql:1189-1212; type info hnsw_sparsevec_support, src/hnswutils.c:1361-1433).  One allocation: the rows'
 // (index, value) pairs, row after row, plus one slack pair (a lane past an empty last row reads it) | ptr [n + 1] | payload
-int pgv_hnsw_upload_sparse(pgv_ctx *ctx, pgv_metric metric, int dim, const int64_t *row_ptr, const int32_t *row_idx,
-                           const float *row_val, int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {
-    const char *who = "pgv_hnsw_upload_sparse";
-    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_sparse: ctx/out is NULL");
+static int hnsw_upload_sparse_rows(const char *who, pgv_ctx *ctx, pgv_metric metric, int dim, const int64_t *row_ptr,
+                                   const int32_t *row_idx, const float *row_val, int64_t n, const void *payload,
+                                   int payload_bytes, pgv_hnsw **out) {
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "%s: ctx/out is NULL", who);
     *out = nullptr;
     PGV_TRY(check_metric(metric));
     PGV_TRY(check_sparse_dim(who, dim));
-    if (n < 0 || n > 0x7fffffff || (n > 0 && !row_ptr)) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_upload_sparse: bad n / row_ptr is NULL");
+    if (n < 0 || n > 0x7fffffff || (n > 0 && !row_ptr)) PGV_FAIL(PGV_ERR_ARG, "%s: bad n / row_ptr is NULL", who);
     if (payload_bytes < 0 || payload_bytes > 4096 || (payload_bytes & 3) || (payload_bytes > 0 && n > 0 && !payload))
         PGV_FAIL(PGV_ERR_ARG, "payload: 0..4096 bytes per element in whole words, got %d", payload_bytes);
     PGV_HIP(hipSetDevice(ctx->device));
@@ -516,11 +526,14 @@ int pgv_hnsw_upload_sparse(pgv_ctx *ctx, pgv_metric metric, int dim, const int64
     // (the host copy of a device row_ptr is checked like a host one: the walk's register rows are sized from it)
     PGV_TRY(stage_csr(ctx, who, "elements", dim, n > 0 ? row_ptr : none, row_idx, row_val, n, true, ctx->plan_b, ctx->rows_stage,
                       ctx->idx_stage, &r));
-    for (int64_t v = 0; v < n; v++)
+    int max_nnz = 0;
+    for (int64_t v = 0; v < n; v++) {
         if (r.host_ptr[v + 1] - r.host_ptr[v] > kHnswMaxNnz)
-            PGV_FAIL(PGV_ERR_DIMS, "pgv_hnsw_upload_sparse: element %lld has %lld stored elements: sparsevec cannot have more than %d "
+            PGV_FAIL(PGV_ERR_DIMS, "%s: element %lld has %lld stored elements: sparsevec cannot have more than %d "
                                    "non-zero elements for hnsw index (src/hnswutils.c:1371)",
-                     (long long)v, (long long)(r.host_ptr[v + 1] - r.host_ptr[v]), kHnswMaxNnz);
+                     who, (long long)v, (long long)(r.host_ptr[v + 1] - r.host_ptr[v]), kHnswMaxNnz);
+        max_nnz = std::max(max_nnz, (int)(r.host_ptr[v + 1] - r.host_ptr[v]));
+    }
     const int64_t total = r.host_ptr[n];
     pgv_hnsw *h = new (std::nothrow) pgv_hnsw();
     if (!h) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
@@ -529,6 +542,7 @@ int pgv_hnsw_upload_sparse(pgv_ctx *ctx, pgv_metric metric, int dim, const int64
     h->dtype = PGV_F32;
     h->dim = dim;
     h->sparse = true;
+    h->sparse_max_nnz = max_nnz;
     h->n = n;
     const size_t elem_bytes = (((size_t)total + 1) * 8 + 255) & ~(size_t)255;
     const size_t ptr_bytes = (((size_t)n + 1) * sizeof(int64_t) + 255) & ~(size_t)255;
@@ -559,6 +573,29 @@ int pgv_hnsw_upload_sparse(pgv_ctx *ctx, pgv_metric metric, int dim, const int64
     *out = h;
     return PGV_OK;
 }
+
+int pgv_hnsw_upload_sparse(pgv_ctx *ctx, pgv_metric metric, int dim, const int64_t *row_ptr, const int32_t *row_idx,
+                           const float *row_val, int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {
+    return hnsw_upload_sparse_rows("pgv_hnsw_upload_sparse", ctx, metric, dim, row_ptr, row_idx, row_val, n, payload, payload_bytes,
+                                   out);
+}
+
+// The same rows uploaded to be BUILT on as well (`CREATE INDEX ... USING hnsw (... sparsevec_*_ops)`): everything the entry
+// above gives, and the build-side entries (pgv_hnsw_build_*, pgv_hnsw_link_*, pgv_hnsw_score_groups) serve the mirror and
+// its views.  The build-side value of the pair {a, b} of element slots is score_element(row = the smaller slot, query =
+// the larger one) -- pgv_hnsw_score_pairs(min, max) -- wherever it is computed: score_element's last bit
+// depends on which side is the query, and the build compares values of one pair that reach it by different routes.
+int pgv_hnsw_upload_sparse_buildable(pgv_ctx *ctx, pgv_metric metric, int dim, const int64_t *row_ptr, const int32_t *row_idx,
+                                     const float *row_val, int64_t n, const void *payload, int payload_bytes, pgv_hnsw **out) {
+    PGV_TRY(hnsw_upload_sparse_rows("pgv_hnsw_upload_sparse_buildable", ctx, metric, dim, row_ptr, row_idx, row_val, n, payload,
+                                    payload_bytes, out));
+    (*out)->buildable = true;
+    return PGV_OK;
+}
+
+int pgv_hnsw_buildable_sparse(const pgv_hnsw *h) { return h && hnsw_is_sparse(h) && h->buildable ? h->dim : 0; }
+
+int64_t pgv_hnsw_elements(const pgv_hnsw *h) { return h ? h->n : -1; }
 
 // queries in CSR -> the device, validated like pgv_sparse_topk's; *max_nnz: the longest one's stored elements
 static int hnsw_stage_sparse_queries(pgv_hnsw *h, const char *who, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val,
@@ -697,7 +734,7 @@ static int hnsw_select_from(pgv_hnsw *h, const int32_t *lw_ids, const float *lw_
             PGV_TRY(ctx->km_g.ensure(sizeof(int32_t) * (size_t)npairs));
             PGV_TRY(launch_expand_groups(ctx, lw_ids, nullptr, ef_construction, lw_cnt, nullptr, pair_start, ngroups,
                                          ctx->km_f.as<int32_t>(), ctx->km_g.as<int32_t>()));
-            PGV_TRY(launch_score_gather(ctx, rows, rows.rows, ctx->km_f.as<int32_t>(), ctx->km_g.as<int32_t>(), npairs,
+            PGV_TRY(hnsw_score_gathered(ctx, rows, ctx->km_f.as<int32_t>(), ctx->km_g.as<int32_t>(), npairs,
                                         ctx->dist_mat.as<float>()));
         } else
             PGV_TRY(launch_score_groups(ctx, rows, lw_ids, nullptr, ef_construction, lw_cnt, nullptr, pair_start, ngroups,
@@ -875,7 +912,7 @@ int pgv_hnsw_score_groups(pgv_hnsw *h, const int32_t *ids, const int64_t *ids_st
         PGV_TRY(ctx->plan_d.ensure(sizeof(int32_t) * (size_t)npairs));
         int32_t *a_dev = ctx->idx_stage.as<int32_t>(), *b_dev = ctx->plan_d.as<int32_t>();
         PGV_TRY(launch_expand_groups(ctx, g_ids, g_at, 0, nullptr, g_from, g_pair, ngroups, a_dev, b_dev));
-        PGV_TRY(launch_score_gather(ctx, rows, rows.rows, a_dev, b_dev, npairs, od.as<float>()));
+        PGV_TRY(hnsw_score_gathered(ctx, rows, a_dev, b_dev, npairs, od.as<float>()));
     } else
         PGV_TRY(launch_score_groups(ctx, rows, g_ids, g_at, 0, nullptr, g_from, g_pair, ngroups, od.as<float>()));
     bool need = true;  // the host tables above must have been read before the caller reuses them
@@ -1051,7 +1088,7 @@ int pgv_hnsw_link_prepare(pgv_hnsw *h, const int32_t *elements, const uint8_t *l
                                    gather ? L->pa.as<int32_t>() : nullptr, gather ? L->pb.as<int32_t>() : nullptr));
     if (npairs > 0) {
         if (gather)
-            PGV_TRY(launch_score_gather(ctx, rows, rows.rows, L->pa.as<int32_t>(), L->pb.as<int32_t>(), npairs, L->tri.as<float>()));
+            PGV_TRY(hnsw_score_gathered(ctx, rows, L->pa.as<int32_t>(), L->pb.as<int32_t>(), npairs, L->tri.as<float>()));
         else
             PGV_TRY(launch_score_groups(ctx, rows, L->ids.as<int32_t>(), L->ids_start, 0, nullptr, L->rec_from, L->pair_start, nrec,
                                         L->tri.as<float>()));
@@ -1105,8 +1142,7 @@ int pgv_hnsw_link_apply(pgv_hnsw *h, int32_t entry) {
                 PGV_TRY(launch_hnsw_link_pairs(ctx, G.nbr, L->rec_pos, L->rec_nstart, L->rec_from, L->rec_off, L->d_link_elem,
                                                L->d_link_dist, L->rec_list, L->list_count, nrec, 1, L->ids_start,
                                                L->ids.as<int32_t>(), L->mm_start, L->pa.as<int32_t>(), L->pb.as<int32_t>()));
-                PGV_TRY(launch_score_gather(ctx, rows, rows.rows, L->pa.as<int32_t>(), L->pb.as<int32_t>(), npairs2,
-                                            L->mm.as<float>()));
+                PGV_TRY(hnsw_score_gathered(ctx, rows, L->pa.as<int32_t>(), L->pb.as<int32_t>(), npairs2, L->mm.as<float>()));
             } else if (npairs2 > 0)
                 PGV_TRY(launch_score_groups(ctx, rows, L->ids.as<int32_t>(), L->ids_start, 0, L->rec_nstart, nullptr, L->mm_start,
                                             nrec, L->mm.as<float>()));

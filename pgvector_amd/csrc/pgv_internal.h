@@ -285,14 +285,16 @@ struct HnswElements {
     // nbits bits in geom.nvec 16-byte vectors, scored by popcounts; dtype and dim are unused (dim = nbits), and metric is
     // bit_metric_slot() of the mirror's pgv_bit_metric: 0 (what it always held) bit_hamming_ops, 1 bit_jaccard_ops
     int nbits = 0;
-    // a bit mirror uploaded by pgv_hnsw_upload_bits_buildable: the build-side entries serve it.  A view has it from its
-    // owner; an importer does not (the exported handle has no field for it, and importers do not build)
+    // a bit mirror uploaded by pgv_hnsw_upload_bits_buildable, or a sparse one uploaded by pgv_hnsw_upload_sparse_buildable:
+    // the build-side entries serve it.  A view has it from its owner; an importer does not (the exported handle has no
+    // field for it, and importers do not build)
     bool buildable = false;
     // a mirror of sparsevec elements (pgv_hnsw_upload_sparse): `elements` holds the rows' (index, value) pairs one row
     // after the other (and one slack pair), sparse_ptr [n + 1] where each row starts -- in the same allocation, like the
     // payload; dtype and geom are unused, dim is the vectors' dimension
     bool sparse = false;
     const int64_t *sparse_ptr = nullptr;
+    int sparse_max_nnz = 0;  // the longest element's stored elements (<= HNSW_MAX_NNZ): sizes the LDS query of a build's walk
     int64_t n = 0;
     pgv::RowGeom geom{};
     void *elements = nullptr;  // [n x ld]
@@ -641,6 +643,12 @@ int launch_sparse_pack(pgv_ctx *ctx, const int32_t *idx, const float *val, int64
 // values of launch_sparse_tiles for the same two vectors, bit for bit
 int launch_sparse_pairs(pgv_ctx *ctx, const RowsView &v, const int64_t *q_ptr, const void *q_elem, const int32_t *slot,
                         const int32_t *query_of, int64_t npairs, float *out);
+// launch_score_groups over sparse rows (the same arguments and output order): pair {a, b} of element slots is
+// launch_sparse_pairs' value for (row min(a, b), query max(a, b)), bit for bit -- the build's orientation rule
+int launch_sparse_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, const int64_t *ids_at, int64_t ids_stride,
+                         const int32_t *n_arr, const int32_t *from_arr, const int64_t *pair_at, int ngroups, float *out);
+// (a[i], b[i]) -> (min, max) in place: slot pairs as the rule above takes them (PGV_HNSW_PAIRS_GATHER=1 over sparse rows)
+int launch_sparse_orient_pairs(pgv_ctx *ctx, int32_t *a, int32_t *b, int64_t npairs);
 
 // kernels_hnsw.hip: the whole first batch of an HNSW scan, one workgroup per query
 int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out);
@@ -648,7 +656,8 @@ struct HnswSearchArgs {
     const void *queries = nullptr;     // staged query rows, or
     SparseCsr sparse_queries{nullptr, nullptr, nullptr, 0};  // the staged queries of a walk over sparse rows, and
     int max_q_nnz = 0;                 // ... the longest one's stored elements (the launch's LDS is sized by it), or
-    const int32_t *qids = nullptr;     // element slots used as queries (build)
+    const int32_t *qids = nullptr;     // element slots used as queries (build; over sparse rows max_q_nnz is then the
+                                       // mirror's longest ELEMENT)
     const int32_t *qlevels = nullptr;  // insert level per query (build)
     int nq = 0, ef = 0, k = 0;
     int64_t *out_elem = nullptr;

@@ -18,6 +18,7 @@ template <> struct VecTraits<SparseRow> {
 
 constexpr int kSparseRegChunks = 4;      // a row of up to 4 x 64 stored elements stays in registers
 constexpr int kSparseMaxNnz = 16000;     // SPARSEVEC_MAX_NNZ (src/sparsevec.h)
+constexpr int kSparseHnswMaxNnz = 1000;  // HNSW_MAX_NNZ (src/hnsw.h:34): an ELEMENT of a sparse HNSW mirror at most
 
 __host__ __device__ constexpr int pad4(int x) { return (x + 3) & ~3; }
 __host__ __device__ constexpr int bitmap_words(int nnz) { return pad4((nnz + 31) / 32); }

@@ -1226,21 +1226,55 @@ link_first_element(pgv_hnsw * mirror, elem * el, int32_t e, int m, int with_list
 }
 
 /*
+ * The caller's rows as this side looks at them -- only to tell whether two of them are the same datum: rows of item_bytes
+ * each at `fixed` (dense and bit rows), or, with csr_ptr set, sparse rows in CSR.
+ */
+typedef struct item_rows
+{
+	const void *fixed;
+	size_t		item_bytes;
+	const int64_t *csr_ptr;		/* [n + 1] */
+	const int32_t *csr_idx;
+	const float *csr_val;
+} item_rows;
+
+/*
+ * datumIsEqual as FindDuplicateInMemory sees it (src/hnswbuild.c:330-335): equal bytes.  Two sparsevec datums of one
+ * column are equal bytes when they store the same number of elements, the same index bytes and the same VALUE BYTES
+ * (0.0 and -0.0 differ, a NaN equals itself).
+ */
+static int
+same_item(const item_rows * r, int32_t a, int32_t b)
+{
+	if (r->csr_ptr)
+	{
+		const int64_t ab = r->csr_ptr[a],
+					bb = r->csr_ptr[b];
+		const size_t nnz = (size_t) (r->csr_ptr[a + 1] - ab);
+
+		if ((size_t) (r->csr_ptr[b + 1] - bb) != nnz)
+			return 0;
+		return nnz == 0 || (memcmp(r->csr_idx + ab, r->csr_idx + bb, nnz * sizeof(int32_t)) == 0 &&
+							memcmp(r->csr_val + ab, r->csr_val + bb, nnz * sizeof(float)) == 0);
+	}
+	return memcmp((const char *) r->fixed + (size_t) a * r->item_bytes, (const char *) r->fixed + (size_t) b * r->item_bytes,
+				  r->item_bytes) == 0;
+}
+
+/*
  * FindDuplicateInMemory, src/hnswbuild.c:313-364, for element e (called in heap order) with its layer-0 list, `count`
  * elements `stride` bytes apart: an element's neighbors are ordered by distance, the identical ones first, so the walk
  * stops at the first neighbor that is not byte for byte e's row.  An identical one with room for another heap TID
  * takes e's: returns that element, or -1 when e has to be linked.
  */
 static int32_t
-find_duplicate(elem * el, const void *rows, size_t item_bytes, int32_t e, const int32_t *list, size_t stride, int count)
+find_duplicate(elem * el, const item_rows * rows, int32_t e, const int32_t *list, size_t stride, int count)
 {
-	const char *v = (const char *) rows + (size_t) e * item_bytes;
-
 	for (int i = 0; i < count; i++)
 	{
 		int32_t		ne = *(const int32_t *) ((const char *) list + (size_t) i * stride);
 
-		if (memcmp(v, (const char *) rows + (size_t) ne * item_bytes, item_bytes) != 0)
+		if (!same_item(rows, e, ne))
 			break;
 		if (el[ne].heaptids < HNSW_HEAPTIDS)
 		{
@@ -1269,7 +1303,7 @@ find_duplicate(elem * el, const void *rows, size_t item_bytes, int32_t e, const 
  * reference's serial loop.
  */
 static int
-build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, int m, int ef_construction,
+build_linked_on_device(pgv_hnsw * mirror, const item_rows * rows, int64_t n, int m, int ef_construction,
 					   int max_batch, elem * el, pgv_hnsw_built * out, phase_clock * clk, int32_t *entry_io,
 					   int64_t *linked_io)
 {
@@ -1374,7 +1408,7 @@ build_linked_on_device(pgv_hnsw * mirror, size_t item_bytes, const void *rows, i
 			const size_t g = (size_t) b * p.lcap;	/* its layer-0 list */
 
 			ids[b] = e;
-			out->dup_of[e] = find_duplicate(el, rows, item_bytes, e, a->sel_ids + g * 2 * (size_t) m, sizeof(int32_t), a->sel_cnt[g]);
+			out->dup_of[e] = find_duplicate(el, rows, e, a->sel_ids + g * 2 * (size_t) m, sizeof(int32_t), a->sel_cnt[g]);
 			is_linked[b] = out->dup_of[e] < 0;
 			if (is_linked[b])
 			{
@@ -1472,8 +1506,7 @@ typedef struct
 {
 	/* the build, as pgv_host_hnsw_build was asked for it */
 	pgv_hnsw   *mirror;
-	const void *rows;
-	size_t		item_bytes;
+	const item_rows *rows;
 	int64_t		n;
 	int			m,
 				ef_construction,
@@ -1723,7 +1756,7 @@ store_new_lists(host_link * h, const batch_plan * p)
 		int32_t		e = (int32_t) (i0 + b);
 		const nlist *l0 = &el[e].layers[0];
 
-		h->out->dup_of[e] = find_duplicate(el, h->rows, h->item_bytes, e, &l0->items[0].element, sizeof(cand), l0->length);
+		h->out->dup_of[e] = find_duplicate(el, h->rows, e, &l0->items[0].element, sizeof(cand), l0->length);
 		if (h->out->dup_of[e] >= 0)
 			layers_free(&el[e]);
 	}
@@ -2319,11 +2352,11 @@ patch_graph(host_link * h, const batch_plan * p)
 }
 
 static int
-build_linked_on_host(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, int m, int ef_construction,
+build_linked_on_host(pgv_hnsw * mirror, const item_rows * rows, int64_t n, int m, int ef_construction,
 					 int max_batch, int device_select, elem * el, pgv_hnsw_built * out, phase_clock * clk,
 					 int32_t *entry_io, int64_t *linked_io)
 {
-	host_link	h = {.mirror = mirror, .rows = rows, .item_bytes = item_bytes, .n = n, .m = m, .ef_construction = ef_construction,
+	host_link	h = {.mirror = mirror, .rows = rows, .n = n, .m = m, .ef_construction = ef_construction,
 		.max_batch = max_batch, .el = el, .out = out, .clk = clk, .entry = -1, .nslices = 1};
 	int			rc;
 
@@ -2433,10 +2466,10 @@ start_graph(pgv_hnsw * mirror, int64_t n, int m, const pgv_rng * rng, pgv_hnsw_b
 	return PGV_OK;
 }
 
-/* The build over rows of item_bytes each, whatever they hold: the mirror scores them, this side copies nothing out of
- * them and compares them as bytes (find_duplicate).  pgv_host_hnsw_build and pgv_host_hnsw_build_bits are this. */
+/* The build over rows whatever they hold: the mirror scores them, this side copies nothing out of them and compares them
+ * as bytes (find_duplicate).  pgv_host_hnsw_build, pgv_host_hnsw_build_bits and pgv_host_hnsw_build_sparse are this. */
 static int
-build_items(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, int m, int ef_construction,
+build_items(pgv_hnsw * mirror, const item_rows * rows, int64_t n, int m, int ef_construction,
 			const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
 {
 	/* SelectNeighbors of the new elements' candidate lists: on the device with the searches (the default), or here from
@@ -2452,7 +2485,7 @@ build_items(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, i
 	int64_t		linked = 0;
 	int			rc;
 
-	if (!mirror || !out || (n > 0 && !rows))
+	if (!mirror || !out || (n > 0 && !rows->fixed && !rows->csr_ptr))
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build: mirror/rows/out is NULL");
 	if (m < 2 || m > 100 || ef_construction < 4 || ef_construction > 1000 || ef_construction < 2 * m)
 		return pgv_host_fail(PGV_ERR_ARG, "m must be 2..100, ef_construction 4..1000 and >= 2 * m (src/hnsw.c:114-125)");
@@ -2482,8 +2515,8 @@ build_items(pgv_hnsw * mirror, size_t item_bytes, const void *rows, int64_t n, i
 	}
 	if (rc == PGV_OK && n > 0)
 		rc = device_link
-			? build_linked_on_device(mirror, item_bytes, rows, n, m, ef_construction, max_batch, el, out, &clk, &entry, &linked)
-			: build_linked_on_host(mirror, item_bytes, rows, n, m, ef_construction, max_batch, device_select, el, out, &clk,
+			? build_linked_on_device(mirror, rows, n, m, ef_construction, max_batch, el, out, &clk, &entry, &linked)
+			: build_linked_on_host(mirror, rows, n, m, ef_construction, max_batch, device_select, el, out, &clk,
 								   &entry, &linked);
 	out->entry = entry;
 	out->nelements = linked;
@@ -2499,7 +2532,9 @@ int
 pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *rows, int64_t n, int m,
 					int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
 {
-	return build_items(mirror, (size_t) dim * (dtype == PGV_F32 ? 4 : 2), rows, n, m, ef_construction, rng, max_batch, out);
+	const item_rows r = {.fixed = rows, .item_bytes = (size_t) dim * (dtype == PGV_F32 ? 4 : 2)};
+
+	return build_items(mirror, &r, n, m, ef_construction, rng, max_batch, out);
 }
 
 /* (a weak reference: this file is also linked against stand-ins of the device library that have no bit mirrors, and
@@ -2521,5 +2556,40 @@ pgv_host_hnsw_build_bits(pgv_hnsw * mirror, int nbits, const void *rows, int64_t
 	if (pgv_hnsw_buildable_bits(mirror) != nbits)
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: not a mirror of %d-bit rows uploaded by "
 							 "pgv_hnsw_upload_bits_buildable", nbits);
-	return build_items(mirror, (size_t) (nbits + 7) / 8, rows, n, m, ef_construction, rng, max_batch, out);
+	{
+		const item_rows r = {.fixed = rows, .item_bytes = (size_t) (nbits + 7) / 8};
+
+		return build_items(mirror, &r, n, m, ef_construction, rng, max_batch, out);
+	}
+}
+
+/* (weak for the same reason) */
+#pragma weak pgv_hnsw_buildable_sparse
+#pragma weak pgv_hnsw_elements
+
+/*
+ * ... over sparsevec elements in CSR (`USING hnsw (... sparsevec_*_ops)`): the rows the mirror was uploaded from.  The
+ * batches, the three forms and the pipeline are build_items'; the rows are looked at only by the duplicate check
+ * (same_item).  Elements are inserted in slot order, which is what makes the searches' distances (candidate as the row,
+ * new element as the query) the build-side values of the mirror's orientation rule (pgv_hip.h).
+ */
+int
+pgv_host_hnsw_build_sparse(pgv_hnsw * mirror, int dim, const int64_t *row_ptr, const int32_t *row_idx, const float *row_val,
+						   int64_t n, int m, int ef_construction, const pgv_rng * rng, int max_batch, pgv_hnsw_built * out)
+{
+	if (!mirror || !out || !row_ptr || (n > 0 && row_ptr[n] > row_ptr[0] && (!row_idx || !row_val)))
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: mirror/row_ptr/row_idx/row_val/out is NULL");
+	if (!pgv_hnsw_buildable_sparse || !pgv_hnsw_elements)
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: the device library has no pgv_hnsw_upload_sparse_buildable");
+	if (dim < 1 || pgv_hnsw_buildable_sparse(mirror) != dim)
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: not a mirror of %d-dimensional sparse rows uploaded by "
+							 "pgv_hnsw_upload_sparse_buildable", dim);
+	if (pgv_hnsw_elements(mirror) != n)
+		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: the mirror (pgv_hnsw_upload_sparse_buildable) holds %lld "
+							 "elements, the rows are %lld", (long long) pgv_hnsw_elements(mirror), (long long) n);
+	{
+		const item_rows r = {.csr_ptr = row_ptr, .csr_idx = row_idx, .csr_val = row_val};
+
+		return build_items(mirror, &r, n, m, ef_construction, rng, max_batch, out);
+	}
 }

@@ -110,6 +110,18 @@ int			pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const voi
  */
 int			pgv_host_hnsw_build_bits(pgv_hnsw * mirror, int nbits, const void *rows, int64_t n, int m, int ef_construction,
 									 const pgv_rng * rng, int max_batch, pgv_hnsw_built * out);
+/*
+ * The same build over SPARSEVEC elements (`USING hnsw (... sparsevec_l2_ops / _ip_ops / _cosine_ops / _l1_ops)`): mirror
+ * is pgv_hnsw_upload_sparse_buildable of all n rows, row_ptr [n + 1] / row_idx / row_val the same rows in CSR in host
+ * memory.  One body with pgv_host_hnsw_build -- the batches, the three forms (device link, PGV_HNSW_HOST_LINK=1,
+ * PGV_HNSW_HOST_SELECT=1) and the result are its; elements are inserted in slot order, so every distance the build
+ * compares is the mirror's build-side value of its pair (the element of the smaller slot is the row, pgv_hip.h).  Two
+ * rows are duplicates when they store the same number of elements with equal index bytes and equal value bytes
+ * (datumIsEqual in FindDuplicateInMemory).  Any other mirror, or one of another dim or n, is PGV_ERR_ARG before any launch.
+ */
+int			pgv_host_hnsw_build_sparse(pgv_hnsw * mirror, int dim, const int64_t *row_ptr, const int32_t *row_idx,
+									   const float *row_val, int64_t n, int m, int ef_construction, const pgv_rng * rng,
+									   int max_batch, pgv_hnsw_built * out);
 void		pgv_host_hnsw_built_free(pgv_hnsw_built * built);
 /*
  * Inside a server: a callback pgv_host_hnsw_build polls between batches, on the calling thread (per thread; NULL

@@ -6,7 +6,8 @@ the exact pgv_sparse_topk on the same rows and queries -- for ef_search 40, 100 
 walk's recall@10 against the exact answer (an element counts when its distance is at most the exact 10th distance: ties
 are answers too).  Every vector has one element in each of its strata of the dimensions (sorted and distinct by
 construction); a vector belongs to one of 256 topics that fix most of its indices, so that near neighbours exist.  The
-graph is built on the device by pgv_host_hnsw_build over the fp16 expansion and set on both mirrors (--graph FILE keeps it
+graph is built on the device by pgv_host_hnsw_build over the fp16 expansion (--native-build: by pgv_host_hnsw_build_sparse over a buildable sparse mirror; the
+same graph on these integer rows) and set on both mirrors (--graph FILE keeps it
 between runs: the A/B runs of PGV_HNSW_SPARSE_PREFETCH are two processes).  Times are HIP events on the library's stream;
 the routes are timed in alternating rounds after a warm-up of every shape, median and minimum over --reps rounds.
 Prints one JSON line; --md FILE also writes the table.
@@ -68,6 +69,9 @@ def main():
     ap.add_argument("--ef-construction", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--graph", default=None, help="npz file: the built graph is loaded from it when it exists, else saved to it")
+    ap.add_argument("--native-build", action="store_true",
+                    help="build the graph on the sparse mirror itself (pgv_hnsw_upload_sparse_buildable + "
+                         "pgv_host_hnsw_build_sparse) instead of over the fp16 twin; on these integer rows it is the same graph")
     ap.add_argument("--md", default=None)
     a = ap.parse_args()
     import torch
@@ -84,6 +88,16 @@ def main():
     build_s = None
     if a.graph and os.path.exists(a.graph):
         built = dict(np.load(a.graph))
+    elif a.native_build:
+        builder = api.SparseHnsw(ctx, api.PGV_NEG_IP, a.dim, rows, buildable=True)
+        host_csr = tuple(x.cpu().numpy() for x in rows)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        built = _host.hnsw_build(builder, None, a.m, a.ef_construction, api.make_rng(seed=1), max_batch=1024, rows_csr=host_csr)
+        torch.cuda.synchronize()
+        build_s = time.perf_counter() - t0
+        builder.close()
+        del host_csr
     else:
         host_rows = rows16.cpu().numpy()
         torch.cuda.synchronize()
@@ -102,6 +116,7 @@ def main():
 
     res = {"rows": a.rows, "dim": a.dim, "row_nnz_total": int(rows[0][-1]), "query_nnz_total": int(queries[0][-1]), "m": a.m,
            "ef_construction": a.ef_construction, "queries": a.queries, "k": K, "reps": a.reps, "build_secs": build_s,
+           "graph_built_on": "sparse mirror" if a.native_build else "fp16 twin",
            "sparse_prefetch": os.environ.get("PGV_HNSW_SPARSE_PREFETCH", "1 (default)"),
            "row_bytes_mean": {"sparse": 8.0 * int(rows[0][-1]) / a.rows, "fp16_twin": 2 * a.dim}, "ef": []}
     exact_d, exact_i = api.sparse_topk(ctx, api.PGV_NEG_IP, a.dim, queries, rows, K)  # warm-up, and the exact answer
