@@ -869,10 +869,10 @@ int			pgv_hnsw_buildable_bits(const pgv_hnsw * h);
  * pgv_hnsw_share (a view has its own stream, scratch and visited bitmaps; the element CSR stays the owner's) work as on
  * any mirror, and pgv_hnsw_score_pairs scores element a[i] against element b[i] (b as the query).  These return
  * PGV_ERR_ARG before any launch: pgv_hnsw_search and pgv_hnsw_score (they take dense queries: use the _sparse twins),
- * pgv_hnsw_export (the handle has no fields for a second allocation; nothing can be imported), pgv_hnsw_scan_begin, and
- * on a mirror of THIS entry every pgv_hnsw_build_* and pgv_hnsw_link_* entry and pgv_hnsw_score_groups (a sparse graph is
- * built on a mirror of pgv_hnsw_upload_sparse_buildable below).  The _sparse entries on any other mirror are
- * PGV_ERR_ARG too.
+ * pgv_hnsw_export (the handle has no fields for a second allocation; nothing can be imported), pgv_hnsw_scan_begin (it
+ * takes dense query rows: an iterative scan of a sparse mirror begins with pgv_hnsw_scan_begin_sparse), and on a mirror
+ * of THIS entry every pgv_hnsw_build_* and pgv_hnsw_link_* entry and pgv_hnsw_score_groups (a sparse graph is built on a
+ * mirror of pgv_hnsw_upload_sparse_buildable below).  The _sparse entries on any other mirror are PGV_ERR_ARG too.
  * Not served: a device-side sparsevec_l2_normalize, the ext/ glue (ext/ returns every sparsevec opclass to
  * the CPU path); bench.py does not measure these entries, tools/bench_sparse_hnsw.py does.
  */
@@ -883,10 +883,11 @@ int			pgv_hnsw_upload_sparse(pgv_ctx * ctx, pgv_metric metric, int dim,
  * A sparse mirror to BUILD on: `CREATE INDEX ... USING hnsw (... sparsevec_l2_ops | _ip_ops | _cosine_ops | _l1_ops)`.
  * Arguments, layout, limits and errors are pgv_hnsw_upload_sparse's (an element of more than 1000 stored elements is
  * PGV_ERR_DIMS with the reference's message).  The mirror behaves in every entry the plain sparse mirror serves exactly
- * as that one does (search_sparse, score_sparse, score_pairs, set / update_graph, payload, share), and IN ADDITION
- * pgv_hnsw_build_search, _build_neighbors, _build_search_keep, _build_select_kept, pgv_hnsw_link_begin / _prepare /
- * _apply / _end and pgv_hnsw_score_groups serve it with the semantics they have on a dense mirror.  Export and iterative
- * scans stay refused.  A view (pgv_hnsw_share) inherits the property: the host build runs on views.
+ * as that one does (search_sparse, scan_begin_sparse, score_sparse, score_pairs, set / update_graph, payload, share),
+ * and IN ADDITION pgv_hnsw_build_search, _build_neighbors, _build_search_keep, _build_select_kept, pgv_hnsw_link_begin /
+ * _prepare / _apply / _end and pgv_hnsw_score_groups serve it with the semantics they have on a dense mirror.  Iterative
+ * scans (pgv_hnsw_scan_begin_sparse) work as on the plain sparse mirror; export stays refused.  A view (pgv_hnsw_share)
+ * inherits the property: the host build runs on views.
  *
  * WHICH SIDE IS THE QUERY.  A pair's value is an fp32 sum whose order of additions depends on which vector is the row
  * and which the query (the row's terms first, then the query's unmatched ones), so on float data swapping the two can
@@ -1011,11 +1012,32 @@ typedef struct pgv_hnsw_scan pgv_hnsw_scan;
  *   ef_search    1..1000 (src/hnsw.c:93-94)
  *   discard_cap  pool entries per query; 0 = min(n, 65536).  State per query: 8 * discard_cap + 4 * (n / 32 + 2) + 16
  *                bytes and the query row
- * PGV_ERR_ARG: a sparse mirror (its queries are staged per call: pgv_hnsw_search_sparse), no graph set, ef_search out
- * of range.  PGV_ERR_NOMEM: the state does not fit (the text has the byte count).
+ * PGV_ERR_ARG: a sparse mirror (it takes sparse queries: pgv_hnsw_scan_begin_sparse), no graph set, ef_search out of
+ * range.  PGV_ERR_NOMEM: the state does not fit (the text has the byte count).
  */
 int			pgv_hnsw_scan_begin(pgv_hnsw * h, const void *queries, int nq, int ef_search, int64_t discard_cap,
 								pgv_hnsw_scan * *out);
+/*
+ * pgv_hnsw_scan_begin on a sparse mirror (pgv_hnsw_upload_sparse, _buildable, or a view of either): hnswbeginscan /
+ * hnswrescan for `USING hnsw (... sparsevec_*_ops)`.  The queries come in CSR and are validated and staged as
+ * pgv_hnsw_search_sparse's: host arrays are checked before anything else, a device q_ptr is copied to the host and checked,
+ * a query may store up to 16 000 elements.  The scan keeps ITS OWN device copy of the queries for its lifetime -- the
+ * offsets, the indices and the values as three arrays, the layout the walk stages a query from (a stored element takes
+ * 8 bytes, as it would side by side) -- so the caller may reuse its arrays as soon as the call returns, and
+ * pgv_hnsw_search_sparse may run between the scan's batches.  Launches nothing.
+ *   ef_search, discard_cap  as pgv_hnsw_scan_begin.  State per query: 8 * discard_cap + 4 * (n / 32 + 2) + 16 bytes, and
+ *                           8 bytes per offset + 8 bytes per stored element of the query copy
+ * pgv_hnsw_scan_next, _drain and _end serve the scan as they serve any other; the order among equal distances is the one
+ * described above ((distance, position in the pool)), and without ties every batch holds the reference's elements,
+ * distances and so->tuples.  A batch's first is pgv_hnsw_search_sparse(ef_search, k = ef_search), bit for bit.
+ * The query's pairs sit in LDS next to the walk's state and the entry step's: ef_search, m and the SCAN's longest query
+ * (whichever queries a batch wants) together may need at most 150 KiB, checked HERE (the text names the three).
+ * PGV_ERR_ARG: not a sparse mirror, no graph set, ef_search outside 1..1000, a negative discard_cap, a NULL handle / out /
+ * q_ptr, a query array that breaks the sparsevec rules, the LDS need.  PGV_ERR_NOMEM: the state does not fit (the text
+ * has the byte count).  *out is NULL after every error.
+ */
+int			pgv_hnsw_scan_begin_sparse(pgv_hnsw * h, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq,
+									   int ef_search, int64_t discard_cap, pgv_hnsw_scan * *out);
 /*
  * The next batch of every query with want[q] != 0 (want == NULL: all of them), one launch, one workgroup per query:
  * GetScanItems for a query's first batch, ResumeScanItems (src/hnswscan.c:61-87) afterwards.  The graph is read as it

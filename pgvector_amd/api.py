@@ -1086,7 +1086,8 @@ class SparseHnsw(Hnsw):
     _l1_ops)` (pgv_hnsw_upload_sparse): rows_csr = (ptr [n + 1], idx, val) as sparse_topk takes them, at most 1000 stored
     elements per element; metric PGV_L2SQ / PGV_NEG_IP / PGV_L1 (cosine: PGV_NEG_IP over normalised vectors).
     set_graph, update_graph, get_payload and close are Hnsw's; search, score and score_pairs take CSR queries / element
-    slots and return sparse_distance_batch's values.  No export: the mirror is not shared across processes.
+    slots and return sparse_distance_batch's values; scan_sparse begins a resumable scan (hnsw.iterative_scan) with CSR
+    queries.  No export: the mirror is not shared across processes.
     buildable=True uploads through pgv_hnsw_upload_sparse_buildable: the same mirror, which the build-side entries serve as
     well (_host.hnsw_build(mirror, None, m, ef_construction, rows_csr=...) builds its graph); views inherit it."""
 
@@ -1132,7 +1133,13 @@ class SparseHnsw(Hnsw):
         return elem, dist, scored
 
     def scan(self, queries_csr, ef_search, discard_cap=0):
-        raise PgvError(PGV_ERR_ARG, "a sparse mirror is not scanned iteratively (pgv_hnsw_scan_begin): use search")
+        raise PgvError(PGV_ERR_ARG, "scan takes dense query rows (pgv_hnsw_scan_begin): a sparse mirror is scanned "
+                                    "iteratively with scan_sparse")
+
+    def scan_sparse(self, queries_csr, ef_search, discard_cap=0):
+        """pgv_hnsw_scan_begin_sparse: a resumable scan of these CSR queries (hnsw.iterative_scan) -> SparseHnswScan, with
+        HnswScan's interface; the scan keeps its own copy of the queries"""
+        return SparseHnswScan(self, queries_csr, ef_search, discard_cap)
 
     def score(self, queries_csr, slot, query_of=None):
         """pgv_hnsw_score_sparse: the distance of element slot[i] to query query_of[i] (None: query 0) of the CSR queries"""
@@ -1219,15 +1226,30 @@ class HnswScan:
             pass
 
 
+class SparseHnswScan(HnswScan):
+    """HnswScan over a sparse mirror (pgv_hnsw_scan_begin_sparse): the queries in CSR, as SparseHnsw.search takes them"""
+
+    def __init__(self, mirror, queries_csr, ef_search, discard_cap=0):
+        q_ptr, q_idx, q_val = _csr(queries_csr)
+        self.mirror, self.nq, self.ef = mirror, int(q_ptr.shape[0]) - 1, int(ef_search)
+        self._like = q_val
+        self.s = None
+        s = C.c_void_p()
+        check(lib.pgv_hnsw_scan_begin_sparse(mirror.h, ptr(q_ptr), ptr(q_idx), ptr(q_val), self.nq, self.ef, int(discard_cap),
+                                             C.byref(s)))
+        self.s = s
+
+
 def hnsw_iterative_search(h, queries, k, keep, ef_search, max_scan_tuples=20000, strict=False, discard_cap=0):
     """hnswgettuple's loop (src/hnswscan.c:242-327) under hnsw.iterative_scan over a batch of queries: batches nearest
     first, `keep` (a boolean array over element slots, the executor's filter) applied to each, with `strict` an element
     nearer than the last one emitted dropped (:313-319), a query stopped at k kept elements; once its so->tuples
     reaches max_scan_tuples a query takes the remaining discarded candidates instead of walking on (:259-266).  Only the
-    queries that still want more advance.  -> (ids: per query the kept element slots in emission order, dist: their
-    distances, scored [nq]: so->tuples at the end)"""
+    queries that still want more advance.  A SparseHnsw takes its queries in CSR.  -> (ids: per query the kept element
+    slots in emission order, dist: their distances, scored [nq]: so->tuples at the end)"""
     keep = np.asarray(keep, dtype=bool)
-    with h.scan(queries, ef_search, discard_cap) as s:
+    begin = h.scan_sparse if getattr(h, "sparse", False) else h.scan
+    with begin(queries, ef_search, discard_cap) as s:
         nq = s.nq
         ids, dist = [[] for _ in range(nq)], [[] for _ in range(nq)]
         prev = np.full(nq, -np.inf)

@@ -105,10 +105,11 @@ __host__ __device__ inline size_t sparse_query_bytes(int sq_cap, int bm_words) {
     return (size_t)sq_cap * sizeof(QElem) + (size_t)kHnswWaves * bm_words * sizeof(uint32_t);
 }
 
-// What a resumable scan (pgv_hnsw_scan_*, SCAN = true) takes in the place of HnswSparse -- sparse mirrors are not scanned,
-// so the last argument is one or the other and the plain walks' arguments stay where they were.  Per query: its visited
-// bitmap (bitmaps[q * words ..), never shared between workgroups), the pool of discarded candidates in the order they were
-// discarded ((key, element) pairs, pool[q * cap ..)), and HnswScanQuery.  A query is one workgroup's for a whole launch.
+// What a resumable scan (pgv_hnsw_scan_*, SCAN = true) over dense or bit rows takes in the place of HnswSparse: the last
+// argument is one or the other, and the plain walks' arguments stay where they were (a scan over sparse rows takes both,
+// HnswSparseScan below).  Per query: its visited bitmap (bitmaps[q * words ..), never shared between workgroups), the pool
+// of discarded candidates in the order they were discarded ((key, element) pairs, pool[q * cap ..)), and HnswScanQuery.  A
+// query is one workgroup's for a whole launch.
 struct HnswScanQuery {
     int64_t tuples;   // so->tuples so far
     int32_t pool_n;   // live pool entries
@@ -125,6 +126,13 @@ struct HnswScanDev {
     int64_t *out_left;      // [nq] or NULL
     int *overflow;          // 0, or 1 + the first query seen to overflow its pool
     int drain;              // pgv_hnsw_scan_drain: the entry step alone
+};
+// ... and a scan over sparse rows (pgv_hnsw_scan_begin_sparse, <SparseRow, METRIC, SCAN = true>): the scan's state and the
+// sparse walk's extras in one last argument, of this form only -- every other instantiation keeps the argument it had.
+// q_ptr / q_idx / q_val are the scan's own copy of its queries; q_cap / bm_words come from the SCAN's longest query,
+// whichever queries a launch wants
+struct HnswSparseScan : HnswScanDev {
+    HnswSparse sp;
 };
 
 // A walk's scalars in LDS, one workgroup's
@@ -291,17 +299,21 @@ __device__ __forceinline__ void scan_entry_step(uint2 *__restrict__ pool, int pn
     __syncthreads();
 }
 
-__device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSparse &sp, const HnswSparse &) { return sp; }
-__device__ __forceinline__ const HnswSparse &sparse_extras(const HnswScanDev &, const HnswSparse &none) { return none; }
+__host__ __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSparse &sp, const HnswSparse &) { return sp; }
+__host__ __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswScanDev &, const HnswSparse &none) { return none; }
+__host__ __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSparseScan &s, const HnswSparse &) { return s.sp; }
+
+// the kernel's last argument: a sparse walk's extras, a scan's state, or -- a scan over sparse rows -- both
+template <typename T, bool SCAN>
+using HnswLast = std::conditional_t<SCAN, std::conditional_t<std::is_same_v<T, SparseRow>, HnswSparseScan, HnswScanDev>, HnswSparse>;
 
 // ELEMQ (sparse rows only): the queries are element slots of the mirror, the build's form of a sparse walk.  An
 // instantiation of its own, so that the plain sparse walks compile to what they were
 template <typename T, int METRIC, bool SCAN = false, bool ELEMQ = false>
 __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
-    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter,
-    std::conditional_t<SCAN, HnswScanDev, HnswSparse> last) {
+    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter, HnswLast<T, SCAN> last) {
     const HnswSparse none{};
-    const HnswSparse &sp = sparse_extras(last, none);  // a sparse walk's extras (a scan has none)
+    const HnswSparse &sp = sparse_extras(last, none);  // a sparse walk's extras (a dense or bit scan has none)
     const auto &ss = last;                             // a resumable scan's state (SCAN)
     const int nq = run.nq, ef = run.ef, k = run.k;
     int64_t *__restrict__ out_elem = run.out_elem;
@@ -836,18 +848,28 @@ __global__ __launch_bounds__(256) void hnsw_patch_kernel(int32_t *__restrict__ n
     for (int64_t j = lane; j < len; j += 64) nbr[dst + j] = packed[src + j];
 }
 
+// the LDS a walk over sparse rows needs (*lds_out, may be NULL), against the limit: the text names ef, m and the query length
+int hnsw_sparse_lds_check(const char *who, int ef, int m, int q_cap, int bm_words, bool scan, size_t *lds_out) {
+    const size_t lds = HnswLds(sparse_query_bytes(q_cap, bm_words), ef, m, scan).total;
+    if (lds_out) *lds_out = lds;
+    if (lds > kHnswLdsLimit)
+        PGV_FAIL(PGV_ERR_ARG, "%s: ef %d / m %d / a query of %d stored elements need %zu bytes of LDS (limit %d)", who, ef, m,
+                 q_cap, lds, (int)kHnswLdsLimit);
+    return PGV_OK;
+}
+
 template <typename T, int METRIC, typename Last = HnswSparse, bool ELEMQ = false>
 int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *bitmaps, int words, int grid,
                   int *counter, const Last &sp = Last{}) {
     constexpr bool kSparse = std::is_same_v<T, SparseRow>;
-    constexpr bool kScan = std::is_same_v<Last, HnswScanDev>;
-    size_t query_bytes = (size_t)g.nvec * sizeof(Raw16);
-    if constexpr (kSparse) query_bytes = sparse_query_bytes(sp.q_cap, sp.bm_words);
-    const size_t lds = HnswLds(query_bytes, run.ef, g.m, kScan).total;  // the layout the kernel carves
-    if (lds > kHnswLdsLimit) {
-        if constexpr (kSparse)
-            PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d / a query of %d stored elements need %zu bytes of LDS (limit %d)",
-                     run.ef, g.m, sp.q_cap, lds, (int)kHnswLdsLimit);
+    constexpr bool kScan = std::is_base_of_v<HnswScanDev, Last>;
+    static_assert(std::is_same_v<Last, HnswLast<T, kScan>>, "the kernel's last argument for these rows");
+    size_t lds = HnswLds((size_t)g.nvec * sizeof(Raw16), run.ef, g.m, kScan).total;  // the layout the kernel carves
+    if constexpr (kSparse) {
+        const HnswSparse none{};
+        const HnswSparse &extras = sparse_extras(sp, none);
+        PGV_TRY(hnsw_sparse_lds_check(kScan ? "hnsw scan" : "hnsw search", run.ef, g.m, extras.q_cap, extras.bm_words, kScan, &lds));
+    } else if (lds > kHnswLdsLimit) {
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
     }
     auto kern = hnsw_search_kernel<T, METRIC, kScan, ELEMQ>;
@@ -1120,10 +1142,24 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
     run.rows_per_trip = per_trip >= 4 ? 4 : (per_trip == 1 ? 1 : 2);
     static const int prefetch = getenv("PGV_HNSW_SPARSE_PREFETCH") ? atoi(getenv("PGV_HNSW_SPARSE_PREFETCH")) : 1;
     PGV_HIP(hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
+    // what a walk over sparse rows takes on top; q_cap / bm_words from max_q_nnz: a scan's longest query, whatever it wants
+    HnswSparse sp{};
+    if (v.sparse()) {
+        sp.row_ptr = v.ptr;
+        sp.q_ptr = a.sparse_queries.ptr;
+        sp.q_idx = a.sparse_queries.idx;
+        sp.q_val = a.sparse_queries.val;
+        sp.q_cap = pad4(a.max_q_nnz);
+        sp.bm_words = v.metric == PGV_NEG_IP ? 0 : bitmap_words(a.max_q_nnz);
+        sp.prefetch = prefetch != 0;
+    }
     if (scan) {  // a batch of a resumable scan, or its drain: the walk's SCAN form over the scan's own state
-        if (v.sparse() || a.qids || !a.out_elem || !a.out_dist || a.k != a.ef)
-            PGV_FAIL(PGV_ERR_ARG, "hnsw scan: dense or bit rows, query vectors, k = ef");
-        HnswScanDev sd;
+        if (a.qids || !a.out_elem || !a.out_dist || a.k != a.ef || (v.sparse() && !a.sparse_queries.ptr))
+            PGV_FAIL(PGV_ERR_ARG, "hnsw scan: query vectors (sparse rows: sparse queries), not element slots; k = ef");
+        if (v.sparse() && a.max_q_nnz > kSparseMaxNnz)
+            PGV_FAIL(PGV_ERR_DIMS, "hnsw scan: a query of %d stored elements", a.max_q_nnz);
+        HnswSparseScan sd;
+        sd.sp = sp;
         sd.pool = static_cast<uint2 *>(scan->pool);
         sd.cap = scan->cap;
         sd.qs = static_cast<HnswScanQuery *>(scan->qstate);
@@ -1132,20 +1168,19 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
         sd.out_left = scan->out_left;
         sd.overflow = scan->overflow;
         sd.drain = scan->drain ? 1 : 0;
+        if (v.sparse()) switch (v.metric) {
+                case PGV_L2SQ: return launch_hnsw_t<SparseRow, 0, HnswSparseScan>(ctx, g, run, bitmaps, words, grid, counter, sd);
+                case PGV_NEG_IP: return launch_hnsw_t<SparseRow, 1, HnswSparseScan>(ctx, g, run, bitmaps, words, grid, counter, sd);
+                case PGV_L1: return launch_hnsw_t<SparseRow, 2, HnswSparseScan>(ctx, g, run, bitmaps, words, grid, counter, sd);
+                default: PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
+            }
+        const HnswScanDev &dense = sd;
         return dispatch_rows(v, [&](auto *tp, auto mc) {
             return launch_hnsw_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value, HnswScanDev>(ctx, g, run, bitmaps, words,
-                                                                                                        grid, counter, sd);
+                                                                                                        grid, counter, dense);
         });
     }
     if (v.sparse()) {
-        HnswSparse sp;
-        sp.row_ptr = v.ptr;
-        sp.q_ptr = a.sparse_queries.ptr;
-        sp.q_idx = a.sparse_queries.idx;
-        sp.q_val = a.sparse_queries.val;
-        sp.q_cap = pad4(a.max_q_nnz);
-        sp.bm_words = v.metric == PGV_NEG_IP ? 0 : bitmap_words(a.max_q_nnz);
-        sp.prefetch = prefetch != 0;
         // the queries of a sparse walk are sparse vectors, or -- the build, which the entry points let through for a mirror
         // of pgv_hnsw_upload_sparse_buildable only -- element slots: then max_q_nnz is the mirror's longest element
         if ((a.sparse_queries.ptr != nullptr) == (a.qids != nullptr))
@@ -1168,6 +1203,10 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
     return dispatch_rows(v, [&](auto *tp, auto mc) {
         return launch_hnsw_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value>(ctx, g, run, bitmaps, words, grid, counter);
     });
+}
+
+int hnsw_sparse_scan_lds_check(const char *who, pgv_metric metric, int ef, int m, int max_q_nnz) {
+    return hnsw_sparse_lds_check(who, ef, m, pad4(max_q_nnz), metric == PGV_NEG_IP ? 0 : bitmap_words(max_q_nnz), true, nullptr);
 }
 
 int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int32_t *ids, const int64_t *packed_off,

@@ -1232,7 +1232,11 @@ int pgv_hnsw_update_graph(pgv_hnsw *h, int32_t entry, const int32_t *elements, i
 struct pgv_hnsw_scan {
     pgv_hnsw *h = nullptr;
     int nq = 0, ef = 0, cap = 0, words = 0;
-    void *queries = nullptr;  // [nq] rows in the mirror's layout (the scan's own copy: the caller's may go away)
+    void *queries = nullptr;  // [nq] rows in the mirror's layout (the scan's own copy: the caller's may go away), or over a
+    void *q_ptr = nullptr;    // sparse mirror the queries in CSR, the scan's own copy as well: [nq + 1] offsets,
+    void *q_idx = nullptr;    // ... the indices and
+    void *q_val = nullptr;    // ... the values, as stage_query reads them
+    int max_q_nnz = 0;        // the longest query's stored elements: every batch's LDS is sized by it
     void *bitmaps = nullptr;  // [nq x words] one visited set per query
     void *pool = nullptr;     // [nq x cap] (key, element)
     void *qstate = nullptr;   // [nq x kHnswScanQueryBytes], then the overflow word
@@ -1246,21 +1250,20 @@ static int hnsw_scan_overflowed(const pgv_hnsw_scan *s) {
              s->failed_query, s->cap);
 }
 
-int pgv_hnsw_scan_begin(pgv_hnsw *h, const void *queries, int nq, int ef_search, int64_t discard_cap, pgv_hnsw_scan **out) {
-    if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin: handle/out is NULL");
-    *out = nullptr;
-    if (hnsw_is_sparse(h))
-        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin: a sparse mirror (pgv_hnsw_upload_sparse) is not scanned iteratively: its "
-                              "queries are staged per call; use pgv_hnsw_search_sparse");
-    hnsw_view_refresh(h);
+// what both begins check after their handle: the counts, and that there is a graph to walk
+static int hnsw_scan_check(pgv_hnsw *h, const char *who, int nq, int ef_search, int64_t discard_cap) {
     if (nq < 0) PGV_FAIL(PGV_ERR_ARG, "bad query count");
     if (ef_search < 1 || ef_search > 1000)
         PGV_FAIL(PGV_ERR_ARG, "hnsw.ef_search must be 1..1000 (src/hnsw.c:93-94), got %d", ef_search);
     if (discard_cap < 0) PGV_FAIL(PGV_ERR_ARG, "discard_cap must be >= 0, got %lld", (long long)discard_cap);
-    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin needs pgv_hnsw_set_graph first");
-    if (nq > 0 && !queries) PGV_FAIL(PGV_ERR_ARG, "queries is NULL");
-    pgv_ctx *ctx = h->ctx;
-    PGV_HIP(hipSetDevice(ctx->device));
+    if (h->graph.m == 0) PGV_FAIL(PGV_ERR_ARG, "%s needs pgv_hnsw_set_graph first", who);
+    return PGV_OK;
+}
+
+// A scan's state on the device, its query copy included: qbytes[i] bytes for *qbufs[i] (nqbufs of them, fields of the new
+// scan), then the visited sets, the pools and the per-query state.  Nothing is written yet.  PGV_ERR_NOMEM frees it all.
+static int hnsw_scan_alloc(pgv_hnsw *h, const char *who, int nq, int ef_search, int64_t discard_cap, const size_t *qbytes,
+                           int nqbufs, void **(*qbuf)(pgv_hnsw_scan *, int), pgv_hnsw_scan **out, size_t *sbytes_out) {
     pgv_hnsw_scan *s = new (std::nothrow) pgv_hnsw_scan();
     if (!s) PGV_FAIL(PGV_ERR_NOMEM, "out of host memory");
     s->h = h;
@@ -1272,30 +1275,103 @@ int pgv_hnsw_scan_begin(pgv_hnsw *h, const void *queries, int nq, int ef_search,
     s->cap = (int)discard_cap;
     s->words = (int)((h->n + 31) / 32) + 1;
     const size_t rows = (size_t)(nq > 0 ? nq : 1);
-    const size_t qbytes = rows * hnsw_row_bytes(h->geom), bbytes = rows * (size_t)s->words * sizeof(uint32_t),
-                 pbytes = rows * (size_t)s->cap * 8, sbytes = rows * kHnswScanQueryBytes + 16;
-    void **bufs[4] = {&s->queries, &s->bitmaps, &s->pool, &s->qstate};
-    const size_t sizes[4] = {qbytes, bbytes, pbytes, sbytes};
-    for (int i = 0; i < 4; i++)
+    const size_t bbytes = rows * (size_t)s->words * sizeof(uint32_t), pbytes = rows * (size_t)s->cap * 8,
+                 sbytes = rows * kHnswScanQueryBytes + 16;
+    void **bufs[6];
+    size_t sizes[6], total = 0;
+    int nb = 0;
+    for (int i = 0; i < nqbufs; i++, nb++) {
+        bufs[nb] = qbuf(s, i);
+        sizes[nb] = qbytes[i];
+    }
+    bufs[nb] = &s->bitmaps, sizes[nb++] = bbytes;
+    bufs[nb] = &s->pool, sizes[nb++] = pbytes;
+    bufs[nb] = &s->qstate, sizes[nb++] = sbytes;
+    for (int i = 0; i < nb; i++) total += sizes[i];
+    for (int i = 0; i < nb; i++)
         if (hipMalloc(bufs[i], sizes[i]) != hipSuccess) {
             (void)hipGetLastError();
             *bufs[i] = nullptr;
+            const int cap = s->cap, words = s->words;
             pgv_hnsw_scan_end(s);
-            PGV_FAIL(PGV_ERR_NOMEM, "pgv_hnsw_scan_begin: hipMalloc(%zu) failed; the state of %d queries takes %zu bytes "
+            PGV_FAIL(PGV_ERR_NOMEM, "%s: hipMalloc(%zu) failed; the state of %d queries takes %zu bytes "
                                     "(discard_cap %d, %d bitmap words per query)",
-                     sizes[i], nq, qbytes + bbytes + pbytes + sbytes, s->cap, s->words);
+                     who, sizes[i], nq, total, cap, words);
         }
-    int rc = put_padded_rows(ctx->stream, s->queries, hnsw_row_bytes(h->geom), queries,
-                             hnsw_src_row_bytes(h->dim, h->dtype, h->nbits), nq);
-    hipError_t e = rc == PGV_OK ? hipMemsetAsync(s->qstate, 0, sbytes, ctx->stream) : hipSuccess;
-    if (rc == PGV_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the caller may reuse queries right away
+    *sbytes_out = sbytes;
+    *out = s;
+    return PGV_OK;
+}
+
+// the end of both begins: the query copy is on its way (rc, on the handle's stream); zero the per-query state and wait --
+// the caller may reuse its query arrays right away
+static int hnsw_scan_publish(pgv_hnsw_scan *s, const char *who, int rc, hipError_t e, size_t sbytes, pgv_hnsw_scan **out) {
+    pgv_ctx *ctx = s->h->ctx;
+    if (rc == PGV_OK && e == hipSuccess) e = hipMemsetAsync(s->qstate, 0, sbytes, ctx->stream);
+    if (rc == PGV_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (rc != PGV_OK || e != hipSuccess) {
         pgv_hnsw_scan_end(s);
         if (rc != PGV_OK) return rc;
-        PGV_FAIL(PGV_ERR_DEVICE, "pgv_hnsw_scan_begin: staging failed: %s", hipGetErrorString(e));
+        PGV_FAIL(PGV_ERR_DEVICE, "%s: staging failed: %s", who, hipGetErrorString(e));
     }
     *out = s;
     return PGV_OK;
+}
+
+int pgv_hnsw_scan_begin(pgv_hnsw *h, const void *queries, int nq, int ef_search, int64_t discard_cap, pgv_hnsw_scan **out) {
+    const char *who = "pgv_hnsw_scan_begin";
+    if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin: handle/out is NULL");
+    *out = nullptr;
+    PGV_NO_SPARSE(h, who, "pgv_hnsw_scan_begin_sparse");
+    hnsw_view_refresh(h);
+    PGV_TRY(hnsw_scan_check(h, who, nq, ef_search, discard_cap));
+    if (nq > 0 && !queries) PGV_FAIL(PGV_ERR_ARG, "queries is NULL");
+    pgv_ctx *ctx = h->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    const size_t qbytes = (size_t)(nq > 0 ? nq : 1) * hnsw_row_bytes(h->geom);
+    pgv_hnsw_scan *s = nullptr;
+    size_t sbytes = 0;
+    PGV_TRY(hnsw_scan_alloc(h, who, nq, ef_search, discard_cap, &qbytes, 1,
+                            [](pgv_hnsw_scan *sc, int) -> void ** { return &sc->queries; }, &s, &sbytes));
+    const int rc = put_padded_rows(ctx->stream, s->queries, hnsw_row_bytes(h->geom), queries,
+                                   hnsw_src_row_bytes(h->dim, h->dtype, h->nbits), nq);
+    return hnsw_scan_publish(s, who, rc, hipSuccess, sbytes, out);
+}
+
+// hnswbeginscan / hnswrescan on a sparse mirror: the queries in CSR, validated and staged as pgv_hnsw_search_sparse's, then
+// copied into the scan's own three arrays (offsets, indices, values -- the layout stage_query reads; 8 bytes per stored
+// element either way) so that the context's staging buffers and the caller's arrays are free again when this returns
+int pgv_hnsw_scan_begin_sparse(pgv_hnsw *h, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq, int ef_search,
+                               int64_t discard_cap, pgv_hnsw_scan **out) {
+    const char *who = "pgv_hnsw_scan_begin_sparse";
+    if (!h || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_begin_sparse: handle/out is NULL");
+    *out = nullptr;
+    PGV_ONLY_SPARSE(h, who);
+    hnsw_view_refresh(h);
+    PGV_TRY(hnsw_scan_check(h, who, nq, ef_search, discard_cap));
+    if (!q_ptr) PGV_FAIL(PGV_ERR_ARG, "q_ptr is NULL");
+    pgv_ctx *ctx = h->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    StagedCsr q;
+    int max_nnz = 0;
+    PGV_TRY(hnsw_stage_sparse_queries(h, who, q_ptr, q_idx, q_val, nq, &q, &max_nnz));
+    // every batch carves the same LDS, sized by the scan's longest query: too much is refused here, not at the first next
+    PGV_TRY(hnsw_sparse_scan_lds_check(who, h->metric, ef_search, h->graph.m, max_nnz));
+    const int64_t total = q.host_ptr[nq];
+    const size_t elems = (size_t)(total > 0 ? total : 1);
+    const size_t qbytes[3] = {sizeof(int64_t) * ((size_t)nq + 1), sizeof(int32_t) * elems, sizeof(float) * elems};
+    pgv_hnsw_scan *s = nullptr;
+    size_t sbytes = 0;
+    PGV_TRY(hnsw_scan_alloc(h, who, nq, ef_search, discard_cap, qbytes, 3,
+                            [](pgv_hnsw_scan *sc, int i) -> void ** { return i == 0 ? &sc->q_ptr : i == 1 ? &sc->q_idx : &sc->q_val; },
+                            &s, &sbytes));
+    s->max_q_nnz = max_nnz;
+    hipError_t e = hipMemcpyAsync(s->q_ptr, q.dev.ptr, qbytes[0], hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && total > 0)
+        e = hipMemcpyAsync(s->q_idx, q.dev.idx, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && total > 0)
+        e = hipMemcpyAsync(s->q_val, q.dev.val, sizeof(float) * (size_t)total, hipMemcpyDeviceToDevice, ctx->stream);
+    return hnsw_scan_publish(s, who, PGV_OK, e, sbytes, out);
 }
 
 // one launch over the scan's state: a batch of every wanted query (ef = the scan's) or the drain of their pools
@@ -1318,6 +1394,11 @@ static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool 
     PGV_TRY(ctx->counters.ensure(256));
     HnswSearchArgs a;
     a.queries = s->queries;
+    if (hnsw_is_sparse(h)) {
+        a.sparse_queries = {static_cast<const int64_t *>(s->q_ptr), static_cast<const int32_t *>(s->q_idx),
+                            static_cast<const float *>(s->q_val), s->nq};
+        a.max_q_nnz = drain ? 0 : s->max_q_nnz;  // (a drain stages no query: count up to 1000 fits whatever the queries store)
+    }
     a.nq = s->nq;
     a.ef = ef;
     a.k = ef;
@@ -1376,6 +1457,9 @@ void pgv_hnsw_scan_end(pgv_hnsw_scan *s) {
         (void)hipStreamSynchronize(s->h->ctx->stream);
     }
     if (s->queries) (void)hipFree(s->queries);
+    if (s->q_ptr) (void)hipFree(s->q_ptr);
+    if (s->q_idx) (void)hipFree(s->q_idx);
+    if (s->q_val) (void)hipFree(s->q_val);
     if (s->bitmaps) (void)hipFree(s->bitmaps);
     if (s->pool) (void)hipFree(s->pool);
     if (s->qstate) (void)hipFree(s->qstate);

@@ -670,7 +670,8 @@ struct HnswSearchArgs {
 };
 // ... and a resumable scan's state on top (pgv_hnsw_scan_*): with it the launch is one batch of every wanted query --
 // the first (GetScanItems) or a resumed one (ResumeScanItems, src/hnswscan.c:61-87) -- or the drain of their pools.
-// bitmaps / words are then the scan's: one visited set per QUERY.  Dense and bit rows only, k = ef
+// bitmaps / words are then the scan's: one visited set per QUERY.  k = ef; query rows, or over sparse rows sparse_queries
+// (the scan's own copy) with max_q_nnz the longest query of the SCAN: every batch carves the same LDS, whatever it wants
 constexpr size_t kHnswScanQueryBytes = 16;  // per query: tuples so far, live pool entries, flags
 struct HnswScanArgs {
     void *pool = nullptr;              // [nq x cap] (key, element) pairs: the discarded candidates, in discard order
@@ -684,6 +685,9 @@ struct HnswScanArgs {
 };
 int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const HnswSearchArgs &a, uint32_t *bitmaps,
                        int words, int grid, int *counter, const HnswScanArgs *scan = nullptr);
+// PGV_ERR_ARG (the text: who, ef, m, the query length) when a scan over sparse rows would need more LDS than a workgroup
+// has: what launch_hnsw_search checks at every batch, for pgv_hnsw_scan_begin_sparse to refuse at once
+int hnsw_sparse_scan_lds_check(const char *who, pgv_metric metric, int ef, int m, int max_q_nnz);
 int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int32_t *ids, const int64_t *packed_off,
                       const int32_t *packed, int nupd);
 
