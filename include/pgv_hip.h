@@ -1062,6 +1062,45 @@ int			pgv_hnsw_scan_next(pgv_hnsw_scan * s, const uint8_t *want, int64_t *out_el
  */
 int			pgv_hnsw_scan_drain(pgv_hnsw_scan * s, const uint8_t *want, int count, int64_t *out_elem, float *out_dist,
 								int32_t *out_count);
+/*
+ * hnswgettuple's loop under a filter (src/hnswscan.c:242-327: hnsw.iterative_scan with a WHERE clause) for every query with
+ * want[q] != 0 (NULL: all), in ONE launch: the workgroup that takes a query keeps it, batch after batch, until it has its k
+ * rows, its pool is empty, or -- past max_scan_tuples -- the pool has been drained.  Per query:
+ *     emitted = 0; prev = the lowest key
+ *     while emitted < k:
+ *         batch = the pool's ef_search nearest (pgv_hnsw_scan_drain) if the scan has started and so->tuples >= max_scan_tuples,
+ *                 else the next batch (pgv_hnsw_scan_next)
+ *         if the batch is empty: stop
+ *         for every (element, key) of the batch, nearest first, while emitted < k:
+ *             strict: an element with key < prev is dropped; otherwise prev = key
+ *             if the element's keep bit is set (or keep is NULL): emit (element, distance)
+ * Works on any scan -- dense, bit (Hamming or Jaccard) and sparse mirrors, views and imported mirrors --, fresh or with
+ * batches already taken.
+ *   want         [nq] bytes or NULL
+ *   keep         a bitmap over element slots, host or device: element e is bit e & 31 of word e >> 5.  NULL keeps every
+ *                element.  keep_stride == 0: one bitmap of (n + 31) / 32 words for every query; otherwise query q's
+ *                begins at keep + q * keep_stride, keep_stride >= (n + 31) / 32
+ *   k            1..4096 rows per query
+ *   max_scan_tuples  >= 1 (hnsw.max_scan_tuples)
+ *   strict       hnsw.iterative_scan = strict_order; it compares the walk's 32-bit keys, which order (and tie) as the
+ *                reference's float8 distances do -- under bit_jaccard_ops too, where two keys may share one float
+ *   out_elem     [nq x k] element slots in emission order, -1 padded;  out_dist [nq x k] +inf padded: for an element the
+ *                very float pgv_hnsw_scan_next hands back for it
+ *   out_count    [nq] rows emitted
+ *   out_scored   [nq] or NULL: so->tuples at the end;  out_batches [nq] or NULL: the walks plus drains this call took for
+ *                the query;  out_left [nq] or NULL: entries left in the pool
+ * Every output may be host or device memory.  An unwanted query gets count 0, padding, its current so->tuples, and its
+ * state untouched.
+ * Afterwards the scan's state is its state after the last batch taken: a second call, a pgv_hnsw_scan_next or a _drain
+ * continues from there.  `prev` and the undelivered rest of the last batch are NOT kept: the elements behind the k-th
+ * emitted row of that batch are gone, as they are for a caller that stops reading pgv_hnsw_scan_next's rows early.
+ * PGV_ERR_ARG, before any launch: a NULL scan / out_elem / out_dist / out_count, k outside 1..4096, max_scan_tuples < 1, a
+ * keep_stride other than 0 below the mirror's (n + 31) / 32 words.  PGV_ERR_NOMEM as pgv_hnsw_scan_next: a query whose
+ * pool would overflow ends flagged, the text names it, every later call on the scan repeats the error.
+ */
+int			pgv_hnsw_scan_filtered(pgv_hnsw_scan * s, const uint8_t *want, const uint32_t *keep, int64_t keep_stride,
+								   int k, int64_t max_scan_tuples, int strict, int64_t *out_elem, float *out_dist,
+								   int32_t *out_count, int64_t *out_scored, int32_t *out_batches, int64_t *out_left);
 /* hnswendscan (src/hnswscan.c:336-345): waits for the handle's stream and frees the state; before pgv_hnsw_free */
 void		pgv_hnsw_scan_end(pgv_hnsw_scan * s);
 

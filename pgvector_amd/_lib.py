@@ -54,7 +54,7 @@ SYMBOLS = [
     "pgv_hnsw_upload_jaccard",
     "pgv_hnsw_upload_bits_buildable", "pgv_hnsw_buildable_bits",
     "pgv_hnsw_upload_sparse_buildable", "pgv_hnsw_buildable_sparse", "pgv_hnsw_elements",
-    "pgv_hnsw_scan_begin_sparse",
+    "pgv_hnsw_scan_begin_sparse", "pgv_hnsw_scan_filtered",
 ]
 
 
@@ -214,6 +214,7 @@ def _load():
     lib.pgv_hnsw_scan_begin_sparse.argtypes = [P, P, P, P, I, I, I64, C.POINTER(P)]
     lib.pgv_hnsw_scan_next.argtypes = [P, P, P, P, P, P, P]
     lib.pgv_hnsw_scan_drain.argtypes = [P, P, I, P, P, P]
+    lib.pgv_hnsw_scan_filtered.argtypes = [P, P, P, I64, I, I64, I, P, P, P, P, P, P]
     lib.pgv_hnsw_scan_end.argtypes = [P]
     lib.pgv_hnsw_scan_end.restype = None
     return lib

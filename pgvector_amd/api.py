@@ -1165,6 +1165,41 @@ def _host_array(x):
     return x.cpu().numpy() if _is_torch(x) else np.asarray(x)
 
 
+def pack_keep(keep):
+    """a filter over element slots as pgv_hnsw_scan_filtered reads it: boolean [n] (one filter for every query) or
+    [nq, n] (one per query) -> uint32 words [(n + 31) / 32] or [nq, (n + 31) / 32], element e at bit e & 31 of word
+    e >> 5.  A boolean tensor is packed where it lives (as int32 words: torch's 32-bit type), a few filters at a time: the
+    temporaries stay below about 128 MB whatever nq is"""
+    if _is_torch(keep):
+        import torch
+        n = int(keep.shape[-1])
+        words = (n + 31) // 32
+        rows = keep.reshape(-1, n)
+        out = torch.empty((rows.shape[0], words), dtype=torch.int32, device=keep.device)
+        weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=keep.device)
+        step = max(1, (32 << 20) // (words * 32))
+        for lo in range(0, rows.shape[0], step):
+            part = rows[lo:lo + step]
+            bits = torch.zeros((part.shape[0], words * 32), dtype=torch.uint8, device=keep.device)
+            bits[:, :n] = part != 0
+            # eight bits a byte (their weights sum to 255 at the most), four bytes a word, the lowest first
+            out[lo:lo + step] = (bits.view(-1, words * 4, 8) * weights).sum(-1, dtype=torch.uint8).view(torch.int32)
+        return out.reshape(tuple(keep.shape[:-1]) + (words,))
+    keep = np.asarray(keep) != 0
+    n = keep.shape[-1]
+    words = (n + 31) // 32
+    bits = np.zeros(keep.shape[:-1] + (words * 32,), dtype=np.uint8)
+    bits[..., :n] = keep
+    return np.ascontiguousarray(np.packbits(bits, axis=-1, bitorder="little")).view("<u4").reshape(keep.shape[:-1] + (words,))
+
+
+def _is_keep_words(keep):
+    """a filter that is packed already: 32-bit integers, an array or a tensor"""
+    if _is_torch(keep):
+        return str(keep.dtype) in ("torch.int32", "torch.uint32")
+    return isinstance(keep, np.ndarray) and keep.dtype in (np.uint32, np.int32)
+
+
 class HnswScan:
     """a resumable scan over a batch of queries (pgv_hnsw_scan_*): hnswgettuple's batches, one launch each.  Close it
     before the mirror it scans."""
@@ -1207,6 +1242,41 @@ class HnswScan:
         got = _empty_like_kind(self._like, (self.nq,), np.int32)
         check(lib.pgv_hnsw_scan_drain(self.s, ptr(want), count, ptr(elem), ptr(dist), ptr(got)))
         return elem, dist, got
+
+    def filtered(self, k, keep=None, max_scan_tuples=20000, strict=False, want=None):
+        """pgv_hnsw_scan_filtered: hnswgettuple's loop under a filter for the wanted queries (None: all), one launch --
+        batches through `keep` until a query has k rows, is exhausted or, past max_scan_tuples, has drained its pool.
+        keep: None (every element), a boolean array or tensor [n] or [nq, n] over element slots (packed with pack_keep),
+        or an array or tensor of 32-bit integers [words] or [nq, words] that is such a bitmap already (words >= (n + 31) /
+        32), passed through as it is.  n is the mirror's element count: any other length is refused here.
+        -> (element slots [nq x k] in emission order / -1, distances [nq x k] / +inf, count [nq], scored [nq]: so->tuples
+        at the end, batches [nq]: walks plus drains taken, left [nq]: pool entries)"""
+        want = self._want(want)
+        k = int(k)
+        stride = 0
+        if keep is not None:
+            n = int(lib.pgv_hnsw_elements(self.mirror.h))
+            if _is_keep_words(keep):
+                if int(keep.shape[-1]) < (n + 31) // 32:
+                    raise PgvError(PGV_ERR_ARG, "keep: %d words, the mirror's %d elements take %d" % (keep.shape[-1], n, (n + 31) // 32))
+                keep = keep.contiguous() if _is_torch(keep) else np.ascontiguousarray(keep)
+            else:
+                if int(keep.shape[-1]) != n:
+                    raise PgvError(PGV_ERR_ARG, "keep: a filter over %d elements, the mirror has %d" % (keep.shape[-1], n))
+                keep = pack_keep(keep)
+            if keep.ndim not in (1, 2) or (keep.ndim == 2 and keep.shape[0] != self.nq):
+                raise PgvError(PGV_ERR_ARG, "keep: one filter [n] or one per query [%d, n]" % self.nq)
+            stride = int(keep.shape[1]) if keep.ndim == 2 else 0
+        shape = (self.nq, max(k, 1))
+        elem = _empty_like_kind(self._like, shape, np.int64)
+        dist = _empty_like_kind(self._like, shape, np.float32)
+        count = _empty_like_kind(self._like, (self.nq,), np.int32)
+        scored = _empty_like_kind(self._like, (self.nq,), np.int64)
+        batches = _empty_like_kind(self._like, (self.nq,), np.int32)
+        left = _empty_like_kind(self._like, (self.nq,), np.int64)
+        check(lib.pgv_hnsw_scan_filtered(self.s, ptr(want), ptr(keep), stride, k, int(max_scan_tuples), int(bool(strict)),
+                                         ptr(elem), ptr(dist), ptr(count), ptr(scored), ptr(batches), ptr(left)))
+        return elem, dist, count, scored, batches, left
 
     def close(self):
         if self.s:
@@ -1283,6 +1353,17 @@ def hnsw_iterative_search(h, queries, k, keep, ef_search, max_scan_tuples=20000,
                     if c[q] == 0 or len(ids[q]) >= k:
                         draining[q] = False
     return ids, dist, scored
+
+
+def hnsw_filtered_search(h, queries, k, keep, ef_search, max_scan_tuples=20000, strict=False, discard_cap=0):
+    """hnsw_iterative_search with the loop on the device: one scan, one pgv_hnsw_scan_filtered launch, one copy back.
+    keep: as HnswScan.filtered takes it.  A SparseHnsw takes its queries in CSR.  -> (ids: per query the kept element
+    slots in emission order, dist: their distances, scored [nq]: so->tuples at the end)"""
+    begin = h.scan_sparse if getattr(h, "sparse", False) else h.scan
+    with begin(queries, ef_search, discard_cap) as s:
+        elem, dist, count, scored, _batches, _left = (_host_array(x) for x in s.filtered(k, keep, max_scan_tuples, strict))
+    ids = [elem[q, :count[q]].tolist() for q in range(s.nq)]
+    return ids, [dist[q, :count[q]].tolist() for q in range(s.nq)], scored.astype(np.int64)
 
 
 def binary_search_hnsw(ctx, metric, dtype, dim, queries, rows, bit_hnsw, ef_search, kc, k, want_candidates=False):

@@ -134,6 +134,19 @@ struct HnswScanDev {
 struct HnswSparseScan : HnswScanDev {
     HnswSparse sp;
 };
+// ... and a filtered scan (pgv_hnsw_scan_filtered, FILTER = true) on top of either: hnswgettuple's loop
+// (src/hnswscan.c:242-327) for one query inside one workgroup.  run.k is then the width of the output rows, run.ef the
+// scan's batch size.  Forms of their own again: every other instantiation keeps the argument it had.
+template <typename Base>
+struct HnswFiltered : Base {
+    const uint32_t *keep;  // element e: bit e & 31 of word e >> 5; NULL keeps everything
+    int64_t keep_stride;   // words between two queries' bitmaps; 0: one bitmap for all
+    int64_t max_tuples;    // hnsw.max_scan_tuples: from so->tuples >= this on the pool is drained, not walked
+    int strict;            // strict_order: an element nearer than the last one that passed is dropped
+    int32_t *out_batches;  // [nq] or NULL: walks plus drains taken
+};
+template <typename L> constexpr bool kIsFiltered = false;
+template <typename B> constexpr bool kIsFiltered<HnswFiltered<B>> = true;
 
 // A walk's scalars in LDS, one workgroup's
 struct WalkScalars {
@@ -142,6 +155,11 @@ struct WalkScalars {
     int tn, tread;      // |T|; T's next unread entry
     uint32_t tkey;      // the key T's entries share
     int pool_n;         // a scan's live pool entries, for the batch
+    // a filtered scan's query (FILTER): the rows its last batch emitted, the last key that passed strict_order, walks plus
+    // drains taken (the rows emitted so far are a register of every thread: see filter_batch)
+    int got;
+    uint32_t prev;
+    int batches;
 };
 // what a scan's entry step keeps in LDS on top: the radix descent's histogram, its verdict, and each wavefront's counts
 struct ScanEntryLds {
@@ -303,15 +321,22 @@ __host__ __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSp
 __host__ __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswScanDev &, const HnswSparse &none) { return none; }
 __host__ __device__ __forceinline__ const HnswSparse &sparse_extras(const HnswSparseScan &s, const HnswSparse &) { return s.sp; }
 
-// the kernel's last argument: a sparse walk's extras, a scan's state, or -- a scan over sparse rows -- both
+// the kernel's last argument: a sparse walk's extras, a scan's state, or -- a scan over sparse rows -- both; a filtered
+// scan's wraps the scan's
 template <typename T, bool SCAN>
-using HnswLast = std::conditional_t<SCAN, std::conditional_t<std::is_same_v<T, SparseRow>, HnswSparseScan, HnswScanDev>, HnswSparse>;
+using HnswLastPlain = std::conditional_t<SCAN, std::conditional_t<std::is_same_v<T, SparseRow>, HnswSparseScan, HnswScanDev>, HnswSparse>;
+template <typename T, bool SCAN, bool FILTER = false>
+using HnswLast = std::conditional_t<FILTER, HnswFiltered<HnswLastPlain<T, SCAN>>, HnswLastPlain<T, SCAN>>;
 
 // ELEMQ (sparse rows only): the queries are element slots of the mirror, the build's form of a sparse walk.  An
 // instantiation of its own, so that the plain sparse walks compile to what they were
-template <typename T, int METRIC, bool SCAN = false, bool ELEMQ = false>
+// FILTER (with SCAN only): a query stays with its workgroup batch after batch -- walk or drain, filter, emit -- until it
+// has its k rows, is exhausted or overflows (pgv_hnsw_scan_filtered); see the query loop below
+template <typename T, int METRIC, bool SCAN = false, bool ELEMQ = false, bool FILTER = false>
 __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
-    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter, HnswLast<T, SCAN> last) {
+    HnswDev g, HnswRun run, uint32_t *__restrict__ bitmaps, int words, int *__restrict__ qcounter,
+    HnswLast<T, SCAN, FILTER> last) {
+    static_assert(!FILTER || (SCAN && !ELEMQ), "a filtered scan is a scan");
     const HnswSparse none{};
     const HnswSparse &sp = sparse_extras(last, none);  // a sparse walk's extras (a dense or bit scan has none)
     const auto &ss = last;                             // a resumable scan's state (SCAN)
@@ -717,6 +742,86 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         }
         jaccard_out(ids, cnt, out_dist + row);
     };
+    // A filtered scan's walk of the staged query (FILTER): into the graph and down its layers, or -- a resumed batch, W
+    // laid out by the entry step -- layer 0 alone.  Leaves W in buffer sc.cur, sc.wn entries; counts so->tuples into
+    // `scored`.  The query loop's own layer loop below, less what only a build asks for; that one stays written out where
+    // it is: with both paths calling one lambda every older instantiation spilled a different number of SGPRs and two of
+    // them changed their VGPR count.
+    auto walk_layers = [&](int qi, bool resumed, int64_t &scored) __attribute__((always_inline)) {
+        if constexpr (FILTER) {
+            if (!resumed) enter_graph();
+            for (int lc = resumed ? 0 : g.levels[g.entry]; lc >= 0; lc--) {
+                const int ef_l = lc == 0 ? ef : 1;
+                const int lm = lc == 0 ? lm0 : g.m;
+                if (!resumed) reset_visited();  // (a resumed batch keeps its visited set: initVisited == false)
+                if (tid == 0) sc.tn = sc.tread = 0;
+                __syncthreads();
+                if (lc == 0 && !resumed) scored += sc.wn;  // its entry points count too (src/hnswutils.c:872-873)
+                for (;;) {
+                    if (wave == 0) next_candidate(lc, lm);
+                    __syncthreads();
+                    const int nb = sc.nb;
+                    if (sc.cand < 0) break;
+                    if (nb == 0) {
+                        __syncthreads();
+                        continue;
+                    }
+                    if (lc == 0) scored += nb;
+                    score_batch(nb);
+                    __syncthreads();
+                    if (wave == 0) merge_batch(qi, lc, ef_l, nb);
+                    __syncthreads();
+                }
+                __syncthreads();
+            }
+        }
+    };
+    // A filtered scan's step after each walk or drain (FILTER; hnswgettuple's inner loop, src/hnswscan.c:293-327): W's
+    // live buffer nearest first through strict_order and the query's keep bitmap, the survivors into the output row at
+    // `emitted`, k rows at the most -- the rest of the batch is dropped.  Wavefront 0 compacts them into W's other buffer,
+    // which is dead between two batches; all 256 threads write them out.  A batch is ascending, so an entry passes
+    // strict_order exactly when it is not nearer than the last key that passed before the batch, and the batch's last key
+    // is the next such key unless nothing passed.  All 256 threads call, after a barrier; ends with one.
+    // `emitted` is the same register in every thread: wavefront 0 publishes only the batch's count, sc.got, which nobody
+    // reads before the barrier behind it and nobody writes again before the next batch's, and every thread adds it.
+    auto filter_batch = [&](int qi, const uint32_t *keep, int &emitted) __attribute__((always_inline)) {
+        if constexpr (FILTER) {
+            const int cur = sc.cur, wn = sc.wn, e0 = emitted;
+            uint32_t *dk = wk + (cur ^ 1) * ef, *di = wi + (cur ^ 1) * ef;
+            if (wave == 0) {
+                const uint32_t *ck = wk + cur * ef, *ci = wi + cur * ef;
+                const uint32_t prev = sc.prev;
+                const int room = k - e0;
+                int cnt = 0;
+                for (int base = 0; base < wn && cnt < room; base += kWave) {
+                    const int j = base + lane < wn ? base + lane : wn - 1;  // never predicate a load
+                    const uint32_t key = ck[j], id = ci[j] & ~kExpanded;
+                    bool ok = base + lane < wn && (!ss.strict || key >= prev);
+                    if (keep) ok = ok && ((keep[id >> 5] >> (id & 31)) & 1u);
+                    const int slot = wave_append(ok, lane, cnt);
+                    if (ok && slot < room) {
+                        dk[slot] = key;
+                        di[slot] = id;
+                    }
+                }
+                if (lane == 0) {
+                    sc.got = cnt < room ? cnt : room;
+                    if (ss.strict && wn > 0 && ck[wn - 1] > prev) sc.prev = ck[wn - 1];
+                    sc.batches = sc.batches + 1;
+                }
+            }
+            __syncthreads();
+            const int got = sc.got;
+            const int64_t at = (int64_t)qi * k + e0;
+            for (int j = tid; j < got; j += kHnswThreads) {
+                out_elem[at + j] = (int64_t)di[j];
+                if constexpr (!kJaccard) out_dist[at + j] = key_to_float(dk[j]);
+            }
+            jaccard_out(di, got, out_dist + at);  // (the kept elements meet the query once more: it is in LDS)
+            emitted = e0 + got;
+            __syncthreads();
+        }
+    };
 
     for (;;) {
         if (tid == 0) sc.query = atomicAdd(qcounter, 1);
@@ -725,6 +830,69 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         if (qi >= nq) return;
 
         int64_t scored = 0;
+        // A filtered scan's query (FILTER) is hnswgettuple's loop, start to end: a batch -- the first walk, a resumed one,
+        // or with so->tuples at max_scan_tuples the entry step alone -- then the filter, until k rows are out, the pool
+        // is empty or it has overflowed.  The query is staged once; its state is written once, when it stops, with the
+        // fields a batch of pgv_hnsw_scan_next writes.  Every batch but the first takes at least one entry out of the
+        // pool and the walks mark new elements visited: a query ends after n elements' worth of work at the most.
+        if constexpr (FILTER) {
+            bitmap = bitmaps + (size_t)qi * words;
+            const HnswScanQuery st = ss.qs[qi];
+            const bool wanted = (!ss.want || ss.want[qi]) && !(st.flags & kScanOverflow) && g.entry >= 0;
+            bool started = st.flags & kScanStarted, over = false;
+            int emitted = 0;
+            scored = st.tuples;
+            if (tid == 0) {
+                sc.pool_n = st.pool_n;
+                sc.prev = 0u;
+                sc.batches = 0;
+            }
+            if (wanted) stage_query(qi);
+            __syncthreads();
+            if (wanted) {
+                const uint32_t *keep = ss.keep ? ss.keep + (int64_t)qi * ss.keep_stride : nullptr;
+                uint2 *pool = ss.pool + (size_t)qi * ss.cap;
+                for (;;) {
+                    const int pn = sc.pool_n;
+                    if (emitted >= k || (started && pn == 0)) break;
+                    const bool drain = started && scored >= ss.max_tuples;
+                    if (started) {
+                        const int take = pn < ef ? pn : ef;
+                        scan_entry_step(pool, pn, take, wk, wi, wk + ef, wi + ef, *reinterpret_cast<ScanEntryLds *>(smem + at.entry));
+                        if (tid == 0) {
+                            sc.wn = take;
+                            sc.cur = 0;
+                            sc.pool_n = pn - take;
+                        }
+                        __syncthreads();
+                    }
+                    if (!drain) walk_layers(qi, started, scored);
+                    started = true;
+                    filter_batch(qi, keep, emitted);
+                    if (sc.pool_n > ss.cap) {  // the pool overflowed in this walk: the query ends flagged
+                        over = true;
+                        break;
+                    }
+                }
+            }
+            const int em = emitted;
+            const int64_t row = (int64_t)qi * k;
+            for (int j = em + tid; j < k; j += kHnswThreads) {
+                out_elem[row + j] = -1;
+                out_dist[row + j] = __uint_as_float(0x7f800000u);
+            }
+            if (tid == 0) {
+                const int pn = over ? ss.cap : sc.pool_n;
+                ss.out_count[qi] = em;
+                if (out_scored) out_scored[qi] = scored;
+                if (ss.out_batches) ss.out_batches[qi] = sc.batches;
+                if (ss.out_left) ss.out_left[qi] = pn;
+                if (sc.batches > 0) ss.qs[qi] = {scored, pn, kScanStarted | (over ? kScanOverflow : 0)};
+                if (over) atomicCAS(ss.overflow, 0, qi + 1);
+            }
+            __syncthreads();
+            continue;
+        }
         // A scan's query (SCAN): not wanted, exhausted, over an empty index or flagged -> no batch, its state stays as it
         // is.  A started one resumes: the entry step lays the pool's nearest into W, the visited set carries over, the
         // upper layers are not walked again (ResumeScanItems, src/hnswscan.c:61-87).  A drain is the entry step alone.
@@ -863,7 +1031,8 @@ int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *
                   int *counter, const Last &sp = Last{}) {
     constexpr bool kSparse = std::is_same_v<T, SparseRow>;
     constexpr bool kScan = std::is_base_of_v<HnswScanDev, Last>;
-    static_assert(std::is_same_v<Last, HnswLast<T, kScan>>, "the kernel's last argument for these rows");
+    constexpr bool kFilter = kIsFiltered<Last>;
+    static_assert(std::is_same_v<Last, HnswLast<T, kScan, kFilter>>, "the kernel's last argument for these rows");
     size_t lds = HnswLds((size_t)g.nvec * sizeof(Raw16), run.ef, g.m, kScan).total;  // the layout the kernel carves
     if constexpr (kSparse) {
         const HnswSparse none{};
@@ -872,7 +1041,7 @@ int launch_hnsw_t(pgv_ctx *ctx, const HnswDev &g, const HnswRun &run, uint32_t *
     } else if (lds > kHnswLdsLimit) {
         PGV_FAIL(PGV_ERR_ARG, "hnsw search: ef %d / m %d need %zu bytes of LDS", run.ef, g.m, lds);
     }
-    auto kern = hnsw_search_kernel<T, METRIC, kScan, ELEMQ>;
+    auto kern = hnsw_search_kernel<T, METRIC, kScan, ELEMQ, kFilter>;
     PGV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kHnswThreads), lds, ctx->stream, g, run, bitmaps, words, counter, sp);
     PGV_HIP(hipGetLastError());
@@ -1154,7 +1323,7 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
         sp.prefetch = prefetch != 0;
     }
     if (scan) {  // a batch of a resumable scan, or its drain: the walk's SCAN form over the scan's own state
-        if (a.qids || !a.out_elem || !a.out_dist || a.k != a.ef || (v.sparse() && !a.sparse_queries.ptr))
+        if (a.qids || !a.out_elem || !a.out_dist || (a.k != a.ef && !scan->filtered) || (v.sparse() && !a.sparse_queries.ptr))
             PGV_FAIL(PGV_ERR_ARG, "hnsw scan: query vectors (sparse rows: sparse queries), not element slots; k = ef");
         if (v.sparse() && a.max_q_nnz > kSparseMaxNnz)
             PGV_FAIL(PGV_ERR_DIMS, "hnsw scan: a query of %d stored elements", a.max_q_nnz);
@@ -1168,6 +1337,34 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
         sd.out_left = scan->out_left;
         sd.overflow = scan->overflow;
         sd.drain = scan->drain ? 1 : 0;
+        if (scan->filtered) {  // hnswgettuple's whole loop per query: the FILTER forms, the scan's state wrapped
+            if (scan->drain || a.k < 1) PGV_FAIL(PGV_ERR_ARG, "hnsw filtered scan: k >= 1, and it drains by itself");
+            auto wrap = [&](auto base) {
+                HnswFiltered<decltype(base)> f;
+                static_cast<decltype(base) &>(f) = base;
+                f.keep = scan->keep;
+                f.keep_stride = scan->keep_stride;
+                f.max_tuples = scan->max_scan_tuples;
+                f.strict = scan->strict ? 1 : 0;
+                f.out_batches = scan->out_batches;
+                return f;
+            };
+            if (v.sparse()) {
+                const auto f = wrap(sd);
+                using F = HnswFiltered<HnswSparseScan>;
+                switch (v.metric) {
+                    case PGV_L2SQ: return launch_hnsw_t<SparseRow, 0, F>(ctx, g, run, bitmaps, words, grid, counter, f);
+                    case PGV_NEG_IP: return launch_hnsw_t<SparseRow, 1, F>(ctx, g, run, bitmaps, words, grid, counter, f);
+                    case PGV_L1: return launch_hnsw_t<SparseRow, 2, F>(ctx, g, run, bitmaps, words, grid, counter, f);
+                    default: PGV_FAIL(PGV_ERR_ARG, "unknown metric %d", (int)v.metric);
+                }
+            }
+            const auto f = wrap(static_cast<const HnswScanDev &>(sd));
+            return dispatch_rows(v, [&](auto *tp, auto mc) {
+                return launch_hnsw_t<std::remove_pointer_t<decltype(tp)>, decltype(mc)::value, HnswFiltered<HnswScanDev>>(
+                    ctx, g, run, bitmaps, words, grid, counter, f);
+            });
+        }
         if (v.sparse()) switch (v.metric) {
                 case PGV_L2SQ: return launch_hnsw_t<SparseRow, 0, HnswSparseScan>(ctx, g, run, bitmaps, words, grid, counter, sd);
                 case PGV_NEG_IP: return launch_hnsw_t<SparseRow, 1, HnswSparseScan>(ctx, g, run, bitmaps, words, grid, counter, sd);

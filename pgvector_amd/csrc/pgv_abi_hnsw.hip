@@ -1374,9 +1374,21 @@ int pgv_hnsw_scan_begin_sparse(pgv_hnsw *h, const int64_t *q_ptr, const int32_t 
     return hnsw_scan_publish(s, who, PGV_OK, e, sbytes, out);
 }
 
-// one launch over the scan's state: a batch of every wanted query (ef = the scan's) or the drain of their pools
+// what pgv_hnsw_scan_filtered hands a launch on top: hnswgettuple's loop runs inside it
+struct HnswScanFilter {
+    const uint32_t *keep;
+    int64_t keep_stride;
+    int k;
+    int64_t max_scan_tuples;
+    bool strict;
+    int32_t *out_batches;
+};
+
+// one launch over the scan's state: a batch of every wanted query (ef = the scan's), the drain of their pools, or -- with
+// `filter` -- every wanted query's whole filtered scan (out_elem / out_dist are then [nq x filter->k])
 static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool drain, int64_t *out_elem, float *out_dist,
-                            int32_t *out_count, int64_t *out_scored, int64_t *out_left) {
+                            int32_t *out_count, int64_t *out_scored, int64_t *out_left,
+                            const HnswScanFilter *filter = nullptr) {
     pgv_hnsw *h = s->h;
     pgv_ctx *ctx = h->ctx;
     hnsw_view_refresh(h);
@@ -1385,9 +1397,16 @@ static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool 
     PGV_TRY(hnsw_graph_acquire(h));
     const void *w_dev = nullptr;
     if (want) PGV_TRY(stage_flat(ctx, want, (size_t)s->nq, ctx->idx_stage, &w_dev));
-    OutArg oe, od, oc, os, ol;
-    PGV_TRY(oe.init(out_elem, sizeof(int64_t) * (size_t)s->nq * ef, ctx->out_stage2));
-    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)s->nq * ef, ctx->out_stage));
+    const int width = filter ? filter->k : ef;  // of an output row
+    const void *keep_dev = nullptr;
+    if (filter && filter->keep) {
+        const size_t kwords = filter->keep_stride ? (size_t)s->nq * (size_t)filter->keep_stride : (size_t)(s->words - 1);
+        PGV_TRY(stage_flat(ctx, filter->keep, sizeof(uint32_t) * kwords, ctx->rows_stage, &keep_dev));
+    }
+    OutArg oe, od, oc, os, ol, ob;
+    PGV_TRY(oe.init(out_elem, sizeof(int64_t) * (size_t)s->nq * width, ctx->out_stage2));
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)s->nq * width, ctx->out_stage));
+    PGV_TRY(ob.init(filter ? filter->out_batches : nullptr, sizeof(int32_t) * (size_t)s->nq, ctx->plan_b));
     PGV_TRY(oc.init(out_count, sizeof(int32_t) * (size_t)s->nq, ctx->sel_a));
     PGV_TRY(os.init(out_scored, sizeof(int64_t) * (size_t)s->nq, ctx->sel_b));
     PGV_TRY(ol.init(out_left, sizeof(int64_t) * (size_t)s->nq, ctx->plan_a));
@@ -1401,7 +1420,7 @@ static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool 
     }
     a.nq = s->nq;
     a.ef = ef;
-    a.k = ef;
+    a.k = width;
     a.out_elem = oe.as<int64_t>();
     a.out_dist = od.as<float>();
     a.out_scored = out_scored ? os.as<int64_t>() : nullptr;
@@ -1414,6 +1433,14 @@ static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool 
     sa.out_left = out_left ? ol.as<int64_t>() : nullptr;
     sa.overflow = reinterpret_cast<int *>(static_cast<char *>(s->qstate) + (size_t)s->nq * kHnswScanQueryBytes);
     sa.drain = drain;
+    if (filter) {
+        sa.filtered = true;
+        sa.keep = static_cast<const uint32_t *>(keep_dev);
+        sa.keep_stride = filter->keep_stride;
+        sa.max_scan_tuples = filter->max_scan_tuples;
+        sa.strict = filter->strict;
+        sa.out_batches = ob.as<int32_t>();
+    }
     // one workgroup per query (an unwanted or exhausted one's only writes its empty outputs): each has its own visited
     // set, so nothing caps the grid but the queries
     const int grid = s->nq < ctx->num_cus * 8 ? s->nq : ctx->num_cus * 8;
@@ -1427,6 +1454,7 @@ static int hnsw_scan_launch(pgv_hnsw_scan *s, const uint8_t *want, int ef, bool 
     PGV_TRY(oc.finish(ctx, &need));
     PGV_TRY(os.finish(ctx, &need));
     PGV_TRY(ol.finish(ctx, &need));
+    PGV_TRY(ob.finish(ctx, &need));
     PGV_HIP(hipStreamSynchronize(ctx->stream));
     if (over > 0) {
         s->failed_query = over - 1;
@@ -1448,6 +1476,22 @@ int pgv_hnsw_scan_drain(pgv_hnsw_scan *s, const uint8_t *want, int count, int64_
     if (count < 1 || count > 1000) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_drain: count must be 1..1000, got %d", count);
     if (s->failed_query >= 0) return hnsw_scan_overflowed(s);
     return hnsw_scan_launch(s, want, count, true, out_elem, out_dist, out_count, nullptr, nullptr);
+}
+
+int pgv_hnsw_scan_filtered(pgv_hnsw_scan *s, const uint8_t *want, const uint32_t *keep, int64_t keep_stride, int k,
+                           int64_t max_scan_tuples, int strict, int64_t *out_elem, float *out_dist, int32_t *out_count,
+                           int64_t *out_scored, int32_t *out_batches, int64_t *out_left) {
+    if (!s || !out_elem || !out_dist || !out_count) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_filtered: scan/out is NULL");
+    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_filtered: k must be 1..4096, got %d", k);
+    if (max_scan_tuples < 1)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_filtered: max_scan_tuples must be >= 1, got %lld", (long long)max_scan_tuples);
+    const int64_t kwords = s->words - 1;  // (n + 31) / 32 of the mirror the scan began on
+    if (keep_stride != 0 && keep_stride < kwords)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_scan_filtered: keep_stride %lld is below the %lld words of one bitmap over the mirror",
+                 (long long)keep_stride, (long long)kwords);
+    if (s->failed_query >= 0) return hnsw_scan_overflowed(s);
+    const HnswScanFilter f{keep, keep ? keep_stride : 0, k, max_scan_tuples, strict != 0, out_batches};
+    return hnsw_scan_launch(s, want, s->ef, false, out_elem, out_dist, out_count, out_scored, out_left, &f);
 }
 
 void pgv_hnsw_scan_end(pgv_hnsw_scan *s) {

@@ -682,6 +682,14 @@ struct HnswScanArgs {
     int64_t *out_left = nullptr;       // [nq] or NULL
     int *overflow = nullptr;           // zero before the first batch; 1 + a query whose pool overflowed
     bool drain = false;
+    // pgv_hnsw_scan_filtered: hnswgettuple's whole loop per query in this one launch (then k is the width of the output
+    // rows, 1..4096, and need not be ef; drain stays false: the loop drains by itself once so->tuples >= max_scan_tuples)
+    bool filtered = false;
+    const uint32_t *keep = nullptr;    // element e: bit e & 31 of word e >> 5; NULL keeps every element
+    int64_t keep_stride = 0;           // words from one query's bitmap to the next; 0: one bitmap shared by all
+    int64_t max_scan_tuples = 0;
+    bool strict = false;
+    int32_t *out_batches = nullptr;    // [nq] or NULL
 };
 int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const HnswSearchArgs &a, uint32_t *bitmaps,
                        int words, int grid, int *counter, const HnswScanArgs *scan = nullptr);
