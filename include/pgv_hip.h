@@ -614,9 +614,11 @@ int			pgv_binary_quantize(pgv_ctx * ctx, pgv_dtype dtype, int dim, const void *r
  * twins src/halfvec.c:605-748): exact kernel values of each query against ITS candidates only.
  *   rows [n x dim], queries [nq x dim], cand [nq x kc] row indexes (-1 = none), k <= kc <= 4096, n < 2^31
  *   out_dist [nq x k] ascending kernel values (L2 squared / -ip / L1, like pgv_exact_topk), out_idx [nq x k] row indexes;
- *   ties by lower candidate position; +inf / -1 padded.
+ *   every real candidate in float8 order (-inf < finite < +inf < NaN: a distance that overflowed is a row like any
+ *   other), ties by lower candidate position, comes before any padding; -1 entries of cand take no part in the order
+ *   and only pad: once a query's real candidates are used up the rest of its row is +inf / -1.
  * The values come from the exact vector-ALU kernel that serves pgv_hnsw_score (no matrix-core expansion).  A candidate
- * of -1 scores +inf whatever the rows hold (and with n == 0 no row is read at all).  A candidate >= n or < -1 is
+ * of -1 contributes no value whatever the rows hold (and with n == 0 no row is read at all).  A candidate >= n or < -1 is
  * PGV_ERR_ARG when cand is host memory; when cand is device memory it is NOT checked and the behaviour is undefined.
  * For cosine the caller passes normalised rows with PGV_NEG_IP, as elsewhere in this ABI.
  */

@@ -188,30 +188,63 @@ __global__ __launch_bounds__(256) void binary_quantize_kernel(const U *__restric
     }
 }
 
-// pgv_rerank: candidate lists [nq x kc] -> the pairs score_gather_kernel reads.  "none" (-1) scores row 0 of the pair's
-// query; rerank_mask_kernel overwrites the value
-__global__ void rerank_pairs_kernel(const int64_t *__restrict__ cand, int64_t total, int kc, int32_t *__restrict__ slot,
-                                    int32_t *__restrict__ query_of) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int64_t c = cand[i];
-    slot[i] = c < 0 ? 0 : (int32_t)c;
-    query_of[i] = (int32_t)(i / kc);
+// pgv_rerank: candidate lists [nq x kc] -> the pairs score_gather_kernel reads.  One workgroup per query packs the
+// query's real candidates to the front of its row of `packed`, in their order (a stable compaction: thread t owns
+// the t-th run of ceil(kc / 256) entries, an exclusive scan over the runs' counts places them); the tail of the row is
+// -1.  A "none" scores row 0 of the pair's query; rerank_mask_kernel overwrites the value.
+constexpr int kRerankThreads = 256;
+__global__ __launch_bounds__(kRerankThreads) void rerank_pairs_kernel(const int64_t *__restrict__ cand, int kc,
+                                                                      int64_t *__restrict__ packed, int32_t *__restrict__ slot,
+                                                                      int32_t *__restrict__ query_of) {
+    __shared__ int scan[kRerankThreads];
+    const int q = blockIdx.x, t = threadIdx.x;
+    const int64_t base = (int64_t)q * kc;
+    const int per = (kc + kRerankThreads - 1) / kRerankThreads;
+    const int lo = t * per < kc ? t * per : kc, hi = lo + per < kc ? lo + per : kc;
+    int mine = 0;
+    for (int i = lo; i < hi; i++) mine += cand[base + i] >= 0;
+    scan[t] = mine;
+    __syncthreads();
+    for (int d = 1; d < kRerankThreads; d <<= 1) {
+        const int add = t >= d ? scan[t - d] : 0;
+        __syncthreads();
+        scan[t] += add;
+        __syncthreads();
+    }
+    const int real = scan[kRerankThreads - 1];
+    int at = scan[t] - mine;
+    for (int i = lo; i < hi; i++) {
+        const int64_t c = cand[base + i];
+        if (c >= 0) {
+            packed[base + at] = c;
+            slot[base + at] = (int32_t)c;
+            at++;
+        }
+    }
+    for (int i = real + t; i < kc; i += kRerankThreads) {
+        packed[base + i] = -1;
+        slot[base + i] = 0;
+    }
+    for (int i = t; i < kc; i += kRerankThreads) query_of[base + i] = q;
 }
 
-__global__ void rerank_mask_kernel(const int64_t *__restrict__ cand, int64_t total, float *__restrict__ vals) {
+// the tail of a packed row takes part in the selection as NaN: float8 order puts NaN last and ties go to the lower
+// position, so every real candidate -- a +inf or NaN one included -- is selected before any of the tail
+__global__ void rerank_mask_kernel(const int64_t *__restrict__ packed, int64_t total, float *__restrict__ vals) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < total && cand[i] < 0) vals[i] = INFINITY;
+    if (i < total && packed[i] < 0) vals[i] = __uint_as_float(0x7fc00000u);
 }
 
-// position inside a query's candidate list -> the row index the list holds there
-__global__ void rerank_map_kernel(const int64_t *__restrict__ cand, int nq, int kc, int k, const int64_t *__restrict__ pos,
-                                  int64_t *__restrict__ out_idx) {
+// position inside a query's packed candidate row -> the row index it holds there; a selected tail entry becomes the
+// padding pgv_rerank promises (+inf / -1)
+__global__ void rerank_map_kernel(const int64_t *__restrict__ packed, int nq, int kc, int k, const int64_t *__restrict__ pos,
+                                  int64_t *__restrict__ out_idx, float *__restrict__ out_dist) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)nq * k) return;
     const int64_t p = pos[i];
-    int64_t c = p < 0 ? -1 : cand[(i / k) * kc + p];
-    out_idx[i] = c < 0 ? -1 : c;
+    const int64_t c = p < 0 ? -1 : packed[(i / k) * kc + p];
+    out_idx[i] = c;
+    if (c < 0) out_dist[i] = INFINITY;
 }
 
 
@@ -442,27 +475,28 @@ int launch_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *r
     return PGV_OK;
 }
 
-int launch_rerank_pairs(pgv_ctx *ctx, const int64_t *cand, int64_t total, int kc, int32_t *slot, int32_t *query_of) {
-    if (total <= 0) return PGV_OK;
-    hipLaunchKernelGGL(rerank_pairs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, cand, total, kc,
-                       slot, query_of);
+int launch_rerank_pairs(pgv_ctx *ctx, const int64_t *cand, int nq, int kc, int64_t *packed, int32_t *slot, int32_t *query_of) {
+    if (nq <= 0) return PGV_OK;
+    hipLaunchKernelGGL(rerank_pairs_kernel, dim3((unsigned)nq), dim3(kRerankThreads), 0, ctx->stream, cand, kc, packed, slot,
+                       query_of);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-int launch_rerank_mask(pgv_ctx *ctx, const int64_t *cand, int64_t total, float *vals) {
+int launch_rerank_mask(pgv_ctx *ctx, const int64_t *packed, int64_t total, float *vals) {
     if (total <= 0) return PGV_OK;
-    hipLaunchKernelGGL(rerank_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, cand, total,
+    hipLaunchKernelGGL(rerank_mask_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, packed, total,
                        vals);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }
 
-int launch_rerank_map(pgv_ctx *ctx, const int64_t *cand, int nq, int kc, int k, const int64_t *pos, int64_t *out_idx) {
+int launch_rerank_map(pgv_ctx *ctx, const int64_t *packed, int nq, int kc, int k, const int64_t *pos, int64_t *out_idx,
+                      float *out_dist) {
     const int64_t total = (int64_t)nq * k;
     if (total <= 0) return PGV_OK;
-    hipLaunchKernelGGL(rerank_map_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, cand, nq, kc, k,
-                       pos, out_idx);
+    hipLaunchKernelGGL(rerank_map_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, packed, nq, kc, k,
+                       pos, out_idx, out_dist);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

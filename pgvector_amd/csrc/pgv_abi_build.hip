@@ -349,9 +349,10 @@ int pgv_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *rows
     return sync_if(ctx, need);
 }
 
-// The outer ORDER BY of the two-stage query: score_gather_kernel (pgv_hnsw_score's exact per-pair kernel) over the
-// nq x kc (candidate, query) pairs, +inf for the "none" entries, launch_topk_segments over segments of kc (ties to the
-// lower position), positions back to row indexes.
+// The outer ORDER BY of the two-stage query: each query's real candidates packed to the front of its row (stably),
+// score_gather_kernel (pgv_hnsw_score's exact per-pair kernel) over the nq x kc (candidate, query) pairs, NaN for the
+// "none" tail, launch_topk_segments over segments of kc (float8 order, ties to the lower position: every real candidate,
+// +inf and NaN ones included, before any "none"), positions back to row indexes and the tail to +inf / -1.
 int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const void *queries, int nq, const void *rows,
                int64_t n, const int64_t *cand, int kc, int k, float *out_dist, int64_t *out_idx) {
     if (!ctx || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "pgv_rerank: ctx/out_dist/out_idx is NULL");
@@ -379,20 +380,20 @@ int pgv_rerank(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, int dim, const 
     OutArg od, oi;
     PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
     PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
-    // plan_a: slot[total] | query_of[total]   plan_b: values[total]   plan_c: selected positions [nq x k]
-    PGV_TRY(ctx->plan_a.ensure(sizeof(int32_t) * 2 * (size_t)total));
+    // plan_a: packed[total] | slot[total] | query_of[total]   plan_b: values[total]   plan_c: selected positions [nq x k]
+    PGV_TRY(ctx->plan_a.ensure((sizeof(int64_t) + sizeof(int32_t) * 2) * (size_t)total));
     PGV_TRY(ctx->plan_b.ensure(sizeof(float) * (size_t)total));
     PGV_TRY(ctx->plan_c.ensure(sizeof(int64_t) * (size_t)nq * k));
-    int32_t *slot = ctx->plan_a.as<int32_t>(), *query_of = slot + total;
+    int64_t *packed = ctx->plan_a.as<int64_t>();
+    int32_t *slot = reinterpret_cast<int32_t *>(packed + total), *query_of = slot + total;
     float *vals = ctx->plan_b.as<float>();
     int64_t *pos = ctx->plan_c.as<int64_t>();
-    if (n > 0) {
-        PGV_TRY(launch_rerank_pairs(ctx, cd, total, kc, slot, query_of));
+    PGV_TRY(launch_rerank_pairs(ctx, cd, nq, kc, packed, slot, query_of));
+    if (n > 0)
         PGV_TRY(launch_score_gather(ctx, RowsView{r_dev, n, g, row_kind(dtype), metric}, q_dev, slot, query_of, total, vals));
-    }
-    PGV_TRY(launch_rerank_mask(ctx, cd, total, vals));  // (n == 0: every entry is "none")
+    PGV_TRY(launch_rerank_mask(ctx, packed, total, vals));  // (n == 0: every entry is "none")
     PGV_TRY(launch_topk_segments(ctx, vals, nullptr, nq, kc, k, od.as<float>(), pos));
-    PGV_TRY(launch_rerank_map(ctx, cd, nq, kc, k, pos, oi.as<int64_t>()));
+    PGV_TRY(launch_rerank_map(ctx, packed, nq, kc, k, pos, oi.as<int64_t>(), od.as<float>()));
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     PGV_TRY(oi.finish(ctx, &need));

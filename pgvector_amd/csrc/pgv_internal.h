@@ -610,11 +610,14 @@ int launch_bit_centers(pgv_ctx *ctx, const int32_t *sums, const int32_t *counts,
                        const int32_t *refill_row, const uint8_t *refill, void *centers);
 // rows [n x dim] tightly packed -> out_bits [n x (dim + 7) / 8], bit i = x[i] > 0, first element in the top bit
 int launch_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *rows, int64_t n, void *out_bits);
-// pgv_rerank around launch_score_gather and launch_topk_segments: cand [nq x kc] -> (slot, query_of) of the pairs
-// (-1: row 0); +inf over the values of the -1 entries; selected positions -> cand entries
-int launch_rerank_pairs(pgv_ctx *ctx, const int64_t *cand, int64_t total, int kc, int32_t *slot, int32_t *query_of);
-int launch_rerank_mask(pgv_ctx *ctx, const int64_t *cand, int64_t total, float *vals);
-int launch_rerank_map(pgv_ctx *ctx, const int64_t *cand, int nq, int kc, int k, const int64_t *pos, int64_t *out_idx);
+// pgv_rerank around launch_score_gather and launch_topk_segments: cand [nq x kc] -> packed [nq x kc], each query's real
+// candidates in front in their order and -1 behind them, and the (slot, query_of) of the packed pairs (-1: row 0); NaN
+// over the values of the -1 entries, so that the selection takes every real candidate first; selected positions ->
+// packed entries, +inf / -1 where the selection reached the -1 tail
+int launch_rerank_pairs(pgv_ctx *ctx, const int64_t *cand, int nq, int kc, int64_t *packed, int32_t *slot, int32_t *query_of);
+int launch_rerank_mask(pgv_ctx *ctx, const int64_t *packed, int64_t total, float *vals);
+int launch_rerank_map(pgv_ctx *ctx, const int64_t *packed, int nq, int kc, int k, const int64_t *pos, int64_t *out_idx,
+                      float *out_dist);
 
 // kernels_sparse.hip: the sparsevec distances of a tile of queries against every row, both CSR on the device
 struct SparseCsr {
