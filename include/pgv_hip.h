@@ -1220,6 +1220,58 @@ int			pgv_hnsw_score_groups(pgv_hnsw * h, const int32_t *ids, const int64_t *ids
 int			pgv_hnsw_update_graph(pgv_hnsw * h, int32_t entry, const int32_t *elements, int nupd,
 								  const int64_t *tuple_offsets, const int32_t *tuples);
 
+/* ------------------------------------------------------ HNSW vacuum side */
+
+/*
+ * Dead elements of a mirror: bit e & 31 of word e >> 5 says that element e has heap TIDs (heaptidsLength != 0: what
+ * CountElement, src/hnswutils.c:715-728, and RemoveElements, :1236-1259, look at while hnswvacuum repairs the graph,
+ * src/hnswvacuum.c:379-502).  live [(n + 31) / 32] words, host or device; any other word count is PGV_ERR_ARG before any
+ * launch; NULL: every element is live again (words is ignored).  The bitmap is copied to the device, kept with the
+ * mirror and seen by its views (pgv_hnsw_share), whichever of them set it.  The call waits for its own handle's stream
+ * and then replaces the bitmap: pgv_hnsw_repair_neighbors calls through OTHER views of the mirror must have returned
+ * before it (each ends synchronized), as searches must before pgv_hnsw_update_graph.
+ *
+ * ONLY pgv_hnsw_repair_neighbors reads it.  pgv_hnsw_search, pgv_hnsw_scan_*, the build-side entries and every other
+ * entry ignore it and behave bit for bit as on a mirror on which nothing was ever marked dead: like the reference's
+ * HnswSearchLayer with skipElement == NULL they walk through dead elements, and dropping those from the answers is the
+ * caller's filter (pgv_hnsw_scan_filtered's keep bitmap has this very layout).
+ *
+ * Dense mirrors only (pgv_hnsw_upload / pgv_hnsw_upload_payload and their views, fp32 and fp16, every metric): on a bit,
+ * Jaccard, sparse or imported mirror pgv_hnsw_set_live and pgv_hnsw_repair_neighbors return PGV_ERR_ARG before any launch
+ * and the text names the mirror kind.  pgv_hnsw_live_count: the bits set among the n elements (n while no bitmap is
+ * set); -1 for a NULL handle and for those mirror kinds (pgv_last_error names the kind).
+ */
+int			pgv_hnsw_set_live(pgv_hnsw * h, const uint32_t *live, int64_t words);
+int64_t		pgv_hnsw_live_count(const pgv_hnsw * h);
+
+/*
+ * HnswFindElementNeighbors(..., existing = true) (src/hnswutils.c:1280-1357), what RepairGraphElement
+ * (src/hnswvacuum.c:226-274) runs for an element with a deleted neighbor, for a batch of LINKED elements of the mirror
+ * against the graph as it stands:
+ *   - each element's level is its own; layers above it are descended with ef = 1 (:1306-1310), every layer from
+ *     min(level, entry level) down is searched with ef_construction + 1 (:1316-1317: the element finds itself);
+ *   - the searches count only live elements towards ef (CountElement, :715-728, at :884 and :962): alwaysAdd = wlen < ef,
+ *     otherwise an element is admitted when strictly nearer than W's furthest; a live admission raises wlen, which is
+ *     never lowered, and once wlen > ef evicts W's furthest whatever it is; a dead admission evicts nothing (:908-975).
+ *     W is therefore not bounded by ef;
+ *   - after a layer's search W, nearest first, loses the element itself and the dead (RemoveElements, :1236-1259) and
+ *     goes through SelectNeighbors on the device as in pgv_hnsw_build_neighbors (plain sweep, no cached closer flags);
+ *     the next layer starts from the unstripped W (:1355).
+ * W holds ef_construction + 1 + dead_cap entries in a workgroup's LDS (PGV_ERR_ARG before any launch when that does not
+ * fit; the text has the byte count; pgv_hnsw_repair_dead_cap_max: the largest dead_cap that fits, -1: none).  A search
+ * that would need more stops: out_status[q] = 1, every count of that element is 0, the other elements are unaffected and
+ * no error is raised -- the caller redoes it with a larger dead_cap.  It is never a silently shorter list.  On a graph of
+ * one layer a dead_cap of the number of dead elements cannot overflow; with more layers a dead element evicted on one
+ * layer can be admitted again on the next, so the certain bound is that number times the layers searched.
+ *   elements [nq] (host: checked against the mirror's slots; device: not checked, a slot outside the mirror gets counts 0)
+ *   out_ids / out_dist / out_closer [nq x layer_cap x 2m], out_count [nq x layer_cap]: as pgv_hnsw_build_neighbors
+ *   out_status [nq]; out_pairs (or NULL): pair distances computed
+ */
+int			pgv_hnsw_repair_neighbors(pgv_hnsw * h, const int32_t *elements, int nq, int ef_construction, int layer_cap,
+									  int dead_cap, int32_t *out_ids, float *out_dist, uint8_t *out_closer,
+									  int32_t *out_count, int32_t *out_status, int64_t *out_pairs);
+int			pgv_hnsw_repair_dead_cap_max(const pgv_hnsw * h, int ef_construction);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ class HnswBuilt(C.Structure):
                 ("deferred_updates", C.c_int64), ("phase_secs", C.c_double * 8)]
 
 
+class HnswRepaired(C.Structure):
+    _fields_ = [("nbr", C.c_void_p), ("nbr_total", C.c_int64), ("entry", C.c_int32), ("dead_cap", C.c_int32),
+                ("examined", C.c_int64), ("repaired", C.c_int64), ("batches", C.c_int64), ("overflow_redos", C.c_int64),
+                ("device_pairs", C.c_int64), ("reselections", C.c_int64), ("phase_secs", C.c_double * 4)]
+
+
 class HnswImage(C.Structure):
     _fields_ = [("dtype", C.c_int), ("dim", C.c_int), ("m", C.c_int), ("ef_construction", C.c_int), ("n", C.c_int64),
                 ("entry", C.c_int32), ("vectors", C.c_void_p), ("levels", C.c_void_p), ("nbr_start", C.c_void_p),
@@ -59,6 +65,9 @@ def _load():
     lib.pgv_host_hnsw_build_sparse.argtypes = [P, I, P, P, P, I64, I, I, P, I, C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_built_free.argtypes = [C.POINTER(HnswBuilt)]
     lib.pgv_host_hnsw_built_free.restype = None
+    lib.pgv_host_hnsw_repair.argtypes = [P, I64, P, P, P, C.c_int32, P, I, I, I, I, C.POINTER(HnswRepaired)]
+    lib.pgv_host_hnsw_repaired_free.argtypes = [C.POINTER(HnswRepaired)]
+    lib.pgv_host_hnsw_repaired_free.restype = None
     lib.pgv_host_hnsw_write_index.argtypes = [C.POINTER(Rel), I, I, I, I, I64, P, P, P, P, P, P, C.c_int32]
     lib.pgv_host_hnsw_stage.argtypes = [C.POINTER(Rel), I, C.POINTER(HnswImage)]
     lib.pgv_host_hnsw_image_free.argtypes = [C.POINTER(HnswImage)]
@@ -178,6 +187,31 @@ def hnsw_build(mirror, rows, m, ef_construction, rng=None, max_batch=1024, rows_
            "deferred_updates": b.deferred_updates,
            "phase_secs": dict(zip(("search", "pairs", "select", "records", "update", "patch", "pairlist", "free"), list(b.phase_secs)))}
     lib.pgv_host_hnsw_built_free(C.byref(b))
+    return out
+
+
+def hnsw_repair(mirror, entry, levels, nbr_start, nbr, live_words, m, ef_construction, max_batch=1024, dead_cap=0):
+    """pgv_host_hnsw_repair: hnswvacuum's RepairGraph over the graph (entry, levels, nbr_start, nbr) of the dense mirror
+    `mirror`, live_words the bitmap of pgv_hnsw_set_live.  The mirror is left holding the repaired graph.  Returns a dict
+    with nbr (a numpy copy), entry and the counters."""
+    levels = np.ascontiguousarray(levels, dtype=np.int32)
+    nbr_start = np.ascontiguousarray(nbr_start, dtype=np.int64)
+    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
+    live_words = np.ascontiguousarray(live_words, dtype=np.uint32)
+    n = int(levels.size)
+    if nbr_start.size != n + 1 or nbr.size != int(nbr_start[-1]) or live_words.size != (n + 31) // 32:
+        raise _lib.PgvError(_lib.PGV_ERR_ARG, "hnsw_repair: levels [n], nbr_start [n + 1], nbr [nbr_start[n]], live [(n + 31) // 32]")
+    r = HnswRepaired()
+    host_check(lib.pgv_host_hnsw_repair(mirror.h, n, C.c_void_p(levels.ctypes.data), C.c_void_p(nbr_start.ctypes.data),
+                                        C.c_void_p(nbr.ctypes.data), int(entry), C.c_void_p(live_words.ctypes.data), int(m),
+                                        int(ef_construction), int(max_batch), int(dead_cap), C.byref(r)))
+    total = int(r.nbr_total)
+    out = {"nbr": np.ctypeslib.as_array(C.cast(r.nbr, C.POINTER(C.c_int32)), shape=(max(total, 1),))[:total].copy(),
+           "entry": int(r.entry), "dead_cap": int(r.dead_cap), "examined": int(r.examined), "repaired": int(r.repaired),
+           "batches": int(r.batches), "overflow_redos": int(r.overflow_redos), "device_pairs": int(r.device_pairs),
+           "reselections": int(r.reselections),
+           "phase_secs": dict(zip(("search", "links", "pairs", "patch"), list(r.phase_secs)))}
+    lib.pgv_host_hnsw_repaired_free(C.byref(r))
     return out
 
 

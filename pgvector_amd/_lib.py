@@ -55,6 +55,7 @@ SYMBOLS = [
     "pgv_hnsw_upload_bits_buildable", "pgv_hnsw_buildable_bits",
     "pgv_hnsw_upload_sparse_buildable", "pgv_hnsw_buildable_sparse", "pgv_hnsw_elements",
     "pgv_hnsw_scan_begin_sparse", "pgv_hnsw_scan_filtered",
+    "pgv_hnsw_set_live", "pgv_hnsw_live_count", "pgv_hnsw_repair_neighbors", "pgv_hnsw_repair_dead_cap_max",
 ]
 
 
@@ -200,6 +201,12 @@ def _load():
     lib.pgv_hnsw_search.argtypes = [P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_build_search.argtypes = [P, P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_build_neighbors.argtypes = [P, P, P, I, I, I, P, P, P, P, P]
+    lib.pgv_hnsw_set_live.argtypes = [P, P, I64]
+    lib.pgv_hnsw_live_count.argtypes = [P]
+    lib.pgv_hnsw_live_count.restype = I64
+    lib.pgv_hnsw_repair_neighbors.argtypes = [P, P, I, I, I, I, P, P, P, P, P, C.POINTER(I64)]
+    lib.pgv_hnsw_repair_dead_cap_max.argtypes = [P, I]
+    lib.pgv_hnsw_repair_dead_cap_max.restype = I
     lib.pgv_hnsw_score_pairs.argtypes = [P, P, P, I64, P]
     lib.pgv_hnsw_score_groups.argtypes = [P, P, P, P, P, I, I64, I64, P]
     lib.pgv_hnsw_update_graph.argtypes = [P, C.c_int32, P, I, P, P]

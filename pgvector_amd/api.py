@@ -50,6 +50,14 @@ def as_dtype(x, dtype):
     return np.ascontiguousarray(x, dtype=_NP_OF[dtype])
 
 
+def live_words(mask):
+    """[n] booleans -> the (n + 31) / 32 uint32 words pgv_hnsw_set_live takes: element e is bit e & 31 of word e >> 5"""
+    mask = np.ascontiguousarray(np.asarray(mask).ravel() != 0)
+    padded = np.zeros(((mask.size + 31) // 32) * 32, dtype=bool)
+    padded[:mask.size] = mask
+    return np.ascontiguousarray(np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32))
+
+
 def make_rng(seed=0, next_double=None, next_u32=None, state=None):
     """pgv_rng: the library's own generator (seed) or caller callbacks (C function pointers)"""
     r = PgvRng()
@@ -930,6 +938,7 @@ class Hnsw:
         tuples = np.ascontiguousarray(tuples, dtype=np.int32)
         check(lib.pgv_hnsw_update_graph(self.h, int(entry), ptr(elements), int(elements.size), ptr(tuple_offsets),
                                         ptr(tuples)))
+        self._graph = None
 
     def set_graph(self, m, entry, levels, nbr_start, nbr):
         """the graph a scan walks (pgv_hnsw_set_graph): per element slot its level and neighbor tuple"""
@@ -937,6 +946,56 @@ class Hnsw:
         nbr_start = np.ascontiguousarray(nbr_start, dtype=np.int64) if not _is_torch(nbr_start) else nbr_start
         nbr = np.ascontiguousarray(nbr, dtype=np.int32) if not _is_torch(nbr) else nbr
         check(lib.pgv_hnsw_set_graph(self.h, int(m), int(entry), ptr(levels), ptr(nbr_start), ptr(nbr)))
+        # (host arrays are remembered for repair(); update_graph forgets them)
+        self._graph = None if _is_torch(levels) or _is_torch(nbr_start) or _is_torch(nbr) else (int(entry), levels, nbr_start, nbr)
+
+    def set_live(self, mask):
+        """pgv_hnsw_set_live: mask [n] of booleans, True = the element still has heap TIDs (None: every element is live
+        again).  Only the repair search reads it; searches and scans walk through dead elements as before."""
+        if mask is None:
+            check(lib.pgv_hnsw_set_live(self.h, None, 0))
+            return
+        words = live_words(mask)
+        check(lib.pgv_hnsw_set_live(self.h, ptr(words), int(words.size)))
+
+    def live_count(self):
+        """pgv_hnsw_live_count: the elements not marked dead"""
+        return int(lib.pgv_hnsw_live_count(self.h))
+
+    def repair(self, mask, m, ef_construction, max_batch=1024, graph=None, dead_cap=0):
+        """pgv_host_hnsw_repair: hnswvacuum's RepairGraph after the elements with mask[e] == False lost their heap TIDs.
+        graph = (entry, levels, nbr_start, nbr), host arrays; None: the arrays of the last set_graph / repair of this
+        object.  Returns a dict: the new nbr and entry (levels and nbr_start do not change) and the counters; the mirror
+        holds the repaired graph and the bitmap afterwards.  max_batch = 1 is the reference's serial loop."""
+        from . import _host
+        if graph is None:
+            graph = getattr(self, "_graph", None)
+            if graph is None:
+                raise PgvError(PGV_ERR_STATE, "Hnsw.repair: no graph given and none set through this object (set_graph)")
+        entry, levels, nbr_start, nbr = graph
+        out = _host.hnsw_repair(self, entry, levels, nbr_start, nbr, live_words(mask), m, ef_construction, max_batch, dead_cap)
+        self._graph = (out["entry"], levels, nbr_start, out["nbr"])
+        return out
+
+    def repair_dead_cap_max(self, ef_construction):
+        """the largest dead_cap of repair_neighbors whose W fits a workgroup's LDS (-1: none)"""
+        return int(lib.pgv_hnsw_repair_dead_cap_max(self.h, int(ef_construction)))
+
+    def repair_neighbors(self, elements, m, ef_construction, layer_cap, dead_cap):
+        """pgv_hnsw_repair_neighbors: HnswFindElementNeighbors(existing = true) for a batch of linked elements ->
+        (ids, dist, closer [nq x layer_cap x 2m], count [nq x layer_cap], status [nq] (1: W overflowed dead_cap, counts 0),
+        pair distances computed).  m is the graph's (set_graph)."""
+        elements = np.ascontiguousarray(elements, dtype=np.int32).ravel()
+        nq, stride = int(elements.size), 2 * int(m)
+        ids = np.full((nq, layer_cap, stride), -1, dtype=np.int32)
+        dist = np.zeros((nq, layer_cap, stride), dtype=np.float32)
+        closer = np.zeros((nq, layer_cap, stride), dtype=np.uint8)
+        count = np.zeros((nq, layer_cap), dtype=np.int32)
+        status = np.zeros((nq,), dtype=np.int32)
+        pairs = C.c_int64(0)
+        check(lib.pgv_hnsw_repair_neighbors(self.h, ptr(elements), nq, int(ef_construction), int(layer_cap), int(dead_cap),
+                                            ptr(ids), ptr(dist), ptr(closer), ptr(count), ptr(status), C.byref(pairs)))
+        return ids, dist, closer, count, status, int(pairs.value)
 
     def search(self, queries, ef_search, k, want_scored=True):
         """hnswgettuple's first batch on the device (pgv_hnsw_search) ->

@@ -261,6 +261,7 @@ void pgv_hnsw_free(pgv_hnsw *h) {
         if (h->graph.mem) (void)hipFree(h->graph.mem);
     }
     h->bitmaps.release();
+    h->live.release();
     delete h;
 }
 
@@ -1223,6 +1224,126 @@ int pgv_hnsw_update_graph(pgv_hnsw *h, int32_t entry, const int32_t *elements, i
     PGV_HIP(hipEventRecord(o->graph_ev, ctx->stream));
     o->graph_ev_set = true;
     return PGV_OK;
+}
+
+// ------------------------------------------------------------------ dead elements and hnswvacuum's repair search
+// Which mirrors the repair entries serve: dense ones of this process (pgv_hnsw_upload / _upload_payload and their views).
+static int hnsw_repair_mirror(const pgv_hnsw *h, const char *who) {
+    if (hnsw_is_sparse(h))
+        PGV_FAIL(PGV_ERR_ARG, "%s: a sparse mirror (pgv_hnsw_upload_sparse) has no dead elements and is not repaired: dense mirrors only", who);
+    if (hnsw_is_bits(h) && (int)h->metric == (int)PGV_BIT_JACCARD)
+        PGV_FAIL(PGV_ERR_ARG, "%s: a Jaccard bit mirror (pgv_hnsw_upload_jaccard) has no dead elements and is not repaired: dense mirrors only", who);
+    if (hnsw_is_bits(h))
+        PGV_FAIL(PGV_ERR_ARG, "%s: a bit mirror (pgv_hnsw_upload_bits) has no dead elements and is not repaired: dense mirrors only", who);
+    const pgv_hnsw *o = h->view_of ? h->view_of : h;
+    if (h->imported || o->imported)
+        PGV_FAIL(PGV_ERR_ARG, "%s: an imported mirror (pgv_hnsw_import) is read-only: the process that uploaded it repairs it", who);
+    return PGV_OK;
+}
+
+int pgv_hnsw_set_live(pgv_hnsw *h, const uint32_t *live, int64_t words) {
+    if (!h) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_set_live: handle is NULL");
+    PGV_TRY(hnsw_repair_mirror(h, "pgv_hnsw_set_live"));
+    pgv_hnsw *o = h->view_of ? h->view_of : h;
+    if (!live) {
+        o->live_set = false;
+        o->live_count = 0;
+        return PGV_OK;
+    }
+    const int64_t want = (h->n + 31) / 32;
+    if (words != want)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_set_live: %lld words for %lld elements, expected %lld", (long long)words, (long long)h->n,
+                 (long long)want);
+    pgv_ctx *ctx = h->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+    // no repair search of THIS handle may still be reading the old bitmap; the ones other views of the mirror launched
+    // are the caller's to have finished (they end synchronized, like every search: pgv_hip.h)
+    PGV_HIP(hipStreamSynchronize(ctx->stream));
+    PGV_TRY(o->live.ensure(want > 0 ? (size_t)want * sizeof(uint32_t) : 16));
+    std::vector<uint32_t> host((size_t)want);
+    if (want > 0) {
+        PGV_HIP(hipMemcpy(host.data(), live, (size_t)want * sizeof(uint32_t), hipMemcpyDefault));
+        if (h->n & 31) host[(size_t)want - 1] &= (1u << (h->n & 31)) - 1u;  // bits past the last element say nothing
+        PGV_HIP(hipMemcpyAsync(o->live.p, host.data(), (size_t)want * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        PGV_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    int64_t count = 0;
+    for (uint32_t w : host) count += __builtin_popcount(w);
+    o->live_count = count;
+    o->live_set = true;
+    return PGV_OK;
+}
+
+int64_t pgv_hnsw_live_count(const pgv_hnsw *h) {
+    if (!h) return -1;
+    if (hnsw_repair_mirror(h, "pgv_hnsw_live_count") != PGV_OK) return -1;  // (the text names the mirror kind)
+    const pgv_hnsw *o = h->view_of ? h->view_of : h;
+    return o->live_set ? o->live_count : h->n;
+}
+
+int pgv_hnsw_repair_dead_cap_max(const pgv_hnsw *h, int ef_construction) {
+    if (!h || h->sparse || h->nbits > 0) return -1;
+    const pgv_hnsw *o = h->view_of ? h->view_of : h;
+    if (o->graph.m == 0 || ef_construction < 4 || ef_construction > 1000) return -1;
+    return hnsw_repair_dead_cap_max(h->geom, ef_construction, o->graph.m);
+}
+
+int pgv_hnsw_repair_neighbors(pgv_hnsw *h, const int32_t *elements, int nq, int ef_construction, int layer_cap, int dead_cap,
+                              int32_t *out_ids, float *out_dist, uint8_t *out_closer, int32_t *out_count, int32_t *out_status,
+                              int64_t *out_pairs) {
+    if (!h || !out_ids || !out_dist || !out_closer || !out_count || !out_status)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_repair_neighbors: handle/out is NULL");
+    PGV_TRY(hnsw_repair_mirror(h, "pgv_hnsw_repair_neighbors"));
+    hnsw_view_refresh(h);
+    if (dead_cap < 0 || dead_cap > 0x3fffffff) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_repair_neighbors: dead_cap %d", dead_cap);
+    PGV_TRY(hnsw_build_args(h, "pgv_hnsw_repair_neighbors", nq, ef_construction, layer_cap));
+    // W's capacity: the stride of the candidate lists the selection reads
+    PGV_TRY(hnsw_repair_lds_check("pgv_hnsw_repair_neighbors", h->geom, ef_construction, dead_cap, h->graph.m, nullptr));
+    const int wcap = ef_construction + 1 + dead_cap;
+    if ((size_t)nq * layer_cap > 0x7fffffff / (size_t)wcap) PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_repair_neighbors: batch too large");
+    if (out_pairs) *out_pairs = 0;
+    if (nq == 0) return PGV_OK;
+    if (!elements) PGV_FAIL(PGV_ERR_ARG, "elements is NULL");
+    if (!is_device_ptr(elements))
+        for (int i = 0; i < nq; i++)
+            if (elements[i] < 0 || elements[i] >= h->n)
+                PGV_FAIL(PGV_ERR_ARG, "pgv_hnsw_repair_neighbors: element %d (entry %d of the batch) is not a slot of the mirror",
+                         (int)elements[i], i);
+    pgv_ctx *ctx = h->ctx;
+    pgv_hnsw *o = h->view_of ? h->view_of : h;
+    PGV_HIP(hipSetDevice(ctx->device));
+    PGV_TRY(hnsw_graph_acquire(h));
+    const size_t per = (size_t)nq * layer_cap;
+    const void *e_dev;
+    PGV_TRY(stage_flat(ctx, elements, sizeof(int32_t) * (size_t)nq, ctx->idx_stage, &e_dev));
+    // the candidate lists stay on the device, as the build's: km_b ids | km_c distances | km_d counts; plan_c the levels
+    PGV_TRY(ctx->km_b.ensure(sizeof(int32_t) * per * wcap));
+    PGV_TRY(ctx->km_c.ensure(sizeof(float) * per * wcap));
+    PGV_TRY(ctx->km_d.ensure(sizeof(int32_t) * per));
+    PGV_TRY(ctx->plan_c.ensure(sizeof(int32_t) * (size_t)nq));
+    OutArg os;
+    PGV_TRY(os.init(out_status, sizeof(int32_t) * (size_t)nq, ctx->plan_d));
+    HnswRepairArgs a;
+    a.qids = static_cast<const int32_t *>(e_dev);
+    a.nq = nq;
+    a.ef_construction = ef_construction;
+    a.dead_cap = dead_cap;
+    a.lcap = layer_cap;
+    a.lw_ids = ctx->km_b.as<int32_t>();
+    a.lw_dist = ctx->km_c.as<float>();
+    a.lw_cnt = ctx->km_d.as<int32_t>();
+    a.qlevels = ctx->plan_c.as<int32_t>();
+    a.status = os.as<int32_t>();
+    int words = 0;
+    const int grid = hnsw_search_grid(ctx, nq, h->n, &words);
+    PGV_TRY(h->bitmaps.ensure((size_t)grid * words * sizeof(uint32_t)));
+    PGV_TRY(ctx->counters.ensure(256));
+    PGV_TRY(launch_hnsw_repair(ctx, hnsw_rows(h), h->graph, o->live_set ? o->live.as<uint32_t>() : nullptr, a,
+                               h->bitmaps.as<uint32_t>(), words, grid, ctx->counters.as<int>()));
+    bool need = false;
+    PGV_TRY(os.finish(ctx, &need));
+    return hnsw_select_from(h, a.lw_ids, a.lw_dist, a.lw_cnt, a.qlevels, nq, wcap, layer_cap, out_ids, out_dist, out_closer,
+                            out_count, out_pairs);
 }
 
 // ------------------------------------------------------------------ resumable scans: hnsw.iterative_scan on the device

@@ -313,6 +313,11 @@ struct pgv_hnsw : HnswElements {
     hipEvent_t graph_ev = nullptr;
     bool graph_ev_set = false;
     struct HnswLinkState *link = nullptr;  // pgv_hnsw_link_begin .. _end: the in-memory build's graph state (owner only)
+    // pgv_hnsw_set_live: bit e = element e has heap TIDs ((n + 31) / 32 words on the device; owner's fields, views look at
+    // view_of's).  Not set: every element is live.  Only pgv_hnsw_repair_neighbors reads it
+    pgv::DBuf live;
+    bool live_set = false;
+    int64_t live_count = 0;
 };
 
 namespace pgv {
@@ -701,6 +706,24 @@ int launch_hnsw_search(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, 
 int hnsw_sparse_scan_lds_check(const char *who, pgv_metric metric, int ef, int m, int max_q_nnz);
 int launch_hnsw_patch(pgv_ctx *ctx, const HnswGraph &graph, int64_t n, const int32_t *ids, const int64_t *packed_off,
                       const int32_t *packed, int nupd);
+
+// kernels_hnsw_repair.hip: hnswvacuum's repair search (HnswFindElementNeighbors with existing = true) over a dense mirror
+// with dead elements, one workgroup per element; W holds ef_construction + 1 + dead_cap entries.  All device arrays
+struct HnswRepairArgs {
+    const int32_t *qids = nullptr;  // [nq] the elements being repaired
+    int nq = 0, ef_construction = 0, dead_cap = 0, lcap = 0;
+    int32_t *lw_ids = nullptr;      // [nq x lcap x (ef_construction + 1 + dead_cap)] every searched layer's stripped W
+    float *lw_dist = nullptr;
+    int32_t *lw_cnt = nullptr;      // [nq x lcap]
+    int32_t *qlevels = nullptr;     // [nq] out: each element's level
+    int32_t *status = nullptr;      // [nq] out: 1 = W overflowed, the element's counts are 0
+};
+// PGV_ERR_ARG (the text: who, ef, dead_cap, m, the bytes) when W does not fit a workgroup's LDS; the largest dead_cap that
+// does (-1: not even dead_cap 0)
+int hnsw_repair_lds_check(const char *who, const RowGeom &geom, int ef_construction, int dead_cap, int m, size_t *lds_out);
+int hnsw_repair_dead_cap_max(const RowGeom &geom, int ef_construction, int m);
+int launch_hnsw_repair(pgv_ctx *ctx, const RowsView &v, const HnswGraph &graph, const uint32_t *live, const HnswRepairArgs &a,
+                       uint32_t *bitmaps, int words, int grid, int *counter);
 
 // kernels_tile.hip: row tiles in LDS (async DMA), queries in registers: 16 queries per pass
 bool tile_scan_supported(const RowGeom &g);

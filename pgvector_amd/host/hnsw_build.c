@@ -665,6 +665,47 @@ select_neighbors(cand * *c, int nc, int lm, const pairsrc * ps, uint8_t *closer_
 	return rn;
 }
 
+/*
+ * HnswUpdateConnection (src/hnswutils.c:1183-1231) on a FULL list that was read back from its tuple, as
+ * HnswUpdateNeighborsOnDisk's GetUpdateIndex does (src/hnswinsert.c:409-448; hnsw_repair.c): no cached closer flags, the
+ * candidates sorted, SelectNeighbors recomputed from scratch -- select_neighbors above, not another one.
+ *   members [lm]: the list in tuple order; tri: the pairs (u, v < u) of the locals 0 .. lm + 1 as pgv_hnsw_score_groups
+ *   returns them with from = 1, local 0 the list's owner, locals 1 .. lm its members, local lm + 1 the newcomer;
+ *   new_dist: the newcomer's distance to the owner as its search found it (hc->distance).
+ * Returns the index of the member the newcomer replaces, -1 when the newcomer itself is the one pruned, or -2 when the
+ * selection could not be made (a list longer than SelectNeighbors' arrays, no pruned candidate): an error, never an answer.
+ */
+int
+pgv_host_hnsw_update_index(const int32_t *members, int lm, int32_t newcomer, float new_dist, const float *tri)
+{
+	cand		items[SORT_KEYS];
+	cand	   *c[SORT_KEYS],
+			   *r[SORT_KEYS],
+			   *w[SORT_KEYS],
+			   *wd[SORT_KEYS],
+			   *added[SORT_KEYS];
+	uint8_t		flag[SORT_KEYS];
+	uint8_t		closer_set = 0;
+	cand	   *pruned = NULL;
+	const pairsrc ps = pairs_of(tri, 1, NULL);
+
+	if (lm < 1 || lm + 1 > SORT_KEYS)
+		return -2;
+	for (int i = 0; i <= lm; i++)
+	{
+		items[i].element = i < lm ? members[i] : newcomer;
+		items[i].distance = i < lm ? tri[(i + 1) * i / 2] : new_dist;
+		items[i].local = i + 1;
+		items[i].closer = 0;
+		c[i] = &items[i];
+	}
+	if (select_neighbors(c, lm + 1, lm, &ps, &closer_set, c[lm], r, &pruned, 1, NULL, w, wd, added, flag) < 0 || pruned == NULL)
+		return -2;
+	if (pruned == c[lm])
+		return -1;
+	return (int) (pruned - items);
+}
+
 /* ------------------------------------------------------------------- build */
 
 void
@@ -1210,6 +1251,13 @@ poll_cancel(int64_t i0, int64_t n)
 	if (cancel_check != NULL && cancel_check(cancel_arg))
 		return pgv_host_fail(PGV_ERR_STATE, "pgv_host_hnsw_build: cancelled after %lld of %lld rows", (long long) i0, (long long) n);
 	return PGV_OK;
+}
+
+/* ... and so can a vacuum's repair (hnsw_repair.c polls the same per-thread callback) */
+int
+pgv_host_hnsw_cancelled(void)
+{
+	return cancel_check != NULL && cancel_check(cancel_arg);
 }
 
 /* the first element has nothing to search: it becomes the entry point (with_lists: the host replay keeps its lists) */

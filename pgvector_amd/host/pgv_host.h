@@ -132,6 +132,51 @@ typedef int (*pgv_host_cancel_check) (void *arg);
 void		pgv_host_hnsw_set_cancel_check(pgv_host_cancel_check check, void *arg);
 
 /*
+ * RepairGraph (src/hnswvacuum.c:379-502) over a graph held in memory, every search, selection and pair distance on the
+ * GPU (hnsw_repair.c).  mirror: a dense mirror of pgv_hnsw_upload / _upload_payload holding all n elements; the call
+ * sets the graph (pgv_hnsw_set_graph) and the live bitmap (pgv_hnsw_set_live) on it itself and leaves it holding the
+ * repaired graph.  levels / nbr_start / nbr / entry: the graph in the layout of pgv_hnsw_set_graph, host memory;
+ * live [(n + 31) / 32]: bit e = element e still has heap TIDs.
+ *   - the entry point first (RepairGraphEntryPoint, :280-373): the highest and the fallback point as RemoveHeapTids
+ *     (:36-173) finds them -- the first live element of the greatest level in slot order, and the runner-up; the highest
+ *     non-entry point is repaired against the entry point; a dead entry point is replaced by it, a live one that needs it
+ *     is repaired against it;
+ *   - then every live element in slot order that NeedsUpdated (:179-220: a dead neighbor, or its layer-0 list not
+ *     full), except the entry point (:241-242): RepairGraphElement (:226-274) -- its tuple rebuilt from
+ *     pgv_hnsw_repair_neighbors, then HnswUpdateNeighborsOnDisk (src/hnswinsert.c:546-580) for every neighbor chosen:
+ *     an existing connection stays (ConnectionExists, :454-468), else a free slot takes the element, else the first dead
+ *     member in list order is replaced (LoadElementsForInsert, :383-403), else HnswUpdateConnection with SelectNeighbors
+ *     from scratch over pair distances of pgv_hnsw_score_groups (GetUpdateIndex, :409-448).
+ * max_batch = 1 is the reference's serial loop.  A larger batch is the next max_batch elements that need repair on the
+ * graph as it stands when the batch begins; their searches all read that graph, then their tuples and back links are
+ * applied in element order and the mirror is patched (pgv_hnsw_update_graph).  A batch ends before an element taller
+ * than the entry point, which is repaired alone and becomes the entry point (:481-482).
+ * dead_cap: W's room for dead elements in the first attempt (0: 64).  An element whose search overflows is redone with
+ * dead_cap doubled, up to what the LDS holds (later batches start from the doubled value, up to 1024); beyond that the call fails with PGV_ERR_NOMEM and the text names the
+ * element.  pgv_host_hnsw_set_cancel_check is polled between batches.  Result: nbr (malloc'ed, the layout of the input;
+ * free with pgv_host_hnsw_repaired_free), the entry point (-1: no live element), counters, wall time per phase.
+ */
+typedef struct pgv_hnsw_repaired
+{
+	int32_t    *nbr;			/* [nbr_start[n]] */
+	int64_t		nbr_total;
+	int32_t		entry;
+	int32_t		dead_cap;		/* the largest dead_cap a search ran with */
+	int64_t		examined;		/* live elements looked at by NeedsUpdated in the main loop */
+	int64_t		repaired;		/* RepairGraphElement runs, the entry-point step's included */
+	int64_t		batches;
+	int64_t		overflow_redos;	/* element searches run again with a larger dead_cap */
+	int64_t		device_pairs;	/* pair distances scored: the selections' and the back links' */
+	int64_t		reselections;	/* back links that went through HnswUpdateConnection */
+	double		phase_secs[4];	/* wall time: searches + selection, back-link replay, pair scoring, graph patch */
+}			pgv_hnsw_repaired;
+
+int			pgv_host_hnsw_repair(pgv_hnsw * mirror, int64_t n, const int32_t *levels, const int64_t *nbr_start,
+								 const int32_t *nbr, int32_t entry, const uint32_t *live, int m, int ef_construction,
+								 int max_batch, int dead_cap, pgv_hnsw_repaired * out);
+void		pgv_host_hnsw_repaired_free(pgv_hnsw_repaired * r);
+
+/*
  * The HNSW index in its on-disk form (src/hnsw.h:40-47, 334-392), either side of the device path.
  *
  * pgv_host_hnsw_write_index: FlushPages (src/hnswbuild.c:300-312) from a built graph -- meta page,
