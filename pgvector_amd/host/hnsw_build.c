@@ -28,13 +28,16 @@
  * list are fetched in a second launch, and it is replayed then; lists are independent, so that
  * changes nothing.
  *
+ * The clock, layer_m, the growing arrays and the requests to pgv_hnsw_score_groups (groupbuf) are hnsw_host.h's, shared
+ * with hnsw_repair.c, which also calls this file's pgv_host_hnsw_update_index and pgv_host_hnsw_cancelled.
+ *
  * The file from top to bottom: the lists and SelectNeighbors; stage A of a batch (its searches) and the helper threads
  * that run it ahead; what the two forms of the build share (plan_batch, find_duplicate, the first element, the cancel
  * poll); build_linked_on_device, the graph updates on the GPU; the host replay of the same updates -- its state in one
  * struct (host_link), one function per numbered step of a batch, build_linked_on_host as the loop over them; and
  * pgv_host_hnsw_build, which draws the levels, decides the form and calls one of the two.
  */
-#include "pgv_host.h"
+#include "hnsw_host.h"
 
 #include <math.h>
 #include <omp.h>
@@ -43,9 +46,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
-
-extern int	pgv_host_fail(int code, const char *fmt,...);
 
 #define HNSW_HEAPTIDS 10		/* src/hnsw.h:69 */
 
@@ -158,22 +158,6 @@ rng_double(rng_state * r)
 	return ldexp((double) (out >> 12), -52);
 }
 
-/* room for one more item in an array that grows by doubling (`first` items to begin with): the array, moved if it had
- * to grow, or NULL when out of memory (the old one stays as it was) */
-static inline void *
-room_for_one(void *arr, int64_t used, int64_t *cap, size_t item_bytes, int64_t first)
-{
-	const int64_t ncap = *cap ? *cap * 2 : first;
-	void	   *grown;
-
-	if (used < *cap)
-		return arr;
-	grown = realloc(arr, item_bytes * (size_t) ncap);
-	if (grown)
-		*cap = ncap;
-	return grown;
-}
-
 /* per-thread bump allocator for a batch's records (ids, distance matrices): reset at the end of the batch instead of
  * a malloc/free pair per list -- a 100 k x 1536 build touched 4.3 M lists and spent 15 % of its time in free() */
 typedef struct
@@ -197,11 +181,8 @@ arena_alloc(arena * a, size_t bytes)
 	bytes = (bytes + 15) & ~(size_t) 15;
 	if (bytes > ARENA_CHUNK)
 	{
-		void	  **big = room_for_one(a->big, a->nbig, &a->bigcap, sizeof(void *), 8);
-
-		if (!big)
+		if (!grow(&a->big, &a->bigcap, a->nbig + 1, sizeof(void *)))
 			return NULL;
-		a->big = big;
 		if ((p = malloc(bytes)) != NULL)
 			a->big[a->nbig++] = p;
 		return p;
@@ -280,15 +261,6 @@ typedef struct
 				link_base;
 }			recpart;
 
-static double
-now_secs(void)
-{
-	struct timespec ts;
-
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return (double) ts.tv_sec + 1e-9 * (double) ts.tv_nsec;
-}
-
 /* where the wall time of a build goes: out->phase_secs[] */
 enum
 {
@@ -311,112 +283,6 @@ phase(phase_clock * clk, int p)
 	clk->secs[clk->cur] += t - clk->t0;
 	clk->t0 = t;
 	clk->cur = p;
-}
-
-static inline int
-layer_m(int m, int lc)
-{
-	return lc == 0 ? 2 * m : m; /* HnswGetLayerM, src/hnsw.h:127 */
-}
-
-/* ------------------------------------------------------------ pair requests */
-
-/* a request to pgv_hnsw_score_groups: lists of element slots and, per list, which of its pairs are wanted */
-typedef struct
-{
-	int32_t    *ids;
-	int64_t    *ids_start;		/* [ngroups + 1] */
-	int32_t    *from;			/* [ngroups] */
-	int64_t    *pair_start;		/* [ngroups + 1] */
-	int64_t		nids,
-				ids_cap;
-	int			ngroups,
-				groups_cap;
-}			groupbuf;
-
-static void
-groups_reset(groupbuf * gb)
-{
-	gb->nids = 0;
-	gb->ngroups = 0;
-}
-
-/* pairs (u, v), v < u, of the locals u >= from of ids[0 .. n): they start at pair0 in the reply.  0 = out of memory */
-static int
-groups_add(groupbuf * gb, const int32_t *ids, int n, int from, int64_t pair0)
-{
-	if (gb->ngroups + 1 >= gb->groups_cap)
-	{
-		int			cap = gb->groups_cap ? gb->groups_cap * 2 : 4096;
-		int64_t    *is = realloc(gb->ids_start, sizeof(int64_t) * (size_t) (cap + 1));
-		int64_t    *ps = realloc(gb->pair_start, sizeof(int64_t) * (size_t) (cap + 1));
-		int32_t    *fr = realloc(gb->from, sizeof(int32_t) * (size_t) cap);
-
-		if (is)
-			gb->ids_start = is;
-		if (ps)
-			gb->pair_start = ps;
-		if (fr)
-			gb->from = fr;
-		if (!is || !ps || !fr)
-			return 0;
-		gb->groups_cap = cap;
-	}
-	if (gb->nids + n > gb->ids_cap)
-	{
-		int64_t		cap = gb->ids_cap ? gb->ids_cap : 65536;
-		int32_t    *grown;
-
-		while (cap < gb->nids + n)
-			cap *= 2;
-		grown = realloc(gb->ids, sizeof(int32_t) * (size_t) cap);
-		if (!grown)
-			return 0;
-		gb->ids = grown;
-		gb->ids_cap = cap;
-	}
-	memcpy(gb->ids + gb->nids, ids, sizeof(int32_t) * (size_t) n);
-	gb->ids_start[gb->ngroups] = gb->nids;
-	gb->from[gb->ngroups] = from;
-	gb->pair_start[gb->ngroups] = pair0;
-	gb->nids += n;
-	gb->ngroups++;
-	gb->ids_start[gb->ngroups] = gb->nids;
-	return 1;
-}
-
-/* pairs a group (n locals, from) asks for */
-static inline int64_t
-group_pairs(int n, int from)
-{
-	if (from < 1)
-		from = 1;
-	return n > from ? ((int64_t) n * (n - 1) - (int64_t) from * (from - 1)) / 2 : 0;
-}
-
-/* the request is complete: npairs pairs in all */
-static void
-groups_end(groupbuf * gb, int64_t npairs)
-{
-	if (gb->ngroups > 0)
-		gb->pair_start[gb->ngroups] = npairs;
-}
-
-static void
-groups_free(groupbuf * gb)
-{
-	free(gb->ids);
-	free(gb->ids_start);
-	free(gb->from);
-	free(gb->pair_start);
-	memset(gb, 0, sizeof(*gb));
-}
-
-/* the distances a request asks for, on `handle` (the mirror, or a helper's view of it) */
-static int
-score_groups(pgv_hnsw * handle, const groupbuf * gb, int64_t npairs, float *out)
-{
-	return pgv_hnsw_score_groups(handle, gb->ids, gb->ids_start, gb->from, gb->pair_start, gb->ngroups, gb->nids, npairs, out);
 }
 
 /* pinned room for n floats: grown to twice what is asked for, what it held is not kept */
@@ -1855,9 +1721,9 @@ part_record(recpart * rp, int32_t owner, int lc, uint8_t *is_dirty)
 		h = (h + 1) & (rp->tab_cap - 1);
 	if (rp->tab[h] != 0)
 		return rp->tab[h];
-	if (!(recs = room_for_one(rp->recs, rp->nrec, &rp->cap, sizeof(record), 1024)))
+	if (!grow(&rp->recs, &rp->cap, rp->nrec + 1, sizeof(record)))
 		return 0;
-	rp->recs = recs;
+	recs = rp->recs;
 	recs[rp->nrec].owner = owner;
 	recs[rp->nrec].lc = lc;
 	recs[rp->nrec].newcap = 0;	/* newcomers, counted by the caller */
@@ -1866,11 +1732,8 @@ part_record(recpart * rp, int32_t owner, int lc, uint8_t *is_dirty)
 		return 0;
 	if (!is_dirty[owner])		/* (owners are dealt to threads: no two write one flag) */
 	{
-		int32_t    *dirty = room_for_one(rp->dirty, rp->ndirty, &rp->dirty_cap, sizeof(int32_t), 1024);
-
-		if (!dirty)
+		if (!grow(&rp->dirty, &rp->dirty_cap, rp->ndirty + 1, sizeof(int32_t)))
 			return 0;
-		rp->dirty = dirty;
 		is_dirty[owner] = 1;
 		rp->dirty[rp->ndirty++] = owner;
 	}
@@ -1949,14 +1812,12 @@ make_records(host_link * h, const batch_plan * p)
 					if ((int) (((uint64_t) ((uint32_t) owner * 2654435761u) * (uint64_t) T) >> 32) != me)
 						continue;
 					ri = part_record(rp, owner, lc, is_dirty);
-					links = room_for_one(rp->links, rp->nlinks, &rp->links_cap, sizeof(link_req), 4096);
-					if (links)
-						rp->links = links;
-					if (ri == 0 || !links)
+					if (ri == 0 || !grow(&rp->links, &rp->links_cap, rp->nlinks + 1, sizeof(link_req)))
 					{
 						rp->oom = 1;
 						break;
 					}
+					links = rp->links;
 					links[rp->nlinks].rec = ri - 1;
 					links[rp->nlinks].element = e;
 					links[rp->nlinks].distance = x->layers[lc].items[i].distance;
@@ -2585,10 +2446,6 @@ pgv_host_hnsw_build(pgv_hnsw * mirror, pgv_dtype dtype, int dim, const void *row
 	return build_items(mirror, &r, n, m, ef_construction, rng, max_batch, out);
 }
 
-/* (a weak reference: this file is also linked against stand-ins of the device library that have no bit mirrors, and
- * against such a library the bits entry says so instead of failing to link) */
-#pragma weak pgv_hnsw_buildable_bits
-
 /* ... over packed bit strings: rows of (nbits + 7) / 8 bytes, VARBITBYTES, the caller's pad bits zero -- so that equal
  * strings are equal bytes (the duplicate check compares whole bytes, as datumIsEqual compares the varbit datums) */
 int
@@ -2599,8 +2456,6 @@ pgv_host_hnsw_build_bits(pgv_hnsw * mirror, int nbits, const void *rows, int64_t
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: mirror/rows/out is NULL");
 	if (nbits < 1 || nbits > 64000)
 		return pgv_host_fail(PGV_ERR_DIMS, "pgv_host_hnsw_build_bits: bit dimensions %d outside 1..64000", nbits);
-	if (!pgv_hnsw_buildable_bits)
-		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: the device library has no pgv_hnsw_upload_bits_buildable");
 	if (pgv_hnsw_buildable_bits(mirror) != nbits)
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_bits: not a mirror of %d-bit rows uploaded by "
 							 "pgv_hnsw_upload_bits_buildable", nbits);
@@ -2610,10 +2465,6 @@ pgv_host_hnsw_build_bits(pgv_hnsw * mirror, int nbits, const void *rows, int64_t
 		return build_items(mirror, &r, n, m, ef_construction, rng, max_batch, out);
 	}
 }
-
-/* (weak for the same reason) */
-#pragma weak pgv_hnsw_buildable_sparse
-#pragma weak pgv_hnsw_elements
 
 /*
  * ... over sparsevec elements in CSR (`USING hnsw (... sparsevec_*_ops)`): the rows the mirror was uploaded from.  The
@@ -2627,8 +2478,6 @@ pgv_host_hnsw_build_sparse(pgv_hnsw * mirror, int dim, const int64_t *row_ptr, c
 {
 	if (!mirror || !out || !row_ptr || (n > 0 && row_ptr[n] > row_ptr[0] && (!row_idx || !row_val)))
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: mirror/row_ptr/row_idx/row_val/out is NULL");
-	if (!pgv_hnsw_buildable_sparse || !pgv_hnsw_elements)
-		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: the device library has no pgv_hnsw_upload_sparse_buildable");
 	if (dim < 1 || pgv_hnsw_buildable_sparse(mirror) != dim)
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_build_sparse: not a mirror of %d-dimensional sparse rows uploaded by "
 							 "pgv_hnsw_upload_sparse_buildable", dim);

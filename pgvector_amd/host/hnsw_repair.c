@@ -15,27 +15,9 @@
  * back links of later elements in element order -- and lists do not depend on each other.  A back link needs distances
  * only when it comes to HnswUpdateConnection (a full list without a dead member); those lists wait, the pairs of all
  * waiting lists are scored in one pgv_hnsw_score_groups call, and they go on -- as many rounds as the busiest list has
- * reselections.  The selection itself is hnsw_build.c's (pgv_host_hnsw_update_index).
+ * reselections.  The selection itself is hnsw_build.c's (pgv_host_hnsw_update_index), the request hnsw_host.h's groupbuf.
  */
-#include "pgv_host.h"
-
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-/*
- * The vacuum-side entries of the device library are weak references: the host glue also links, whole, into programs that
- * stand in for the device with an older set of entries (tests/c/mock_hip.c); there pgv_host_hnsw_repair reports that the
- * entries are missing instead of keeping every such program from linking -- or finds the program's own stand-ins
- * (tests/c/hnsw_repair_asan_driver.c).  Once the mock has the entries the pragmas can go.
- */
-#pragma weak pgv_hnsw_set_live
-#pragma weak pgv_hnsw_repair_neighbors
-#pragma weak pgv_hnsw_repair_dead_cap_max
-
-extern int	pgv_host_fail(int code, const char *fmt,...);
-extern int	pgv_host_hnsw_update_index(const int32_t *members, int lm, int32_t newcomer, float new_dist, const float *tri);
-extern int	pgv_host_hnsw_cancelled(void);
+#include "hnsw_host.h"
 
 #define DEAD_CAP_CARRY 1024
 
@@ -97,15 +79,9 @@ typedef struct
 	listrun    *runs;
 	int64_t		nruns,
 				runs_cap;
-	/* one round's scoring request and its reply */
-	int32_t    *g_ids;
-	int64_t    *g_start;
-	int32_t    *g_from;
-	int64_t    *g_pair;
-	int64_t		g_ids_cap,
-				g_start_cap,
-				g_from_cap,
-				g_pair_cap;
+	/* one round's scoring request, how many pairs it asks for so far, and its reply */
+	groupbuf	gb;
+	int64_t		npairs;
 	float	   *tri;
 	int64_t		tri_cap;
 	/* the patch: the changed tuples whole, tup_off [npatched + 1] where each starts in tup */
@@ -115,21 +91,6 @@ typedef struct
 				tup_cap;
 }			repair;
 
-static double
-now_secs(void)
-{
-	struct timespec ts;
-
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return (double) ts.tv_sec + 1e-9 * (double) ts.tv_nsec;
-}
-
-static inline int
-layer_m(int m, int lc)
-{
-	return lc == 0 ? 2 * m : m;
-}
-
 static inline int
 is_live(const repair * R, int32_t e)
 {
@@ -137,26 +98,14 @@ is_live(const repair * R, int32_t e)
 }
 
 static int
-grow(void **p, int64_t *cap, int64_t want, size_t item)
+out_of_memory(void)
 {
-	void	   *q;
-	int64_t		c = *cap;
-
-	if (want <= c)
-		return PGV_OK;
-	c = c < 64 ? 64 : c;
-	while (c < want)
-		c *= 2;
-	q = realloc(*p, (size_t) c * item);
-	if (!q)
-		return pgv_host_fail(PGV_ERR_NOMEM, "pgv_host_hnsw_repair: out of host memory");
-	*p = q;
-	*cap = c;
-	return PGV_OK;
+	return pgv_host_fail(PGV_ERR_NOMEM, "pgv_host_hnsw_repair: out of host memory");
 }
 
 /* room for `want` items in R->name, whose capacity is R->name_cap: the one way these arrays are sized */
-#define ROOM(R, name, want) grow((void **) &(R)->name, &(R)->name##_cap, (want), sizeof(*(R)->name))
+#define ROOM(R, name, want) \
+	(grow(&(R)->name, &(R)->name##_cap, (want), sizeof(*(R)->name)) ? PGV_OK : out_of_memory())
 
 /* NeedsUpdated (src/hnswvacuum.c:179-220): a neighbor being deleted, or the last slot of layer 0 empty */
 static int
@@ -278,7 +227,7 @@ backlink_cmp(const void *pa, const void *pb)
  * (src/hnswinsert.c:409-540).
  */
 static int
-run_list(repair * R, listrun * run, int64_t *ngroups, int64_t *nids, int64_t *npairs)
+run_list(repair * R, listrun * run)
 {
 	while (run->next < run->end)
 	{
@@ -312,19 +261,15 @@ run_list(repair * R, listrun * run, int64_t *ngroups, int64_t *nids, int64_t *np
 				if (run->tri_at < 0)
 				{
 					/* HnswUpdateConnection: the owner, its members and the newcomer meet on the device first */
-					const int64_t g = *ngroups;
-					int32_t    *ids = R->g_ids + *nids;
+					int32_t		ids[2 * 100 + 2];	/* (m <= 100, src/hnsw.h:56) */
 
 					ids[0] = ev->owner;
 					memcpy(ids + 1, list, sizeof(int32_t) * (size_t) lm);
 					ids[lm + 1] = ev->e;
-					R->g_start[g] = *nids;
-					R->g_from[g] = 1;
-					R->g_pair[g] = *npairs;
-					run->tri_at = *npairs;
-					*nids += lm + 2;
-					*npairs += (int64_t) (lm + 2) * (lm + 1) / 2;
-					*ngroups = g + 1;
+					if (!groups_add(&R->gb, ids, lm + 2, 1, R->npairs))
+						return out_of_memory();
+					run->tri_at = R->npairs;
+					R->npairs += group_pairs(lm + 2, 1);
 					return 1;
 				}
 				idx = pgv_host_hnsw_update_index(list, lm, ev->e, ev->dist, R->tri + run->tri_at);
@@ -419,43 +364,32 @@ apply_batch(repair * R, const int32_t *elems, int nb, int lcap)
 		i = j;
 	}
 	/* rounds: every list as far as it gets without new distances; the waiting lists' pairs in one launch */
-	{
-		const int64_t gsize = stride + 2;
-
-		if ((rc = ROOM(R, g_ids, R->nruns * gsize)) != PGV_OK || (rc = ROOM(R, g_start, R->nruns + 1)) != PGV_OK ||
-			(rc = ROOM(R, g_from, R->nruns)) != PGV_OK || (rc = ROOM(R, g_pair, R->nruns + 1)) != PGV_OK)
-			return rc;
-	}
 	for (int64_t waiting = R->nruns; waiting > 0;)
 	{
-		int64_t		ngroups = 0,
-					nids = 0,
-					npairs = 0;
-
+		groups_reset(&R->gb);
+		R->npairs = 0;
 		waiting = 0;
 		for (int64_t k = 0; k < R->nruns; k++)
 			if (R->runs[k].next < R->runs[k].end)
 			{
-				const int	w = run_list(R, &R->runs[k], &ngroups, &nids, &npairs);
+				const int	w = run_list(R, &R->runs[k]);
 
 				if (w > 1)
 					return w;
 				waiting += w;
 			}
-		if (ngroups == 0)
+		if (waiting == 0)
 			break;
-		R->g_start[ngroups] = nids;
-		R->g_pair[ngroups] = npairs;
-		if ((rc = ROOM(R, tri, npairs)) != PGV_OK)
+		groups_end(&R->gb, R->npairs);
+		if ((rc = ROOM(R, tri, R->npairs)) != PGV_OK)
 			return rc;
 		t1 = now_secs();
 		R->out->phase_secs[1] += t1 - t0;
-		if ((rc = pgv_hnsw_score_groups(R->mirror, R->g_ids, R->g_start, R->g_from, R->g_pair, (int) ngroups, nids, npairs,
-										R->tri)) != PGV_OK)
+		if ((rc = score_groups(R->mirror, &R->gb, R->npairs, R->tri)) != PGV_OK)
 			return rc;
 		t0 = now_secs();
 		R->out->phase_secs[2] += t0 - t1;
-		R->out->device_pairs += npairs;
+		R->out->device_pairs += R->npairs;
 	}
 	t1 = now_secs();
 	R->out->phase_secs[1] += t1 - t0;
@@ -529,9 +463,6 @@ pgv_host_hnsw_repair(pgv_hnsw * mirror, int64_t n, const int32_t *levels, const 
 	if (!mirror || !out || !levels || !nbr_start || !nbr || !live)
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_repair: mirror/graph/live/out is NULL");
 	memset(out, 0, sizeof(*out));
-	if (!pgv_hnsw_set_live || !pgv_hnsw_repair_neighbors || !pgv_hnsw_repair_dead_cap_max)
-		return pgv_host_fail(PGV_ERR_STATE, "pgv_host_hnsw_repair: the device library has no pgv_hnsw_set_live / "
-							 "pgv_hnsw_repair_neighbors");
 	if (n < 1 || n > 0x7fffffff || m < 2 || m > 100 || entry < -1 || entry >= n || max_batch < 1 || dead_cap < 0)
 		return pgv_host_fail(PGV_ERR_ARG, "pgv_host_hnsw_repair: bad sizes (n %lld, m %d, entry %d, max_batch %d, dead_cap %d)",
 							 (long long) n, m, (int) entry, max_batch, dead_cap);
@@ -574,7 +505,7 @@ pgv_host_hnsw_repair(pgv_hnsw * mirror, int64_t n, const int32_t *levels, const 
 	batch = malloc(sizeof(int32_t) * (size_t) max_batch);
 	if (!R.nbr || !R.pos_of || !R.patched || !batch)
 	{
-		rc = pgv_host_fail(PGV_ERR_NOMEM, "pgv_host_hnsw_repair: out of host memory");
+		rc = out_of_memory();
 		goto done;
 	}
 	memcpy(R.nbr, nbr, sizeof(int32_t) * (size_t) out->nbr_total);
@@ -692,10 +623,7 @@ done:
 	free(R.patch_list);
 	free(R.events);
 	free(R.runs);
-	free(R.g_ids);
-	free(R.g_start);
-	free(R.g_from);
-	free(R.g_pair);
+	groups_free(&R.gb);
 	free(R.tri);
 	free(R.tup_off);
 	free(R.tup);

@@ -1149,6 +1149,53 @@ test_ivf_f16(void)
 	return 0;
 }
 
+/*
+ * ---- HNSW vacuum: pgv_host_hnsw_repair on the stand-in device, serial (max_batch 1) and batched.  64 elements, every
+ * fourth dead: small enough that full lists without a dead member occur, so rounds go through pgv_hnsw_score_groups.  The
+ * stand-in's search does not look at the graph, so what a repair leaves depends on the host logic alone: the tuples are
+ * pinned whole (FNV-1a over the slots), and every change to the order of batches, back links or scored pairs moves them.
+ */
+#include "hnsw_repair_scenario.h"
+
+static int
+test_hnsw_repair(void)
+{
+	static const struct
+	{
+		int			max_batch;
+		int64_t		repaired,
+					batches,
+					reselections;
+		uint64_t	tuples;
+	}			want[] = {{1, 34, 34, 68, 0x908f79fb9087c29cull}, {8, 37, 7, 74, 0x37b92583ceefd652ull}};
+	repair_scenario s;
+
+	EXPECT(repair_scenario_make(&s, 64, 1) == 0);
+	for (int r = 0; r < 2; r++)
+	{
+		pgv_hnsw_repaired out;
+		uint64_t	hash = 1469598103934665603ull;
+
+		CHECK(pgv_host_hnsw_repair(s.h, s.n, s.levels, s.start, s.nbr, s.entry, s.live, RS_M, 16, want[r].max_batch, 2, &out));
+		EXPECT(out.reselections > 0);
+		EXPECT(!repair_scenario_broken(&s, &out));
+		EXPECT(pgv_hnsw_live_count(s.h) == 48 && out.examined == 48);
+		for (int64_t i = 0; i < out.nbr_total; i++)
+			hash = (hash ^ (uint32_t) out.nbr[i]) * 1099511628211ull;
+		if (out.repaired != want[r].repaired || out.batches != want[r].batches || out.reselections != want[r].reselections ||
+			hash != want[r].tuples)
+		{
+			fprintf(stderr, "hnsw repair, max_batch %d: repaired %lld batches %lld reselections %lld tuples %llx\n",
+					want[r].max_batch, (long long) out.repaired, (long long) out.batches, (long long) out.reselections,
+					(unsigned long long) hash);
+			return 1;
+		}
+		pgv_host_hnsw_repaired_free(&out);
+	}
+	repair_scenario_free(&s);
+	return 0;
+}
+
 int
 main(void)
 {
@@ -1158,6 +1205,8 @@ main(void)
 	if (test_hnsw_build())
 		return 1;
 	if (test_hnsw_build_f16())
+		return 1;
+	if (test_hnsw_repair())
 		return 1;
 	if (test_ivf())
 		return 1;

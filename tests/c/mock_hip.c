@@ -235,6 +235,7 @@ struct pgv_hnsw
 	int32_t    *nbr;
 	char	   *payload;		/* [n x payload_bytes] (pgv_hnsw_upload_payload) */
 	int			payload_bytes;
+	uint32_t   *live;			/* [(n + 31) / 32] (pgv_hnsw_set_live), NULL: every element is live */
 	/* pgv_hnsw_link_begin .. _end: distance and closer flag (bit 0; bit 1 of a list's first slot: closerSet) per tuple slot,
 	 * and the batch handed to pgv_hnsw_link_prepare */
 	float	   *nb_dist;
@@ -1213,7 +1214,29 @@ pgv_hnsw_free(pgv_hnsw * h)
 	graph_free(h);
 	dev_free(h->vectors);
 	dev_free(h->payload);
+	dev_free(h->live);
 	dev_free(h);
+}
+
+/* (no bit and no sparse mirrors here) */
+int
+pgv_hnsw_buildable_bits(const pgv_hnsw * h)
+{
+	(void) h;
+	return 0;
+}
+
+int
+pgv_hnsw_buildable_sparse(const pgv_hnsw * h)
+{
+	(void) h;
+	return 0;
+}
+
+int64_t
+pgv_hnsw_elements(const pgv_hnsw * h)
+{
+	return h ? h->n : -1;
 }
 
 int
@@ -1249,6 +1272,122 @@ pgv_hnsw_update_graph(pgv_hnsw * h, int32_t entry, const int32_t *elements, int 
 			return fail(PGV_ERR_ARG, "mock: tuple size");
 		memcpy(h->nbr + h->nbr_start[e], tuples + tuple_offsets[i], sizeof(int32_t) * (size_t) len);
 	}
+	return PGV_OK;
+}
+
+/*
+ * The vacuum side.  pgv_hnsw_repair_neighbors is something much simpler than the device's search: an element's "repair
+ * search" answers, on every layer, the nearest live elements of that layer by brute force, furthest first, and every fifth
+ * element overflows any dead_cap below 100 (the others below 3), so that a caller's redo runs with several doublings.
+ * That is no model of the search (tests/hnsw_repair_model.py and the GPU tests are); it feeds pgv_host_hnsw_repair lists of
+ * the right shape, which is what its buffers are sized by.  Not through views.
+ */
+int
+pgv_hnsw_set_live(pgv_hnsw * h, const uint32_t *live, int64_t words)
+{
+	if (live && words != (h->n + 31) / 32)
+		return fail(PGV_ERR_ARG, "mock: live bitmap size");
+	dev_free(h->live);
+	h->live = live ? dev_alloc(sizeof(uint32_t) * (size_t) words) : NULL;
+	if (live)
+		memcpy(h->live, live, sizeof(uint32_t) * (size_t) words);
+	return PGV_OK;
+}
+
+static int
+hnsw_is_live(const pgv_hnsw * h, int64_t e)
+{
+	return !h->live || ((h->live[e >> 5] >> (e & 31)) & 1u);
+}
+
+int64_t
+pgv_hnsw_live_count(const pgv_hnsw * h)
+{
+	int64_t		c = 0;
+
+	for (int64_t e = 0; h && e < h->n; e++)
+		c += hnsw_is_live(h, e);
+	return h ? c : -1;
+}
+
+int
+pgv_hnsw_repair_dead_cap_max(const pgv_hnsw * h, int ef_construction)
+{
+	(void) h;
+	(void) ef_construction;
+	return 4096;
+}
+
+/* the lm nearest live elements x != e with levels[x] >= lc, nearest first; returns how many */
+static int
+nearest_live(const pgv_hnsw * h, int64_t e, int lc, int lm, int32_t *ids, float *ds)
+{
+	int			cnt = 0;
+
+	for (int64_t x = 0; x < h->n; x++)
+	{
+		float		d;
+		int			j;
+
+		if (x == e || h->levels[x] < lc || !hnsw_is_live(h, x))
+			continue;
+		d = dist(h->metric, h->dim, h->vectors + (size_t) e * h->dim, h->vectors + (size_t) x * h->dim);
+		if (cnt == lm && d >= ds[cnt - 1])
+			continue;
+		j = cnt < lm ? cnt++ : lm - 1;
+		while (j > 0 && ds[j - 1] > d)
+		{
+			ds[j] = ds[j - 1];
+			ids[j] = ids[j - 1];
+			j--;
+		}
+		ds[j] = d;
+		ids[j] = (int32_t) x;
+	}
+	return cnt;
+}
+
+int
+pgv_hnsw_repair_neighbors(pgv_hnsw * h, const int32_t *elements, int nq, int ef_construction, int layer_cap, int dead_cap,
+						  int32_t *out_ids, float *out_dist, uint8_t *out_closer, int32_t *out_count, int32_t *out_status,
+						  int64_t *out_pairs)
+{
+	const int	stride = 2 * h->m;
+	int32_t    *ids = malloc(sizeof(int32_t) * (size_t) stride);
+	float	   *ds = malloc(sizeof(float) * (size_t) stride);
+
+	(void) ef_construction;
+	if (out_pairs)
+		*out_pairs = 0;
+	for (int q = 0; q < nq; q++)
+	{
+		const int32_t e = elements[q];
+
+		if (e < 0 || e >= h->n)
+		{
+			free(ids);
+			free(ds);
+			return fail(PGV_ERR_ARG, "mock: no such element");
+		}
+		out_status[q] = dead_cap < (e % 5 == 0 ? 100 : 3);
+		for (int lc = 0; lc < layer_cap; lc++)
+		{
+			const size_t o = ((size_t) q * layer_cap + lc) * stride;
+			int			cnt = 0;
+
+			if (!out_status[q] && lc <= h->levels[e])
+				cnt = nearest_live(h, e, lc, lc == 0 ? stride : h->m, ids, ds);
+			out_count[(size_t) q * layer_cap + lc] = cnt;
+			for (int i = 0; i < cnt; i++)	/* furthest first, as a list taken whole */
+			{
+				out_ids[o + i] = ids[cnt - 1 - i];
+				out_dist[o + i] = ds[cnt - 1 - i];
+				out_closer[o + i] = 0;
+			}
+		}
+	}
+	free(ids);
+	free(ds);
 	return PGV_OK;
 }
 

@@ -1,6 +1,5 @@
 """pgv_host_hnsw_repair's host logic under AddressSanitizer and UndefinedBehaviorSanitizer, as a program of its own
-(tests/c/hnsw_repair_asan_driver.c against tests/c/mock_hip.c; the three device entries the mock lacks are stood in for
-by the driver itself).  Its buffers are sized batch by batch and grow at different rates -- the selections, the back links,
+(tests/c/hnsw_repair_asan_driver.c against tests/c/mock_hip.c).  Its buffers are sized batch by batch and grow at different rates -- the selections, the back links,
 the scoring requests, the patch -- so the runs vary the batch size: max_batch 1 walks the patch's totals across the first
 powers of two, the large batches grow everything at once."""
 import glob
