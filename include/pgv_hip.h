@@ -358,6 +358,42 @@ int			pgv_scan_batch(pgv_index * index, const void *queries, int nq, const int32
 						   int probes, int k, float *out_dist, int64_t *out_slot, uint64_t *out_tid);
 
 /*
+ * `ORDER BY emb <-> $1 LIMIT k` under a WHERE clause: the reference's iterative scan (ivfflat.iterative_scan =
+ * relaxed_order, src/ivfscan.c:134, :268-277, :400-406) with the executor's filter and LIMIT applied, for a batch of
+ * queries, on the device.  Per query, with L[0 .. P) the P = min(max(max_probes, probes), nlists) nearest lists as
+ * pgv_rank_lists ranks them (probes clamped to nlists):
+ *     emitted = 0; used = 0
+ *     while emitted < k and used < P:
+ *         batch = lists L[used .. min(used + probes, P)); used = that end
+ *         the batch's rows in tuplesort input order (lists in that order, slot order inside), sorted ascending by value
+ *           in float8 order (-inf < finite < +inf < NaN), ties to the lower input position
+ *         for each row of the sorted batch while emitted < k: if its keep bit is set (or keep is NULL): emit it
+ * A batch that brings the count to exactly k ends the scan (the executor does not ask again); max_probes <= probes is
+ * the plain one-batch scan (iterative scan off).
+ *   keep        a bitmap over ROW SLOTS (the index into vectors / tids, what out_slot reports; pgv_index_rows of them):
+ *               slot s is bit s & 31 of word s >> 5.  keep_stride 0: one bitmap of (n + 31) / 32 words for all queries;
+ *               else query q's begins at keep + q * keep_stride, keep_stride >= (n + 31) / 32.  NULL keeps every row.
+ *               pgv_hnsw_scan_filtered's layout
+ *   out_dist / out_slot  [nq x k] in emission order, padded with +inf / -1; a real row whose value is +inf or NaN is a
+ *               row like any other and comes before the padding
+ *   out_tid     [nq x k] or NULL; needs an index uploaded with tids; padded with ~0
+ *   out_count   [nq] rows emitted;  out_probes [nq] or NULL: `used` at the end
+ * Every pointer may be host or device memory.  The values are the exact vector-ALU values, bit for bit what
+ * pgv_scan_lists returns for that query and row (no matrix-core expansion, no shadow: pgv_ctx_set_exact_scan and
+ * pgv_ctx_set_bound do not matter here).  Only the rows whose keep bit is set are read, and only in the rounds a query
+ * needs: the bitmap is counted first, and a list that keeps nothing is never touched.
+ * 1 <= k <= 4096.  PGV_ERR_ARG before any launch for: a NULL index, queries, out_dist, out_slot or out_count; k out of
+ * range; probes < 1; a nonzero keep_stride below the word count; out_tid on an index without tids; a bit index
+ * (pgv_index_upload_bits: not served here); an L1 index.  nq == 0 returns PGV_OK at once.  Serves fp32 and fp16
+ * indexes under PGV_L2SQ and PGV_NEG_IP, pgv_index_share views and imported mirrors.  Not served: the Postgres
+ * extension's scan (ext/), and a loop that goes on past the one planned chain of launches (there is none to go on
+ * with: the plan knows every round a query needs from the bitmap alone).
+ */
+int			pgv_search_filtered(pgv_index * index, const void *queries, int nq, int probes, int max_probes, int k,
+									const uint32_t *keep, int64_t keep_stride, float *out_dist, int64_t *out_slot,
+									uint64_t *out_tid, int32_t *out_count, int32_t *out_probes);
+
+/*
  * One backend's index scan, device-resident between the amgettuple calls (src/ivfscan.c:361-414).
  * This is the path a Postgres backend binds: one query at a time, LIMIT k tuples pulled.
  *   pgv_query_rank   GetScanLists (src/ivfscan.c:47-118): ranks every center against the query

@@ -36,6 +36,7 @@ SYMBOLS = [
     "pgv_ctx_sync", "pgv_ctx_stream", "pgv_timer_start", "pgv_timer_stop", "pgv_ctx_set_profiling", "pgv_ctx_set_exact_scan", "pgv_index_share", "pgv_pinned_alloc", "pgv_pinned_free",
     "pgv_ctx_reset_stats", "pgv_ctx_get_stats", "pgv_index_upload", "pgv_index_free",
     "pgv_index_rows", "pgv_index_lists", "pgv_rank_lists", "pgv_scan_lists", "pgv_search_batch", "pgv_scan_batch",
+    "pgv_search_filtered",
     "pgv_assign", "pgv_kmeans", "pgv_lloyd_partial", "pgv_lloyd_finish", "pgv_kmeanspp_init",
     "pgv_distance_batch", "pgv_cosine_distance_batch", "pgv_bit_distance_batch", "pgv_hnsw_upload", "pgv_hnsw_free", "pgv_hnsw_score", "pgv_hnsw_set_graph", "pgv_hnsw_search",
     "pgv_hnsw_build_search", "pgv_hnsw_build_neighbors", "pgv_hnsw_link_begin", "pgv_hnsw_link_prepare",
@@ -157,6 +158,7 @@ def _load():
     lib.pgv_rank_lists.argtypes = [P, P, I, I, P, P]
     lib.pgv_scan_lists.argtypes = [P, P, P, I, P, P, I64, C.POINTER(I64)]
     lib.pgv_search_batch.argtypes = [P, P, I, I, I, P, P, P]
+    lib.pgv_search_filtered.argtypes = [P, P, I, I, I, I, P, I64, P, P, P, P, P]
     lib.pgv_scan_batch.argtypes = [P, P, I, P, I, I, P, P, P]
     lib.pgv_query_begin.argtypes = [P, C.POINTER(P)]
     lib.pgv_query_end.argtypes = [P]

@@ -255,6 +255,39 @@ class IvfIndex:
         check(lib.pgv_search_batch(self.h, ptr(queries), nq, probes, k, ptr(dist), ptr(slot), ptr(tid)))
         return dist, slot, tid
 
+    def search_filtered(self, queries, probes, k, keep=None, max_probes=0, want_tid=False):
+        """pgv_search_filtered: `ORDER BY ... LIMIT k` under a filter, the reference's iterative scan with the loop on
+        the device -- batches of `probes` lists up to max_probes (0: one batch), stopping once k kept rows are out.
+        keep: None (every row), a boolean array or tensor [n] or [nq, n] over row slots (packed with pack_keep), or 32-bit
+        words [words] or [nq, words] that are such a bitmap already (words >= (n + 31) / 32).  n is the index's row count.
+        -> (dist [nq x k] in emission order / +inf, slot [nq x k] / -1[, tid [nq x k] / ~0], count [nq], probes_used [nq]).
+        A bit index raises the library's refusal."""
+        queries = as_dtype(queries, self.dtype) if self.dtype is not None else _as_bytes(queries)
+        nq, k = int(queries.shape[0]), int(k)
+        stride = 0
+        if keep is not None:
+            n = int(self.rows)
+            if _is_keep_words(keep):
+                if int(keep.shape[-1]) < (n + 31) // 32:
+                    raise PgvError(PGV_ERR_ARG, "keep: %d words, the index's %d rows take %d" % (keep.shape[-1], n, (n + 31) // 32))
+                keep = keep.contiguous() if _is_torch(keep) else np.ascontiguousarray(keep)
+            else:
+                if int(keep.shape[-1]) != n:
+                    raise PgvError(PGV_ERR_ARG, "keep: a filter over %d rows, the index has %d" % (keep.shape[-1], n))
+                keep = pack_keep(keep)
+            if keep.ndim not in (1, 2) or (keep.ndim == 2 and keep.shape[0] != nq):
+                raise PgvError(PGV_ERR_ARG, "keep: one filter [n] or one per query [%d, n]" % nq)
+            stride = int(keep.shape[1]) if keep.ndim == 2 else 0
+        shape = (nq, max(k, 1))
+        dist = _empty_like_kind(queries, shape, np.float32)
+        slot = _empty_like_kind(queries, shape, np.int64)
+        tid = _empty_like_kind(queries, shape, np.uint64 if not _on_device(queries) else np.int64) if want_tid else None
+        count = _empty_like_kind(queries, (nq,), np.int32)
+        used = _empty_like_kind(queries, (nq,), np.int32)
+        check(lib.pgv_search_filtered(self.h, ptr(queries), nq, int(probes), int(max_probes), k, ptr(keep), stride, ptr(dist),
+                                      ptr(slot), ptr(tid), ptr(count), ptr(used)))
+        return (dist, slot, tid, count, used) if want_tid else (dist, slot, count, used)
+
 
 def _scan_batch(self, queries, probe_lists, k, want_tid=False, out=None):
     """GetScanItems + sorted head for probe lists chosen elsewhere (pgv_scan_batch)"""

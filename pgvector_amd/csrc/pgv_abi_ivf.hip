@@ -1361,6 +1361,129 @@ int pgv_scan_batch(pgv_index *ix, const void *queries, int nq, const int32_t *pr
                           out_tid, true);
 }
 
+// The iterative scan under a filter (include/pgv_hip.h; kernels_ivf_filter.hip): rank P lists for the
+// whole batch, then per chunk of queries count -> plan -> (the call's one read-back: how many values, tasks and segments
+// the plan made) -> score -> select and emit.  No host loop over rounds: the plan decides every query's last round
+int pgv_search_filtered(pgv_index *ix, const void *queries, int nq, int probes, int max_probes, int k, const uint32_t *keep,
+                        int64_t keep_stride, float *out_dist, int64_t *out_slot, uint64_t *out_tid, int32_t *out_count,
+                        int32_t *out_probes) {
+    if (!ix) PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: index is NULL");
+    PGV_NO_BIT_INDEX(ix, "pgv_search_filtered");
+    if (ix->metric != PGV_L2SQ && ix->metric != PGV_NEG_IP)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: L2 and inner product indexes only (metric %d)", (int)ix->metric);
+    if (nq < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: nq < 0");
+    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: k %d outside 1..4096", k);
+    if (probes < 1) PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: probes %d < 1", probes);
+    if (!queries || !out_dist || !out_slot || !out_count)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: queries/out_dist/out_slot/out_count is NULL");
+    const int64_t n = ix->nrows, kwords = (n + 31) / 32;
+    if (keep && keep_stride != 0 && keep_stride < kwords)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: keep_stride %lld is below the %lld words of one bitmap over the index's rows",
+                 (long long)keep_stride, (long long)kwords);
+    if (out_tid && !ix->tids) PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: out_tid on an index uploaded without tids");
+    if (n > 0xffffffffll) PGV_FAIL(PGV_ERR_ARG, "pgv_search_filtered: more than 2^32 rows");
+    if (nq == 0) return PGV_OK;
+    if (probes > ix->nlists) probes = ix->nlists;
+    const int P = std::min(std::max(max_probes, probes), ix->nlists);
+    const int nrounds = (P + probes - 1) / probes;
+    if (!keep) keep_stride = 0;
+    pgv_ctx *ctx = ix->ctx;
+    PGV_HIP(hipSetDevice(ctx->device));
+
+    const void *q_dev, *keep_dev = nullptr;
+    PGV_TRY(stage_queries(ix, queries, nq, &q_dev));
+    if (keep)
+        PGV_TRY(stage_flat(ctx, keep, sizeof(uint32_t) * (keep_stride ? (size_t)nq * (size_t)keep_stride : (size_t)kwords),
+                           ctx->rows_stage, &keep_dev));
+    const uint32_t *kd = static_cast<const uint32_t *>(keep_dev);
+    PGV_TRY(ctx->idx_stage.ensure(sizeof(int32_t) * (size_t)nq * P));
+    int32_t *lists = ctx->idx_stage.as<int32_t>();
+    PGV_TRY(rank_lists_dev(ix, q_dev, nq, P, lists, nullptr));
+
+    OutArg od, os, ot, oc, op;
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
+    PGV_TRY(os.init(out_slot, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
+    PGV_TRY(ot.init(out_tid, sizeof(uint64_t) * (size_t)nq * k, ctx->sel_b));
+    PGV_TRY(oc.init(out_count, sizeof(int32_t) * (size_t)nq, ctx->sel_a));
+    PGV_TRY(op.init(out_probes, sizeof(int32_t) * (size_t)nq, ctx->ms_a));
+
+    IvfFilterPlan plan;
+    plan.list_off = ix->list_offsets;
+    plan.P = P;
+    plan.probes = probes;
+    plan.k = k;
+    ivf_filter_task_rows(&plan.task_rows, &plan.task_rows_max);
+    plan.cnt_mode = !keep ? 0 : (keep_stride == 0 ? 1 : 2);
+    // one bitmap for all queries: the counts depend on the list only, once for the call
+    if (plan.cnt_mode == 1) {
+        PGV_TRY(ctx->plan_a.ensure(sizeof(uint32_t) * (size_t)ix->nlists));
+        PGV_TRY(launch_ivf_keep_count(ctx, kd, 0, nullptr, P, ix->list_offsets, ix->nlists, ctx->plan_a.as<uint32_t>()));
+    }
+    // a chunk of queries: its plan tables (tasks by their bound: every list in whole tasks of task_rows) stay below
+    // 2^24 entries, and the values it scores below 2^27 -- known only once the plan has run, so a chunk that scores
+    // more is halved and planned again (a single query scores what its lists keep, whatever that is)
+    const int64_t tasks_per_query = ix->len_prefix[P] / plan.task_rows + P;
+    constexpr int64_t kTableCap = (int64_t)1 << 24, kValueCap = (int64_t)1 << 27;
+    int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(nq, kTableCap / std::max<int64_t>(tasks_per_query, P + 1)));
+    for (int q0 = 0; q0 < nq;) {
+        const int cn = std::min(chunk, nq - q0);
+        const size_t cnt_b = plan.cnt_mode == 2 ? ((sizeof(uint32_t) * (size_t)cn * P + 255) & ~(size_t)255) : 0;
+        if (plan.cnt_mode == 2) PGV_TRY(ctx->plan_a.ensure(cnt_b));
+        PGV_TRY(ctx->plan_b.ensure(sizeof(unsigned long long) * (size_t)cn * (P + 1)));
+        PGV_TRY(ctx->plan_c.ensure(256));
+        PGV_TRY(ctx->tasks.ensure(sizeof(IvfFilterTask) * (size_t)cn * (size_t)tasks_per_query));
+        PGV_TRY(ctx->pairs.ensure(sizeof(IvfFilterSeg) * (size_t)cn * nrounds));
+        plan.nq = cn;
+        plan.lists = lists + (size_t)q0 * P;
+        plan.cnt = ctx->plan_a.as<uint32_t>();
+        plan.pre = ctx->plan_b.as<unsigned long long>();
+        plan.totals = ctx->plan_c.as<unsigned long long>();
+        plan.tasks = ctx->tasks.as<IvfFilterTask>();
+        plan.segs = ctx->pairs.as<IvfFilterSeg>();
+        plan.out_dist = od.as<float>() + (size_t)q0 * k;
+        plan.out_slot = os.as<int64_t>() + (size_t)q0 * k;
+        plan.out_tid = out_tid ? ot.as<uint64_t>() + (size_t)q0 * k : nullptr;
+        plan.out_count = oc.as<int32_t>() + q0;
+        plan.out_probes = out_probes ? op.as<int32_t>() + q0 : nullptr;
+        const uint32_t *ck = kd ? kd + (size_t)q0 * (size_t)keep_stride : nullptr;
+        if (plan.cnt_mode == 2)
+            PGV_TRY(launch_ivf_keep_count(ctx, ck, keep_stride, plan.lists, P, ix->list_offsets, (int64_t)cn * P,
+                                          ctx->plan_a.as<uint32_t>()));
+        PGV_HIP(hipMemsetAsync(plan.totals, 0, 3 * sizeof(unsigned long long), ctx->stream));
+        PGV_TRY(launch_ivf_filter_plan(ctx, plan));
+        unsigned long long totals[3];
+        PGV_HIP(hipMemcpyAsync(totals, plan.totals, sizeof(totals), hipMemcpyDeviceToHost, ctx->stream));
+        PGV_HIP(hipStreamSynchronize(ctx->stream));
+        if ((int64_t)totals[0] > kValueCap && cn > 1) {
+            chunk = (cn + 1) / 2;
+            continue;
+        }
+        if (totals[0] > 0) {
+            // (4 floats of slack at either end: the selection's vector loads start at the 16-byte boundary below a segment)
+            PGV_TRY(ctx->plan_d.ensure(sizeof(float) * ((size_t)totals[0] + 8)));
+            PGV_TRY(ctx->dist_mat.ensure(sizeof(int64_t) * (size_t)totals[0]));
+            float *vals = ctx->plan_d.as<float>() + 4;
+            int64_t *slots = ctx->dist_mat.as<int64_t>();
+            PGV_TRY(scan_turn_begin(ctx));
+            ScanTimer timer{ctx};
+            PGV_TRY(timer.begin((double)totals[0], (double)totals[0]));
+            PGV_TRY(launch_ivf_filtered_scan(ctx, ivf_rows(ix), static_cast<const char *>(q_dev) + (size_t)q0 * ivf_rows(ix).row_bytes(),
+                                             ck, keep_stride, plan, (int64_t)totals[1], vals, slots));
+            PGV_TRY(timer.end());
+            PGV_TRY(scan_turn_end(ctx));
+            PGV_TRY(launch_ivf_filter_emit(ctx, vals, slots, plan, (int64_t)totals[2], ix->tids));
+        }
+        q0 += cn;
+    }
+    bool need = false;
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(os.finish(ctx, &need));
+    PGV_TRY(ot.finish(ctx, &need));
+    PGV_TRY(oc.finish(ctx, &need));
+    PGV_TRY(op.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
 // the query cast of the shadow paths on its own (tests: shadow_query_kernel's outputs against a host model)
 int pgv_index_shadow_cast(pgv_index *ix, const void *queries, int nq, void *out_qcast, float *out_qscale, float *out_qeps,
                           float *out_cscale, float *out_ceps) {

@@ -871,6 +871,50 @@ int launch_topk_segments(pgv_ctx *ctx, const float *vals, const int64_t *seg_sta
 int launch_positions_to_slots(pgv_ctx *ctx, const pgv_index *ix, const int32_t *probe_lists,
                               const int64_t *probe_off, int nq, int probes, int k,
                               const int64_t *pos, int64_t *out_slot, uint64_t *out_tid);
+// kernels_ivf_filter.hip: the iterative list scan under a keep bitmap (pgv_search_filtered): count the
+// kept rows of every (query, ranked list), plan the rounds each query needs, score only the kept rows of those rounds,
+// select and emit.  One score task: rows [row0, row0 + nrows) of the list that starts at list_beg, for one query; the
+// list's kept rows go to out0 + (position among the list's kept rows)
+struct IvfFilterTask {
+    int64_t row0, out0, list_beg;
+    int32_t nrows, query;
+};
+// one (query, round) with kept rows: its values at [start, start + len), of which the kseg smallest are emitted to
+// out[query * k + out_at ..)
+struct IvfFilterSeg {
+    int64_t start;
+    uint32_t len;
+    int32_t query, kseg, out_at;
+};
+struct IvfFilterPlan {  // all device arrays; the queries are those of one chunk
+    const int32_t *lists = nullptr;     // [nq x P] ranked lists
+    const int64_t *list_off = nullptr;  // the index's list offsets
+    const uint32_t *cnt = nullptr;      // kept rows: cnt_mode 0 none (no bitmap) | 1 [nlists] | 2 [nq x P]
+    int cnt_mode = 0;
+    int nq = 0, P = 0, probes = 0, k = 0;
+    int task_rows = 0, task_rows_max = 0;  // ivf_filter_task_rows
+    unsigned long long *pre = nullptr;     // [nq x (P + 1)] scratch: kept rows in front of each ranked list
+    unsigned long long *totals = nullptr;  // [3] zero before the plan: values scored | tasks | segments
+    IvfFilterTask *tasks = nullptr;        // room for nq x (rows of the P longest lists / task_rows + P)
+    IvfFilterSeg *segs = nullptr;          // room for nq x ceil(P / probes)
+    float *out_dist = nullptr;             // [nq x k]
+    int64_t *out_slot = nullptr;           // [nq x k]
+    uint64_t *out_tid = nullptr;           // [nq x k] or null
+    int32_t *out_count = nullptr;          // [nq]
+    int32_t *out_probes = nullptr;         // [nq] or null
+};
+void ivf_filter_task_rows(int *task_rows, int *task_rows_max);
+// lists null: item i = list i under the one bitmap; else item i = ranked list lists[i] of query i / P under its own
+int launch_ivf_keep_count(pgv_ctx *ctx, const uint32_t *keep, int64_t keep_stride, const int32_t *lists, int P,
+                          const int64_t *list_off, int64_t nitems, uint32_t *out);
+int launch_ivf_filter_plan(pgv_ctx *ctx, const IvfFilterPlan &p);
+// ntasks / nsegs: the plan's totals (or bounds of them); the values are bit for bit launch_scan's with one query a task
+int launch_ivf_filtered_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const uint32_t *keep, int64_t keep_stride,
+                             const IvfFilterPlan &p, int64_t ntasks, float *out_val, int64_t *out_slot);
+// vals: 3 readable floats in front and behind (pgv_select.h's vector loads)
+int launch_ivf_filter_emit(pgv_ctx *ctx, const float *vals, const int64_t *slots, const IvfFilterPlan &p, int64_t nsegs,
+                           const uint64_t *tids);
+
 // kernels_query.hip: the exact tail of the MFMA L2 scans.  The rows the candidates come
 // from: an index's tuples (list_offsets set) or its centers (one dense run)
 struct ExactRows {
