@@ -49,7 +49,7 @@
 //     of the tile -- and out_rel): the query words are then addressed from SGPRs, arrive through the scalar cache and
 //     the inner step keeps the `v_xor_b32 v, s, v` + `v_bcnt_u32_b32` form.  The alternative -- staging the group's query slices in LDS as
 //     scan_kernel does (QT x 128 B per slice, a ds_read per word) -- was not built: UNMEASURED against this one
-#include "pgv_device.h"
+#include "lane_rows.h"
 
 namespace pgv {
 
@@ -92,7 +92,7 @@ __device__ __forceinline__ void hamming_tile(Raw16 *tile, const char *task_rows,
     auto fetch = [&](int s) {
         const int vi = s * kBitSliceVecs + lv;
         const bool ok = vi < nvec;
-        const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
+        const int vc = ok ? vi : nvec - 1;  // never predicate a load (lane_rows.h)
 #pragma unroll
         for (int i = 0; i < kBitSliceVecs; i++) {
             int r = lr + i * kBitRowsPerTrip;
@@ -265,18 +265,8 @@ __global__ __launch_bounds__(kBitThreads) void hamming_list_kernel(
     const int tid = threadIdx.x;
     const int ntasks = *ntasks_ptr;
 
-    for (;;) {
-        if (tid == 0) lds_task = atomicAdd(task_counter, 1);
-        __syncthreads();
-        const int t = uniform32(lds_task);
-        if (t >= ntasks) {
-            // every workgroup ends here exactly once; the last one leaves both words zero for the next launch
-            if (tid == 0 && atomicAdd(task_counter + 1, 1) == (int)gridDim.x - 1) {
-                atomicExch(task_counter + 1, 0);
-                atomicExch(task_counter, 0);
-            }
-            return;
-        }
+    for (int task; pull_task(task_counter, ntasks, &lds_task, &task);) {
+        const int t = uniform32(task);
         const int64_t row0 = uniform64(tasks[t].row0);
         const int nrows = uniform32(tasks[t].nrows);
         const int pair0 = uniform32(tasks[t].pair0);

@@ -369,21 +369,14 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
     const size_t row_bytes = (size_t)g.nvec * sizeof(Raw16);
     uint32_t *bitmap = bitmaps + (size_t)blockIdx.x * words;  // (a scan's: the query's own, set below)
 
-    // distance of the query (in LDS) to the rows bi[0 .. nb): every wavefront takes R x rpw rows per trip -- R rows' loads
-    // in flight per lane group.  A walk is a chain of ~100 such batches, each waiting for its rows: with one row per trip
-    // a batch of 32 neighbors was eight dependent round trips to HBM per wavefront (same box, 400 k x 1536, ef 100:
-    // 352 k QPS with R = 1, 456 k with R = 2; 1 M x 1536: 366-403 k with R = 2, 385-413 k with R = 4, the default;
-    // profiles/r05/hnsw_build_device_link.md).  Each row keeps its own accumulator and element order: the distances do not
-    // depend on R.
-    // A bit mirror (T = BitRow, bit_hamming_ops: hamming_distance, src/bitvec.c:45-56) counts the differing bits of the
-    // same 16-byte vectors in an integer; the count (<= 64 000) and every partial sum of the reduction are exact in fp32.
-    // A Jaccard mirror (<BitRow, 1>, bit_jaccard_ops: jaccard_distance, src/bitvec.c:60-70 over BitJaccardDistanceDefault,
-    // src/bitutils.c:99-131) counts two integers in the same loop, x = popcount(a ^ b) and u = popcount(a | b), both exact
-    // like the Hamming count, and one lane forms jaccard_key(x, u): an integer that orders and ties exactly as the
-    // reference's float8 does (pgv_device.h), so everything that compares keys serves it unchanged.  A key does not carry
-    // (x, u): where distances are handed back (OUT: a search's results, a build's W of every searched layer), the elements
-    // jids[0 .. nb) -- at most ef -- are scored once more by this loop and jout[i] = jaccard_value(x, u), the (float) of the
-    // reference's float8.
+    // distance of the query (in LDS) to the rows bi[0 .. nb): lane_rows.h's rule -- its clamped trip, accumulators and
+    // epilogue -- written out here, because through the header the fp32 walk measured 13 % slower
+    // (profiles/r33_lane_rows.md).  Every wavefront takes R x rpw rows per trip; same box, 400 k x 1536, ef 100: 352 k QPS
+    // with R = 1, 456 k with R = 2; 1 M x 1536: 366-403 k with R = 2, 385-413 k with R = 4, the default
+    // (profiles/r05/hnsw_build_device_link.md).  The distances do not depend on R.
+    // A Jaccard walk's key does not carry (x, u): where distances are handed back (OUT: a search's results, a build's W of
+    // every searched layer), the elements jids[0 .. nb) -- at most ef -- are scored once more by this loop and jout[i] =
+    // jaccard_value(x, u), the (float) of the reference's float8.
     const uint32_t *jids = nullptr;
     float *jout = nullptr;
     auto score_rows = [&](auto rc, auto oc, int nb) __attribute__((always_inline)) {
@@ -412,7 +405,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
             for (int c = 0; c < g.nchunks; c++) {
                 const int vi = c * lpr + sub;
                 const bool ok = vi < g.nvec;
-                const int vc = ok ? vi : g.nvec - 1;  // never predicate a load (see scan_kernel)
+                const int vc = ok ? vi : g.nvec - 1;  // never predicate a load (lane_rows.h)
                 Raw16 rv[R];
 #pragma unroll
                 for (int r = 0; r < R; r++) rv[r] = load16(rp[r] + (size_t)vc * sizeof(Raw16));
@@ -477,7 +470,7 @@ __global__ __launch_bounds__(kHnswThreads) void hnsw_search_kernel(
         const int mine = nb > wave ? (nb - wave + kHnswWaves - 1) / kHnswWaves : 0;  // <= 50 < 64: one lane per row
         if (mine == 0) return;
         const int ij = wave + kHnswWaves * lane;
-        const int32_t ej = bi[ij < nb ? ij : nb - 1];  // never predicate a load (see scan_kernel)
+        const int32_t ej = bi[ij < nb ? ij : nb - 1];  // never predicate a load (lane_rows.h)
         const int64_t rbj = sp.row_ptr[ej];
         const int rnj = (int)(sp.row_ptr[ej + 1] - rbj);
         RegRow cur;

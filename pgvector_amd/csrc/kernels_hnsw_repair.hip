@@ -35,8 +35,7 @@
 //     on the next while the live entry that replaced it is still among the entry points, so the certain bound is
 //     (layers searched) x (dead elements) -- callers double dead_cap and redo (pgv_host_hnsw_repair).
 //   * A separate kernel: hnsw_search_kernel's instantiations are not touched (profiles/r31_hnsw_repair.md has their
-//     resource usage on both commits).  The row scoring is the walk's: the same loads, the same accumulator per row and
-//     the same element order, so a distance is the walk's distance bit for bit.
+//     resource usage on both commits).  The row scoring is a hand-written copy of lane_rows.h's rule, as the walk's.
 #include "pgv_device.h"
 
 namespace pgv {
@@ -127,8 +126,8 @@ __global__ __launch_bounds__(kRepairThreads) void hnsw_repair_kernel(RepairDev g
         return !g.live || ((g.live[e >> 5] >> (e & 31)) & 1u);
     };
 
-    // distance of the query (in LDS) to the rows bi[0 .. nb) into bk: the walk's score_rows at four rows a trip -- every
-    // row its own accumulator, the elements in the same order, so the keys are the walk's
+    // distance of the query (in LDS) to the rows bi[0 .. nb) into bk: lane_rows.h's clamped trip at four rows a trip,
+    // written out here (through the header this kernel measured slower over fp16 rows, profiles/r33_lane_rows.md)
     auto score_batch = [&](int nb) __attribute__((always_inline)) {
         constexpr int R = 4;
         const int step = kRepairWaves * rpw;

@@ -14,12 +14,11 @@
 //                              order, so a round's segment is a slice of that run: [pre[r probes], pre[(r + 1) probes])
 //   ivf_filtered_scan_kernel   persistent workgroups pull tasks (query, row range of one list): the query into LDS, the
 //                              range's kept row offsets compacted into LDS in slot order by one wavefront (a keep word a
-//                              lane, popcount prefix), then ONLY the kept rows scored in scan_kernel's lane layout --
-//                              1 << lpr_log2 lanes a row, 16-byte slices, R rows in flight per lane, loads never
-//                              predicated -- with its element order and group_sum_to_last: the values are bit for bit
-//                              pgv_scan_lists'.  Value and slot land at the row's position inside its segment
+//                              lane, popcount prefix), then ONLY the kept rows scored, by lane_rows.h's rule as
+//                              scan_kernel streams them.  Value and slot land at the row's position inside its segment
 //   ivf_filter_emit_kernel     pgv_select.h's selection over each segment for the rows the round can still emit
 //                              (min(kept, k - emitted before)), written straight behind the earlier rounds' rows
+#include "lane_rows.h"
 #include "pgv_select.h"
 
 namespace pgv {
@@ -171,7 +170,6 @@ __global__ __launch_bounds__(kFiltThreads, 4) void ivf_filtered_scan_kernel(
     const char *__restrict__ rows, const char *__restrict__ queries, const uint32_t *__restrict__ keep, int64_t keep_stride,
     const IvfFilterTask *__restrict__ tasks, const unsigned long long *__restrict__ totals, int *__restrict__ task_counter,
     float *__restrict__ out_val, int64_t *__restrict__ out_slot, int nvec, int lpr_log2, int nchunks, int kept_cap) {
-    constexpr int N = VecTraits<T>::N;
     constexpr int R = kFiltR<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // layout: [nvec] Raw16 query slices | [kept_cap] uint16 kept row offsets | task id, kept rows, kept in front per wave
@@ -181,27 +179,12 @@ __global__ __launch_bounds__(kFiltThreads, 4) void ivf_filtered_scan_kernel(
     int *lds_nk = lds_task + 1;
     unsigned *lds_front = reinterpret_cast<unsigned *>(lds_task + 2);  // [kFiltWaves]
 
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int lpr = 1 << lpr_log2;
-    const int sub = lane & (lpr - 1);   // which slice of the row
-    const int rsub = lane >> lpr_log2;  // which row of the wave-load
-    const int rpw = kWave >> lpr_log2;  // rows per wave-load
+    const LaneSplit ls(lpr_log2);
+    const int lane = ls.lane, wave = ls.wave;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
     const int ntasks = (int)totals[1];
 
-    for (;;) {
-        if (threadIdx.x == 0) *lds_task = atomicAdd(task_counter, 1);
-        __syncthreads();
-        const int t = *lds_task;
-        if (t >= ntasks) {
-            // every workgroup ends here exactly once; the last one leaves both words zero for the next launch
-            if (threadIdx.x == 0 && atomicAdd(task_counter + 1, 1) == (int)gridDim.x - 1) {
-                atomicExch(task_counter + 1, 0);
-                atomicExch(task_counter, 0);
-            }
-            return;
-        }
+    for (int t; pull_task(task_counter, ntasks, lds_task, &t);) {
         const IvfFilterTask task = tasks[t];
         for (int i = threadIdx.x; i < nvec; i += kFiltThreads)
             lds_q[i] = load16(queries + (size_t)task.query * row_bytes + (size_t)i * sizeof(Raw16));
@@ -247,61 +230,22 @@ __global__ __launch_bounds__(kFiltThreads, 4) void ivf_filtered_scan_kernel(
         const char *task_rows = rows + (size_t)task.row0 * row_bytes;
         auto row_of = [&](int idx) { return keep ? (int)lds_kept[idx] : idx; };
 
-        for (int b = wave; b * R * rpw < nk; b += kFiltWaves) {
-            float acc[R];
-#pragma unroll
-            for (int r = 0; r < R; r++) acc[r] = 0.f;
+        for (int b = wave; b * R * ls.rpw < nk; b += kFiltWaves) {
+            PairAcc<T, METRIC> acc[R][1];
             const char *rp[R];
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                int idx = b * R * rpw + r * rpw + rsub;
+                int idx = b * R * ls.rpw + r * ls.rpw + ls.rsub;
                 idx = idx < nk ? idx : nk - 1;  // tail rows are computed, not stored
                 rp[r] = task_rows + (size_t)row_of(idx) * row_bytes;
             }
-            // scan_kernel's trip over the row for one query: the loads of slice c + 1 in flight while slice c is scored,
-            // no load predicated, a ragged last slice with its address clamped and its operands zeroed
-            const int nfull = nvec >> lpr_log2;
-            auto score = [&](const Raw16(&rowv)[R], int vq, bool ok, auto masked) {
-                Unpacked<T> uq(lds_q[vq]);
-                if constexpr (decltype(masked)::value) {
-#pragma unroll
-                    for (int e = 0; e < N; e++) uq.v[e] = ok ? uq.v[e] : 0.f;
-                }
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    Unpacked<T> u(rowv[r]);
-#pragma unroll
-                    for (int e = 0; e < N; e++)
-                        acc[r] = accum<METRIC>(acc[r], (decltype(masked)::value && !ok) ? 0.f : u.v[e], uq.v[e]);
-                }
-            };
-            Raw16 cur[R], nxt[R];
-            {
-                const int vi = sub < nvec ? sub : nvec - 1;
-#pragma unroll
-                for (int r = 0; r < R; r++) cur[r] = load16(rp[r] + (size_t)vi * sizeof(Raw16));
-            }
-            for (int c = 0; c < nfull; c++) {
-                const int vi = c * lpr + sub;
-                int vn = vi + lpr;
-                vn = vn < nvec ? vn : nvec - 1;
-#pragma unroll
-                for (int r = 0; r < R; r++) nxt[r] = load16(rp[r] + (size_t)vn * sizeof(Raw16));
-                score(cur, vi, true, std::false_type{});
-#pragma unroll
-                for (int r = 0; r < R; r++) cur[r] = nxt[r];
-            }
-            if (nfull < nchunks) {
-                const int vi = nfull * lpr + sub;
-                const bool ok = vi < nvec;
-                score(cur, ok ? vi : nvec - 1, ok, std::true_type{});
-            }
+            stream_rows(acc, rp, lds_q, ls, nvec, lpr_log2, nchunks);
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                const int idx = b * R * rpw + r * rpw + rsub;
-                const float s = group_sum_to_last(acc[r], lpr_log2);
-                if (sub == lpr - 1 && idx < nk) {
-                    out_val[out0 + idx] = finish<METRIC>(s);
+                const int idx = b * R * ls.rpw + r * ls.rpw + ls.rsub;
+                acc[r][0].fold(lpr_log2);
+                if (ls.last() && idx < nk) {
+                    out_val[out0 + idx] = acc[r][0].value();
                     out_slot[out0 + idx] = task.row0 + row_of(idx);
                 }
             }

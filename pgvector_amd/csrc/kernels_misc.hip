@@ -5,7 +5,7 @@
 //                     fp32 accumulators, the division and the clamp in double)
 //   hamming_distance, jaccard_distance   src/bitvec.c:45-70 over src/bitutils.c:49-131
 // Both are plain HBM streaming: rows are read once with 16-byte loads, the query stays in L2.
-#include "pgv_device.h"
+#include "lane_rows.h"
 
 namespace pgv {
 
@@ -14,28 +14,23 @@ namespace {
 constexpr int kMiscThreads = 256;
 constexpr int kMiscWaves = kMiscThreads / kWave;
 
-// lanes cooperating on a row like scan_kernel: (1 << lpr_log2) adjacent lanes, nchunks trips
+// lanes cooperating on a row by lane_rows.h's split; three sums a row, so the epilogues are their own
 template <typename T>
 __global__ __launch_bounds__(kMiscThreads) void cosine_kernel(const char *__restrict__ rows, const char *__restrict__ query,
                                                               int64_t n, double *__restrict__ out, int nvec,
                                                               int lpr_log2, int nchunks) {
     constexpr int N = VecTraits<T>::N;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int lpr = 1 << lpr_log2;
-    const int sub = lane & (lpr - 1);
-    const int rsub = lane >> lpr_log2;
-    const int rpw = kWave >> lpr_log2;
+    const LaneSplit ls(lpr_log2);
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    const int64_t i = ((int64_t)blockIdx.x * kMiscWaves + wave) * rpw + rsub;
+    const int64_t i = ((int64_t)blockIdx.x * kMiscWaves + ls.wave) * ls.rpw + ls.rsub;
     const bool valid = i < n;
     const char *rp = rows + (size_t)(valid ? i : n - 1) * row_bytes;
     // similarity += ax[i] * bx[i]; norma += ax[i] * ax[i]; normb += bx[i] * bx[i]  (vector.c:656-662)
     float sim = 0.f, na = 0.f, nb = 0.f;
     for (int c = 0; c < nchunks; c++) {
-        const int vi = c * lpr + sub;
+        const int vi = c * ls.lpr + ls.sub;
         const bool ok = vi < nvec;
-        const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
+        const int vc = ok ? vi : nvec - 1;
         const Raw16 rv = load16(rp + (size_t)vc * sizeof(Raw16));
         const Raw16 qv = load16(query + (size_t)vc * sizeof(Raw16));
         Unpacked<T> ur(rv);
@@ -51,7 +46,7 @@ __global__ __launch_bounds__(kMiscThreads) void cosine_kernel(const char *__rest
     sim = group_sum_to_last(sim, lpr_log2);
     na = group_sum_to_last(na, lpr_log2);
     nb = group_sum_to_last(nb, lpr_log2);
-    if (sub == lpr - 1 && valid) {
+    if (ls.last() && valid) {
         // Use sqrt(a * b) over sqrt(a) * sqrt(b) (vector.c:664-665), then cosine_distance's clamp (:688-694)
         double similarity = (double)sim / sqrt((double)na * (double)nb);
         if (similarity > 1.0)
@@ -68,20 +63,15 @@ template <int MODE>
 __global__ __launch_bounds__(kMiscThreads) void bit_kernel(const char *__restrict__ rows, const char *__restrict__ query,
                                                            int64_t n, double *__restrict__ out, int nvec, int lpr_log2,
                                                            int nchunks) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int lpr = 1 << lpr_log2;
-    const int sub = lane & (lpr - 1);
-    const int rsub = lane >> lpr_log2;
-    const int rpw = kWave >> lpr_log2;
+    const LaneSplit ls(lpr_log2);
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
-    const int64_t i = ((int64_t)blockIdx.x * kMiscWaves + wave) * rpw + rsub;
+    const int64_t i = ((int64_t)blockIdx.x * kMiscWaves + ls.wave) * ls.rpw + ls.rsub;
     const bool valid = i < n;
     const char *rp = rows + (size_t)(valid ? i : n - 1) * row_bytes;
     // counts stay far below 2^24 (at most 64000 bits, src/ivfutils.c:416), so fp32 sums of them are exact
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     for (int c = 0; c < nchunks; c++) {
-        const int vi = c * lpr + sub;
+        const int vi = c * ls.lpr + ls.sub;
         const bool ok = vi < nvec;
         const int vc = ok ? vi : nvec - 1;
         const Raw16 rv = load16(rp + (size_t)vc * sizeof(Raw16));
@@ -108,7 +98,7 @@ __global__ __launch_bounds__(kMiscThreads) void bit_kernel(const char *__restric
         c1 = group_sum_to_last(c1, lpr_log2);
         c2 = group_sum_to_last(c2, lpr_log2);
     }
-    if (sub == lpr - 1 && valid) {
+    if (ls.last() && valid) {
         if (MODE == 0)
             out[i] = (double)c0;
         else

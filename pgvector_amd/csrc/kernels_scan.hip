@@ -5,18 +5,14 @@
 // (src/ivfkmeans.c:52-71): rows are streamed once from HBM with coalesced
 // 16-byte loads and scored against a small group of queries held in LDS.
 //
-//   * one wavefront (64 lanes) cooperates on rows: `1 << lpr_log2` adjacent
-//     lanes own one row, each lane a 16-byte slice per trip, R independent
-//     rows per lane in flight; partial sums are folded with DPP at the end.
+//   * the rows are scored by the lane-group rule of lane_rows.h, R independent rows per lane in flight.
 //   * a workgroup (4 waves) owns a ScanTask = a run of rows of one list x up
 //     to QT queries that probe that list; the rows are read from HBM once
 //     for all QT queries (query batching is where QPS beyond the single-query
 //     roofline comes from).
 //   * workgroups are persistent and pull tasks from a device counter, so
 //     ragged list lengths balance themselves.
-//   * fp32 accumulate in every case, fp16 rows converted exactly
-//     (src/halfutils.c:46-78 does the same with cvtph_ps).
-#include "pgv_device.h"
+#include "lane_rows.h"
 
 #include <type_traits>
 
@@ -38,35 +34,17 @@ __global__ __launch_bounds__(THREADS, scan_min_waves(QT, R)) void scan_kernel(
     const ScanTask *__restrict__ tasks, const int *__restrict__ ntasks_ptr,
     int *__restrict__ task_counter, const ScanPair *__restrict__ pairs, float *__restrict__ out,
     int nvec, int lpr_log2, int nchunks) {
-    constexpr int N = VecTraits<T>::N;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // layout: [QT * nvec] Raw16 query slices | [QT] int64 out_rel | int task id
     Raw16 *lds_q = reinterpret_cast<Raw16 *>(smem);
     int64_t *lds_rel = reinterpret_cast<int64_t *>(smem + (size_t)QT * nvec * sizeof(Raw16));
     int *lds_task = reinterpret_cast<int *>(lds_rel + QT);
 
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int lpr = 1 << lpr_log2;
-    const int sub = lane & (lpr - 1);  // which slice of the row
-    const int rsub = lane >> lpr_log2; // which row of the wave-load
-    const int rpw = kWave >> lpr_log2; // rows per wave-load
+    const LaneSplit ls(lpr_log2);
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
     const int ntasks = *ntasks_ptr;
 
-    for (;;) {
-        if (threadIdx.x == 0) *lds_task = atomicAdd(task_counter, 1);
-        __syncthreads();
-        const int t = *lds_task;
-        if (t >= ntasks) {
-            // every workgroup ends here exactly once; the last one leaves both words zero for the next launch
-            // (no memset launch per scan: k-means++ issues one scan per center)
-            if (threadIdx.x == 0 && atomicAdd(task_counter + 1, 1) == (int)gridDim.x - 1) {
-                atomicExch(task_counter + 1, 0);
-                atomicExch(task_counter, 0);
-            }
-            return;
-        }
+    for (int t; pull_task(task_counter, ntasks, lds_task, &t);) {
         const ScanTask task = tasks[t];
 
         // stage this task's queries (L2-resident) into LDS
@@ -83,79 +61,24 @@ __global__ __launch_bounds__(THREADS, scan_min_waves(QT, R)) void scan_kernel(
         __syncthreads();
 
         const char *task_rows = rows + (size_t)task.row0 * row_bytes;
-        for (int b = wave; b * R * rpw < task.nrows; b += THREADS / kWave) {
-            float acc[R][QT];
-#pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int q = 0; q < QT; q++) acc[r][q] = 0.f;
-
+        for (int b = ls.wave; b * R * ls.rpw < task.nrows; b += THREADS / kWave) {
+            PairAcc<T, METRIC> acc[R][QT];
             const char *rp[R];
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                int row = b * R * rpw + r * rpw + rsub;
+                int row = b * R * ls.rpw + r * ls.rpw + ls.rsub;
                 row = row < task.nrows ? row : task.nrows - 1;  // tail rows are computed, not stored
                 rp[r] = task_rows + (size_t)row * row_bytes;
             }
-
-            // Software-pipelined trip over the row: the loads of slice c+1 are in flight
-            // while slice c is scored.  Loads are never predicated (a branch around a load
-            // makes hipcc drain vmcnt per load).  Whole slices run without any masking; only
-            // a ragged last slice (dim not a multiple of the lane group) clamps its address
-            // and zeroes the operands of the lanes past the end.
-            const int nfull = nvec >> lpr_log2;
-            auto score = [&](const Raw16(&rowv)[R], int vq, bool ok, auto masked) {
-                float rf[R][N];
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    Unpacked<T> u(rowv[r]);
-#pragma unroll
-                    for (int e = 0; e < N; e++) rf[r][e] = (decltype(masked)::value && !ok) ? 0.f : u.v[e];
-                }
-#pragma unroll
-                for (int q = 0; q < QT; q++) {
-                    Unpacked<T> uq(lds_q[q * nvec + vq]);
-                    if constexpr (decltype(masked)::value) {
-#pragma unroll
-                        for (int e = 0; e < N; e++) uq.v[e] = ok ? uq.v[e] : 0.f;
-                    }
-#pragma unroll
-                    for (int r = 0; r < R; r++)
-#pragma unroll
-                        for (int e = 0; e < N; e++)
-                            acc[r][q] = accum<METRIC>(acc[r][q], rf[r][e], uq.v[e]);
-                }
-            };
-            Raw16 cur[R], nxt[R];
-            {
-                const int vi = sub < nvec ? sub : nvec - 1;
-#pragma unroll
-                for (int r = 0; r < R; r++) cur[r] = load16(rp[r] + (size_t)vi * sizeof(Raw16));
-            }
-            for (int c = 0; c < nfull; c++) {
-                const int vi = c * lpr + sub;
-                int vn = vi + lpr;
-                vn = vn < nvec ? vn : nvec - 1;
-#pragma unroll
-                for (int r = 0; r < R; r++) nxt[r] = load16(rp[r] + (size_t)vn * sizeof(Raw16));
-                score(cur, vi, true, std::false_type{});
-#pragma unroll
-                for (int r = 0; r < R; r++) cur[r] = nxt[r];
-            }
-            if (nfull < nchunks) {
-                const int vi = nfull * lpr + sub;
-                const bool ok = vi < nvec;
-                score(cur, ok ? vi : nvec - 1, ok, std::true_type{});
-            }
-
+            stream_rows(acc, rp, lds_q, ls, nvec, lpr_log2, nchunks);
 #pragma unroll
             for (int r = 0; r < R; r++) {
-                const int row = b * R * rpw + r * rpw + rsub;
+                const int row = b * R * ls.rpw + r * ls.rpw + ls.rsub;
 #pragma unroll
                 for (int q = 0; q < QT; q++) {
-                    float s = group_sum_to_last(acc[r][q], lpr_log2);
-                    if (sub == lpr - 1 && row < task.nrows && q < task.npairs)
-                        out[lds_rel[q] + task.row0 + row] = finish<METRIC>(s);
+                    acc[r][q].fold(lpr_log2);
+                    if (ls.last() && row < task.nrows && q < task.npairs)
+                        out[lds_rel[q] + task.row0 + row] = acc[r][q].value();
                 }
             }
         }
@@ -170,74 +93,29 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
     const char *__restrict__ rows, const char *__restrict__ queries,
     const int32_t *__restrict__ slot, const int32_t *__restrict__ query_of, int64_t npairs,
     float *__restrict__ out, int nvec, int lpr_log2, int nchunks) {
-    constexpr int N = VecTraits<T>::N;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int lpr = 1 << lpr_log2;
-    const int sub = lane & (lpr - 1);
-    const int rsub = lane >> lpr_log2;
-    const int rpw = kWave >> lpr_log2;
+    const LaneSplit ls(lpr_log2);
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
 
-    const int64_t base = ((int64_t)blockIdx.x * kScanWaves + wave) * R * rpw;
+    const int64_t base = ((int64_t)blockIdx.x * kScanWaves + ls.wave) * R * ls.rpw;
     if (base >= npairs) return;
 
-    constexpr bool kBits = std::is_same_v<T, BitRow>;  // packed bit rows: the differing bits, counted in an integer
-    // ... <BitRow, 1>, a Jaccard mirror: the bits set in either row as well, and the value is jaccard_distance's
-    constexpr bool kJaccard = kBits && METRIC == 1;
-    std::conditional_t<kBits, int, float> acc[R];
-    [[maybe_unused]] int uni[R];
+    PairAcc<T, METRIC> acc[R];  // (packed bit rows: <BitRow, 0> Hamming, <BitRow, 1> a Jaccard mirror)
     const char *rp[R];
     const char *qp[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-        int64_t p = base + r * rpw + rsub;
+        int64_t p = base + r * ls.rpw + ls.rsub;
         p = p < npairs ? p : npairs - 1;
-        acc[r] = 0;
-        if constexpr (kJaccard) uni[r] = 0;
         rp[r] = rows + (size_t)slot[p] * row_bytes;
         qp[r] = queries + (size_t)(query_of ? query_of[p] : 0) * row_bytes;
     }
-    for (int c = 0; c < nchunks; c++) {
-        const int vi = c * lpr + sub;
-        const bool ok = vi < nvec;
-        const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
-        Raw16 rv[R], qv[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            rv[r] = load16(rp[r] + (size_t)vc * sizeof(Raw16));
-            qv[r] = load16(qp[r] + (size_t)vc * sizeof(Raw16));
-        }
-        if constexpr (kJaccard) {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                acc[r] += ok ? hamming16(rv[r], qv[r]) : 0;
-                uni[r] += ok ? union16(rv[r], qv[r]) : 0;
-            }
-        } else if constexpr (kBits) {
-#pragma unroll
-            for (int r = 0; r < R; r++) acc[r] += ok ? hamming16(rv[r], qv[r]) : 0;
-        } else {
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                Unpacked<T> ur(rv[r]);
-                Unpacked<T> uq(qv[r]);
-#pragma unroll
-                for (int e = 0; e < N; e++)
-                    acc[r] = accum<METRIC>(acc[r], ok ? ur.v[e] : 0.f, ok ? uq.v[e] : 0.f);
-            }
-        }
-    }
+    for (int c = 0; c < nchunks; c++)
+        clamped_trip(acc, rp, [&](int r, int v) { return load16(qp[r] + (size_t)v * sizeof(Raw16)); }, ls, nvec, c);
 #pragma unroll
     for (int r = 0; r < R; r++) {
-        const int64_t p = base + r * rpw + rsub;
-        float s = group_sum_to_last((float)acc[r], lpr_log2);  // (a bit count and its partial sums are exact in fp32)
-        if constexpr (kJaccard) {
-            const int u = (int)group_sum_to_last((float)uni[r], lpr_log2);
-            if (sub == lpr - 1 && p < npairs) out[p] = jaccard_value((int)s, u);
-        } else {
-            if (sub == lpr - 1 && p < npairs) out[p] = finish<METRIC>(s);
-        }
+        const int64_t p = base + r * ls.rpw + ls.rsub;
+        acc[r].fold(lpr_log2);
+        if (ls.last() && p < npairs) out[p] = acc[r].value();
     }
 }
 
@@ -245,27 +123,16 @@ __global__ __launch_bounds__(kScanThreads) void score_gather_kernel(
 // neighbor list, src/hnswutils.c:1040-1059): group g is the rows ids[at .. at + n), wanted are the pairs (u, v < u) for
 // u >= from, written u ascending then v from pair_at[g] on.  score_gather_kernel reads both rows of every pair from L2
 // -- a 64-candidate list's 2016 pairs are 4032 row reads of 64 rows, and that traffic is what bounds it; here a worker (the
-// lanes that share a row) takes a TILE of 4 x 4 pairs: 8 row reads for 16 pairs.  Each pair keeps its own accumulator
-// and the element order, the lane split and the cross-lane sum of score_gather_kernel: the values are bit for bit the
-// same.  One workgroup per group, its workers take the group's tiles round-robin.
+// lanes that share a row) takes a TILE of 4 x 4 pairs: 8 row reads for 16 pairs, each pair with its own PairAcc fed as a
+// clamped trip feeds it.  One workgroup per group, its workers take the group's tiles round-robin.
 template <typename T, int METRIC>
 __global__ __launch_bounds__(kScanThreads) void score_groups_kernel(
     const char *__restrict__ rows, const int32_t *__restrict__ ids, const int64_t *__restrict__ ids_at, int64_t ids_stride,
     const int32_t *__restrict__ n_arr, const int32_t *__restrict__ from_arr, const int64_t *__restrict__ pair_at, int ngroups,
     float *__restrict__ out, int nvec, int lpr_log2, int nchunks) {
-    constexpr int N = VecTraits<T>::N;
     constexpr int TU = 4, TV = 4;
-    // packed bit rows (a buildable bit mirror, pgv_hnsw_upload_bits_buildable): 16 counts of differing bits, and under
-    // bit_jaccard_ops (<BitRow, 1>) 16 counts of the bits set in either row as well -- score_gather_kernel's integers
-    constexpr bool kBits = std::is_same_v<T, BitRow>;
-    constexpr bool kJaccard = kBits && METRIC == 1;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const int lpr = 1 << lpr_log2;
-    const int sub = lane & (lpr - 1);
-    const int rsub = lane >> lpr_log2;
-    const int rpw = kWave >> lpr_log2;
-    const int worker = wave * rpw + rsub, nworkers = kScanWaves * rpw;
+    const LaneSplit ls(lpr_log2);
+    const int worker = ls.wave * ls.rpw + ls.rsub, nworkers = kScanWaves * ls.rpw;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
     for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
         const int64_t p0 = pair_at[g];
@@ -287,60 +154,28 @@ __global__ __launch_bounds__(kScanThreads) void score_groups_kernel(
                 for (int i = 0; i < TU; i++) up[i] = rows + (size_t)gi[u0 + i < n ? u0 + i : n - 1] * row_bytes;
 #pragma unroll
                 for (int j = 0; j < TV; j++) vp[j] = rows + (size_t)gi[v0 + j < n ? v0 + j : n - 1] * row_bytes;
-                std::conditional_t<kBits, int, float> acc[TU][TV];
-                [[maybe_unused]] int uni[TU][TV];
-#pragma unroll
-                for (int i = 0; i < TU; i++)
-#pragma unroll
-                    for (int j = 0; j < TV; j++) {
-                        acc[i][j] = 0;
-                        if constexpr (kJaccard) uni[i][j] = 0;
-                    }
+                PairAcc<T, METRIC> acc[TU][TV];
                 for (int c = 0; c < nchunks; c++) {
-                    const int vi = c * lpr + sub;
+                    const int vi = c * ls.lpr + ls.sub;
                     const bool ok = vi < nvec;
-                    const int vc = ok ? vi : nvec - 1;  // never predicate a load (see scan_kernel)
+                    const int vc = ok ? vi : nvec - 1;
                     Raw16 ur[TU], vr[TV];
 #pragma unroll
                     for (int i = 0; i < TU; i++) ur[i] = load16(up[i] + (size_t)vc * sizeof(Raw16));
 #pragma unroll
                     for (int j = 0; j < TV; j++) vr[j] = load16(vp[j] + (size_t)vc * sizeof(Raw16));
-                    if constexpr (kBits) {
 #pragma unroll
-                        for (int i = 0; i < TU; i++)
+                    for (int i = 0; i < TU; i++)
 #pragma unroll
-                            for (int j = 0; j < TV; j++) {
-                                acc[i][j] += ok ? hamming16(ur[i], vr[j]) : 0;
-                                if constexpr (kJaccard) uni[i][j] += ok ? union16(ur[i], vr[j]) : 0;
-                            }
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < TU; i++) {
-                            Unpacked<T> a(ur[i]);
-#pragma unroll
-                            for (int j = 0; j < TV; j++) {
-                                Unpacked<T> b(vr[j]);
-#pragma unroll
-                                for (int e = 0; e < N; e++)
-                                    acc[i][j] = accum<METRIC>(acc[i][j], ok ? a.v[e] : 0.f, ok ? b.v[e] : 0.f);
-                            }
-                        }
-                    }
+                        for (int j = 0; j < TV; j++) acc[i][j].add(ur[i], vr[j], ok);
                 }
 #pragma unroll
                 for (int i = 0; i < TU; i++)
 #pragma unroll
                     for (int j = 0; j < TV; j++) {
-                        const float sum = group_sum_to_last((float)acc[i][j], lpr_log2);  // (a bit count: exact in fp32)
+                        acc[i][j].fold(lpr_log2);
                         const int u = u0 + i, v = v0 + j;
-                        const bool mine = sub == lpr - 1 && u < n && v < u;
-                        const int64_t at = p0 + (int64_t)u * (u - 1) / 2 - base + v;
-                        if constexpr (kJaccard) {
-                            const int bits = (int)group_sum_to_last((float)uni[i][j], lpr_log2);
-                            if (mine) out[at] = jaccard_value((int)sum, bits);
-                        } else {
-                            if (mine) out[at] = finish<METRIC>(sum);
-                        }
+                        if (ls.last() && u < n && v < u) out[p0 + (int64_t)u * (u - 1) / 2 - base + v] = acc[i][j].value();
                     }
             }
         }
