@@ -636,6 +636,23 @@ int			pgv_bit_topk(pgv_ctx * ctx, int nbits, const void *queries, int nq,
 						 const void *rows, int64_t n, int k, float *out_dist, int64_t *out_idx);
 
 /*
+ * `ORDER BY b <%> $1 LIMIT k` without an index, for a BATCH of queries (jaccard_distance src/bitvec.c:60-70 over
+ * BitJaccardDistanceDefault src/bitutils.c:99-131, feeding the executor's top-N sort): the exact Tanimoto search over
+ * fingerprints, and the ground truth of a bit_jaccard_ops index.  queries and rows as pgv_bit_topk takes them (VARBITS
+ * payloads of (nbits + 7) / 8 bytes, counted whole, pad bits zero; host or device; device rows whose byte length is a
+ * multiple of 16 are used in place).  out_idx [nq x k] row indexes in ascending order of the reference's float8, which
+ * is the order of the exact ratio x / u, x = popcount(a ^ b), u = popcount(a | b); u = 0 and x = u are both distance 1
+ * and tie with each other; equal float8 values go to the lower row index (pgv_exact_topk's rule).  No two different
+ * ratios are merged: the rows are ranked by an integer image of x / u that separates any two ratios of bit counts up
+ * to 64 000, not by a float.  out_dist [nq x k] is (float) of that float8, bit for bit (what pgv_hnsw_search returns
+ * over a Jaccard mirror); entries beyond n are +inf / -1.  1 <= k <= 4096, 0 <= nbits <= 64 000 (a longer string is
+ * PGV_ERR_DIMS: the image's proof ends there, as the Jaccard mirror's does; nbits == 0: every distance is 1, the
+ * answer is rows 0 .. min(k, n) - 1), n <= 2^32.  The queries are served in pgv_bit_topk's chunks.
+ */
+int			pgv_bit_jaccard_topk(pgv_ctx * ctx, int nbits, const void *queries, int nq,
+								 const void *rows, int64_t n, int k, float *out_dist, int64_t *out_idx);
+
+/*
  * binary_quantize (src/vector.c:952-979, halfvec_binary_quantize in src/halfvec.c): bit i = x[i] > 0, exactly the C
  * comparison -- +0.0, -0.0, NaN and negatives give 0, every positive value 1 (+inf and the subnormals included; the
  * bit is decided from the element's pattern, not by a floating-point compare).  rows [n x dim] host or device,

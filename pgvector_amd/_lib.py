@@ -57,6 +57,7 @@ SYMBOLS = [
     "pgv_hnsw_upload_sparse_buildable", "pgv_hnsw_buildable_sparse", "pgv_hnsw_elements",
     "pgv_hnsw_scan_begin_sparse", "pgv_hnsw_scan_filtered",
     "pgv_hnsw_set_live", "pgv_hnsw_live_count", "pgv_hnsw_repair_neighbors", "pgv_hnsw_repair_dead_cap_max",
+    "pgv_bit_jaccard_topk",
 ]
 
 
@@ -189,6 +190,7 @@ def _load():
     lib.pgv_cosine_distance_batch.argtypes = [P, I, I, P, P, I64, P]
     lib.pgv_bit_distance_batch.argtypes = [P, I, I, P, P, I64, P]
     lib.pgv_bit_topk.argtypes = [P, I, P, I, P, I64, I, P, P]
+    lib.pgv_bit_jaccard_topk.argtypes = [P, I, P, I, P, I64, I, P, P]
     lib.pgv_binary_quantize.argtypes = [P, I, I, P, I64, P]
     lib.pgv_rerank.argtypes = [P, I, I, I, P, I, P, I64, P, I, I, P, P]
     lib.pgv_index_upload_bits.argtypes = [P, I, I, P, P, P, P, C.POINTER(P)]

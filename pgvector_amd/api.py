@@ -585,6 +585,19 @@ def bit_topk(ctx, nbits, queries, rows, k, out=None):
     return dist, idx
 
 
+def bit_jaccard_topk(ctx, nbits, queries, rows, k, out=None):
+    """pgv_bit_jaccard_topk: `ORDER BY b <%> $1 LIMIT k` for a batch of packed bit strings of at most 64 000 bits, shaped
+    like bit_topk -> (dist [nq x k] float32: (float) of the reference's float8, idx [nq x k] int64), in the order of the
+    exact ratios popcount(a ^ b) / popcount(a | b), ties to the lower row"""
+    queries, rows = _as_bytes(queries), _as_bytes(rows)
+    nq, n = int(queries.shape[0]), int(rows.shape[0])
+    dist, idx = out if out is not None else (_empty_like_kind(queries, (nq, k), np.float32),
+                                            _empty_like_kind(queries, (nq, k), np.int64))
+    check(lib.pgv_bit_jaccard_topk(ctx.h, int(nbits), ptr(queries) if nbits and nq else None, nq,
+                                   ptr(rows) if nbits and n else None, n, int(k), ptr(dist), ptr(idx)))
+    return dist, idx
+
+
 _CSR_DTYPES = (np.int64, np.int32, np.float32)
 
 

@@ -4,6 +4,8 @@
 // for a batch of queries.
 //   hamming_tile_kernel      hamming_distance (src/bitvec.c:45-56 over BitHammingDistanceDefault, src/bitutils.c:49-73)
 //                            of a tile of rows against a tile of queries, into pgv_bit_topk's distance matrix
+//   jaccard_tile_kernel      the same tile under jaccard_distance (src/bitvec.c:60-70), into pgv_bit_jaccard_topk's matrix
+//                            of order images; bit_popcount_kernel in front of it, jaccard_values_kernel behind the selection
 //   binary_quantize_kernel   binary_quantize (src/vector.c:952-979, halfvec_binary_quantize in src/halfvec.c)
 //   rerank_*_kernel          what pgv_rerank needs around score_gather_kernel and topk_kernel
 //   hamming_list_kernel      the list scan of `USING ivfflat (col bit_hamming_ops)`: GetScanItems (src/ivfscan.c:123-187)
@@ -79,10 +81,12 @@ __device__ __forceinline__ int popc_add(uint32_t x, int acc) {
 
 // acc[q] += hamming(row tid of the tile, query q) for q < QT.  task_rows: the tile's first row; nrows in 1..256 of them
 // are real; qrow(q): the wave-uniform pointer to query q's words.  Every lane of the workgroup calls it; `tile` is free
-// for the next call once every lane has passed a barrier
-template <int QT, typename QRow>
+// for the next call once every lane has passed a barrier.
+// COMMON (jaccard_tile_kernel): the word operation is `and` instead of `xor` -- acc[q] += |row & query q|, the one count
+// jaccard_distance needs per pair -- and *row_pop += |row|, 32 more counts per slice whatever QT
+template <int QT, bool COMMON = false, typename QRow>
 __device__ __forceinline__ void hamming_tile(Raw16 *tile, const char *task_rows, int nrows, int nvec, QRow qrow,
-                                             int (&acc)[QT]) {
+                                             int (&acc)[QT], int *row_pop = nullptr) {
     const int tid = threadIdx.x;
     const int nslices = (nvec + kBitSliceVecs - 1) / kBitSliceVecs;
     const size_t row_bytes = (size_t)nvec * sizeof(Raw16);
@@ -112,6 +116,10 @@ __device__ __forceinline__ void hamming_tile(Raw16 *tile, const char *task_rows,
 #pragma unroll
         for (int v = 0; v < kBitSliceVecs; v++) rv[v] = tile[tid * kBitLdsStride + v];
         if (s + 1 < nslices) fetch(s + 1);
+        if constexpr (COMMON) {
+#pragma unroll
+            for (int i = 0; i < kBitSliceWords; i++) *row_pop = popc_add(rv[i / 4].w[i % 4], *row_pop);
+        }
 
         // four scalar loads of 8 words per query, each in flight while the 8 words before it are counted; the last
         // one of a query is followed by the first one of the next
@@ -130,7 +138,10 @@ __device__ __forceinline__ void hamming_tile(Raw16 *tile, const char *task_rows,
                     ahead = part(qp);
                 }
 #pragma unroll
-                for (int i = 0; i < 8; i++) acc[q] = popc_add(rv[2 * p + i / 4].w[i % 4] ^ cur[i], acc[q]);
+                for (int i = 0; i < 8; i++) {
+                    const uint32_t a = rv[2 * p + i / 4].w[i % 4];
+                    acc[q] = popc_add(COMMON ? a & cur[i] : a ^ cur[i], acc[q]);
+                }
                 cur = ahead;
             }
         }
@@ -159,6 +170,74 @@ __global__ __launch_bounds__(kBitThreads) void hamming_tile_kernel(const char *_
         for (int q = 0; q < kBitQueries; q++)
             if (q0 + q < nq) out[(size_t)(q0 + q) * (size_t)n + (size_t)(row0 + tid)] = (float)acc[q];
     }
+}
+
+// ---- pgv_bit_jaccard_topk: jaccard_distance (src/bitvec.c:60-70 over BitJaccardDistanceDefault, src/bitutils.c:99-131)
+// The same tile of 256 rows x 32 queries, counting ONE thing per word pair: c = |a & b|.  With pa = |a| (counted by the
+// lane from its own row's words as they pass through its registers) and pb = |b| (bit_popcount_kernel, once per call),
+// |a | b| = u = pa + pb - c and |a ^ b| = x = u - c, so the inner step stays the Hamming loop's two instructions a word.
+// What is stored is not the distance but its order image (jaccard_image, pgv_device.h): a finite float per pair whose
+// order and ties are those of the exact ratio x / u, which is what the selection needs; jaccard_values_kernel puts the
+// reference's value over the k selected ones afterwards.
+__global__ __launch_bounds__(kBitThreads) void jaccard_tile_kernel(const char *__restrict__ rows,
+                                                                   const uint32_t *__restrict__ queries,
+                                                                   const int *__restrict__ qpop, int64_t n, int nq, int nvec,
+                                                                   int qwords, int nqt, float *__restrict__ out) {
+    __shared__ Raw16 tile[kBitTileVecs];
+    const int qt = (int)(blockIdx.x % (unsigned)nqt);
+    const int64_t row0 = (int64_t)(blockIdx.x / (unsigned)nqt) * kBitThreads;
+    const int q0 = qt * kBitQueries;
+    const int nrows = n - row0 < kBitThreads ? (int)(n - row0) : kBitThreads;
+
+    int acc[kBitQueries] = {};
+    int pa = 0;
+    hamming_tile<kBitQueries, true>(
+        tile, rows + (size_t)row0 * ((size_t)nvec * sizeof(Raw16)), nrows, nvec,
+        [&](int q) { return queries + (size_t)(q0 + q < nq ? q0 + q : nq - 1) * qwords; }, acc, &pa);
+
+    const int tid = threadIdx.x;
+    if (tid < nrows) {
+#pragma unroll
+        for (int q = 0; q < kBitQueries; q++)
+            if (q0 + q < nq) {
+                const int u = pa + qpop[q0 + q] - acc[q];  // (qpop[q0 + q]: wave-uniform, a scalar load)
+                out[(size_t)(q0 + q) * (size_t)n + (size_t)(row0 + tid)] = jaccard_image(u - acc[q], u);
+            }
+    }
+}
+
+// qpop[q] = |query q| over its staged words (whole bytes, zero padding): one wavefront per query
+constexpr int kPopThreads = 256;
+__global__ __launch_bounds__(kPopThreads) void bit_popcount_kernel(const uint32_t *__restrict__ queries, int nq, int qwords,
+                                                                   int *__restrict__ qpop) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int q = blockIdx.x * (kPopThreads / kWave) + (threadIdx.x >> 6);
+    const uint32_t *p = queries + (size_t)(q < nq ? q : nq - 1) * qwords;
+    int c = 0;
+    for (int w = lane; w < qwords; w += kWave) c += __popc(p[w]);
+    const float total = group_sum_to_last((float)c, 6);  // (at most 64 000 + padding: exact in fp32, as lane_rows.h's counts)
+    if (lane == kWave - 1 && q < nq) qpop[q] = (int)total;
+}
+
+// out_dist[q * k + j] = (float) of the reference's float8 for (query q, row out_idx[q * k + j]), over the image the
+// selection left there: one lane group per selected pair counts x and u again with lane_rows.h's Jaccard accumulator
+// (the walk's jaccard_out does the same for its W).  A padding entry (index -1) keeps its +inf
+__global__ __launch_bounds__(kPopThreads) void jaccard_values_kernel(const char *__restrict__ rows,
+                                                                     const char *__restrict__ queries, int qbytes,
+                                                                     const int64_t *__restrict__ idx, int64_t npairs, int k,
+                                                                     float *__restrict__ out, int nvec, int lpr_log2,
+                                                                     int nchunks) {
+    const LaneSplit ls(lpr_log2);
+    const int64_t p = ((int64_t)blockIdx.x * (kPopThreads / kWave) + ls.wave) * ls.rpw + ls.rsub;
+    const int64_t pc = p < npairs ? p : npairs - 1;  // tail pairs are computed, not stored
+    const int64_t row = idx[pc];
+    PairAcc<BitRow, 1> acc[1];
+    const char *const rp[1] = {rows + (size_t)(row < 0 ? 0 : row) * ((size_t)nvec * sizeof(Raw16))};
+    const char *qp = queries + (size_t)(pc / k) * (size_t)qbytes;
+    for (int c = 0; c < nchunks; c++)
+        clamped_trip(acc, rp, [&](int, int v) { return load16(qp + (size_t)v * sizeof(Raw16)); }, ls, nvec, c);
+    acc[0].fold(lpr_log2);
+    if (ls.last() && p < npairs && row >= 0) out[p] = acc[0].value();
 }
 
 // bit i = x[i] > 0, decided from the element's bit pattern so that the denormal mode cannot matter: sign clear,
@@ -377,6 +456,46 @@ int launch_hamming_tiles(pgv_ctx *ctx, const RowsView &v, const void *queries, i
     hipLaunchKernelGGL(hamming_tile_kernel, dim3((unsigned)grid), dim3(kBitThreads), 0, ctx->stream,
                        static_cast<const char *>(v.rows), static_cast<const uint32_t *>(queries), n, nq, v.geom.nvec, qbytes / 4,
                        nqt, out);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_bit_popcounts(pgv_ctx *ctx, const void *queries, int qbytes, int nq, int *qpop) {
+    if (nq <= 0) return PGV_OK;
+    const int per = kPopThreads / kWave;
+    hipLaunchKernelGGL(bit_popcount_kernel, dim3((unsigned)((nq + per - 1) / per)), dim3(kPopThreads), 0, ctx->stream,
+                       static_cast<const uint32_t *>(queries), nq, qbytes / 4, qpop);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_jaccard_tiles(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const int *qpop, int nq,
+                         float *out) {
+    const int64_t n = v.n;
+    if (n <= 0 || nq <= 0) return PGV_OK;
+    if (!v.bits() || qbytes < bit_query_bytes(v.geom.ld * 8))
+        PGV_FAIL(PGV_ERR_ARG, "bit scan: bit rows, queries in whole slices");
+    if (v.geom.ld * 8 > kHnswMaxBits)  // the image's division needs u < 2^16, its proof 64 000 bits (whole 16-byte vectors)
+        PGV_FAIL(PGV_ERR_DIMS, "Jaccard scan: rows longer than %d bits", kHnswMaxBits);
+    const int nqt = (nq + kBitQueries - 1) / kBitQueries;
+    const int64_t grid = (n + kBitThreads - 1) / kBitThreads * nqt;
+    if (grid > 0x7fffffff) PGV_FAIL(PGV_ERR_ARG, "bit scan: too many tiles");
+    hipLaunchKernelGGL(jaccard_tile_kernel, dim3((unsigned)grid), dim3(kBitThreads), 0, ctx->stream,
+                       static_cast<const char *>(v.rows), static_cast<const uint32_t *>(queries), qpop, n, nq, v.geom.nvec,
+                       qbytes / 4, nqt, out);
+    PGV_HIP(hipGetLastError());
+    return PGV_OK;
+}
+
+int launch_jaccard_values(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const int64_t *idx, int nq, int k,
+                          float *out_dist) {
+    const int64_t npairs = (int64_t)nq * k;
+    if (v.n <= 0 || npairs <= 0) return PGV_OK;  // (no rows: every entry is padding)
+    if (!v.bits() || (size_t)qbytes < v.row_bytes()) PGV_FAIL(PGV_ERR_ARG, "Jaccard values: bit rows, queries no shorter");
+    const int64_t per = (int64_t)(kPopThreads / kWave) * (kWave >> v.geom.lpr_log2);  // pairs a workgroup
+    hipLaunchKernelGGL(jaccard_values_kernel, dim3((unsigned)((npairs + per - 1) / per)), dim3(kPopThreads), 0, ctx->stream,
+                       static_cast<const char *>(v.rows), static_cast<const char *>(queries), qbytes, idx, npairs, k, out_dist,
+                       v.geom.nvec, v.geom.lpr_log2, v.geom.nchunks);
     PGV_HIP(hipGetLastError());
     return PGV_OK;
 }

@@ -278,20 +278,29 @@ BitGeom bit_geom(int nbits) {
 }
 // staged bit rows [n x ld bytes] (ld: row_ld or q_ld) as the Hamming kernels take them
 RowsView bit_rows(const void *rows, int64_t n, int ld) { return {rows, n, bit_row_geom(ld * 8), RowKind::Bits, PGV_L1}; }
-}  // namespace
 
-// `ORDER BY b <~> $1 LIMIT k` without an index for a batch of queries: pgv_exact_topk's structure over packed bits.  The
-// scan (hamming_tile_kernel, kernels_bit.hip) fills the chunk's distance matrix mat[q * n + row] with the integer counts
-// as floats (exact: at most 512 000), launch_topk_segments selects with ties to the lower row.
-int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const void *rows, int64_t n, int k, float *out_dist,
-                 int64_t *out_idx) {
-    if (!ctx || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: ctx/out_dist/out_idx is NULL");
-    if (nbits < 0 || nbits > 64000 * 8) PGV_FAIL(PGV_ERR_DIMS, "bit length %d out of range", nbits);
-    if (nq < 0 || n < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: nq/n < 0");
-    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: k %d outside 1..4096", k);
-    if (n > 0xffffffffll) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: more than 2^32 rows");
-    if (nq == 0) return PGV_OK;
-    if (nbits > 0 && (!queries || (n > 0 && !rows))) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_topk: queries/rows is NULL");
+// what pgv_bit_topk and pgv_bit_jaccard_topk refuse alike, in pgv_bit_topk's words; max_bits is the entry's own limit and
+// why_max what it says about a longer string
+int check_bit_topk(const char *who, pgv_ctx *ctx, int nbits, int max_bits, const void *queries, int nq, const void *rows,
+                   int64_t n, int k, const float *out_dist, const int64_t *out_idx, const char *why_max = nullptr) {
+    if (!ctx || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "%s: ctx/out_dist/out_idx is NULL", who);
+    if (why_max && nbits > max_bits) PGV_FAIL(PGV_ERR_DIMS, "%s: bit length %d: %s", who, nbits, why_max);
+    if (nbits < 0 || nbits > max_bits) PGV_FAIL(PGV_ERR_DIMS, "bit length %d out of range", nbits);
+    if (nq < 0 || n < 0) PGV_FAIL(PGV_ERR_ARG, "%s: nq/n < 0", who);
+    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "%s: k %d outside 1..4096", who, k);
+    if (n > 0xffffffffll) PGV_FAIL(PGV_ERR_ARG, "%s: more than 2^32 rows", who);
+    if (nq > 0 && nbits > 0 && (!queries || (n > 0 && !rows))) PGV_FAIL(PGV_ERR_ARG, "%s: queries/rows is NULL", who);
+    return PGV_OK;
+}
+
+// The body of both entries behind their checks (nq > 0): stage queries and rows, then per chunk of queries fill the
+// chunk's matrix mat[q * n + row] and select from it.  begin(rows view, staged queries, q_ld) runs once in front of the
+// first chunk; scan(rows view, the chunk's queries, q_ld, q0, cn, mat) fills the matrix between the timer's events;
+// after(rows view, the chunk's queries, q_ld, cn, the chunk's out_dist, out_idx) follows the chunk's selection.  Neither
+// runs when there are no rows or no bits
+extern "C++" template <typename Begin, typename Scan, typename After>
+int bit_topk_chunks(pgv_ctx *ctx, int nbits, const void *queries, int nq, const void *rows, int64_t n, int k, float *out_dist,
+                    int64_t *out_idx, Begin begin, Scan scan, After after) {
     PGV_HIP(hipSetDevice(ctx->device));
     const int bytes = (nbits + 7) / 8;  // VARBITBYTES
     // rows in whole 16-byte vectors like pgv_bit_distance_batch's, queries in whole register slices of the scan kernel
@@ -302,6 +311,9 @@ int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const voi
         PGV_TRY(stage_rows(ctx, queries, nq, bytes, q_ld, ctx->q_stage, &q_dev));
         PGV_TRY(stage_rows(ctx, rows, n, bytes, g.row_ld, ctx->rows_stage, &r_dev));
     }
+    const bool scanned = bytes > 0 && n > 0;
+    const RowsView rv = scanned ? bit_rows(r_dev, n, g.row_ld) : RowsView{};
+    if (scanned) PGV_TRY(begin(rv, q_dev, q_ld));
     OutArg od, oi;
     PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
     PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
@@ -313,23 +325,88 @@ int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const voi
         const int cn = std::min(chunk, nq - q0);
         PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * std::max<size_t>((size_t)cn * (size_t)n, 4)));
         float *mat = ctx->dist_mat.as<float>();
+        const char *qp = scanned ? static_cast<const char *>(q_dev) + (size_t)q0 * q_ld : nullptr;
+        float *cd = od.as<float>() + (size_t)q0 * k;
+        int64_t *ci = oi.as<int64_t>() + (size_t)q0 * k;
         if (n > 0 && bytes == 0) {
             // empty bit strings: every distance is 0 (src/bitutils.c:71), so the ties leave rows 0 .. k - 1
             PGV_HIP(hipMemsetAsync(mat, 0, sizeof(float) * (size_t)cn * (size_t)n, ctx->stream));
         } else if (n > 0) {
             ScanTimer timer{ctx};
             PGV_TRY(timer.begin((double)n * cn, (double)n * ((cn + 31) / 32), true));
-            PGV_TRY(launch_hamming_tiles(ctx, bit_rows(r_dev, n, g.row_ld), static_cast<const char *>(q_dev) + (size_t)q0 * q_ld,
-                                         q_ld, cn, mat));
+            PGV_TRY(scan(rv, qp, q_ld, q0, cn, mat));
             PGV_TRY(timer.end());
         }
-        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, od.as<float>() + (size_t)q0 * k,
-                                     oi.as<int64_t>() + (size_t)q0 * k));
+        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, cd, ci));
+        if (scanned) PGV_TRY(after(rv, qp, q_ld, cn, cd, ci));
     }
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));
     PGV_TRY(oi.finish(ctx, &need));
     return sync_if(ctx, need);
+}
+}  // namespace
+
+// `ORDER BY b <~> $1 LIMIT k` without an index for a batch of queries: pgv_exact_topk's structure over packed bits.  The
+// scan (hamming_tile_kernel, kernels_bit.hip) fills the chunk's distance matrix mat[q * n + row] with the integer counts
+// as floats (exact: at most 512 000), launch_topk_segments selects with ties to the lower row.
+int pgv_bit_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const void *rows, int64_t n, int k, float *out_dist,
+                 int64_t *out_idx) {
+    PGV_TRY(check_bit_topk("pgv_bit_topk", ctx, nbits, 64000 * 8, queries, nq, rows, n, k, out_dist, out_idx));
+    if (nq == 0) return PGV_OK;
+    return bit_topk_chunks(
+        ctx, nbits, queries, nq, rows, n, k, out_dist, out_idx, [](const RowsView &, const void *, int) { return PGV_OK; },
+        [&](const RowsView &rv, const char *qp, int q_ld, int, int cn, float *mat) {
+            return launch_hamming_tiles(ctx, rv, qp, q_ld, cn, mat);
+        },
+        [](const RowsView &, const char *, int, int, float *, int64_t *) { return PGV_OK; });
+}
+
+// `ORDER BY b <%> $1 LIMIT k` without an index for a batch of queries: pgv_bit_topk's loop with three launches a chunk.
+// jaccard_tile_kernel fills the matrix with the pairs' order images (finite floats ordered and tied as the exact ratios
+// x / u are, which is how the reference's float8 values are: pgv_device.h), from the queries' popcounts, counted once in
+// front; launch_topk_segments selects as it does for any floats; jaccard_values_kernel writes the reference's value over
+// the image of every selected pair.
+int pgv_bit_jaccard_topk(pgv_ctx *ctx, int nbits, const void *queries, int nq, const void *rows, int64_t n, int k,
+                         float *out_dist, int64_t *out_idx) {
+    PGV_TRY(check_bit_topk("pgv_bit_jaccard_topk", ctx, nbits, kHnswMaxBits, queries, nq, rows, n, k, out_dist, out_idx,
+                           "the order image of a Jaccard distance is exact up to 64 000 bits"));
+    if (nq == 0) return PGV_OK;
+    if (nbits == 0) {
+        // empty bit strings share no bit: every distance is 1 (src/bitutils.c:127-128), the ties leave rows 0 .. k - 1
+        PGV_HIP(hipSetDevice(ctx->device));
+        std::vector<float> d((size_t)nq * k, INFINITY);
+        std::vector<int64_t> idx((size_t)nq * k, -1);
+        for (size_t q = 0; q < (size_t)nq; q++)
+            for (int64_t j = 0; j < k && j < n; j++) {
+                d[q * k + j] = 1.0f;
+                idx[q * k + j] = j;
+            }
+        OutArg od, oi;
+        PGV_TRY(od.init(out_dist, sizeof(float) * d.size(), ctx->out_stage));
+        PGV_TRY(oi.init(out_idx, sizeof(int64_t) * idx.size(), ctx->out_stage2));
+        PGV_HIP(hipMemcpyAsync(od.dev, d.data(), od.bytes, hipMemcpyHostToDevice, ctx->stream));
+        PGV_HIP(hipMemcpyAsync(oi.dev, idx.data(), oi.bytes, hipMemcpyHostToDevice, ctx->stream));
+        PGV_HIP(hipStreamSynchronize(ctx->stream));  // d and idx go out of scope
+        bool need = false;
+        PGV_TRY(od.finish(ctx, &need));
+        PGV_TRY(oi.finish(ctx, &need));
+        return sync_if(ctx, need);
+    }
+    const int *qpop = nullptr;
+    return bit_topk_chunks(
+        ctx, nbits, queries, nq, rows, n, k, out_dist, out_idx,
+        [&](const RowsView &, const void *q_dev, int q_ld) {
+            PGV_TRY(ctx->plan_a.ensure(sizeof(int) * (size_t)nq));
+            qpop = ctx->plan_a.as<int>();
+            return launch_bit_popcounts(ctx, q_dev, q_ld, nq, ctx->plan_a.as<int>());
+        },
+        [&](const RowsView &rv, const char *qp, int q_ld, int q0, int cn, float *mat) {
+            return launch_jaccard_tiles(ctx, rv, qp, q_ld, qpop + q0, cn, mat);
+        },
+        [&](const RowsView &rv, const char *qp, int q_ld, int cn, float *cd, int64_t *ci) {
+            return launch_jaccard_values(ctx, rv, qp, q_ld, ci, cn, k, cd);
+        });
 }
 
 int pgv_binary_quantize(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *rows, int64_t n, void *out_bits) {

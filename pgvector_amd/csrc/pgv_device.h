@@ -83,16 +83,19 @@ __device__ __forceinline__ int union16(const Raw16 &a, const Raw16 &b) {
 // u = 0 (two empty strings) and x = u (nothing in common) are both distance 1: key S.  Keys never reach 0xffffffff.
 constexpr uint32_t kJaccardScale = 0xFFFFFF00u;
 static_assert(kJaccardScale > 64000ull * 64000ull, "the Jaccard key must separate any two ratios of bit counts");
-__device__ __forceinline__ uint32_t jaccard_key(int x, int u) {
-    if (x >= u) return kJaccardScale;
-    // floor(x * S / u) by long division in 16-bit digits: u < 2^16 and the top digit of x * S is below u (x < u), so two
-    // 32-bit divisions give the two digits of the quotient -- a 64-bit division is several times the instructions
-    const uint64_t n = (uint64_t)(uint32_t)x * kJaccardScale;
+// floor(x * scale / u) for 0 <= x < u < 2^16 by long division in 16-bit digits: the top digit of x * scale is below u, so
+// two 32-bit divisions give the two digits of the quotient -- a 64-bit division is several times the instructions
+__device__ __forceinline__ uint32_t scaled_ratio(int x, int u, uint32_t scale) {
+    const uint64_t n = (uint64_t)(uint32_t)x * scale;
     const uint32_t d = (uint32_t)u;
     const uint32_t t1 = ((uint32_t)(n >> 32) << 16) | ((uint32_t)(n >> 16) & 0xffffu);
     const uint32_t q1 = t1 / d, r1 = t1 - q1 * d;
     const uint32_t t0 = (r1 << 16) | ((uint32_t)n & 0xffffu);
     return (q1 << 16) | (t0 / d);
+}
+__device__ __forceinline__ uint32_t jaccard_key(int x, int u) {
+    if (x >= u) return kJaccardScale;
+    return scaled_ratio(x, u, kJaccardScale);
 }
 // ... and the value handed back: (float) of the reference's float8 for the pair, bit for bit (IEEE double division: the
 // build has no fast-math flag)
@@ -348,6 +351,26 @@ __device__ __forceinline__ float key_to_float(uint32_t k) {
     if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
+}
+
+// The brute-force scan's image of a Jaccard distance (pgv_bit_jaccard_topk): the selection kernels read FLOATS, and
+// float_to_key merges every NaN pattern and the two zeros, so jaccard_key's 32 bits cannot be stored there as they are.
+// r = floor(x * S / u) in [0, S] (S when x >= u, u = 0 included; 64 000^2 < S: strictly monotone and injective on the
+// ratios, as above) goes to the float whose key is kJaccardImageBase + r, the key of -FLT_MAX being the base, and the
+// keys from the negative denormals through both zeros to the positive denormals (kJaccardImageGap of them) are stepped
+// over: every stored value is a finite NORMAL float, none is -0, so the image's order is that of its keys both for
+// float_to_key and for a float comparison, whether or not the comparing kernel flushes denormals.
+constexpr uint32_t kJaccardImageScale = 4200000000u;
+constexpr uint32_t kJaccardImageBase = 0x00800000u;   // float_to_key(-FLT_MAX)
+constexpr uint32_t kJaccardImageGapAt = 0x7f800000u;  // float_to_key of the negative denormal of largest magnitude
+constexpr uint32_t kJaccardImageGap = 0x01000000u;    // ... up to the positive one: 2 x (2^23 - 1) denormals, -0, +0
+static_assert(kJaccardImageScale > 64000ull * 64000ull, "the Jaccard image must separate any two ratios of bit counts");
+static_assert((uint64_t)kJaccardImageBase + kJaccardImageScale + kJaccardImageGap <= 0xff7fffffull,
+              "the Jaccard image must end at or below the key of FLT_MAX");
+__device__ __forceinline__ float jaccard_image(int x, int u) {
+    const uint32_t r = x >= u ? kJaccardImageScale : scaled_ratio(x, u, kJaccardImageScale);
+    const uint32_t key = kJaccardImageBase + r;
+    return key_to_float(key >= kJaccardImageGapAt ? key + kJaccardImageGap : key);
 }
 
 }  // namespace pgv

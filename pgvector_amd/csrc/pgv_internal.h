@@ -595,6 +595,17 @@ inline int bit_query_bytes(int nbits) {
     return ((nbits + 7) / 8 + slice - 1) / slice * slice;
 }
 int launch_hamming_tiles(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, int nq, float *out);
+// ... and under jaccard_distance (pgv_bit_jaccard_topk), rows of at most 64 000 bits.  launch_bit_popcounts: qpop[q] = the
+// bits set in staged query q.  launch_jaccard_tiles: the same rows, queries and tiles as launch_hamming_tiles, qpop the
+// popcounts of THESE queries; out[q * n + row] = the pair's order image (jaccard_image, pgv_device.h: finite floats in the
+// order of the exact distances, equal only where those are), what launch_topk_segments selects from.
+// launch_jaccard_values: out_dist[q * k + j] = (float) of the reference's float8 of (query q, row idx[q * k + j]) over
+// the nq x k selected entries; an entry with idx -1 is left as it is
+int launch_bit_popcounts(pgv_ctx *ctx, const void *queries, int qbytes, int nq, int *qpop);
+int launch_jaccard_tiles(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const int *qpop, int nq,
+                         float *out);
+int launch_jaccard_values(pgv_ctx *ctx, const RowsView &v, const void *queries, int qbytes, const int64_t *idx, int nq, int k,
+                          float *out_dist);
 // the list scan of a bit index (pgv_index::nbits): the plan of launch_plan_batch with 256 rows per task and qt queries per
 // group (hamming_list_group_size), the same rows and queries as launch_hamming_tiles; out[pair.out_rel + row]
 int hamming_list_group_size(double queries_per_list);
