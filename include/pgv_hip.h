@@ -744,6 +744,39 @@ int			pgv_sparse_topk(pgv_ctx * ctx, pgv_metric metric, int dim,
 							const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
 							int k, float *out_dist, int64_t *out_idx);
 
+/*
+ * The same top-k by inner product (sparsevec_ip_ops; cosine: normalised vectors) over rows that STAY on the device,
+ * inverted: pgv_sparse_topk visits every (query, row) pair, while only the indices both vectors store add a term to an
+ * inner product, so a query needs no more of the rows than the postings of the dimensions it stores.
+ *
+ * pgv_sparse_rows_upload: n rows in CSR under the rules of this section (host arrays validated with the same texts, device
+ * arrays unchecked -- except a device row_ptr, whose host copy is checked like a host one) -> a mirror of 8 bytes a stored
+ * element plus a directory of 8 bytes per (block of 4096 consecutive rows, dimension present in it); no array of `dim`
+ * entries is made.  The caller's arrays are not needed afterwards.  n < 2^31 and row_ptr[n] < 2^32, else PGV_ERR_ARG (the
+ * text names the limit); n == 0 is legal.  Synchronises.  pgv_sparse_rows_free releases everything; NULL is a no-op.  A
+ * mirror belongs to its context and must be freed before it.
+ *
+ * pgv_sparse_rows_topk: pgv_sparse_topk(PGV_NEG_IP)'s contract for nq queries in CSR against the mirror's rows: out_dist
+ * [nq x k] ascending kernel values, out_idx [nq x k] row indexes, ties by lower index, entries beyond n +inf / -1, an
+ * empty intersection +0.0, 1 <= k <= 4096, nq == 0 returns PGV_OK at once, the same chunks of queries
+ * (PGV_SPARSE_MATRIX_FLOATS).  The value is the fp32 sum of q[j] * x[j] over the shared indices j, accumulated with fmaf
+ * in ASCENDING INDEX order (the order in which the reference's merge loop meets the matches, src/sparsevec.c:905-936)
+ * and negated as 0 - ip: it depends on the (query, row) pair alone, no atomics are used, two calls give the same bits, and
+ * on integer-valued data they are pgv_sparse_topk's.  There is no metric argument: L2 and L1 need the terms of the indices
+ * only one side stores, which a walk over the shared postings never sees, and this library computes no "total minus
+ * matched" (the rule above), so they stay with pgv_sparse_topk.  Not served: ext/ glue.  bench.py does not measure these
+ * entries; tools/bench_sparse_inv_topk.py does, beside pgv_sparse_topk.
+ */
+typedef struct pgv_sparse_rows pgv_sparse_rows;
+
+int			pgv_sparse_rows_upload(pgv_ctx * ctx, int dim,
+								   const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+								   pgv_sparse_rows ** out);
+void		pgv_sparse_rows_free(pgv_sparse_rows * rows);
+int			pgv_sparse_rows_topk(pgv_sparse_rows * rows,
+								 const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq,
+								 int k, float *out_dist, int64_t *out_idx);
+
 /* ----------------------------------- IVFFlat over bit strings (bit_hamming_ops) */
 
 /*

@@ -58,7 +58,12 @@ SYMBOLS = [
     "pgv_hnsw_scan_begin_sparse", "pgv_hnsw_scan_filtered",
     "pgv_hnsw_set_live", "pgv_hnsw_live_count", "pgv_hnsw_repair_neighbors", "pgv_hnsw_repair_dead_cap_max",
     "pgv_bit_jaccard_topk",
+    "pgv_sparse_rows_upload", "pgv_sparse_rows_free", "pgv_sparse_rows_topk",
 ]
+
+# inverted sparsevec rows (pgv_sparse_rows_*): rows of a block and queries of a scan workgroup's tile -- kInvRows and
+# kInvQueries of csrc/kernels_sparse_inv.hip, for the tests' edge shapes
+SPARSE_INV_ROWS, SPARSE_INV_QUERIES = 4096, 4
 
 
 class PgvError(RuntimeError):
@@ -201,6 +206,10 @@ def _load():
     lib.pgv_sparse_distance_batch.argtypes = [P, I, I, I, P, P, P, P, P, I64, P]
     lib.pgv_sparse_cosine_distance_batch.argtypes = [P, I, I, P, P, P, P, P, I64, P]
     lib.pgv_sparse_topk.argtypes = [P, I, I, P, P, P, I, P, P, P, I64, I, P, P]
+    lib.pgv_sparse_rows_upload.argtypes = [P, I, P, P, P, I64, C.POINTER(P)]
+    lib.pgv_sparse_rows_free.argtypes = [P]
+    lib.pgv_sparse_rows_free.restype = None
+    lib.pgv_sparse_rows_topk.argtypes = [P, P, P, P, I, I, P, P]
     lib.pgv_hnsw_set_graph.argtypes = [P, I, C.c_int32, P, P, P]
     lib.pgv_hnsw_search.argtypes = [P, P, I, I, I, P, P, P]
     lib.pgv_hnsw_build_search.argtypes = [P, P, P, I, I, I, P, P, P]

@@ -651,6 +651,44 @@ def sparse_topk(ctx, metric, dim, queries, rows, k, out=None):
     return dist, idx
 
 
+class SparseRows:
+    """sparsevec rows kept on the device inverted (pgv_sparse_rows_upload): rows_csr = (ptr [n + 1], idx, val) as
+    sparse_topk takes them; topk is sparse_topk(PGV_NEG_IP) over them, served from the postings of the dimensions each
+    query stores.  Blocks of _lib.SPARSE_INV_ROWS rows, query tiles of _lib.SPARSE_INV_QUERIES"""
+
+    def __init__(self, ctx, dim, rows_csr):
+        self.ctx, self.dim = ctx, int(dim)
+        r_ptr, r_idx, r_val = _csr(rows_csr)
+        self.n = int(r_ptr.shape[0]) - 1
+        h = C.c_void_p()
+        check(lib.pgv_sparse_rows_upload(ctx.h, self.dim, ptr(r_ptr), ptr(r_idx), ptr(r_val), self.n, C.byref(h)))
+        self.h = h
+        ctx._adopt(self)
+
+    def topk(self, queries_csr, k, out=None):
+        """pgv_sparse_rows_topk: CSR queries -> (dist [nq x k] float32 ascending negative inner products, idx [nq x k] int64),
+        ties to the lower row, +inf / -1 beyond n, living where the queries' values live"""
+        q_ptr, q_idx, q_val = _csr(queries_csr)
+        nq = int(q_ptr.shape[0]) - 1
+        dist, idx = out if out is not None else (_empty_like_kind(q_val, (nq, k), np.float32),
+                                                _empty_like_kind(q_val, (nq, k), np.int64))
+        check(lib.pgv_sparse_rows_topk(self.h, ptr(q_ptr), ptr(q_idx), ptr(q_val), nq, int(k), ptr(dist), ptr(idx)))
+        return dist, idx
+
+    def free(self):
+        if self.h:
+            lib.pgv_sparse_rows_free(self.h)
+            self.h = None
+
+    close = free  # what a Context calls on the handles it adopted
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def binary_quantize(ctx, dtype, dim, rows):
     """pgv_binary_quantize: rows [n x dim] -> packed bits [n x (dim + 7) // 8] uint8, bit i = rows[:, i] > 0, first element
     in the top bit of byte 0 (np.packbits' order)"""

@@ -1,5 +1,6 @@
 // pgv_abi_sparse.hip -- extern "C" entry points of libpgv_hip (include/pgv_hip.h): the sparsevec distances and the exact
 // top-k over CSR vectors.  The kernels are kernels_sparse.hip's; the selection is launch_topk_segments, as in pgv_bit_topk.
+// pgv_sparse_rows_*: the same top-k by inner product over rows kept inverted on the device (kernels_sparse_inv.hip).
 #include "pgv_abi_common.h"
 
 namespace {
@@ -170,6 +171,13 @@ int sparse_one_query(pgv_ctx *ctx, const char *who, int mode, int dim, int q_nnz
 
 }  // namespace
 
+// sparsevec rows inverted on the device (pgv_sparse_rows_upload): the mirror is kernels_sparse_inv.hip's
+struct pgv_sparse_rows {
+    pgv_ctx *ctx = nullptr;
+    int dim = 0;
+    SparseInv inv;
+};
+
 extern "C" {
 
 int pgv_sparse_distance_batch(pgv_ctx *ctx, pgv_metric metric, int dim, int q_nnz, const int32_t *q_idx, const float *q_val,
@@ -231,6 +239,81 @@ int pgv_sparse_topk(pgv_ctx *ctx, pgv_metric metric, int dim, const int64_t *q_p
         if (n > 0) PGV_TRY(launch_run(ctx, (int)metric, tiles_dev, runs[ri++], q, r, mat, n));
         PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, od.as<float>() + (size_t)q0 * k,
                                      oi.as<int64_t>() + (size_t)q0 * k));
+    }
+    bool need = false;
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(oi.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
+int pgv_sparse_rows_upload(pgv_ctx *ctx, int dim, const int64_t *row_ptr, const int32_t *row_idx, const float *row_val, int64_t n,
+                           pgv_sparse_rows **out) {
+    const char *who = "pgv_sparse_rows_upload";
+    if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_upload: ctx/out is NULL");
+    *out = nullptr;
+    PGV_TRY(check_sparse_dim(who, dim));
+    if (n < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_upload: n < 0");
+    if (n >= (int64_t)1 << 31) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_upload: %lld rows, not fewer than 2^31", (long long)n);
+    if (!row_ptr) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_upload: row_ptr is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    // (the host's copy of a device row_ptr is checked like a host one: the build's key kernel walks the rows by it)
+    StagedCsr r;
+    PGV_TRY(stage_csr(ctx, who, "rows", dim, row_ptr, row_idx, row_val, n, true, ctx->plan_b, ctx->rows_stage, ctx->idx_stage, &r));
+    const int64_t total = r.host_ptr[n];
+    if (total >= (int64_t)1 << 32)
+        PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_upload: %lld stored elements, not fewer than 2^32", (long long)total);
+    pgv_sparse_rows *rows = new (std::nothrow) pgv_sparse_rows;
+    if (!rows) PGV_FAIL(PGV_ERR_NOMEM, "pgv_sparse_rows_upload: out of host memory");
+    rows->ctx = ctx;
+    rows->dim = dim;
+    const int rc = sparse_inv_build(ctx, dim, r.dev, total, &rows->inv);
+    if (rc != PGV_OK) {
+        delete rows;
+        return rc;
+    }
+    *out = rows;
+    return PGV_OK;
+}
+
+void pgv_sparse_rows_free(pgv_sparse_rows *rows) {
+    if (!rows) return;
+    (void)hipSetDevice(rows->ctx->device);
+    sparse_inv_release(&rows->inv);
+    delete rows;
+}
+
+// pgv_sparse_topk(PGV_NEG_IP) over an uploaded mirror: the same chunks, the same selection; sparse_inv_scan_kernel fills
+// the chunk's matrix from the postings of the dimensions each query stores
+int pgv_sparse_rows_topk(pgv_sparse_rows *rows, const int64_t *q_ptr, const int32_t *q_idx, const float *q_val, int nq, int k,
+                         float *out_dist, int64_t *out_idx) {
+    const char *who = "pgv_sparse_rows_topk";
+    if (!rows || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_topk: rows/out_dist/out_idx is NULL");
+    if (nq < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_topk: nq < 0");
+    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_topk: k %d outside 1..4096", k);
+    if (nq == 0) return PGV_OK;
+    if (!q_ptr) PGV_FAIL(PGV_ERR_ARG, "pgv_sparse_rows_topk: q_ptr is NULL");
+    pgv_ctx *ctx = rows->ctx;
+    const int64_t n = rows->inv.n;
+    PGV_HIP(hipSetDevice(ctx->device));
+    StagedCsr q;
+    PGV_TRY(stage_csr(ctx, who, "queries", rows->dim, q_ptr, q_idx, q_val, nq, true, ctx->plan_c, ctx->q_stage, ctx->centers_stage, &q));
+    OutArg od, oi;
+    PGV_TRY(od.init(out_dist, sizeof(float) * (size_t)nq * k, ctx->out_stage));
+    PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
+    // query tiles are consecutive queries, sparse_inv_queries() a tile, counted from the chunk's first: the kernel derives
+    // them from its workgroup index, so nothing is planned here
+    const int chunk = n > 0 ? (int)std::min<int64_t>(nq, std::max<int64_t>(1, sparse_matrix_floats() / n)) : nq;
+    for (int q0 = 0; q0 < nq; q0 += chunk) {
+        const int cn = std::min(chunk, nq - q0);
+        PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * std::max<size_t>((size_t)cn * (size_t)n, 4)));
+        float *mat = ctx->dist_mat.as<float>();
+        if (n > 0) {
+            ScanTimer timer{ctx};
+            PGV_TRY(timer.begin((double)n * cn, (double)rows->inv.total, true));
+            PGV_TRY(launch_sparse_inv_scan(ctx, rows->inv, q.dev, q0, cn, mat));
+            PGV_TRY(timer.end());
+        }
+        PGV_TRY(launch_topk_segments(ctx, mat, nullptr, cn, n, k, od.as<float>() + (size_t)q0 * k, oi.as<int64_t>() + (size_t)q0 * k));
     }
     bool need = false;
     PGV_TRY(od.finish(ctx, &need));

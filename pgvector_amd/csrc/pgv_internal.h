@@ -669,6 +669,29 @@ int launch_sparse_groups(pgv_ctx *ctx, const RowsView &v, const int32_t *ids, co
 // (a[i], b[i]) -> (min, max) in place: slot pairs as the rule above takes them (PGV_HNSW_PAIRS_GATHER=1 over sparse rows)
 int launch_sparse_orient_pairs(pgv_ctx *ctx, int32_t *a, int32_t *b, int64_t npairs);
 
+// kernels_sparse_inv.hip: sparsevec rows inverted on the device (pgv_sparse_rows_upload).  The rows are cut
+// into blocks of sparse_inv_rows() consecutive rows; a block's stored elements lie sorted by (dimension, row) as 8-byte
+// postings, the postings of one dimension inside one block being a run; the directory lists the runs in that order
+struct SparseInvPosting {
+    uint32_t row;  // the row's index inside its block
+    float val;
+};
+struct SparseInv {
+    int64_t n = 0, total = 0;             // rows; stored elements (< 2^32)
+    uint32_t nblocks = 0, ndir = 0;       // row blocks; runs
+    SparseInvPosting *post = nullptr;     // [total + 1] (one slack posting: a load clamped to a run's start stays inside)
+    int32_t *dir_dim = nullptr;           // [ndir + 1] a run's dimension, ascending inside a block
+    uint32_t *dir_start = nullptr;        // [ndir + 1] where the run starts in post; [ndir] = total
+    uint32_t *blk_dir = nullptr;          // [nblocks + 1] block b's runs are [blk_dir[b], blk_dir[b + 1])
+};
+int sparse_inv_rows();     // rows of a block
+int sparse_inv_queries();  // queries of a scan workgroup's tile, a wavefront each
+// rows: the staged CSR (device) with total = ptr[n] stored elements.  Synchronises; the build's scratch is freed before it returns
+int sparse_inv_build(pgv_ctx *ctx, int dim, const SparseCsr &rows, int64_t total, SparseInv *out);
+void sparse_inv_release(SparseInv *inv);
+// mat[(q - q0) * inv.n + row] = 0 - <query q, row> for queries [q0, q0 + nq) of the staged query CSR
+int launch_sparse_inv_scan(pgv_ctx *ctx, const SparseInv &inv, const SparseCsr &q, int q0, int nq, float *mat);
+
 // kernels_hnsw.hip: the whole first batch of an HNSW scan, one workgroup per query
 int hnsw_search_grid(pgv_ctx *ctx, int nq, int64_t n, int *words_out);
 struct HnswSearchArgs {
