@@ -606,6 +606,31 @@ int			pgv_cosine_distance_batch(pgv_ctx * ctx, pgv_dtype dtype, int dim,
 									  const void *query, const void *rows, int64_t n, double *out);
 
 /*
+ * `ORDER BY embedding <=> $1 LIMIT k` without an index, for a BATCH of queries against the rows AS THE TABLE STORES THEM
+ * (cosine_distance src/vector.c:649-697, src/halfvec.c:652-700, feeding the executor's top-N sort): no normalised copy
+ * of the table, and the operator's own value instead of a dot product of two rounded unit vectors.  Arguments as
+ * pgv_exact_topk takes them: queries [nq x dim] and rows [n x dim], fp32 or fp16, host or device memory.  out_dist
+ * [nq x k] float8 cosine distances ascending, out_idx [nq x k] row indexes; equal float8 values go to the lower index;
+ * NaN (a zero query, a zero row, an overflowed norm product) sorts after every number, NaNs tie with each other by
+ * index and come before the padding; entries beyond n are +inf / -1.  1 <= k <= 4096, n <= 2^32; nq == 0 returns PGV_OK
+ * at once, n == 0 gives all padding.
+ *   Value: d = 1 - clamp((double) ip / sqrt((double) na * (double) nb), -1, 1) with ip, na, nb fp32 sums of exactly the
+ * reference's terms: the reference's arithmetic in another summation order (pgv_exact_topk's rule for PGV_NEG_IP).  It
+ * depends on the (query, row) pair and dim only: ONE scan kernel serves every nq and n (a short tile is padded), so
+ * neither the batch size nor the chunking nor a row's position changes a bit, and data whose three sums are exact in
+ * fp32 (small integers) gives the reference's float8 bit for bit.
+ *   Order: that of the float8, never of a rounded float: two rows whose float8 values differ are neither swapped nor
+ * tied.  (The float selection kernels rank a truncated image of d; where the k-th value's image class reaches past the
+ * selection it is re-ranked by the remaining mantissa bits.)
+ *   The queries are served in chunks of min(nq, max(1, 2^29 / n)) (whole multiples of 128 from 128 on): up to
+ * n = 2^29 the chunk's two float matrices stay within pgv_exact_topk's 4 GiB of scratch; beyond that a chunk is one
+ * query and the two take 8 n bytes (32 GiB at n = 2^32), and a device that cannot hold them gives PGV_ERR_NOMEM.  Not served: pgv_rerank under cosine, sparsevec
+ * (pgv_sparse_cosine_distance_batch), and the extension under ext/, which does not call this entry.
+ */
+int			pgv_cosine_topk(pgv_ctx * ctx, pgv_dtype dtype, int dim, const void *queries, int nq,
+							const void *rows, int64_t n, int k, double *out_dist, int64_t *out_idx);
+
+/*
  * hamming_distance / jaccard_distance (`<~>`, `<%>`; src/bitvec.c:45-70 over src/bitutils.c:49-131)
  * of one bit string against n bit strings of the same length: VARBITS payloads, (nbits + 7) / 8
  * bytes each, first bit = most significant bit of byte 0, rows contiguous.  out [n] float8 (exact).

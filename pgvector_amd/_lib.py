@@ -59,6 +59,7 @@ SYMBOLS = [
     "pgv_hnsw_set_live", "pgv_hnsw_live_count", "pgv_hnsw_repair_neighbors", "pgv_hnsw_repair_dead_cap_max",
     "pgv_bit_jaccard_topk",
     "pgv_sparse_rows_upload", "pgv_sparse_rows_free", "pgv_sparse_rows_topk",
+    "pgv_cosine_topk",
 ]
 
 # inverted sparsevec rows (pgv_sparse_rows_*): rows of a block and queries of a scan workgroup's tile -- kInvRows and
@@ -193,6 +194,7 @@ def _load():
     lib.pgv_hnsw_free.restype = None
     lib.pgv_hnsw_score.argtypes = [P, P, I, P, P, I64, P]
     lib.pgv_cosine_distance_batch.argtypes = [P, I, I, P, P, I64, P]
+    lib.pgv_cosine_topk.argtypes = [P, I, I, P, I, P, I64, I, P, P]
     lib.pgv_bit_distance_batch.argtypes = [P, I, I, P, P, I64, P]
     lib.pgv_bit_topk.argtypes = [P, I, P, I, P, I64, I, P, P]
     lib.pgv_bit_jaccard_topk.argtypes = [P, I, P, I, P, I64, I, P, P]

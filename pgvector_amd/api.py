@@ -555,6 +555,24 @@ def cosine_distance_batch(ctx, dtype, dim, query, rows):
     return out
 
 
+def cosine_topk(ctx, queries, rows, k, out=None):
+    """pgv_cosine_topk: `ORDER BY v <=> $1 LIMIT k` for a batch of queries against the rows as stored (no normalised
+    copy) -> (dist [nq x k] float64: the operator's float8, idx [nq x k] int64), ordered by the float8, ties to the lower
+    row, NaN behind the numbers.  float16 rows are halfvec rows, everything else is served as float32; host arrays are
+    converted to that element type, tensors must both have it already (a mismatch is a TypeError, not a copy of a table)"""
+    dtype = PGV_F16 if "float16" in str(rows.dtype) else PGV_F32
+    want = np.dtype(_NP_OF[dtype]).name
+    for name, x in (("queries", queries), ("rows", rows)):
+        if _is_torch(x) and str(x.dtype) != "torch." + want:
+            raise TypeError("cosine_topk: %s are %s, the call reads %s" % (name, x.dtype, want))
+    queries, rows = as_dtype(queries, dtype), as_dtype(rows, dtype)
+    nq, n, dim = int(queries.shape[0]), int(rows.shape[0]), int(queries.shape[1])
+    dist, idx = out if out is not None else (_empty_like_kind(queries, (nq, k), np.float64),
+                                            _empty_like_kind(queries, (nq, k), np.int64))
+    check(lib.pgv_cosine_topk(ctx.h, dtype, dim, ptr(queries), nq, ptr(rows) if n else None, n, int(k), ptr(dist), ptr(idx)))
+    return dist, idx
+
+
 PGV_BIT_HAMMING, PGV_BIT_JACCARD = 0, 1
 
 

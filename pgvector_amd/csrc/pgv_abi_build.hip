@@ -234,6 +234,100 @@ int pgv_cosine_distance_batch(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void
     return sync_if(ctx, need);
 }
 
+// the floats of a query chunk's two matrices (IP and KEY) at most, each: 2^29, or PGV_COSINE_MATRIX_FLOATS (tests reach
+// the chunk split with small shapes through it; read at every call)
+static int64_t cosine_matrix_floats() {
+    const char *e = getenv("PGV_COSINE_MATRIX_FLOATS");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (int64_t)v : (int64_t)1 << 29;
+}
+
+// `ORDER BY embedding <=> $1 LIMIT k` without an index for a batch of queries, rows as the table stores them: per chunk
+// of queries cosine_tile_kernel (kernels_cosine.hip) fills two matrices, IP (the inner products) and KEY (the float8
+// distance truncated to a float: ordered like it, coarser), and the squared norms; launch_topk_segments selects k + 1
+// by KEY; a query whose boundary key class ends inside that selection is settled, the others have their row of KEY
+// rewritten to separate the class by the low bits of the float8 and are selected again; cosine_finish_kernel recomputes
+// the float8 of the selected pairs and sorts them by (float8, index).
+int pgv_cosine_topk(pgv_ctx *ctx, pgv_dtype dtype, int dim, const void *queries, int nq, const void *rows, int64_t n,
+                    int k, double *out_dist, int64_t *out_idx) {
+    if (!ctx || !out_dist || !out_idx) PGV_FAIL(PGV_ERR_ARG, "pgv_cosine_topk: ctx/out_dist/out_idx is NULL");
+    PGV_TRY(check_common(dtype, dim));
+    if (nq < 0 || n < 0) PGV_FAIL(PGV_ERR_ARG, "pgv_cosine_topk: nq/n < 0");
+    if (k < 1 || k > 4096) PGV_FAIL(PGV_ERR_ARG, "pgv_cosine_topk: k %d outside 1..4096", k);
+    if (n > 0xffffffffll) PGV_FAIL(PGV_ERR_ARG, "pgv_cosine_topk: more than 2^32 rows");
+    if (nq == 0) return PGV_OK;
+    if (!queries || (n > 0 && !rows)) PGV_FAIL(PGV_ERR_ARG, "pgv_cosine_topk: queries/rows is NULL");
+    PGV_HIP(hipSetDevice(ctx->device));
+    const RowGeom g = row_geom(dim, dtype);
+    const void *q_dev, *r_dev = nullptr;
+    PGV_TRY(stage_rows(ctx, queries, nq, dim, dtype, g, ctx->q_stage, &q_dev));
+    if (n > 0) PGV_TRY(stage_rows(ctx, rows, n, dim, dtype, g, ctx->rows_stage, &r_dev));
+    const size_t row_bytes = (size_t)g.ld * elem_size(dtype);
+    OutArg od, oi;
+    PGV_TRY(od.init(out_dist, sizeof(double) * (size_t)nq * k, ctx->out_stage));
+    PGV_TRY(oi.init(out_idx, sizeof(int64_t) * (size_t)nq * k, ctx->out_stage2));
+    bool need = false;
+    if (n == 0) {  // all padding
+        PGV_TRY(launch_cosine_finish(ctx, nullptr, nullptr, nullptr, nullptr, 0, 0, nq, 0, k, od.as<double>(), oi.as<int64_t>()));
+        PGV_TRY(od.finish(ctx, &need));
+        PGV_TRY(oi.finish(ctx, &need));
+        return sync_if(ctx, need);
+    }
+
+    // whole 128-query tiles of the scan kernel from 128 on; IP and KEY together stay within pgv_exact_topk's 4 GiB up
+    // to n = 2^29 (beyond: one query a chunk, 8 n bytes)
+    int chunk = (int)std::min<int64_t>(nq, std::max<int64_t>(1, cosine_matrix_floats() / n));
+    if (chunk >= 128) chunk = chunk / 128 * 128;
+    const int kk = (int)std::min<int64_t>(std::min(k + 1, 4096), n);
+    // scratch of a chunk: na [chunk] | nb [n] | kb [chunk] | sel_val [chunk x kk] | unsettled [chunk] | count, then the
+    // positions sel_pos [chunk x kk] | sel2_pos [chunk x k]
+    const size_t words = (size_t)chunk * (3 + (size_t)kk) + (size_t)n + 1;
+    const size_t pos_at = (words * 4 + 15) / 16 * 16;
+    PGV_TRY(ctx->ms_a.ensure(pos_at + sizeof(int64_t) * (size_t)chunk * ((size_t)kk + k)));
+    float *na = ctx->ms_a.as<float>(), *nb = na + chunk, *kb = nb + n, *sel_val = kb + chunk;
+    int *unsettled = reinterpret_cast<int *>(sel_val + (size_t)chunk * kk), *count = unsettled + chunk;
+    int64_t *sel_pos = reinterpret_cast<int64_t *>(ctx->ms_a.as<char>() + pos_at), *sel2_pos = sel_pos + (size_t)chunk * kk;
+    for (int q0 = 0; q0 < nq; q0 += chunk) {
+        const int cn = std::min(chunk, nq - q0);
+        const size_t mat_floats = ((size_t)cn * (size_t)n + 3) / 4 * 4;
+        PGV_TRY(ctx->dist_mat.ensure(sizeof(float) * (2 * mat_floats + 4)));
+        float *key = ctx->dist_mat.as<float>(), *ip = key + mat_floats;
+        const char *qp = static_cast<const char *>(q_dev) + (size_t)q0 * row_bytes;
+        {
+            ScanTimer timer{ctx};
+            PGV_TRY(timer.begin((double)n * cn, (double)n * ((cn + 127) / 128), true));
+            PGV_TRY(launch_cosine_tiles(ctx, dtype, g, r_dev, n, qp, cn, ip, key, na, nb));
+            PGV_TRY(timer.end());
+        }
+        PGV_TRY(launch_topk_segments(ctx, key, nullptr, cn, n, kk, sel_val, sel_pos));
+        // kk == n: the selection holds every row, in the order of the KEYS -- with n == k + 1 the row that has to go may
+        // sit anywhere in the last key class, so the finish ranks all n by the float8 and emits the first k
+        const int64_t *pos = sel_pos;
+        int pos_stride = kk, take = kk == n ? kk : k;
+        if (kk < n) {
+            PGV_TRY(launch_cosine_settle(ctx, sel_val, cn, kk, k, n, kb, unsettled, count));
+            // one word a chunk: nothing to refine is the common case (h_c is rewritten by the next chunk only after
+            // this synchronisation)
+            PGV_TRY(ctx->h_c.ensure(sizeof(int)));
+            PGV_HIP(hipMemcpyAsync(ctx->h_c.p, count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            PGV_HIP(hipStreamSynchronize(ctx->stream));
+            if (*ctx->h_c.as<int>() > 0) {
+                PGV_TRY(launch_cosine_refine(ctx, key, ip, na, nb, kb, unsettled, cn, n));
+                // a settled query's row is as it was, and its k smallest keys are its exact set either way.  sel_val
+                // is done with: the second selection's values (images) go over it
+                PGV_TRY(launch_topk_segments(ctx, key, nullptr, cn, n, k, sel_val, sel2_pos));
+                pos = sel2_pos;
+                pos_stride = k;
+            }
+        }
+        PGV_TRY(launch_cosine_finish(ctx, ip, na, nb, pos, pos_stride, take, cn, n, k, od.as<double>() + (size_t)q0 * k,
+                                     oi.as<int64_t>() + (size_t)q0 * k));
+    }
+    PGV_TRY(od.finish(ctx, &need));
+    PGV_TRY(oi.finish(ctx, &need));
+    return sync_if(ctx, need);
+}
+
 int pgv_bit_distance_batch(pgv_ctx *ctx, pgv_bit_metric metric, int nbits, const void *query, const void *rows,
                            int64_t n, double *out) {
     if (!ctx || !out) PGV_FAIL(PGV_ERR_ARG, "pgv_bit_distance_batch: ctx/out is NULL");

@@ -818,6 +818,23 @@ int mfma_scan_queries_per_task();
 int launch_mfma_dense(pgv_ctx *ctx, pgv_metric metric, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n,
                       const void *queries, int nq, const float *row_norms, float *out, int64_t out_stride);
 int dense_chain_length(const RowGeom &g, pgv_dtype dtype);  // products per accumulator chain, at most
+// kernels_cosine.hip: pgv_cosine_topk.  launch_cosine_tiles: every query x every row in 128 x 128 tiles under
+// cosine_distance -- ip / key[q * n + row] (the fp32 inner product | the float8 distance truncated to a float, an order
+// image for the float selection) and the squared norms na [nq], nb [n], summed in the scan's own registers
+int launch_cosine_tiles(pgv_ctx *ctx, pgv_dtype dtype, const RowGeom &g, const void *rows, int64_t n, const void *queries,
+                        int nq, float *ip, float *key, float *na, float *nb);
+// sel_val [nq x kk]: launch_topk_segments over key with kk = min(k + 1, 4096) < n -> unsettled[q] = the boundary's key
+// class may go on behind the selection, kb[q] = that key, *count = how many such queries
+int launch_cosine_settle(pgv_ctx *ctx, const float *sel_val, int nq, int kk, int k, int64_t n, float *kb, int *unsettled,
+                         int *count);
+// ... whose rows of key are rewritten in place so that the k smallest are the exact set by (float8, index)
+int launch_cosine_refine(pgv_ctx *ctx, float *key, const float *ip, const float *na, const float *nb, const float *kb,
+                         const int *unsettled, int nq, int64_t n);
+// pos [nq x pos_stride]: the first `take` (<= 4096) of a row are ranked by (float8, index) -- the exact set of k, or all
+// n rows when the selection holds every one -- and the first k of them go to out_dist (float8) / out_idx [nq x k],
+// NaN behind the numbers, +inf / -1 behind those
+int launch_cosine_finish(pgv_ctx *ctx, const float *ip, const float *na, const float *nb, const int64_t *pos,
+                         int pos_stride, int take, int nq, int64_t n, int k, double *out_dist, int64_t *out_idx);
 int launch_row_norms(pgv_ctx *ctx, const RowsView &v, float *out, unsigned *max_bits);
 int launch_mfma_scan(pgv_ctx *ctx, const RowsView &v, const void *queries, const ScanWork &w, const float *row_norms,
                      const float *query_norms, float *out, bool stream_rows, int queries_per_task = 32,
